@@ -2,7 +2,7 @@
 """bench.py -- headline benchmark of BASELINE.json: M disparity-hypotheses/s (W x H x D) of
 the TwoView cost-volume / support-weight / WTA path on synthetic 1920x1080x256 pairs.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|small|c5|c4|c1]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|small|c5|c4|c1] [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one stereo pair per GPU: WTA left->right,
 WTA right->left, cross-check, and the device-side hand-over of the two depth maps
@@ -16,6 +16,14 @@ other than the final gather.
 --workload c4 is the MultiViewStereo configuration (8 views 1280x960, 128 levels, r=2): a step is
 runTask over all 8 views -- initial estimates, the all-gather of the depth maps (N>1: views are
 sharded over the ranks, strong scaling), the ordered cross-check chain.
+
+A plain run sets up, warms up, times the steps and prints the headline line (metric, value, unit,
+higher_is_better, dtype, ms_per_step).  --full adds everything else this script measures or checks:
+first calls on fresh contexts, the check against the reference's arithmetic, per-kernel times and the
+roofline, the CPU baseline with its parity band, the communicator record and, for the default C3 run,
+the short legs of the other configurations and the flat-area sweep.  --dump-outputs DIR writes the
+depth maps of the last timed step, every file finite: NaN / inf entries are written as 0.0, and what
+stood there as <name>_nonfinite.npy (the inputs are seeded: the same in every run with the same arguments).
 """
 import argparse
 import json
@@ -66,6 +74,37 @@ WORKLOADS = {
             "MultiViewStereo r=2, 3 neighbours, distorted cameras from the project's projection matrices"),
 }
 C4_VIEWS = 8
+
+
+DUMP_BYTES_MAX = 64 * 10**6    # --dump-outputs: all files together
+DUMP_SAMPLE_SEED = 0x5EED0D0
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every file finite.  A depth map holds NaN (no depth: masked out, no candidate) and +inf (rejected by
+    the ratio test) where the library returns them, so each map is written as dirname/<name>.npy in float64 with those
+    entries set to 0.0 (a depth is positive) and dirname/<name>_nonfinite.npy in float32 saying what stood there (0 a
+    depth, 1 NaN, 2 +inf, 3 -inf): together the map bit for bit.  Where all files would exceed DUMP_BYTES_MAX, every one
+    is replaced by the same fraction of its elements (flattened) at indices drawn with DUMP_SAMPLE_SEED, ascending: the
+    same sample in every run with the same arguments, so that two builds can be compared output for output."""
+    os.makedirs(dirname, exist_ok=True)
+    encoded = {}
+    for name, v in arrays.items():
+        a = np.ascontiguousarray(v, dtype=np.float64)
+        kind = np.zeros(a.shape, dtype=np.float32)
+        kind[np.isnan(a)] = 1
+        kind[a == np.inf] = 2
+        kind[a == -np.inf] = 3
+        encoded[name] = np.where(kind == 0, a, 0.0)
+        encoded[name + "_nonfinite"] = kind
+    arrays = encoded
+    total = sum(a.nbytes for a in arrays.values())
+    frac = min(1.0, (DUMP_BYTES_MAX - 1024 * len(arrays)) / max(1, total))      # (room for the .npy headers)
+    for name, a in arrays.items():
+        if frac < 1.0:
+            flat = a.reshape(-1)
+            a = flat[np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(flat.size, int(flat.size * frac), replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 NO_FMA_CEILING_TLANE = 256 * 4 * 16 * 2.4e9 / 1e12   # separate v_mul_f64 / v_add_f64: 16 lanes per SIMD per clock = 39.3 T lane-op/s
@@ -191,6 +230,31 @@ def run_c4(args, rank, world, dev, dev_index, backend):
         multiview_sharded(eng, C4_VIEWS)
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:                         # (every rank holds the final maps of all views)
+        dump_outputs(args.dump_outputs, {"depth_view%d" % v: ctx.download_depth(v) for v in range(C4_VIEWS)})
+    hyp_per_step = W * H * D * links                            # nominal: every pixel x level x neighbour
+    head = {"metric": "Mdisparity-hypotheses/s (WxHxD)", "unit": "Mhyp/s", "build_id": capi.build_id(), "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+            "dtype": "f64", "data": "synthetic" if wl == "c4" else "fixture (the example project's eight bunny views, Qt-scaled)"}
+    config = {"workload": desc + "; initial estimates + depth-map all-gather + ordered cross-check",
+              "width": W, "height": H, "depth_levels": D, "views": C4_VIEWS, "view_neighbour_links": links,
+              "window_radius": int(p.window_radius), "weights": "geodesic",
+              "parallelism": ("views sharded, %s all-gather" % ("RCCL" if backend == "nccl" else backend))
+              if world > 1 else "single GPU",
+              "arithmetic": ("certified (default): fused sweeps in the staged cost kernel, every unit's winner certified against "
+                             "a proven error bound, its score recomputed and ambiguous units redone in the reference's arithmetic "
+                             "-- same bits as 'exact' (DESIGN.md 2b)" if args.arith == "certified"
+                             else "exact: the reference's operation order, no contraction, everywhere")}
+    if not args.full:
+        if world > 1:
+            tmax = torch.tensor([dt], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
+            dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+            dt = float(tmax.item())
+        ctx.close()
+        if rank != 0:
+            return None
+        return dict(head, value=round(hyp_per_step * args.steps / dt / 1e6, 3), ms_per_step=round(dt / args.steps * 1e3, 3),
+                    config=config)
     # per-kernel durations (roofline): the library keeps two views' estimates in flight on two streams, so the HIP events
     # around a kernel also time its neighbour's share of the GPU; an extra, untimed pass with one view at a time gives
     # each kernel's own duration
@@ -223,7 +287,6 @@ def run_c4(args, rank, world, dev, dev_index, backend):
         waves[1] += st["mvs_waves_listed"]
     result = None
     if rank == 0:
-        hyp_per_step = W * H * D * links                        # nominal: every pixel x level x neighbour
         T = (2 * p.window_radius + 1) ** 2
         name, (ms, launches) = max(prof.items(), key=lambda kv: kv[1][0])
         my_links = sum(len(neigh[v]) for v in my_views)
@@ -232,26 +295,16 @@ def run_c4(args, rank, world, dev, dev_index, backend):
         alg_bytes = 14.0 * W * H * my_links * prof_steps
         hbm = alg_bytes / (ms * 1e-3) / 1e9
         executed = pmc_executed(wl, name, ms / launches) if not os.environ.get("SRH_BENCH_C4_SMALL") else None
-        result = {
-            "metric": "Mdisparity-hypotheses/s (WxHxD)", "value": round(hyp_per_step * args.steps / dt / 1e6, 3),
-            "unit": "Mhyp/s", "build_id": capi.build_id(), "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 3), "first_call_ms": first_call_ms, "first_call_samples_ms": first_call_samples, "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None, "dtype": "f64",
-            "data": "synthetic" if wl == "c4" else "fixture (the example project's eight bunny views, Qt-scaled)",
-            "config": {"workload": desc + "; initial estimates + depth-map all-gather + ordered cross-check",
-                       "width": W, "height": H, "depth_levels": D, "views": C4_VIEWS, "view_neighbour_links": links,
-                       "window_radius": int(p.window_radius), "weights": "geodesic",
-                       "parallelism": ("views sharded, %s all-gather" % ("RCCL" if backend == "nccl" else backend))
-                       if world > 1 else "single GPU",
-                       "arithmetic": ("certified (default): fused sweeps in the staged cost kernel, every unit's winner certified against "
-                                      "a proven error bound, its score recomputed and ambiguous units redone in the reference's arithmetic "
-                                      "-- same bits as 'exact' (DESIGN.md 2b)" if args.arith == "certified"
-                                      else "exact: the reference's operation order, no contraction, everywhere"),
-                       "masked_in_fraction": round(float(np.mean([m.mean() for m in masks])), 4),
-                       # which cost kernel did the work: 64-pixel waves (per neighbour link) evaluated from LDS copies of the
-                       # other view (mvs_staged_cost_kernel) / by gathers (mvs_list_cost_kernel)
-                       "cost_waves_staged": int(waves[0]), "cost_waves_gathering": int(waves[1]),
-                       "n_eval_reference_rank0_per_step": int(n_eval)},
+        result = dict(
+            head, value=round(hyp_per_step * args.steps / dt / 1e6, 3),
+            ms_per_step=round(dt / args.steps * 1e3, 3), first_call_ms=first_call_ms, first_call_samples_ms=first_call_samples,
+            config=dict(config,
+                        masked_in_fraction=round(float(np.mean([m.mean() for m in masks])), 4),
+                        # which cost kernel did the work: 64-pixel waves (per neighbour link) evaluated from LDS copies of the
+                        # other view (mvs_staged_cost_kernel) / by gathers (mvs_list_cost_kernel)
+                        cost_waves_staged=int(waves[0]), cost_waves_gathering=int(waves[1]),
+                        n_eval_reference_rank0_per_step=int(n_eval)))
+        result.update({
             "roofline": {"bound": "valu_fp64", "kernel": name,
                          "achieved": (executed or {}).get("tflops", round(valu, 3)), "peak": FP64_VALU_PEAK_TFLOPS,
                          "unit": "TFLOP/s", "frac": (executed or {}).get("frac_of_fp64_peak", round(valu / FP64_VALU_PEAK_TFLOPS, 5)),
@@ -268,7 +321,7 @@ def run_c4(args, rank, world, dev, dev_index, backend):
                                  "traffic_over_algorithmic": None}},
             "kernels_ms": {k: [round(v[0], 3), v[1]] for k, v in sorted(prof.items())},
             "cpu_baseline": None,
-        }
+        })
         if world == 1:
             # the nominal W*H*D*links counts every pixel, level and link; the reference evaluates a cost per CANDIDATE of a
             # masked-in pixel's curve: that is the work there is, and the rate to quote
@@ -400,7 +453,7 @@ def run_twoview(args, workload, rank, world, dev, dev_index, backend):
         return sorted(v)[len(v) // 2], v
 
     # the process's very first call (C3 in the default run: kernels' code objects not yet resident either)
-    first_call_cold = first_call() if not rows_shard and not args.no_first_call else None
+    first_call_cold = first_call() if args.full and not rows_shard and not args.no_first_call else None
 
     ctx = capi.Context(dev_index)
     ctx.set_stream(torch.cuda.current_stream().cuda_stream)
@@ -410,7 +463,7 @@ def run_twoview(args, workload, rank, world, dev, dev_index, backend):
     ctx.upload_view(0, L, ml, cl)
     ctx.upload_view(1, R, mr, cr)
     mismatch = None
-    if args.arith != "exact" and workload not in ("c1", "c5") and not args.no_exact_check:
+    if args.full and args.arith != "exact" and workload not in ("c1", "c5") and not args.no_exact_check:
         # untimed: the same pass in the reference's arithmetic, to count the depths the chosen arithmetic changes
         # (certified: must be 0 -- it is the parity mode; fma / f32: the measured winner-mismatch rate)
         ctx.set_option("arith", capi.ARITH_EXACT)
@@ -470,18 +523,55 @@ def run_twoview(args, workload, rank, world, dev, dev_index, backend):
     for _ in range(args.warmup):
         step()
     fence()
-    ctx.profile_reset()
-    ctx.profile_enable(True)
+    if args.full:
+        ctx.profile_reset()
+        ctx.profile_enable(True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     fence()
     dt = time.perf_counter() - t0
     ctx.profile_enable(False)
+    if args.dump_outputs and rank == 0:
+        if rows_shard:                                  # the stitched, cross-checked maps live in rank 0's context
+            maps = {"depth_left": ctx.download_depth(0), "depth_right": ctx.download_depth(1)}
+        elif world > 1:                                 # what the last step's gather brought to rank 0: every rank's pair
+            got = recv[(state["n"] - 1) % NBUF]
+            maps = {"depth_%s_rank%d" % (side, r): got[r][k].cpu().numpy() for r in range(world)
+                    for k, side in enumerate(("left", "right"))}
+        else:
+            last = outs[(state["n"] - 1) % NBUF].cpu().numpy()
+            maps = {"depth_left": last[0], "depth_right": last[1]}
+        dump_outputs(args.dump_outputs, maps)
     if world > 1:
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    hyp_per_step_per_gpu = 2 * W * H * D
+    value = (1 if rows_shard else world) * hyp_per_step_per_gpu * args.steps / dt / 1e6
+    head = {"metric": "Mdisparity-hypotheses/s (WxHxD)", "value": round(value, 3), "unit": "Mhyp/s",
+            "build_id": capi.build_id(), "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(dt / args.steps * 1e3, 3),
+            "higher_is_better": True, "scaling": "strong" if rows_shard else "weak", "vs_baseline": None,
+            "dtype": ("f32" if args.arith == "f32" else "f64"), "data": "synthetic" if workload != "c1" else "fixture (example project's bunny pair, Qt-scaled)"}
+    config = {"workload": desc + "; TwoView WTA both directions + cross-check; one pair per GPU",
+              "width": W, "height": H, "depth_levels": D, "window_radius": int(p.window_radius),
+              "weights": "geodesic" if wkind == capi.WEIGHT_GEODESIC else "adaptive",
+              "pairs_per_gpu": 1,
+              # (weak scaling: rank r computes its OWN pair -- C5: seed + r, SURVEY 8(d)'s eight pairs ...50 to ...57;
+              # other workloads: seed + 0x10000*r)
+              "pair_seed_rank0": seed, "pair_seed_of_rank_r": ("seed + r" if workload == "c5" else "seed + 0x10000*r") if not rows_shard else "one pair",
+              "parallelism": (("ONE pair in %d row bands, %s gather to rank 0, cross-check there" if rows_shard else "%.0s pairs sharded, %s gather")
+                              % (world, "RCCL" if backend == "nccl" else backend)) if world > 1 else "single GPU",
+              "arithmetic": ("certified (default): fused multiply-adds in the strip kernel's cost loops, every WTA decision checked "
+                             "against a proven error bound, uncovered pixels redone in the reference's arithmetic -- same bits as "
+                             "'exact' (DESIGN.md 2b); kernels without a fused form run the reference's arithmetic" if args.arith == "certified"
+                             else "exact: the reference's operation order, no contraction, everywhere" if args.arith == "exact"
+                             else "fma: multiply-adds of the cost loops fused, UNCHECKED (opt-in, NOT a parity mode)" if args.arith == "fma"
+                             else "f32: cost loops in packed single precision (opt-in, NOT the parity mode, NOT the reference's precision)")}
+    if not args.full:
+        ctx.close()
+        return dict(head, config=config) if rank == 0 else None
 
     prof_timed = ctx.profile()
     stats = ctx.stats()
@@ -525,9 +615,6 @@ def run_twoview(args, workload, rank, world, dev, dev_index, backend):
             certified = {}
         if certified is not None:
             certified["passes"] = passes
-    hyp_per_step_per_gpu = 2 * W * H * D
-    value = (1 if rows_shard else world) * hyp_per_step_per_gpu * args.steps / dt / 1e6
-
     result = None
     if rank == 0:
         # dominant kernel by accumulated HIP-event time on the launch stream
@@ -548,36 +635,18 @@ def run_twoview(args, workload, rank, world, dev, dev_index, backend):
         traffic = pmc_traffic(workload, name, pmc_mode)
         executed = pmc_executed(workload, name, avg_ms, pmc_mode) if args.arith != "f32" else None
         VALU_PEAK = 157.3 if args.arith == "f32" else FP64_VALU_PEAK_TFLOPS
-        result = {
-            "metric": "Mdisparity-hypotheses/s (WxHxD)", "value": round(value, 3), "unit": "Mhyp/s",
-            "build_id": capi.build_id(), "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 3),
+        result = dict(head)
+        result.update({
             # ms_per_step is STEADY STATE (the same uploaded pair again, after the warm-up steps); first_call_ms is what a new pair
             # costs: a fresh context, uploads untimed, ONE srh_twoview_compute with a fence (measured after the timed steps, the
             # process's code objects resident); first_call_cold_process_ms: the same as this process's very first call
             "first_call_ms": first_call_warm, "first_call_samples_ms": first_call_samples, "first_call_cold_process_ms": first_call_cold,
-            "higher_is_better": True, "scaling": "strong" if rows_shard else "weak", "vs_baseline": None,
-            "dtype": ("f32" if args.arith == "f32" else "f64"), "data": "synthetic" if workload != "c1" else "fixture (example project's bunny pair, Qt-scaled)",
-            "config": {"workload": desc + "; TwoView WTA both directions + cross-check; one pair per GPU",
-                       "width": W, "height": H, "depth_levels": D, "window_radius": int(p.window_radius),
-                       "weights": "geodesic" if wkind == capi.WEIGHT_GEODESIC else "adaptive",
-                       "pairs_per_gpu": 1,
-                       # (weak scaling: rank r computes its OWN pair -- C5: seed + r, SURVEY 8(d)'s eight pairs ...50 to ...57;
-                       # other workloads: seed + 0x10000*r)
-                       "pair_seed_rank0": seed, "pair_seed_of_rank_r": ("seed + r" if workload == "c5" else "seed + 0x10000*r") if not rows_shard else "one pair",
-                       "parallelism": (("ONE pair in %d row bands, %s gather to rank 0, cross-check there" if rows_shard else "%.0s pairs sharded, %s gather")
-                                                           % (world, "RCCL" if backend == "nccl" else backend)) if world > 1 else "single GPU",
-                       "dense_path": bool(stats["used_dense_path"]),
-                       "arithmetic": ("certified (default): fused multiply-adds in the strip kernel's cost loops, every WTA decision checked "
-                                      "against a proven error bound, uncovered pixels redone in the reference's arithmetic -- same bits as "
-                                      "'exact' (DESIGN.md 2b); kernels without a fused form run the reference's arithmetic" if args.arith == "certified"
-                                      else "exact: the reference's operation order, no contraction, everywhere" if args.arith == "exact"
-                                      else "fma: multiply-adds of the cost loops fused, UNCHECKED (opt-in, NOT a parity mode)" if args.arith == "fma"
-                                      else "f32: cost loops in packed single precision (opt-in, NOT the parity mode, NOT the reference's precision)"),
-                       "certified_scan": certified,
-                       "winner_mismatch_vs_exact": mismatch,
-                       "n_eval_reference_last_pass": stats["n_eval"],
-                       "n_eval_device_last_pass": stats["n_eval_device"]},
+            "config": dict(config,
+                           dense_path=bool(stats["used_dense_path"]),
+                           certified_scan=certified,
+                           winner_mismatch_vs_exact=mismatch,
+                           n_eval_reference_last_pass=stats["n_eval"],
+                           n_eval_device_last_pass=stats["n_eval_device"]),
             # The binding roof is the vector FP64 ALU (intensity ~3e4 flop/B; SQ_INSTS_MFMA = 0).
             # "achieved" prices the NOMINAL algorithmic flops (1823 per hypothesis at r=5) against the 78.6 TFLOP/s
             # FMA datasheet peak; "executed" is what the kernel really issues (PMC multiply + add lane-ops) against the
@@ -611,7 +680,7 @@ def run_twoview(args, workload, rank, world, dev, dev_index, backend):
                                  "alg_bytes_per_launch": round(bytes_per_launch),
                                  "traffic_over_algorithmic": (round(traffic / bytes_per_launch, 1) if traffic else None)}},
             "kernels_ms": {k: [round(v[0], 3), v[1]] for k, v in sorted(prof.items())},
-        }
+        })
         if TV_OVERLAP and not rows_shard:
             result["kernels_ms_timed"] = {k: [round(v[0], 3), v[1]] for k, v in sorted(prof_timed.items())}
         if world == 1 and args.cpu_rows > 0:
@@ -648,6 +717,7 @@ def other_configs(args, rank, world, dev, dev_index, backend):
         # (two warm-up steps: the first learns the candidate-list capacities of a pair, the second is the first to queue both
         # passes side by side and allocates the second pass's band buffers)
         a.steps, a.warmup, a.cpu_rows, a.workload, a.cpu_all_cores = 3, 2, rows, w, False
+        a.dump_outputs = None                                    # (the outputs are the headline's)
         t0 = time.perf_counter()
         try:
             r = run_c4(a, rank, world, dev, dev_index, backend) if w in ("c4", "c1m") else run_twoview(a, w, rank, world, dev, dev_index, backend)
@@ -833,7 +903,16 @@ def main():
                     help="skip the untimed pass in the reference's arithmetic that counts the depths the chosen arithmetic changes "
                          "(profiling passes: only the kernels of the timed steps are to be traced)")
     ap.add_argument("--no-configs", action="store_true",
-                    help="headline line only: skip the short driver-timed legs of the other BASELINE configurations")
+                    help="with --full: skip the short driver-timed legs of the other BASELINE configurations")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: first calls, the check against the reference's arithmetic, "
+                         "per-kernel times and roofline, the CPU baseline with its parity band, the communicator record and "
+                         "(C3) the legs of the other configurations and the flat-area sweep.  Without it a run sets up, warms "
+                         "up, times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the depth maps of the last step as DIR/<name>.npy (float64, NaN / inf "
+                         "entries 0.0) and DIR/<name>_nonfinite.npy (float32: 0 a depth, 1 NaN, 2 +inf, 3 -inf); a fixed, seeded "
+                         "sample of every file where all of them would exceed %d MB" % (DUMP_BYTES_MAX // 10**6))
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -863,11 +942,11 @@ def main():
             dist.init_process_group("nccl", device_id=dev, timeout=tmo)
         else:
             dist.init_process_group(backend, timeout=tmo)
-    comm = comm_record(dist, backend, world, dev) if rank == 0 or world > 1 else None
+    comm = comm_record(dist, backend, world, dev) if args.full and (rank == 0 or world > 1) else None
 
     if args.workload in ("c4", "c1m"):
         result = run_c4(args, rank, world, dev, dev_index, backend)
-        if result is not None:
+        if result is not None and args.full:
             result["comm"] = comm
         if world > 1:
             dist.barrier()
@@ -877,9 +956,9 @@ def main():
         return
 
     result = run_twoview(args, args.workload, rank, world, dev, dev_index, backend)
-    if result is not None:
+    if result is not None and args.full:
         result["comm"] = comm
-    if rank == 0 and world == 1 and args.workload == "c3" and not args.no_configs and args.arith in ("certified", "exact"):
+    if args.full and rank == 0 and world == 1 and args.workload == "c3" and not args.no_configs and args.arith in ("certified", "exact"):
         result["configs"] = other_configs(args, rank, world, dev, dev_index, backend)
         if args.arith == "certified" and result["config"].get("certified_scan"):
             result["config"]["certified_scan"]["flat_area_sweep"] = flat_area_sweep(dev_index)

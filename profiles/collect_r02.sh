@@ -7,7 +7,7 @@ set -u
 OUT=${1:-gpurun_out/r02}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-B="python3 bench.py"
+B="python3 bench.py --full"
 for w in c1 c2 c3 c4 c5; do
 	timeout -k 10 300 $B --workload $w --steps 5 --warmup 2 > "$OUT/${w}_bench.json" 2> "$OUT/${w}_bench.err"
 done

@@ -9,7 +9,7 @@ set -u
 OUT=${1:-gpurun_out/r03}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-B="python3 bench.py"
+B="python3 bench.py --full"
 timeout -k 10 400 $B --steps 20 --warmup 3 > "$OUT/default_bench.json" 2> "$OUT/default_bench.err"
 for w in c1 c2 c3 c4 c5; do
 	timeout -k 10 300 $B --workload $w --steps 5 --warmup 2 --no-configs > "$OUT/${w}_bench.json" 2> "$OUT/${w}_bench.err"

@@ -11,7 +11,7 @@ OUT=${1:-gpurun_out/r05}
 PART=${2:-all}        # all | a (bench lines, kernel stats, experiments, phase stamps) | b (the PMC passes): one gpurun call each
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-B="python3 bench.py"
+B="python3 bench.py --full"
 if [ "$PART" != b ]; then
 timeout -k 10 400 $B --steps 20 --warmup 3 > "$OUT/default_bench.json" 2> "$OUT/default_bench.err"
 for w in c1 c2 c3 c4 c5 c1m; do

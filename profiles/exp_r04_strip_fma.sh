@@ -3,7 +3,7 @@
 # experiment (timing-experiment build), C3, both forms.  usage: bash profiles/exp_r04_strip_fma.sh gpurun_out/r4f
 set -u
 O=${1:-gpurun_out/r4f}; mkdir -p $O
-B="python3 bench.py --workload c3 --cpu-rows 0 --no-configs"
+B="python3 bench.py --full --workload c3 --cpu-rows 0 --no-configs"
 for ar in certified exact; do
   SRH_LIBRARY=$PWD/profiles/lib/libstereo_recon_hip_prof.so timeout -k 10 200 $B --steps 2 --warmup 1 --arith $ar > $O/phases_$ar.json 2> $O/phases_$ar.err
   grep "srh dbg" $O/phases_$ar.err | grep -v rows | tail -9 > $O/c3_strip8_phases_$ar.txt

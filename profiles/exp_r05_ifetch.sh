@@ -7,7 +7,7 @@ rocprofv3 --list-avail 2>/dev/null | grep -o "SQC_ICACHE[A-Z_]*\|SQ_IFETCH[A-Z_]
 echo >> $OUT/avail_if.txt
 for set in "SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE" "SQ_IFETCH SQ_IFETCH_LEVEL SQ_WAVE_CYCLES SQ_BUSY_CYCLES" "SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS"; do
 	tag=$(echo $set | cut -d' ' -f1)
-	timeout -k 10 300 rocprofv3 --pmc $set -d $OUT/pmc_if_$tag --output-format csv -- python3 bench.py --workload c3 --steps 1 --warmup 0 --cpu-rows 0 --no-configs --no-exact-check > $OUT/pmc_if_$tag.log 2>&1 || { tail -5 $OUT/pmc_if_$tag.log; continue; }
+	timeout -k 10 300 rocprofv3 --pmc $set -d $OUT/pmc_if_$tag --output-format csv -- python3 bench.py --full --workload c3 --steps 1 --warmup 0 --cpu-rows 0 --no-configs --no-exact-check > $OUT/pmc_if_$tag.log 2>&1 || { tail -5 $OUT/pmc_if_$tag.log; continue; }
 	f=$(find $OUT/pmc_if_$tag -name '*counter_collection.csv' | head -1)
 	python3 - "$f" <<'PY'
 import csv, sys, collections
