@@ -213,6 +213,12 @@ int  srh_synchronize(srh_context *ctx);
  *   "debug_alloc_limit_mb"  refuse band buffers above this size as if the device were out of memory (0 = off; tests)
  *   "debug_mvs_cmax_hint"   the list capacity the next MultiViewStereo estimate is queued with (0 = forget; test of the redo of a
  *                     view whose lists were cut)
+ *   "filter_invalid"  0 (default, as the reference's call site under #if 0): srh_twoview_compute ends with the cross-check;
+ *                     SRH_FILTER_* flags (1 gaps, 2 median, 3 both): it then runs srh_view_filter_invalid on both maps,
+ *                     with progress steps 6 "Filling invalid pixels..." and, with the median, 7 "Filtering invalid pixels..."
+ *   "filter_gap_width" the gap width srh_twoview_compute's filter uses (default 2, GAP_WIDTH_THRESHOLD)
+ *   "filter_replay"   1: every median hole is selected by the exact replay of the heap (a test hook: identical bits; the
+ *                     replay is today the only selection)
  * The library reads no environment variable: what a host runs is what it set here. */
 int  srh_set_option(srh_context *ctx, const char *name, long value);
 
@@ -266,7 +272,7 @@ int  srh_twoview_cost_rows(srh_context *ctx, int ref_slot, int other_slot, const
 int  srh_debug_exp(srh_context *ctx, const double *x, int n, double *kernel_out, double *library_out);
 int  srh_twoview_cross_check(srh_context *ctx, int left_slot, int right_slot, const srh_params *p);
 /* computeDepthMaps minus colourisation (twoviewstereo.cpp:150-227): both passes +
- * cross-check, progress steps 1,3,5,8; synchronous; host outputs may be NULL.  The two passes
+ * cross-check, progress steps 1,3,5,8 (option "filter_invalid": 1,3,5,6[,7],8 and the hole filling); synchronous; host outputs may be NULL.  The two passes
  * run side by side on the device (option "tv_overlap"); the progress steps are emitted as the
  * passes are QUEUED. */
 int  srh_twoview_compute(srh_context *ctx, int left_slot, int right_slot, const srh_params *p,
@@ -340,6 +346,28 @@ int  srh_mvs_mrf_state(srh_context *ctx, int w, int h, int top_k, int32_t *label
  * *n_masked = pixels with a WHITE mask (coverage = finite depths / masked pixels is what the reference prints). */
 int  srh_view_point_cloud(srh_context *ctx, int slot, const srh_params *p, double *xyz_out, uint8_t *rgb_out,
                           uint8_t *valid_out, int64_t *n_points, int64_t *n_masked, int64_t *n_finite);
+
+/* ---- hole filling: TwoViewStereo::filterInvalidPixels (twoviewstereo.cpp:676-811) and weightedMedian (:821-860) ----
+ * In place on `slot`'s depth map D, with the slot's image I and mask M; DESIGN.md 4b.
+ *   SRH_FILTER_GAPS    the function's compiled body: per row, a run of isinf pixels with end - start < gap_width (the
+ *                      reference's GAP_WIDTH_THRESHOLD is 2) is filled from both ends inward with the last non-inf value
+ *                      before it and the first after it (NaN past the row's end), a non-finite one taking the other's
+ *                      value.  NaN pixels are never gap-filled.  The result is G (without this flag G = D).
+ *   SRH_FILTER_MEDIAN  its `#if 0` half: NaN where M is not WHITE; D where D (the map BEFORE the gap fill) is finite;
+ *                      elsewhere weightedMedian of G over the support window of I at the pixel (p->weight_kind,
+ *                      p->window_radius <= 5: else SRH_E_UNSUPPORTED): taps with a depth not NaN, inside
+ *                      [min_depth, max_depth] and a weight > 1e-10, the libstdc++ heap's pop order, NaN for fewer than two.
+ * Results are the same bits as the reference's loops.  Any slot works (MultiViewStereo views at radius 2 too); the
+ * reference has this stage for TwoViewStereo (radius 5) only, the one parity target.  info may be NULL. */
+enum { SRH_FILTER_GAPS = 1, SRH_FILTER_MEDIAN = 2 };
+typedef struct srh_filter_info {
+	int64_t holes;          /* WHITE pixels with a non-finite depth on entry */
+	int64_t gap_filled;     /* pixels the gap fill wrote */
+	int64_t median_filled;  /* holes the weighted median made finite */
+	int64_t replayed;       /* holes whose median the exact replay of the heap selected (<= holes) */
+} srh_filter_info;
+int  srh_view_filter_invalid(srh_context *ctx, int slot, const srh_params *p, int flags, int gap_width,
+                             srh_filter_info *info);
 
 /* ---- epipolar curves ----
  * TwoViewStereo::epipolarCurve (public member, twoviewstereo.hpp:66-70, twoviewstereo.cpp:999-1054;

@@ -77,6 +77,15 @@ class Stats(C.Structure):
                 ("scan_tiles_template", C.c_int64), ("scan_tiles_walked", C.c_int64)]
 
 
+class FilterInfo(C.Structure):
+    """srh_filter_info"""
+    _fields_ = [("holes", C.c_int64), ("gap_filled", C.c_int64), ("median_filled", C.c_int64), ("replayed", C.c_int64)]
+
+
+# srh_view_filter_invalid flags
+FILTER_GAPS, FILTER_MEDIAN = 1, 2
+
+
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_int, C.c_char_p, C.c_void_p)
 
 # every symbol include/stereo_recon_hip.h declares
@@ -88,7 +97,8 @@ EXPORTS = [
     "srh_view_upload", "srh_view_size", "srh_view_depth_download", "srh_view_depth_upload",
     "srh_view_depth_device_ptr", "srh_view_depth_copy_to_device", "srh_view_depth_copy_from_device",
     "srh_twoview_wta", "srh_twoview_cross_check", "srh_twoview_compute", "srh_twoview_cost_rows", "srh_debug_exp",
-    "srh_mvs_initial_estimate", "srh_mvs_cross_check", "srh_view_point_cloud", "srh_epipolar_curves",
+    "srh_mvs_initial_estimate", "srh_mvs_cross_check", "srh_view_point_cloud", "srh_view_filter_invalid",
+    "srh_epipolar_curves",
     "srh_epipolar_preview", "srh_refraction_error",
     "srh_mrf_params_defaults", "srh_mvs_mrf_estimate", "srh_mvs_mrf_state", "srh_mvs_mrf_dims", "srh_mvs_initial_estimate_mrf",
     "srh_mvs_initial_estimate_peaks", "srh_mvs_mrf_estimate_views",
@@ -163,6 +173,7 @@ def lib():
     L.srh_epipolar_preview.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, c_double_p, c_double_p, c_int32_p]
     L.srh_refraction_error.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]
     L.srh_view_point_cloud.argtypes = [vp, C.c_int, C.POINTER(Params), c_double_p, c_uint8_p, c_uint8_p, vp, vp, vp]
+    L.srh_view_filter_invalid.argtypes = [vp, C.c_int, C.POINTER(Params), C.c_int, C.c_int, C.POINTER(FilterInfo)]
     L.srh_view_depth_copy_to_device.argtypes = [vp, C.c_int, vp, C.c_size_t]
     L.srh_view_depth_copy_from_device.argtypes = [vp, C.c_int, vp, C.c_size_t]
     L.srh_twoview_wta.argtypes = [vp, C.c_int, C.c_int, C.POINTER(Params), C.c_int, C.c_int]
@@ -462,6 +473,13 @@ class Context:
                                           valid.ctypes.data_as(c_uint8_p), C.cast(C.byref(n, 0), C.c_void_p),
                                           C.cast(C.byref(n, 8), C.c_void_p), C.cast(C.byref(n, 16), C.c_void_p)))
         return dict(xyz=xyz, rgb=rgb, valid=valid, n_points=int(n[0]), n_masked=int(n[1]), n_finite=int(n[2]))
+
+    def filter_invalid(self, slot, p, flags=FILTER_GAPS | FILTER_MEDIAN, gap_width=2):
+        """TwoViewStereo::filterInvalidPixels on the slot's depth map, in place (srh_view_filter_invalid)
+        -> dict(holes, gap_filled, median_filled, replayed)."""
+        info = FilterInfo()
+        _check(lib().srh_view_filter_invalid(self._h, slot, C.byref(p), flags, gap_width, C.byref(info)))
+        return {k: int(getattr(info, k)) for k, _ in FilterInfo._fields_}
 
     def mvs_mrf_estimate(self, view_slot, top_k, peaks_dev, m=None):
         """MRF branch of computeInitialEstimate on the device peaks buffer -> dict(iterations, energy_initial, energy_final)."""

@@ -197,6 +197,9 @@ struct srh_context {
 	std::vector<PendingEvt> pending;
 	srh_stats stats;
 	bool last_fused = false;                            // the last TwoView pass ran the fused kernel
+	int filter_invalid = 0;                             // option "filter_invalid": SRH_FILTER_* flags srh_twoview_compute ends with (0: none)
+	int filter_gap_width = 2;                           // option "filter_gap_width" (GAP_WIDTH_THRESHOLD)
+	int filter_replay = 0;                              // option "filter_replay": every median hole by the exact replay (test hook)
 };
 
 static bool cancelled(srh_context *c) { return c->cancel && *c->cancel; }
@@ -791,6 +794,12 @@ extern "C" int srh_set_option(srh_context *c, const char *name, long value) {
 		return SRH_OK;
 	}
 	if (!strcmp(name, "tv_overlap")) { c->tv_overlap = value != 0; return SRH_OK; }
+	if (!strcmp(name, "filter_invalid")) {
+		if (value < 0 || value > 3) return fail(SRH_E_INVALID, "filter_invalid must be 0..3 (SRH_FILTER_GAPS | SRH_FILTER_MEDIAN)");
+		c->filter_invalid = (int)value; return SRH_OK;
+	}
+	if (!strcmp(name, "filter_gap_width")) { c->filter_gap_width = (int)value; return SRH_OK; }
+	if (!strcmp(name, "filter_replay")) { c->filter_replay = value != 0; return SRH_OK; }
 	if (!strcmp(name, "tscan")) { c->tscan = value != 0; return SRH_OK; }
 	if (!strcmp(name, "geodma")) { c->geodma = value != 0; return SRH_OK; }
 	if (!strcmp(name, "f32_form")) { c->f32_form = value != 0; return SRH_OK; }
@@ -1714,6 +1723,8 @@ static bool tv_pass_stands(const srh_context::TvDefer &d) {
 	return !(d.strip && h.strip_overflow != 0) && h.cert_overflow == 0 && h.not_row_aligned == 0;
 }
 
+static int twoview_filter(srh_context *c, int left, int right, const srh_params *p);
+
 extern "C" int srh_twoview_compute(srh_context *c, int left, int right, const srh_params *p,
                                    double *left_out, double *right_out)
 {
@@ -1784,8 +1795,8 @@ extern "C" int srh_twoview_compute(srh_context *c, int left, int right, const sr
 		progress(c, 5, "Detecting inconsistencies...");
 		if ((rc = srh_twoview_cross_check(c, left, right, p))) return rc;
 		const ViewHost &L = c->views[left], &Rv = c->views[right];
-		if (left_out) HIP_TRY(hipMemcpyAsync(left_out, L.depth, (size_t)L.w*L.h*sizeof(double), hipMemcpyDeviceToHost, c->stream));
-		if (right_out) HIP_TRY(hipMemcpyAsync(right_out, Rv.depth, (size_t)Rv.w*Rv.h*sizeof(double), hipMemcpyDeviceToHost, c->stream));
+		if (left_out && !c->filter_invalid) HIP_TRY(hipMemcpyAsync(left_out, L.depth, (size_t)L.w*L.h*sizeof(double), hipMemcpyDeviceToHost, c->stream));
+		if (right_out && !c->filter_invalid) HIP_TRY(hipMemcpyAsync(right_out, Rv.depth, (size_t)Rv.w*Rv.h*sizeof(double), hipMemcpyDeviceToHost, c->stream));
 		HIP_TRY(hipStreamSynchronize(c->stream));
 		if (c->debug_trace)
 			for (srh_context::TvDefer *d : { &d0, &d1 })
@@ -1813,6 +1824,11 @@ extern "C" int srh_twoview_compute(srh_context *c, int left, int right, const sr
 			c->stats.n_flagged = (int64_t)d1.host->n_flagged;
 			c->stats.used_dense_path = d1.lists ? 0 : 1;
 			c->stats.used_fused_kernel = c->last_fused ? 1 : 0;
+			if (c->filter_invalid) {
+				if ((rc = twoview_filter(c, left, right, p))) return rc;
+				if (left_out && (rc = srh_view_depth_download(c, left, left_out))) return rc;
+				if (right_out && (rc = srh_view_depth_download(c, right, right_out))) return rc;
+			}
 			progress(c, 8, "Finished!");
 			return SRH_OK;
 		}
@@ -1835,6 +1851,7 @@ extern "C" int srh_twoview_compute(srh_context *c, int left, int right, const sr
 	if ((rc = fetch_counters(c, c->stats.used_dense_path))) return rc;
 	progress(c, 5, "Detecting inconsistencies...");
 	if ((rc = srh_twoview_cross_check(c, left, right, p))) return rc;
+	if (c->filter_invalid && (rc = twoview_filter(c, left, right, p))) return rc;
 	if (left_out && (rc = srh_view_depth_download(c, left, left_out))) return rc;
 	if (right_out && (rc = srh_view_depth_download(c, right, right_out))) return rc;
 	if ((rc = srh_synchronize(c))) return rc;
@@ -2206,6 +2223,90 @@ extern "C" int srh_view_point_cloud(srh_context *c, int slot, const srh_params *
 	if (n_masked) *n_masked = (int64_t)hc[1];
 	if (n_finite) *n_finite = (int64_t)hc[2];
 	return SRH_OK;
+}
+
+// ------------------------------------------------------------------ hole filling (srh_filter.hip)
+// One map: G = the gap-filled map (or a copy of D) in the band buffer, then the holes of D listed and NaN written where
+// the mask is not WHITE, then the median of every listed hole from G into D.  emit7: progress step 7 before the median
+// (srh_twoview_compute, first map).
+static int filter_view(srh_context *c, int slot, const srh_params *p, int flags, int gap, srh_filter_info *info, bool emit7)
+{
+	const ViewHost &v = c->views[slot];
+	const size_t n = (size_t)v.w*v.h;
+	const bool gaps = (flags & SRH_FILTER_GAPS) != 0, median = (flags & SRH_FILTER_MEDIAN) != 0;
+	// scratch: G (n doubles) | hole list (n u32) | 4 counters, in the band buffer (free between runs)
+	const size_t need = n + (n + 1)/2 + 4;
+	int rc;
+	if ((rc = ensure(c->wbuf, c->wbuf_cap, need))) return rc;
+	double *G = c->wbuf;
+	uint32_t *holes = reinterpret_cast<uint32_t *>(c->wbuf + n);
+	unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(c->wbuf + need - 4);
+	HIP_TRY(hipMemsetAsync(d_cnt, 0, 4*sizeof(unsigned long long), c->stream));
+	if (gaps) {
+		Scope s(c, "filter_gap_kernel");
+		launch_filter_gaps(c->stream, v.depth, G, v.w, v.h, gap, d_cnt);
+	} else if (median) HIP_TRY(hipMemcpyAsync(G, v.depth, n*sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+	HIP_TRY(hipGetLastError());
+	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
+	{ Scope s(c, "filter_holes_kernel");
+	  launch_filter_holes(c->stream, v.mask, v.depth, v.w, v.h, median, holes, d_cnt); }
+	HIP_TRY(hipGetLastError());
+	unsigned long long hc[4] = { 0, 0, 0, 0 };
+	HIP_TRY(hipMemcpyAsync(hc, d_cnt, sizeof(hc), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	if (median) {
+		if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
+		if (emit7) progress(c, 7, "Filtering invalid pixels...");
+		// (option "filter_replay": the replay is the kernel's only selection today -- every hole takes it either way)
+		{ Scope s(c, "filter_median_kernel");
+		  launch_filter_median(c->stream, c->d_views, slot, *p, G, holes, (int)hc[0], v.depth, d_cnt); }
+		HIP_TRY(hipGetLastError());
+	} else if (gaps) HIP_TRY(hipMemcpyAsync(v.depth, G, n*sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+	HIP_TRY(hipMemcpyAsync(hc, d_cnt, sizeof(hc), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	if (info) {
+		info->holes = (int64_t)hc[0];
+		info->gap_filled = (int64_t)hc[1];
+		info->median_filled = (int64_t)hc[2];
+		info->replayed = (int64_t)hc[3];
+	}
+	return SRH_OK;
+}
+
+static int check_filter(srh_context *c, int slot, const srh_params *p, int flags)
+{
+	int rc;
+	if ((rc = check_slot(c, slot, true)) || (rc = check_params(p))) return rc;
+	if (flags < 0 || flags > (SRH_FILTER_GAPS | SRH_FILTER_MEDIAN)) return fail(SRH_E_INVALID, "filter flags %d unknown", flags);
+	if ((flags & SRH_FILTER_MEDIAN) && p->window_radius > 5)
+		return fail(SRH_E_UNSUPPORTED, "weighted median: window_radius %d > 5", p->window_radius);
+	if ((size_t)c->views[slot].w*c->views[slot].h >= ((size_t)1 << 31))
+		return fail(SRH_E_UNSUPPORTED, "hole filling: view of %d x %d pixels", c->views[slot].w, c->views[slot].h);
+	return SRH_OK;
+}
+
+extern "C" int srh_view_filter_invalid(srh_context *c, int slot, const srh_params *p, int flags, int gap_width,
+                                       srh_filter_info *info)
+{
+	int rc;
+	if ((rc = check_filter(c, slot, p, flags))) return rc;
+	HIP_TRY(hipSetDevice(c->device));
+	if (info) *info = srh_filter_info();
+	return filter_view(c, slot, p, flags, gap_width, info, false);
+}
+
+// srh_twoview_compute's tail with option "filter_invalid" (filterInvalidPixels at the #if 0 call site, :200-223):
+// both maps, progress 6, and 7 before the first median.  (The reference's right-map loop tests left.width() (:748):
+// moot, TwoView views are equal-sized -- each map here is filled over its own width.)
+static int twoview_filter(srh_context *c, int left, int right, const srh_params *p)
+{
+	int rc;
+	const int flags = c->filter_invalid;
+	if ((rc = check_filter(c, left, p, flags)) || (rc = check_filter(c, right, p, flags))) return rc;
+	progress(c, 6, "Filling invalid pixels...");
+	if ((rc = filter_view(c, left, p, flags, c->filter_gap_width, nullptr, true))) return rc;
+	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
+	return filter_view(c, right, p, flags, c->filter_gap_width, nullptr, false);
 }
 
 // ------------------------------------------------------------------ epipolar curves on request

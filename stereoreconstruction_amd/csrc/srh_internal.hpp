@@ -330,6 +330,12 @@ void launch_mvs_list_cost(hipStream_t st, const ViewDev *views, int ref, const i
                           double *unit_peaks, bool peaks, const int32_t *nwin, const uint32_t *act, int nact);
 void launch_mvs_combine(hipStream_t st, const ViewDev *views, int ref, int nneigh, int width, const srh_params &P,
                         int y0, int nrows, const double *best, const double *unit_peaks, double *peaks);
+// hole filling (srh_filter.hip); cnt: 4 counters, see srh_filter_info
+void launch_filter_gaps(hipStream_t st, const double *D, double *G, int w, int h, int gap, unsigned long long *cnt);
+void launch_filter_holes(hipStream_t st, const uint8_t *mask, double *D, int w, int h, bool median, uint32_t *holes,
+                         unsigned long long *cnt);
+void launch_filter_median(hipStream_t st, const ViewDev *views, int slot, const srh_params &P, const double *G,
+                          const uint32_t *holes, int nholes, double *D, unsigned long long *cnt);
 void launch_point_cloud(hipStream_t st, const ViewDev *views, int slot, int w, int h, const srh_params &P,
                         double *xyz, uint8_t *rgb, uint8_t *valid, unsigned long long *counts);
 // MRF stage (srh_mrf.hip): one scratch buffer, carved the same way by every launch

@@ -134,6 +134,25 @@ void TwoViewStereo::crossCheck(CameraPtr leftView_, CameraPtr rightView_) {
 		error_ = srh_last_error();
 }
 
+void TwoViewStereo::filterInvalidPixels() {
+	if (!ctx_) return;
+	const int flags = filterFlags ? filterFlags : SRH_FILTER_GAPS;
+	TwoViewHooks hooks = { this, &progressUpdate, &stageUpdate };
+	srh_set_hooks(ctx_, cancelFlag(), onProgress, &hooks);
+	emitProgress(6);
+	emitStage("Filling invalid pixels...");
+	if (flags & SRH_FILTER_MEDIAN) { emitProgress(7); emitStage("Filtering invalid pixels..."); }
+	int rc = srh_view_depth_upload(ctx_, 0, computedDepthLeft.data());
+	if (rc == SRH_OK) rc = srh_view_depth_upload(ctx_, 1, computedDepthRight.data());
+	// (the reference's right-map loop tests left.width() (:748): the views are equal-sized, each map is filled over its own)
+	if (rc == SRH_OK) rc = srh_view_filter_invalid(ctx_, 0, &params_, flags, 2, nullptr);
+	if (rc == SRH_OK && !isCancelled()) rc = srh_view_filter_invalid(ctx_, 1, &params_, flags, 2, nullptr);
+	if (rc == SRH_OK) rc = srh_view_depth_download(ctx_, 0, computedDepthLeft.data());
+	if (rc == SRH_OK) rc = srh_view_depth_download(ctx_, 1, computedDepthRight.data());
+	srh_set_hooks(ctx_, nullptr, nullptr, nullptr);
+	if (rc != SRH_OK && rc != SRH_E_CANCELLED) error_ = srh_last_error();
+}
+
 double TwoViewStereo::depthFromLabel(int label) const {
 	double t = static_cast<double>(label) / (numDepthLevels - 1);
 	t /= (5.0 - 4.0*t);
@@ -147,6 +166,7 @@ void TwoViewStereo::computeDepthMaps() {
 	if (!uploadViews()) return;
 	TwoViewHooks hooks = { this, &progressUpdate, &stageUpdate };
 	srh_set_hooks(ctx_, cancelFlag(), onProgress, &hooks);
+	srh_set_option(ctx_, "filter_invalid", filterFlags);
 	const int rc_ = srh_twoview_compute(ctx_, 0, 1, &params_, computedDepthLeft.data(), computedDepthRight.data());
 	srh_set_hooks(ctx_, nullptr, nullptr, nullptr);
 	if (rc_ == SRH_E_CANCELLED) return;              // reference: silent return on cancel

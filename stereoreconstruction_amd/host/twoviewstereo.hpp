@@ -29,6 +29,11 @@ public:
 
 	void computeDepthMaps();
 
+	// Hole filling after the cross-check (SRH_FILTER_* flags: 1 gaps, 2 weighted median, 3 both = filterInvalidPixels with
+	// its #if 0 half).  0 (default) is the reference, whose call site is under #if 0 (twoviewstereo.cpp:200-223).
+	void setFilterInvalid(int flags) { filterFlags = flags; }
+	int filterInvalid() const { return filterFlags; }
+
 	// Candidate pixels, in visiting order, of pixel (x,y) of the left (fromLeft) or right view in the
 	// other view.  The reference's public epipolarCurve (twoviewstereo.hpp:66-70) takes the unprojected
 	// ray, camera offset, plane normal, mask and view; all of them follow from the pixel and the
@@ -55,8 +60,11 @@ protected:
 	void crossCheck(CameraPtr leftView, CameraPtr rightView);
 	// label -> depth, non-uniform (:981-985)
 	double depthFromLabel(int label) const;
-	// cost_sad, filterInvalidPixels and weightedMedian are unreachable in the reference (never called /
-	// call site under `#if 0`, twoviewstereo.cpp:200) and have no counterpart here.
+	// ... and the hole filling of both maps (:676-767, progress 6): the compiled body, the row gap fill -- or, after
+	// setFilterInvalid, what its flags ask for (with the median: also progress 7 and the #if 0 half, :769-810).
+	// (cost_sad is never called in the reference and has no counterpart here; weightedMedian is per pixel and stateful
+	// on the reference's weightFuncs: the device does it inside filterInvalidPixels.)
+	void filterInvalidPixels();
 
 private:
 	bool uploadViews();
@@ -72,6 +80,7 @@ private:
 	Image resultLeft, resultRight;
 	DepthMap computedDepthLeft, computedDepthRight;
 	srh_params params_;
+	int filterFlags = 0;
 	srh_context *ctx_;
 	std::string error_;
 };

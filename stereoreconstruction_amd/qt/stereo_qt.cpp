@@ -181,10 +181,33 @@ void TwoViewStereo::computeDepthMaps() {
 	    srh_view_depth_download(ctx_, 0, computedDepthLeft.data()) != SRH_OK ||
 	    srh_view_depth_download(ctx_, 1, computedDepthRight.data()) != SRH_OK) { error_ = srh_last_error(); return; }
 	if (isCancelled()) return;
+	if (filterFlags) {
+		filterInvalidPixels();
+		if (isCancelled() || !error_.isEmpty()) return;
+	}
 	resultLeft = colorize(computedDepthLeft, left.w, left.h);
 	resultRight = colorize(computedDepthRight, right.w, right.h);
 	emit progressUpdate(8);
 	emit stageUpdate("Finished!");
+}
+
+void TwoViewStereo::filterInvalidPixels() {
+	if (!ctx_ || !uploadViews()) return;
+	const int flags = filterFlags ? filterFlags : SRH_FILTER_GAPS;
+	emit progressUpdate(6);
+	emit stageUpdate("Filling invalid pixels...");
+	if (srh_view_depth_upload(ctx_, 0, computedDepthLeft.data()) != SRH_OK ||
+	    srh_view_depth_upload(ctx_, 1, computedDepthRight.data()) != SRH_OK) { error_ = srh_last_error(); return; }
+	if (flags & SRH_FILTER_MEDIAN) {
+		emit progressUpdate(7);
+		emit stageUpdate("Filtering invalid pixels...");
+	}
+	if (isCancelled()) return;
+	// (the reference's right-map loop tests left.width() (:748): the views are equal-sized, each map is filled over its own)
+	if (srh_view_filter_invalid(ctx_, 0, &params_, flags, 2, nullptr) != SRH_OK ||
+	    srh_view_filter_invalid(ctx_, 1, &params_, flags, 2, nullptr) != SRH_OK ||
+	    srh_view_depth_download(ctx_, 0, computedDepthLeft.data()) != SRH_OK ||
+	    srh_view_depth_download(ctx_, 1, computedDepthRight.data()) != SRH_OK) error_ = srh_last_error();
 }
 
 // ------------------------------------------------------------------ MultiViewStereo

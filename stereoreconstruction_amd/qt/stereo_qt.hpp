@@ -115,9 +115,16 @@ public:
 	const DepthMap &rightDepths() const { return computedDepthRight; }
 	srh_params &params() { return params_; }
 	QString lastError() const { return error_; }
+	// hole filling after the cross-check (SRH_FILTER_* flags); 0 (default) = the reference, call site under #if 0
+	void setFilterInvalid(int flags) { filterFlags = flags; }
 
 public: // Task implementation continued: public in the reference as well (stereo/twoviewstereo.hpp:50-52)
 	void runTask() { computeDepthMaps(); }
+
+protected:
+	// stereo/twoviewstereo.hpp, protected: the compiled body (row gap fill of both maps, progress 6), or what
+	// setFilterInvalid asks for (the median: progress 7 and the #if 0 half, twoviewstereo.cpp:769-810)
+	void filterInvalidPixels();
 
 private:
 	QImage colorize(const DepthMap &d, int w, int h) const;
@@ -131,6 +138,7 @@ private:
 	QImage resultLeft, resultRight;
 	DepthMap computedDepthLeft, computedDepthRight;
 	srh_params params_;
+	int filterFlags = 0;
 	srh_context *ctx_;
 	mutable bool uploaded_ = false;                        // views resident on the device (epipolarCurve before computeDepthMaps)
 	bool uploadViews() const;
