@@ -6,6 +6,7 @@
 #include "srh_geom.hpp"
 
 #include <algorithm>
+#include <cassert>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -13,6 +14,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <limits>
 #include <vector>
 
@@ -36,35 +38,195 @@ static int fail(int code, const char *fmt, ...) {
 			return fail(SRH_E_DEVICE, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
 	} while (0)
 
+// ------------------------------------------------------------------ device memory
+// Band buffers grow on demand.  A request the device cannot serve is not the end of the call: g_oom tells the entry
+// point (with_thinner_bands below) to release the band buffers, halve the band budget and run again.
+// g_alloc_limit (option "debug_alloc_limit_mb") makes requests above a size fail the same way: the test of that path.
+// (both are set from the context at the start of every retrying entry point -- with_thinner_bands -- so that a limit set
+// through one thread applies to calls made on another)
+static thread_local bool g_oom = false;
+static thread_local size_t g_alloc_limit = 0;
+
+// ---- the process's pool of device blocks -----------------------------------------------------------------------------
+// A TwoViewStereo / MultiViewStereo object of the reference lives for one computation (twoviewstereo.cpp:150-227; the GUI
+// makes a new one per run), so a drop-in creates and destroys contexts again and again in one process -- and a context's
+// band buffers are gigabytes.  Handing them back to the driver at srh_destroy and asking for them again at the next
+// object's first call is not free on this stack: measured (profiles/r06_first_call.txt, HIP API trace) ONE hipMalloc of 11 GB
+// now and then takes 0.9 ... 1.5 s when tens of GB have just been freed by the same process (its siblings: 0.3 ms).  So band
+// buffers and view planes (230 MB for a 1920 x 1080 view) released by srh_destroy, free_view or a growing buffer go to a
+// process-wide pool, per device, under their real size, and the next context's requests are served from it (best fit, at
+// most 1.5x the request); what is under the floor or does not fit the pool's cap is freed.  The pool is emptied before an
+// allocation is declared out of memory, and counts as available memory for the band planner.
+// Option "band_pool_mb" (any context; process-wide): the cap, default 65 536; 0 empties and disables the pool.
+struct PoolBlock { void *p; size_t bytes; int device; };
+static std::mutex g_pool_mu;
+static std::vector<PoolBlock> g_pool;
+static size_t g_pool_bytes = 0, g_pool_cap = (size_t)65536 << 20;
+static const size_t POOL_MIN_BYTES = (size_t)4 << 20;                // smaller buffers are not worth a pool entry
+
+static void pool_flush(int device) {                                 // (device < 0: every device)
+	std::vector<PoolBlock> out;
+	{
+		std::lock_guard<std::mutex> g(g_pool_mu);
+		for (size_t k = 0; k < g_pool.size();)
+			if (device < 0 || g_pool[k].device == device) { out.push_back(g_pool[k]); g_pool_bytes -= g_pool[k].bytes; g_pool[k] = g_pool.back(); g_pool.pop_back(); }
+			else ++k;
+	}
+	int cur = 0;
+	const bool have = hipGetDevice(&cur) == hipSuccess;
+	for (const PoolBlock &b : out) { (void)hipSetDevice(b.device); (void)hipFree(b.p); }
+	if (have) (void)hipSetDevice(cur);
+}
+static size_t pool_bytes_on(int device) {
+	std::lock_guard<std::mutex> g(g_pool_mu);
+	size_t b = 0;
+	for (const PoolBlock &k : g_pool) if (k.device == device) b += k.bytes;
+	return b;
+}
+// a released block of `bytes` on the current device: into the pool, or back to the driver
+static void pool_give(void *p, size_t bytes) {
+	if (!p) return;
+	int dev = 0;
+	if (bytes >= POOL_MIN_BYTES && hipGetDevice(&dev) == hipSuccess) {
+		std::lock_guard<std::mutex> g(g_pool_mu);
+		if (g_pool_bytes + bytes <= g_pool_cap) { g_pool.push_back({p, bytes, dev}); g_pool_bytes += bytes; return; }
+	}
+	(void)hipFree(p);
+}
+// a block of at least `bytes` (at most 1.5x) from the pool, or null; *got = its size
+static void *pool_take(size_t bytes, size_t *got) {
+	int dev = 0;
+	if (bytes < POOL_MIN_BYTES || hipGetDevice(&dev) != hipSuccess) return nullptr;
+	std::lock_guard<std::mutex> g(g_pool_mu);
+	size_t best = g_pool.size();
+	for (size_t k = 0; k < g_pool.size(); ++k)
+		if (g_pool[k].device == dev && g_pool[k].bytes >= bytes && g_pool[k].bytes <= bytes + bytes/2 &&
+		    (best == g_pool.size() || g_pool[k].bytes < g_pool[best].bytes)) best = k;
+	if (best == g_pool.size()) return nullptr;
+	void *p = g_pool[best].p;
+	*got = g_pool[best].bytes;
+	g_pool_bytes -= g_pool[best].bytes;
+	g_pool[best] = g_pool.back(); g_pool.pop_back();
+	return p;
+}
+
+// Every device block of this file: from the pool, else from the driver -- and after an out-of-memory answer once more,
+// with this device's pool given back first (the pool's blocks are memory too).  *got = the block's real size.
+static hipError_t dev_alloc(void **p, size_t bytes, size_t *got) {
+	if ((*p = pool_take(bytes, got))) return hipSuccess;
+	hipError_t e = hipMalloc(p, bytes);
+	if (e == hipErrorOutOfMemory) {
+		(void)hipGetLastError();
+		int dev = 0;
+		if (hipGetDevice(&dev) == hipSuccess && pool_bytes_on(dev)) { pool_flush(dev); e = hipMalloc(p, bytes); }
+	}
+	if (e != hipSuccess) { *p = nullptr; (void)hipGetLastError(); return e; }
+	*got = bytes;
+	return hipSuccess;
+}
+
+// A device buffer: the block, its real size in bytes and the elements of T it holds.  Not copyable; a move leaves the source
+// empty and goes into an empty buffer only, so no assignment drops a block.  Nothing frees it implicitly: release() (to
+// the pool, whose floor and cap decide what waits there) and free() (to the driver) show where device memory leaves, and
+// the device waits they need stay at their call sites.
+template <class T>
+struct DevBuf {
+	T *p = nullptr;
+	size_t n = 0, block = 0;
+	DevBuf() = default;
+	DevBuf(DevBuf &&o) noexcept { *this = std::move(o); }
+	DevBuf &operator=(DevBuf &&o) noexcept {
+		assert(!p && "a held block is released, not overwritten");
+		p = o.p; n = o.n; block = o.block;
+		o.p = nullptr; o.n = o.block = 0;
+		return *this;
+	}
+	operator T *() const { return p; }
+	T *operator->() const { return p; }
+	size_t bytes() const { return block; }
+	// `count` elements into this empty buffer
+	hipError_t alloc(size_t count) {
+		void *q = nullptr;
+		size_t got = 0;
+		const hipError_t e = dev_alloc(&q, count*sizeof(T), &got);
+		if (e == hipSuccess) { p = (T *)q; n = got/sizeof(T); block = got; }
+		return e;
+	}
+	// a band buffer of at least `need` elements (kept when it holds them already)
+	int ensure(size_t need) {
+		if (n >= need) return SRH_OK;
+		// (a buffer that is being outgrown: hipFree used to wait for the device before it let go of it; the pool must not hand it to
+		// another context while a kernel queued earlier still reads it -- growth is rare, the wait is kept)
+		if (p) { (void)hipDeviceSynchronize(); release(); }
+		if (g_alloc_limit && need*sizeof(T) > g_alloc_limit) {
+			g_oom = true;
+			return fail(SRH_E_DEVICE, "band buffer of %zu bytes refused (debug_alloc_limit_mb)", need*sizeof(T));
+		}
+		const hipError_t e = alloc(need);
+		if (e == hipErrorOutOfMemory) g_oom = true;
+		if (e != hipSuccess) return fail(SRH_E_DEVICE, "hipMalloc of a %zu-byte band buffer: %s", need*sizeof(T), hipGetErrorString(e));
+		return SRH_OK;
+	}
+	void release() { pool_give(p, block); p = nullptr; n = block = 0; }
+	void free() { if (p) (void)hipFree(p); p = nullptr; n = block = 0; }
+};
+
+// The band buffers of one pass: scratch sized by the band height, which an out-of-memory retry gives back
+// (release_band_buffers).  The context runs on its own set; the second TwoView pass (TvSlot) and the second MultiViewStereo
+// estimate in flight (MvsSlot 1) hold one each and swap it with the context's for their launches.  each() is the one list.
+struct BandBuffers {
+	DevBuf<double> wbuf;            // support windows of the band
+	DevBuf<double> cost;            // cost rows of the band
+	DevBuf<double> tnum;            // per-label table of the pinhole walk
+	DevBuf<double> pconst;          // per-pixel constants of the dense kernel's fast form (4 doubles per pixel of a band)
+	DevBuf<PixRange> prange;        // per-pixel candidate column range of a band (strip kernel, scan)
+	DevBuf<uint32_t> cflag;         // certified arithmetic: [count | band pixels whose decisions the bound does not cover]
+	DevBuf<uint8_t> stpl;           // template scan: the pass's candidate template (twoview_template_kernel)
+	DevBuf<uint32_t> tileflag;      //   and the tiles it leaves to twoview_scan_kernel: [count | tile indices]
+	DevBuf<int32_t> lcount;         // candidate-list path: candidates per pixel
+	DevBuf<uint32_t> lcand;         //   candidate pixels (cx | cy<<16)
+	DevBuf<uint32_t> lrowinfo;      //   row runs of the lists (srh_rows.hip)
+	DevBuf<int32_t> lmeta;
+	DevBuf<uint32_t> mvs_wdesc;     // window descriptors of the MultiViewStereo walk kernel's waves
+	DevBuf<int32_t> mvs_nwin;
+	template <class F> void each(F f) {
+		f(wbuf); f(cost); f(tnum); f(pconst); f(prange); f(cflag); f(stpl); f(tileflag);
+		f(lcount); f(lcand); f(lrowinfo); f(lmeta); f(mvs_wdesc); f(mvs_nwin);
+	}
+	size_t bytes() { size_t b = 0; each([&](auto &x) { b += x.bytes(); }); return b; }
+	void release() { each([](auto &x) { x.release(); }); }
+	void free() { each([](auto &x) { x.free(); }); }
+};
+
 // ------------------------------------------------------------------ context
 struct ViewHost {
 	int w = 0, h = 0;
 	bool present = false;
-	uint32_t *rgba = nullptr;
-	uint8_t  *mask = nullptr;
-	double   *gray = nullptr, *gray_tv = nullptr, *depth = nullptr;
-	double   *edges = nullptr;     // 4 planes of neighbour colour distances (geodesic windows)
-	uint8_t  *full = nullptr;      // 1 where the whole (2*full_r+1)^2 TwoView window is usable
-	int       full_r = 0;
+	DevBuf<uint32_t> rgba;
+	DevBuf<uint8_t>  mask;
+	DevBuf<double>   gray, gray_tv, depth;
+	DevBuf<double>   edges;        // 4 planes of neighbour colour distances (geodesic windows)
+	DevBuf<uint8_t>  full;         // 1 where the whole (2*full_r+1)^2 TwoView window is usable
+	int              full_r = 0;
 	// strip kernel (srh_strip.hip): NaN-bordered copy of gray_tv, zero-bordered "window fully usable" plane for radius fullp_r
-	double   *tvp = nullptr;   bool tvp_valid = false;
-	double   *geo5 = nullptr;  bool geo5_valid = false;   // edge + tap planes with their borders written out (geodesic_dma_kernel)
-	bool      geo5_denied = false;                        // released by an out-of-memory retry: this upload keeps the register-staged windows kernel
-	uint8_t  *fullp = nullptr; int fullp_r = 0;
+	DevBuf<double>   tvp;   bool tvp_valid = false;
+	DevBuf<double>   geo5;  bool geo5_valid = false;      // edge + tap planes with their borders written out (geodesic_dma_kernel)
+	bool             geo5_denied = false;                 // released by an out-of-memory retry: this upload keeps the register-staged windows kernel
+	DevBuf<uint8_t>  fullp; int fullp_r = 0;
 	// how the candidate lists of this view against slot j are best evaluated, learnt from the last run:
 	// 0 unknown, 1 row runs (srh_rows.hip), 2 list order (srh_list.hip: steep curves)
 	uint8_t   list_mode[SRH_MAX_VIEWS] = {0};
 	// MultiViewStereo list path: the masked-in pixels (y*w + x) row by row, even rows left to right, odd rows right to
 	// left, so that consecutive entries are neighbours in the image also across a row change; act_row[y] = first entry of
 	// row y (h + 1 values).  A wave of the walk / cost kernels takes 64 consecutive entries.
-	uint32_t *act = nullptr; size_t act_cap = 0;
+	DevBuf<uint32_t> act;
 	std::vector<uint32_t> act_row, act_host;
 	std::vector<uint8_t> hmask;    // host copy of the mask bytes (empty: no mask, every pixel counts): `act` is built from it
 	bool act_valid = false;        //   when the MultiViewStereo list path first asks (ensure_act); TwoView callers never pay for it
 	srh_camera cam;
 	// MRF branch over several views (srh_mvs_initial_estimate_peaks / srh_mvs_mrf_estimate_views)
-	double   *peaks = nullptr; size_t peaks_cap = 0; int peaks_k = 0;   // top-K peaks of the last initial estimate
-	double   *mrf = nullptr;   size_t mrf_cap = 0;                      // this view's own TRW-S scratch
+	DevBuf<double> peaks; int peaks_k = 0;      // top-K peaks of the last initial estimate
+	DevBuf<double> mrf;                         // this view's own TRW-S scratch
 };
 
 struct ProfEntry { double ms = 0; int64_t n = 0; };
@@ -78,15 +240,9 @@ struct MvsSlot {
 	hipStream_t stream = nullptr;
 	hipEvent_t ev = nullptr, done = nullptr;
 	int *h_maxc = nullptr;                              // pinned: longest list of the queued pass
-	bool own_buffers = false;                           // slot 1: its own band buffers, swapped into the context for its launches
-	double *wbuf = nullptr; size_t wbuf_cap = 0;
-	double *cost = nullptr; size_t cost_cap = 0;
-	double *tnum = nullptr; size_t tnum_cap = 0;
-	int32_t *lcount = nullptr; size_t lcount_cap = 0;
-	uint32_t *lcand = nullptr; size_t lcand_cap = 0;
-	uint32_t *mvs_wdesc = nullptr; size_t mvs_wdesc_cap = 0;
-	int32_t *mvs_nwin = nullptr; size_t mvs_nwin_cap = 0;
-	Counters *d_cnt = nullptr; int *d_span = nullptr;
+	bool own_buffers = false;                           // slot 1: its own band buffers and counters, swapped into the context for its launches
+	BandBuffers band;
+	DevBuf<Counters> d_cnt; DevBuf<int> d_span;
 	bool pending = false;                               // kernels queued, capacity check outstanding
 	int view = -1, nneigh = 0, y0 = 0, y1 = 0, cmax = 0;
 	int32_t neigh[SRH_MAX_NEIGH] = {0};
@@ -98,30 +254,21 @@ struct srh_context {
 	hipStream_t own_stream = nullptr;
 	hipStream_t stream = nullptr;
 	ViewHost views[SRH_MAX_VIEWS];
-	ViewDev *d_views = nullptr;
-	int32_t *d_slots = nullptr;
+	DevBuf<ViewDev> d_views;
+	DevBuf<int32_t> d_slots;
 	int32_t slots_host[SRH_MAX_VIEWS] = {0}; int slots_n = 0;   // what d_slots holds (srh_mvs_cross_check: the same list for every view of a run)
-	Counters *d_cnt = nullptr;
-	int *d_span = nullptr;
-	double *wbuf = nullptr;   size_t wbuf_cap = 0;      // doubles
-	double *cost = nullptr;   size_t cost_cap = 0;      // doubles
-	double *tnum = nullptr;   size_t tnum_cap = 0;      // per-label table of the pinhole walk
+	DevBuf<Counters> d_cnt;
+	DevBuf<int> d_span;
+	BandBuffers band;
 	hipStream_t mrf_stream[SRH_MAX_VIEWS] = { nullptr };            // one stream per view of srh_mvs_mrf_estimate_views
 	void *mrf_host = nullptr;                                       // pinned: per view {energy, pad, status[4]}
-	double *mrf_peaks = nullptr; size_t mrf_peaks_cap = 0;   // top-K peaks of srh_mvs_initial_estimate_mrf
-	double *mrf = nullptr;    size_t mrf_cap = 0;       // MRF stage scratch (srh_mrf.hip); mrf_w/h/k: what the last run left in it
+	DevBuf<double> mrf_peaks;                           // top-K peaks of srh_mvs_initial_estimate_mrf
+	DevBuf<double> mrf;                                 // MRF stage scratch (srh_mrf.hip); mrf_w/h/k: what the last run left in it
 	int mrf_w = 0, mrf_h = 0, mrf_k = 0;
-	double *pconst = nullptr; size_t pconst_cap = 0;    // per-pixel constants of the dense kernel's fast form (4 doubles per pixel of a band)
-	PixRange *prange = nullptr; size_t prange_cap = 0;  // per-pixel candidate column range of a band (strip kernel, scan)
-	uint32_t *cflag = nullptr; size_t cflag_cap = 0;    // certified arithmetic: [count | band pixels whose decisions the bound does not cover]
-	uint8_t *stpl = nullptr; size_t stpl_cap = 0;       // template scan: the pass's candidate template (twoview_template_kernel)
-	uint32_t *tileflag = nullptr; size_t tileflag_cap = 0;  //   and the tiles it leaves to twoview_scan_kernel: [count | tile indices]
 	int geodma = 1;                                     // option "geodma": 1 = the dense path's r = 5 geodesic windows by the persistent LDS-DMA kernel (default), 0 = geodesic_reg_kernel
 	int tscan = 1;                                      // option "tscan": 1 = template scan on the dense path (default), 0 = every tile through twoview_scan_kernel
 	int strip = 1;                                      // option "strip": 1 = persistent strip cost kernel (default), 0 = one workgroup per tile, 4 / 8 = force the 4- / 8-wave form
 	int num_cus = 256;
-	int32_t *lcount = nullptr; size_t lcount_cap = 0;   // candidate-list path: candidates per pixel
-	uint32_t *lcand = nullptr; size_t lcand_cap = 0;    //   candidate pixels (cx | cy<<16)
 	bool force_walk = false;                            // option "force_generic" = 2: never use the list path either
 	int list_count_pass = 0;                            // option "list_count_pass": size a pair's first lists by a counting pass (round 5) instead of the host's guess
 	int list_cmax_hint = 0;                             // longest candidate list seen so far (list-path capacity)
@@ -135,11 +282,7 @@ struct srh_context {
 	int mvs_turn = 0, mvs_last = -1;
 	bool in_settle = false;
 	int mvs_staged = 1;                                 // option "mvs_staged": the list cost kernel takes its windows from LDS copies of the other view where they fit (default), 0 = gathers only
-	uint32_t *mvs_wdesc = nullptr; size_t mvs_wdesc_cap = 0;   // window descriptors of the walk kernel's waves
-	int32_t *mvs_nwin = nullptr; size_t mvs_nwin_cap = 0;
 	bool list_rows = true;                              // option "list_rows": evaluate lists in row runs (srh_rows.hip)
-	uint32_t *lrowinfo = nullptr; size_t lrowinfo_cap = 0;
-	int32_t *lmeta = nullptr; size_t lmeta_cap = 0;
 	void *comm = nullptr; int comm_ranks = 0, comm_rank = 0;   // RCCL communicator (srh_comm_init)
 	// bytes per band of scratch (windows, cost rows, candidate lists) the caller ASKS for: every band ends in the tails of
 	// its kernels, so the largest configuration should take one band where the device has the room (MI355X: 288 GB).
@@ -177,12 +320,8 @@ struct srh_context {
 	struct TvSlot {
 		hipStream_t stream = nullptr;
 		hipEvent_t go = nullptr, done = nullptr;
-		Counters *d_cnt = nullptr; int *d_span = nullptr;
-		double *wbuf = nullptr, *cost = nullptr, *tnum = nullptr, *pconst = nullptr;
-		PixRange *prange = nullptr; uint32_t *cflag = nullptr, *lcand = nullptr, *lrowinfo = nullptr; int32_t *lcount = nullptr, *lmeta = nullptr;
-		uint8_t *stpl = nullptr; uint32_t *tileflag = nullptr;
-		size_t wbuf_cap = 0, cost_cap = 0, tnum_cap = 0, pconst_cap = 0, prange_cap = 0, cflag_cap = 0, lcand_cap = 0, lrowinfo_cap = 0,
-		       lcount_cap = 0, lmeta_cap = 0, stpl_cap = 0, tileflag_cap = 0;
+		DevBuf<Counters> d_cnt; DevBuf<int> d_span;
+		BandBuffers band;
 	} tv_slot;
 	int tv_overlap = 1;                                 // option "tv_overlap": 0 = both passes on the context's stream, one after the other
 	int f32_form = 0;                                   // option "f32_form" (f32 mode only, not a parity mode): 1 = the one-pass sums in single precision (priced in DESIGN.md 9.0'' (i))
@@ -237,104 +376,6 @@ struct Scope {
 	}
 };
 
-// Band buffers grow on demand.  A request the device cannot serve is not the end of the call: g_oom tells the entry
-// point (with_thinner_bands below) to release the band buffers, halve the band budget and run again.
-// g_alloc_limit (option "debug_alloc_limit_mb") makes requests above a size fail the same way: the test of that path.
-// (both are set from the context at the start of every retrying entry point -- with_thinner_bands -- so that a limit set
-// through one thread applies to calls made on another)
-static thread_local bool g_oom = false;
-static thread_local size_t g_alloc_limit = 0;
-
-// ---- the process's pool of band buffers ------------------------------------------------------------------------------
-// A TwoViewStereo / MultiViewStereo object of the reference lives for one computation (twoviewstereo.cpp:150-227; the GUI
-// makes a new one per run), so a drop-in creates and destroys contexts again and again in one process -- and a context's
-// band buffers are gigabytes.  Handing them back to the driver at srh_destroy and asking for them again at the next
-// object's first call is not free on this stack: measured (profiles/r06_first_call.txt, HIP API trace) ONE hipMalloc of 11 GB
-// now and then takes 0.9 ... 1.5 s when tens of GB have just been freed by the same process (its siblings: 0.3 ms).  So band
-// buffers released by srh_destroy (and by a growing buffer) go to a process-wide pool, per device, and the next context's
-// requests are served from it (best fit, at most 1.5x the request); what does not fit the pool's cap is freed.  The pool
-// is emptied before an allocation is declared out of memory, and counts as available memory for the band planner.
-// Option "band_pool_mb" (any context; process-wide): the cap, default 65 536; 0 empties and disables the pool.
-struct PoolBlock { void *p; size_t bytes; int device; };
-static std::mutex g_pool_mu;
-static std::vector<PoolBlock> g_pool;
-static size_t g_pool_bytes = 0, g_pool_cap = (size_t)65536 << 20;
-static const size_t POOL_MIN_BYTES = (size_t)4 << 20;                // smaller buffers are not worth a pool entry
-
-static void pool_flush(int device) {                                 // (device < 0: every device)
-	std::vector<PoolBlock> out;
-	{
-		std::lock_guard<std::mutex> g(g_pool_mu);
-		for (size_t k = 0; k < g_pool.size();)
-			if (device < 0 || g_pool[k].device == device) { out.push_back(g_pool[k]); g_pool_bytes -= g_pool[k].bytes; g_pool[k] = g_pool.back(); g_pool.pop_back(); }
-			else ++k;
-	}
-	int cur = 0;
-	const bool have = hipGetDevice(&cur) == hipSuccess;
-	for (const PoolBlock &b : out) { (void)hipSetDevice(b.device); (void)hipFree(b.p); }
-	if (have) (void)hipSetDevice(cur);
-}
-static size_t pool_bytes_on(int device) {
-	std::lock_guard<std::mutex> g(g_pool_mu);
-	size_t b = 0;
-	for (const PoolBlock &k : g_pool) if (k.device == device) b += k.bytes;
-	return b;
-}
-// a released band buffer of `bytes` on the current device: into the pool, or back to the driver
-static void pool_give(void *p, size_t bytes) {
-	if (!p) return;
-	int dev = 0;
-	if (bytes >= POOL_MIN_BYTES && hipGetDevice(&dev) == hipSuccess) {
-		std::lock_guard<std::mutex> g(g_pool_mu);
-		if (g_pool_bytes + bytes <= g_pool_cap) { g_pool.push_back({p, bytes, dev}); g_pool_bytes += bytes; return; }
-	}
-	(void)hipFree(p);
-}
-// a block of at least `bytes` (at most 1.5x) from the pool, or null; *got = its size
-static void *pool_take(size_t bytes, size_t *got) {
-	int dev = 0;
-	if (bytes < POOL_MIN_BYTES || hipGetDevice(&dev) != hipSuccess) return nullptr;
-	std::lock_guard<std::mutex> g(g_pool_mu);
-	size_t best = g_pool.size();
-	for (size_t k = 0; k < g_pool.size(); ++k)
-		if (g_pool[k].device == dev && g_pool[k].bytes >= bytes && g_pool[k].bytes <= bytes + bytes/2 &&
-		    (best == g_pool.size() || g_pool[k].bytes < g_pool[best].bytes)) best = k;
-	if (best == g_pool.size()) return nullptr;
-	void *p = g_pool[best].p;
-	*got = g_pool[best].bytes;
-	g_pool_bytes -= g_pool[best].bytes;
-	g_pool[best] = g_pool.back(); g_pool.pop_back();
-	return p;
-}
-
-template <class T>
-static int ensure(T *&ptr, size_t &cap, size_t need) {
-	if (cap >= need) return SRH_OK;
-	// (a buffer that is being outgrown: hipFree used to wait for the device before it let go of it; the pool must not hand it to
-	// another context while a kernel queued earlier still reads it -- growth is rare, the wait is kept)
-	if (ptr) { (void)hipDeviceSynchronize(); pool_give(ptr, cap*sizeof(T)); ptr = nullptr; cap = 0; }
-	if (g_alloc_limit && need*sizeof(T) > g_alloc_limit) {
-		g_oom = true;
-		return fail(SRH_E_DEVICE, "band buffer of %zu bytes refused (debug_alloc_limit_mb)", need*sizeof(T));
-	}
-	size_t got = 0;
-	if (void *q = pool_take(need*sizeof(T), &got)) { ptr = (T *)q; cap = got/sizeof(T); return SRH_OK; }
-	hipError_t e = hipMalloc((void **)&ptr, need*sizeof(T));
-	if (e == hipErrorOutOfMemory) {
-		// the pool's blocks are memory too: give them back and ask once more before the bands get thinner
-		(void)hipGetLastError();
-		int dev = 0;
-		if (hipGetDevice(&dev) == hipSuccess && pool_bytes_on(dev)) { pool_flush(dev); e = hipMalloc((void **)&ptr, need*sizeof(T)); }
-	}
-	if (e != hipSuccess) {
-		ptr = nullptr;
-		(void)hipGetLastError();
-		if (e == hipErrorOutOfMemory) g_oom = true;
-		return fail(SRH_E_DEVICE, "hipMalloc of a %zu-byte band buffer: %s", need*sizeof(T), hipGetErrorString(e));
-	}
-	cap = need;
-	return SRH_OK;
-}
 
 static int mvs_settle_all(srh_context *c);
 // settle: finish the MultiViewStereo estimates in flight first (every entry point but srh_mvs_initial_estimate itself)
@@ -605,12 +646,10 @@ extern "C" int srh_create(int device, srh_context **out) {
 	hipError_t e2 = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
 	if (e2 != hipSuccess) { delete c; return fail(SRH_E_DEVICE, "hipStreamCreate: %s", hipGetErrorString(e2)); }
 	c->stream = c->own_stream;
-	if (hipMalloc((void **)&c->d_views, sizeof(ViewDev)*SRH_MAX_VIEWS) != hipSuccess ||
-	    hipMalloc((void **)&c->d_slots, sizeof(int32_t)*SRH_MAX_VIEWS) != hipSuccess ||
-	    hipMalloc((void **)&c->d_cnt, sizeof(Counters)) != hipSuccess ||
-	    hipMalloc((void **)&c->d_span, 4*sizeof(int)) != hipSuccess) {
+	if (c->d_views.alloc(SRH_MAX_VIEWS) != hipSuccess || c->d_slots.alloc(SRH_MAX_VIEWS) != hipSuccess ||
+	    c->d_cnt.alloc(1) != hipSuccess || c->d_span.alloc(4) != hipSuccess) {
 		srh_destroy(c);
-		return fail(SRH_E_DEVICE, "hipMalloc of context tables failed");
+		return fail(SRH_E_DEVICE, "allocating the context tables failed");
 	}
 	// ordered on the context's own (non-blocking) stream, which the null stream does not synchronise with
 	if (hipMemsetAsync(c->d_views, 0, sizeof(ViewDev)*SRH_MAX_VIEWS, c->stream) != hipSuccess ||
@@ -623,31 +662,11 @@ extern "C" int srh_create(int device, srh_context **out) {
 	return SRH_OK;
 }
 
-// a view plane: from the process's pool when it holds a block of that size, else from the driver (the planes of a 1920 x 1080
-// view are 230 MB: released and asked for again with every stereo object, like the band buffers)
-static hipError_t plane_alloc(void **p, size_t bytes) {
-	size_t got = 0;
-	if (void *q = pool_take(bytes, &got)) { *p = q; return hipSuccess; }
-	return hipMalloc(p, bytes);
-}
-
-// (hipFree waited for the device before it released a plane; so does this, before a plane can reach another context)
+// (freeing a plane used to wait for the device; so does this, before a plane can reach another context)
 static void free_view(ViewHost &v) {
-	const size_t n = (size_t)v.w*v.h;
 	if (v.rgba || v.gray || v.edges || v.tvp || v.geo5) (void)hipDeviceSynchronize();
-	pool_give(v.rgba, n*4);
-	if (v.mask) hipFree(v.mask);
-	pool_give(v.gray, n*sizeof(double));
-	pool_give(v.gray_tv, n*sizeof(double));
-	pool_give(v.depth, n*sizeof(double));
-	pool_give(v.edges, 4*n*sizeof(double));
-	if (v.full) hipFree(v.full);
-	pool_give(v.tvp, v.tvp ? padded_size(v.w, v.h)*sizeof(double) : 0);
-	pool_give(v.geo5, v.geo5 ? geo5_doubles(v.w, v.h)*sizeof(double) : 0);
-	if (v.fullp) hipFree(v.fullp);
-	if (v.peaks) hipFree(v.peaks);
-	if (v.mrf) hipFree(v.mrf);
-	if (v.act) hipFree(v.act);
+	v.rgba.release(); v.mask.release(); v.gray.release(); v.gray_tv.release(); v.depth.release(); v.edges.release();
+	v.full.release(); v.tvp.release(); v.geo5.release(); v.fullp.release(); v.act.release(); v.peaks.release(); v.mrf.release();
 	v = ViewHost();
 }
 
@@ -668,64 +687,26 @@ extern "C" void srh_destroy(srh_context *c) {
 		if (S.ev) hipEventDestroy(S.ev);
 		if (S.done) hipEventDestroy(S.done);
 		if (S.h_maxc) hipHostFree(S.h_maxc);
-		pool_give(S.wbuf, S.wbuf_cap*sizeof(double));
-		pool_give(S.cost, S.cost_cap*sizeof(double));
-		if (S.tnum) hipFree(S.tnum);
-		pool_give(S.lcount, S.lcount_cap*sizeof(int32_t));
-		pool_give(S.lcand, S.lcand_cap*sizeof(uint32_t));
-		if (S.mvs_wdesc) hipFree(S.mvs_wdesc);
-		if (S.mvs_nwin) hipFree(S.mvs_nwin);
-		if (S.d_cnt) hipFree(S.d_cnt);
-		if (S.d_span) hipFree(S.d_span);
+		S.band.release(); S.d_cnt.release(); S.d_span.release();
 	}
 	for (auto &v : c->views) free_view(v);
-	if (c->d_views) hipFree(c->d_views);
-	if (c->d_slots) hipFree(c->d_slots);
-	if (c->d_cnt) hipFree(c->d_cnt);
-	if (c->d_span) hipFree(c->d_span);
+	c->d_views.release(); c->d_slots.release(); c->d_cnt.release(); c->d_span.release();
 	// (every stream of the context has been waited for above: its band buffers are idle and go to the process's pool)
 	(void)hipDeviceSynchronize();
 	(void)hipStreamSynchronize(c->stream);
 	if (c->tv_slot.stream) (void)hipStreamSynchronize(c->tv_slot.stream);
-	pool_give(c->wbuf, c->wbuf_cap*sizeof(double));
-	pool_give(c->cost, c->cost_cap*sizeof(double));
-	if (c->tnum) hipFree(c->tnum);
-	pool_give(c->pconst, c->pconst_cap*sizeof(double));
-	pool_give(c->prange, c->prange_cap*sizeof(PixRange));
-	pool_give(c->cflag, c->cflag_cap*sizeof(uint32_t));
-	if (c->stpl) hipFree(c->stpl);
-	if (c->tileflag) hipFree(c->tileflag);
+	c->band.release();
 	for (auto &d : c->tv_defer) { if (d.host) hipHostFree(d.host); if (d.span) hipHostFree(d.span); }
 	{
 		srh_context::TvSlot &T = c->tv_slot;
 		if (T.stream) { hipStreamSynchronize(T.stream); hipStreamDestroy(T.stream); }
 		if (T.go) hipEventDestroy(T.go);
 		if (T.done) hipEventDestroy(T.done);
-		if (T.d_cnt) hipFree(T.d_cnt);
-		if (T.d_span) hipFree(T.d_span);
-		if (T.tnum) hipFree(T.tnum);
-		pool_give(T.wbuf, T.wbuf_cap*sizeof(double));
-		pool_give(T.cost, T.cost_cap*sizeof(double));
-		pool_give(T.pconst, T.pconst_cap*sizeof(double));
-		pool_give(T.prange, T.prange_cap*sizeof(PixRange));
-		pool_give(T.cflag, T.cflag_cap*sizeof(uint32_t));
-		pool_give(T.lcand, T.lcand_cap*sizeof(uint32_t));
-		pool_give(T.lrowinfo, T.lrowinfo_cap*sizeof(uint32_t));
-		pool_give(T.lcount, T.lcount_cap*sizeof(int32_t));
-		pool_give(T.lmeta, T.lmeta_cap*sizeof(int32_t));
-		if (T.stpl) hipFree(T.stpl);
-		if (T.tileflag) hipFree(T.tileflag);
+		T.d_cnt.release(); T.d_span.release(); T.band.release();
 	}
-	if (c->mrf) hipFree(c->mrf);
-	if (c->mrf_peaks) hipFree(c->mrf_peaks);
+	c->mrf.release(); c->mrf_peaks.release();
 	for (int i = 0; i < SRH_MAX_VIEWS; ++i) if (c->mrf_stream[i]) hipStreamDestroy(c->mrf_stream[i]);
 	if (c->mrf_host) hipHostFree(c->mrf_host);
-	pool_give(c->lcount, c->lcount_cap*sizeof(int32_t));
-	pool_give(c->lcand, c->lcand_cap*sizeof(uint32_t));
-	pool_give(c->lrowinfo, c->lrowinfo_cap*sizeof(uint32_t));
-	pool_give(c->lmeta, c->lmeta_cap*sizeof(int32_t));
-	if (c->mvs_wdesc) hipFree(c->mvs_wdesc);
-	if (c->mvs_nwin) hipFree(c->mvs_nwin);
 	if (c->comm) (void)rccl_comm_destroy(c->comm);
 	if (c->own_stream) hipStreamDestroy(c->own_stream);
 	delete c;
@@ -838,13 +819,13 @@ extern "C" int srh_view_upload(srh_context *c, int slot, int w, int h,
 	if (!v.present || v.w != w || v.h != h) {
 		HIP_TRY(hipStreamSynchronize(c->stream));
 		free_view(v);
-		HIP_TRY(plane_alloc((void **)&v.rgba, n*4));
-		HIP_TRY(hipMalloc((void **)&v.mask, n));
-		HIP_TRY(plane_alloc((void **)&v.gray, n*sizeof(double)));
-		HIP_TRY(plane_alloc((void **)&v.gray_tv, n*sizeof(double)));
-		HIP_TRY(plane_alloc((void **)&v.depth, n*sizeof(double)));
-		HIP_TRY(plane_alloc((void **)&v.edges, 4*n*sizeof(double)));
-		HIP_TRY(hipMalloc((void **)&v.full, full_stat_offset(n) + 16));      // (+ the map's two counters, full_window_kernel)
+		HIP_TRY(v.rgba.alloc(n));
+		HIP_TRY(v.mask.alloc(n));
+		HIP_TRY(v.gray.alloc(n));
+		HIP_TRY(v.gray_tv.alloc(n));
+		HIP_TRY(v.depth.alloc(n));
+		HIP_TRY(v.edges.alloc(4*n));
+		HIP_TRY(v.full.alloc(full_stat_offset(n) + 16));      // (+ the map's two counters, full_window_kernel)
 		v.w = w; v.h = h; v.present = true;
 	}
 	v.cam = *cam;
@@ -928,15 +909,10 @@ extern "C" int srh_view_depth_copy_from_device(srh_context *c, int slot, const v
 
 // ------------------------------------------------------------------ runs
 // bytes of device memory the band buffers hold now (they are re-used or re-allocated by the next run)
-static size_t held_band_bytes(const srh_context *c) {
-	size_t b = c->wbuf_cap*8 + c->cost_cap*8 + c->pconst_cap*8 + c->prange_cap*sizeof(PixRange) + c->lcount_cap*4 + c->lcand_cap*4
-	         + c->lrowinfo_cap*4 + c->lmeta_cap*4 + c->mvs_wdesc_cap*4 + c->mvs_nwin_cap*4 + c->cflag_cap*4;
-	for (const MvsSlot &S : c->mvs_slot)
-		b += S.wbuf_cap*8 + S.cost_cap*8 + S.lcount_cap*4 + S.lcand_cap*4 + S.mvs_wdesc_cap*4 + S.mvs_nwin_cap*4;
-	const srh_context::TvSlot &T = c->tv_slot;
-	b += T.wbuf_cap*8 + T.cost_cap*8 + T.pconst_cap*8 + T.prange_cap*sizeof(PixRange) + T.cflag_cap*4 + T.lcand_cap*4 + T.lrowinfo_cap*4
-	   + T.lcount_cap*4 + T.lmeta_cap*4;
-	for (const ViewHost &v : c->views) if (v.geo5) b += geo5_doubles(v.w, v.h)*sizeof(double);   // (released with the band buffers)
+static size_t held_band_bytes(srh_context *c) {
+	size_t b = c->band.bytes() + c->tv_slot.band.bytes();
+	for (MvsSlot &S : c->mvs_slot) b += S.band.bytes();
+	for (const ViewHost &v : c->views) b += v.geo5.bytes();                 // (released with the band buffers)
 	return b;
 }
 
@@ -960,27 +936,16 @@ static size_t band_budget(srh_context *c) {
 
 static void release_band_buffers(srh_context *c) {
 	pool_flush(c->device);                                        // (out of memory: the pool's blocks go back to the driver first)
-	auto drop = [](auto *&p, size_t &cap) { if (p) (void)hipFree(p); p = nullptr; cap = 0; };
-	drop(c->wbuf, c->wbuf_cap); drop(c->cost, c->cost_cap); drop(c->pconst, c->pconst_cap); drop(c->prange, c->prange_cap);
-	drop(c->lcount, c->lcount_cap); drop(c->lcand, c->lcand_cap); drop(c->lrowinfo, c->lrowinfo_cap); drop(c->lmeta, c->lmeta_cap);
-	drop(c->mvs_wdesc, c->mvs_wdesc_cap); drop(c->mvs_nwin, c->mvs_nwin_cap); drop(c->cflag, c->cflag_cap);
-	drop(c->stpl, c->stpl_cap); drop(c->tileflag, c->tileflag_cap);
-	for (MvsSlot &S : c->mvs_slot) {
-		drop(S.wbuf, S.wbuf_cap); drop(S.cost, S.cost_cap); drop(S.lcount, S.lcount_cap); drop(S.lcand, S.lcand_cap);
-		drop(S.mvs_wdesc, S.mvs_wdesc_cap); drop(S.mvs_nwin, S.mvs_nwin_cap);
-	}
+	c->band.free();
+	for (MvsSlot &S : c->mvs_slot) S.band.free();
 	// (called with everything drained; while the second TwoView pass is being queued the slot holds the FIRST pass's
 	// buffers, which may be in use: with_thinner_bands waits for that stream as well)
-	srh_context::TvSlot &T = c->tv_slot;
-	drop(T.wbuf, T.wbuf_cap); drop(T.cost, T.cost_cap); drop(T.pconst, T.pconst_cap); drop(T.prange, T.prange_cap);
-	drop(T.cflag, T.cflag_cap); drop(T.lcand, T.lcand_cap); drop(T.lrowinfo, T.lrowinfo_cap); drop(T.lcount, T.lcount_cap);
-	drop(T.lmeta, T.lmeta_cap);
-	drop(T.stpl, T.stpl_cap); drop(T.tileflag, T.tileflag_cap);
+	c->tv_slot.band.free();
 	// the geodesic_dma_kernel's second copy of the edge / tap planes (42 B per pixel and view, made on first use): memory an
 	// out-of-memory retry must be able to reclaim -- the register-staged kernel needs no such copy and serves the view until
 	// it is uploaded again
 	for (ViewHost &v : c->views)
-		if (v.geo5) { (void)hipFree(v.geo5); v.geo5 = nullptr; v.geo5_valid = false; v.geo5_denied = true; }
+		if (v.geo5) { v.geo5.free(); v.geo5_valid = false; v.geo5_denied = true; }
 }
 
 // Run `body`; when it fails because a band buffer could not be allocated, wait for everything in flight, release the
@@ -1081,7 +1046,7 @@ static int fetch_counters(srh_context *c, int used_dense) {
 	return SRH_OK;
 }
 
-// support windows of rows [by, by+nr) of view `ref` into c->wbuf
+// support windows of rows [by, by+nr) of view `ref` into c->band.wbuf
 static void run_weights(srh_context *c, int ref, int W, const srh_params &p, int by, int nr, size_t wstride,
                         double *pconst = nullptr, bool wimg = false) {
 	if (p.weight_kind == SRH_WEIGHT_GEODESIC && !c->force_generic && wimg && c->geodma && p.window_radius == 5 && !c->views[ref].geo5_denied) {
@@ -1089,7 +1054,7 @@ static void run_weights(srh_context *c, int ref, int W, const srh_params &p, int
 		ViewHost &v = c->views[ref];
 		bool ok = true;
 		if (!v.geo5) {
-			if (plane_alloc((void **)&v.geo5, geo5_doubles(v.w, v.h)*sizeof(double)) != hipSuccess) { (void)hipGetLastError(); v.geo5 = nullptr; ok = false; }   // (no room: the register-staged kernel needs no second copy)
+			if (v.geo5.alloc(geo5_doubles(v.w, v.h)) != hipSuccess) ok = false;   // (no room: the register-staged kernel needs no second copy)
 			v.geo5_valid = false;
 		}
 		if (ok && !v.geo5_valid) {
@@ -1099,19 +1064,19 @@ static void run_weights(srh_context *c, int ref, int W, const srh_params &p, int
 		}
 		if (ok) {
 			Scope s(c, "geodesic_dma_kernel");
-			if (launch_geodesic_dma(c->stream, c->d_views, ref, W, v.geo5, p, by, nr, c->wbuf, pconst, c->num_cus)) return;
+			if (launch_geodesic_dma(c->stream, c->d_views, ref, W, v.geo5, p, by, nr, c->band.wbuf, pconst, c->num_cus)) return;
 		}
 	}
 	if (p.weight_kind == SRH_WEIGHT_GEODESIC && !c->force_generic) {
 		Scope s(c, "geodesic_reg_kernel");
-		if (launch_geodesic_reg(c->stream, c->d_views, ref, W, c->views[ref].edges, p, by, nr, c->wbuf, wstride, pconst, wimg)) return;
+		if (launch_geodesic_reg(c->stream, c->d_views, ref, W, c->views[ref].edges, p, by, nr, c->band.wbuf, wstride, pconst, wimg)) return;
 	}
 	if (p.weight_kind == SRH_WEIGHT_ADAPTIVE && !c->force_generic) {
 		Scope s(c, "adaptive_reg_kernel");
-		if (launch_adaptive_reg(c->stream, c->d_views, ref, W, p, by, nr, c->wbuf, wstride, pconst, wimg)) return;
+		if (launch_adaptive_reg(c->stream, c->d_views, ref, W, p, by, nr, c->band.wbuf, wstride, pconst, wimg)) return;
 	}
 	Scope s(c, "weights_kernel");
-	launch_weights(c->stream, c->d_views, ref, W, p, by, nr, c->wbuf, wstride, pconst, wimg);
+	launch_weights(c->stream, c->d_views, ref, W, p, by, nr, c->band.wbuf, wstride, pconst, wimg);
 }
 
 // Can every epipolar curve of `a` in `b` stay on its own image row?  Undistorted, non-refractive
@@ -1231,20 +1196,20 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 	if (dense && c->use_fused && (c->arith == 0 || c->arith == 3) && p->num_depth_levels <= SRH_FUSED_MAXC &&
 	    fx_bx*p->image_scale*fabs(1.0/p->min_depth - 1.0/p->max_depth) + 1.0 <= (double)SRH_FUSED_MAXC) {
 		HIP_TRY(hipMemsetAsync(c->d_cnt, 0, sizeof(Counters), c->stream));
-		if ((rc = ensure(c->tnum, c->tnum_cap, (size_t)p->num_depth_levels))) return rc;
+		if ((rc = c->band.tnum.ensure((size_t)p->num_depth_levels))) return rc;
 		{ Scope s(c, "pinhole_label_table_kernel");
-		  launch_pinhole_label_table(c->stream, c->d_views, ref, *p, false, c->tnum); }
+		  launch_pinhole_label_table(c->stream, c->d_views, ref, *p, false, c->band.tnum); }
 		size_t rows = budget / ((size_t)T*sizeof(double)*(size_t)W);
 		if (rows < 1) rows = 1;
 		if (rows > (size_t)(y1 - y0)) rows = (size_t)(y1 - y0);
-		if ((rc = ensure(c->wbuf, c->wbuf_cap, wbuf_doubles(W, (int)rows, T)))) return rc;
+		if ((rc = c->band.wbuf.ensure(wbuf_doubles(W, (int)rows, T)))) return rc;
 		bool launched = true;
 		for (int by = y0; by < y1 && launched; by += (int)rows) {
 			if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
 			const int nr = std::min((int)rows, y1 - by);
 			run_weights(c, ref, W, *p, by, nr, SRH_WTILE);
 			Scope s(c, "twoview_fused_kernel");
-			launched = launch_twoview_fused(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->wbuf, c->tnum, c->d_cnt);
+			launched = launch_twoview_fused(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, c->band.tnum, c->d_cnt);
 		}
 		HIP_TRY(hipGetLastError());
 		if (launched) {
@@ -1283,7 +1248,7 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 		// visits every point, takes such a run)
 		if (!dense && !c->force_walk && R <= 5 && W < 65536 && H < 65536 && p->wta_margin >= 0) {
 			const size_t npix = (size_t)(y1 - y0)*W;
-			if ((rc = ensure(c->lcount, c->lcount_cap, npix))) return rc;
+			if ((rc = c->band.lcount.ensure(npix))) return rc;
 			ViewHost &O = c->views[oth];
 			if (O.full_r != R) {
 				Scope s(c, "full_window_kernel");
@@ -1293,9 +1258,9 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 				O.full_r = R;
 			}
 			// the label-only part of pointFromDepth, once per pass instead of once per pixel and label
-			if ((rc = ensure(c->tnum, c->tnum_cap, (size_t)p->num_depth_levels))) return rc;
+			if ((rc = c->band.tnum.ensure((size_t)p->num_depth_levels))) return rc;
 			{ Scope s(c, "label_plane_table_kernel");
-			  launch_label_plane_table(c->stream, c->d_views, ref, *p, false, c->tnum); }
+			  launch_label_plane_table(c->stream, c->d_views, ref, *p, false, c->band.tnum); }
 			// list capacity: the longest list seen so far on this context (hint); the FIRST time a guess from the geometry
 			// (estimate_list_capacity: a few dozen curves' coarse polylines projected on the host -- round 5 ran a counting pass
 			// there, twoview_count_kernel, 10 ms of a C5 pair's first call, and then sized the slots too tightly, so that the
@@ -1306,7 +1271,7 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 			if (cmax <= 0 && c->list_count_pass) {
 				HIP_TRY(hipMemsetAsync(c->d_span, 0, sizeof(int), c->stream));
 				{ Scope s(c, "twoview_count_kernel");
-				  launch_twoview_count(c->stream, c->d_views, ref, oth, W, *p, y0, y1 - y0, c->lcount, c->d_cnt, c->d_span, c->tnum); }
+				  launch_twoview_count(c->stream, c->d_views, ref, oth, W, *p, y0, y1 - y0, c->band.lcount, c->d_cnt, c->d_span, c->band.tnum); }
 				int maxc = 0;
 				HIP_TRY(hipMemcpyAsync(&maxc, c->d_span, sizeof(int), hipMemcpyDeviceToHost, c->stream));
 				HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1329,25 +1294,25 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 				size_t lrows = budget / (per_px*(size_t)W);
 				if (lrows < 1) lrows = 1;
 				if (lrows > (size_t)(y1 - y0)) lrows = (size_t)(y1 - y0);
-				if ((rc = ensure(c->wbuf, c->wbuf_cap, rows_mode ? wimg_doubles(W, (int)lrows, p->window_radius) : wbuf_doubles(W, (int)lrows, T)))) return rc;
+				if ((rc = c->band.wbuf.ensure(rows_mode ? wimg_doubles(W, (int)lrows, p->window_radius) : wbuf_doubles(W, (int)lrows, T)))) return rc;
 				// row runs: lists and row tables are tiled per 64 pixels, cost slots per 32-pixel tile of a row
 				const size_t px64 = (lrows*W + 63) & ~(size_t)63, px32 = lrows*(size_t)((W + 7)/8)*8;        /* (cost slots: tiles of 8 pixels) */
-				if ((rc = ensure(c->cost, c->cost_cap, (rows_mode ? px32 : lrows*W)*(size_t)ccap))) return rc;
-				if ((rc = ensure(c->lcand, c->lcand_cap, (rows_mode ? px64 : lrows*W)*(size_t)cmax))) return rc;
+				if ((rc = c->band.cost.ensure((rows_mode ? px32 : lrows*W)*(size_t)ccap))) return rc;
+				if ((rc = c->band.lcand.ensure((rows_mode ? px64 : lrows*W)*(size_t)cmax))) return rc;
 				const bool rows_cert = rows_mode && cert_ok;
 				// the row-run cost kernel takes the pixels' constants (meanL, totalWeight, sum2, 1/totalWeight, SA) from the weights
 				// kernel, which has the window in registers anyway, instead of making them on one lane in eight per tile
 				const bool rows_pc = rows_mode;
-				if (rows_pc && (rc = ensure(c->pconst, c->pconst_cap, (lrows*(size_t)W + SRH_WTILE)*SRH_PC))) return rc;
+				if (rows_pc && (rc = c->band.pconst.ensure((lrows*(size_t)W + SRH_WTILE)*SRH_PC))) return rc;
 				if (rows_mode) {
-					if ((rc = ensure(c->lrowinfo, c->lrowinfo_cap, px64*(size_t)SRH_ROWS_NR))) return rc;
-					if ((rc = ensure(c->lmeta, c->lmeta_cap, lrows*W))) return rc;
-					if (rows_cert && (rc = ensure(c->cflag, c->cflag_cap, lrows*W + 1))) return rc;
+					if ((rc = c->band.lrowinfo.ensure(px64*(size_t)SRH_ROWS_NR))) return rc;
+					if ((rc = c->band.lmeta.ensure(lrows*W))) return rc;
+					if (rows_cert && (rc = c->band.cflag.ensure(lrows*W + 1))) return rc;
 					if (rows_cert) {
 						// NaN-bordered planes of both views: the general cost of the certified redo reads them without bound tests
 						for (int k = 0; k < 2; ++k) {
 							ViewHost &v = c->views[k == 0 ? ref : oth];
-							if (!v.tvp) HIP_TRY(plane_alloc((void **)&v.tvp, padded_size(v.w, v.h)*sizeof(double)));
+							if (!v.tvp) HIP_TRY(v.tvp.alloc(padded_size(v.w, v.h)));
 							if (!v.tvp_valid) {
 								Scope s(c, "padded_plane_kernel");
 								launch_padded_plane(c->stream, v.gray_tv, v.w, v.h, v.tvp);
@@ -1359,7 +1324,7 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 				for (int by = y0; by < y1; by += (int)lrows) {
 					if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
 					const int nr = std::min((int)lrows, y1 - by);
-					int32_t *cnt_band = c->lcount + (size_t)(by - y0)*W;
+					int32_t *cnt_band = c->band.lcount + (size_t)(by - y0)*W;
 					if (rows_mode) {
 						// The list kernel does not need the support windows, and its last waves drain for long (a wave walks
 						// its 64 curves for ~2 ms): the windows are computed on a side stream queued behind it -- the geodesic
@@ -1371,48 +1336,48 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 						}
 						HIP_TRY(hipEventRecord(c->side_go, c->stream));             // the window buffer's last readers are done by then
 						{ Scope s(c, "twoview_rows_list_kernel");
-						  launch_twoview_rows_list(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->lcand, cmax,
-						                           cnt_band, c->lrowinfo, c->lmeta, smax, c->d_cnt, c->d_span, c->tnum); }
+						  launch_twoview_rows_list(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.lcand, cmax,
+						                           cnt_band, c->band.lrowinfo, c->band.lmeta, smax, c->d_cnt, c->d_span, c->band.tnum); }
 						if (c->side_weights) {
 							HIP_TRY(hipStreamWaitEvent(c->side_stream, c->side_go, 0));
 							std::swap(c->stream, c->side_stream);
-							run_weights(c, ref, W, *p, by, nr, SRH_WTILE, rows_pc ? c->pconst : nullptr, true);
+							run_weights(c, ref, W, *p, by, nr, SRH_WTILE, rows_pc ? c->band.pconst : nullptr, true);
 							std::swap(c->stream, c->side_stream);
 							HIP_TRY(hipEventRecord(c->side_done, c->side_stream));
 							HIP_TRY(hipStreamWaitEvent(c->stream, c->side_done, 0));
-						} else run_weights(c, ref, W, *p, by, nr, SRH_WTILE, rows_pc ? c->pconst : nullptr, true);
-						if (rows_cert) HIP_TRY(hipMemsetAsync(c->cflag, 0, sizeof(uint32_t), c->stream));
+						} else run_weights(c, ref, W, *p, by, nr, SRH_WTILE, rows_pc ? c->band.pconst : nullptr, true);
+						if (rows_cert) HIP_TRY(hipMemsetAsync(c->band.cflag, 0, sizeof(uint32_t), c->stream));
 						HIP_TRY(hipMemsetAsync(&c->d_cnt->strip_ticket, 0, 2*sizeof(unsigned int), c->stream));   // the cost kernel's waves draw their tiles from it
 						{ Scope s(c, "twoview_rows_cost_kernel");
-						  launch_twoview_rows_cost(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->wbuf, O.full,
-						                           c->lrowinfo, c->lmeta, c->cost, smax, c->d_cnt, rows_cert ? (c->cert_form == 1 ? 5 : 3) : 0,
-						                           rows_pc ? c->pconst : nullptr, rows_cert && c->rows_masked ? O.tvp : nullptr, c->num_cus,
+						  launch_twoview_rows_cost(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, O.full,
+						                           c->band.lrowinfo, c->band.lmeta, c->band.cost, smax, c->d_cnt, rows_cert ? (c->cert_form == 1 ? 5 : 3) : 0,
+						                           rows_pc ? c->band.pconst : nullptr, rows_cert && c->rows_masked ? O.tvp : nullptr, c->num_cus,
 						                           c->rows_masked == 1 ? (const uint32_t *)(O.full + full_stat_offset((size_t)O.w*O.h)) : nullptr); }
 						{ Scope s(c, "twoview_rows_scan_kernel");
-						  launch_twoview_rows_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, cnt_band, c->lcand, cmax,
-						                           c->lrowinfo, c->lmeta, c->cost, smax, rows_cert ? c->cflag : nullptr, -1, c->d_cnt); }
+						  launch_twoview_rows_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, cnt_band, c->band.lcand, cmax,
+						                           c->band.lrowinfo, c->band.lmeta, c->band.cost, smax, rows_cert ? c->band.cflag : nullptr, -1, c->d_cnt); }
 						if (rows_cert) {
 							// certified arithmetic: the flagged pixels once more in the reference's arithmetic, launched for a capacity
 							// (a list cut by a too small capacity is harmless here: the pass is repeated anyway)
 							const int cap = redo_capacity((size_t)nr*W);
 							{ Scope s(c, "twoview_rows_refill_kernel");
-							  launch_twoview_rows_refill(c->stream, W, O.w, *p, by, c->cflag, cap, c->wbuf, c->views[ref].tvp, O.tvp,
-							                             c->lrowinfo, c->lmeta, c->cost, smax, c->d_cnt); }
+							  launch_twoview_rows_refill(c->stream, W, O.w, *p, by, c->band.cflag, cap, c->band.wbuf, c->views[ref].tvp, O.tvp,
+							                             c->band.lrowinfo, c->band.lmeta, c->band.cost, smax, c->d_cnt); }
 							Scope s(c, "twoview_rows_rescan_kernel");
-							launch_twoview_rows_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, cnt_band, c->lcand, cmax,
-							                         c->lrowinfo, c->lmeta, c->cost, smax, c->cflag, cap, c->d_cnt);
+							launch_twoview_rows_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, cnt_band, c->band.lcand, cmax,
+							                         c->band.lrowinfo, c->band.lmeta, c->band.cost, smax, c->band.cflag, cap, c->d_cnt);
 						}
 						continue;
 					}
 					run_weights(c, ref, W, *p, by, nr, SRH_WTILE);
 					{ Scope s(c, "twoview_list_kernel");
-					  launch_twoview_list(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->lcand, cmax,
-					                      cnt_band, c->d_cnt, c->d_span, c->tnum); }
+					  launch_twoview_list(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.lcand, cmax,
+					                      cnt_band, c->d_cnt, c->d_span, c->band.tnum); }
 					{ Scope s(c, "twoview_list_cost_kernel");
-					  launch_twoview_list_cost(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->wbuf, O.full,
-					                           cnt_band, c->lcand, c->cost, cmax, c->d_cnt); }
+					  launch_twoview_list_cost(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, O.full,
+					                           cnt_band, c->band.lcand, c->band.cost, cmax, c->d_cnt); }
 					{ Scope s(c, "twoview_list_scan_kernel");
-					  launch_twoview_list_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, cnt_band, c->lcand, c->cost, cmax); }
+					  launch_twoview_list_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, cnt_band, c->band.lcand, c->band.cost, cmax); }
 				}
 				if (c->defer && attempt == 0 && pass == 0 && rows_mode &&
 				    ((c->list_cmax_hint > 0 && c->list_smax_hint > 0 && c->views[ref].list_mode[oth] == 1) ||
@@ -1482,14 +1447,14 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 		}
 		const bool tscan = dense && c->tscan != 0;
 		if (dense) {
-			if ((rc = ensure(c->tnum, c->tnum_cap, (size_t)p->num_depth_levels + 8))) return rc;   // (+ 8: the template scan reads the table in whole eights)
+			if ((rc = c->band.tnum.ensure((size_t)p->num_depth_levels + 8))) return rc;   // (+ 8: the template scan reads the table in whole eights)
 			{ Scope s(c, "pinhole_label_table_kernel");
-			  launch_pinhole_label_table(c->stream, c->d_views, ref, *p, false, c->tnum); }
+			  launch_pinhole_label_table(c->stream, c->d_views, ref, *p, false, c->band.tnum); }
 			if (tscan) {
 				// the pass's candidate template: the reference's walk at one pixel (srh_dense.hip, "template scan")
-				if ((rc = ensure(c->stpl, c->stpl_cap, scan_template_bytes()))) return rc;
+				if ((rc = c->band.stpl.ensure(scan_template_bytes()))) return rc;
 				Scope s(c, "twoview_template_kernel");
-				launch_scan_template(c->stream, c->d_views, ref, oth, *p, y0, y1 - y0, c->tnum, c->stpl);
+				launch_scan_template(c->stream, c->d_views, ref, oth, *p, y0, y1 - y0, c->band.tnum, c->band.stpl);
 			}
 		}
 		size_t rows = 0;
@@ -1505,17 +1470,17 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 		}
 		const bool wimg = strip;                                       // the band's windows in the LDS image's layout
 		const size_t wstride = SRH_WTILE;
-		if ((rc = ensure(c->wbuf, c->wbuf_cap, wimg ? wimg_doubles(W, (int)rows, R) : wbuf_doubles(W, (int)rows, T)))) return rc;
-		if (dense && (rc = ensure(c->cost, c->cost_cap, rows*(size_t)((W + 31)/32)*32*(size_t)cstride))) return rc;   // 32-pixel tiles
+		if ((rc = c->band.wbuf.ensure(wimg ? wimg_doubles(W, (int)rows, R) : wbuf_doubles(W, (int)rows, T)))) return rc;
+		if (dense && (rc = c->band.cost.ensure(rows*(size_t)((W + 31)/32)*32*(size_t)cstride))) return rc;   // 32-pixel tiles
 		// (+ one tile of slack: the strip kernel copies whole 32-pixel pieces of these rows)
-		if (dense && (rc = ensure(c->pconst, c->pconst_cap, (rows*(size_t)W + SRH_WTILE)*SRH_PC))) return rc;
+		if (dense && (rc = c->band.pconst.ensure((rows*(size_t)W + SRH_WTILE)*SRH_PC))) return rc;
 		int lanes = 8;
-		if (dense && (rc = ensure(c->prange, c->prange_cap, rows*(size_t)W + SRH_WTILE))) return rc;
-		if (tscan && (rc = ensure(c->tileflag, c->tileflag_cap, rows*(size_t)((W + 63)/64) + 1))) return rc;
+		if (dense && (rc = c->band.prange.ensure(rows*(size_t)W + SRH_WTILE))) return rc;
+		if (tscan && (rc = c->band.tileflag.ensure(rows*(size_t)((W + 63)/64) + 1))) return rc;
 		const bool cert = dense && cert_ok;
 		// (the strip kernel's certified form: 5 = one sweep over the window, 3 = the reference's two sweeps fused; option "cert_form")
 		const int cost_arith = c->arith == 3 ? (cert ? (c->cert_form == 1 ? 5 : 3) : 0) : c->arith;
-		if (cert && (rc = ensure(c->cflag, c->cflag_cap, rows*(size_t)W + 1))) return rc;
+		if (cert && (rc = c->band.cflag.ensure(rows*(size_t)W + 1))) return rc;
 		const bool planes = dense && (R == 5 || R == 2);
 		if (strip) lanes = strip_block_lanes(cstride, c->strip == 1 ? 0 : c->strip);
 		if (planes) {
@@ -1523,7 +1488,7 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 			// certified redo on either dense path)
 			for (int k = 0; k < 2; ++k) {
 				ViewHost &v = c->views[k == 0 ? ref : oth];
-				if (!v.tvp) HIP_TRY(plane_alloc((void **)&v.tvp, padded_size(v.w, v.h)*sizeof(double)));
+				if (!v.tvp) HIP_TRY(v.tvp.alloc(padded_size(v.w, v.h)));
 				if (!v.tvp_valid) {
 					Scope s(c, "padded_plane_kernel");
 					launch_padded_plane(c->stream, v.gray_tv, v.w, v.h, v.tvp);
@@ -1534,7 +1499,7 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 		if (strip) {
 			// zero-bordered "window fully usable" plane of the other view
 			ViewHost &O = c->views[oth];
-			if (!O.fullp) HIP_TRY(hipMalloc((void **)&O.fullp, padded_size(O.w, O.h)));
+			if (!O.fullp) HIP_TRY(O.fullp.alloc(padded_size(O.w, O.h)));
 			if (O.fullp_r != R) {
 				Scope s(c, "padded_full_kernel");
 				launch_padded_full(c->stream, O.gray_tv, O.w, O.h, R, O.fullp);
@@ -1545,10 +1510,10 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 		for (int by = y0; by < y1; by += (int)rows) {
 			if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
 			const int nr = std::min((int)rows, y1 - by);
-			run_weights(c, ref, W, *p, by, nr, wstride, dense ? c->pconst : nullptr, wimg);
+			run_weights(c, ref, W, *p, by, nr, wstride, dense ? c->band.pconst : nullptr, wimg);
 			if (dense) {
 				Scope s(c, "pixel_range_kernel");
-				launch_pixel_range(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->tnum, cstride, c->prange);
+				launch_pixel_range(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.tnum, cstride, c->band.prange);
 			}
 			if (dense) {
 				// the band's cost rows under one arithmetic: strip kernel or one workgroup per tile, then the left-out columns
@@ -1556,24 +1521,24 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 					if (strip) {
 						HIP_TRY(hipMemsetAsync(&c->d_cnt->strip_ticket, 0, 2*sizeof(unsigned int), c->stream));
 						{ Scope s(c, "twoview_strip_cost_kernel");
-						  launch_twoview_strip_cost(c->stream, c->d_views, ref, oth, W, H, *p, by, nr, c->wbuf, c->pconst, c->prange,
-						                            c->views[ref].tvp, c->views[oth].tvp, c->views[oth].fullp, c->cost, cstride,
+						  launch_twoview_strip_cost(c->stream, c->d_views, ref, oth, W, H, *p, by, nr, c->band.wbuf, c->band.pconst, c->band.prange,
+						                            c->views[ref].tvp, c->views[oth].tvp, c->views[oth].fullp, c->band.cost, cstride,
 						                            c->d_cnt, arith, c->num_cus, lanes, c->diag && c->diag->raw); }
 						Scope s(c, "twoview_lazy_fill_kernel");
-						launch_twoview_lazy_fill(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->prange, c->wbuf, wstride,
-						                         c->views[ref].tvp, c->views[oth].tvp, true, lanes, lanes == 8, c->cost, cstride, c->d_cnt);
+						launch_twoview_lazy_fill(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.prange, c->band.wbuf, wstride,
+						                         c->views[ref].tvp, c->views[oth].tvp, true, lanes, lanes == 8, c->band.cost, cstride, c->d_cnt);
 					} else {
 						{ Scope s(c, "twoview_dense_cost_kernel");
 						  if (arith == 2)
-							launch_twoview_dense_cost_f32(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->wbuf, wstride,
-							                              c->tnum, c->cost, cstride, c->d_cnt, c->pconst, c->f32_form);
+							launch_twoview_dense_cost_f32(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, wstride,
+							                              c->band.tnum, c->band.cost, cstride, c->d_cnt, c->band.pconst, c->f32_form);
 						  else
-							launch_twoview_dense_cost(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->wbuf, wstride,
-							                          c->tnum, c->cost, cstride, c->d_cnt, c->pconst, arith, c->prange); }
+							launch_twoview_dense_cost(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, wstride,
+							                          c->band.tnum, c->band.cost, cstride, c->d_cnt, c->band.pconst, arith, c->band.prange); }
 						Scope s(c, "twoview_lazy_fill_kernel");
-						launch_twoview_lazy_fill(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->prange, c->wbuf, wstride,
+						launch_twoview_lazy_fill(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.prange, c->band.wbuf, wstride,
 						                         planes ? c->views[ref].tvp : nullptr, planes ? c->views[oth].tvp : nullptr, false, 8,
-						                         arith != 5, c->cost, cstride, c->d_cnt);   // (the one-pass form leaves no column out)
+						                         arith != 5, c->band.cost, cstride, c->d_cnt);   // (the one-pass form leaves no column out)
 					}
 					return SRH_OK;
 				};
@@ -1586,34 +1551,34 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 					if (by != y0 || nr != y1 - y0) return fail(SRH_E_UNSUPPORTED, "cost rows: the rows asked for do not fit one band (%d of %d)", nr, y1 - y0);
 					if (dg.cost) {
 						if (dg.cost_doubles < nd) return fail(SRH_E_INVALID, "cost rows: buffer of %zu doubles, %zu needed", dg.cost_doubles, nd);
-						HIP_TRY(hipMemsetAsync(c->cost, 0xff, nd*sizeof(double), c->stream));   // (never-written entries read as a NaN with payload -1)
+						HIP_TRY(hipMemsetAsync(c->band.cost, 0xff, nd*sizeof(double), c->stream));   // (never-written entries read as a NaN with payload -1)
 						if ((rc = cost_pass(dg.form))) return rc;
-						HIP_TRY(hipMemcpyAsync(dg.cost, c->cost, nd*sizeof(double), hipMemcpyDeviceToHost, c->stream));
-						if (dg.range) HIP_TRY(hipMemcpyAsync(dg.range, c->prange, (size_t)nr*W*sizeof(PixRange), hipMemcpyDeviceToHost, c->stream));
+						HIP_TRY(hipMemcpyAsync(dg.cost, c->band.cost, nd*sizeof(double), hipMemcpyDeviceToHost, c->stream));
+						if (dg.range) HIP_TRY(hipMemcpyAsync(dg.range, c->band.prange, (size_t)nr*W*sizeof(PixRange), hipMemcpyDeviceToHost, c->stream));
 						HIP_TRY(hipStreamSynchronize(c->stream));
 					}
 					dg.done = true;
 					return SRH_OK;
 				}
-				if (cert) HIP_TRY(hipMemsetAsync(c->cflag, 0, sizeof(uint32_t), c->stream));
+				if (cert) HIP_TRY(hipMemsetAsync(c->band.cflag, 0, sizeof(uint32_t), c->stream));
 				if ((rc = cost_pass(cost_arith))) return rc;
 				{ Scope s(c, "twoview_scan_kernel");
-				  launch_twoview_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->tnum, c->cost, cstride, c->d_cnt, c->prange,
-				                      cert ? c->cflag : nullptr, -1, cert && strip ? c->pconst : nullptr, tscan ? c->stpl : nullptr, c->tileflag, c->num_cus); }
+				  launch_twoview_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.tnum, c->band.cost, cstride, c->d_cnt, c->band.prange,
+				                      cert ? c->band.cflag : nullptr, -1, cert && strip ? c->band.pconst : nullptr, tscan ? c->band.stpl : nullptr, c->band.tileflag, c->num_cus); }
 				if (cert) {
 					// the pixels whose decisions the bound does not cover, in the reference's arithmetic: their cost rows are
 					// refilled and they are scanned again -- launched for a capacity, the count stays on the device
 					const int cap = redo_capacity((size_t)nr*W);
 					{ Scope s(c, "twoview_refill_kernel");
-					  launch_twoview_refill(c->stream, W, *p, by, c->prange, c->cflag, cap, c->wbuf, wimg, c->views[ref].tvp,
-					                        c->views[oth].tvp, c->cost, cstride, c->d_cnt); }
+					  launch_twoview_refill(c->stream, W, *p, by, c->band.prange, c->band.cflag, cap, c->band.wbuf, wimg, c->views[ref].tvp,
+					                        c->views[oth].tvp, c->band.cost, cstride, c->d_cnt); }
 					Scope s(c, "twoview_rescan_kernel");
-					launch_twoview_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->tnum, c->cost, cstride, c->d_cnt, c->prange,
-					                    c->cflag, cap);
+					launch_twoview_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.tnum, c->band.cost, cstride, c->d_cnt, c->band.prange,
+					                    c->band.cflag, cap);
 				}
 			} else {
 				Scope s(c, "twoview_generic_kernel");
-				launch_twoview_generic(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->wbuf, wstride, c->d_cnt);
+				launch_twoview_generic(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, wstride, c->d_cnt);
 			}
 		}
 		HIP_TRY(hipGetLastError());
@@ -1670,8 +1635,8 @@ extern "C" int srh_twoview_cost_rows(srh_context *c, int ref, int oth, const srh
 extern "C" int srh_debug_exp(srh_context *c, const double *x, int n, double *kernel_out, double *library_out) {
 	if (!c || !x || !kernel_out || !library_out || n < 1) return fail(SRH_E_INVALID, "null argument");
 	HIP_TRY(hipSetDevice(c->device));
-	double *d = nullptr;
-	HIP_TRY(hipMalloc((void **)&d, (size_t)n*3*sizeof(double)));
+	DevBuf<double> d;
+	HIP_TRY(d.alloc((size_t)n*3));
 	hipError_t e = hipMemcpyAsync(d, x, (size_t)n*sizeof(double), hipMemcpyHostToDevice, c->stream);
 	if (e == hipSuccess) {
 		launch_geo_exp_probe(c->stream, d, n, d + n, d + 2*(size_t)n);
@@ -1679,7 +1644,7 @@ extern "C" int srh_debug_exp(srh_context *c, const double *x, int n, double *ker
 	}
 	if (e == hipSuccess) e = hipMemcpyAsync(library_out, d + 2*(size_t)n, (size_t)n*sizeof(double), hipMemcpyDeviceToHost, c->stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-	(void)hipFree(d);
+	d.free();
 	if (e != hipSuccess) return fail(SRH_E_DEVICE, "srh_debug_exp: %s", hipGetErrorString(e));
 	return SRH_OK;
 }
@@ -1701,19 +1666,8 @@ extern "C" int srh_twoview_cross_check(srh_context *c, int left, int right, cons
 static void tv_slot_swap(srh_context *c) {
 	srh_context::TvSlot &T = c->tv_slot;
 	std::swap(c->stream, T.stream);
+	std::swap(c->band, T.band);
 	std::swap(c->d_cnt, T.d_cnt); std::swap(c->d_span, T.d_span);
-	std::swap(c->wbuf, T.wbuf); std::swap(c->wbuf_cap, T.wbuf_cap);
-	std::swap(c->cost, T.cost); std::swap(c->cost_cap, T.cost_cap);
-	std::swap(c->tnum, T.tnum); std::swap(c->tnum_cap, T.tnum_cap);
-	std::swap(c->pconst, T.pconst); std::swap(c->pconst_cap, T.pconst_cap);
-	std::swap(c->prange, T.prange); std::swap(c->prange_cap, T.prange_cap);
-	std::swap(c->cflag, T.cflag); std::swap(c->cflag_cap, T.cflag_cap);
-	std::swap(c->lcand, T.lcand); std::swap(c->lcand_cap, T.lcand_cap);
-	std::swap(c->lrowinfo, T.lrowinfo); std::swap(c->lrowinfo_cap, T.lrowinfo_cap);
-	std::swap(c->lcount, T.lcount); std::swap(c->lcount_cap, T.lcount_cap);
-	std::swap(c->lmeta, T.lmeta); std::swap(c->lmeta_cap, T.lmeta_cap);
-	std::swap(c->stpl, T.stpl); std::swap(c->stpl_cap, T.stpl_cap);
-	std::swap(c->tileflag, T.tileflag); std::swap(c->tileflag_cap, T.tileflag_cap);
 }
 
 static bool tv_pass_stands(const srh_context::TvDefer &d) {
@@ -1742,14 +1696,14 @@ extern "C" int srh_twoview_compute(srh_context *c, int left, int right, const sr
 			HIP_TRY(hipStreamCreateWithFlags(&T.stream, hipStreamNonBlocking));
 			HIP_TRY(hipEventCreateWithFlags(&T.go, hipEventDisableTiming));
 			HIP_TRY(hipEventCreateWithFlags(&T.done, hipEventDisableTiming));
-			HIP_TRY(hipMalloc((void **)&T.d_cnt, sizeof(Counters)));
-			HIP_TRY(hipMalloc((void **)&T.d_span, 4*sizeof(int)));
+			HIP_TRY(T.d_cnt.alloc(1));
+			HIP_TRY(T.d_span.alloc(4));
 		}
 		// the NaN-bordered planes both passes read (twoview_wta_run makes them on demand, on its own stream) exist at `go`
 		if (p->window_radius == 5 || p->window_radius == 2)
 			for (int k = 0; k < 2; ++k) {
 				ViewHost &v = c->views[k == 0 ? left : right];
-				if (!v.tvp) HIP_TRY(plane_alloc((void **)&v.tvp, padded_size(v.w, v.h)*sizeof(double)));
+				if (!v.tvp) HIP_TRY(v.tvp.alloc(padded_size(v.w, v.h)));
 				if (!v.tvp_valid) {
 					Scope s(c, "padded_plane_kernel");
 					launch_padded_plane(c->stream, v.gray_tv, v.w, v.h, v.tvp);
@@ -1879,11 +1833,10 @@ static int ensure_act(srh_context *c, ViewHost &v) {
 	}
 	v.act_row[h] = (uint32_t)act.size();
 	if (!act.empty()) {
-		if (v.act_cap < act.size()) {
+		if (v.act.n < act.size()) {
 			// (other streams may still read the old list: estimates of this view queued before the re-upload were settled by it)
-			if (v.act) { HIP_TRY(hipFree(v.act)); v.act = nullptr; v.act_cap = 0; }
-			HIP_TRY(hipMalloc((void **)&v.act, (size_t)w*h*sizeof(uint32_t)));
-			v.act_cap = (size_t)w*h;
+			v.act.free();
+			HIP_TRY(v.act.alloc((size_t)w*h));
 		}
 		HIP_TRY(hipMemcpyAsync(v.act, act.data(), act.size()*sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
 		HIP_TRY(hipStreamSynchronize(c->stream));                  // once per upload: either slot's stream may read it next
@@ -1909,9 +1862,9 @@ static int mvs_list_launch(srh_context *c, int view, const int32_t *neigh, int n
 	bool neigh_pinhole = true;                                  // (certified label projections: plain pinhole neighbours only)
 	for (int i = 0; i < nneigh; ++i) { const srh_camera &nc = c->views[neigh[i]].cam; if (nc.is_refractive || nc.is_distorted) neigh_pinhole = false; }
 	if (table) {
-		if ((rc = ensure(c->tnum, c->tnum_cap, (size_t)p->num_depth_levels))) return rc;
+		if ((rc = c->band.tnum.ensure((size_t)p->num_depth_levels))) return rc;
 		Scope s(c, "pinhole_label_table_kernel");
-		launch_pinhole_label_table(c->stream, c->d_views, view, *p, true, c->tnum);
+		launch_pinhole_label_table(c->stream, c->d_views, view, *p, true, c->band.tnum);
 	}
 		HIP_TRY(hipMemsetAsync(c->d_cnt, 0, sizeof(Counters), c->stream));
 		HIP_TRY(hipMemsetAsync(c->d_span, 0, 4*sizeof(int), c->stream));
@@ -1933,17 +1886,17 @@ static int mvs_list_launch(srh_context *c, int view, const int32_t *neigh, int n
 			const size_t na = (size_t)A.act_row[by + nr] - A.act_row[by];
 			lunits = std::max(lunits, ((na + 127) & ~(size_t)127)*(size_t)nneigh);
 		}
-		if ((rc = ensure(c->wbuf, c->wbuf_cap, wbuf_doubles(W, (int)lrows, T)))) return rc;
-		if ((rc = ensure(c->cost, c->cost_cap, units*2 + (peaks_dev ? units*(size_t)p->top_k*2 : 0)))) return rc;   // best pairs + per-unit top-K, by pixel
-		if ((rc = ensure(c->lcand, c->lcand_cap, std::max<size_t>(lunits, 128)*(size_t)cmax))) return rc;   // wave-tiled lists
-		if ((rc = ensure(c->lcount, c->lcount_cap, std::max<size_t>(lunits, 128)))) return rc;
+		if ((rc = c->band.wbuf.ensure(wbuf_doubles(W, (int)lrows, T)))) return rc;
+		if ((rc = c->band.cost.ensure(units*2 + (peaks_dev ? units*(size_t)p->top_k*2 : 0)))) return rc;   // best pairs + per-unit top-K, by pixel
+		if ((rc = c->band.lcand.ensure(std::max<size_t>(lunits, 128)*(size_t)cmax))) return rc;   // wave-tiled lists
+		if ((rc = c->band.lcount.ensure(std::max<size_t>(lunits, 128)))) return rc;
 		const bool staged = c->mvs_staged != 0;
 		if (staged) {
 			int maxw; size_t words;
 			mvs_staging_shape(&maxw, &words);
 			const size_t waves = std::max<size_t>(lunits, 128)/64;
-			if ((rc = ensure(c->mvs_wdesc, c->mvs_wdesc_cap, waves*words))) return rc;
-			if ((rc = ensure(c->mvs_nwin, c->mvs_nwin_cap, waves))) return rc;
+			if ((rc = c->band.mvs_wdesc.ensure(waves*words))) return rc;
+			if ((rc = c->band.mvs_nwin.ensure(waves))) return rc;
 		}
 		for (int by = y0; by < y1; by += (int)lrows) {
 			if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
@@ -1952,21 +1905,21 @@ static int mvs_list_launch(srh_context *c, int view, const int32_t *neigh, int n
 			const int nact = (int)(A.act_row[by + nr] - A.act_row[by]);
 			run_weights(c, view, W, *p, by, nr, wstride);
 			{ Scope s(c, "mvs_walk_kernel");
-			  launch_mvs_walk(c->stream, c->d_views, view, neigh, nneigh, W, *p, by, nr, table ? c->tnum : nullptr, c->lcand, cmax, c->lcount,
-			                  c->d_cnt, c->d_span, staged ? c->mvs_wdesc : nullptr, staged ? c->mvs_nwin : nullptr, act, nact,
+			  launch_mvs_walk(c->stream, c->d_views, view, neigh, nneigh, W, *p, by, nr, table ? c->band.tnum : nullptr, c->band.lcand, cmax, c->band.lcount,
+			                  c->d_cnt, c->d_span, staged ? c->band.mvs_wdesc : nullptr, staged ? c->band.mvs_nwin : nullptr, act, nact,
 			                  peaks_dev != nullptr, neigh_pinhole && c->arith == 3); }
-			double *const upk = peaks_dev ? c->cost + units*2 : nullptr;
+			double *const upk = peaks_dev ? c->band.cost + units*2 : nullptr;
 			if (staged) {
 				Scope s(c, "mvs_staged_cost_kernel");
-				launch_mvs_staged_cost(c->stream, c->d_views, view, neigh, nneigh, W, *p, by, nr, c->wbuf, wstride,
-				                       c->lcand, cmax, c->lcount, c->cost, c->mvs_wdesc, c->mvs_nwin, c->d_cnt, act, nact, upk,
+				launch_mvs_staged_cost(c->stream, c->d_views, view, neigh, nneigh, W, *p, by, nr, c->band.wbuf, wstride,
+				                       c->band.lcand, cmax, c->band.lcount, c->band.cost, c->band.mvs_wdesc, c->band.mvs_nwin, c->d_cnt, act, nact, upk,
 				                       c->arith == 3 && !peaks_dev);
 			}
 			{ Scope s(c, "mvs_list_cost_kernel");
-			  launch_mvs_list_cost(c->stream, c->d_views, view, neigh, nneigh, W, *p, by, nr, c->wbuf, wstride,
-			                       c->lcand, cmax, c->lcount, c->cost, upk, peaks_dev != nullptr, staged ? c->mvs_nwin : nullptr, act, nact); }
+			  launch_mvs_list_cost(c->stream, c->d_views, view, neigh, nneigh, W, *p, by, nr, c->band.wbuf, wstride,
+			                       c->band.lcand, cmax, c->band.lcount, c->band.cost, upk, peaks_dev != nullptr, staged ? c->band.mvs_nwin : nullptr, act, nact); }
 			{ Scope s(c, "mvs_combine_kernel");
-			  launch_mvs_combine(c->stream, c->d_views, view, nneigh, W, *p, by, nr, c->cost, upk, (double *)peaks_dev); }
+			  launch_mvs_combine(c->stream, c->d_views, view, nneigh, W, *p, by, nr, c->band.cost, upk, (double *)peaks_dev); }
 		}
 	HIP_TRY(hipGetLastError());
 	return SRH_OK;
@@ -1995,13 +1948,7 @@ static void mvs_print_phases(srh_context *c) {
 static void mvs_slot_swap(srh_context *c, MvsSlot &S) {
 	std::swap(c->stream, S.stream);
 	if (!S.own_buffers) return;
-	std::swap(c->wbuf, S.wbuf); std::swap(c->wbuf_cap, S.wbuf_cap);
-	std::swap(c->cost, S.cost); std::swap(c->cost_cap, S.cost_cap);
-	std::swap(c->tnum, S.tnum); std::swap(c->tnum_cap, S.tnum_cap);
-	std::swap(c->lcount, S.lcount); std::swap(c->lcount_cap, S.lcount_cap);
-	std::swap(c->lcand, S.lcand); std::swap(c->lcand_cap, S.lcand_cap);
-	std::swap(c->mvs_wdesc, S.mvs_wdesc); std::swap(c->mvs_wdesc_cap, S.mvs_wdesc_cap);
-	std::swap(c->mvs_nwin, S.mvs_nwin); std::swap(c->mvs_nwin_cap, S.mvs_nwin_cap);
+	std::swap(c->band, S.band);
 	std::swap(c->d_cnt, S.d_cnt); std::swap(c->d_span, S.d_span);
 }
 
@@ -2100,8 +2047,8 @@ static int mvs_initial_estimate_run(srh_context *c, int view, const int32_t *nei
 				*S.h_maxc = 0;
 				S.own_buffers = k >= 1;
 				if (S.own_buffers) {
-					HIP_TRY(hipMalloc((void **)&S.d_cnt, sizeof(Counters)));
-					HIP_TRY(hipMalloc((void **)&S.d_span, 4*sizeof(int)));
+					HIP_TRY(S.d_cnt.alloc(1));
+					HIP_TRY(S.d_span.alloc(4));
 				}
 			}
 			HIP_TRY(hipEventRecord(S.ev, c->stream));                 // after whatever the caller's stream holds
@@ -2151,16 +2098,16 @@ static int mvs_initial_estimate_run(srh_context *c, int view, const int32_t *nei
 	if ((rc = mvs_settle_all(c))) return rc;
 
 	const int rows = band_rows(c, W, H, T);
-	if ((rc = ensure(c->wbuf, c->wbuf_cap, wbuf_doubles(W, rows, T)))) return rc;
-	if ((rc = ensure(c->cost, c->cost_cap, (size_t)rows*W*2*(size_t)std::max(nneigh, 1)))) return rc;   // per-neighbour best (cost, depth)
+	if ((rc = c->band.wbuf.ensure(wbuf_doubles(W, rows, T)))) return rc;
+	if ((rc = c->band.cost.ensure((size_t)rows*W*2*(size_t)std::max(nneigh, 1)))) return rc;   // per-neighbour best (cost, depth)
 	HIP_TRY(hipMemsetAsync(c->d_cnt, 0, sizeof(Counters), c->stream));
 	for (int by = y0; by < y1; by += rows) {
 		if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
 		const int nr = std::min(rows, y1 - by);
 		run_weights(c, view, W, *p, by, nr, wstride);
 		{ Scope s(c, "mvs_generic_kernel");
-		  launch_mvs_generic(c->stream, c->d_views, view, neigh, nneigh, W, *p, by, nr, c->wbuf, wstride,
-		                     (double *)peaks_dev, c->force_generic ? nullptr : c->cost, c->d_cnt); }
+		  launch_mvs_generic(c->stream, c->d_views, view, neigh, nneigh, W, *p, by, nr, c->band.wbuf, wstride,
+		                     (double *)peaks_dev, c->force_generic ? nullptr : c->band.cost, c->d_cnt); }
 	}
 	HIP_TRY(hipGetLastError());
 	c->stats.used_dense_path = 0;
@@ -2204,11 +2151,11 @@ extern "C" int srh_view_point_cloud(srh_context *c, int slot, const srh_params *
 	const size_t n = (size_t)v.w*v.h;
 	// scratch: xyz (3n doubles) | rgb (3n) | valid (n) | 3 counters, in the band buffer (free between runs)
 	const size_t need = 3*n + (3*n + n + 7)/8 + 4;
-	if ((rc = ensure(c->wbuf, c->wbuf_cap, need))) return rc;
-	double *d_xyz = c->wbuf;
-	uint8_t *d_rgb = reinterpret_cast<uint8_t *>(c->wbuf + 3*n);
+	if ((rc = c->band.wbuf.ensure(need))) return rc;
+	double *d_xyz = c->band.wbuf;
+	uint8_t *d_rgb = reinterpret_cast<uint8_t *>(c->band.wbuf + 3*n);
 	uint8_t *d_valid = d_rgb + 3*n;
-	unsigned long long *d_counts = reinterpret_cast<unsigned long long *>(c->wbuf + need - 4);
+	unsigned long long *d_counts = reinterpret_cast<unsigned long long *>(c->band.wbuf + need - 4);
 	HIP_TRY(hipMemsetAsync(d_counts, 0, 3*sizeof(unsigned long long), c->stream));
 	{ Scope s(c, "point_cloud_kernel");
 	  launch_point_cloud(c->stream, c->d_views, slot, v.w, v.h, *p, d_xyz, d_rgb, d_valid, d_counts); }
@@ -2237,10 +2184,10 @@ static int filter_view(srh_context *c, int slot, const srh_params *p, int flags,
 	// scratch: G (n doubles) | hole list (n u32) | 4 counters, in the band buffer (free between runs)
 	const size_t need = n + (n + 1)/2 + 4;
 	int rc;
-	if ((rc = ensure(c->wbuf, c->wbuf_cap, need))) return rc;
-	double *G = c->wbuf;
-	uint32_t *holes = reinterpret_cast<uint32_t *>(c->wbuf + n);
-	unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(c->wbuf + need - 4);
+	if ((rc = c->band.wbuf.ensure(need))) return rc;
+	double *G = c->band.wbuf;
+	uint32_t *holes = reinterpret_cast<uint32_t *>(c->band.wbuf + n);
+	unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(c->band.wbuf + need - 4);
 	HIP_TRY(hipMemsetAsync(d_cnt, 0, 4*sizeof(unsigned long long), c->stream));
 	if (gaps) {
 		Scope s(c, "filter_gap_kernel");
@@ -2320,11 +2267,11 @@ extern "C" int srh_epipolar_curves(srh_context *c, int ref, int oth, const srh_p
 		return fail(SRH_E_INVALID, "bad query buffers");
 	if (nq == 0) return SRH_OK;
 	HIP_TRY(hipSetDevice(c->device));
-	int32_t *d_xy = nullptr, *d_out = nullptr, *d_n = nullptr;
+	DevBuf<int32_t> d_xy, d_out, d_n;
 	const size_t out_bytes = (size_t)nq*2*(size_t)max_pts*sizeof(int32_t);
-	hipError_t e = hipMalloc((void **)&d_xy, (size_t)nq*2*sizeof(int32_t));
-	if (e == hipSuccess) e = hipMalloc((void **)&d_n, (size_t)nq*sizeof(int32_t));
-	if (e == hipSuccess && out_bytes) e = hipMalloc((void **)&d_out, out_bytes);
+	hipError_t e = d_xy.alloc((size_t)nq*2);
+	if (e == hipSuccess) e = d_n.alloc(nq);
+	if (e == hipSuccess && out_bytes) e = d_out.alloc((size_t)nq*2*(size_t)max_pts);
 	if (e == hipSuccess) e = hipMemcpyAsync(d_xy, xy, (size_t)nq*2*sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
 	if (e == hipSuccess) {
 		Scope s(c, "epipolar_curves_kernel");
@@ -2335,9 +2282,7 @@ extern "C" int srh_epipolar_curves(srh_context *c, int ref, int oth, const srh_p
 	if (e == hipSuccess && out_bytes) e = hipMemcpyAsync(out_xy, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
 	else (void)hipStreamSynchronize(c->stream);
-	if (d_xy) (void)hipFree(d_xy);
-	if (d_n) (void)hipFree(d_n);
-	if (d_out) (void)hipFree(d_out);
+	d_xy.free(); d_n.free(); d_out.free();
 	if (e != hipSuccess) return fail(SRH_E_DEVICE, "epipolar curves: %s", hipGetErrorString(e));
 	return SRH_OK;
 }
@@ -2359,7 +2304,7 @@ extern "C" int srh_mvs_mrf_estimate(srh_context *c, int slot, int K, const void 
 	HIP_TRY(hipSetDevice(c->device));
 	const ViewHost &v = c->views[slot];
 	const int w = v.w, h = v.h;
-	if ((rc = ensure(c->mrf, c->mrf_cap, mrf_scratch_doubles(w, h)))) return rc;
+	if ((rc = c->mrf.ensure(mrf_scratch_doubles(w, h)))) return rc;
 	c->mrf_w = c->mrf_h = c->mrf_k = 0;
 	MrfLayout lay;
 	{ Scope s(c, "mrf_data_kernel");
@@ -2405,7 +2350,7 @@ extern "C" int srh_mvs_initial_estimate_mrf(srh_context *c, int slot, const int3
 	if (p->top_k < 1 || p->top_k > 15) return fail(SRH_E_UNSUPPORTED, "top_k %d outside [1,15]", p->top_k);
 	HIP_TRY(hipSetDevice(c->device));
 	const ViewHost &v = c->views[slot];
-	if ((rc = ensure(c->mrf_peaks, c->mrf_peaks_cap, (size_t)v.w*v.h*p->top_k*2))) return rc;
+	if ((rc = c->mrf_peaks.ensure((size_t)v.w*v.h*p->top_k*2))) return rc;
 	if ((rc = srh_mvs_initial_estimate(c, slot, neigh, nneigh, p, 0, 0, c->mrf_peaks))) return rc;
 	return srh_mvs_mrf_estimate(c, slot, p->top_k, c->mrf_peaks, m, info);
 }
@@ -2418,7 +2363,7 @@ extern "C" int srh_mvs_initial_estimate_peaks(srh_context *c, int slot, const in
 	HIP_TRY(hipSetDevice(c->device));
 	ViewHost &v = c->views[slot];
 	v.peaks_k = 0;
-	if ((rc = ensure(v.peaks, v.peaks_cap, (size_t)v.w*v.h*p->top_k*2))) return rc;
+	if ((rc = v.peaks.ensure((size_t)v.w*v.h*p->top_k*2))) return rc;
 	if ((rc = srh_mvs_initial_estimate(c, slot, neigh, nneigh, p, 0, 0, v.peaks))) return rc;
 	v.peaks_k = p->top_k;
 	return SRH_OK;
@@ -2454,7 +2399,7 @@ extern "C" int srh_mvs_mrf_estimate_views(srh_context *c, const int32_t *slots, 
 		r.slot = slots[i]; r.w = v.w; r.h = v.h; r.K = v.peaks_k; r.iters = 0; r.left = m->max_iters; r.active = true; r.st = nullptr;
 		if (!c->mrf_stream[i]) { if (hipStreamCreateWithFlags(&c->mrf_stream[i], hipStreamNonBlocking) != hipSuccess) return cleanup(fail(SRH_E_DEVICE, "stream creation failed")); }
 		r.st = c->mrf_stream[i];
-		if ((rc = ensure(v.mrf, v.mrf_cap, mrf_scratch_doubles(r.w, r.h)))) return cleanup(rc);
+		if ((rc = v.mrf.ensure(mrf_scratch_doubles(r.w, r.h)))) return cleanup(rc);
 		r.buf = v.mrf;
 		if (hipStreamWaitEvent(r.st, ev, 0) != hipSuccess ||
 		    launch_mrf_setup(r.st, r.buf, r.w, r.h, r.K, m->beta, m->lambda, m->phi_u, v.peaks, r.lay) != hipSuccess ||
@@ -2543,8 +2488,8 @@ extern "C" int srh_epipolar_preview(srh_context *c, int ref, int oth, double zmi
 	HIP_TRY(hipSetDevice(c->device));
 	const size_t nout = (size_t)nq*nd*2;
 	// scratch in the band buffer: [xy | out | counts]
-	if ((rc = ensure(c->wbuf, c->wbuf_cap, (size_t)2*nq + nout + (size_t)(nq + 1)/2 + 2))) return rc;
-	double *d_xy = c->wbuf, *d_out = c->wbuf + 2*(size_t)nq;
+	if ((rc = c->band.wbuf.ensure((size_t)2*nq + nout + (size_t)(nq + 1)/2 + 2))) return rc;
+	double *d_xy = c->band.wbuf, *d_out = c->band.wbuf + 2*(size_t)nq;
 	int32_t *d_cnt = reinterpret_cast<int32_t *>(d_out + nout);
 	HIP_TRY(hipMemcpyAsync(d_xy, xy, (size_t)2*nq*sizeof(double), hipMemcpyHostToDevice, c->stream));
 	{ Scope s(c, "epipolar_preview_kernel");
@@ -2565,8 +2510,8 @@ extern "C" int srh_refraction_error(srh_context *c, int v1, int v2, int n, const
 	HIP_TRY(hipSetDevice(c->device));
 	std::vector<double> err((size_t)n);
 	if (n > 0) {
-		if ((rc = ensure(c->wbuf, c->wbuf_cap, (size_t)5*n))) return rc;
-		double *d1 = c->wbuf, *d2 = c->wbuf + 2*(size_t)n, *de = c->wbuf + 4*(size_t)n;
+		if ((rc = c->band.wbuf.ensure((size_t)5*n))) return rc;
+		double *d1 = c->band.wbuf, *d2 = c->band.wbuf + 2*(size_t)n, *de = c->band.wbuf + 4*(size_t)n;
 		HIP_TRY(hipMemcpyAsync(d1, p1, (size_t)2*n*sizeof(double), hipMemcpyHostToDevice, c->stream));
 		HIP_TRY(hipMemcpyAsync(d2, p2, (size_t)2*n*sizeof(double), hipMemcpyHostToDevice, c->stream));
 		{ Scope s(c, "refraction_error_kernel");
@@ -2664,11 +2609,11 @@ extern "C" int srh_comm_allgather_host(srh_context *c, const double *send_host, 
 	// windows from on its own stream: finish the estimates in flight first, like every other entry point
 	if ((rc = mvs_settle_all(c))) return rc;
 	// staging in the band scratch (free between runs): [send | recv]
-	if ((rc = ensure(c->wbuf, c->wbuf_cap, count*(size_t)(c->comm_ranks + 1)))) return rc;
-	HIP_TRY(hipMemcpyAsync(c->wbuf, send_host, count*sizeof(double), hipMemcpyHostToDevice, c->stream));
-	if (const char *e = rccl_allgather_f64(c->comm, c->wbuf, c->wbuf + count, count, c->stream))
+	if ((rc = c->band.wbuf.ensure(count*(size_t)(c->comm_ranks + 1)))) return rc;
+	HIP_TRY(hipMemcpyAsync(c->band.wbuf, send_host, count*sizeof(double), hipMemcpyHostToDevice, c->stream));
+	if (const char *e = rccl_allgather_f64(c->comm, c->band.wbuf, c->band.wbuf + count, count, c->stream))
 		return comm_failed(c, "all-gather", e);
-	HIP_TRY(hipMemcpyAsync(recv_host, c->wbuf + count, count*(size_t)c->comm_ranks*sizeof(double), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipMemcpyAsync(recv_host, c->band.wbuf + count, count*(size_t)c->comm_ranks*sizeof(double), hipMemcpyDeviceToHost, c->stream));
 	if (const char *e = rccl_wait_stream(c->comm, c->stream, "the all-gather")) return comm_failed(c, "all-gather", e);   // (bounded: never a bare hipStreamSynchronize behind a collective)
 	return SRH_OK;
 }
@@ -2689,8 +2634,8 @@ extern "C" int srh_comm_allgather_views(srh_context *c, const int32_t *slots, in
 	auto shard = [&](int r, int &lo, int &hi) { const int base = nviews/world, extra = nviews % world;
 	                                            lo = r*base + std::min(r, extra); hi = lo + base + (r < extra ? 1 : 0); };
 	// [send | recv] in the band scratch (free between runs); everything below is ordered on the context's stream
-	if ((rc = ensure(c->wbuf, c->wbuf_cap, (size_t)(world + 1)*per*npix))) return rc;
-	double *send = c->wbuf, *recv = c->wbuf + (size_t)per*npix;
+	if ((rc = c->band.wbuf.ensure((size_t)(world + 1)*per*npix))) return rc;
+	double *send = c->band.wbuf, *recv = c->band.wbuf + (size_t)per*npix;
 	launch_fill(c->stream, send, (size_t)per*npix, __builtin_nan(""));
 	int lo, hi;
 	shard(rank, lo, hi);
