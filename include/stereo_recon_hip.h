@@ -163,7 +163,9 @@ void srh_destroy(srh_context *ctx);
 int  srh_set_stream(srh_context *ctx, void *hip_stream);
 int  srh_set_hooks(srh_context *ctx, const volatile int *cancel, srh_progress_fn progress, void *user);
 int  srh_synchronize(srh_context *ctx);
-/* Tuning / test switches (results never depend on them, "arith" = 1 / 2 excepted):
+/* TwoView matching cost (option "cost"): TwoViewStereo::cost_ncc (default) or cost_sad (twoviewstereo.cpp:864-905) */
+enum { SRH_COST_NCC = 0, SRH_COST_SAD = 1 };
+/* Tuning / test switches (results never depend on them, "arith" = 1 / 2, "cost" and "filter_invalid" excepted):
  *   "force_generic"   0 default paths; 1 never the dense row-aligned TwoView kernels nor the MVS list kernels;
  *                     2 additionally no candidate lists at all (one thread per pixel walks and costs its curve)
  *   "fused"           1: row-aligned pairs run the single fused kernel (geometry + cost + WTA per 16-pixel tile
@@ -213,6 +215,12 @@ int  srh_synchronize(srh_context *ctx);
  *   "debug_alloc_limit_mb"  refuse band buffers above this size as if the device were out of memory (0 = off; tests)
  *   "debug_mvs_cmax_hint"   the list capacity the next MultiViewStereo estimate is queued with (0 = forget; test of the redo of a
  *                     view whose lists were cut)
+ *   "cost"            CHANGES RESULTS.  SRH_COST_NCC (0, default): the weighted NCC of cost_ncc.  SRH_COST_SAD (1): the
+ *                     support-weighted, truncated SAD of cost_sad (min(|gl - gr|, max_color_diff) per tap, the left tap
+ *                     sample() and the right tap pixel() behind both masks; bad_ret for numPixels <= 4 or totalWeight <=
+ *                     1e-10), the WTA, ratio test and cross-check unchanged.  SAD runs on the candidate lists (rectified
+ *                     rigs too: there is no dense, strip or fused SAD kernel) in the reference's arithmetic; "arith" does
+ *                     not apply to it.  srh_twoview_cost_rows is SRH_E_UNSUPPORTED under SAD.
  *   "filter_invalid"  0 (default, as the reference's call site under #if 0): srh_twoview_compute ends with the cross-check;
  *                     SRH_FILTER_* flags (1 gaps, 2 median, 3 both): it then runs srh_view_filter_invalid on both maps,
  *                     with progress steps 6 "Filling invalid pixels..." and, with the median, 7 "Filtering invalid pixels..."
@@ -265,6 +273,12 @@ int  srh_twoview_wta(srh_context *ctx, int ref_slot, int oth_slot, const srh_par
  * SRH_E_UNSUPPORTED when the pair does not take the dense plan. */
 int  srh_twoview_cost_rows(srh_context *ctx, int ref_slot, int other_slot, const srh_params *p, int y0, int y1, int form, int raw,
                            double *cost_out, size_t cost_doubles, int32_t *range_out, int *cstride_out, int *used_strip_kernel);
+/* cost_sad (kind SRH_COST_SAD) or cost_ncc (SRH_COST_NCC) of n arbitrary pairs: xy holds n x (x1, y1, x2, y2), (x1, y1) a
+ * pixel of ref_slot (else SRH_E_INVALID), (x2, y2) any pixel position of oth_slot (taps outside it are skipped).  The
+ * support window of (x1, y1) is built on the device (p->weight_kind, p->window_radius <= 5).  Host pointers; synchronous.
+ * The backend of the host classes' protected cost_sad / cost_ncc. */
+int  srh_twoview_pair_costs(srh_context *ctx, int ref_slot, int oth_slot, const srh_params *p, int kind, int n,
+                            const int32_t *xy, double *out);
 /* DIAGNOSTIC (tests/test_gpu_geodesic_exp.py): the GeodesicWeight kernels evaluate exp(-w/sigma) (geodesicweight.cpp:128-130)
  * by the device library's exp sequence written out in their source (srh_dense.hip, geo_exp_n: constants of THIS ROCm's
  * ocml) -- this entry evaluates n arguments by that sequence (kernel_out) and by the library's exp() itself (library_out),

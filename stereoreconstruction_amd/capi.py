@@ -85,6 +85,9 @@ class FilterInfo(C.Structure):
 # srh_view_filter_invalid flags
 FILTER_GAPS, FILTER_MEDIAN = 1, 2
 
+# option "cost" / srh_twoview_pair_costs kind: TwoViewStereo::cost_ncc, cost_sad
+COST_NCC, COST_SAD = 0, 1
+
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_int, C.c_char_p, C.c_void_p)
 
@@ -96,7 +99,7 @@ EXPORTS = [
     "srh_create", "srh_destroy", "srh_set_stream", "srh_set_hooks", "srh_synchronize", "srh_set_option",
     "srh_view_upload", "srh_view_size", "srh_view_depth_download", "srh_view_depth_upload",
     "srh_view_depth_device_ptr", "srh_view_depth_copy_to_device", "srh_view_depth_copy_from_device",
-    "srh_twoview_wta", "srh_twoview_cross_check", "srh_twoview_compute", "srh_twoview_cost_rows", "srh_debug_exp",
+    "srh_twoview_wta", "srh_twoview_cross_check", "srh_twoview_compute", "srh_twoview_cost_rows", "srh_twoview_pair_costs", "srh_debug_exp",
     "srh_mvs_initial_estimate", "srh_mvs_cross_check", "srh_view_point_cloud", "srh_view_filter_invalid",
     "srh_epipolar_curves",
     "srh_epipolar_preview", "srh_refraction_error",
@@ -174,6 +177,7 @@ def lib():
     L.srh_refraction_error.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]
     L.srh_view_point_cloud.argtypes = [vp, C.c_int, C.POINTER(Params), c_double_p, c_uint8_p, c_uint8_p, vp, vp, vp]
     L.srh_view_filter_invalid.argtypes = [vp, C.c_int, C.POINTER(Params), C.c_int, C.c_int, C.POINTER(FilterInfo)]
+    L.srh_twoview_pair_costs.argtypes = [vp, C.c_int, C.c_int, C.POINTER(Params), C.c_int, C.c_int, c_int32_p, c_double_p]
     L.srh_view_depth_copy_to_device.argtypes = [vp, C.c_int, vp, C.c_size_t]
     L.srh_view_depth_copy_from_device.argtypes = [vp, C.c_int, vp, C.c_size_t]
     L.srh_twoview_wta.argtypes = [vp, C.c_int, C.c_int, C.POINTER(Params), C.c_int, C.c_int]
@@ -480,6 +484,15 @@ class Context:
         info = FilterInfo()
         _check(lib().srh_view_filter_invalid(self._h, slot, C.byref(p), flags, gap_width, C.byref(info)))
         return {k: int(getattr(info, k)) for k, _ in FilterInfo._fields_}
+
+    def twoview_pair_costs(self, ref, oth, p, xy, kind=COST_SAD):
+        """cost_sad (kind COST_SAD) or cost_ncc (COST_NCC) of arbitrary pairs: xy (n, 4) int rows (x1, y1, x2, y2), the
+        support window of (x1, y1) in view `ref` -> (n,) float64 (srh_twoview_pair_costs)."""
+        a = np.ascontiguousarray(np.asarray(xy, dtype=np.int32).reshape(-1, 4))
+        out = np.empty(a.shape[0], np.float64)
+        _check(lib().srh_twoview_pair_costs(self._h, ref, oth, C.byref(p), kind, a.shape[0],
+                                            a.ctypes.data_as(c_int32_p), out.ctypes.data_as(c_double_p)))
+        return out
 
     def mvs_mrf_estimate(self, view_slot, top_k, peaks_dev, m=None):
         """MRF branch of computeInitialEstimate on the device peaks buffer -> dict(iterations, energy_initial, energy_final)."""

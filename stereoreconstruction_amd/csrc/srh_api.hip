@@ -213,6 +213,8 @@ struct ViewHost {
 	DevBuf<double>   geo5;  bool geo5_valid = false;      // edge + tap planes with their borders written out (geodesic_dma_kernel)
 	bool             geo5_denied = false;                 // released by an out-of-memory retry: this upload keeps the register-staged windows kernel
 	DevBuf<uint8_t>  fullp; int fullp_r = 0;
+	DevBuf<uint8_t>  fulls; int fulls_r = 0;            // cost_sad's "window fully usable" plane of radius fulls_r (srh_sad.hip): its own
+	                                                      // validity (pixel() behind the mask), so never the NCC plane `full`
 	// how the candidate lists of this view against slot j are best evaluated, learnt from the last run:
 	// 0 unknown, 1 row runs (srh_rows.hip), 2 list order (srh_list.hip: steep curves)
 	uint8_t   list_mode[SRH_MAX_VIEWS] = {0};
@@ -339,6 +341,7 @@ struct srh_context {
 	int filter_invalid = 0;                             // option "filter_invalid": SRH_FILTER_* flags srh_twoview_compute ends with (0: none)
 	int filter_gap_width = 2;                           // option "filter_gap_width" (GAP_WIDTH_THRESHOLD)
 	int filter_replay = 0;                              // option "filter_replay": every median hole by the exact replay (test hook)
+	int cost_kind = SRH_COST_NCC;                       // option "cost": the TwoView matching cost, SRH_COST_NCC or SRH_COST_SAD
 };
 
 static bool cancelled(srh_context *c) { return c->cancel && *c->cancel; }
@@ -666,7 +669,7 @@ extern "C" int srh_create(int device, srh_context **out) {
 static void free_view(ViewHost &v) {
 	if (v.rgba || v.gray || v.edges || v.tvp || v.geo5) (void)hipDeviceSynchronize();
 	v.rgba.release(); v.mask.release(); v.gray.release(); v.gray_tv.release(); v.depth.release(); v.edges.release();
-	v.full.release(); v.tvp.release(); v.geo5.release(); v.fullp.release(); v.act.release(); v.peaks.release(); v.mrf.release();
+	v.full.release(); v.fulls.release(); v.tvp.release(); v.geo5.release(); v.fullp.release(); v.act.release(); v.peaks.release(); v.mrf.release();
 	v = ViewHost();
 }
 
@@ -781,6 +784,10 @@ extern "C" int srh_set_option(srh_context *c, const char *name, long value) {
 	}
 	if (!strcmp(name, "filter_gap_width")) { c->filter_gap_width = (int)value; return SRH_OK; }
 	if (!strcmp(name, "filter_replay")) { c->filter_replay = value != 0; return SRH_OK; }
+	if (!strcmp(name, "cost")) {
+		if (value != SRH_COST_NCC && value != SRH_COST_SAD) return fail(SRH_E_INVALID, "cost must be 0 (SRH_COST_NCC) or 1 (SRH_COST_SAD)");
+		c->cost_kind = (int)value; return SRH_OK;
+	}
 	if (!strcmp(name, "tscan")) { c->tscan = value != 0; return SRH_OK; }
 	if (!strcmp(name, "geodma")) { c->geodma = value != 0; return SRH_OK; }
 	if (!strcmp(name, "f32_form")) { c->f32_form = value != 0; return SRH_OK; }
@@ -829,7 +836,7 @@ extern "C" int srh_view_upload(srh_context *c, int slot, int w, int h,
 		v.w = w; v.h = h; v.present = true;
 	}
 	v.cam = *cam;
-	v.full_r = 0;                                               // recomputed on demand for the new pixels
+	v.full_r = 0; v.fulls_r = 0;                                // recomputed on demand for the new pixels
 	v.tvp_valid = false; v.fullp_r = 0; v.geo5_valid = false; v.geo5_denied = false;
 	v.peaks_k = 0;                                              // the top-K peaks belonged to the previous image
 	if (c->mrf_w == w && c->mrf_h == h) c->mrf_w = c->mrf_h = c->mrf_k = 0;
@@ -1174,7 +1181,9 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 	const size_t budget = band_budget(c);
 
 	// ---- plan: dense row-aligned kernels, or the general curve-walk kernel
-	bool dense = !c->force_generic && (R == 5 || R == 2);
+	// (cost_sad: no dense, strip or fused kernel -- rectified rigs take the row-run lists too)
+	const bool sad = c->cost_kind == SRH_COST_SAD;
+	bool dense = !c->force_generic && !sad && (R == 5 || R == 2);
 	int cstride = 0;
 	double fx_bx = 0;
 	if (dense && !rig_is_row_aligned(L.cam, Rv.cam, &fx_bx)) {
@@ -1232,7 +1241,7 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 	bool strip = dense && c->strip != 0 && c->arith != 2 && cstride + SRH_WTILE <= strip_chunk_columns();
 	// certified arithmetic (arith = 3, the default): fused cost loops in the strip kernel + the certified scan; where the
 	// strip kernel does not run, or the parameters leave the bound no room, the reference's arithmetic
-	bool cert_ok = c->arith == 3 && cert_bound(*p).ok != 0;
+	bool cert_ok = c->arith == 3 && !sad && cert_bound(*p).ok != 0;
 	c->stats.n_certified = c->stats.n_flagged = 0;
 	// The exact redo of flagged pixels is launched for a CAPACITY -- the whole band: the list buffer holds every pixel of it,
 	// the redo kernels share the list in grid-stride loops and read the count on the device -- so however many pixels flag
@@ -1250,7 +1259,13 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 			const size_t npix = (size_t)(y1 - y0)*W;
 			if ((rc = c->band.lcount.ensure(npix))) return rc;
 			ViewHost &O = c->views[oth];
-			if (O.full_r != R) {
+			if (sad && O.fulls_r != R) {
+				if (!O.fulls) HIP_TRY(O.fulls.alloc((size_t)O.w*O.h));
+				Scope s(c, "sad_full_window_kernel");
+				launch_sad_full_window(c->stream, O.mask, O.w, O.h, R, O.fulls);
+				O.fulls_r = R;
+			}
+			if (!sad && O.full_r != R) {
 				Scope s(c, "full_window_kernel");
 				uint32_t *stat = (uint32_t *)(O.full + full_stat_offset((size_t)O.w*O.h));
 				HIP_TRY(hipMemsetAsync(stat, 0, 2*sizeof(uint32_t), c->stream));
@@ -1302,7 +1317,7 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 				const bool rows_cert = rows_mode && cert_ok;
 				// the row-run cost kernel takes the pixels' constants (meanL, totalWeight, sum2, 1/totalWeight, SA) from the weights
 				// kernel, which has the window in registers anyway, instead of making them on one lane in eight per tile
-				const bool rows_pc = rows_mode;
+				const bool rows_pc = rows_mode && !sad;
 				if (rows_pc && (rc = c->band.pconst.ensure((lrows*(size_t)W + SRH_WTILE)*SRH_PC))) return rc;
 				if (rows_mode) {
 					if ((rc = c->band.lrowinfo.ensure(px64*(size_t)SRH_ROWS_NR))) return rc;
@@ -1348,6 +1363,11 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 						} else run_weights(c, ref, W, *p, by, nr, SRH_WTILE, rows_pc ? c->band.pconst : nullptr, true);
 						if (rows_cert) HIP_TRY(hipMemsetAsync(c->band.cflag, 0, sizeof(uint32_t), c->stream));
 						HIP_TRY(hipMemsetAsync(&c->d_cnt->strip_ticket, 0, 2*sizeof(unsigned int), c->stream));   // the cost kernel's waves draw their tiles from it
+						if (sad) {
+							Scope s(c, "twoview_rows_sad_kernel");
+							launch_twoview_rows_sad(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, O.fulls,
+							                        c->band.lrowinfo, c->band.lmeta, c->band.cost, smax, c->d_cnt);
+						} else
 						{ Scope s(c, "twoview_rows_cost_kernel");
 						  launch_twoview_rows_cost(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, O.full,
 						                           c->band.lrowinfo, c->band.lmeta, c->band.cost, smax, c->d_cnt, rows_cert ? (c->cert_form == 1 ? 5 : 3) : 0,
@@ -1373,6 +1393,11 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 					{ Scope s(c, "twoview_list_kernel");
 					  launch_twoview_list(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.lcand, cmax,
 					                      cnt_band, c->d_cnt, c->d_span, c->band.tnum); }
+					if (sad) {
+						Scope s(c, "twoview_list_sad_kernel");
+						launch_twoview_list_sad(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf,
+						                        cnt_band, c->band.lcand, c->band.cost, cmax, c->d_cnt);
+					} else
 					{ Scope s(c, "twoview_list_cost_kernel");
 					  launch_twoview_list_cost(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, O.full,
 					                           cnt_band, c->band.lcand, c->band.cost, cmax, c->d_cnt); }
@@ -1578,7 +1603,7 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 				}
 			} else {
 				Scope s(c, "twoview_generic_kernel");
-				launch_twoview_generic(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, wstride, c->d_cnt);
+				launch_twoview_generic(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, wstride, c->d_cnt, sad);
 			}
 		}
 		HIP_TRY(hipGetLastError());
@@ -1617,6 +1642,7 @@ extern "C" int srh_twoview_cost_rows(srh_context *c, int ref, int oth, const srh
 	if ((rc = check_slot(c, ref, true)) || (rc = check_slot(c, oth, true)) || (rc = check_params(p))) return rc;
 	if (form != 0 && form != 3 && form != 5 && form != 1) return fail(SRH_E_INVALID, "form must be 0, 1, 3 or 5");
 	if ((form == 3 || form == 5) && !cert_bound(*p).ok) return fail(SRH_E_UNSUPPORTED, "the parameters leave the error bound no room");
+	if (c->cost_kind == SRH_COST_SAD) return fail(SRH_E_UNSUPPORTED, "cost rows exist for cost_ncc only (cost_sad has no dense plan)");
 	srh_context::Diag dg;
 	dg.form = form; dg.raw = raw != 0; dg.cost = cost_out; dg.cost_doubles = cost_doubles; dg.range = range_out;
 	c->diag = &dg;
@@ -1629,6 +1655,35 @@ extern "C" int srh_twoview_cost_rows(srh_context *c, int ref, int oth, const srh
 	if (!dg.done) return fail(SRH_E_UNSUPPORTED, "cost rows exist on the row-aligned dense plan only (radius 5 or 2, rectified pinhole pair)");
 	if (cstride_out) *cstride_out = dg.cstride;
 	if (used_strip) *used_strip = dg.strip ? 1 : 0;
+	return SRH_OK;
+}
+
+// cost_sad / cost_ncc of arbitrary pairs (the host classes' protected cost_sad / cost_ncc, tests): the support window of
+// (x1, y1) built on the device, the reference-form costs of srh_walk.hpp; synchronous, host pointers
+extern "C" int srh_twoview_pair_costs(srh_context *c, int ref, int oth, const srh_params *p, int kind, int n,
+                                      const int32_t *xy, double *out)
+{
+	int rc;
+	if ((rc = check_slot(c, ref, true)) || (rc = check_slot(c, oth, true)) || (rc = check_params(p))) return rc;
+	if (kind != SRH_COST_NCC && kind != SRH_COST_SAD) return fail(SRH_E_INVALID, "kind must be SRH_COST_NCC or SRH_COST_SAD");
+	if (n < 0 || (n > 0 && (!xy || !out))) return fail(SRH_E_INVALID, "null pairs or output");
+	if (p->window_radius > 5) return fail(SRH_E_UNSUPPORTED, "pair costs take window radii up to 5");
+	if (n == 0) return SRH_OK;
+	const ViewHost &L = c->views[ref];
+	for (int k = 0; k < n; ++k)
+		if (xy[4*k] < 0 || xy[4*k + 1] < 0 || xy[4*k] >= L.w || xy[4*k + 1] >= L.h)
+			return fail(SRH_E_INVALID, "pair %d: reference pixel (%d, %d) outside the %dx%d view", k, xy[4*k], xy[4*k + 1], L.w, L.h);
+	HIP_TRY(hipSetDevice(c->device));
+	DevBuf<int32_t> dxy; DevBuf<double> dout;
+	HIP_TRY(dxy.alloc((size_t)4*n));
+	HIP_TRY(dout.alloc((size_t)n));
+	HIP_TRY(hipMemcpyAsync(dxy, xy, (size_t)4*n*sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+	{ Scope s(c, "pair_costs_kernel");
+	  launch_pair_costs(c->stream, c->d_views, ref, oth, *p, kind == SRH_COST_SAD, n, dxy, dout); }
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(out, dout, (size_t)n*sizeof(double), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	dxy.free(); dout.free();
 	return SRH_OK;
 }
 

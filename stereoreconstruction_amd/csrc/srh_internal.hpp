@@ -210,7 +210,7 @@ void launch_fill(hipStream_t st, double *p, size_t n, double v);
 void launch_weights(hipStream_t st, const ViewDev *views, int ref, int width, const srh_params &P,
                     int y0, int nrows, double *wbuf, size_t wstride, double *pconst = nullptr, bool wimg = false);
 void launch_twoview_generic(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P,
-                            int y0, int nrows, const double *wbuf, size_t wstride, Counters *cnt);
+                            int y0, int nrows, const double *wbuf, size_t wstride, Counters *cnt, bool sad = false);
 void launch_twoview_cross_check(hipStream_t st, const ViewDev *views, int self, int other, int w, int h,
                                 const srh_params &P);
 void launch_mvs_generic(hipStream_t st, const ViewDev *views, int ref, const int32_t *neigh, int nneigh, int width,
@@ -336,6 +336,20 @@ void launch_filter_holes(hipStream_t st, const uint8_t *mask, double *D, int w, 
                          unsigned long long *cnt);
 void launch_filter_median(hipStream_t st, const ViewDev *views, int slot, const srh_params &P, const double *G,
                           const uint32_t *holes, int nholes, double *D, unsigned long long *cnt);
+// weighted SAD, TwoViewStereo::cost_sad (srh_sad.hip)
+// full (w*h bytes): 1 where the whole (2R+1)^2 window of cost_sad's OTHER-view side is usable (inside the image, mask WHITE)
+void launch_sad_full_window(hipStream_t st, const uint8_t *mask, int w, int h, int R, uint8_t *full);
+// the row-run lists' cost slots (srh_rows.hip layout) with cost_sad; the windows in the LDS-image layout
+bool launch_twoview_rows_sad(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P,
+                             int y0, int nrows, const double *wbuf, const uint8_t *full_sad_oth,
+                             const uint32_t *rowinfo, const int32_t *meta, double *cost, int smax, Counters *cnt);
+// the list-order costs (srh_list.hip layout) with cost_sad; the windows tile-major
+void launch_twoview_list_sad(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P,
+                             int y0, int nrows, const double *wbuf, const int32_t *count, const uint32_t *cand,
+                             double *cost, int cmax, Counters *cnt);
+// cost of arbitrary pairs xy[4k..4k+3] = (x1, y1, x2, y2), the window of (x1, y1) built per lane; sad: cost_sad, else cost_ncc
+void launch_pair_costs(hipStream_t st, const ViewDev *views, int ref, int oth, const srh_params &P, bool sad, int n,
+                       const int32_t *xy, double *out);
 void launch_point_cloud(hipStream_t st, const ViewDev *views, int slot, int w, int h, const srh_params &P,
                         double *xyz, uint8_t *rgb, uint8_t *valid, unsigned long long *counts);
 // MRF stage (srh_mrf.hip): one scratch buffer, carved the same way by every launch

@@ -122,6 +122,7 @@ void launch_weights(hipStream_t st, const ViewDev *views, int ref, int width, co
 }
 
 // ------------------------------------------------------------------ TwoView, general geometry
+template <bool SAD>
 struct TwoViewDirectVisitor {
 	const ViewDev &L, &Rv;
 	const double *wq;
@@ -132,7 +133,7 @@ struct TwoViewDirectVisitor {
 	int wx, wy;
 	unsigned n;
 	__device__ __forceinline__ void operator()(int cx, int cy) {
-		const double cost = tv_cost(L, Rv, wq, wstride, P, x, y, cx, cy);
+		const double cost = SAD ? tv_cost_sad(L, Rv, wq, wstride, P, x, y, cx, cy) : tv_cost(L, Rv, wq, wstride, P, x, y, cx, cy);
 		++n;
 		if (cost + P.wta_margin < minCost) {                   // twoviewstereo.cpp:293-301
 			secondBest = minCost;
@@ -142,6 +143,8 @@ struct TwoViewDirectVisitor {
 	}
 };
 
+// SAD: the cost is cost_sad (option "cost" = SRH_COST_SAD), else cost_ncc
+template <bool SAD>
 __global__ void twoview_generic_kernel(const ViewDev *__restrict__ views, int ref, int oth, srh_params P,
                                        int y0, int nrows, const double *__restrict__ wbuf, size_t wstride,
                                        Counters *__restrict__ cnt)
@@ -159,7 +162,7 @@ __global__ void twoview_generic_kernel(const ViewDev *__restrict__ views, int re
 			n_pix = 1;
 			const Ray ray = cam_unproject(L.cam, (x + 0.5) / P.image_scale, (y + 0.5) / P.image_scale);
 			const int T = (2*P.window_radius + 1)*(2*P.window_radius + 1);
-			TwoViewDirectVisitor vis = { L, Rv, wbuf + wbuf_offset(W, T, (int)(q / W), x), wstride, P, x, y,
+			TwoViewDirectVisitor<SAD> vis = { L, Rv, wbuf + wbuf_offset(W, T, (int)(q / W), x), wstride, P, x, y,
 			                             __builtin_inf(), __builtin_inf(), -1, -1, 0 };
 			walk_curve<false>(ray, L.cam, Rv, P, vis);
 			n_eval = vis.n;
@@ -176,11 +179,15 @@ __global__ void twoview_generic_kernel(const ViewDev *__restrict__ views, int re
 }
 
 void launch_twoview_generic(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P,
-                            int y0, int nrows, const double *wbuf, size_t wstride, Counters *cnt)
+                            int y0, int nrows, const double *wbuf, size_t wstride, Counters *cnt, bool sad)
 {
 	const size_t n = (size_t)nrows*width;
-	hipLaunchKernelGGL(twoview_generic_kernel, dim3((unsigned)((n + 127)/128)), dim3(128), 0, st,
-	                   views, ref, oth, P, y0, nrows, wbuf, wstride, cnt);
+	if (sad)
+		hipLaunchKernelGGL(twoview_generic_kernel<true>, dim3((unsigned)((n + 127)/128)), dim3(128), 0, st,
+		                   views, ref, oth, P, y0, nrows, wbuf, wstride, cnt);
+	else
+		hipLaunchKernelGGL(twoview_generic_kernel<false>, dim3((unsigned)((n + 127)/128)), dim3(128), 0, st,
+		                   views, ref, oth, P, y0, nrows, wbuf, wstride, cnt);
 }
 
 // one direction of TwoViewStereo::crossCheck (twoviewstereo.cpp:604-636 / :638-670)

@@ -1,9 +1,10 @@
-// srh_walk.hpp -- device-side epipolar-curve walker and the two weighted-NCC costs.
+// srh_walk.hpp -- device-side epipolar-curve walker, the two weighted-NCC costs and the weighted SAD.
 //
 //   walk_curve<MVS>   TwoViewStereo::epipolarCurve (stereo/twoviewstereo.cpp:999-1054) /
 //                     MultiViewStereo::epipolarCurve (stereo/multiviewstereo.cpp:754-810):
 //                     calls vis(cx, cy) for every candidate pixel, in the reference's order.
 //   tv_cost           TwoViewStereo::cost_ncc (twoviewstereo.cpp:909-977), lower is better
+//   tv_cost_sad       TwoViewStereo::cost_sad (twoviewstereo.cpp:864-905), lower is better
 //   mvs_cost          free cost_ncc (multiviewstereo.cpp:113-189), higher is better
 //   candidate_depth   camera-space z of the two-ray mid-point (twoviewstereo.cpp:287-300)
 #pragma once
@@ -339,6 +340,41 @@ __device__ __forceinline__ double tv_cost(const ViewDev &L, const ViewDev &Rv, c
 	}
 	const double v = 255*(1.0 - fabs(sum1) / sqrt(sum2 * sum3));
 	return (v < P.max_color_diff) ? v : P.max_color_diff;       // std::min(MAX_COLOR_DIFF, v): NaN -> 120
+}
+
+// gray value of the other view's tap in cost_sad: right.pixel() where the mask is WHITE, NaN where the tap is skipped
+// (unlike sample(), pixel() is valid on the last column and row: the `gray` plane, not gray_tv)
+__device__ __forceinline__ double sad_tap(const ViewDev &V, int x, int y) {
+	if (x < 0 || y < 0 || x >= V.w || y >= V.h) return __builtin_nan("");
+	const size_t i = (size_t)y*V.w + x;
+	return V.mask[i] == 1 ? V.gray[i] : __builtin_nan("");
+}
+
+// TwoViewStereo::cost_sad (twoviewstereo.cpp:864-905), lower is better; window layout as tv_cost.  The left tap is
+// left.sample() behind leftMask (gray_tv holds both), the right tap right.pixel() behind rightMask (sad_tap).
+__device__ __forceinline__ double tv_cost_sad(const ViewDev &L, const ViewDev &Rv, const double *__restrict__ wq,
+                                              size_t wstride, const srh_params &P, int x1, int y1, int x2, int y2,
+                                              size_t wrow = 0)
+{
+	const int R = P.window_radius, WS = 2*R + 1;
+	if (wrow == 0) wrow = (size_t)WS*wstride;
+	int numPixels = 0;
+	double sum = 0.0, totalWeight = 0.0;
+	for (int row = -R; row <= R; ++row) {
+		for (int col = -R; col <= R; ++col) {
+			const double gl = tv_tap(L, x1 + col, y1 + row);
+			const double gr = sad_tap(Rv, x2 + col, y2 + row);
+			const double weight = wq[(size_t)(row + R)*wrow + (size_t)(col + R)*wstride];
+			if (gl == gl && gr == gr && weight > P.weight_cutoff) {
+				const double diff = fabs(gl - gr);
+				sum += weight*(diff < P.max_color_diff ? diff : P.max_color_diff);   // std::min(MAX_COLOR_DIFF, diff)
+				totalWeight += weight;
+				++numPixels;
+			}
+		}
+	}
+	if (numPixels <= 4 || totalWeight <= 1e-10) return P.bad_ret;
+	return sum / totalWeight;
 }
 
 // cost_ncc in the reference's arithmetic for ANY validity pattern (a skipped tap adds +0.0: the same sums, same order as

@@ -112,10 +112,30 @@ std::vector<std::pair<int, int> > TwoViewStereo::epipolarCurve(int x, int y, boo
 	return curve;
 }
 
+double TwoViewStereo::pairCost(int kind, int x1, int y1, int x2, int y2, bool fromLeft) {
+	double out = std::numeric_limits<double>::quiet_NaN();
+	if (!ctx_ || !leftView || !rightView || left.isNull() || right.isNull() || !uploadViews()) return out;
+	const int32_t xy[4] = { x1, y1, x2, y2 };
+	if (srh_twoview_pair_costs(ctx_, fromLeft ? 0 : 1, fromLeft ? 1 : 0, &params_, kind, 1, xy, &out) != SRH_OK) {
+		error_ = srh_last_error();
+		return std::numeric_limits<double>::quiet_NaN();
+	}
+	return out;
+}
+
+double TwoViewStereo::cost_sad(int x1, int y1, int x2, int y2, bool fromLeft) {
+	return pairCost(SRH_COST_SAD, x1, y1, x2, y2, fromLeft);
+}
+
+double TwoViewStereo::cost_ncc(int x1, int y1, int x2, int y2, bool fromLeft) {
+	return pairCost(SRH_COST_NCC, x1, y1, x2, y2, fromLeft);
+}
+
 void TwoViewStereo::computeCostVolumes(CameraPtr leftView_, CameraPtr rightView_) {
 	if (!ctx_ || !leftView_ || !rightView_) return;
 	leftView = leftView_; rightView = rightView_;
 	if (!uploadViews()) return;
+	if (srh_set_option(ctx_, "cost", costKind) != SRH_OK) { error_ = srh_last_error(); return; }
 	if (srh_twoview_wta(ctx_, 0, 1, &params_, 0, 0) != SRH_OK || srh_twoview_wta(ctx_, 1, 0, &params_, 0, 0) != SRH_OK ||
 	    srh_view_depth_download(ctx_, 0, computedDepthLeft.data()) != SRH_OK ||
 	    srh_view_depth_download(ctx_, 1, computedDepthRight.data()) != SRH_OK)
@@ -167,6 +187,11 @@ void TwoViewStereo::computeDepthMaps() {
 	TwoViewHooks hooks = { this, &progressUpdate, &stageUpdate };
 	srh_set_hooks(ctx_, cancelFlag(), onProgress, &hooks);
 	srh_set_option(ctx_, "filter_invalid", filterFlags);
+	if (srh_set_option(ctx_, "cost", costKind) != SRH_OK) {
+		error_ = srh_last_error();
+		srh_set_hooks(ctx_, nullptr, nullptr, nullptr);
+		return;
+	}
 	const int rc_ = srh_twoview_compute(ctx_, 0, 1, &params_, computedDepthLeft.data(), computedDepthRight.data());
 	srh_set_hooks(ctx_, nullptr, nullptr, nullptr);
 	if (rc_ == SRH_E_CANCELLED) return;              // reference: silent return on cancel

@@ -34,6 +34,11 @@ public:
 	void setFilterInvalid(int flags) { filterFlags = flags; }
 	int filterInvalid() const { return filterFlags; }
 
+	// Matching cost of the WTA: SRH_COST_NCC (0, default: cost_ncc, as the reference's computeCostVolumes) or SRH_COST_SAD
+	// (1: cost_sad, twoviewstereo.cpp:864-905).  The WTA, ratio test, cross-check and hole filling are the same for both.
+	void setCostFunction(int kind) { costKind = kind; }
+	int costFunction() const { return costKind; }
+
 	// Candidate pixels, in visiting order, of pixel (x,y) of the left (fromLeft) or right view in the
 	// other view.  The reference's public epipolarCurve (twoviewstereo.hpp:66-70) takes the unprojected
 	// ray, camera offset, plane normal, mask and view; all of them follow from the pixel and the
@@ -62,12 +67,20 @@ protected:
 	double depthFromLabel(int label) const;
 	// ... and the hole filling of both maps (:676-767, progress 6): the compiled body, the row gap fill -- or, after
 	// setFilterInvalid, what its flags ask for (with the median: also progress 7 and the #if 0 half, :769-810).
-	// (cost_sad is never called in the reference and has no counterpart here; weightedMedian is per pixel and stateful
-	// on the reference's weightFuncs: the device does it inside filterInvalidPixels.)
+	// (weightedMedian is per pixel and stateful on the reference's weightFuncs: the device does it inside
+	// filterInvalidPixels.)
 	void filterInvalidPixels();
+	// the two matching costs (twoviewstereo.hpp:92-99) of reference pixel (x1,y1) against (x2,y2) of the other view.  The
+	// reference passes the two images and masks and reads the window of weightFuncs, which init_weights has set for
+	// (x1,y1) beforehand; as with epipolarCurve, all of that follows from the pixels and the direction: fromLeft = the
+	// left view is the reference, else the right one.  The window is built on the device for each call (one round trip:
+	// srh_twoview_pair_costs takes many pairs at once).  NaN when the device call fails (lastError()).
+	double cost_sad(int x1, int y1, int x2, int y2, bool fromLeft = true);
+	double cost_ncc(int x1, int y1, int x2, int y2, bool fromLeft = true);
 
 private:
 	bool uploadViews();
+	double pairCost(int kind, int x1, int y1, int x2, int y2, bool fromLeft);
 	void colorize(const DepthMap &d, Image &out) const;
 	void colorFromDepth(double depth, uint8_t rgb[3]) const;
 
@@ -81,6 +94,7 @@ private:
 	DepthMap computedDepthLeft, computedDepthRight;
 	srh_params params_;
 	int filterFlags = 0;
+	int costKind = SRH_COST_NCC;
 	srh_context *ctx_;
 	std::string error_;
 };

@@ -167,6 +167,7 @@ void TwoViewStereo::computeDepthMaps() {
 	params_.min_depth = minDepth; params_.max_depth = maxDepth;
 	params_.num_depth_levels = numDepthLevels; params_.image_scale = imageScale;
 	if (!uploadViews()) return;
+	if (srh_set_option(ctx_, "cost", costKind) != SRH_OK) { error_ = srh_last_error(); return; }
 	emit progressUpdate(1);
 	emit stageUpdate("Computing cost volume for left image...");
 	if (srh_twoview_wta(ctx_, 0, 1, &params_, 0, 0) != SRH_OK) { error_ = srh_last_error(); return; }
@@ -190,6 +191,22 @@ void TwoViewStereo::computeDepthMaps() {
 	emit progressUpdate(8);
 	emit stageUpdate("Finished!");
 }
+
+double TwoViewStereo::pairCost(int kind, int x1, int y1, int x2, int y2, bool fromLeft) {
+	double out = std::numeric_limits<double>::quiet_NaN();
+	if (!ctx_ || left.w <= 0 || right.w <= 0 || !uploadViews()) return out;
+	srh_params p = params_;
+	p.min_depth = minDepth; p.max_depth = maxDepth; p.num_depth_levels = numDepthLevels; p.image_scale = imageScale;
+	const int32_t xy[4] = { x1, y1, x2, y2 };
+	if (srh_twoview_pair_costs(ctx_, fromLeft ? 0 : 1, fromLeft ? 1 : 0, &p, kind, 1, xy, &out) != SRH_OK) {
+		error_ = srh_last_error();
+		return std::numeric_limits<double>::quiet_NaN();
+	}
+	return out;
+}
+
+double TwoViewStereo::cost_sad(int x1, int y1, int x2, int y2, bool fromLeft) { return pairCost(SRH_COST_SAD, x1, y1, x2, y2, fromLeft); }
+double TwoViewStereo::cost_ncc(int x1, int y1, int x2, int y2, bool fromLeft) { return pairCost(SRH_COST_NCC, x1, y1, x2, y2, fromLeft); }
 
 void TwoViewStereo::filterInvalidPixels() {
 	if (!ctx_ || !uploadViews()) return;

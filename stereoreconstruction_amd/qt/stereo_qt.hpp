@@ -117,6 +117,9 @@ public:
 	QString lastError() const { return error_; }
 	// hole filling after the cross-check (SRH_FILTER_* flags); 0 (default) = the reference, call site under #if 0
 	void setFilterInvalid(int flags) { filterFlags = flags; }
+	// matching cost of the WTA: SRH_COST_NCC (0, default: cost_ncc, the reference's) or SRH_COST_SAD (1: cost_sad)
+	void setCostFunction(int kind) { costKind = kind; }
+	int costFunction() const { return costKind; }
 
 public: // Task implementation continued: public in the reference as well (stereo/twoviewstereo.hpp:50-52)
 	void runTask() { computeDepthMaps(); }
@@ -125,8 +128,15 @@ protected:
 	// stereo/twoviewstereo.hpp, protected: the compiled body (row gap fill of both maps, progress 6), or what
 	// setFilterInvalid asks for (the median: progress 7 and the #if 0 half, twoviewstereo.cpp:769-810)
 	void filterInvalidPixels();
+	// stereo/twoviewstereo.hpp:92-99, protected: cost_sad / cost_ncc of reference pixel (x1,y1) against (x2,y2) of the
+	// other view.  The reference passes both images and masks and reads weightFuncs, set by init_weights for (x1,y1); as
+	// with curveOfPixel all of it follows from the pixels and the direction (fromLeft: the left view is the reference).
+	// One device round trip per call (srh_twoview_pair_costs takes many pairs); NaN when it fails (lastError()).
+	double cost_sad(int x1, int y1, int x2, int y2, bool fromLeft = true);
+	double cost_ncc(int x1, int y1, int x2, int y2, bool fromLeft = true);
 
 private:
+	double pairCost(int kind, int x1, int y1, int x2, int y2, bool fromLeft);
 	QImage colorize(const DepthMap &d, int w, int h) const;
 	CameraPtr leftView, rightView;
 	srh_camera leftCam, rightCam;                          // snapshots taken by the constructor (srq::cameraInfo)
@@ -139,6 +149,7 @@ private:
 	DepthMap computedDepthLeft, computedDepthRight;
 	srh_params params_;
 	int filterFlags = 0;
+	int costKind = SRH_COST_NCC;
 	srh_context *ctx_;
 	mutable bool uploaded_ = false;                        // views resident on the device (epipolarCurve before computeDepthMaps)
 	bool uploadViews() const;
