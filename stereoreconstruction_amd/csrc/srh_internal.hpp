@@ -177,7 +177,7 @@ struct Counters {
 	unsigned long long cert_overflow;     // certified redo: a flagged pixel with more candidates than the wave rescan holds (the pass is repeated in mode 0)
 	unsigned long long scan_tiles_template, scan_tiles_walked;   // dense TwoView scan: 64-pixel tiles settled by the template scan / left to the per-pixel walk
 	unsigned long long mvs_waves_staged, mvs_waves_listed;   // MultiViewStereo walk kernel: waves (with candidates) left to the staged / the gathering cost kernel
-	unsigned int strip_ticket, strip_pad; // strip kernel: work-item counter of the current launch
+	unsigned int strip_ticket, strip_ticket_border;   // strip kernel: work-item counters of the current launch (main, border instantiation)
 	unsigned long long dbg_cycles, dbg_blocks, dbg_total_cycles, dbg_waves;   // SRH_DENSE_DBG=2 instrumentation
 	unsigned long long dbg_phase[8];
 	unsigned long long dbg_wave[64];      // diagnostic build: phase k of wave w of a workgroup at [8*k + w]

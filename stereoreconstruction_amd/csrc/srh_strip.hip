@@ -36,6 +36,7 @@ void strip_exp_set(int repeat) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_strip_exp_
 #define ST_TP 32                       // pixels per tile (= SRH_WTILE)
 #define ST_NCB 8                       // candidate columns per block
 #define ST_CHUNK 320                   // candidate columns a tile can hold in LDS
+#define ST_BROWS 1                     // rows per work item of the border instantiation
 
 typedef __attribute__((address_space(3))) void st_lds_void;
 typedef __attribute__((address_space(1))) const void st_gbl_void;
@@ -124,11 +125,21 @@ struct StripArgs {
 	double *cost; int cstride;              // cost rows, tile-transposed: ((tile*cstride) + k)*32 + pixel
 	Counters *cnt;
 	int n1, n2;                             // rows [0,n1) in 16-row items, [n1,n2) in 8-row items, the rest in 4-row items
+	                                        // (border instantiation: rows [0,n1) and [n2,nrows), in ST_BROWS-row items)
 	int nitems;
 	double weight_cutoff, bad_ret, max_color_diff;
 	CertBound cb;                           // certified arithmetic (AR == 3): the constants of the error bound, srh_internal.hpp
 	int redo;                               // certified forms: 1 = uncovered candidates re-evaluated in place in the reference's arithmetic (default); 0 = raw
 };
+
+// work items of the main instantiation: tall items first -- 3/4 of the rows in 16-row items, 2/3 of the rest in 8-row items,
+// the remainder in 4-row items
+static void strip_items(StripArgs &a) {
+	a.n1 = ((a.nrows*3/4)/16)*16;
+	a.n2 = a.n1 + (((a.nrows - a.n1)*2/3)/8)*8;
+	const int nseg = a.n1/16 + (a.n2 - a.n1)/8 + (a.nrows - a.n2 + 3)/4;
+	a.nitems = nseg*((a.W + ST_TP - 1)/ST_TP);
+}
 
 template <int R, int NBUF>
 struct StripSmem {
@@ -325,7 +336,16 @@ __device__ __noinline__ void strip_select_block(const StripSmem<R, NBUF> &S, int
 // whose error bound (srh_internal.hpp, CertBound) is not below cb.e0 is stored as NaN, a value above max_color_diff + e0
 // as max_color_diff itself (the exact cost is then max_color_diff too), anything else unclamped -- the certified scan
 // does the rest.  Candidates of the select forms are evaluated in the reference's arithmetic in every mode.
-template <int R, int NWV, int NBUF, int AR>
+//
+// BORDER: the same kernel over the rows whose window the image's top or bottom edge cuts (y < R, y > H - 2 - R; the main
+// instantiation is launched without them).  Every candidate of such a pixel used to take the blocked select form.  Here a
+// pixel whose taps on the window rows inside the image, [ra, rb), are all usable -- with a candidate whose window in the
+// other view is usable on those rows -- runs the fast form's exact two sweeps over [ra, rb) only: the taps the reference
+// skips are exactly the rows left out, so the sums are its own (twoviewstereo.cpp:917-976, same order, same operations).
+// The pixel's meanL, totalWeight and sum2 over those rows and the per-column "usable" bytes are worked out per tile into
+// the LDS copies of pconst and `full`; the band buffers are not touched (pconst slot 3 stays 0 there), so the certified
+// scan keeps treating the pixel's costs as the reference's very numbers (cert_pixel_exact) -- which they are, in every mode.
+template <int R, int NWV, int NBUF, int AR, bool BORDER>
 __global__ __launch_bounds__(NWV*64, 2)
 void twoview_strip_cost_kernel(const StripArgs A)
 {
@@ -399,14 +419,28 @@ void twoview_strip_cost_kernel(const StripArgs A)
 
 	for (;;) {
 		// ---- next work item: (row segment, tile column); tall segments first, so the tail of the launch is short
-		if (tid == 0) S.item = (int)atomicAdd(&A.cnt->strip_ticket, 1u);
+		if (tid == 0) S.item = (int)atomicAdd(BORDER ? &A.cnt->strip_ticket_border : &A.cnt->strip_ticket, 1u);
 		__syncthreads();                           // also: every wave has left the previous item's last tile
 		const int item = __builtin_amdgcn_readfirstlane(S.item);
 		ST_STAMP(0);                                  // ticket + waiting for the workgroup's other waves
 		if (item >= A.nitems) break;
-		const int seg = item / tiles_per_row, tx = item - seg*tiles_per_row;
+		int seg = item / tiles_per_row, tx = item - seg*tiles_per_row;
+		if (BORDER) {
+			// tile column major, the two edge columns first: their corner pixels leave the most to phase 2, so they should not
+			// be the launch's last items
+			const int nseg = (A.n1 + ST_BROWS - 1)/ST_BROWS + (A.nrows - A.n2 + ST_BROWS - 1)/ST_BROWS;
+			const int k = item / nseg;
+			seg = item - k*nseg;
+			tx = k == 0 ? 0 : k == 1 ? tiles_per_row - 1 : k - 1;
+		}
 		int ya, nh;
-		{
+		if (BORDER) {
+			// rows [0, n1) and [n2, nrows) of the band, in items of up to ST_BROWS rows
+			const int st = (A.n1 + ST_BROWS - 1)/ST_BROWS;
+			if (seg < st) { ya = seg*ST_BROWS; nh = A.n1 - ya; }
+			else { ya = A.n2 + (seg - st)*ST_BROWS; nh = A.nrows - ya; }
+			if (nh > ST_BROWS) nh = ST_BROWS;
+		} else {
 			const int s16 = A.n1 >> 4, s8 = (A.n2 - A.n1) >> 3;
 			if (seg < s16) { ya = seg*16; nh = 16; }
 			else if (seg < s16 + s8) { ya = A.n1 + (seg - s16)*8; nh = 8; }
@@ -452,9 +486,9 @@ void twoview_strip_cost_kernel(const StripArgs A)
 		};
 		static_assert(RW*8 <= 3*1024, "three pieces per row of the other view");
 		auto issue_full = [&](int fy, int fb) {
-			// bytes [cs, cs + RW) of row fy, from the 4-byte granule that holds the first one
+			// bytes [cs, cs + RW) of row fy, from the 4-byte granule that holds the first one (BORDER: worked out per tile)
 			const size_t a0 = (size_t)(fy + SRH_PADY)*SP + (size_t)(cs + SRH_PADL);
-			if (wv == NWV - 1) st_dma4(A.oth_fullp + (a0 & ~(size_t)3), &S.full[fb][0], (RW + 4 + 3) & ~3, lane);
+			if (!BORDER && wv == NWV - 1) st_dma4(A.oth_fullp + (a0 & ~(size_t)3), &S.full[fb][0], (RW + 4 + 3) & ~3, lane);
 		};
 
 		bool first = true;
@@ -521,8 +555,59 @@ void twoview_strip_cost_kernel(const StripArgs A)
 				issue_full(y + 1, nxt);
 				issue_tile_inputs(r + 1, nxt, wnxt, true, NBUF == 2);
 			}
-			const int foff = (int)(((size_t)(y + SRH_PADY)*SP + (size_t)(cs + SRH_PADL)) & 3);   // first byte inside its granule
+			const int foff = BORDER ? 0 : (int)(((size_t)(y + SRH_PADY)*SP + (size_t)(cs + SRH_PADL)) & 3);   // first byte inside its granule
 			const unsigned char *rfull = &CS.full[cur][foff];
+			// window rows on image rows with usable taps at all (rows 0 .. H - 2: the last row's gray_tv is NaN like everything
+			// outside), as phase 2 has them; [0, WS) as constants in the main instantiation
+			const int bra = BORDER ? (y < R ? R - y : 0) : 0;
+			const int brb = BORDER ? (y + R > A.H - 2 ? WS - (y + R - (A.H - 2)) : WS) : WS;
+			if (BORDER) {
+				// the other view: per staged column, usable on every row of [bra, brb) (full[nxt] is free: no "full" DMA here) ...
+				unsigned char *cok = &S.full[nxt][0];
+				for (int k = tid; k < RW; k += NT) {
+					bool ok = true;
+					for (int row = bra; row < brb; ++row) {
+						const int sl = s0 + row >= NS ? s0 + row - NS : s0 + row;
+						const double v = CS.rt[sl][k];
+						ok = ok && v == v;
+					}
+					cok[k] = ok ? 1 : 0;
+				}
+				// ... and the pixel's constants over [bra, brb), one lane per pixel, in the reference's order and operations
+				if (g == 0) {
+					bool all = x < W;
+					double mL = 0, tw = 0;
+					for (int row = bra; row < brb; ++row) {
+						const int sl = s0 + row >= NS ? s0 + row - NS : s0 + row;
+						for (int col = 0; col < WS; ++col) {
+							const double gl = CS.lt[sl][i + col], wt = CS.w[wcur][row][i][col];
+							all = all && gl == gl && wt > A.weight_cutoff;
+							mL += wt*gl;
+							tw += wt;
+						}
+					}
+					double s2 = 0;
+					if (all && !(tw < 1e-10)) {
+						mL /= tw;
+						for (int row = bra; row < brb; ++row) {
+							const int sl = s0 + row >= NS ? s0 + row - NS : s0 + row;
+							for (int col = 0; col < WS; ++col) {
+								const double t = CS.w[wcur][row][i][col]*CS.lt[sl][i + col] - mL;
+								s2 += t*t;
+							}
+						}
+					} else all = false;
+					S.pc[cur][i][0] = mL; S.pc[cur][i][1] = tw; S.pc[cur][i][2] = s2; S.pc[cur][i][3] = all ? 1.0/tw : 0.0;
+				}
+				__syncthreads();
+				// candidate column cs + k: its window covers staged columns k .. k + 2R
+				for (int k = tid; k < CHUNK + NCB; k += NT) {
+					bool ok = true;
+					for (int d = 0; d < WS; ++d) ok = ok && cok[k + d] != 0;
+					S.full[cur][k] = ok ? 1 : 0;
+				}
+				__syncthreads();
+			}
 
 			// ---- which form do the tile's candidates need?  (uniform: every wave looks at the whole tile)
 			bool need_general = false;
@@ -595,26 +680,29 @@ void twoview_strip_cost_kernel(const StripArgs A)
 					auto two_sweeps = [&](auto fma_c, auto cert_c) {
 						constexpr bool FMAc = decltype(fma_c)::value, CERTc = decltype(cert_c)::value;
 						const double mL = CS.pc[cur][i][0], tw = CS.pc[cur][i][1], s2 = CS.pc[cur][i][2];
+						// window rows [ra, rb): all of them, as compile-time bounds, outside the border instantiation
+						const int ra = BORDER ? bra : 0, rb = BORDER ? brb : WS;
+						const int sa = BORDER ? (s0 + ra >= NS ? s0 + ra - NS : s0 + ra) : s0;
 						// Both passes are modulo-scheduled by hand (see twoview_dense_cost_kernel): a register is refilled
 						// with the next row's value right after its last use, so the LDS latency is always a row ahead.
 						double r_[NR], wv_[WS], acc[NCB];
 						{
-							const double2 *rp = reinterpret_cast<const double2 *>(rbase + s0*RW + rc);
-							const double2 *wp = reinterpret_cast<const double2 *>(&CS.w[wcur][0][i][0]);
+							const double2 *rp = reinterpret_cast<const double2 *>(rbase + sa*RW + rc);
+							const double2 *wp = reinterpret_cast<const double2 *>(&CS.w[wcur][ra][i][0]);
 #pragma unroll
 							for (int m = 0; m < NR/2; ++m) { const double2 v = rp[m]; r_[2*m] = v.x; r_[2*m + 1] = v.y; }
 #pragma unroll
 							for (int m = 0; m < (WS - 1)/2; ++m) { const double2 v = wp[m]; wv_[2*m] = v.x; wv_[2*m + 1] = v.y; }
-							wv_[WS - 1] = CS.w[wcur][0][i][WS - 1];
+							wv_[WS - 1] = CS.w[wcur][ra][i][WS - 1];
 						}
 #pragma unroll
 						for (int j = 0; j < NCB; ++j) acc[j] = 0.0;
 						__builtin_amdgcn_s_waitcnt(0xC07F);              // lgkmcnt(0): the pre-header's reads have landed
 #pragma unroll 1
-						for (int row = 0; row < WS; ++row) {
+						for (int row = ra; row < rb; ++row) {
 							int seen = 0;
 							prog_step(1, seen);
-							const int nrow = row + 1 < WS ? row + 1 : 0;          // last refill = row 0, for pass 2
+							const int nrow = row + 1 < rb ? row + 1 : ra;         // last refill = row ra, for pass 2
 							const int nsl = s0 + nrow >= NS ? s0 + nrow - NS : s0 + nrow;
 							const double2 *rp = reinterpret_cast<const double2 *>(rbase + nsl*RW + rc);
 							const double2 *wp = reinterpret_cast<const double2 *>(&CS.w[wcur][nrow][i][0]);
@@ -645,15 +733,15 @@ void twoview_strip_cost_kernel(const StripArgs A)
 						}
 						double mR[NCB], s1[NCB], s3[NCB], av[WS];
 #pragma unroll
-						for (int col = 0; col < WS; ++col) av[col] = CS.lt[s0][i + col];
+						for (int col = 0; col < WS; ++col) av[col] = CS.lt[sa][i + col];
 #pragma unroll
 						for (int j = 0; j < NCB; ++j) { mR[j] = acc[j]/tw; s1[j] = 0.0; s3[j] = 0.0; }
 						__builtin_amdgcn_s_waitcnt(0xC07F);
 #pragma unroll 1
-						for (int row = 0; row < WS; ++row) {
+						for (int row = ra; row < rb; ++row) {
 							int seen = 0;
 							prog_step(3, seen);
-							const int nrow = row + 1 < WS ? row + 1 : 0;
+							const int nrow = row + 1 < rb ? row + 1 : ra;
 							const int nsl = s0 + nrow >= NS ? s0 + nrow - NS : s0 + nrow;
 							const double2 *rp = reinterpret_cast<const double2 *>(rbase + nsl*RW + rc);
 							const double2 *wp = reinterpret_cast<const double2 *>(&CS.w[wcur][nrow][i][0]);
@@ -711,7 +799,9 @@ void twoview_strip_cost_kernel(const StripArgs A)
 							__builtin_amdgcn_sched_barrier(0);
 						}
 					};
-					if (fast && ONEPASS && !pix_exact) {
+					if (BORDER) {
+						if (fast) two_sweeps(std::false_type(), std::false_type());   // (the select forms' arithmetic, in every mode)
+					} else if (fast && ONEPASS && !pix_exact) {
 						// ---- certified ONE-PASS form (srh_internal.hpp, CertBound): P = sum w r, Q = sum ((w l - meanL) w) r,
 						// U = sum w^2 r^2 in one sweep over the window; registers are refilled in place a row ahead, as below
 						const double mL = CS.pc[cur][i][0], itw = CS.pc[cur][i][3], s2 = CS.pc[cur][i][2];   // (slot 3 of a pixel with every tap usable: 1/totalWeight)
@@ -782,7 +872,7 @@ void twoview_strip_cost_kernel(const StripArgs A)
 							if (st) crow[(size_t)(c0 + j - e_min)*ST_TP] = !okc ? __builtin_nan("") : (v > mhi ? mcd : v);
 						}
 					} else if (fast && !ONEPASS && !pix_exact) two_sweeps(std::integral_constant<bool, FMA>(), std::integral_constant<bool, CERT>());
-					if (fast && CERT && (pix_exact || bad_blk)) two_sweeps(std::false_type(), std::false_type());   // (bad_blk is only raised when A.redo)
+					if (!BORDER && fast && CERT && (pix_exact || bad_blk)) two_sweeps(std::false_type(), std::false_type());   // (bad_blk is only raised when A.redo)
 				}
 			}
 			if (NWV == 8) __builtin_amdgcn_s_setprio(2);
@@ -896,26 +986,48 @@ void twoview_strip_cost_kernel(const StripArgs A)
 #undef ST_STAMP
 }
 
-template <int R, int NWV, int NBUF, int AR>
+template <int R, int NWV, int NBUF, int AR, bool BORDER>
 static void launch_strip_variant(hipStream_t st, const StripArgs &a, int num_cus)
 {
 	typedef StripSmem<R, NBUF> Smem;
 	size_t lds = sizeof(Smem);
-	(void)hipFuncSetAttribute((const void *)twoview_strip_cost_kernel<R, NWV, NBUF, AR>,
+	(void)hipFuncSetAttribute((const void *)twoview_strip_cost_kernel<R, NWV, NBUF, AR, BORDER>,
 	                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 	int grid = num_cus*(NBUF == 2 ? 1 : 2);
 	if (grid > a.nitems) grid = a.nitems;
 	if (grid < 1) grid = 1;
-	hipLaunchKernelGGL((twoview_strip_cost_kernel<R, NWV, NBUF, AR>), dim3((unsigned)grid), dim3(NWV*64), lds, st, a);
+	hipLaunchKernelGGL((twoview_strip_cost_kernel<R, NWV, NBUF, AR, BORDER>), dim3((unsigned)grid), dim3(NWV*64), lds, st, a);
 }
 
+// The band's rows whose window the image's top or bottom edge cuts, [0, t) and [b, nrows), go to the border instantiation
+// (one for every arithmetic: its fast blocks and select forms are the reference's arithmetic); the main instantiation
+// gets the rows between as a band of their own -- the same kernel binary, on buffers offset by t rows.
 template <int R, int NWV, int NBUF>
 static void launch_strip_arith(hipStream_t st, const StripArgs &a, int num_cus, int arith)
 {
-	if (arith == 5) launch_strip_variant<R, NWV, NBUF, 5>(st, a, num_cus);
-	else if (arith == 3) launch_strip_variant<R, NWV, NBUF, 3>(st, a, num_cus);
-	else if (arith == 1) launch_strip_variant<R, NWV, NBUF, 1>(st, a, num_cus);
-	else launch_strip_variant<R, NWV, NBUF, 0>(st, a, num_cus);
+	const int tiles_per_row = (a.W + ST_TP - 1)/ST_TP;
+	const int t = std::min(std::max(R - a.y0, 0), a.nrows);
+	const int b = std::min(std::max(a.H - 1 - R - a.y0, t), a.nrows);
+	if (b > t) {
+		StripArgs m = a;
+		const size_t tiles = (size_t)t*tiles_per_row;
+		m.y0 = a.y0 + t; m.nrows = b - t;
+		m.wimg = a.wimg + tiles*(ST_TP*StripSmem<R, NBUF>::WPIX);
+		m.pconst = a.pconst + (size_t)t*a.W*SRH_PC;
+		m.prange = a.prange + (size_t)t*a.W;
+		m.cost = a.cost + tiles*(size_t)a.cstride*ST_TP;
+		strip_items(m);
+		if (arith == 5) launch_strip_variant<R, NWV, NBUF, 5, false>(st, m, num_cus);
+		else if (arith == 3) launch_strip_variant<R, NWV, NBUF, 3, false>(st, m, num_cus);
+		else if (arith == 1) launch_strip_variant<R, NWV, NBUF, 1, false>(st, m, num_cus);
+		else launch_strip_variant<R, NWV, NBUF, 0, false>(st, m, num_cus);
+	}
+	if (t > 0 || b < a.nrows) {
+		StripArgs e = a;
+		e.n1 = t; e.n2 = b;
+		e.nitems = ((t + ST_BROWS - 1)/ST_BROWS + (a.nrows - b + ST_BROWS - 1)/ST_BROWS)*tiles_per_row;
+		launch_strip_variant<R, NWV, NBUF, 0, true>(st, e, num_cus);
+	}
 }
 
 // form: 0 = by the candidate range (16 block lanes only pay when a pixel has at least 17 blocks), 4 / 8 = forced
@@ -937,11 +1049,6 @@ bool launch_twoview_strip_cost(hipStream_t st, const ViewDev *views, int ref, in
 	a.wimg = wimg; a.pconst = pconst; a.prange = prange;
 	a.ref_tvp = ref_tvp; a.oth_tvp = oth_tvp; a.oth_fullp = oth_fullp;
 	a.cost = cost; a.cstride = cstride; a.cnt = cnt;
-	// tall items first: 3/4 of the rows in 16-row items, 2/3 of the rest in 8-row items, the remainder in 4-row items
-	a.n1 = ((nrows*3/4)/16)*16;
-	a.n2 = a.n1 + (((nrows - a.n1)*2/3)/8)*8;
-	const int nseg = a.n1/16 + (a.n2 - a.n1)/8 + (nrows - a.n2 + 3)/4;
-	a.nitems = nseg*((width + ST_TP - 1)/ST_TP);
 	a.weight_cutoff = P.weight_cutoff; a.bad_ret = P.bad_ret; a.max_color_diff = P.max_color_diff;
 	a.cb = cert_bound(P);
 	a.redo = raw ? 0 : 1;
