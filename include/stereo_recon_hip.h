@@ -218,9 +218,21 @@ enum { SRH_COST_NCC = 0, SRH_COST_SAD = 1 };
  *   "cost"            CHANGES RESULTS.  SRH_COST_NCC (0, default): the weighted NCC of cost_ncc.  SRH_COST_SAD (1): the
  *                     support-weighted, truncated SAD of cost_sad (min(|gl - gr|, max_color_diff) per tap, the left tap
  *                     sample() and the right tap pixel() behind both masks; bad_ret for numPixels <= 4 or totalWeight <=
- *                     1e-10), the WTA, ratio test and cross-check unchanged.  SAD runs on the candidate lists (rectified
- *                     rigs too: there is no dense, strip or fused SAD kernel) in the reference's arithmetic; "arith" does
- *                     not apply to it.  srh_twoview_cost_rows is SRH_E_UNSUPPORTED under SAD.
+ *                     1e-10), the WTA, ratio test and cross-check unchanged.  SAD runs in the reference's arithmetic;
+ *                     "arith" does not apply to it.  By default it runs on the candidate lists, rectified rigs too; with
+ *                     "sad_dense" = 1 a rectified rig takes the dense plan, its cost rows filled by the persistent SAD
+ *                     strip kernel (there is no per-tile and no fused SAD kernel).  srh_twoview_cost_rows under SAD needs
+ *                     "sad_dense" = 1 (else SRH_E_UNSUPPORTED).
+ *   "sad_dense"       0 (default): cost_sad on the candidate lists.  1: under "cost" = SRH_COST_SAD a pair that is row-aligned
+ *                     (the rig test of the NCC dense plan), with window radius 5 or 2, "force_generic" off and a candidate
+ *                     range that fits the strip kernel's chunk (cstride + 32 <= 320 columns) takes the row-aligned dense
+ *                     plan: twoview_strip_sad_kernel fills the cost rows (every column of every pixel's range, for every
+ *                     image size and band), the NCC plan's range, template and scan kernels run unchanged behind it,
+ *                     uncertified.  srh_stats.used_dense_path and used_strip_kernel are then 1.  Any other pair -- a rig
+ *                     that is not row-aligned, another radius, a wider range, a plan the device refutes (a range wider
+ *                     than the chunk after all, a candidate off its row, "force_dense" included) -- runs on the row-run,
+ *                     list-order or walk kernels exactly as with 0.  The fused plan is never taken under SAD.  Nothing
+ *                     changes under "cost" = SRH_COST_NCC.  Identical bits: a tuning switch like "strip" and "tscan".
  *   "filter_invalid"  0 (default, as the reference's call site under #if 0): srh_twoview_compute ends with the cross-check;
  *                     SRH_FILTER_* flags (1 gaps, 2 median, 3 both): it then runs srh_view_filter_invalid on both maps,
  *                     with progress steps 6 "Filling invalid pixels..." and, with the median, 7 "Filtering invalid pixels..."
@@ -270,7 +282,9 @@ int  srh_twoview_wta(srh_context *ctx, int ref_slot, int oth_slot, const srh_par
  * [row][tile of 32 pixels][k = column - range.lo, < *cstride_out][pixel of the tile]; an entry the kernels never wrote
  * reads as a NaN with all bits set.  range_out: (lo, hi) per pixel, hi < lo = no candidates.  cost_out == NULL: only
  * *cstride_out (to size the buffer: rows * ceil(w/32)*32 * cstride doubles).  The rows must fit one band;
- * SRH_E_UNSUPPORTED when the pair does not take the dense plan. */
+ * SRH_E_UNSUPPORTED when the pair does not take the dense plan.  Under "cost" = SRH_COST_SAD with "sad_dense" = 1: the
+ * SAD cost rows in the same layout, *used_strip_kernel = 1; form must be 0 (else SRH_E_INVALID), raw is ignored; with
+ * "sad_dense" = 0: SRH_E_UNSUPPORTED. */
 int  srh_twoview_cost_rows(srh_context *ctx, int ref_slot, int other_slot, const srh_params *p, int y0, int y1, int form, int raw,
                            double *cost_out, size_t cost_doubles, int32_t *range_out, int *cstride_out, int *used_strip_kernel);
 /* cost_sad (kind SRH_COST_SAD) or cost_ncc (SRH_COST_NCC) of n arbitrary pairs: xy holds n x (x1, y1, x2, y2), (x1, y1) a

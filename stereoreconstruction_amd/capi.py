@@ -444,7 +444,8 @@ class Context:
     # -- MultiViewStereo
     def twoview_cost_rows(self, ref, oth, p, y0, y1, form, raw=False):
         """srh_twoview_cost_rows (diagnostic) -> (cost (rows, w, cstride) float64 with cost[r, x, k] the cost of column
-        lo + k, range (rows, w, 2) int32, used_strip_kernel)."""
+        lo + k, range (rows, w, 2) int32, used_strip_kernel).  Under set_option("cost", COST_SAD) the rows are cost_sad's and
+        need set_option("sad_dense", 1) and form 0 (anything else raises); an entry no kernel wrote is a NaN with all bits set."""
         w, h = self.view_size(ref)
         cs, us = C.c_int(0), C.c_int(0)
         _check(lib().srh_twoview_cost_rows(self._h, ref, oth, C.byref(p), y0, y1, form, 1 if raw else 0, None, 0, None, C.byref(cs), C.byref(us)))

@@ -215,6 +215,9 @@ struct ViewHost {
 	DevBuf<uint8_t>  fullp; int fullp_r = 0;
 	DevBuf<uint8_t>  fulls; int fulls_r = 0;            // cost_sad's "window fully usable" plane of radius fulls_r (srh_sad.hip): its own
 	                                                      // validity (pixel() behind the mask), so never the NCC plane `full`
+	// cost_sad on the dense plan (srh_sad_strip.hip): NaN-bordered copy of gray where the mask is WHITE, zero-bordered copy of `fulls`
+	DevBuf<double>   grayp; bool grayp_valid = false;
+	DevBuf<uint8_t>  fullsp; int fullsp_r = 0;
 	// how the candidate lists of this view against slot j are best evaluated, learnt from the last run:
 	// 0 unknown, 1 row runs (srh_rows.hip), 2 list order (srh_list.hip: steep curves)
 	uint8_t   list_mode[SRH_MAX_VIEWS] = {0};
@@ -342,6 +345,7 @@ struct srh_context {
 	int filter_gap_width = 2;                           // option "filter_gap_width" (GAP_WIDTH_THRESHOLD)
 	int filter_replay = 0;                              // option "filter_replay": every median hole by the exact replay (test hook)
 	int cost_kind = SRH_COST_NCC;                       // option "cost": the TwoView matching cost, SRH_COST_NCC or SRH_COST_SAD
+	int sad_dense = 0;                                  // option "sad_dense": cost_sad of row-aligned rigs on the dense plan (srh_sad_strip.hip)
 };
 
 static bool cancelled(srh_context *c) { return c->cancel && *c->cancel; }
@@ -669,7 +673,7 @@ extern "C" int srh_create(int device, srh_context **out) {
 static void free_view(ViewHost &v) {
 	if (v.rgba || v.gray || v.edges || v.tvp || v.geo5) (void)hipDeviceSynchronize();
 	v.rgba.release(); v.mask.release(); v.gray.release(); v.gray_tv.release(); v.depth.release(); v.edges.release();
-	v.full.release(); v.fulls.release(); v.tvp.release(); v.geo5.release(); v.fullp.release(); v.act.release(); v.peaks.release(); v.mrf.release();
+	v.full.release(); v.fulls.release(); v.grayp.release(); v.fullsp.release(); v.tvp.release(); v.geo5.release(); v.fullp.release(); v.act.release(); v.peaks.release(); v.mrf.release();
 	v = ViewHost();
 }
 
@@ -788,6 +792,7 @@ extern "C" int srh_set_option(srh_context *c, const char *name, long value) {
 		if (value != SRH_COST_NCC && value != SRH_COST_SAD) return fail(SRH_E_INVALID, "cost must be 0 (SRH_COST_NCC) or 1 (SRH_COST_SAD)");
 		c->cost_kind = (int)value; return SRH_OK;
 	}
+	if (!strcmp(name, "sad_dense")) { c->sad_dense = value != 0; return SRH_OK; }
 	if (!strcmp(name, "tscan")) { c->tscan = value != 0; return SRH_OK; }
 	if (!strcmp(name, "geodma")) { c->geodma = value != 0; return SRH_OK; }
 	if (!strcmp(name, "f32_form")) { c->f32_form = value != 0; return SRH_OK; }
@@ -837,7 +842,7 @@ extern "C" int srh_view_upload(srh_context *c, int slot, int w, int h,
 	}
 	v.cam = *cam;
 	v.full_r = 0; v.fulls_r = 0;                                // recomputed on demand for the new pixels
-	v.tvp_valid = false; v.fullp_r = 0; v.geo5_valid = false; v.geo5_denied = false;
+	v.tvp_valid = false; v.fullp_r = 0; v.grayp_valid = false; v.fullsp_r = 0; v.geo5_valid = false; v.geo5_denied = false;
 	v.peaks_k = 0;                                              // the top-K peaks belonged to the previous image
 	if (c->mrf_w == w && c->mrf_h == h) c->mrf_w = c->mrf_h = c->mrf_k = 0;
 	for (int j = 0; j < SRH_MAX_VIEWS; ++j) { v.list_mode[j] = 0; c->views[j].list_mode[slot] = 0; }   // new geometry
@@ -1158,6 +1163,38 @@ static void estimate_list_capacity(const srh_camera &rc, const srh_camera &oc, i
 	smax = (int)((sm + 7) & ~7L);
 }
 
+// The planes twoview_strip_sad_kernel stages from (option "sad_dense"), made on first use after an upload, on c->stream:
+// the NaN-bordered gray_tv plane (the reference side's taps), the NaN-bordered masked gray plane (the other side's) and the
+// zero-bordered copy of cost_sad's "window fully usable" plane of radius R
+static int ensure_sad_planes(srh_context *c, ViewHost &v, int R) {
+	if (!v.tvp) HIP_TRY(v.tvp.alloc(padded_size(v.w, v.h)));
+	if (!v.tvp_valid) {
+		Scope s(c, "padded_plane_kernel");
+		launch_padded_plane(c->stream, v.gray_tv, v.w, v.h, v.tvp);
+		v.tvp_valid = true;
+	}
+	if (!v.grayp) HIP_TRY(v.grayp.alloc(padded_size(v.w, v.h)));
+	if (!v.grayp_valid) {
+		Scope s(c, "padded_gray_kernel");
+		launch_padded_gray(c->stream, v.gray, v.mask, v.w, v.h, v.grayp);
+		v.grayp_valid = true;
+	}
+	if (v.fulls_r != R) {
+		if (!v.fulls) HIP_TRY(v.fulls.alloc((size_t)v.w*v.h));
+		Scope s(c, "sad_full_window_kernel");
+		launch_sad_full_window(c->stream, v.mask, v.w, v.h, R, v.fulls);
+		v.fulls_r = R;
+		v.fullsp_r = 0;
+	}
+	if (!v.fullsp) HIP_TRY(v.fullsp.alloc(padded_size(v.w, v.h)));
+	if (v.fullsp_r != R) {
+		Scope s(c, "padded_bytes_kernel");
+		launch_padded_bytes(c->stream, v.fulls, v.w, v.h, v.fullsp);
+		v.fullsp_r = R;
+	}
+	return SRH_OK;
+}
+
 extern "C" int srh_twoview_wta(srh_context *c, int ref, int oth, const srh_params *p, int y0, int y1) {
 	int rc;
 	if ((rc = check_slot(c, ref, true)) || (rc = check_slot(c, oth, true)) || (rc = check_params(p))) return rc;
@@ -1181,9 +1218,10 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 	const size_t budget = band_budget(c);
 
 	// ---- plan: dense row-aligned kernels, or the general curve-walk kernel
-	// (cost_sad: no dense, strip or fused kernel -- rectified rigs take the row-run lists too)
+	// (cost_sad: the dense plan only with option "sad_dense", its cost rows filled by twoview_strip_sad_kernel; no per-tile
+	// and no fused kernel -- without the option rectified rigs take the row-run lists too)
 	const bool sad = c->cost_kind == SRH_COST_SAD;
-	bool dense = !c->force_generic && !sad && (R == 5 || R == 2);
+	bool dense = !c->force_generic && (!sad || c->sad_dense) && (R == 5 || R == 2);
 	int cstride = 0;
 	double fx_bx = 0;
 	if (dense && !rig_is_row_aligned(L.cam, Rv.cam, &fx_bx)) {
@@ -1198,11 +1236,13 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 		if (!(p->min_depth > 0) || !(p->max_depth > 0) || !(span < 4096.0)) dense = false;
 		else cstride = (((int)ceil(span) + 3) + 7) & ~7;
 		if (cstride > W + 8) cstride = (W + 8 + 7) & ~7;
+		// cost_sad has the strip form only: a range wider than its chunk takes the candidate lists
+		if (sad && dense && cstride + SRH_WTILE > strip_chunk_columns()) dense = false;
 	}
 
 	c->last_fused = false;
 	// ---- row-aligned rig whose candidate range fits an LDS cost row: one fused kernel per band (srh_fused.hip)
-	if (dense && c->use_fused && (c->arith == 0 || c->arith == 3) && p->num_depth_levels <= SRH_FUSED_MAXC &&
+	if (dense && !sad && c->use_fused && (c->arith == 0 || c->arith == 3) && p->num_depth_levels <= SRH_FUSED_MAXC &&
 	    fx_bx*p->image_scale*fabs(1.0/p->min_depth - 1.0/p->max_depth) + 1.0 <= (double)SRH_FUSED_MAXC) {
 		HIP_TRY(hipMemsetAsync(c->d_cnt, 0, sizeof(Counters), c->stream));
 		if ((rc = c->band.tnum.ensure((size_t)p->num_depth_levels))) return rc;
@@ -1238,7 +1278,7 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 	// 32-pixel tile inside one LDS chunk; anything else, or a range that turns out wider, takes the per-tile kernel
 	// (and enough tiles to keep every persistent workgroup busy for dozens of tiles: a small image is better served by
 	// one workgroup per tile; option strip = 4 / 8 forces the strip kernel for tests)
-	bool strip = dense && c->strip != 0 && c->arith != 2 && cstride + SRH_WTILE <= strip_chunk_columns();
+	bool strip = dense && (sad || (c->strip != 0 && c->arith != 2)) && cstride + SRH_WTILE <= strip_chunk_columns();
 	// certified arithmetic (arith = 3, the default): fused cost loops in the strip kernel + the certified scan; where the
 	// strip kernel does not run, or the parameters leave the bound no room, the reference's arithmetic
 	bool cert_ok = c->arith == 3 && !sad && cert_bound(*p).ok != 0;
@@ -1490,7 +1530,7 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 			if (rows < 1) rows = 1;
 			if (rows > (size_t)(y1 - y0)) rows = (size_t)(y1 - y0);
 			// the strip kernel wants dozens of tiles per persistent workgroup and launch; thin bands take the per-tile kernel
-			if (strip && c->strip == 1 && (size_t)((W + SRH_WTILE - 1)/SRH_WTILE)*rows < (size_t)48*2*c->num_cus) strip = false;
+			if (strip && !sad && c->strip == 1 && (size_t)((W + SRH_WTILE - 1)/SRH_WTILE)*rows < (size_t)48*2*c->num_cus) strip = false;
 			else break;
 		}
 		const bool wimg = strip;                                       // the band's windows in the LDS image's layout
@@ -1521,7 +1561,9 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 				}
 			}
 		}
-		if (strip) {
+		if (strip && sad) {
+			if ((rc = ensure_sad_planes(c, c->views[oth], R))) return rc;
+		} else if (strip) {
 			// zero-bordered "window fully usable" plane of the other view
 			ViewHost &O = c->views[oth];
 			if (!O.fullp) HIP_TRY(O.fullp.alloc(padded_size(O.w, O.h)));
@@ -1535,7 +1577,7 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 		for (int by = y0; by < y1; by += (int)rows) {
 			if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
 			const int nr = std::min((int)rows, y1 - by);
-			run_weights(c, ref, W, *p, by, nr, wstride, dense ? c->band.pconst : nullptr, wimg);
+			run_weights(c, ref, W, *p, by, nr, wstride, dense && !sad ? c->band.pconst : nullptr, wimg);
 			if (dense) {
 				Scope s(c, "pixel_range_kernel");
 				launch_pixel_range(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.tnum, cstride, c->band.prange);
@@ -1543,7 +1585,14 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 			if (dense) {
 				// the band's cost rows under one arithmetic: strip kernel or one workgroup per tile, then the left-out columns
 				auto cost_pass = [&](int arith) -> int {
-					if (strip) {
+					if (sad) {
+						// (every column of [lo, hi] is written: no fill launch, which would evaluate cost_ncc)
+						HIP_TRY(hipMemsetAsync(&c->d_cnt->strip_ticket, 0, 2*sizeof(unsigned int), c->stream));
+						Scope s(c, "twoview_strip_sad_kernel");
+						if (!launch_twoview_strip_sad(c->stream, W, H, *p, by, nr, c->band.wbuf, c->band.prange, c->views[ref].tvp,
+						                              c->views[oth].grayp, c->views[oth].fullsp, c->band.cost, cstride, c->d_cnt, c->num_cus))
+							return fail(SRH_E_UNSUPPORTED, "twoview_strip_sad_kernel: no instantiation for radius %d", R);
+					} else if (strip) {
 						HIP_TRY(hipMemsetAsync(&c->d_cnt->strip_ticket, 0, 2*sizeof(unsigned int), c->stream));
 						{ Scope s(c, "twoview_strip_cost_kernel");
 						  launch_twoview_strip_cost(c->stream, c->d_views, ref, oth, W, H, *p, by, nr, c->band.wbuf, c->band.pconst, c->band.prange,
@@ -1620,6 +1669,7 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 		Counters hc;
 		HIP_TRY(hipMemcpyAsync(&hc, c->d_cnt, sizeof(hc), hipMemcpyDeviceToHost, c->stream));
 		HIP_TRY(hipStreamSynchronize(c->stream));
+		if (strip && sad && hc.strip_overflow != 0) { strip = false; dense = false; continue; }   // (cost_sad: the candidate lists)
 		if (strip && hc.strip_overflow != 0) { strip = false; continue; }   // a tile's ranges did not fit one chunk: per-tile kernel
 		if (hc.cert_overflow != 0) { cert_ok = false; continue; }           // more flagged pixels than the redo covers: mode 0
 		c->stats.n_certified = (int64_t)hc.n_certified; c->stats.n_flagged = (int64_t)hc.n_flagged;
@@ -1642,7 +1692,9 @@ extern "C" int srh_twoview_cost_rows(srh_context *c, int ref, int oth, const srh
 	if ((rc = check_slot(c, ref, true)) || (rc = check_slot(c, oth, true)) || (rc = check_params(p))) return rc;
 	if (form != 0 && form != 3 && form != 5 && form != 1) return fail(SRH_E_INVALID, "form must be 0, 1, 3 or 5");
 	if ((form == 3 || form == 5) && !cert_bound(*p).ok) return fail(SRH_E_UNSUPPORTED, "the parameters leave the error bound no room");
-	if (c->cost_kind == SRH_COST_SAD) return fail(SRH_E_UNSUPPORTED, "cost rows exist for cost_ncc only (cost_sad has no dense plan)");
+	const bool sad = c->cost_kind == SRH_COST_SAD;
+	if (sad && !c->sad_dense) return fail(SRH_E_UNSUPPORTED, "cost rows of cost_sad exist on the dense plan only (option sad_dense)");
+	if (sad && form != 0) return fail(SRH_E_INVALID, "cost_sad has the reference's arithmetic only: form must be 0");
 	srh_context::Diag dg;
 	dg.form = form; dg.raw = raw != 0; dg.cost = cost_out; dg.cost_doubles = cost_doubles; dg.range = range_out;
 	c->diag = &dg;
@@ -1755,6 +1807,9 @@ extern "C" int srh_twoview_compute(srh_context *c, int left, int right, const sr
 			HIP_TRY(T.d_span.alloc(4));
 		}
 		// the NaN-bordered planes both passes read (twoview_wta_run makes them on demand, on its own stream) exist at `go`
+		if (c->cost_kind == SRH_COST_SAD && c->sad_dense && (p->window_radius == 5 || p->window_radius == 2))
+			for (int k = 0; k < 2; ++k)
+				if ((rc = ensure_sad_planes(c, c->views[k == 0 ? left : right], p->window_radius))) return rc;
 		if (p->window_radius == 5 || p->window_radius == 2)
 			for (int k = 0; k < 2; ++k) {
 				ViewHost &v = c->views[k == 0 ? left : right];

@@ -347,6 +347,14 @@ bool launch_twoview_rows_sad(hipStream_t st, const ViewDev *views, int ref, int 
 void launch_twoview_list_sad(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P,
                              int y0, int nrows, const double *wbuf, const int32_t *count, const uint32_t *cand,
                              double *cost, int cmax, Counters *cnt);
+// cost_sad on the row-aligned dense plan (srh_sad_strip.hip; option "sad_dense"): the other view's masked gray plane and
+// its cost_sad "window fully usable" bytes (launch_sad_full_window's) on the padded raster of padded_size(w, h), then the
+// persistent kernel that fills every column [lo, hi] of the band's cost rows (tile-transposed, as twoview_scan_kernel reads)
+void launch_padded_gray(hipStream_t st, const double *gray, const uint8_t *mask, int w, int h, double *out);
+void launch_padded_bytes(hipStream_t st, const uint8_t *in, int w, int h, uint8_t *out);
+bool launch_twoview_strip_sad(hipStream_t st, int width, int height, const srh_params &P, int y0, int nrows,
+                              const double *wimg, const PixRange *prange, const double *ref_tvp, const double *oth_grayp,
+                              const uint8_t *oth_fullp, double *cost, int cstride, Counters *cnt, int num_cus);
 // cost of arbitrary pairs xy[4k..4k+3] = (x1, y1, x2, y2), the window of (x1, y1) built per lane; sad: cost_sad, else cost_ncc
 void launch_pair_costs(hipStream_t st, const ViewDev *views, int ref, int oth, const srh_params &P, bool sad, int n,
                        const int32_t *xy, double *out);

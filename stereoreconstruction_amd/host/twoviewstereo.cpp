@@ -136,6 +136,7 @@ void TwoViewStereo::computeCostVolumes(CameraPtr leftView_, CameraPtr rightView_
 	leftView = leftView_; rightView = rightView_;
 	if (!uploadViews()) return;
 	if (srh_set_option(ctx_, "cost", costKind) != SRH_OK) { error_ = srh_last_error(); return; }
+	srh_set_option(ctx_, "sad_dense", sadDenseOn);
 	if (srh_twoview_wta(ctx_, 0, 1, &params_, 0, 0) != SRH_OK || srh_twoview_wta(ctx_, 1, 0, &params_, 0, 0) != SRH_OK ||
 	    srh_view_depth_download(ctx_, 0, computedDepthLeft.data()) != SRH_OK ||
 	    srh_view_depth_download(ctx_, 1, computedDepthRight.data()) != SRH_OK)
@@ -187,6 +188,7 @@ void TwoViewStereo::computeDepthMaps() {
 	TwoViewHooks hooks = { this, &progressUpdate, &stageUpdate };
 	srh_set_hooks(ctx_, cancelFlag(), onProgress, &hooks);
 	srh_set_option(ctx_, "filter_invalid", filterFlags);
+	srh_set_option(ctx_, "sad_dense", sadDenseOn);
 	if (srh_set_option(ctx_, "cost", costKind) != SRH_OK) {
 		error_ = srh_last_error();
 		srh_set_hooks(ctx_, nullptr, nullptr, nullptr);

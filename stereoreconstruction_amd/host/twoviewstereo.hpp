@@ -38,6 +38,9 @@ public:
 	// (1: cost_sad, twoviewstereo.cpp:864-905).  The WTA, ratio test, cross-check and hole filling are the same for both.
 	void setCostFunction(int kind) { costKind = kind; }
 	int costFunction() const { return costKind; }
+	// SAD of a rectified pair on the dense plan (option "sad_dense": 1 = on, 0 = default): a tuning switch, never the result
+	void setSadDense(int on) { sadDenseOn = on; }
+	int sadDense() const { return sadDenseOn; }
 
 	// Candidate pixels, in visiting order, of pixel (x,y) of the left (fromLeft) or right view in the
 	// other view.  The reference's public epipolarCurve (twoviewstereo.hpp:66-70) takes the unprojected
@@ -95,6 +98,7 @@ private:
 	srh_params params_;
 	int filterFlags = 0;
 	int costKind = SRH_COST_NCC;
+	int sadDenseOn = 0;
 	srh_context *ctx_;
 	std::string error_;
 };

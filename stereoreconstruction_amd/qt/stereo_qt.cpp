@@ -168,6 +168,7 @@ void TwoViewStereo::computeDepthMaps() {
 	params_.num_depth_levels = numDepthLevels; params_.image_scale = imageScale;
 	if (!uploadViews()) return;
 	if (srh_set_option(ctx_, "cost", costKind) != SRH_OK) { error_ = srh_last_error(); return; }
+	srh_set_option(ctx_, "sad_dense", sadDenseOn);
 	emit progressUpdate(1);
 	emit stageUpdate("Computing cost volume for left image...");
 	if (srh_twoview_wta(ctx_, 0, 1, &params_, 0, 0) != SRH_OK) { error_ = srh_last_error(); return; }

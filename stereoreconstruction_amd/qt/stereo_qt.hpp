@@ -120,6 +120,9 @@ public:
 	// matching cost of the WTA: SRH_COST_NCC (0, default: cost_ncc, the reference's) or SRH_COST_SAD (1: cost_sad)
 	void setCostFunction(int kind) { costKind = kind; }
 	int costFunction() const { return costKind; }
+	// SAD of a rectified pair on the dense plan (option "sad_dense": 1 = on, 0 = default): a tuning switch, never the result
+	void setSadDense(int on) { sadDenseOn = on; }
+	int sadDense() const { return sadDenseOn; }
 
 public: // Task implementation continued: public in the reference as well (stereo/twoviewstereo.hpp:50-52)
 	void runTask() { computeDepthMaps(); }
@@ -150,6 +153,7 @@ private:
 	srh_params params_;
 	int filterFlags = 0;
 	int costKind = SRH_COST_NCC;
+	int sadDenseOn = 0;
 	srh_context *ctx_;
 	mutable bool uploaded_ = false;                        // views resident on the device (epipolarCurve before computeDepthMaps)
 	bool uploadViews() const;
