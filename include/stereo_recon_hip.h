@@ -364,6 +364,72 @@ int  srh_mvs_mrf_estimate_views(srh_context *ctx, const int32_t *view_slots, int
 int  srh_mvs_mrf_dims(srh_context *ctx, int *w, int *h, int *top_k);
 int  srh_mvs_mrf_state(srh_context *ctx, int w, int h, int top_k, int32_t *labels, double *data_costs, double *messages);
 
+/* ---- TwoViewStereo, MRF stage (second half) ----
+ * The step after winner-take-all: a regularised depth map from the full label cost volume.  PARITY UNPINNED: the
+ * reference's branch is compile-time dead (#undef USE_MRF, twoviewstereo.cpp:35), no longer compiles against its own
+ * cost_ncc signature, and hands the energy to alpha-expansion from a third-party library that is not in its tree: no
+ * compiled reference can pin any of it.
+ * FROM THE REFERENCE'S LINES:
+ *   labels 0 .. D-1 with depthFromLabel (:981-985); a label's pixel in the other view is pointFromDepth on the pixel's
+ *   ray, project into the other view (:309-313), times image_scale, truncated toward zero (the live path's rule, the int
+ *   parameters at :1019-1028; huge coordinates saturate as everywhere on this path).  The dead branch's "- 0.5"
+ *   (:314-315) is deliberately NOT taken: it dates from a cost_ncc that sampled at fractional positions and would select
+ *   the pixel left of / above the one that contains the projection.
+ *   data cost of (pixel, label) = the live path's pair cost (cost_ncc, or cost_sad under option "cost") at (x, y) and the
+ *   label's pixel with the support window of (x, y); WINDOW_SIZE*BAD_RET = (2*window_radius + 1)*bad_ret (:258) where
+ *   pointFromDepth or project fails and on every label of a pixel whose mask is not WHITE (never costed, :270-271).
+ *   E = sum_p D_p(l_p) + sum_(p,q) lambda*min(|l_p - l_q|, smooth_max) over the 4-connected W x H grid, weight 1, every
+ *   pixel a node (the graph of Expansion(width, height, ...), :347); SMOOTHNESS_EXP 1, _MAX 2, _LAMBDA 0.25 (:69-71).
+ *   start: messages zero, labelling all 0 (energy_initial is its energy); loop: do { one sweep } while (prev - energy >
+ *   min_energy_drop && numIters-- > 0) with 50 and 5 (:378-390); output: depthFromLabel(label) where the mask is WHITE
+ *   (:324), NaN elsewhere; no ratio test and no INF from this stage; crossCheck follows unchanged.
+ * OURS: the optimiser -- sequential TRW-S, the engine of the MultiViewStereo branch above (gamma = 1/2, forward sweep,
+ *   backward sweep, labels read off by a forward pass, minima taken with ">" so that the lowest index wins a tie, the
+ *   minimum message subtracted at every update) with L = D labels.  The reference's masked 8-neighbour graph (:351-368) is
+ *   NOT restated: it indexes its pixel map out of bounds at the image border and registers every interior edge from both
+ *   ends -- there is nothing well-defined to restate.
+ * LIMITS: 2 <= D <= 256, smooth_exp == 1, 0 < smooth_max <= 4 (else SRH_E_UNSUPPORTED); lambda >= 0, max_iters >= 0.
+ * Data costs must be finite for the results to be defined bit for bit. */
+typedef struct srh_twoview_mrf_params {
+	int32_t smooth_exp;           /* SMOOTHNESS_EXP 1 (twoviewstereo.cpp:69) */
+	double  smooth_max, lambda;   /* SMOOTHNESS_MAX 2, SMOOTHNESS_LAMBDA 0.25 (:70-71) */
+	int32_t max_iters;            /* 50 (:378) */
+	double  min_energy_drop;      /* 5 (:390) */
+} srh_twoview_mrf_params;
+void srh_twoview_mrf_params_defaults(srh_twoview_mrf_params *m);   /* needs no device */
+/* what pixel_out holds (both coordinates) for a label whose projection failed and for every label of a masked-out pixel */
+#define SRH_LABEL_PIXEL_NONE (-2147483647 - 1)
+/* The label cost volume of rows [y0, y1) (y1 <= 0: all) of ref_slot against oth_slot, to HOST buffers: cost_out
+ * [pixel][label] doubles (rows*w*D), pixel_out (may be NULL) [pixel][label][x2, y2] the labels' pixels in the other view.
+ * Every entry that is not the fill value is the bits srh_twoview_pair_costs returns for that pair and cost kind (option
+ * "cost").  window_radius <= 5.  A building block and a test window; synchronous. */
+int  srh_twoview_label_costs(srh_context *ctx, int ref_slot, int oth_slot, const srh_params *p, int y0, int y1,
+                             double *cost_out, int32_t *pixel_out);
+/* The optimiser on a caller's DEVICE volume (w*h*L doubles, [pixel][label], L == p->num_depth_levels): writes the slot's
+ * depth map with the depth range of p.  The counterpart of srh_mvs_mrf_estimate.  A run needs two message planes of
+ * w*h*L doubles beside the volume (+ the hand-over granules); when that does not fit the free device memory (option
+ * "mem_limit_mb" honoured) the call fails with SRH_E_DEVICE and a message that names the bytes needed, before anything
+ * is queued -- there are no bands: a sweep needs the whole grid.  The cancel flag is polled between sweeps.  (A volume
+ * on a 16-byte boundary with L a multiple of its labels per lane, ceil(L/64), is moved 16 bytes at a time: same bits.) */
+int  srh_twoview_mrf_optimize(srh_context *ctx, int view_slot, const srh_params *p, int L, const void *costs_dev,
+                              const srh_twoview_mrf_params *m, srh_mrf_info *info);
+/* One direction: the label cost volume in the context's scratch (three volumes in all: 12.7 GB at 1920x1080x256), the
+ * optimiser, the depth map of ref_slot. */
+int  srh_twoview_mrf(srh_context *ctx, int ref_slot, int oth_slot, const srh_params *p,
+                     const srh_twoview_mrf_params *m, srh_mrf_info *info);
+/* computeDepthMaps as a USE_MRF build runs it: both directions one after the other, then the cross-check; progress steps
+ * 1, 2 "Optimizing...", 3, 4 "Optimizing...", 5, 8 (option "filter_invalid": 6 and 7 where srh_twoview_compute puts
+ * them); synchronous; host outputs and infos (two entries: left, right) may be NULL. */
+int  srh_twoview_compute_mrf(srh_context *ctx, int left_slot, int right_slot, const srh_params *p,
+                             const srh_twoview_mrf_params *m, double *left_depth_out, double *right_depth_out,
+                             srh_mrf_info *infos);
+/* State of the last srh_twoview_mrf / srh_twoview_mrf_optimize on this context (the semantics of srh_mvs_mrf_state), to
+ * HOST buffers (each may be NULL): labels (w*h), data_costs (w*h*L; only after srh_twoview_mrf -- the volume of
+ * srh_twoview_mrf_optimize is the caller's: SRH_E_INVALID), messages (w*h*2*L: [pixel][towards x+1, towards y+1][label]).
+ * After srh_twoview_compute_mrf the state is that of its second (right) direction. */
+int  srh_twoview_mrf_dims(srh_context *ctx, int *w, int *h, int *L);
+int  srh_twoview_mrf_state(srh_context *ctx, int w, int h, int L, int32_t *labels, double *data_costs, double *messages);
+
 /* ---- depth map -> point cloud ----
  * The output side of the path (the reference keeps only the PLY writer, multiviewstereo.cpp:291-315,
  * and the per-view coverage figure it logs, :402-421).  For every pixel of `slot` whose mask is WHITE and whose depth is

@@ -62,6 +62,15 @@ class SrhMrfInfo(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("energy_initial", C.c_double), ("energy_final", C.c_double)]
 
 
+class SrhTwoviewMrfParams(C.Structure):
+    """srh_twoview_mrf_params"""
+    _fields_ = [("smooth_exp", C.c_int32), ("smooth_max", C.c_double), ("lambda_", C.c_double),
+                ("max_iters", C.c_int32), ("min_energy_drop", C.c_double)]
+
+
+# what srh_twoview_label_costs writes for a label without a pixel (SRH_LABEL_PIXEL_NONE)
+LABEL_PIXEL_NONE = -2147483648
+
 # option "arith" (include/stereo_recon_hip.h)
 ARITH_EXACT, ARITH_FMA, ARITH_F32, ARITH_CERTIFIED = 0, 1, 2, 3
 ARITH_DEFAULT = ARITH_CERTIFIED
@@ -105,6 +114,8 @@ EXPORTS = [
     "srh_epipolar_preview", "srh_refraction_error",
     "srh_mrf_params_defaults", "srh_mvs_mrf_estimate", "srh_mvs_mrf_state", "srh_mvs_mrf_dims", "srh_mvs_initial_estimate_mrf",
     "srh_mvs_initial_estimate_peaks", "srh_mvs_mrf_estimate_views",
+    "srh_twoview_mrf_params_defaults", "srh_twoview_label_costs", "srh_twoview_mrf_optimize", "srh_twoview_mrf",
+    "srh_twoview_compute_mrf", "srh_twoview_mrf_dims", "srh_twoview_mrf_state",
     "srh_comm_unique_id", "srh_comm_init", "srh_comm_gather_depth", "srh_comm_allgather_depth", "srh_comm_allgather_host",
     "srh_comm_allgather_views",
     "srh_comm_destroy", "srh_comm_set_timeout_ms", "srh_comm_version", "srh_comm_info",
@@ -171,6 +182,15 @@ def lib():
     L.srh_mvs_mrf_estimate_views.argtypes = [vp, c_int32_p, C.c_int, C.POINTER(SrhMrfParams), C.POINTER(SrhMrfInfo)]
     L.srh_mvs_mrf_state.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_int32_p, c_double_p, c_double_p]
     L.srh_mvs_mrf_dims.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    tmp = C.POINTER(SrhTwoviewMrfParams)
+    L.srh_twoview_mrf_params_defaults.argtypes = [tmp]
+    L.srh_twoview_mrf_params_defaults.restype = None
+    L.srh_twoview_label_costs.argtypes = [vp, C.c_int, C.c_int, C.POINTER(Params), C.c_int, C.c_int, c_double_p, c_int32_p]
+    L.srh_twoview_mrf_optimize.argtypes = [vp, C.c_int, C.POINTER(Params), C.c_int, C.c_void_p, tmp, C.POINTER(SrhMrfInfo)]
+    L.srh_twoview_mrf.argtypes = [vp, C.c_int, C.c_int, C.POINTER(Params), tmp, C.POINTER(SrhMrfInfo)]
+    L.srh_twoview_compute_mrf.argtypes = [vp, C.c_int, C.c_int, C.POINTER(Params), tmp, c_double_p, c_double_p, C.POINTER(SrhMrfInfo)]
+    L.srh_twoview_mrf_dims.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.srh_twoview_mrf_state.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_int32_p, c_double_p, c_double_p]
     L.srh_comm_allgather_views.argtypes = [vp, c_int32_p, C.c_int]
     L.srh_hw_queues_requested.restype = C.c_int
     L.srh_epipolar_preview.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, c_double_p, c_double_p, c_int32_p]
@@ -234,6 +254,22 @@ def mrf_params(**kw):
     for k, v in kw.items():
         setattr(m, "lambda_" if k == "lambda" else k, v)
     return m
+
+
+def twoview_mrf_params(**kw):
+    """srh_twoview_mrf_params with the reference's constants (twoviewstereo.cpp:69-71, 378, 390)."""
+    m = SrhTwoviewMrfParams()
+    lib().srh_twoview_mrf_params_defaults(C.byref(m))
+    for k, v in kw.items():
+        k = "lambda_" if k == "lambda" else k
+        if not hasattr(m, k):
+            raise AttributeError(k)
+        setattr(m, k, v)
+    return m
+
+
+def _mrf_info(info):
+    return dict(iterations=info.iterations, energy_initial=info.energy_initial, energy_final=info.energy_final)
 
 
 def params_mvs(**kw):
@@ -536,6 +572,59 @@ class Context:
         """(w, h, top_k) of the single-view MRF run whose state mvs_mrf_state reports."""
         w, h, k = C.c_int(), C.c_int(), C.c_int()
         _check(lib().srh_mvs_mrf_dims(self._h, C.byref(w), C.byref(h), C.byref(k)))
+        return w.value, h.value, k.value
+
+    # -- TwoViewStereo, MRF stage
+    def twoview_label_costs(self, ref_slot, oth_slot, p, y0=0, y1=0, want_pixels=True):
+        """The label cost volume of rows [y0, y1) (y1 <= 0: all) -> (costs (rows, w, D) float64, pixels (rows, w, D, 2) int32
+        or None): srh_twoview_label_costs.  A label without a pixel holds LABEL_PIXEL_NONE."""
+        w, h = self.view_size(ref_slot)
+        rows = (y1 if y1 > 0 else h) - y0
+        D = p.num_depth_levels
+        cost = np.empty((max(rows, 0), w, D), dtype=np.float64)
+        pix = np.empty((max(rows, 0), w, D, 2), dtype=np.int32) if want_pixels else None
+        _check(lib().srh_twoview_label_costs(self._h, ref_slot, oth_slot, C.byref(p), y0, y1, _dptr(cost),
+                                             pix.ctypes.data_as(c_int32_p) if want_pixels else None))
+        return cost, pix
+
+    def twoview_mrf_optimize(self, view_slot, p, L, costs_dev, m=None):
+        """TRW-S on a device volume (w*h*L doubles, [pixel][label]); writes the slot's depth map
+        -> dict(iterations, energy_initial, energy_final)."""
+        m = m if m is not None else twoview_mrf_params()
+        info = SrhMrfInfo()
+        _check(lib().srh_twoview_mrf_optimize(self._h, view_slot, C.byref(p), L, C.c_void_p(costs_dev), C.byref(m), C.byref(info)))
+        return _mrf_info(info)
+
+    def twoview_mrf(self, ref_slot, oth_slot, p, m=None):
+        """One direction of the MRF stage: label costs, optimiser, depth map of ref_slot."""
+        m = m if m is not None else twoview_mrf_params()
+        info = SrhMrfInfo()
+        _check(lib().srh_twoview_mrf(self._h, ref_slot, oth_slot, C.byref(p), C.byref(m), C.byref(info)))
+        return _mrf_info(info)
+
+    def twoview_compute_mrf(self, left_slot, right_slot, p, m=None):
+        """computeDepthMaps of a USE_MRF build -> (left map, right map, [left info, right info])."""
+        m = m if m is not None else twoview_mrf_params()
+        w, h = self.view_size(left_slot)
+        dl = np.empty((h, w), dtype=np.float64)
+        dr = np.empty((h, w), dtype=np.float64)
+        infos = (SrhMrfInfo * 2)()
+        _check(lib().srh_twoview_compute_mrf(self._h, left_slot, right_slot, C.byref(p), C.byref(m), _dptr(dl), _dptr(dr), infos))
+        return dl, dr, [_mrf_info(i) for i in infos]
+
+    def twoview_mrf_state(self, w, h, L, want_costs=False):
+        """(labels (h,w) int32, data_costs (h,w,L) or None, messages (h,w,2,L)) of the last single-direction run."""
+        labels = np.zeros((h, w), dtype=np.int32)
+        D = np.zeros((h, w, L), dtype=np.float64) if want_costs else None
+        M = np.zeros((h, w, 2, L), dtype=np.float64)
+        _check(lib().srh_twoview_mrf_state(self._h, w, h, L, labels.ctypes.data_as(c_int32_p),
+                                           _dptr(D) if want_costs else None, _dptr(M)))
+        return labels, D, M
+
+    def twoview_mrf_dims(self):
+        """(w, h, L) of the run whose state twoview_mrf_state reports."""
+        w, h, k = C.c_int(), C.c_int(), C.c_int()
+        _check(lib().srh_twoview_mrf_dims(self._h, C.byref(w), C.byref(h), C.byref(k)))
         return w.value, h.value, k.value
 
     def epipolar_preview(self, ref_slot, oth_slot, min_depth, max_depth, num_depths, xy):

@@ -270,6 +270,10 @@ struct srh_context {
 	DevBuf<double> mrf_peaks;                           // top-K peaks of srh_mvs_initial_estimate_mrf
 	DevBuf<double> mrf;                                 // MRF stage scratch (srh_mrf.hip); mrf_w/h/k: what the last run left in it
 	int mrf_w = 0, mrf_h = 0, mrf_k = 0;
+	DevBuf<double> tvmrf;                               // TwoViewStereo MRF stage scratch (srh_twoview_mrf.hip): messages, granules, labels
+	DevBuf<double> tvmrf_costs;                         //   and the label cost volume of srh_twoview_mrf
+	int tvmrf_w = 0, tvmrf_h = 0, tvmrf_l = 0;          // what the last single-direction run left in them
+	bool tvmrf_own_costs = false;                       //   (its data costs are in tvmrf_costs, not in a caller's volume)
 	int geodma = 1;                                     // option "geodma": 1 = the dense path's r = 5 geodesic windows by the persistent LDS-DMA kernel (default), 0 = geodesic_reg_kernel
 	int tscan = 1;                                      // option "tscan": 1 = template scan on the dense path (default), 0 = every tile through twoview_scan_kernel
 	int strip = 1;                                      // option "strip": 1 = persistent strip cost kernel (default), 0 = one workgroup per tile, 4 / 8 = force the 4- / 8-wave form
@@ -712,6 +716,7 @@ extern "C" void srh_destroy(srh_context *c) {
 		T.d_cnt.release(); T.d_span.release(); T.band.release();
 	}
 	c->mrf.release(); c->mrf_peaks.release();
+	c->tvmrf.release(); c->tvmrf_costs.release();
 	for (int i = 0; i < SRH_MAX_VIEWS; ++i) if (c->mrf_stream[i]) hipStreamDestroy(c->mrf_stream[i]);
 	if (c->mrf_host) hipHostFree(c->mrf_host);
 	if (c->comm) (void)rccl_comm_destroy(c->comm);
@@ -845,6 +850,7 @@ extern "C" int srh_view_upload(srh_context *c, int slot, int w, int h,
 	v.tvp_valid = false; v.fullp_r = 0; v.grayp_valid = false; v.fullsp_r = 0; v.geo5_valid = false; v.geo5_denied = false;
 	v.peaks_k = 0;                                              // the top-K peaks belonged to the previous image
 	if (c->mrf_w == w && c->mrf_h == h) c->mrf_w = c->mrf_h = c->mrf_k = 0;
+	if (c->tvmrf_w == w && c->tvmrf_h == h) c->tvmrf_w = c->tvmrf_h = c->tvmrf_l = 0;
 	for (int j = 0; j < SRH_MAX_VIEWS; ++j) { v.list_mode[j] = 0; c->views[j].list_mode[slot] = 0; }   // new geometry
 	HIP_TRY(hipMemcpyAsync(v.rgba, rgba, n*4, hipMemcpyHostToDevice, c->stream));
 	if (mask) HIP_TRY(hipMemcpyAsync(v.mask, mask, n, hipMemcpyHostToDevice, c->stream));
@@ -2582,6 +2588,232 @@ extern "C" int srh_mvs_mrf_state(srh_context *c, int bw, int bh, int bk, int32_t
 	if (messages) {
 		HIP_TRY(hipMemcpy2DAsync(messages, 2*L*sizeof(double), lay.Mh, 16*sizeof(double), L*sizeof(double), n, hipMemcpyDeviceToHost, c->stream));
 		HIP_TRY(hipMemcpy2DAsync(messages + L, 2*L*sizeof(double), lay.Mv, 16*sizeof(double), L*sizeof(double), n, hipMemcpyDeviceToHost, c->stream));
+	}
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	return SRH_OK;
+}
+
+// ------------------------------------------------------------------ TwoViewStereo, MRF stage (srh_twoview_mrf.hip)
+extern "C" void srh_twoview_mrf_params_defaults(srh_twoview_mrf_params *m)
+{
+	if (!m) return;
+	m->smooth_exp = 1; m->smooth_max = 2; m->lambda = 0.25;          // twoviewstereo.cpp:69-71
+	m->max_iters = 50; m->min_energy_drop = 5;                       // :378, :390
+}
+
+static int check_tvmrf_params(const srh_twoview_mrf_params *m, int L)
+{
+	if (!m) return fail(SRH_E_INVALID, "null MRF params");
+	if (L < 2 || L > 256) return fail(SRH_E_UNSUPPORTED, "%d labels outside [2,256] (64 lanes per pixel, up to 4 labels per lane)", L);
+	if (m->smooth_exp != 1) return fail(SRH_E_UNSUPPORTED, "smooth_exp %d: only the truncated-linear term (1) is built", m->smooth_exp);
+	if (!(m->smooth_max > 0 && m->smooth_max <= 4)) return fail(SRH_E_UNSUPPORTED, "smooth_max %g outside (0,4] (the message window reaches 3 labels)", m->smooth_max);
+	if (!(m->lambda >= 0 && m->lambda < __builtin_inf())) return fail(SRH_E_INVALID, "lambda %g must be finite and >= 0", m->lambda);
+	if (m->max_iters < 0 || m->max_iters > (1 << 24)) return fail(SRH_E_INVALID, "max_iters %d outside [0,2^24]", m->max_iters);
+	return SRH_OK;
+}
+
+// bytes of device memory a run still has to find: the message planes (+ granules, labels), and the cost volume when it is ours
+static int tvmrf_reserve(srh_context *c, int w, int h, int L, bool own_costs)
+{
+	const size_t scratch = twoview_mrf_scratch_doubles(w, h, L), vol = own_costs ? (size_t)w*h*L : 0;
+	const size_t need = (scratch + vol)*sizeof(double);
+	size_t missing = 0;
+	if (c->tvmrf.n < scratch) missing += scratch*sizeof(double);
+	if (c->tvmrf_costs.n < vol) missing += vol*sizeof(double);
+	size_t free_b = 0, total_b = 0;
+	if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+		size_t avail = free_b + pool_bytes_on(c->device);
+		if (c->tvmrf.n < scratch) avail += c->tvmrf.bytes();            // (an outgrown buffer is released first)
+		if (c->tvmrf_costs.n < vol) avail += c->tvmrf_costs.bytes();
+		size_t want = missing;
+		if (c->mem_limit) { want = need; if (avail > c->mem_limit) avail = c->mem_limit; }   // the pretended device holds the whole run
+		if (want > avail)
+			return fail(SRH_E_DEVICE, "the MRF stage of a %dx%dx%d volume needs %zu bytes of device memory (%s: %zu per volume, no bands: a sweep needs the whole grid), %zu are available",
+			            w, h, L, need, own_costs ? "costs and two message planes" : "two message planes", (size_t)w*h*L*sizeof(double), avail);
+	} else (void)hipGetLastError();
+	int rc;
+	if ((rc = c->tvmrf.ensure(scratch))) return rc;
+	if (vol && (rc = c->tvmrf_costs.ensure(vol))) return rc;
+	return SRH_OK;
+}
+
+// the optimiser on `costs` (device, [pixel][L]); the scratch is reserved
+static int tvmrf_run(srh_context *c, int slot, const srh_params *p, int L, const double *costs, const srh_twoview_mrf_params *m, srh_mrf_info *info)
+{
+	int rc;
+	const ViewHost &v = c->views[slot];
+	const int w = v.w, h = v.h;
+	c->tvmrf_w = c->tvmrf_h = c->tvmrf_l = 0;
+	TvMrfLayout lay;
+	HIP_TRY(launch_twoview_mrf_setup(c->stream, c->tvmrf, w, h, L, lay));
+	struct { double energy, pad; unsigned status[4]; } hs;
+	auto energy = [&](double &e) -> int {
+		{ Scope s(c, "twoview_mrf_energy_kernel");
+		  HIP_TRY(launch_twoview_mrf_energy(c->stream, c->tvmrf, costs, w, h, L, m->lambda, m->smooth_max)); }
+		HIP_TRY(hipMemcpyAsync(&hs, lay.energy, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
+		HIP_TRY(hipStreamSynchronize(c->stream));
+		if (hs.status[0])
+			return fail(SRH_E_DEVICE, "TwoView MRF pass %u: band %u waited too long for the band above (hand-off never arrived)", hs.status[2], hs.status[1] - 1);
+		e = hs.energy;
+		return SRH_OK;
+	};
+	// twoviewstereo.cpp:378-390
+	double e = 0.0, prev = 0.0;
+	if ((rc = energy(e))) return rc;
+	const double e0 = e;
+	int num_iters = m->max_iters, iters = 0;
+	do {
+		if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
+		prev = e;
+		{ Scope s(c, "twoview_mrf_pass_kernel");
+		  HIP_TRY(launch_twoview_mrf_sweep(c->stream, c->tvmrf, costs, w, h, L, m->lambda, m->smooth_max, iters)); }
+		if ((rc = energy(e))) return rc;
+		++iters;
+	} while (prev - e > m->min_energy_drop && num_iters-- > 0);
+	{ Scope s(c, "twoview_mrf_depth_kernel");
+	  HIP_TRY(launch_twoview_mrf_depth(c->stream, c->d_views, slot, *p, c->tvmrf, w, h, L)); }
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	c->tvmrf_w = w; c->tvmrf_h = h; c->tvmrf_l = L;
+	if (info) { info->iterations = iters; info->energy_initial = e0; info->energy_final = e; }
+	return SRH_OK;
+}
+
+extern "C" int srh_twoview_mrf_optimize(srh_context *c, int slot, const srh_params *p, int L, const void *costs_dev,
+                                        const srh_twoview_mrf_params *m, srh_mrf_info *info)
+{
+	int rc;
+	if ((rc = check_slot(c, slot, true)) || (rc = check_params(p))) return rc;
+	if (!costs_dev) return fail(SRH_E_INVALID, "null cost volume");
+	if ((rc = check_tvmrf_params(m, L))) return rc;
+	if (L != p->num_depth_levels) return fail(SRH_E_INVALID, "%d labels, but num_depth_levels is %d (depthFromLabel needs the label count)", L, p->num_depth_levels);
+	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
+	HIP_TRY(hipSetDevice(c->device));
+	const ViewHost &v = c->views[slot];
+	c->tvmrf_w = c->tvmrf_h = c->tvmrf_l = 0;
+	if ((rc = tvmrf_reserve(c, v.w, v.h, L, false))) return rc;
+	c->tvmrf_own_costs = false;
+	return tvmrf_run(c, slot, p, L, static_cast<const double *>(costs_dev), m, info);
+}
+
+static int check_label_costs(srh_context *c, int ref, int oth, const srh_params *p)
+{
+	int rc;
+	if ((rc = check_slot(c, ref, true)) || (rc = check_slot(c, oth, true)) || (rc = check_params(p))) return rc;
+	if (ref == oth) return fail(SRH_E_INVALID, "ref and other view are the same slot");
+	if (p->window_radius > 5) return fail(SRH_E_UNSUPPORTED, "label costs take window radii up to 5");
+	return SRH_OK;
+}
+
+extern "C" int srh_twoview_label_costs(srh_context *c, int ref, int oth, const srh_params *p, int y0, int y1,
+                                       double *cost_out, int32_t *pixel_out)
+{
+	int rc;
+	if ((rc = check_label_costs(c, ref, oth, p))) return rc;
+	if (!cost_out) return fail(SRH_E_INVALID, "null cost output");
+	const ViewHost &v = c->views[ref];
+	if (y1 <= 0) y1 = v.h;
+	if (y0 < 0 || y0 >= y1 || y1 > v.h) return fail(SRH_E_INVALID, "rows [%d,%d) outside the view's %d rows", y0, y1, v.h);
+	HIP_TRY(hipSetDevice(c->device));
+	const int D = p->num_depth_levels;
+	const size_t n = (size_t)(y1 - y0)*v.w*D;
+	DevBuf<double> dcost; DevBuf<int32_t> dpix;
+	auto done = [&](int r) { dcost.free(); dpix.free(); return r; };
+	if (dcost.alloc(n) != hipSuccess || (pixel_out && dpix.alloc(2*n) != hipSuccess))
+		return done(fail(SRH_E_DEVICE, "label costs: no device memory for %zu bytes", n*(sizeof(double) + (pixel_out ? 2*sizeof(int32_t) : 0))));
+	hipError_t e;
+	{ Scope s(c, "twoview_label_costs_kernel");
+	  e = launch_twoview_label_costs(c->stream, c->d_views, ref, oth, v.w, *p, c->cost_kind == SRH_COST_SAD, y0, y1 - y0,
+	                                 (2*p->window_radius + 1)*p->bad_ret, dcost, pixel_out ? (int32_t *)dpix : nullptr); }
+	if (e == hipSuccess) e = hipMemcpyAsync(cost_out, dcost, n*sizeof(double), hipMemcpyDeviceToHost, c->stream);
+	if (e == hipSuccess && pixel_out) e = hipMemcpyAsync(pixel_out, dpix, 2*n*sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+	if (e != hipSuccess) return done(fail(SRH_E_DEVICE, "label costs: %s", hipGetErrorString(e)));
+	return done(SRH_OK);
+}
+
+extern "C" int srh_twoview_mrf(srh_context *c, int ref, int oth, const srh_params *p, const srh_twoview_mrf_params *m, srh_mrf_info *info)
+{
+	int rc;
+	if ((rc = check_label_costs(c, ref, oth, p))) return rc;
+	const int L = p->num_depth_levels;
+	if ((rc = check_tvmrf_params(m, L))) return rc;
+	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
+	HIP_TRY(hipSetDevice(c->device));
+	const ViewHost &v = c->views[ref];
+	c->tvmrf_w = c->tvmrf_h = c->tvmrf_l = 0;
+	if ((rc = tvmrf_reserve(c, v.w, v.h, L, true))) return rc;
+	c->tvmrf_own_costs = true;
+	{ Scope s(c, "twoview_label_costs_kernel");
+	  HIP_TRY(launch_twoview_label_costs(c->stream, c->d_views, ref, oth, v.w, *p, c->cost_kind == SRH_COST_SAD, 0, v.h,
+	                                     (2*p->window_radius + 1)*p->bad_ret, c->tvmrf_costs, nullptr)); }
+	return tvmrf_run(c, ref, p, L, c->tvmrf_costs, m, info);
+}
+
+extern "C" int srh_twoview_compute_mrf(srh_context *c, int left, int right, const srh_params *p, const srh_twoview_mrf_params *m,
+                                       double *left_out, double *right_out, srh_mrf_info *infos)
+{
+	int rc;
+	if ((rc = check_label_costs(c, left, right, p))) return rc;
+	if ((rc = check_tvmrf_params(m, p->num_depth_levels))) return rc;
+	const ViewHost &L = c->views[left], &Rv = c->views[right];
+	if (L.w != Rv.w || L.h != Rv.h) return fail(SRH_E_INVALID, "TwoViewStereo needs equal-sized views");
+	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
+	// progress steps as a USE_MRF build of TwoViewStereo emits them (twoviewstereo.cpp:234, 337, 405, 506, 597, 225)
+	for (int k = 0; k < 2; ++k) {
+		const int ref = k == 0 ? left : right, oth = k == 0 ? right : left;
+		progress(c, 1 + 2*k, k == 0 ? "Computing cost volume for left image..." : "Computing cost volume for right image...");
+		HIP_TRY(hipSetDevice(c->device));
+		const ViewHost &v = c->views[ref];
+		const int D = p->num_depth_levels;
+		c->tvmrf_w = c->tvmrf_h = c->tvmrf_l = 0;
+		if ((rc = tvmrf_reserve(c, v.w, v.h, D, true))) return rc;
+		c->tvmrf_own_costs = true;
+		{ Scope s(c, "twoview_label_costs_kernel");
+		  HIP_TRY(launch_twoview_label_costs(c->stream, c->d_views, ref, oth, v.w, *p, c->cost_kind == SRH_COST_SAD, 0, v.h,
+		                                     (2*p->window_radius + 1)*p->bad_ret, c->tvmrf_costs, nullptr)); }
+		if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
+		progress(c, 2 + 2*k, "Optimizing...");
+		if ((rc = tvmrf_run(c, ref, p, D, c->tvmrf_costs, m, infos ? infos + k : nullptr))) return rc;
+		if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
+	}
+	progress(c, 5, "Detecting inconsistencies...");
+	if ((rc = srh_twoview_cross_check(c, left, right, p))) return rc;
+	if (c->filter_invalid && (rc = twoview_filter(c, left, right, p))) return rc;
+	if (left_out && (rc = srh_view_depth_download(c, left, left_out))) return rc;
+	if (right_out && (rc = srh_view_depth_download(c, right, right_out))) return rc;
+	if ((rc = srh_synchronize(c))) return rc;
+	progress(c, 8, "Finished!");
+	return SRH_OK;
+}
+
+extern "C" int srh_twoview_mrf_dims(srh_context *c, int *w, int *h, int *L)
+{
+	if (!c) return fail(SRH_E_INVALID, "null context");
+	if (!c->tvmrf_w) return fail(SRH_E_INVALID, "no finished TwoView MRF run on this context");
+	if (w) *w = c->tvmrf_w;
+	if (h) *h = c->tvmrf_h;
+	if (L) *L = c->tvmrf_l;
+	return SRH_OK;
+}
+
+extern "C" int srh_twoview_mrf_state(srh_context *c, int bw, int bh, int bl, int32_t *labels, double *data_costs, double *messages)
+{
+	if (!c) return fail(SRH_E_INVALID, "null context");
+	if (!c->tvmrf_w) return fail(SRH_E_INVALID, "no finished TwoView MRF run on this context");
+	if (bw != c->tvmrf_w || bh != c->tvmrf_h || bl != c->tvmrf_l)
+		return fail(SRH_E_INVALID, "buffers sized for %dx%d, L = %d, the last TwoView MRF run was %dx%d, L = %d", bw, bh, bl, c->tvmrf_w, c->tvmrf_h, c->tvmrf_l);
+	if (data_costs && !c->tvmrf_own_costs)
+		return fail(SRH_E_INVALID, "the data costs of srh_twoview_mrf_optimize are the caller's volume: the context keeps none");
+	HIP_TRY(hipSetDevice(c->device));
+	const int w = c->tvmrf_w, h = c->tvmrf_h, L = c->tvmrf_l;
+	const size_t n = (size_t)w*h;
+	TvMrfLayout lay;
+	launch_twoview_mrf_layout(c->tvmrf, w, h, L, lay);
+	if (labels) HIP_TRY(hipMemcpyAsync(labels, lay.ans, n*sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+	if (data_costs) HIP_TRY(hipMemcpyAsync(data_costs, c->tvmrf_costs, n*L*sizeof(double), hipMemcpyDeviceToHost, c->stream));
+	if (messages) {
+		HIP_TRY(hipMemcpy2DAsync(messages, 2*L*sizeof(double), lay.Mh, L*sizeof(double), L*sizeof(double), n, hipMemcpyDeviceToHost, c->stream));
+		HIP_TRY(hipMemcpy2DAsync(messages + L, 2*L*sizeof(double), lay.Mv, L*sizeof(double), L*sizeof(double), n, hipMemcpyDeviceToHost, c->stream));
 	}
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	return SRH_OK;

@@ -376,6 +376,25 @@ hipError_t launch_mrf_setup(hipStream_t st, double *buf, int w, int h, int K, do
 hipError_t launch_mrf_sweep(hipStream_t st, double *buf, int w, int h, int K, double psiu, int sweep);
 hipError_t launch_mrf_energy(hipStream_t st, double *buf, int w, int h, int K, double psiu);
 hipError_t launch_mrf_depth(hipStream_t st, const ViewDev *views, int slot, double *buf, int w, int h, int K);
+// MRF stage of TwoViewStereo (srh_twoview_mrf.hip): the message planes, hand-over granules, labels and control words in one
+// scratch buffer carved the same way by every launch; the data costs ([pixel][L] doubles) are a buffer of their own
+struct TvMrfLayout {
+	double *Mh, *Mv, *trash, *partial, *energy;
+	unsigned long long *hand; size_t hand_words;
+	unsigned *status, *sync;
+	int32_t *ans;
+	int nparts, nbands;
+	size_t sync_words, total_doubles;
+};
+size_t twoview_mrf_scratch_doubles(int w, int h, int L);
+void launch_twoview_mrf_layout(double *buf, int w, int h, int L, TvMrfLayout &lay);
+hipError_t launch_twoview_mrf_setup(hipStream_t st, double *buf, int w, int h, int L, TvMrfLayout &lay);
+hipError_t launch_twoview_mrf_sweep(hipStream_t st, double *buf, const double *costs, int w, int h, int L, double lambda, double smax, int sweep);
+hipError_t launch_twoview_mrf_energy(hipStream_t st, double *buf, const double *costs, int w, int h, int L, double lambda, double smax);
+hipError_t launch_twoview_mrf_depth(hipStream_t st, const ViewDev *views, int slot, const srh_params &P, double *buf, int w, int h, int L);
+// the label cost volume of rows [y0, y0 + nrows): cost [pixel][label], pixel (optional) [pixel][label][x2, y2]
+hipError_t launch_twoview_label_costs(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P, bool sad,
+                                      int y0, int nrows, double fill, double *cost, int32_t *pixel);
 void launch_epipolar_preview(hipStream_t st, const ViewDev *views, int ref, int oth, double zmin, double zmax, int nd,
                              int nq, const double *xy, double *out, int32_t *counts);
 void launch_refraction_error(hipStream_t st, const ViewDev *views, int v1, int v2, int n, const double *p1, const double *p2, double *err);

@@ -43,6 +43,8 @@ TwoViewStereo::TwoViewStereo(CameraPtr leftView_, Image left_, Image leftMask_,
 	srh_params_twoview_defaults(&params_);
 	params_.min_depth = minDepth; params_.max_depth = maxDepth;
 	params_.num_depth_levels = numDepthLevels; params_.image_scale = imageScale;
+	srh_twoview_mrf_params_defaults(&mrfParams_);
+	mrfInfo_[0] = mrfInfo_[1] = srh_mrf_info();
 	if (srh_create(deviceOrdinal, &ctx_) != SRH_OK) { error_ = srh_last_error(); ctx_ = nullptr; }
 }
 
@@ -181,7 +183,7 @@ double TwoViewStereo::depthFromLabel(int label) const {
 }
 
 void TwoViewStereo::computeDepthMaps() {
-	// twoviewstereo.cpp:150-227: cost volumes (steps 1,3), cross-check (5), colourise, finished (8)
+	// twoviewstereo.cpp:150-227: cost volumes (steps 1,3; setUseMRF: + the optimiser, 2,4), cross-check (5), colourise, finished (8)
 	if (!ctx_) { if (error_.empty()) error_ = "no device context"; return; }
 	if (!leftView || !rightView || left.isNull() || right.isNull()) { error_ = "missing view"; return; }
 	if (!uploadViews()) return;
@@ -194,7 +196,9 @@ void TwoViewStereo::computeDepthMaps() {
 		srh_set_hooks(ctx_, nullptr, nullptr, nullptr);
 		return;
 	}
-	const int rc_ = srh_twoview_compute(ctx_, 0, 1, &params_, computedDepthLeft.data(), computedDepthRight.data());
+	mrfInfo_[0] = mrfInfo_[1] = srh_mrf_info();
+	const int rc_ = useMrf ? srh_twoview_compute_mrf(ctx_, 0, 1, &params_, &mrfParams_, computedDepthLeft.data(), computedDepthRight.data(), mrfInfo_)
+	                       : srh_twoview_compute(ctx_, 0, 1, &params_, computedDepthLeft.data(), computedDepthRight.data());
 	srh_set_hooks(ctx_, nullptr, nullptr, nullptr);
 	if (rc_ == SRH_E_CANCELLED) return;              // reference: silent return on cancel
 	if (rc_ != SRH_OK) { error_ = srh_last_error(); return; }

@@ -42,6 +42,16 @@ public:
 	void setSadDense(int on) { sadDenseOn = on; }
 	int sadDense() const { return sadDenseOn; }
 
+	// The MRF stage (a USE_MRF build of the reference, twoviewstereo.cpp:240-258, 308-403, 504-570; PARITY UNPINNED, see
+	// stereo_recon_hip.h): off (default) computeDepthMaps is the WTA of the reference as it is compiled; on, each direction's
+	// depth map comes from TRW-S over the full label cost volume (srh_twoview_compute_mrf: progress 1, 2 "Optimizing...",
+	// 3, 4 "Optimizing...", 5, 8), the cross-check and the optional hole filling unchanged.  numSteps() stays 8.
+	void setUseMRF(bool on) { useMrf = on; }
+	bool useMRF() const { return useMrf; }
+	srh_twoview_mrf_params &mrfParams() { return mrfParams_; }     // SMOOTHNESS_EXP / _MAX / _LAMBDA, 50 sweeps, drop 5
+	// what the optimiser of the last computeDepthMaps reported for the left / right map (iterations 0: none ran)
+	const srh_mrf_info &mrfInfo(bool left = true) const { return mrfInfo_[left ? 0 : 1]; }
+
 	// Candidate pixels, in visiting order, of pixel (x,y) of the left (fromLeft) or right view in the
 	// other view.  The reference's public epipolarCurve (twoviewstereo.hpp:66-70) takes the unprojected
 	// ray, camera offset, plane normal, mask and view; all of them follow from the pixel and the
@@ -99,6 +109,9 @@ private:
 	int filterFlags = 0;
 	int costKind = SRH_COST_NCC;
 	int sadDenseOn = 0;
+	bool useMrf = false;
+	srh_twoview_mrf_params mrfParams_;
+	srh_mrf_info mrfInfo_[2];
 	srh_context *ctx_;
 	std::string error_;
 };

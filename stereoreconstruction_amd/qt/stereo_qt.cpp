@@ -106,7 +106,17 @@ TwoViewStereo::TwoViewStereo(CameraPtr leftView_, QImage left_, QImage leftMask_
 	computedDepthLeft.assign(static_cast<size_t>(left.w)*left.h, NaN);
 	computedDepthRight.assign(static_cast<size_t>(left.w)*left.h, NaN);      // sized from the LEFT image, as :119
 	srh_params_twoview_defaults(&params_);
+	srh_twoview_mrf_params_defaults(&mrfParams_);
+	mrfInfo_[0] = mrfInfo_[1] = srh_mrf_info();
 	if (srh_create(deviceOrdinal, &ctx_) != SRH_OK) { error_ = srh_last_error(); ctx_ = nullptr; }
+}
+
+namespace { void relayToTwoView(int step, const char *stage, void *user) { static_cast<TwoViewStereo *>(user)->relayProgress(step, stage); } }
+
+void TwoViewStereo::relayProgress(int step, const char *stage) {
+	if (isCancelled()) cancelWord_ = 1;
+	emit progressUpdate(step);
+	emit stageUpdate(QString::fromLatin1(stage));
 }
 
 TwoViewStereo::~TwoViewStereo() { if (ctx_) srh_destroy(ctx_); }
@@ -169,6 +179,21 @@ void TwoViewStereo::computeDepthMaps() {
 	if (!uploadViews()) return;
 	if (srh_set_option(ctx_, "cost", costKind) != SRH_OK) { error_ = srh_last_error(); return; }
 	srh_set_option(ctx_, "sad_dense", sadDenseOn);
+	mrfInfo_[0] = mrfInfo_[1] = srh_mrf_info();
+	if (useMrf) {
+		// a USE_MRF build: the library sequences the run and reports the steps (1, 2, 3, 4, 5, [6, 7,] 8) through its hook
+		cancelWord_ = isCancelled() ? 1 : 0;
+		srh_set_hooks(ctx_, &cancelWord_, relayToTwoView, this);
+		srh_set_option(ctx_, "filter_invalid", filterFlags);
+		const int rc = srh_twoview_compute_mrf(ctx_, 0, 1, &params_, &mrfParams_, computedDepthLeft.data(), computedDepthRight.data(), mrfInfo_);
+		srh_set_option(ctx_, "filter_invalid", 0);
+		srh_set_hooks(ctx_, nullptr, nullptr, nullptr);
+		if (rc == SRH_E_CANCELLED) return;
+		if (rc != SRH_OK) { error_ = srh_last_error(); return; }
+		resultLeft = colorize(computedDepthLeft, left.w, left.h);
+		resultRight = colorize(computedDepthRight, right.w, right.h);
+		return;
+	}
 	emit progressUpdate(1);
 	emit stageUpdate("Computing cost volume for left image...");
 	if (srh_twoview_wta(ctx_, 0, 1, &params_, 0, 0) != SRH_OK) { error_ = srh_last_error(); return; }

@@ -123,6 +123,14 @@ public:
 	// SAD of a rectified pair on the dense plan (option "sad_dense": 1 = on, 0 = default): a tuning switch, never the result
 	void setSadDense(int on) { sadDenseOn = on; }
 	int sadDense() const { return sadDenseOn; }
+	// the MRF stage (a USE_MRF build of the reference; PARITY UNPINNED, stereo_recon_hip.h): off (default) = the WTA; on, each
+	// map comes from TRW-S over the label cost volume (srh_twoview_compute_mrf: progress 1, 2 "Optimizing...", 3, 4, 5, 8),
+	// cross-check and optional hole filling unchanged.  Cancellation is observed at every progress step.
+	void setUseMRF(bool on) { useMrf = on; }
+	bool useMRF() const { return useMrf; }
+	srh_twoview_mrf_params &mrfParams() { return mrfParams_; }
+	const srh_mrf_info &mrfInfo(bool left = true) const { return mrfInfo_[left ? 0 : 1]; }
+	void relayProgress(int step, const char *stage);       // (the library's progress hook lands here)
 
 public: // Task implementation continued: public in the reference as well (stereo/twoviewstereo.hpp:50-52)
 	void runTask() { computeDepthMaps(); }
@@ -154,6 +162,10 @@ private:
 	int filterFlags = 0;
 	int costKind = SRH_COST_NCC;
 	int sadDenseOn = 0;
+	bool useMrf = false;
+	srh_twoview_mrf_params mrfParams_;
+	srh_mrf_info mrfInfo_[2];
+	volatile int cancelWord_ = 0;                          // what the library polls: set from isCancelled() at progress steps
 	srh_context *ctx_;
 	mutable bool uploaded_ = false;                        // views resident on the device (epipolarCurve before computeDepthMaps)
 	bool uploadViews() const;
