@@ -165,6 +165,8 @@ int  srh_set_hooks(srh_context *ctx, const volatile int *cancel, srh_progress_fn
 int  srh_synchronize(srh_context *ctx);
 /* TwoView matching cost (option "cost"): TwoViewStereo::cost_ncc (default) or cost_sad (twoviewstereo.cpp:864-905) */
 enum { SRH_COST_NCC = 0, SRH_COST_SAD = 1 };
+/* By-products of the TwoView winner-take-all scan a pass keeps per reference pixel (option "wta_outputs") */
+enum { SRH_WTA_WINNERS = 1, SRH_WTA_COSTS = 2 };
 /* Tuning / test switches (results never depend on them, "arith" = 1 / 2, "cost" and "filter_invalid" excepted):
  *   "force_generic"   0 default paths; 1 never the dense row-aligned TwoView kernels nor the MVS list kernels;
  *                     2 additionally no candidate lists at all (one thread per pixel walks and costs its curve)
@@ -233,6 +235,16 @@ enum { SRH_COST_NCC = 0, SRH_COST_SAD = 1 };
  *                     than the chunk after all, a candidate off its row, "force_dense" included) -- runs on the row-run,
  *                     list-order or walk kernels exactly as with 0.  The fused plan is never taken under SAD.  Nothing
  *                     changes under "cost" = SRH_COST_NCC.  Identical bits: a tuning switch like "strip" and "tscan".
+ *   "wta_outputs"     never changes a depth map.  0 (default): a WTA pass keeps the depth only -- no allocation, no extra store.
+ *                     SRH_WTA_WINNERS (1): every pass ref -> oth (srh_twoview_wta, both passes of srh_twoview_compute) also keeps,
+ *                     per reference pixel, win_xy -- the candidate pixel of `oth` that held minCost at the end of the scan -- and
+ *                     runner_xy -- the one that held it immediately before the last improvement, whose cost is the secondBest of
+ *                     the ratio test; (-1, -1) = none.  SRH_WTA_WINNERS | SRH_WTA_COSTS (3): also min_cost and second_cost, the
+ *                     cost of (x, y) -> win_xy / runner_xy in the reference's arithmetic whatever "arith" chose the winner -- the
+ *                     bits srh_twoview_pair_costs returns for that pair under the current "cost"; +INF = none.  2 alone:
+ *                     SRH_E_INVALID.  16 / 32 bytes per pixel of the reference view in device memory, allocated by the first
+ *                     pass that keeps them; read with srh_view_wta_outputs*.  They describe the WTA stage: the cross-check and
+ *                     "filter_invalid" do not touch them.
  *   "filter_invalid"  0 (default, as the reference's call site under #if 0): srh_twoview_compute ends with the cross-check;
  *                     SRH_FILTER_* flags (1 gaps, 2 median, 3 both): it then runs srh_view_filter_invalid on both maps,
  *                     with progress steps 6 "Filling invalid pixels..." and, with the median, 7 "Filtering invalid pixels..."
@@ -252,6 +264,19 @@ int  srh_view_size(srh_context *ctx, int slot, int *w, int *h);
 int  srh_view_depth_download(srh_context *ctx, int slot, double *host_out);
 int  srh_view_depth_upload(srh_context *ctx, int slot, const double *host_in);
 int  srh_view_depth_device_ptr(srh_context *ctx, int slot, void **dev_ptr);
+/* The by-products of the last TwoView WTA pass that had `slot` as its reference view (option "wta_outputs"):
+ * win_xy, runner_xy: w*h*2 int32 (x, y), (-1, -1) = none; min_cost, second_cost: w*h doubles, +INF = none.  A pass over
+ * rows [y0, y1) writes those rows only, as it does in the depth map; rows no pass has written since the planes were made
+ * hold the "none" values.  srh_view_wta_outputs: host buffers, each may be NULL, synchronous (it completes what is in
+ * flight first, like srh_view_depth_download).  srh_view_wta_outputs_device: the device planes themselves, with the
+ * semantics of srh_view_depth_device_ptr; each argument may be NULL.  srh_view_wta_outputs_state: what the slot holds --
+ * *flags = SRH_WTA_* bits, 0 when it holds nothing, *oth_slot = the other view of that pass (-1: none).
+ * Both getters return SRH_E_INVALID when the slot holds nothing (the option was off, or no pass yet), when the slot was
+ * uploaded again since, when the slot's depth map last came from srh_twoview_mrf* (no scan made it), and when a cost
+ * plane is asked for and only the winners were kept. */
+int  srh_view_wta_outputs(srh_context *ctx, int slot, int32_t *win_xy, int32_t *runner_xy, double *min_cost, double *second_cost);
+int  srh_view_wta_outputs_device(srh_context *ctx, int slot, void **win_xy, void **runner_xy, void **min_cost, void **second_cost);
+int  srh_view_wta_outputs_state(srh_context *ctx, int slot, int *flags, int *oth_slot);
 /* Asynchronous device-to-device copy of the slot's depth map (w*h doubles) into caller-owned
  * DEVICE memory of `dst_bytes` bytes (e.g. a tensor that RCCL then gathers); ordered on the context
  * stream.  SRH_E_INVALID when the buffer is smaller than the map (views may differ in size). */

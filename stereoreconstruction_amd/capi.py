@@ -97,6 +97,9 @@ FILTER_GAPS, FILTER_MEDIAN = 1, 2
 # option "cost" / srh_twoview_pair_costs kind: TwoViewStereo::cost_ncc, cost_sad
 COST_NCC, COST_SAD = 0, 1
 
+# option "wta_outputs": the by-products of the WTA scan a pass keeps (SRH_WTA_*)
+WTA_WINNERS, WTA_COSTS = 1, 2
+
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_int, C.c_char_p, C.c_void_p)
 
@@ -108,6 +111,7 @@ EXPORTS = [
     "srh_create", "srh_destroy", "srh_set_stream", "srh_set_hooks", "srh_synchronize", "srh_set_option",
     "srh_view_upload", "srh_view_size", "srh_view_depth_download", "srh_view_depth_upload",
     "srh_view_depth_device_ptr", "srh_view_depth_copy_to_device", "srh_view_depth_copy_from_device",
+    "srh_view_wta_outputs", "srh_view_wta_outputs_device", "srh_view_wta_outputs_state",
     "srh_twoview_wta", "srh_twoview_cross_check", "srh_twoview_compute", "srh_twoview_cost_rows", "srh_twoview_pair_costs", "srh_debug_exp",
     "srh_mvs_initial_estimate", "srh_mvs_cross_check", "srh_view_point_cloud", "srh_view_filter_invalid",
     "srh_epipolar_curves",
@@ -174,6 +178,9 @@ def lib():
     L.srh_view_depth_download.argtypes = [vp, C.c_int, c_double_p]
     L.srh_view_depth_upload.argtypes = [vp, C.c_int, c_double_p]
     L.srh_view_depth_device_ptr.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    L.srh_view_wta_outputs.argtypes = [vp, C.c_int, c_int32_p, c_int32_p, c_double_p, c_double_p]
+    L.srh_view_wta_outputs_device.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.srh_view_wta_outputs_state.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.srh_mrf_params_defaults.argtypes = [C.POINTER(SrhMrfParams)]
     L.srh_mrf_params_defaults.restype = None
     L.srh_mvs_mrf_estimate.argtypes = [vp, C.c_int, C.c_int, C.c_void_p, C.POINTER(SrhMrfParams), C.POINTER(SrhMrfInfo)]
@@ -445,6 +452,36 @@ class Context:
         p = C.c_void_p()
         _check(lib().srh_view_depth_device_ptr(self._h, slot, C.byref(p)))
         return p.value
+
+    def wta_outputs_state(self, slot):
+        """(flags, oth_slot): the WTA_* planes the slot holds from its last WTA pass as the reference view (0: none) and the
+        other view of that pass (srh_view_wta_outputs_state)."""
+        f, o = C.c_int(0), C.c_int(-1)
+        _check(lib().srh_view_wta_outputs_state(self._h, slot, C.byref(f), C.byref(o)))
+        return f.value, o.value
+
+    def wta_outputs(self, slot, costs=None):
+        """The by-products of the slot's last WTA pass (option "wta_outputs"): dict(win_xy (h, w, 2) int32, runner_xy
+        (h, w, 2) int32, min_cost (h, w), second_cost (h, w)); (-1, -1) / +inf = none.  costs: None = the cost planes when
+        they were kept (else absent from the dict), True = ask for them (an error when only the winners were kept)."""
+        w, h = self.view_size(slot)
+        if costs is None:
+            costs = bool(self.wta_outputs_state(slot)[0] & WTA_COSTS)
+        out = {"win_xy": np.empty((h, w, 2), dtype=np.int32), "runner_xy": np.empty((h, w, 2), dtype=np.int32)}
+        if costs:
+            out["min_cost"] = np.empty((h, w), dtype=np.float64)
+            out["second_cost"] = np.empty((h, w), dtype=np.float64)
+        _check(lib().srh_view_wta_outputs(self._h, slot, out["win_xy"].ctypes.data_as(c_int32_p),
+                                          out["runner_xy"].ctypes.data_as(c_int32_p),
+                                          _dptr(out["min_cost"]) if costs else None, _dptr(out["second_cost"]) if costs else None))
+        return out
+
+    def wta_outputs_device(self, slot, costs=True):
+        """Device addresses (win_xy, runner_xy, min_cost, second_cost) of the slot's planes (srh_view_wta_outputs_device)."""
+        p = [C.c_void_p() for _ in range(4)]
+        _check(lib().srh_view_wta_outputs_device(self._h, slot, C.byref(p[0]), C.byref(p[1]),
+                                                 C.byref(p[2]) if costs else None, C.byref(p[3]) if costs else None))
+        return tuple(q.value for q in p)
 
     def copy_depth_to_device(self, slot, dst_dev_ptr, dst_bytes):
         _check(lib().srh_view_depth_copy_to_device(self._h, slot, C.c_void_p(dst_dev_ptr), C.c_size_t(dst_bytes)))

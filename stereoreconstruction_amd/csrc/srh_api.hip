@@ -230,6 +230,11 @@ struct ViewHost {
 	bool act_valid = false;        //   when the MultiViewStereo list path first asks (ensure_act); TwoView callers never pay for it
 	srh_camera cam;
 	// MRF branch over several views (srh_mvs_initial_estimate_peaks / srh_mvs_mrf_estimate_views)
+	// by-products of the last TwoView WTA pass with this view as the reference (option "wta_outputs"):
+	// win_xy | runner_xy (2 int32 each per pixel) and min_cost | second_cost, allocated by the first pass that keeps them
+	DevBuf<int32_t> wta_xy;
+	DevBuf<double>  wta_cost;
+	int wta_flags = 0, wta_oth = -1;            // what the planes hold (SRH_WTA_*; 0: nothing, or stale) and against which slot
 	DevBuf<double> peaks; int peaks_k = 0;      // top-K peaks of the last initial estimate
 	DevBuf<double> mrf;                         // this view's own TRW-S scratch
 };
@@ -350,6 +355,7 @@ struct srh_context {
 	int filter_replay = 0;                              // option "filter_replay": every median hole by the exact replay (test hook)
 	int cost_kind = SRH_COST_NCC;                       // option "cost": the TwoView matching cost, SRH_COST_NCC or SRH_COST_SAD
 	int sad_dense = 0;                                  // option "sad_dense": cost_sad of row-aligned rigs on the dense plan (srh_sad_strip.hip)
+	int wta_outputs = 0;                                // option "wta_outputs": SRH_WTA_* planes a TwoView WTA pass keeps per reference pixel (never changes a depth map)
 };
 
 static bool cancelled(srh_context *c) { return c->cancel && *c->cancel; }
@@ -678,6 +684,7 @@ static void free_view(ViewHost &v) {
 	if (v.rgba || v.gray || v.edges || v.tvp || v.geo5) (void)hipDeviceSynchronize();
 	v.rgba.release(); v.mask.release(); v.gray.release(); v.gray_tv.release(); v.depth.release(); v.edges.release();
 	v.full.release(); v.fulls.release(); v.grayp.release(); v.fullsp.release(); v.tvp.release(); v.geo5.release(); v.fullp.release(); v.act.release(); v.peaks.release(); v.mrf.release();
+	v.wta_xy.release(); v.wta_cost.release();
 	v = ViewHost();
 }
 
@@ -798,6 +805,11 @@ extern "C" int srh_set_option(srh_context *c, const char *name, long value) {
 		c->cost_kind = (int)value; return SRH_OK;
 	}
 	if (!strcmp(name, "sad_dense")) { c->sad_dense = value != 0; return SRH_OK; }
+	if (!strcmp(name, "wta_outputs")) {
+		if (value != 0 && value != SRH_WTA_WINNERS && value != (SRH_WTA_WINNERS | SRH_WTA_COSTS))
+			return fail(SRH_E_INVALID, "wta_outputs must be 0, 1 (SRH_WTA_WINNERS) or 3 (SRH_WTA_WINNERS | SRH_WTA_COSTS): the costs are those of the kept winners");
+		c->wta_outputs = (int)value; return SRH_OK;
+	}
 	if (!strcmp(name, "tscan")) { c->tscan = value != 0; return SRH_OK; }
 	if (!strcmp(name, "geodma")) { c->geodma = value != 0; return SRH_OK; }
 	if (!strcmp(name, "f32_form")) { c->f32_form = value != 0; return SRH_OK; }
@@ -849,6 +861,7 @@ extern "C" int srh_view_upload(srh_context *c, int slot, int w, int h,
 	v.full_r = 0; v.fulls_r = 0;                                // recomputed on demand for the new pixels
 	v.tvp_valid = false; v.fullp_r = 0; v.grayp_valid = false; v.fullsp_r = 0; v.geo5_valid = false; v.geo5_denied = false;
 	v.peaks_k = 0;                                              // the top-K peaks belonged to the previous image
+	v.wta_flags = 0; v.wta_oth = -1;                            // and so did the WTA by-products
 	if (c->mrf_w == w && c->mrf_h == h) c->mrf_w = c->mrf_h = c->mrf_k = 0;
 	if (c->tvmrf_w == w && c->tvmrf_h == h) c->tvmrf_w = c->tvmrf_h = c->tvmrf_l = 0;
 	for (int j = 0; j < SRH_MAX_VIEWS; ++j) { v.list_mode[j] = 0; c->views[j].list_mode[slot] = 0; }   // new geometry
@@ -900,6 +913,48 @@ extern "C" int srh_view_depth_device_ptr(srh_context *c, int slot, void **dev_pt
 	int rc = check_slot(c, slot, true); if (rc) return rc;
 	if (!dev_ptr) return fail(SRH_E_INVALID, "null output");
 	*dev_ptr = c->views[slot].depth;
+	return SRH_OK;
+}
+
+// ---- by-products of the WTA scan (option "wta_outputs")
+static int check_wta_outputs(srh_context *c, int slot, bool costs) {
+	const ViewHost &v = c->views[slot];
+	if (!v.wta_flags) return fail(SRH_E_INVALID, "view slot %d holds no WTA outputs (option \"wta_outputs\" off, no WTA pass since the upload, or its depth map came from the MRF stage)", slot);
+	if (costs && !(v.wta_flags & SRH_WTA_COSTS)) return fail(SRH_E_INVALID, "view slot %d kept the winners only (wta_outputs = 1): no cost planes", slot);
+	return SRH_OK;
+}
+
+extern "C" int srh_view_wta_outputs_state(srh_context *c, int slot, int *flags, int *oth_slot) {
+	int rc = check_slot(c, slot, true); if (rc) return rc;
+	const ViewHost &v = c->views[slot];
+	if (flags) *flags = v.wta_flags;
+	if (oth_slot) *oth_slot = v.wta_flags ? v.wta_oth : -1;
+	return SRH_OK;
+}
+
+extern "C" int srh_view_wta_outputs_device(srh_context *c, int slot, void **win_xy, void **runner_xy, void **min_cost, void **second_cost) {
+	int rc = check_slot(c, slot, true); if (rc) return rc;
+	if ((rc = check_wta_outputs(c, slot, min_cost || second_cost))) return rc;
+	const ViewHost &v = c->views[slot];
+	const size_t n = (size_t)v.w*v.h;
+	if (win_xy) *win_xy = v.wta_xy;
+	if (runner_xy) *runner_xy = v.wta_xy + 2*n;
+	if (min_cost) *min_cost = v.wta_cost;
+	if (second_cost) *second_cost = v.wta_cost + n;
+	return SRH_OK;
+}
+
+extern "C" int srh_view_wta_outputs(srh_context *c, int slot, int32_t *win_xy, int32_t *runner_xy, double *min_cost, double *second_cost) {
+	int rc = check_slot(c, slot, true); if (rc) return rc;
+	if ((rc = check_wta_outputs(c, slot, min_cost || second_cost))) return rc;
+	HIP_TRY(hipSetDevice(c->device));
+	const ViewHost &v = c->views[slot];
+	const size_t n = (size_t)v.w*v.h;
+	if (win_xy) HIP_TRY(hipMemcpyAsync(win_xy, v.wta_xy, 2*n*sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+	if (runner_xy) HIP_TRY(hipMemcpyAsync(runner_xy, v.wta_xy + 2*n, 2*n*sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+	if (min_cost) HIP_TRY(hipMemcpyAsync(min_cost, v.wta_cost, n*sizeof(double), hipMemcpyDeviceToHost, c->stream));
+	if (second_cost) HIP_TRY(hipMemcpyAsync(second_cost, v.wta_cost + n, n*sizeof(double), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
 	return SRH_OK;
 }
 
@@ -1116,6 +1171,23 @@ static bool rig_is_row_aligned(const srh_camera &a, const srh_camera &b, double 
 
 static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p, int y0, int y1);
 
+// The WTA by-products of a pass ref -> oth (option "wta_outputs"): the planes exist and hold either what an earlier pass of
+// the same kind left (a pass over some rows writes those rows only, as it does in the depth map) or the "none" values.
+// Allocated like the view's other planes; a refusal is a clean SRH_E_DEVICE before the pass queues anything.  Option off:
+// no allocation, no launch -- the slot's planes, if any, no longer describe its depth map.
+static int ensure_wta_planes(srh_context *c, int ref, int oth) {
+	ViewHost &v = c->views[ref];
+	if (!c->wta_outputs) { v.wta_flags = 0; return SRH_OK; }
+	const size_t n = (size_t)v.w*v.h;
+	if (v.wta_flags == c->wta_outputs && v.wta_oth == oth) return SRH_OK;
+	if (!v.wta_xy) HIP_TRY(v.wta_xy.alloc(4*n));
+	if ((c->wta_outputs & SRH_WTA_COSTS) && !v.wta_cost) HIP_TRY(v.wta_cost.alloc(2*n));
+	HIP_TRY(hipMemsetAsync(v.wta_xy, 0xff, 4*n*sizeof(int32_t), c->stream));           // (-1, -1): no winner, no runner-up
+	if (c->wta_outputs & SRH_WTA_COSTS) launch_fill(c->stream, v.wta_cost, 2*n, __builtin_inf());
+	v.wta_flags = c->wta_outputs; v.wta_oth = oth;
+	return SRH_OK;
+}
+
 // A first guess of a pair's list capacities, before any pass has measured them (the list path of srh_twoview_wta):
 // cmax = candidates per pixel, smax = cost slots per pixel (row runs in 8-column blocks).  A curve's candidates are the
 // raster points of its kept segments with the joints counted once, so at most the Chebyshev length of the polyline through
@@ -1222,6 +1294,18 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 	const int R = p->window_radius;
 	const int T = (2*R + 1)*(2*R + 1);
 	const size_t budget = band_budget(c);
+	// by-products of the scan (option "wta_outputs"): every scan kernel of the pass stores winner and runner-up where it
+	// stores the depth (wout), and twoview_winner_costs_kernel follows the band's last scan with their exact costs.  A
+	// repeated attempt rewrites every row of the pass, so the planes hold what the attempt whose depth map stands wrote.
+	if (!c->diag && (rc = ensure_wta_planes(c, ref, oth))) return rc;
+	int32_t *const wout = (c->wta_outputs && !c->diag) ? (int32_t *)c->views[ref].wta_xy : nullptr;
+	auto winner_costs = [&](int by, int nr, bool wimg_layout) {
+		if (!wout || !(c->wta_outputs & SRH_WTA_COSTS)) return;
+		Scope s(c, "twoview_winner_costs_kernel");
+		double *mc = c->views[ref].wta_cost;
+		launch_twoview_winner_costs(c->stream, c->d_views, ref, oth, W, *p, c->cost_kind == SRH_COST_SAD, by, nr, c->band.wbuf, wimg_layout,
+		                            wout, mc, mc + (size_t)W*H);
+	};
 
 	// ---- plan: dense row-aligned kernels, or the general curve-walk kernel
 	// (cost_sad: the dense plan only with option "sad_dense", its cost rows filled by twoview_strip_sad_kernel; no per-tile
@@ -1264,7 +1348,8 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 			const int nr = std::min((int)rows, y1 - by);
 			run_weights(c, ref, W, *p, by, nr, SRH_WTILE);
 			Scope s(c, "twoview_fused_kernel");
-			launched = launch_twoview_fused(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, c->band.tnum, c->d_cnt);
+			launched = launch_twoview_fused(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, c->band.tnum, c->d_cnt, wout);
+			if (launched) winner_costs(by, nr, false);
 		}
 		HIP_TRY(hipGetLastError());
 		if (launched) {
@@ -1421,7 +1506,7 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 						                           c->rows_masked == 1 ? (const uint32_t *)(O.full + full_stat_offset((size_t)O.w*O.h)) : nullptr); }
 						{ Scope s(c, "twoview_rows_scan_kernel");
 						  launch_twoview_rows_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, cnt_band, c->band.lcand, cmax,
-						                           c->band.lrowinfo, c->band.lmeta, c->band.cost, smax, rows_cert ? c->band.cflag : nullptr, -1, c->d_cnt); }
+						                           c->band.lrowinfo, c->band.lmeta, c->band.cost, smax, rows_cert ? c->band.cflag : nullptr, -1, c->d_cnt, wout); }
 						if (rows_cert) {
 							// certified arithmetic: the flagged pixels once more in the reference's arithmetic, launched for a capacity
 							// (a list cut by a too small capacity is harmless here: the pass is repeated anyway)
@@ -1431,8 +1516,9 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 							                             c->band.lrowinfo, c->band.lmeta, c->band.cost, smax, c->d_cnt); }
 							Scope s(c, "twoview_rows_rescan_kernel");
 							launch_twoview_rows_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, cnt_band, c->band.lcand, cmax,
-							                         c->band.lrowinfo, c->band.lmeta, c->band.cost, smax, c->band.cflag, cap, c->d_cnt);
+							                         c->band.lrowinfo, c->band.lmeta, c->band.cost, smax, c->band.cflag, cap, c->d_cnt, wout);
 						}
+						winner_costs(by, nr, true);
 						continue;
 					}
 					run_weights(c, ref, W, *p, by, nr, SRH_WTILE);
@@ -1448,7 +1534,8 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 					  launch_twoview_list_cost(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, O.full,
 					                           cnt_band, c->band.lcand, c->band.cost, cmax, c->d_cnt); }
 					{ Scope s(c, "twoview_list_scan_kernel");
-					  launch_twoview_list_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, cnt_band, c->band.lcand, c->band.cost, cmax); }
+					  launch_twoview_list_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, cnt_band, c->band.lcand, c->band.cost, cmax, wout); }
+					winner_costs(by, nr, false);
 				}
 				if (c->defer && attempt == 0 && pass == 0 && rows_mode &&
 				    ((c->list_cmax_hint > 0 && c->list_smax_hint > 0 && c->views[ref].list_mode[oth] == 1) ||
@@ -1644,7 +1731,7 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 				if ((rc = cost_pass(cost_arith))) return rc;
 				{ Scope s(c, "twoview_scan_kernel");
 				  launch_twoview_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.tnum, c->band.cost, cstride, c->d_cnt, c->band.prange,
-				                      cert ? c->band.cflag : nullptr, -1, cert && strip ? c->band.pconst : nullptr, tscan ? c->band.stpl : nullptr, c->band.tileflag, c->num_cus); }
+				                      cert ? c->band.cflag : nullptr, -1, cert && strip ? c->band.pconst : nullptr, tscan ? c->band.stpl : nullptr, c->band.tileflag, c->num_cus, wout); }
 				if (cert) {
 					// the pixels whose decisions the bound does not cover, in the reference's arithmetic: their cost rows are
 					// refilled and they are scanned again -- launched for a capacity, the count stays on the device
@@ -1654,11 +1741,13 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 					                        c->views[oth].tvp, c->band.cost, cstride, c->d_cnt); }
 					Scope s(c, "twoview_rescan_kernel");
 					launch_twoview_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.tnum, c->band.cost, cstride, c->d_cnt, c->band.prange,
-					                    c->band.cflag, cap);
+					                    c->band.cflag, cap, nullptr, nullptr, nullptr, c->num_cus, wout);
 				}
+				winner_costs(by, nr, wimg);
 			} else {
-				Scope s(c, "twoview_generic_kernel");
-				launch_twoview_generic(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, wstride, c->d_cnt, sad);
+				{ Scope s(c, "twoview_generic_kernel");
+				  launch_twoview_generic(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, wstride, c->d_cnt, sad, wout); }
+				winner_costs(by, nr, false);
 			}
 		}
 		HIP_TRY(hipGetLastError());
@@ -1826,6 +1915,8 @@ extern "C" int srh_twoview_compute(srh_context *c, int left, int right, const sr
 					v.tvp_valid = true;
 				}
 			}
+		// (and the WTA by-products' planes of both views, option "wta_outputs", are allocated and hold their "none" values there)
+		if ((rc = ensure_wta_planes(c, left, right)) || (rc = ensure_wta_planes(c, right, left))) return rc;
 		HIP_TRY(hipEventRecord(T.go, c->stream));
 	}
 	// progress steps as TwoViewStereo emits them (twoviewstereo.cpp:234,405,597,225)
@@ -2641,9 +2732,10 @@ static int tvmrf_reserve(srh_context *c, int w, int h, int L, bool own_costs)
 static int tvmrf_run(srh_context *c, int slot, const srh_params *p, int L, const double *costs, const srh_twoview_mrf_params *m, srh_mrf_info *info)
 {
 	int rc;
-	const ViewHost &v = c->views[slot];
+	ViewHost &v = c->views[slot];
 	const int w = v.w, h = v.h;
 	c->tvmrf_w = c->tvmrf_h = c->tvmrf_l = 0;
+	v.wta_flags = 0;                                            // no scan made this depth map: the WTA by-products are stale
 	TvMrfLayout lay;
 	HIP_TRY(launch_twoview_mrf_setup(c->stream, c->tvmrf, w, h, L, lay));
 	struct { double energy, pad; unsigned status[4]; } hs;

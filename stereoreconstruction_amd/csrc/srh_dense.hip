@@ -1611,6 +1611,7 @@ __device__ __forceinline__ int wave_max_i32(int v) {
 struct TwoViewScanState {
 	double minCost, secondBest;
 	int wcol;                 // winning column relative to lo, -1 = none
+	int pcol;                 // WTA: the column that held minCost before the last improvement (its cost is secondBest), -1 = none
 };
 
 // CERT: the cost rows hold FUSED costs (twoview_strip_cost_kernel<.., 3>): the reference's decisions are replayed on
@@ -1631,13 +1632,16 @@ struct TwoViewScanState {
 // LISTED: the exact scan of the flagged pixels only (lane k takes pixel cflag[1 + k]; their cost rows were refilled in
 // the reference's arithmetic by twoview_refill_kernel).
 // one tile (64 pixels of a row; LISTED: 64 listed pixels) of twoview_scan_kernel; `bid` = its index in the band
-template <bool CERT, bool LISTED>
+// WTA (option "wta_outputs"): winner and runner-up into wout (wta_store, srh_internal.hpp) wherever the depth is written; a
+// flagged pixel's pairs are written again by its exact scan, as its depth is
+template <bool CERT, bool LISTED, bool WTA>
 __device__ __forceinline__
 void twoview_scan_tile(const int bid, const ViewDev *__restrict__ views, int ref, int oth, const srh_params &P,
                        int y0, int nrows, const double *__restrict__ tnum,
                        const double *__restrict__ cost, int cstride,
                        Counters *__restrict__ cnt, const PixRange *__restrict__ prange,
-                       uint32_t *__restrict__ cflag, int nlist, const CertBound &cb, const double *__restrict__ pexact)
+                       uint32_t *__restrict__ cflag, int nlist, const CertBound &cb, const double *__restrict__ pexact,
+                       int32_t *__restrict__ wout)
 {
 	const ViewDev &L = views[ref];
 	const ViewDev &Rv = views[oth];
@@ -1699,10 +1703,11 @@ void twoview_scan_tile(const int bid, const ViewDev *__restrict__ views, int ref
 	__syncthreads();
 
 	double depth = __builtin_nan("");
+	int owin = -1, orun = -1;                                  // WTA: winner / runner-up columns of row y, -1 = none
 	if (active) {
 		n_pix = 1;
 		const double *crow = cost + ((size_t)trow*((W + DC_TP - 1)/DC_TP) + (x/DC_TP))*(size_t)cstride*DC_TP + (x % DC_TP);
-		TwoViewScanState st = { __builtin_inf(), __builtin_inf(), -1 };
+		TwoViewScanState st = { __builtin_inf(), __builtin_inf(), -1, -1 };
 		int qn = 0;
 		// pexact (the band's per-pixel constants, given when the cost kernel redoes uncovered candidates in place): a pixel the
 		// cost kernel evaluated in the reference's arithmetic throughout (cert_pixel_exact) -- every stored cost is the
@@ -1740,6 +1745,7 @@ void twoview_scan_tile(const int bid, const ViewDev *__restrict__ views, int ref
 					if (cv + P.wta_margin < st.minCost) {           // twoviewstereo.cpp:293-301
 						st.secondBest = st.minCost;
 						st.minCost = cv;
+						if (WTA) st.pcol = st.wcol;
 						st.wcol = col[k];
 					}
 				}
@@ -1816,8 +1822,10 @@ void twoview_scan_tile(const int bid, const ViewDev *__restrict__ views, int ref
 			    !(cert_sure(st.minCost, P.max_color_diff, cb.m_hi) && cert_sure(st.secondBest, P.max_color_diff, cb.m_hi))) n_flag = 1;
 		}
 		if (CERT && n_flag) cflag[1 + atomicAdd(&cflag[0], 1u)] = (uint32_t)((size_t)trow*W + x);
+		if (WTA) { owin = st.wcol >= 0 ? lo + st.wcol : -1; orun = st.pcol >= 0 ? lo + st.pcol : -1; }
 	}
 	if (listed_on && x < W) L.depth[(size_t)y*W + x] = depth;
+	if (WTA && listed_on && x < W) wta_store(wout, (size_t)W*L.h, (size_t)y*W + x, owin, owin >= 0 ? y : -1, orun, orun >= 0 ? y : -1);
 	if (LISTED || !cnt) return;                        // (the pixels were counted by the certified scan)
 	// the tile is one wave: its counts are summed by lane shuffles, one atomic each
 	n_eval = wave_sum_u32(n_eval); n_pix = wave_sum_u32(n_pix); bad = wave_sum_u32(bad); n_flag = wave_sum_u32(n_flag);
@@ -1833,22 +1841,23 @@ void twoview_scan_tile(const int bid, const ViewDev *__restrict__ views, int ref
 // tilelist == nullptr: one workgroup per tile of the band (LISTED: per 64 listed pixels).  tilelist = [count | tile
 // indices]: behind twoview_tscan_kernel, only the tiles it left (a pixel whose curve is not certainly the template's),
 // shared by the launch's workgroups in a grid-stride loop; the count is read on the device.
-template <bool CERT, bool LISTED>
-__global__ __launch_bounds__(SC_TW, CERT ? SC_OCC - 1 : SC_OCC)
+// (WTA: one wave per SIMD fewer than the kernel's own bound, so that the two more values a lane carries cost no scratch)
+template <bool CERT, bool LISTED, bool WTA>
+__global__ __launch_bounds__(SC_TW, (CERT ? SC_OCC - 1 : SC_OCC) - (WTA ? 1 : 0))
 void twoview_scan_kernel(const ViewDev *__restrict__ views, int ref, int oth, srh_params P,
                          int y0, int nrows, const double *__restrict__ tnum,
                          const double *__restrict__ cost, int cstride,
                          Counters *__restrict__ cnt, const PixRange *__restrict__ prange,
                          uint32_t *__restrict__ cflag, int nlist, CertBound cb, const double *__restrict__ pexact,
-                         const uint32_t *__restrict__ tilelist)
+                         const uint32_t *__restrict__ tilelist, int32_t *__restrict__ wout)
 {
 	if (LISTED || !tilelist) {
-		twoview_scan_tile<CERT, LISTED>((int)blockIdx.x, views, ref, oth, P, y0, nrows, tnum, cost, cstride, cnt, prange, cflag, nlist, cb, pexact);
+		twoview_scan_tile<CERT, LISTED, WTA>((int)blockIdx.x, views, ref, oth, P, y0, nrows, tnum, cost, cstride, cnt, prange, cflag, nlist, cb, pexact, wout);
 		return;
 	}
 	const uint32_t n = tilelist[0];
 	for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
-		twoview_scan_tile<CERT, LISTED>((int)tilelist[1 + i], views, ref, oth, P, y0, nrows, tnum, cost, cstride, cnt, prange, cflag, nlist, cb, pexact);
+		twoview_scan_tile<CERT, LISTED, WTA>((int)tilelist[1 + i], views, ref, oth, P, y0, nrows, tnum, cost, cstride, cnt, prange, cflag, nlist, cb, pexact, wout);
 		__syncthreads();                                              // (the tile's LDS is reused)
 	}
 }
@@ -2025,14 +2034,15 @@ void twoview_template_kernel(const ViewDev *__restrict__ views, int ref, int oth
 
 #define TS_U 8                         // look-ups in flight per lane
 // one tile; returns false when the tile is left to twoview_scan_kernel
-template <bool CERT>
+template <bool CERT, bool WTA>
 __device__ __forceinline__
 bool twoview_tscan_tile(const int bid, const ViewDev *__restrict__ views, int ref, int oth, const srh_params &P,
                         int y0, int nrows, const double *__restrict__ tnum,
                         const double *__restrict__ cost, int cstride,
                         Counters *__restrict__ cnt, const PixRange *__restrict__ prange,
                         uint32_t *__restrict__ cflag, const CertBound &cb, const double *__restrict__ pexact,
-                        const ScanTemplate *__restrict__ tpl, unsigned char *smask, unsigned &n_eval_acc, unsigned &n_pix_acc, unsigned &n_flag_acc)
+                        const ScanTemplate *__restrict__ tpl, unsigned char *smask, unsigned &n_eval_acc, unsigned &n_pix_acc, unsigned &n_flag_acc,
+                        int32_t *__restrict__ wout)
 {
 	const ViewDev &L = views[ref];
 	const ViewDev &Rv = views[oth];
@@ -2149,11 +2159,12 @@ bool twoview_tscan_tile(const int bid, const ViewDev *__restrict__ views, int re
 
 	unsigned n_eval = 0, n_flag = 0;
 	double depth = __builtin_nan("");
+	int owin = -1, orun = -1;
 	if (active) {
 		n_pix_acc += 1;
 		const double *crow = cost + ((size_t)trow*((W + DC_TP - 1)/DC_TP) + (x/DC_TP))*(size_t)cstride*DC_TP + (x % DC_TP);
 		double minCost = __builtin_inf(), secondBest = __builtin_inf();
-		int wcol = -1;
+		int wcol = -1, pcol = -1;                                      // (pcol, WTA: who held minCost before the last improvement)
 		bool px_sure = false;
 		if (CERT && pexact) { const double *pc = pexact + ((size_t)trow*W + x)*SRH_PC; px_sure = cert_pixel_exact(cb, pc[2], pc[3]); }
 		const int xm = tid - smin;                                     // smask index of column x + s: tid + (s - smin)
@@ -2216,7 +2227,7 @@ bool twoview_tscan_tile(const int bid, const ViewDev *__restrict__ views, int re
 							    !(px_sure && cv == cv)) n_flag = 1;
 						}
 					}
-					if (t < minCost) { secondBest = minCost; minCost = cv; wcol = kk[u]; }   // twoviewstereo.cpp:293-301
+					if (t < minCost) { secondBest = minCost; minCost = cv; if (WTA) pcol = wcol; wcol = kk[u]; }   // twoviewstereo.cpp:293-301
 				}
 			}
 		};
@@ -2232,8 +2243,10 @@ bool twoview_tscan_tile(const int bid, const ViewDev *__restrict__ views, int re
 			    !(cert_sure(minCost, P.max_color_diff, cb.m_hi) && cert_sure(secondBest, P.max_color_diff, cb.m_hi))) n_flag = 1;
 		}
 		if (CERT && n_flag) cflag[1 + atomicAdd(&cflag[0], 1u)] = (uint32_t)((size_t)trow*W + x);
+		if (WTA) { owin = wcol >= 0 ? lo + wcol : -1; orun = pcol >= 0 ? lo + pcol : -1; }
 	}
 	if (x < W) L.depth[(size_t)y*W + x] = depth;
+	if (WTA && x < W) wta_store(wout, (size_t)W*L.h, (size_t)y*W + x, owin, owin >= 0 ? y : -1, orun, orun >= 0 ? y : -1);
 	n_eval_acc += n_eval; n_flag_acc += n_flag;
 	return true;
 }
@@ -2242,14 +2255,14 @@ bool twoview_tscan_tile(const int bid, const ViewDev *__restrict__ views, int re
 // 32 400 of them on C3 -- costs 0.8 ms of workgroup launches whatever the tiles do: the fixed part of twoview_scan_kernel);
 // the counters travel in registers and are added once per workgroup.  A tile that does not verify goes on `tilelist`
 // = [count | tile indices] for twoview_scan_kernel.
-template <bool CERT>
+template <bool CERT, bool WTA>
 __global__ __launch_bounds__(SC_TW, 4)
 void twoview_tscan_kernel(const ViewDev *__restrict__ views, int ref, int oth, srh_params P,
                           int y0, int nrows, const double *__restrict__ tnum,
                           const double *__restrict__ cost, int cstride,
                           Counters *__restrict__ cnt, const PixRange *__restrict__ prange,
                           uint32_t *__restrict__ cflag, CertBound cb, const double *__restrict__ pexact,
-                          const ScanTemplate *__restrict__ tpl, uint32_t *__restrict__ tilelist)
+                          const ScanTemplate *__restrict__ tpl, uint32_t *__restrict__ tilelist, int32_t *__restrict__ wout)
 {
 	__shared__ unsigned char smask[SC_TW + TS_MAXSPAN + 16];
 	const int W = views[ref].w;
@@ -2258,8 +2271,8 @@ void twoview_tscan_kernel(const ViewDev *__restrict__ views, int ref, int oth, s
 	const bool tok = tpl->ok != 0;
 	unsigned n_eval = 0, n_pix = 0, n_flag = 0, n_tpl = 0, n_walk = 0;
 	for (int bid = blockIdx.x; bid < ntiles; bid += gridDim.x) {
-		const bool done = tok && twoview_tscan_tile<CERT>(bid, views, ref, oth, P, y0, nrows, tnum, cost, cstride, cnt, prange, cflag, cb, pexact,
-		                                                 tpl, smask, n_eval, n_pix, n_flag);
+		const bool done = tok && twoview_tscan_tile<CERT, WTA>(bid, views, ref, oth, P, y0, nrows, tnum, cost, cstride, cnt, prange, cflag, cb, pexact,
+		                                                      tpl, smask, n_eval, n_pix, n_flag, wout);
 		if (!done) { if (tid == 0) tilelist[1 + atomicAdd(&tilelist[0], 1u)] = (uint32_t)bid; ++n_walk; } else ++n_tpl;
 		__syncthreads();                                              // (smask is reused)
 	}
@@ -2284,11 +2297,12 @@ void twoview_tscan_kernel(const ViewDev *__restrict__ views, int ref, int oth, s
 // (twoviewstereo.cpp:293-305) over them.  Same functions, same order, same bits as the one-lane form.
 #define RSW_MAXD 1024                  // labels (else: the one-lane form)
 #define RSW_MAXC 6144                  // candidates of a pixel (more: Counters::cert_overflow, the pass is repeated in mode 0)
+template <bool WTA>
 __global__ __launch_bounds__(64)
 void twoview_rescan_wave_kernel(const ViewDev *__restrict__ views, int ref, int oth, srh_params P, int y0,
                                 const double *__restrict__ tnum, const double *__restrict__ cost, int cstride,
                                 const PixRange *__restrict__ prange, const uint32_t *__restrict__ cflag, int cap,
-                                Counters *__restrict__ cnt)
+                                Counters *__restrict__ cnt, int32_t *__restrict__ wout)
 {
 	const ViewDev &L = views[ref];
 	const ViewDev &Rv = views[oth];
@@ -2372,15 +2386,17 @@ void twoview_rescan_wave_kernel(const ViewDev *__restrict__ views, int ref, int 
 		// (5) running minimum, ratio test, depth of the winner
 		if (lane == 0) {
 			double minCost = __builtin_inf(), secondBest = __builtin_inf();
-			int wcol = -1;
+			int wcol = -1, pcol = -1;
 			for (int k = 0; k < n; ++k) {
 				const double cv = scost[k];
-				if (cv + P.wta_margin < minCost) { secondBest = minCost; minCost = cv; wcol = scol[k]; }   // twoviewstereo.cpp:293-301
+				if (cv + P.wta_margin < minCost) { secondBest = minCost; minCost = cv; if (WTA) pcol = wcol; wcol = scol[k]; }   // twoviewstereo.cpp:293-301
 			}
 			double depth = __builtin_nan("");
 			if (wcol >= 0) depth = candidate_depth(L.cam, Rv.cam, P, ray, lo + wcol, y);
 			if (minCost > P.second_best_factor*secondBest) depth = __builtin_inf();
 			L.depth[(size_t)y*W + x] = depth;
+			if (WTA) wta_store(wout, (size_t)W*L.h, (size_t)y*W + x, wcol >= 0 ? lo + wcol : -1, wcol >= 0 ? y : -1,
+			                   pcol >= 0 ? lo + pcol : -1, pcol >= 0 ? y : -1);
 		}
 		__syncthreads();
 	}
@@ -2397,7 +2413,7 @@ void launch_scan_template(hipStream_t st, const ViewDev *views, int ref, int oth
 void launch_twoview_scan(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P,
                          int y0, int nrows, const double *tnum, const double *cost, int cstride,
                          Counters *cnt, const PixRange *prange, uint32_t *cflag, int nlist, const double *pexact,
-                         const void *tpl, uint32_t *tilelist, int num_cus)
+                         const void *tpl, uint32_t *tilelist, int num_cus, int32_t *wout)
 {
 	const int tiles = (width + SC_TW - 1)/SC_TW;
 	const CertBound cb = cert_bound(P);
@@ -2407,23 +2423,35 @@ void launch_twoview_scan(hipStream_t st, const ViewDev *views, int ref, int oth,
 	const unsigned pgrid = (unsigned)std::min<long long>((long long)tiles*nrows, (long long)num_cus*4*8);
 	const unsigned wgrid = tp ? (unsigned)std::min<long long>((long long)tiles*nrows, (long long)num_cus*4*4) : (unsigned)(tiles*nrows);
 	if (tp) (void)hipMemsetAsync(tilelist, 0, sizeof(uint32_t), st);
+	// (wout: the WTA = true instantiations, option "wta_outputs"; without it the kernels as they were)
+#define SRH_TSCAN(C_, W_, FLAG_, PEX_)                                                                         \
+	hipLaunchKernelGGL((twoview_tscan_kernel<C_, W_>), dim3(pgrid), dim3(SC_TW), 0, st,                        \
+	                   views, ref, oth, P, y0, nrows, tnum, cost, cstride, cnt, prange, FLAG_, cb, PEX_, tp, tilelist, wout)
+#define SRH_SCAN(C_, L_, W_, GRID_, FLAG_, NL_, PEX_, TL_)                                                     \
+	hipLaunchKernelGGL((twoview_scan_kernel<C_, L_, W_>), dim3(GRID_), dim3(SC_TW), 0, st,                     \
+	                   views, ref, oth, P, y0, nrows, tnum, cost, cstride, cnt, prange, FLAG_, NL_, cb, PEX_, TL_, wout)
 	if (!cflag) {
-		if (tp) hipLaunchKernelGGL((twoview_tscan_kernel<false>), dim3(pgrid), dim3(SC_TW), 0, st,
-		                           views, ref, oth, P, y0, nrows, tnum, cost, cstride, cnt, prange, nullptr, cb, nullptr, tp, tilelist);
-		hipLaunchKernelGGL((twoview_scan_kernel<false, false>), dim3(wgrid), dim3(SC_TW), 0, st,
-		                   views, ref, oth, P, y0, nrows, tnum, cost, cstride, cnt, prange, nullptr, 0, cb, nullptr, tilelist);
+		if (tp) { if (wout) SRH_TSCAN(false, true, nullptr, nullptr); else SRH_TSCAN(false, false, nullptr, nullptr); }
+		if (wout) SRH_SCAN(false, false, true, wgrid, nullptr, 0, nullptr, tilelist);
+		else      SRH_SCAN(false, false, false, wgrid, nullptr, 0, nullptr, tilelist);
 	} else if (nlist < 0) {
-		if (tp) hipLaunchKernelGGL((twoview_tscan_kernel<true>), dim3(pgrid), dim3(SC_TW), 0, st,
-		                           views, ref, oth, P, y0, nrows, tnum, cost, cstride, cnt, prange, cflag, cb, pexact, tp, tilelist);
-		hipLaunchKernelGGL((twoview_scan_kernel<true, false>), dim3(wgrid), dim3(SC_TW), 0, st,
-		                   views, ref, oth, P, y0, nrows, tnum, cost, cstride, cnt, prange, cflag, 0, cb, pexact, tilelist);
-	} else if (nlist > 0 && P.num_depth_levels <= RSW_MAXD && cstride <= 4096)
+		if (tp) { if (wout) SRH_TSCAN(true, true, cflag, pexact); else SRH_TSCAN(true, false, cflag, pexact); }
+		if (wout) SRH_SCAN(true, false, true, wgrid, cflag, 0, pexact, tilelist);
+		else      SRH_SCAN(true, false, false, wgrid, cflag, 0, pexact, tilelist);
+	} else if (nlist > 0 && P.num_depth_levels <= RSW_MAXD && cstride <= 4096) {
 		// (the list may hold up to the band's pixels: workgroups share it in a grid-stride loop, the count is read on the device)
-		hipLaunchKernelGGL(twoview_rescan_wave_kernel, dim3((unsigned)(nlist < 2048 ? nlist : 2048)), dim3(64), 0, st,
-		                   views, ref, oth, P, y0, tnum, cost, cstride, prange, cflag, nlist, cnt);
-	else if (nlist > 0)
-		hipLaunchKernelGGL((twoview_scan_kernel<false, true>), dim3((unsigned)((nlist + SC_TW - 1)/SC_TW)), dim3(SC_TW), 0, st,
-		                   views, ref, oth, P, y0, nrows, tnum, cost, cstride, cnt, prange, cflag, nlist, cb, nullptr, nullptr);
+		const dim3 rgrid((unsigned)(nlist < 2048 ? nlist : 2048));
+		if (wout) hipLaunchKernelGGL(twoview_rescan_wave_kernel<true>, rgrid, dim3(64), 0, st,
+		                             views, ref, oth, P, y0, tnum, cost, cstride, prange, cflag, nlist, cnt, wout);
+		else      hipLaunchKernelGGL(twoview_rescan_wave_kernel<false>, rgrid, dim3(64), 0, st,
+		                             views, ref, oth, P, y0, tnum, cost, cstride, prange, cflag, nlist, cnt, wout);
+	} else if (nlist > 0) {
+		const unsigned lgrid = (unsigned)((nlist + SC_TW - 1)/SC_TW);
+		if (wout) SRH_SCAN(false, true, true, lgrid, cflag, nlist, nullptr, nullptr);
+		else      SRH_SCAN(false, true, false, lgrid, cflag, nlist, nullptr, nullptr);
+	}
+#undef SRH_TSCAN
+#undef SRH_SCAN
 }
 
 } // namespace srh

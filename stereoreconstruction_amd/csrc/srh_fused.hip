@@ -124,11 +124,14 @@ __device__ __forceinline__ int next_joint(const unsigned *J, int from) {
 	}
 }
 
-template <int R, int MAXC>
+// WTA (option "wta_outputs"): winner and runner-up into wout (wta_store, srh_internal.hpp).  The lanes' parallel running
+// minimum knows the winner but not who held the minimum before it, so such a launch takes every pixel through the
+// sequential replay of phase F, which does.
+template <int R, int MAXC, bool WTA>
 __global__ __launch_bounds__(FZ_THREADS, 2)
 void twoview_fused_kernel(const ViewDev *__restrict__ views, int ref, int oth, srh_params P,
                           int y0, int nrows, const double *__restrict__ wbuf, const double *__restrict__ tnum,
-                          Counters *__restrict__ cnt)
+                          Counters *__restrict__ cnt, int32_t *__restrict__ wout)
 {
 	typedef FusedSmem<R, MAXC> Smem;
 	constexpr int WS = Smem::WS, T = Smem::T, WP = Smem::WP;
@@ -711,10 +714,11 @@ void twoview_fused_kernel(const ViewDev *__restrict__ views, int ref, int oth, s
 	const bool owner = wc != -2147483647 && Pm == gmin;
 	if (owner || (t == 0 && !(gmin < inf))) {
 		double depth = nan;                                       // twoviewstereo.cpp:269
+		int ocol = -2147483647, rcol = -2147483647;
 		if (active) {
 			double minCost = owner ? Pm : inf, secondBest = owner ? sec : inf;
 			int wcol = wc;
-			if (pix && ambs) {
+			if (pix && (ambs || WTA)) {
 				// replay with the reference's margin rule, sequentially (rare: two costs within 1e-10 of each other)
 				const int ilast = S.ilast[p], K0 = S.k0[p], dirp = S.dir[p], ca = S.ca[p], cb = S.cb[p], corg = S.corg[p];
 				minCost = inf; secondBest = inf; wcol = -2147483647;
@@ -722,7 +726,7 @@ void twoview_fused_kernel(const ViewDev *__restrict__ views, int ref, int oth, s
 					if (c < ca || c > cb) return;
 					if (S.mrow[c - cmin] != 1) return;
 					const double cv = S.cost[Smem::slot(p, c - corg)];
-					if (cv + P.wta_margin < minCost) { secondBest = minCost; minCost = cv; wcol = c; }   // twoviewstereo.cpp:293-301
+					if (cv + P.wta_margin < minCost) { secondBest = minCost; minCost = cv; if (WTA) rcol = wcol; wcol = c; }   // twoviewstereo.cpp:293-301
 				};
 				if (dirp > 0) {
 					for (int i = 0; i <= ilast; ++i) visit(K0 + i);
@@ -741,8 +745,11 @@ void twoview_fused_kernel(const ViewDev *__restrict__ views, int ref, int oth, s
 				depth = candidate_depth(L.cam, Rv.cam, P, ray, wcol, y);
 			}
 			if (minCost > P.second_best_factor*secondBest) depth = inf;   // twoviewstereo.cpp:304-305
+			ocol = wcol;
 		}
 		if (x < W) L.depth[(size_t)y*W + x] = depth;
+		if (WTA && x < W) wta_store(wout, (size_t)W*L.h, (size_t)y*W + x, ocol == -2147483647 ? -1 : ocol, ocol == -2147483647 ? -1 : y,
+		                            rcol == -2147483647 ? -1 : rcol, rcol == -2147483647 ? -1 : y);
 	}
 	if (t == 0 && active) ++n_pix;
 	if (tid == 0 && S.bad) atomicAdd(&cnt->not_row_aligned, 1ull);
@@ -765,7 +772,7 @@ void twoview_fused_kernel(const ViewDev *__restrict__ views, int ref, int oth, s
 }
 
 bool launch_twoview_fused(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P,
-                          int y0, int nrows, const double *wbuf, const double *tnum, Counters *cnt)
+                          int y0, int nrows, const double *wbuf, const double *tnum, Counters *cnt, int32_t *wout)
 {
 	const int tiles = (width + FZ_TP - 1)/FZ_TP;
 	const dim3 grid((unsigned)(tiles*nrows));
@@ -773,15 +780,22 @@ bool launch_twoview_fused(hipStream_t st, const ViewDev *views, int ref, int oth
 	{                                                                                                        \
 		typedef FusedSmem<RR, MC> Smem;                                                                      \
 		/* per device, hence on every launch */                                                              \
-		(void)hipFuncSetAttribute((const void *)twoview_fused_kernel<RR, MC>,                                \
+		if (wout) {                                                                                          \
+			(void)hipFuncSetAttribute((const void *)twoview_fused_kernel<RR, MC, true>,                      \
+			                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Smem));       \
+			hipLaunchKernelGGL((twoview_fused_kernel<RR, MC, true>), grid, dim3(FZ_THREADS), sizeof(Smem), st, \
+			                   views, ref, oth, P, y0, nrows, wbuf, tnum, cnt, wout);                        \
+			return true;                                                                                     \
+		}                                                                                                    \
+		(void)hipFuncSetAttribute((const void *)twoview_fused_kernel<RR, MC, false>,                         \
 		                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Smem));           \
-		hipLaunchKernelGGL((twoview_fused_kernel<RR, MC>), grid, dim3(FZ_THREADS), sizeof(Smem), st,         \
-		                   views, ref, oth, P, y0, nrows, wbuf, tnum, cnt);                                  \
+		hipLaunchKernelGGL((twoview_fused_kernel<RR, MC, false>), grid, dim3(FZ_THREADS), sizeof(Smem), st,  \
+		                   views, ref, oth, P, y0, nrows, wbuf, tnum, cnt, wout);                            \
 		return true;                                                                                         \
 	}
 #ifdef SRH_PROFILE_PHASES
 	{ static bool once = false; if (!once) { once = true; int nb = 0;
-	  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)twoview_fused_kernel<5, SRH_FUSED_MAXC>, FZ_THREADS, sizeof(FusedSmem<5, SRH_FUSED_MAXC>));
+	  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)twoview_fused_kernel<5, SRH_FUSED_MAXC, false>, FZ_THREADS, sizeof(FusedSmem<5, SRH_FUSED_MAXC>));
 	  fprintf(stderr, "[srh dbg] fused<5>: %zu bytes of LDS, %d workgroups per CU\n", sizeof(FusedSmem<5, SRH_FUSED_MAXC>), nb); } }
 #endif
 	if (P.num_depth_levels > SRH_FUSED_MAXC) return false;        // the label projections share the cost rows' LDS

@@ -165,6 +165,24 @@ inline CertBound cert_bound(const srh_params &P, bool mvs = false) {
 	return c;
 }
 
+// ---- by-products of the winner-take-all scan (option "wta_outputs") ------------------------------------------
+// Two int32 pairs per pixel of the reference view, planes back to back in one allocation: win_xy[npix][2] -- the candidate
+// pixel of the other view that held minCost at the end of the scan -- then runner_xy[npix][2] -- the one that held it
+// immediately before the last improvement (its cost is secondBest); (-1, -1) = none.  Every scan kernel takes the planes as
+// `wout` (nullptr: the WTA = false instantiation, the code the kernels had before) and writes a pixel's pairs where it
+// writes the pixel's depth.
+#ifdef __HIPCC__
+__device__ __forceinline__ void wta_store(int32_t *__restrict__ wout, size_t npix, size_t pv, int wx, int wy, int rx, int ry) {
+	*reinterpret_cast<int2 *>(wout + 2*pv) = make_int2(wx, wy);
+	*reinterpret_cast<int2 *>(wout + 2*(npix + pv)) = make_int2(rx, ry);
+}
+#endif
+// exact costs of the two pairs (srh_wta_out.hip): min_cost[npix] and second_cost[npix] of rows [y0, y0 + nrows), in the
+// reference's arithmetic (tv_cost / tv_cost_sad: the bits of pair_costs_kernel), from the band's window buffer in either layout
+void launch_twoview_winner_costs(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P, bool sad,
+                                 int y0, int nrows, const double *wbuf, bool wimg, const int32_t *wout,
+                                 double *min_cost, double *second_cost);
+
 // Work counters accumulated by the kernels (device memory, zeroed per run).
 struct Counters {
 	unsigned long long n_pixels;
@@ -210,7 +228,8 @@ void launch_fill(hipStream_t st, double *p, size_t n, double v);
 void launch_weights(hipStream_t st, const ViewDev *views, int ref, int width, const srh_params &P,
                     int y0, int nrows, double *wbuf, size_t wstride, double *pconst = nullptr, bool wimg = false);
 void launch_twoview_generic(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P,
-                            int y0, int nrows, const double *wbuf, size_t wstride, Counters *cnt, bool sad = false);
+                            int y0, int nrows, const double *wbuf, size_t wstride, Counters *cnt, bool sad = false,
+                            int32_t *wout = nullptr);
 void launch_twoview_cross_check(hipStream_t st, const ViewDev *views, int self, int other, int w, int h,
                                 const srh_params &P);
 void launch_mvs_generic(hipStream_t st, const ViewDev *views, int ref, const int32_t *neigh, int nneigh, int width,
@@ -249,7 +268,7 @@ void launch_twoview_scan(hipStream_t st, const ViewDev *views, int ref, int oth,
                          Counters *cnt, const PixRange *prange, uint32_t *cflag = nullptr, int nlist = -1,
                          const double *pexact = nullptr,    // certified scan: the band's pconst when the cost kernel applies cert_pixel_exact
                          const void *tpl = nullptr, uint32_t *tilelist = nullptr,   // template scan (launch_scan_template) + the tiles it leaves: [count | tile indices]
-                         int num_cus = 256);
+                         int num_cus = 256, int32_t *wout = nullptr);
 // the pass's candidate template (twoview_template_kernel) into `tpl` (scan_template_bytes() bytes)
 size_t scan_template_bytes();
 void launch_scan_template(hipStream_t st, const ViewDev *views, int ref, int oth, const srh_params &P, int y0, int nrows,
@@ -293,7 +312,7 @@ void exp_set_rows(int mode);
 // SRH_FUSED_MAXC: cost-row columns (and labels) a pixel may have in LDS.
 #define SRH_FUSED_MAXC 256
 bool launch_twoview_fused(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P,
-                          int y0, int nrows, const double *wbuf, const double *tnum, Counters *cnt);
+                          int y0, int nrows, const double *wbuf, const double *tnum, Counters *cnt, int32_t *wout = nullptr);
 
 // Candidate-list TwoView path for arbitrary geometry, srh_list.hip
 void launch_twoview_count(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P,
@@ -307,7 +326,8 @@ bool launch_twoview_list_cost(hipStream_t st, const ViewDev *views, int ref, int
                               int y0, int nrows, const double *wbuf, const uint8_t *full_oth,
                               const int32_t *count, const uint32_t *cand, double *cost, int cmax, Counters *cnt);
 void launch_twoview_list_scan(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P,
-                              int y0, int nrows, const int32_t *count, const uint32_t *cand, const double *cost, int cmax);
+                              int y0, int nrows, const int32_t *count, const uint32_t *cand, const double *cost, int cmax,
+                              int32_t *wout = nullptr);
 // act / nact: the band's masked-in pixels (y*w + x) in the view's serpentine order -- the units of the launch, 128 per
 // block and link, so that every wave is full and its 64 pixels lie side by side (also across a row change).
 // wdesc / nwin (or null): per wave of the walk launch (2 per 128-pixel block and link), the windows of list slots whose
@@ -417,7 +437,7 @@ bool launch_twoview_rows_cost(hipStream_t st, const ViewDev *views, int ref, int
 void launch_twoview_rows_scan(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P,
                               int y0, int nrows, const int32_t *count, const uint32_t *cand, int cmax,
                               const uint32_t *rowinfo, const int32_t *meta, const double *cost, int smax,
-                              uint32_t *cflag = nullptr, int nlist = -1, Counters *cnt = nullptr);
+                              uint32_t *cflag = nullptr, int nlist = -1, Counters *cnt = nullptr, int32_t *wout = nullptr);
 bool launch_twoview_rows_refill(hipStream_t st, int width, int oth_width, const srh_params &P, int y0,
                                 const uint32_t *cflag, int cap, const double *wbuf, const double *ref_tvp, const double *oth_tvp,
                                 const uint32_t *rowinfo, const int32_t *meta, double *cost, int smax, Counters *cnt);

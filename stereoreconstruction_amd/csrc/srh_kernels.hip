@@ -122,7 +122,8 @@ void launch_weights(hipStream_t st, const ViewDev *views, int ref, int width, co
 }
 
 // ------------------------------------------------------------------ TwoView, general geometry
-template <bool SAD>
+// WTA (option "wta_outputs"): the candidate that held minCost before the last improvement travels along (px, py)
+template <bool SAD, bool WTA>
 struct TwoViewDirectVisitor {
 	const ViewDev &L, &Rv;
 	const double *wq;
@@ -132,22 +133,24 @@ struct TwoViewDirectVisitor {
 	double minCost, secondBest;
 	int wx, wy;
 	unsigned n;
+	int px, py;
 	__device__ __forceinline__ void operator()(int cx, int cy) {
 		const double cost = SAD ? tv_cost_sad(L, Rv, wq, wstride, P, x, y, cx, cy) : tv_cost(L, Rv, wq, wstride, P, x, y, cx, cy);
 		++n;
 		if (cost + P.wta_margin < minCost) {                   // twoviewstereo.cpp:293-301
 			secondBest = minCost;
 			minCost = cost;
+			if (WTA) { px = wx; py = wy; }
 			wx = cx; wy = cy;
 		}
 	}
 };
 
-// SAD: the cost is cost_sad (option "cost" = SRH_COST_SAD), else cost_ncc
-template <bool SAD>
+// SAD: the cost is cost_sad (option "cost" = SRH_COST_SAD), else cost_ncc; WTA: winner and runner-up into wout (wta_store)
+template <bool SAD, bool WTA>
 __global__ void twoview_generic_kernel(const ViewDev *__restrict__ views, int ref, int oth, srh_params P,
                                        int y0, int nrows, const double *__restrict__ wbuf, size_t wstride,
-                                       Counters *__restrict__ cnt)
+                                       Counters *__restrict__ cnt, int32_t *__restrict__ wout)
 {
 	const ViewDev &L = views[ref];
 	const ViewDev &Rv = views[oth];
@@ -158,20 +161,23 @@ __global__ void twoview_generic_kernel(const ViewDev *__restrict__ views, int re
 		const int x = (int)(q % W), y = y0 + (int)(q / W);
 		const size_t pv = (size_t)y*W + x;
 		double depth = __builtin_nan("");                       // twoviewstereo.cpp:269
+		int ox = -1, oy = -1, rx = -1, ry = -1;
 		if (L.mask[pv] == 1) {
 			n_pix = 1;
 			const Ray ray = cam_unproject(L.cam, (x + 0.5) / P.image_scale, (y + 0.5) / P.image_scale);
 			const int T = (2*P.window_radius + 1)*(2*P.window_radius + 1);
-			TwoViewDirectVisitor<SAD> vis = { L, Rv, wbuf + wbuf_offset(W, T, (int)(q / W), x), wstride, P, x, y,
-			                             __builtin_inf(), __builtin_inf(), -1, -1, 0 };
+			TwoViewDirectVisitor<SAD, WTA> vis = { L, Rv, wbuf + wbuf_offset(W, T, (int)(q / W), x), wstride, P, x, y,
+			                             __builtin_inf(), __builtin_inf(), -1, -1, 0, -1, -1 };
 			walk_curve<false>(ray, L.cam, Rv, P, vis);
 			n_eval = vis.n;
+			if (WTA) { ox = vis.wx; oy = vis.wy; rx = vis.px; ry = vis.py; }
 			if (vis.wx >= 0)                                       // at least one candidate was scanned
 				depth = candidate_depth(L.cam, Rv.cam, P, ray, vis.wx, vis.wy);
 			if (vis.minCost > P.second_best_factor*vis.secondBest)   // twoviewstereo.cpp:304-305
 				depth = __builtin_inf();
 		}
 		L.depth[pv] = depth;
+		if (WTA) wta_store(wout, (size_t)W*L.h, pv, ox, oy, rx, ry);
 	}
 	block_count_add(&cnt->n_eval, n_eval);
 	block_count_add(&cnt->n_eval_device, n_eval);
@@ -179,15 +185,14 @@ __global__ void twoview_generic_kernel(const ViewDev *__restrict__ views, int re
 }
 
 void launch_twoview_generic(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P,
-                            int y0, int nrows, const double *wbuf, size_t wstride, Counters *cnt, bool sad)
+                            int y0, int nrows, const double *wbuf, size_t wstride, Counters *cnt, bool sad, int32_t *wout)
 {
 	const size_t n = (size_t)nrows*width;
-	if (sad)
-		hipLaunchKernelGGL(twoview_generic_kernel<true>, dim3((unsigned)((n + 127)/128)), dim3(128), 0, st,
-		                   views, ref, oth, P, y0, nrows, wbuf, wstride, cnt);
-	else
-		hipLaunchKernelGGL(twoview_generic_kernel<false>, dim3((unsigned)((n + 127)/128)), dim3(128), 0, st,
-		                   views, ref, oth, P, y0, nrows, wbuf, wstride, cnt);
+	const dim3 grid((unsigned)((n + 127)/128)), block(128);
+#define SRH_GEN_LAUNCH(S_, W_) hipLaunchKernelGGL((twoview_generic_kernel<S_, W_>), grid, block, 0, st, views, ref, oth, P, y0, nrows, wbuf, wstride, cnt, wout)
+	if (sad) { if (wout) SRH_GEN_LAUNCH(true, true); else SRH_GEN_LAUNCH(true, false); }
+	else     { if (wout) SRH_GEN_LAUNCH(false, true); else SRH_GEN_LAUNCH(false, false); }
+#undef SRH_GEN_LAUNCH
 }
 
 // one direction of TwoViewStereo::crossCheck (twoviewstereo.cpp:604-636 / :638-670)

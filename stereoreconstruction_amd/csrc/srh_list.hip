@@ -407,9 +407,12 @@ bool launch_twoview_list_cost(hipStream_t st, const ViewDev *views, int ref, int
 // ------------------------------------------------------------------ list scan
 #define LS_QN 16
 
+// WTA: winner and runner-up into wout (wta_store, srh_internal.hpp)
+template <bool WTA>
 __global__ void twoview_list_scan_kernel(const ViewDev *__restrict__ views, int ref, int oth, srh_params P,
                                          int y0, int nrows, const int32_t *__restrict__ count,
-                                         const uint32_t *__restrict__ cand, const double *__restrict__ cost, int cmax)
+                                         const uint32_t *__restrict__ cand, const double *__restrict__ cost, int cmax,
+                                         int32_t *__restrict__ wout)
 {
 	const ViewDev &L = views[ref];
 	const ViewDev &Rv = views[oth];
@@ -419,6 +422,7 @@ __global__ void twoview_list_scan_kernel(const ViewDev *__restrict__ views, int 
 	const int x = (int)(q % W), y = y0 + (int)(q / W);
 	const size_t pv = (size_t)y*W + x;
 	double depth = __builtin_nan("");
+	uint32_t wwin = 0xffffffffu, wrun = 0xffffffffu;
 	if (L.mask[pv] == 1) {
 		const int n = count[q] < cmax ? count[q] : cmax;
 		const uint32_t *clist = cand + q*(size_t)cmax;
@@ -440,6 +444,7 @@ __global__ void twoview_list_scan_kernel(const ViewDev *__restrict__ views, int 
 					if (c[j] + P.wta_margin < minCost) {               // twoviewstereo.cpp:293-301
 						secondBest = minCost;
 						minCost = c[j];
+						if (WTA) wrun = win;
 						win = e[j];
 					}
 				}
@@ -452,16 +457,24 @@ __global__ void twoview_list_scan_kernel(const ViewDev *__restrict__ views, int 
 		}
 		if (minCost > P.second_best_factor*secondBest)                 // twoviewstereo.cpp:304-305
 			depth = __builtin_inf();
+		wwin = win;
 	}
 	L.depth[pv] = depth;
+	if (WTA) wta_store(wout, (size_t)W*L.h, pv, wwin == 0xffffffffu ? -1 : (int)(wwin & 0xffffu), wwin == 0xffffffffu ? -1 : (int)(wwin >> 16),
+	                   wrun == 0xffffffffu ? -1 : (int)(wrun & 0xffffu), wrun == 0xffffffffu ? -1 : (int)(wrun >> 16));
 }
 
 void launch_twoview_list_scan(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P,
-                              int y0, int nrows, const int32_t *count, const uint32_t *cand, const double *cost, int cmax)
+                              int y0, int nrows, const int32_t *count, const uint32_t *cand, const double *cost, int cmax,
+                              int32_t *wout)
 {
 	const size_t n = (size_t)nrows*width;
-	hipLaunchKernelGGL(twoview_list_scan_kernel, dim3((unsigned)((n + 127)/128)), dim3(128), 0, st,
-	                   views, ref, oth, P, y0, nrows, count, cand, cost, cmax);
+	if (wout)
+		hipLaunchKernelGGL(twoview_list_scan_kernel<true>, dim3((unsigned)((n + 127)/128)), dim3(128), 0, st,
+		                   views, ref, oth, P, y0, nrows, count, cand, cost, cmax, wout);
+	else
+		hipLaunchKernelGGL(twoview_list_scan_kernel<false>, dim3((unsigned)((n + 127)/128)), dim3(128), 0, st,
+		                   views, ref, oth, P, y0, nrows, count, cand, cost, cmax, nullptr);
 }
 
 } // namespace srh

@@ -967,14 +967,15 @@ bool launch_twoview_rows_refill(hipStream_t st, int width, int oth_width, const 
 
 // CERT / LISTED: as twoview_scan_kernel (srh_dense.hip): the certified scan on fused costs flags the pixels with a decision
 // the error bound does not cover; the listed scan is the exact scan of those pixels after twoview_rows_refill_kernel.
-template <bool CERT, bool LISTED>
+// WTA: winner and runner-up into wout (wta_store, srh_internal.hpp); a listed pixel's pairs are written again by its exact scan
+template <bool CERT, bool LISTED, bool WTA>
 __global__ __launch_bounds__(RW_LT)
 void twoview_rows_scan_kernel(const ViewDev *__restrict__ views, int ref, int oth, srh_params P,
                               int y0, int nrows, const int32_t *__restrict__ count,
                               const uint32_t *__restrict__ cand, int cmax,
                               const uint32_t *__restrict__ rowinfo, const int32_t *__restrict__ meta,
                               const double *__restrict__ cost, int smax, uint32_t *__restrict__ cflag, int nlist,
-                              Counters *__restrict__ cnt, const CertBound cb)
+                              Counters *__restrict__ cnt, const CertBound cb, int32_t *__restrict__ wout)
 {
 	const ViewDev &L = views[ref];
 	const ViewDev &Rv = views[oth];
@@ -988,6 +989,7 @@ void twoview_rows_scan_kernel(const ViewDev *__restrict__ views, int ref, int ot
 	const int x = (int)(q % W), y = y0 + (int)(q / W);
 	const size_t pv = (size_t)y*W + x;
 	double depth = __builtin_nan("");
+	uint32_t wwin = 0xffffffffu, wrun = 0xffffffffu;
 	if (L.mask[pv] == 1) {
 		const int m = meta[q];
 		const int ymin = (int)(short)(m & 0xffff), nr = m >> 16;
@@ -1029,10 +1031,12 @@ void twoview_rows_scan_kernel(const ViewDev *__restrict__ views, int ref, int ot
 				if (k0 + j < n && c[j] + P.wta_margin < minCost) {     // twoviewstereo.cpp:293-301
 					secondBest = minCost;
 					minCost = c[j];
+					if (WTA) wrun = win;
 					win = e[j];
 				}
 			}
 		}
+		wwin = win;
 		if (win != 0xffffffffu) {
 			const Ray ray = cam_unproject(L.cam, (x + 0.5) / P.image_scale, (y + 0.5) / P.image_scale);
 			depth = candidate_depth(L.cam, Rv.cam, P, ray, (int)(win & 0xffffu), (int)(win >> 16));
@@ -1050,25 +1054,25 @@ void twoview_rows_scan_kernel(const ViewDev *__restrict__ views, int ref, int ot
 		}
 	}
 	L.depth[pv] = depth;
+	if (WTA) wta_store(wout, (size_t)W*L.h, pv, wwin == 0xffffffffu ? -1 : (int)(wwin & 0xffffu), wwin == 0xffffffffu ? -1 : (int)(wwin >> 16),
+	                   wrun == 0xffffffffu ? -1 : (int)(wrun & 0xffffu), wrun == 0xffffffffu ? -1 : (int)(wrun >> 16));
 }
 
 // cflag == nullptr: exact scan.  cflag, nlist < 0: certified scan.  cflag, nlist >= 0: exact scan of the listed pixels.
 void launch_twoview_rows_scan(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P,
                               int y0, int nrows, const int32_t *count, const uint32_t *cand, int cmax,
                               const uint32_t *rowinfo, const int32_t *meta, const double *cost, int smax,
-                              uint32_t *cflag, int nlist, Counters *cnt)
+                              uint32_t *cflag, int nlist, Counters *cnt, int32_t *wout)
 {
 	const size_t n = (size_t)nrows*width;
 	const CertBound cb = cert_bound(P);
-	if (!cflag)
-		hipLaunchKernelGGL((twoview_rows_scan_kernel<false, false>), dim3((unsigned)((n + RW_LT - 1)/RW_LT)), dim3(RW_LT), 0, st,
-		                   views, ref, oth, P, y0, nrows, count, cand, cmax, rowinfo, meta, cost, smax, nullptr, 0, cnt, cb);
-	else if (nlist < 0)
-		hipLaunchKernelGGL((twoview_rows_scan_kernel<true, false>), dim3((unsigned)((n + RW_LT - 1)/RW_LT)), dim3(RW_LT), 0, st,
-		                   views, ref, oth, P, y0, nrows, count, cand, cmax, rowinfo, meta, cost, smax, cflag, 0, cnt, cb);
-	else if (nlist > 0)
-		hipLaunchKernelGGL((twoview_rows_scan_kernel<false, true>), dim3((unsigned)((nlist + RW_LT - 1)/RW_LT)), dim3(RW_LT), 0, st,
-		                   views, ref, oth, P, y0, nrows, count, cand, cmax, rowinfo, meta, cost, smax, cflag, nlist, cnt, cb);
+#define SRH_RS_LAUNCH(C_, L_, W_, N_, FLAG_, NL_)                                                                              \
+	hipLaunchKernelGGL((twoview_rows_scan_kernel<C_, L_, W_>), dim3((unsigned)(((N_) + RW_LT - 1)/RW_LT)), dim3(RW_LT), 0, st, \
+	                   views, ref, oth, P, y0, nrows, count, cand, cmax, rowinfo, meta, cost, smax, FLAG_, NL_, cnt, cb, wout)
+	if (!cflag) { if (wout) SRH_RS_LAUNCH(false, false, true, n, nullptr, 0); else SRH_RS_LAUNCH(false, false, false, n, nullptr, 0); }
+	else if (nlist < 0) { if (wout) SRH_RS_LAUNCH(true, false, true, n, cflag, 0); else SRH_RS_LAUNCH(true, false, false, n, cflag, 0); }
+	else if (nlist > 0) { if (wout) SRH_RS_LAUNCH(false, true, true, nlist, cflag, nlist); else SRH_RS_LAUNCH(false, true, false, nlist, cflag, nlist); }
+#undef SRH_RS_LAUNCH
 }
 
 } // namespace srh

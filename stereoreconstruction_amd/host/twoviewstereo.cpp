@@ -139,10 +139,35 @@ void TwoViewStereo::computeCostVolumes(CameraPtr leftView_, CameraPtr rightView_
 	if (!uploadViews()) return;
 	if (srh_set_option(ctx_, "cost", costKind) != SRH_OK) { error_ = srh_last_error(); return; }
 	srh_set_option(ctx_, "sad_dense", sadDenseOn);
+	if (srh_set_option(ctx_, "wta_outputs", wtaFlags) != SRH_OK) { error_ = srh_last_error(); return; }
 	if (srh_twoview_wta(ctx_, 0, 1, &params_, 0, 0) != SRH_OK || srh_twoview_wta(ctx_, 1, 0, &params_, 0, 0) != SRH_OK ||
 	    srh_view_depth_download(ctx_, 0, computedDepthLeft.data()) != SRH_OK ||
-	    srh_view_depth_download(ctx_, 1, computedDepthRight.data()) != SRH_OK)
+	    srh_view_depth_download(ctx_, 1, computedDepthRight.data()) != SRH_OK) {
 		error_ = srh_last_error();
+		return;
+	}
+	fetchWtaOutputs();
+}
+
+// the kept by-products of both passes (slot 0: the left map's, slot 1: the right map's); empty when nothing was kept
+void TwoViewStereo::fetchWtaOutputs() {
+	for (int k = 0; k < 2; ++k) { winners_[k].clear(); runners_[k].clear(); minCosts_[k].clear(); secondCosts_[k].clear(); }
+	if (!ctx_ || !wtaFlags) return;
+	for (int k = 0; k < 2; ++k) {
+		int flags = 0, w = 0, h = 0;
+		if (srh_view_wta_outputs_state(ctx_, k, &flags, nullptr) != SRH_OK || srh_view_size(ctx_, k, &w, &h) != SRH_OK) { error_ = srh_last_error(); return; }
+		if (!(flags & SRH_WTA_WINNERS)) continue;
+		const size_t n = static_cast<size_t>(w)*h;
+		const bool costs = (flags & SRH_WTA_COSTS) != 0;
+		winners_[k].resize(2*n); runners_[k].resize(2*n);
+		if (costs) { minCosts_[k].resize(n); secondCosts_[k].resize(n); }
+		if (srh_view_wta_outputs(ctx_, k, winners_[k].data(), runners_[k].data(), costs ? minCosts_[k].data() : nullptr,
+		                         costs ? secondCosts_[k].data() : nullptr) != SRH_OK) {
+			error_ = srh_last_error();
+			winners_[k].clear(); runners_[k].clear(); minCosts_[k].clear(); secondCosts_[k].clear();
+			return;
+		}
+	}
 }
 
 void TwoViewStereo::crossCheck(CameraPtr leftView_, CameraPtr rightView_) {
@@ -191,7 +216,7 @@ void TwoViewStereo::computeDepthMaps() {
 	srh_set_hooks(ctx_, cancelFlag(), onProgress, &hooks);
 	srh_set_option(ctx_, "filter_invalid", filterFlags);
 	srh_set_option(ctx_, "sad_dense", sadDenseOn);
-	if (srh_set_option(ctx_, "cost", costKind) != SRH_OK) {
+	if (srh_set_option(ctx_, "cost", costKind) != SRH_OK || srh_set_option(ctx_, "wta_outputs", wtaFlags) != SRH_OK) {
 		error_ = srh_last_error();
 		srh_set_hooks(ctx_, nullptr, nullptr, nullptr);
 		return;
@@ -202,6 +227,7 @@ void TwoViewStereo::computeDepthMaps() {
 	srh_set_hooks(ctx_, nullptr, nullptr, nullptr);
 	if (rc_ == SRH_E_CANCELLED) return;              // reference: silent return on cancel
 	if (rc_ != SRH_OK) { error_ = srh_last_error(); return; }
+	fetchWtaOutputs();
 	colorize(computedDepthLeft, resultLeft);
 	colorize(computedDepthRight, resultRight);
 }

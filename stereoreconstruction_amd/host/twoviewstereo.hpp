@@ -42,6 +42,22 @@ public:
 	void setSadDense(int on) { sadDenseOn = on; }
 	int sadDense() const { return sadDenseOn; }
 
+	// By-products of the WTA scan (option "wta_outputs"; never the depth maps): SRH_WTA_WINNERS (1) keeps, per pixel of each
+	// map, the candidate pixel of the other view that won and the one that held the minimum before it (its cost is the
+	// ratio test's secondBest); SRH_WTA_WINNERS | SRH_WTA_COSTS (3) also their costs in the reference's arithmetic.  0
+	// (default): nothing is kept.  After computeDepthMaps(): (x, y) pairs, (-1, -1) = none; costs, +INF = none.  Empty
+	// vectors when the outputs were not kept, or under setUseMRF(true) (no scan makes those maps).
+	void setKeepWtaOutputs(int flags) { wtaFlags = flags; }
+	int keepWtaOutputs() const { return wtaFlags; }
+	const std::vector<int32_t> &leftWinners() const { return winners_[0]; }
+	const std::vector<int32_t> &leftRunnersUp() const { return runners_[0]; }
+	const std::vector<double> &leftMinCosts() const { return minCosts_[0]; }
+	const std::vector<double> &leftSecondCosts() const { return secondCosts_[0]; }
+	const std::vector<int32_t> &rightWinners() const { return winners_[1]; }
+	const std::vector<int32_t> &rightRunnersUp() const { return runners_[1]; }
+	const std::vector<double> &rightMinCosts() const { return minCosts_[1]; }
+	const std::vector<double> &rightSecondCosts() const { return secondCosts_[1]; }
+
 	// The MRF stage (a USE_MRF build of the reference, twoviewstereo.cpp:240-258, 308-403, 504-570; PARITY UNPINNED, see
 	// stereo_recon_hip.h): off (default) computeDepthMaps is the WTA of the reference as it is compiled; on, each direction's
 	// depth map comes from TRW-S over the full label cost volume (srh_twoview_compute_mrf: progress 1, 2 "Optimizing...",
@@ -94,6 +110,7 @@ protected:
 private:
 	bool uploadViews();
 	double pairCost(int kind, int x1, int y1, int x2, int y2, bool fromLeft);
+	void fetchWtaOutputs();
 	void colorize(const DepthMap &d, Image &out) const;
 	void colorFromDepth(double depth, uint8_t rgb[3]) const;
 
@@ -109,6 +126,9 @@ private:
 	int filterFlags = 0;
 	int costKind = SRH_COST_NCC;
 	int sadDenseOn = 0;
+	int wtaFlags = 0;
+	std::vector<int32_t> winners_[2], runners_[2];
+	std::vector<double> minCosts_[2], secondCosts_[2];
 	bool useMrf = false;
 	srh_twoview_mrf_params mrfParams_;
 	srh_mrf_info mrfInfo_[2];

@@ -169,6 +169,27 @@ std::vector<std::array<double, 3> > TwoViewStereo::curveOfPixel(int x, int y, bo
 	return curve;
 }
 
+// the kept by-products of both passes (slot 0: the left map's, slot 1: the right map's); empty when nothing was kept
+void TwoViewStereo::fetchWtaOutputs() {
+	for (int k = 0; k < 2; ++k) { winners_[k].clear(); runners_[k].clear(); minCosts_[k].clear(); secondCosts_[k].clear(); }
+	if (!ctx_ || !wtaFlags) return;
+	for (int k = 0; k < 2; ++k) {
+		int flags = 0, w = 0, h = 0;
+		if (srh_view_wta_outputs_state(ctx_, k, &flags, nullptr) != SRH_OK || srh_view_size(ctx_, k, &w, &h) != SRH_OK) { error_ = srh_last_error(); return; }
+		if (!(flags & SRH_WTA_WINNERS)) continue;
+		const size_t n = static_cast<size_t>(w)*h;
+		const bool costs = (flags & SRH_WTA_COSTS) != 0;
+		winners_[k].resize(2*n); runners_[k].resize(2*n);
+		if (costs) { minCosts_[k].resize(n); secondCosts_[k].resize(n); }
+		if (srh_view_wta_outputs(ctx_, k, winners_[k].data(), runners_[k].data(), costs ? minCosts_[k].data() : nullptr,
+		                         costs ? secondCosts_[k].data() : nullptr) != SRH_OK) {
+			error_ = srh_last_error();
+			winners_[k].clear(); runners_[k].clear(); minCosts_[k].clear(); secondCosts_[k].clear();
+			return;
+		}
+	}
+}
+
 void TwoViewStereo::computeDepthMaps() {
 	// twoviewstereo.cpp:150-227: cost volumes (steps 1, 3), cross-check (5), colourise, finished (8).
 	// Errors are silent, as in the reference; lastError() keeps the library's message.
@@ -179,6 +200,7 @@ void TwoViewStereo::computeDepthMaps() {
 	if (!uploadViews()) return;
 	if (srh_set_option(ctx_, "cost", costKind) != SRH_OK) { error_ = srh_last_error(); return; }
 	srh_set_option(ctx_, "sad_dense", sadDenseOn);
+	if (srh_set_option(ctx_, "wta_outputs", wtaFlags) != SRH_OK) { error_ = srh_last_error(); return; }
 	mrfInfo_[0] = mrfInfo_[1] = srh_mrf_info();
 	if (useMrf) {
 		// a USE_MRF build: the library sequences the run and reports the steps (1, 2, 3, 4, 5, [6, 7,] 8) through its hook
@@ -190,6 +212,7 @@ void TwoViewStereo::computeDepthMaps() {
 		srh_set_hooks(ctx_, nullptr, nullptr, nullptr);
 		if (rc == SRH_E_CANCELLED) return;
 		if (rc != SRH_OK) { error_ = srh_last_error(); return; }
+		fetchWtaOutputs();                                  // (no scan made these maps: the vectors come back empty)
 		resultLeft = colorize(computedDepthLeft, left.w, left.h);
 		resultRight = colorize(computedDepthRight, right.w, right.h);
 		return;
@@ -208,6 +231,8 @@ void TwoViewStereo::computeDepthMaps() {
 	    srh_view_depth_download(ctx_, 0, computedDepthLeft.data()) != SRH_OK ||
 	    srh_view_depth_download(ctx_, 1, computedDepthRight.data()) != SRH_OK) { error_ = srh_last_error(); return; }
 	if (isCancelled()) return;
+	fetchWtaOutputs();
+	if (!error_.isEmpty()) return;
 	if (filterFlags) {
 		filterInvalidPixels();
 		if (isCancelled() || !error_.isEmpty()) return;

@@ -123,6 +123,20 @@ public:
 	// SAD of a rectified pair on the dense plan (option "sad_dense": 1 = on, 0 = default): a tuning switch, never the result
 	void setSadDense(int on) { sadDenseOn = on; }
 	int sadDense() const { return sadDenseOn; }
+	// by-products of the WTA scan (option "wta_outputs"; never the depth maps): SRH_WTA_WINNERS (1) keeps per pixel of each map
+	// the winning candidate pixel of the other view and the one that held the minimum before it, SRH_WTA_WINNERS |
+	// SRH_WTA_COSTS (3) also their costs in the reference's arithmetic; 0 (default) nothing.  After computeDepthMaps(): (x, y)
+	// pairs, (-1, -1) = none; costs, +INF = none.  Empty when nothing was kept, or under setUseMRF(true).
+	void setKeepWtaOutputs(int flags) { wtaFlags = flags; }
+	int keepWtaOutputs() const { return wtaFlags; }
+	const std::vector<int32_t> &leftWinners() const { return winners_[0]; }
+	const std::vector<int32_t> &leftRunnersUp() const { return runners_[0]; }
+	const std::vector<double> &leftMinCosts() const { return minCosts_[0]; }
+	const std::vector<double> &leftSecondCosts() const { return secondCosts_[0]; }
+	const std::vector<int32_t> &rightWinners() const { return winners_[1]; }
+	const std::vector<int32_t> &rightRunnersUp() const { return runners_[1]; }
+	const std::vector<double> &rightMinCosts() const { return minCosts_[1]; }
+	const std::vector<double> &rightSecondCosts() const { return secondCosts_[1]; }
 	// the MRF stage (a USE_MRF build of the reference; PARITY UNPINNED, stereo_recon_hip.h): off (default) = the WTA; on, each
 	// map comes from TRW-S over the label cost volume (srh_twoview_compute_mrf: progress 1, 2 "Optimizing...", 3, 4, 5, 8),
 	// cross-check and optional hole filling unchanged.  Cancellation is observed at every progress step.
@@ -148,6 +162,7 @@ protected:
 
 private:
 	double pairCost(int kind, int x1, int y1, int x2, int y2, bool fromLeft);
+	void fetchWtaOutputs();
 	QImage colorize(const DepthMap &d, int w, int h) const;
 	CameraPtr leftView, rightView;
 	srh_camera leftCam, rightCam;                          // snapshots taken by the constructor (srq::cameraInfo)
@@ -162,6 +177,9 @@ private:
 	int filterFlags = 0;
 	int costKind = SRH_COST_NCC;
 	int sadDenseOn = 0;
+	int wtaFlags = 0;
+	std::vector<int32_t> winners_[2], runners_[2];
+	std::vector<double> minCosts_[2], secondCosts_[2];
 	bool useMrf = false;
 	srh_twoview_mrf_params mrfParams_;
 	srh_mrf_info mrfInfo_[2];
