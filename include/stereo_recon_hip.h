@@ -260,6 +260,46 @@ int  srh_set_option(srh_context *ctx, const char *name, long value);
 int  srh_view_upload(srh_context *ctx, int slot, int w, int h,
                      const uint8_t *rgba, const uint8_t *mask, const srh_camera *cam);
 int  srh_view_size(srh_context *ctx, int slot, int *w, int *h);
+/* ---- views at FILE resolution: the scaling the reference performs first, on the device ----
+ * MultiViewStereo::initialize (multiviewstereo.cpp:216-241) smooth-scales every image with scaledToWidth(width*imageScale,
+ * Qt::SmoothTransformation) and takes the mask from the alpha channel of a second copy scaled with Qt::FastTransformation;
+ * TwoViewStereo's constructor (twoviewstereo.cpp:89-124) smooth-scales both images and both mask images.  These entry
+ * points do the same in Qt 5.9.7's integer arithmetic, bit for bit, without Qt: an opt-in beside srh_view_upload, which
+ * still takes ALREADY SCALED bytes.
+ *   size    dw = (int)(src_w*image_scale); f = dw/src_w; SRH_SCALE_SMOOTH: dh = (int)(f*src_h + 0.9999), SRH_SCALE_FAST:
+ *           dh = floor(f*src_h + 0.5) (one less than the smooth height now and then: 101x77 at 0.5 gives 50x39 and 50x38).
+ *           dw <= 0 (or dh <= 0): SRH_E_INVALID.  dw == src_w: the identity (Qt returns the image itself, not
+ *           premultiplied).  Anything else that is not a strict downscale in both axes: SRH_E_UNSUPPORTED.
+ *   smooth  a source with alpha (has_alpha != 0: what QImage makes Format_ARGB32) is premultiplied by Qt's integer rule and
+ *           the result holds premultiplied bytes, which the reference reads raw; has_alpha == 0 (Format_RGB32): the A bytes
+ *           handed over are ignored and alpha is 255.
+ *   fast    nearest neighbour by Qt's two placement rules (with / without alpha); with alpha a fully transparent pixel
+ *           comes out as four zero bytes.
+ * rgba buffers: R, G, B, A bytes, HOST memory. */
+enum { SRH_SCALE_SMOOTH = 0, SRH_SCALE_FAST = 1 };
+/* how srh_view_upload_scaled derives the slot's mask:
+ *   SRH_MASK_NONE          every pixel WHITE
+ *   SRH_MASK_ALPHA_FAST    MultiViewStereo: has_alpha != 0: WHITE <=> alpha == 255 on the fast-scaled copy of the image; rows of
+ *                          the image beyond that copy's height are not WHITE (the reference's mask image is that much shorter
+ *                          and VectorImage::pixel out of bounds is not WHITE).  has_alpha == 0: every pixel WHITE.
+ *   SRH_MASK_IMAGE_SMOOTH  TwoViewStereo: mask_rgba (mask_w x mask_h) smooth-scaled by ITS OWN width; WHITE <=> r = g = b =
+ *                          a = 255 in the scaled raw bytes, pixels beyond the scaled mask image are not WHITE.  mask_rgba ==
+ *                          NULL (a null QImage): every pixel WHITE. */
+enum { SRH_MASK_NONE = 0, SRH_MASK_ALPHA_FAST = 1, SRH_MASK_IMAGE_SMOOTH = 2 };
+/* the size scaledToWidth gives; needs no device */
+int  srh_scaled_size(int src_w, int src_h, double image_scale, int mode, int *w_out, int *h_out);
+/* host -> device -> host: rgba_out receives the srh_scaled_size(...) pixels; w_out / h_out may be NULL */
+int  srh_image_scale(srh_context *ctx, const uint8_t *rgba, int src_w, int src_h, int has_alpha, double image_scale, int mode,
+                     uint8_t *rgba_out, int *w_out, int *h_out);
+/* The view at file resolution into `slot`: scaled on the device, mask by mask_rule, then exactly what srh_view_upload does
+ * with the same scaled bytes and mask -- srh_view_size reports the scaled size and every later call behaves the same.
+ * mask_rgba / mask_w / mask_h / mask_has_alpha are read under SRH_MASK_IMAGE_SMOOTH only.  A refused shape (image or mask
+ * image) leaves the slot as it was.  The staging buffers come from the allocator of the view planes and go back to it. */
+int  srh_view_upload_scaled(srh_context *ctx, int slot, int src_w, int src_h, const uint8_t *rgba, int has_alpha,
+                            const uint8_t *mask_rgba, int mask_w, int mask_h, int mask_has_alpha,
+                            double image_scale, int mask_rule, const srh_camera *cam);
+/* what the slot holds: rgba_out w*h*4 bytes, mask_out w*h bytes (1 = WHITE); each may be NULL; synchronous */
+int  srh_view_image_download(srh_context *ctx, int slot, uint8_t *rgba_out, uint8_t *mask_out);
 /* The context keeps one depth map (w*h doubles) per view slot in device memory. */
 int  srh_view_depth_download(srh_context *ctx, int slot, double *host_out);
 int  srh_view_depth_upload(srh_context *ctx, int slot, const double *host_in);

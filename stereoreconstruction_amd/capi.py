@@ -99,6 +99,9 @@ COST_NCC, COST_SAD = 0, 1
 
 # option "wta_outputs": the by-products of the WTA scan a pass keeps (SRH_WTA_*)
 WTA_WINNERS, WTA_COSTS = 1, 2
+# scaling at file resolution (SRH_SCALE_*, SRH_MASK_*)
+SCALE_SMOOTH, SCALE_FAST = 0, 1
+MASK_NONE, MASK_ALPHA_FAST, MASK_IMAGE_SMOOTH = 0, 1, 2
 
 
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_int, C.c_char_p, C.c_void_p)
@@ -109,7 +112,8 @@ EXPORTS = [
     "srh_params_twoview_defaults", "srh_params_mvs_defaults", "srh_camera_from_krt", "srh_camera_from_p",
     "srh_mvs_neighbours", "srh_cert_bound", "srh_cert_sigma3",
     "srh_create", "srh_destroy", "srh_set_stream", "srh_set_hooks", "srh_synchronize", "srh_set_option",
-    "srh_view_upload", "srh_view_size", "srh_view_depth_download", "srh_view_depth_upload",
+    "srh_view_upload", "srh_view_size", "srh_scaled_size", "srh_image_scale", "srh_view_upload_scaled", "srh_view_image_download",
+    "srh_view_depth_download", "srh_view_depth_upload",
     "srh_view_depth_device_ptr", "srh_view_depth_copy_to_device", "srh_view_depth_copy_from_device",
     "srh_view_wta_outputs", "srh_view_wta_outputs_device", "srh_view_wta_outputs_state",
     "srh_twoview_wta", "srh_twoview_cross_check", "srh_twoview_compute", "srh_twoview_cost_rows", "srh_twoview_pair_costs", "srh_debug_exp",
@@ -175,6 +179,12 @@ def lib():
     L.srh_set_option.argtypes = [vp, C.c_char_p, C.c_long]
     L.srh_view_upload.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_uint8_p, c_uint8_p, C.POINTER(Camera)]
     L.srh_view_size.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.srh_scaled_size.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.srh_image_scale.argtypes = [vp, c_uint8_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, c_uint8_p,
+                                  C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.srh_view_upload_scaled.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_uint8_p, C.c_int, c_uint8_p, C.c_int, C.c_int, C.c_int,
+                                         C.c_double, C.c_int, C.POINTER(Camera)]
+    L.srh_view_image_download.argtypes = [vp, C.c_int, c_uint8_p, c_uint8_p]
     L.srh_view_depth_download.argtypes = [vp, C.c_int, c_double_p]
     L.srh_view_depth_upload.argtypes = [vp, C.c_int, c_double_p]
     L.srh_view_depth_device_ptr.argtypes = [vp, C.c_int, C.POINTER(vp)]
@@ -357,6 +367,21 @@ def device_count():
     return n.value
 
 
+def scaled_size(src_w, src_h, image_scale, mode=SCALE_SMOOTH):
+    """(w, h) QImage::scaledToWidth((int)(src_w*image_scale), mode) gives (srh_scaled_size; no device).  A shape the library
+    does not scale raises StereoHipError with .code SRH_E_INVALID (-1) or SRH_E_UNSUPPORTED (-5)."""
+    w, h = C.c_int(0), C.c_int(0)
+    _check(lib().srh_scaled_size(int(src_w), int(src_h), float(image_scale), int(mode), C.byref(w), C.byref(h)))
+    return w.value, h.value
+
+
+def _rgba_arg(rgba, what="rgba"):
+    rgba = np.ascontiguousarray(rgba, dtype=np.uint8)
+    if rgba.ndim != 3 or rgba.shape[2] != 4:
+        raise ValueError("%s must be HxWx4 uint8" % what)
+    return rgba
+
+
 def _torch_runtime_first():
     """PyTorch-ROCm wheels bundle their own libamdhip64 / libhsa-runtime64; this library links the
     system ROCm.  Both can live in one process, but the bundled runtime must attach to the GPU first
@@ -429,6 +454,37 @@ class Context:
                 raise ValueError("mask must be HxW uint8")
         _check(lib().srh_view_upload(self._h, slot, w, h, rgba.ctypes.data_as(c_uint8_p),
                                      m.ctypes.data_as(c_uint8_p) if m is not None else None, C.byref(cam)))
+
+    def scale_image(self, rgba, has_alpha, image_scale, mode=SCALE_SMOOTH):
+        """rgba (HxWx4, file resolution) scaled on the device as Qt scales it (srh_image_scale): the scaled HxWx4 bytes."""
+        rgba = _rgba_arg(rgba)
+        h, w = rgba.shape[:2]
+        dw, dh = scaled_size(w, h, image_scale, mode)
+        out = np.empty((dh, dw, 4), dtype=np.uint8)
+        _check(lib().srh_image_scale(self._h, rgba.ctypes.data_as(c_uint8_p), w, h, int(bool(has_alpha)), float(image_scale),
+                                     int(mode), out.ctypes.data_as(c_uint8_p), None, None))
+        return out
+
+    def upload_view_scaled(self, slot, rgba, has_alpha, image_scale, cam, mask_rule=MASK_NONE, mask_rgba=None, mask_has_alpha=False):
+        """The view at file resolution: scaled on the device, mask by mask_rule (MASK_ALPHA_FAST: MultiViewStereo's rule;
+        MASK_IMAGE_SMOOTH with mask_rgba: TwoViewStereo's), then as upload_view of the scaled bytes (srh_view_upload_scaled)."""
+        rgba = _rgba_arg(rgba)
+        h, w = rgba.shape[:2]
+        m, mw, mh = None, 0, 0
+        if mask_rgba is not None:
+            m = _rgba_arg(mask_rgba, "mask_rgba")
+            mh, mw = m.shape[:2]
+        _check(lib().srh_view_upload_scaled(self._h, slot, w, h, rgba.ctypes.data_as(c_uint8_p), int(bool(has_alpha)),
+                                            m.ctypes.data_as(c_uint8_p) if m is not None else None, mw, mh, int(bool(mask_has_alpha)),
+                                            float(image_scale), int(mask_rule), C.byref(cam)))
+
+    def download_view_image(self, slot):
+        """(rgba HxWx4, mask HxW) as the slot holds them (srh_view_image_download)."""
+        w, h = self.view_size(slot)
+        rgba = np.empty((h, w, 4), dtype=np.uint8)
+        mask = np.empty((h, w), dtype=np.uint8)
+        _check(lib().srh_view_image_download(self._h, slot, rgba.ctypes.data_as(c_uint8_p), mask.ctypes.data_as(c_uint8_p)))
+        return rgba, mask
 
     def view_size(self, slot):
         w, h = C.c_int(0), C.c_int(0)

@@ -836,10 +836,12 @@ extern "C" int srh_synchronize(srh_context *c) {
 }
 
 // ------------------------------------------------------------------ views
-extern "C" int srh_view_upload(srh_context *c, int slot, int w, int h,
-                               const uint8_t *rgba, const uint8_t *mask, const srh_camera *cam)
+// The pixels and mask of a w x h view into `slot` and every plane derived from them.  rgba / mask: host memory
+// (srh_view_upload) or device memory of this context's device (srh_view_upload_scaled), as `kind` says; hmask: the mask
+// bytes in host memory (null with a null mask).
+static int view_install(srh_context *c, int slot, int w, int h, const void *rgba, const void *mask, const uint8_t *hmask,
+                        hipMemcpyKind kind, const srh_camera *cam)
 {
-	int rc = check_slot(c, slot, false); if (rc) return rc;
 	if (w <= 0 || h <= 0 || (size_t)w*h > ((size_t)1 << 30)) return fail(SRH_E_INVALID, "bad image size %dx%d", w, h);
 	if (!rgba || !cam) return fail(SRH_E_INVALID, "null rgba / camera");
 	HIP_TRY(hipSetDevice(c->device));
@@ -865,10 +867,10 @@ extern "C" int srh_view_upload(srh_context *c, int slot, int w, int h,
 	if (c->mrf_w == w && c->mrf_h == h) c->mrf_w = c->mrf_h = c->mrf_k = 0;
 	if (c->tvmrf_w == w && c->tvmrf_h == h) c->tvmrf_w = c->tvmrf_h = c->tvmrf_l = 0;
 	for (int j = 0; j < SRH_MAX_VIEWS; ++j) { v.list_mode[j] = 0; c->views[j].list_mode[slot] = 0; }   // new geometry
-	HIP_TRY(hipMemcpyAsync(v.rgba, rgba, n*4, hipMemcpyHostToDevice, c->stream));
-	if (mask) HIP_TRY(hipMemcpyAsync(v.mask, mask, n, hipMemcpyHostToDevice, c->stream));
+	HIP_TRY(hipMemcpyAsync(v.rgba, rgba, n*4, kind, c->stream));
+	if (mask) HIP_TRY(hipMemcpyAsync(v.mask, mask, n, kind, c->stream));
 	else      HIP_TRY(hipMemsetAsync(v.mask, 1, n, c->stream));
-	if (mask) v.hmask.assign(mask, mask + n); else v.hmask.clear();
+	if (mask) v.hmask.assign(hmask, hmask + n); else v.hmask.clear();
 	v.act_valid = false;
 	{ Scope s(c, "prep_view_kernel"); launch_prep_view(c->stream, v.rgba, v.mask, w, h, v.gray, v.gray_tv); }
 	{ Scope s(c, "edge_planes_kernel"); launch_edge_planes(c->stream, v.rgba, w, h, v.edges); }
@@ -879,6 +881,172 @@ extern "C" int srh_view_upload(srh_context *c, int slot, int w, int h,
 	HIP_TRY(hipMemcpyAsync(c->d_views + slot, &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));   // the host buffers and `d` may go away after return
 	HIP_TRY(hipGetLastError());
+	return SRH_OK;
+}
+
+extern "C" int srh_view_upload(srh_context *c, int slot, int w, int h,
+                               const uint8_t *rgba, const uint8_t *mask, const srh_camera *cam)
+{
+	int rc = check_slot(c, slot, false); if (rc) return rc;
+	return view_install(c, slot, w, h, rgba, mask, mask, hipMemcpyHostToDevice, cam);
+}
+
+// ---- views at file resolution: Qt's scaling on the device (srh_scale.hip)
+extern "C" int srh_scaled_size(int src_w, int src_h, double image_scale, int mode, int *w_out, int *h_out) {
+	int w = 0, h = 0;
+	const char *why = "";
+	const int rc = scale_target_size(src_w, src_h, image_scale, mode, &w, &h, &why);
+	if (rc) return fail(rc, "%dx%d at scale %g: %s", src_w, src_h, image_scale, why);
+	if (w_out) *w_out = w;
+	if (h_out) *h_out = h;
+	return SRH_OK;
+}
+
+// The staging of one scaling: the source image at file resolution and the fast scale's index maps.  Blocks of the view
+// planes' allocator; release() once the stream has drained (the kernels queued on it read them).
+struct ScaleStage {
+	DevBuf<uint32_t> src;
+	DevBuf<int32_t> dmap;
+	std::vector<int32_t> hmap;                                        // the maps on the host: alive until the copy queued from it is done
+	void release() { src.release(); dmap.release(); }
+};
+
+static int stage_source(srh_context *c, const uint8_t *rgba, int sw, int sh, ScaleStage &st) {
+	const size_t ns = (size_t)sw*sh;
+	if (ns > ((size_t)1 << 30)) return fail(SRH_E_INVALID, "bad image size %dx%d", sw, sh);
+	HIP_TRY(st.src.alloc(ns + 4));                                     // (+ the reach of the smooth kernel's aligned 16-byte loads)
+	HIP_TRY(hipMemsetAsync(st.src + ns, 0, 16, c->stream));
+	HIP_TRY(hipMemcpyAsync(st.src, rgba, ns*4, hipMemcpyHostToDevice, c->stream));
+	return SRH_OK;
+}
+
+// The staged sw x sh source scaled to dw x dh (scale_target_size's answer, not the identity) into `out`, a device buffer the
+// caller releases; queued on the context's stream.  The smooth scale premultiplies the staged source in place: a fast scale
+// of the same source is queued before it.
+static int scale_staged(srh_context *c, ScaleStage &st, int sw, int sh, bool has_alpha, int dw, int dh, int mode, DevBuf<uint32_t> &out) {
+	const size_t ns = (size_t)sw*sh;
+	if (mode == SRH_SCALE_SMOOTH) {
+		if (!(scale_axis_inside(sw, dw) && scale_axis_inside(sh, dh)))
+			return fail(SRH_E_UNSUPPORTED, "%dx%d -> %dx%d: a run of the smooth scale would leave the image", sw, sh, dw, dh);
+		HIP_TRY(out.alloc((size_t)dw*dh));
+		{ Scope s(c, "premultiply_kernel"); launch_premultiply(c->stream, st.src, ns, has_alpha); }
+		{ Scope s(c, "smooth_scale_kernel"); launch_smooth_scale(c->stream, st.src, sw, sh, out, dw, dh); }
+	} else {
+		std::vector<int32_t> &map = st.hmap;
+		map.assign((size_t)dw + dh, 0);
+		if (!scale_fast_maps(sw, sh, dw, dh, has_alpha, map.data()))
+			return fail(SRH_E_UNSUPPORTED, "%dx%d -> %dx%d: a tap of the fast scale would leave the image", sw, sh, dw, dh);
+		HIP_TRY(out.alloc((size_t)dw*dh));
+		HIP_TRY(st.dmap.alloc(map.size()));
+		HIP_TRY(hipMemcpyAsync(st.dmap, map.data(), map.size()*sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+		{ Scope s(c, "fast_scale_kernel"); launch_fast_scale(c->stream, st.src, sw, out, dw, dh, st.dmap, has_alpha); }
+	}
+	HIP_TRY(hipGetLastError());
+	return SRH_OK;
+}
+
+// the identity (dw == sw): the staged source itself becomes `out`; an opaque source gets alpha 255
+static int scale_identity(srh_context *c, ScaleStage &st, int sw, int sh, bool has_alpha, DevBuf<uint32_t> &out) {
+	if (!has_alpha) { Scope s(c, "premultiply_kernel"); launch_premultiply(c->stream, st.src, (size_t)sw*sh, false); }
+	out = std::move(st.src);
+	return SRH_OK;
+}
+
+// the stream drained, the staging back in the pool; rc, or the device's error
+static int scale_finish(srh_context *c, ScaleStage &st, int rc) {
+	const hipError_t e = hipStreamSynchronize(c->stream);
+	st.release();
+	if (rc == SRH_OK && e != hipSuccess) rc = fail(SRH_E_DEVICE, "image scaling: %s", hipGetErrorString(e));
+	return rc;
+}
+
+extern "C" int srh_image_scale(srh_context *c, const uint8_t *rgba, int src_w, int src_h, int has_alpha, double image_scale, int mode,
+                               uint8_t *rgba_out, int *w_out, int *h_out)
+{
+	if (!c) return fail(SRH_E_INVALID, "null context");
+	if (!rgba || !rgba_out) return fail(SRH_E_INVALID, "null rgba");
+	int dw = 0, dh = 0;
+	int rc = srh_scaled_size(src_w, src_h, image_scale, mode, &dw, &dh); if (rc) return rc;
+	{ rc = mvs_settle_all(c); if (rc) return rc; }
+	HIP_TRY(hipSetDevice(c->device));
+	ScaleStage st;
+	DevBuf<uint32_t> out;
+	rc = stage_source(c, rgba, src_w, src_h, st);
+	if (rc == SRH_OK) rc = dw == src_w ? scale_identity(c, st, src_w, src_h, has_alpha != 0, out)
+	                                   : scale_staged(c, st, src_w, src_h, has_alpha != 0, dw, dh, mode, out);
+	rc = scale_finish(c, st, rc);
+	if (rc == SRH_OK) {
+		const hipError_t e = hipMemcpy(rgba_out, out, (size_t)dw*dh*4, hipMemcpyDeviceToHost);
+		if (e != hipSuccess) rc = fail(SRH_E_DEVICE, "image scaling, read-back: %s", hipGetErrorString(e));
+	}
+	out.release();
+	if (rc) return rc;
+	if (w_out) *w_out = dw;
+	if (h_out) *h_out = dh;
+	return SRH_OK;
+}
+
+extern "C" int srh_view_upload_scaled(srh_context *c, int slot, int src_w, int src_h, const uint8_t *rgba, int has_alpha,
+                                      const uint8_t *mask_rgba, int mask_w, int mask_h, int mask_has_alpha,
+                                      double image_scale, int mask_rule, const srh_camera *cam)
+{
+	int rc = check_slot(c, slot, false); if (rc) return rc;
+	if (!rgba || !cam) return fail(SRH_E_INVALID, "null rgba / camera");
+	if (mask_rule != SRH_MASK_NONE && mask_rule != SRH_MASK_ALPHA_FAST && mask_rule != SRH_MASK_IMAGE_SMOOTH)
+		return fail(SRH_E_INVALID, "mask_rule %d unknown", mask_rule);
+	// every refusal of a shape comes before the slot is touched
+	int dw = 0, dh = 0, mw = 0, mh = 0;
+	if ((rc = srh_scaled_size(src_w, src_h, image_scale, SRH_SCALE_SMOOTH, &dw, &dh))) return rc;
+	const bool alpha_mask = mask_rule == SRH_MASK_ALPHA_FAST && has_alpha;
+	const bool image_mask = mask_rule == SRH_MASK_IMAGE_SMOOTH && mask_rgba;
+	if (alpha_mask && (rc = srh_scaled_size(src_w, src_h, image_scale, SRH_SCALE_FAST, &mw, &mh))) return rc;
+	if (image_mask && (rc = srh_scaled_size(mask_w, mask_h, image_scale, SRH_SCALE_SMOOTH, &mw, &mh))) return rc;
+	HIP_TRY(hipSetDevice(c->device));
+	ScaleStage st, mst;
+	DevBuf<uint32_t> img, mimg;
+	DevBuf<uint8_t> dmask;
+	std::vector<uint8_t> hmask;
+	const bool identity = dw == src_w;
+	auto run = [&]() -> int {
+		// the image is staged once: the mask source of MultiViewStereo's rule is its fast scale, queued before the smooth
+		// scale premultiplies the staging in place
+		int r = stage_source(c, rgba, src_w, src_h, st); if (r) return r;
+		if (alpha_mask && !identity && (r = scale_staged(c, st, src_w, src_h, true, mw, mh, SRH_SCALE_FAST, mimg))) return r;
+		r = identity ? scale_identity(c, st, src_w, src_h, has_alpha != 0, img)
+		             : scale_staged(c, st, src_w, src_h, has_alpha != 0, dw, dh, SRH_SCALE_SMOOTH, img);
+		if (r) return r;
+		if (image_mask) {
+			if ((r = stage_source(c, mask_rgba, mask_w, mask_h, mst))) return r;
+			r = mw == mask_w ? scale_identity(c, mst, mask_w, mask_h, mask_has_alpha != 0, mimg)
+			                 : scale_staged(c, mst, mask_w, mask_h, mask_has_alpha != 0, mw, mh, SRH_SCALE_SMOOTH, mimg);
+			if (r) return r;
+		}
+		if (alpha_mask || image_mask) {
+			const size_t n = (size_t)dw*dh;
+			HIP_TRY(dmask.alloc(n));
+			// (the identity under MultiViewStereo's rule: the fast copy is the image itself)
+			const uint32_t *msrc = alpha_mask && identity ? img.p : mimg.p;
+			{ Scope s(c, "scale_mask_kernel"); launch_scale_mask(c->stream, msrc, mw, mh, alpha_mask, dmask, dw, dh); }
+			hmask.resize(n);
+			HIP_TRY(hipMemcpyAsync(hmask.data(), dmask, n, hipMemcpyDeviceToHost, c->stream));
+			HIP_TRY(hipStreamSynchronize(c->stream));
+		}
+		return view_install(c, slot, dw, dh, img, dmask.p, hmask.data(), hipMemcpyDeviceToDevice, cam);
+	};
+	rc = run();
+	rc = scale_finish(c, st, rc);
+	mst.release(); img.release(); mimg.release(); dmask.release();
+	return rc;
+}
+
+extern "C" int srh_view_image_download(srh_context *c, int slot, uint8_t *rgba_out, uint8_t *mask_out) {
+	int rc = check_slot(c, slot, true); if (rc) return rc;
+	HIP_TRY(hipSetDevice(c->device));
+	const ViewHost &v = c->views[slot];
+	const size_t n = (size_t)v.w*v.h;
+	if (rgba_out) HIP_TRY(hipMemcpyAsync(rgba_out, v.rgba, n*4, hipMemcpyDeviceToHost, c->stream));
+	if (mask_out) HIP_TRY(hipMemcpyAsync(mask_out, v.mask, n, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
 	return SRH_OK;
 }
 

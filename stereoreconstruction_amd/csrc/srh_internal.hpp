@@ -441,6 +441,15 @@ void launch_twoview_rows_scan(hipStream_t st, const ViewDev *views, int ref, int
 bool launch_twoview_rows_refill(hipStream_t st, int width, int oth_width, const srh_params &P, int y0,
                                 const uint32_t *cflag, int cap, const double *wbuf, const double *ref_tvp, const double *oth_tvp,
                                 const uint32_t *rowinfo, const int32_t *meta, double *cost, int smax, Counters *cnt);
+// image scaling in Qt's arithmetic, srh_scale.hip
+int  scale_target_size(int sw, int sh, double scale, int mode, int *dw, int *dh, const char **why);   // SRH_OK, or the refusal's code
+bool scale_axis_inside(int s, int d);                   // every run of the smooth scale ends inside the axis
+bool scale_fast_maps(int sw, int sh, int dw, int dh, bool has_alpha, int32_t *map);   // dw source columns, then dh source rows
+void launch_premultiply(hipStream_t st, uint32_t *px, size_t n, bool has_alpha);      // in place; an opaque source: alpha := 255
+// src: 16-byte aligned and readable up to 3 pixels past its end
+void launch_smooth_scale(hipStream_t st, const uint32_t *src, int sw, int sh, uint32_t *dst, int dw, int dh);
+void launch_fast_scale(hipStream_t st, const uint32_t *src, int sw, uint32_t *dst, int dw, int dh, const int32_t *map, bool has_alpha);
+void launch_scale_mask(hipStream_t st, const uint32_t *img, int mw, int mh, bool alpha_only, uint8_t *mask, int w, int h);
 // RCCL exchange, srh_comm.hip (functions return nullptr or an error string)
 const char *rccl_unique_id_get(void *out128);
 const char *rccl_comm_init(void **comm, int nranks, int rank, const void *id128);

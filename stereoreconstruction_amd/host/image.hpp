@@ -1,6 +1,8 @@
 // image.hpp -- 8-bit RGBA raster standing in for QImage at the boundary of the Qt-free classes.
-// The C-ABI takes images ALREADY scaled (QImage::scaledToWidth is Qt-version-specific
-// arithmetic and stays in the Qt adapter, SURVEY.md section 7 "Third-party resampling").
+// Two ways in.  ALREADY SCALED images (srh_view_upload; the constructors and initialize() overloads that say so): the
+// caller has done what QImage::scaledToWidth does.  Or images at FILE RESOLUTION (srh_view_upload_scaled; the
+// ImageDecoder form of MultiViewStereo::initialize and the ScaleOnDevice form of TwoViewStereo's constructor): the library
+// scales them on the device in Qt 5.9.7's integer arithmetic, bit for bit -- no Qt needed.
 #pragma once
 
 #include <cstdint>
@@ -9,6 +11,10 @@
 struct Image {
 	int w = 0, h = 0;
 	std::vector<uint8_t> rgba;                       // w*h*4, byte order R,G,B,A
+	// QImage::hasAlphaChannel() of the decoded file (Format_ARGB32 rather than Format_RGB32).  Read only where the library
+	// scales the image: a source with alpha is premultiplied before the smooth scale and is the source of MultiViewStereo's
+	// mask; without, the A bytes are ignored and alpha is 255.
+	bool hasAlpha = true;
 	Image() { }
 	Image(int w_, int h_, uint8_t r = 255, uint8_t g = 255, uint8_t b = 255, uint8_t a = 255)
 		: w(w_), h(h_), rgba(static_cast<size_t>(w_)*h_*4)

@@ -75,6 +75,47 @@ void MultiViewStereo::initialize(ProjectPtr project_, ImageSetPtr imageSet__, co
 	}
 }
 
+void MultiViewStereo::initialize(ProjectPtr project_, ImageSetPtr imageSet__, const std::vector<CameraPtr> &views_,
+                                 double minDepth_, double maxDepth_, int numDepthLevels_,
+                                 double crossCheckThreshold_, double imageScale_, const ImageDecoder &decode)
+{
+	// multiviewstereo.cpp:193-247 with the decoding handed to `decode` and both scalings done on the device
+	std::vector<CameraPtr> kept;
+	std::vector<Image> imgs;
+	std::vector<std::vector<uint8_t> > scaledMasks;
+	for (size_t i = 0; i < views_.size() && ctx_; ++i) if (views_[i] && imageSet__) {
+		const ProjectImagePtr pi = imageSet__->defaultImageForCamera(views_[i]);
+		Image src;
+		if (!pi || !decode || !decode(pi->file(), src) || src.isNull()) continue;
+		const srh_camera cam = views_[i]->snapshot();
+		const int slot = static_cast<int>(kept.size());
+		if (slot >= SRH_MAX_VIEWS) { error_ = "too many views"; break; }
+		int w = 0, h = 0;
+		if (srh_view_upload_scaled(ctx_, slot, src.w, src.h, src.rgba.data(), src.hasAlpha ? 1 : 0, nullptr, 0, 0, 0,
+		                           imageScale_, SRH_MASK_ALPHA_FAST, &cam) != SRH_OK ||
+		    srh_view_size(ctx_, slot, &w, &h) != SRH_OK) { error_ = srh_last_error(); continue; }
+		Image im(w, h);
+		im.hasAlpha = src.hasAlpha;
+		std::vector<uint8_t> m(static_cast<size_t>(w)*h);
+		if (srh_view_image_download(ctx_, slot, im.rgba.data(), m.data()) != SRH_OK) { error_ = srh_last_error(); continue; }
+		kept.push_back(views_[i]); imgs.push_back(im); scaledMasks.push_back(m);
+	}
+	initialize(kept, imgs, minDepth_, maxDepth_, numDepthLevels_, crossCheckThreshold_, imageScale_);
+	project = project_;
+	imageSet_ = imageSet__;
+	masks = scaledMasks;
+}
+
+const Image *MultiViewStereo::image(CameraPtr view) const {
+	for (size_t v = 0; v < views.size(); ++v) if (views[v] == view) return &images[v];
+	return nullptr;
+}
+
+const std::vector<uint8_t> *MultiViewStereo::mask(CameraPtr view) const {
+	for (size_t v = 0; v < views.size(); ++v) if (views[v] == view) return &masks[v];
+	return nullptr;
+}
+
 int MultiViewStereo::numSteps() const { return 2*static_cast<int>(views.size()); }
 
 void MultiViewStereo::colorize(size_t v) {

@@ -45,6 +45,17 @@ public:
 	                double crossCheckThreshold,
 	                double imageScale,
 	                const ImageLoader &load);
+	// The same with the scaling done HERE, on the device, in Qt's arithmetic (srh_view_upload_scaled, SRH_MASK_ALPHA_FAST;
+	// DESIGN.md 4f): decode(file, image) returns the file's pixels undecorated, at file resolution, with image.hasAlpha set;
+	// the smooth-scaled image and the mask of the fast-scaled copy's alpha come back from the device.  A view whose file
+	// `decode` cannot produce is skipped; one whose shape the library does not scale is skipped with lastError() set.
+	typedef std::function<bool(const std::string &file, Image &image)> ImageDecoder;
+	void initialize(ProjectPtr project, ImageSetPtr imageSet, const std::vector<CameraPtr> &views,
+	                double minDepth, double maxDepth,
+	                int numDepthLevels,
+	                double crossCheckThreshold,
+	                double imageScale,
+	                const ImageDecoder &decode);
 	ImageSetPtr imageSet() const { return imageSet_; }   // the image set of the last initialize (multiviewstereo.hpp:62)
 
 	std::string title() const { return "Multi-View Stereo"; }
@@ -58,6 +69,10 @@ public:
 	// "percent of pixels have depth hypotheses": finite depths among the masked-in pixels (:402-421)
 	double coverage(CameraPtr view) const;
 	const std::vector<std::vector<int> > &neighbourViews() const { return neighbours; }
+	// what initialize() kept for the view, as runTask uploads it: the scaled pixels and the mask bytes (1 = WHITE); null when
+	// the view is not part of the run
+	const Image *image(CameraPtr view) const;
+	const std::vector<uint8_t> *mask(CameraPtr view) const;
 
 	srh_params &params() { return params_; }
 	// The reference picks the MRF branch of computeInitialEstimate at build time (CONFIG+=mrf -> USE_MRF,

@@ -35,6 +35,11 @@ TwoViewStereo::TwoViewStereo(CameraPtr leftView_, Image left_, Image leftMask_,
 	// masks: null => all WHITE (twoviewstereo.cpp:105-113)
 	leftMask = whiteMask(leftMask_, left.w, left.h);
 	rightMask = whiteMask(rightMask_, right.w, right.h);
+	setUp(deviceOrdinal);
+}
+
+// result images, depth maps and parameters for the images in hand; the context, unless the caller made it already
+void TwoViewStereo::setUp(int deviceOrdinal) {
 	resultLeft = Image(left.w, left.h);
 	resultRight = Image(right.w, right.h);
 	const double NaN = std::numeric_limits<double>::quiet_NaN();
@@ -45,7 +50,39 @@ TwoViewStereo::TwoViewStereo(CameraPtr leftView_, Image left_, Image leftMask_,
 	params_.num_depth_levels = numDepthLevels; params_.image_scale = imageScale;
 	srh_twoview_mrf_params_defaults(&mrfParams_);
 	mrfInfo_[0] = mrfInfo_[1] = srh_mrf_info();
+	if (!ctx_ && error_.empty() && srh_create(deviceOrdinal, &ctx_) != SRH_OK) { error_ = srh_last_error(); ctx_ = nullptr; }
+}
+
+TwoViewStereo::TwoViewStereo(ScaleOnDevice, CameraPtr leftView_, const Image &left_, const Image &leftMask_,
+                             CameraPtr rightView_, const Image &right_, const Image &rightMask_,
+                             double minDepth_, double maxDepth_, int numDepthLevels_,
+                             double imageScale_, int deviceOrdinal)
+	: leftView(leftView_), rightView(rightView_)
+	, minDepth(minDepth_), maxDepth(maxDepth_), numDepthLevels(numDepthLevels_), imageScale(imageScale_)
+	, ctx_(nullptr)
+{
+	// twoviewstereo.cpp:89-113: scaledToWidth(width*imageScale, Qt::SmoothTransformation) of both images and both masks
 	if (srh_create(deviceOrdinal, &ctx_) != SRH_OK) { error_ = srh_last_error(); ctx_ = nullptr; }
+	const Image *src[2] = { &left_, &right_ }, *msk[2] = { &leftMask_, &rightMask_ };
+	Image *dst[2] = { &left, &right };
+	std::vector<uint8_t> *dmask[2] = { &leftMask, &rightMask };
+	CameraPtr cams[2] = { leftView, rightView };
+	for (int s = 0; s < 2 && ctx_ && error_.empty(); ++s) {
+		if (!cams[s] || src[s]->isNull()) { error_ = "null view or image"; break; }
+		const srh_camera cam = cams[s]->snapshot();
+		const bool hasMask = !msk[s]->isNull();
+		int w = 0, h = 0;
+		if (srh_view_upload_scaled(ctx_, s, src[s]->w, src[s]->h, src[s]->rgba.data(), src[s]->hasAlpha ? 1 : 0,
+		                           hasMask ? msk[s]->rgba.data() : nullptr, msk[s]->w, msk[s]->h, msk[s]->hasAlpha ? 1 : 0,
+		                           imageScale, SRH_MASK_IMAGE_SMOOTH, &cam) != SRH_OK ||
+		    srh_view_size(ctx_, s, &w, &h) != SRH_OK) { error_ = srh_last_error(); break; }
+		*dst[s] = Image(w, h);
+		dst[s]->hasAlpha = src[s]->hasAlpha;
+		dmask[s]->resize(static_cast<size_t>(w)*h);
+		if (srh_view_image_download(ctx_, s, dst[s]->rgba.data(), dmask[s]->data()) != SRH_OK) { error_ = srh_last_error(); break; }
+	}
+	if (!error_.empty()) { left = right = Image(); leftMask.clear(); rightMask.clear(); }
+	setUp(deviceOrdinal);
 }
 
 TwoViewStereo::~TwoViewStereo() { if (ctx_) srh_destroy(ctx_); }

@@ -22,6 +22,18 @@ public:
 	              int numDepthLevels,
 	              double imageScale = 1.0,
 	              int deviceOrdinal = 0);
+	// The reference's constructor as it is called (twoviewstereo.cpp:89-124): images and mask images at FILE RESOLUTION,
+	// smooth-scaled here, on the device, in Qt's arithmetic (srh_view_upload_scaled, SRH_MASK_IMAGE_SMOOTH) --
+	// each image by width*imageScale, each mask image by its own; a null mask image: all WHITE.  Image::hasAlpha says which
+	// of Qt's two 32-bit formats the file decoded to.  A shape the library does not scale leaves lastError() set and the
+	// object without images (computeDepthMaps then fails the way it does without a device).
+	struct ScaleOnDevice { };
+	TwoViewStereo(ScaleOnDevice, CameraPtr leftView, const Image &left, const Image &leftMask,
+	              CameraPtr rightView, const Image &right, const Image &rightMask,
+	              double minDepth, double maxDepth,
+	              int numDepthLevels,
+	              double imageScale = 1.0,
+	              int deviceOrdinal = 0);
 	~TwoViewStereo();
 
 	std::string title() const { return "Two-View Stereo"; }
@@ -74,6 +86,12 @@ public:
 	// direction, which is what StereoWidget has in hand (stereowidget.cpp:621-672).
 	std::vector<std::pair<int, int> > epipolarCurve(int x, int y, bool fromLeft = true);
 
+	// the scaled images and masks (1 = WHITE) computeDepthMaps uploads
+	const Image &leftImage() const { return left; }
+	const Image &rightImage() const { return right; }
+	const std::vector<uint8_t> &leftMaskBytes() const { return leftMask; }
+	const std::vector<uint8_t> &rightMaskBytes() const { return rightMask; }
+
 	Image leftDepthMap() const { return resultLeft; }
 	Image rightDepthMap() const { return resultRight; }
 
@@ -109,6 +127,7 @@ protected:
 
 private:
 	bool uploadViews();
+	void setUp(int deviceOrdinal);
 	double pairCost(int kind, int x1, int y1, int x2, int y2, bool fromLeft);
 	void fetchWtaOutputs();
 	void colorize(const DepthMap &d, Image &out) const;
