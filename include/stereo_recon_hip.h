@@ -506,6 +506,53 @@ int  srh_twoview_mrf_state(srh_context *ctx, int w, int h, int L, int32_t *label
 int  srh_view_point_cloud(srh_context *ctx, int slot, const srh_params *p, double *xyz_out, uint8_t *rgb_out,
                           uint8_t *valid_out, int64_t *n_points, int64_t *n_masked, int64_t *n_finite);
 
+/* ---- depth-map fusion: the views' depth maps -> one oriented cloud ----
+ * NOT IN THE REFERENCE (it stops at outputPLYFile and hands its images to PMVS for a merged model); only the geometry is
+ * the reference's: the point of a pixel is srh_view_point_cloud's, and the consistency test is that of
+ * MultiViewStereo::crossCheck (multiviewstereo.cpp:666-729) applied to EVERY other view, the other view's mask consulted.
+ *   points   pixel i of list entry v has a point P(v, i) when srh_view_point_cloud gives it one (mask WHITE, depth finite,
+ *            pointFromDepth succeeds; the depth -1 has none).
+ *   fusion   list entries in order v = 0 .. nviews-1, each strictly after the one before it.  For every pixel i of v with a point
+ *            P1 that no earlier entry has claimed: the MEMBERS are (v, i) and, for every u != v in ascending u, the pixel
+ *            j = (int)(y2)*w_u + (int)(x2) of (x2, y2) = image_scale * project_u(P1) when it lies inside u, has a point P2 and
+ *            |P1 - P2| is finite and < thr (dist_threshold, or p->cross_check_threshold when that is <= 0); a claimed pixel
+ *            still counts.  Fewer than min_views members: the pixel is UNSUPPORTED (nothing emitted, nothing claimed).
+ *            Otherwise ONE point is emitted: the members' points added up in ascending list index (the first one starts the
+ *            sum) / (double)m; per colour channel (2*sum + m)/(2*m) of the members' bytes in integers; nviews = m; and every
+ *            member of an entry u > v is CLAIMED (it is not emitted when u's turn comes).
+ *   normal   from v's own points: horizontal tangent P_R - P_L (both neighbours usable), else P_R - P, else P - P_L; the
+ *            vertical one alike with P_D - P_U; a neighbour is usable inside the image, with a point and a depth within
+ *            `gap` of the pixel's (normal_depth_gap, or 2*(max_depth - min_depth)/(num_depth_levels - 1) when that is <= 0).
+ *            Both tangents and a finite cross product of length > 0: its unit vector, turned towards the camera centre
+ *            (flags bit 0 set); else the unit vector from P to the camera centre (bit 0 clear).
+ *   output   compacted in ascending (v, i) by an ordered stream compaction (no atomic decides a position): xyz, normal
+ *            (3 doubles each), rgb (3 bytes), nviews, flags (1 byte each), src (2 int32: list index, pixel index).
+ * The result is a pure function of the inputs: the same call gives the same bytes.  It stays in the context until the next
+ * srh_mvs_fuse or srh_destroy (a later view upload does not touch it; a failed or cancelled srh_mvs_fuse leaves none).  The
+ * call reads depth maps, masks, pixels and cameras and modifies none of them.  Views may differ in size; nviews == 1 with
+ * min_views == 1 gives the view's own cloud.  All views must be in this one context (a sharded run: after
+ * srh_comm_allgather_views they are).  The cancel hook is polled between the views. */
+typedef struct srh_fuse_params {
+	double  dist_threshold;     /* 0: p->cross_check_threshold */
+	double  normal_depth_gap;   /* 0: two depth steps of p */
+	int32_t min_views;          /* 2 */
+	int32_t flags;              /* 0; reserved */
+} srh_fuse_params;
+void srh_fuse_params_defaults(srh_fuse_params *f);   /* 0, 0, 2, 0; needs no device */
+/* n_candidates: pixels with a point, over all views = n_points + n_claimed + n_unsupported; n_normals: points with bit 0 */
+typedef struct srh_fuse_info {
+	int64_t n_points, n_candidates, n_claimed, n_unsupported, n_normals;
+} srh_fuse_info;
+/* f == NULL: the defaults; info may be NULL.  SRH_E_INVALID: nviews < 1, a duplicate or empty slot, min_views < 1. */
+int  srh_mvs_fuse(srh_context *ctx, const int32_t *slots, int nviews, const srh_params *p, const srh_fuse_params *f,
+                  srh_fuse_info *info);
+int  srh_mvs_fused_count(srh_context *ctx, int64_t *n);
+/* points [first, first + count) to HOST buffers, each may be NULL; a window outside [0, n]: SRH_E_INVALID */
+int  srh_mvs_fused_download(srh_context *ctx, int64_t first, int64_t count, double *xyz, double *normals, uint8_t *rgb,
+                            uint8_t *nviews, uint8_t *flags, int32_t *src);
+/* the DEVICE arrays themselves (n entries each; null pointers when n == 0); each argument may be NULL */
+int  srh_mvs_fused_device(srh_context *ctx, void **xyz, void **normals, void **rgb, void **nviews, void **flags, void **src);
+
 /* ---- hole filling: TwoViewStereo::filterInvalidPixels (twoviewstereo.cpp:676-811) and weightedMedian (:821-860) ----
  * In place on `slot`'s depth map D, with the slot's image I and mask M; DESIGN.md 4b.
  *   SRH_FILTER_GAPS    the function's compiled body: per row, a run of isinf pixels with end - start < gap_width (the

@@ -94,6 +94,21 @@ class FilterInfo(C.Structure):
 # srh_view_filter_invalid flags
 FILTER_GAPS, FILTER_MEDIAN = 1, 2
 
+
+class FuseParams(C.Structure):
+    """srh_fuse_params"""
+    _fields_ = [("dist_threshold", C.c_double), ("normal_depth_gap", C.c_double), ("min_views", C.c_int32), ("flags", C.c_int32)]
+
+
+class FuseInfo(C.Structure):
+    """srh_fuse_info"""
+    _fields_ = [("n_points", C.c_int64), ("n_candidates", C.c_int64), ("n_claimed", C.c_int64),
+                ("n_unsupported", C.c_int64), ("n_normals", C.c_int64)]
+
+
+# srh_mvs_fuse: bit 0 of a fused point's flags
+FUSE_HAS_NORMAL = 1
+
 # option "cost" / srh_twoview_pair_costs kind: TwoViewStereo::cost_ncc, cost_sad
 COST_NCC, COST_SAD = 0, 1
 
@@ -118,6 +133,7 @@ EXPORTS = [
     "srh_view_wta_outputs", "srh_view_wta_outputs_device", "srh_view_wta_outputs_state",
     "srh_twoview_wta", "srh_twoview_cross_check", "srh_twoview_compute", "srh_twoview_cost_rows", "srh_twoview_pair_costs", "srh_debug_exp",
     "srh_mvs_initial_estimate", "srh_mvs_cross_check", "srh_view_point_cloud", "srh_view_filter_invalid",
+    "srh_fuse_params_defaults", "srh_mvs_fuse", "srh_mvs_fused_count", "srh_mvs_fused_download", "srh_mvs_fused_device",
     "srh_epipolar_curves",
     "srh_epipolar_preview", "srh_refraction_error",
     "srh_mrf_params_defaults", "srh_mvs_mrf_estimate", "srh_mvs_mrf_state", "srh_mvs_mrf_dims", "srh_mvs_initial_estimate_mrf",
@@ -214,6 +230,12 @@ def lib():
     L.srh_refraction_error.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]
     L.srh_view_point_cloud.argtypes = [vp, C.c_int, C.POINTER(Params), c_double_p, c_uint8_p, c_uint8_p, vp, vp, vp]
     L.srh_view_filter_invalid.argtypes = [vp, C.c_int, C.POINTER(Params), C.c_int, C.c_int, C.POINTER(FilterInfo)]
+    L.srh_fuse_params_defaults.argtypes = [C.POINTER(FuseParams)]
+    L.srh_fuse_params_defaults.restype = None
+    L.srh_mvs_fuse.argtypes = [vp, c_int32_p, C.c_int, C.POINTER(Params), C.POINTER(FuseParams), C.POINTER(FuseInfo)]
+    L.srh_mvs_fused_count.argtypes = [vp, C.POINTER(C.c_int64)]
+    L.srh_mvs_fused_download.argtypes = [vp, C.c_int64, C.c_int64, c_double_p, c_double_p, c_uint8_p, c_uint8_p, c_uint8_p, c_int32_p]
+    L.srh_mvs_fused_device.argtypes = [vp] + [C.POINTER(vp)] * 6
     L.srh_twoview_pair_costs.argtypes = [vp, C.c_int, C.c_int, C.POINTER(Params), C.c_int, C.c_int, c_int32_p, c_double_p]
     L.srh_view_depth_copy_to_device.argtypes = [vp, C.c_int, vp, C.c_size_t]
     L.srh_view_depth_copy_from_device.argtypes = [vp, C.c_int, vp, C.c_size_t]
@@ -283,6 +305,17 @@ def twoview_mrf_params(**kw):
             raise AttributeError(k)
         setattr(m, k, v)
     return m
+
+
+def fuse_params(**kw):
+    """srh_fuse_params with its defaults (dist_threshold 0, normal_depth_gap 0, min_views 2, flags 0)."""
+    f = FuseParams()
+    lib().srh_fuse_params_defaults(C.byref(f))
+    for k, v in kw.items():
+        if not hasattr(f, k):
+            raise AttributeError(k)
+        setattr(f, k, v)
+    return f
 
 
 def _mrf_info(info):
@@ -607,6 +640,40 @@ class Context:
                                           valid.ctypes.data_as(c_uint8_p), C.cast(C.byref(n, 0), C.c_void_p),
                                           C.cast(C.byref(n, 8), C.c_void_p), C.cast(C.byref(n, 16), C.c_void_p)))
         return dict(xyz=xyz, rgb=rgb, valid=valid, n_points=int(n[0]), n_masked=int(n[1]), n_finite=int(n[2]))
+
+    def mvs_fuse(self, slots, p, f=None):
+        """The depth maps of the listed slots fused into one oriented cloud (srh_mvs_fuse) -> dict(xyz (n,3) float64,
+        normals (n,3) float64, rgb (n,3) uint8, nviews (n,) uint8, flags (n,) uint8 (bit 0: the normal comes from the
+        surface), src (n,2) int32 (index into `slots`, pixel index), n_points, n_candidates, n_claimed, n_unsupported,
+        n_normals)."""
+        s = np.ascontiguousarray(slots, dtype=np.int32)
+        info = FuseInfo()
+        _check(lib().srh_mvs_fuse(self._h, s.ctypes.data_as(c_int32_p), len(s), C.byref(p),
+                                  C.byref(f) if f is not None else None, C.byref(info)))
+        out = self.mvs_fused_download(0, self.mvs_fused_count())
+        out.update({k: int(getattr(info, k)) for k, _ in FuseInfo._fields_})
+        return out
+
+    def mvs_fused_count(self):
+        n = C.c_int64(0)
+        _check(lib().srh_mvs_fused_count(self._h, C.byref(n)))
+        return int(n.value)
+
+    def mvs_fused_download(self, first, count):
+        """Points [first, first + count) of the last srh_mvs_fuse -> dict of arrays (see mvs_fuse)."""
+        k = max(int(count), 0)
+        out = dict(xyz=np.empty((k, 3), np.float64), normals=np.empty((k, 3), np.float64), rgb=np.empty((k, 3), np.uint8),
+                   nviews=np.empty(k, np.uint8), flags=np.empty(k, np.uint8), src=np.empty((k, 2), np.int32))
+        _check(lib().srh_mvs_fused_download(self._h, first, count, _dptr(out["xyz"]), _dptr(out["normals"]),
+                                            out["rgb"].ctypes.data_as(c_uint8_p), out["nviews"].ctypes.data_as(c_uint8_p),
+                                            out["flags"].ctypes.data_as(c_uint8_p), out["src"].ctypes.data_as(c_int32_p)))
+        return out
+
+    def mvs_fused_device(self):
+        """Device addresses of the fused cloud's arrays -> dict(xyz, normals, rgb, nviews, flags, src) of ints (0: empty)."""
+        ptrs = [C.c_void_p() for _ in range(6)]
+        _check(lib().srh_mvs_fused_device(self._h, *[C.byref(q) for q in ptrs]))
+        return dict(zip(("xyz", "normals", "rgb", "nviews", "flags", "src"), [q.value or 0 for q in ptrs]))
 
     def filter_invalid(self, slot, p, flags=FILTER_GAPS | FILTER_MEDIAN, gap_width=2):
         """TwoViewStereo::filterInvalidPixels on the slot's depth map, in place (srh_view_filter_invalid)

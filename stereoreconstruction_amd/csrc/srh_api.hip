@@ -356,6 +356,12 @@ struct srh_context {
 	int cost_kind = SRH_COST_NCC;                       // option "cost": the TwoView matching cost, SRH_COST_NCC or SRH_COST_SAD
 	int sad_dense = 0;                                  // option "sad_dense": cost_sad of row-aligned rigs on the dense plan (srh_sad_strip.hip)
 	int wta_outputs = 0;                                // option "wta_outputs": SRH_WTA_* planes a TwoView WTA pass keeps per reference pixel (never changes a depth map)
+	// srh_mvs_fuse (srh_fuse.hip): the fused cloud of the last call -- one block carved into the arrays of
+	// fuse_out -- and the call's scratch (point maps, flags, staging planes), which goes back to the pool when the call ends
+	DevBuf<double> fuse_result, fuse_scratch;
+	FuseCloud fuse_out = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+	int64_t fuse_n = 0;
+	bool fuse_valid = false;
 };
 
 static bool cancelled(srh_context *c) { return c->cancel && *c->cancel; }
@@ -724,6 +730,7 @@ extern "C" void srh_destroy(srh_context *c) {
 	}
 	c->mrf.release(); c->mrf_peaks.release();
 	c->tvmrf.release(); c->tvmrf_costs.release();
+	c->fuse_result.release(); c->fuse_scratch.release();
 	for (int i = 0; i < SRH_MAX_VIEWS; ++i) if (c->mrf_stream[i]) hipStreamDestroy(c->mrf_stream[i]);
 	if (c->mrf_host) hipHostFree(c->mrf_host);
 	if (c->comm) (void)rccl_comm_destroy(c->comm);
@@ -2489,6 +2496,19 @@ static int mvs_initial_estimate_run(srh_context *c, int view, const int32_t *nei
 	return SRH_OK;
 }
 
+// the view list travels once per run: MultiViewStereo::crossCheck is called per view with the same list, and a copy per
+// call (from caller memory: with a host wait) put a copy, two dispatch gaps and a host round trip between the kernels
+static int slots_to_device(srh_context *c, const int32_t *slots, int nviews) {
+	if (c->slots_n != nviews || memcmp(c->slots_host, slots, sizeof(int32_t)*nviews) != 0) {
+		c->slots_n = 0;                                             // (a failed copy must not leave a cache entry behind)
+		memcpy(c->slots_host, slots, sizeof(int32_t)*nviews);
+		HIP_TRY(hipMemcpyAsync(c->d_slots, c->slots_host, sizeof(int32_t)*nviews, hipMemcpyHostToDevice, c->stream));
+		HIP_TRY(hipStreamSynchronize(c->stream));                   // (the context's copy may change with the next call)
+		c->slots_n = nviews;
+	}
+	return SRH_OK;
+}
+
 extern "C" int srh_mvs_cross_check(srh_context *c, const int32_t *slots, int nviews, int view_index,
                                    const srh_params *p)
 {
@@ -2499,15 +2519,7 @@ extern "C" int srh_mvs_cross_check(srh_context *c, const int32_t *slots, int nvi
 	if (view_index < 0 || view_index >= nviews) return fail(SRH_E_INVALID, "view_index %d outside [0,%d)", view_index, nviews);
 	for (int i = 0; i < nviews; ++i) if ((rc = check_slot(c, slots[i], true))) return rc;
 	HIP_TRY(hipSetDevice(c->device));
-	// the view list travels once per run: MultiViewStereo::crossCheck is called per view with the same list, and a copy per
-	// call (from caller memory: with a host wait) put a copy, two dispatch gaps and a host round trip between the kernels
-	if (c->slots_n != nviews || memcmp(c->slots_host, slots, sizeof(int32_t)*nviews) != 0) {
-		c->slots_n = 0;                                             // (a failed copy must not leave a cache entry behind)
-		memcpy(c->slots_host, slots, sizeof(int32_t)*nviews);
-		HIP_TRY(hipMemcpyAsync(c->d_slots, c->slots_host, sizeof(int32_t)*nviews, hipMemcpyHostToDevice, c->stream));
-		HIP_TRY(hipStreamSynchronize(c->stream));                   // (the context's copy may change with the next call)
-		c->slots_n = nviews;
-	}
+	if ((rc = slots_to_device(c, slots, nviews))) return rc;
 	const ViewHost &A = c->views[slots[view_index]];
 	{ Scope s(c, "mvs_cross_check_kernel");
 	  launch_mvs_cross_check(c->stream, c->d_views, c->d_slots, nviews, view_index, A.w, A.h, *p); }
@@ -2544,6 +2556,176 @@ extern "C" int srh_view_point_cloud(srh_context *c, int slot, const srh_params *
 	if (n_points) *n_points = (int64_t)hc[0];
 	if (n_masked) *n_masked = (int64_t)hc[1];
 	if (n_finite) *n_finite = (int64_t)hc[2];
+	return SRH_OK;
+}
+
+// ------------------------------------------------------------------ depth-map fusion (srh_fuse.hip)
+extern "C" void srh_fuse_params_defaults(srh_fuse_params *f) {
+	if (!f) return;
+	f->dist_threshold = 0; f->normal_depth_gap = 0; f->min_views = 2; f->flags = 0;
+}
+
+// the arrays of a cloud of `cap` points in one block of doubles: xyz | normals | src | rgb | nviews | flags
+static size_t fuse_cloud_doubles(size_t cap) { return 7*cap + (5*cap + 7)/8; }
+static FuseCloud fuse_cloud_carve(double *base, size_t cap) {
+	FuseCloud f;
+	f.xyz = base; f.nrm = base + 3*cap;
+	f.src = reinterpret_cast<int32_t *>(base + 6*cap);
+	f.rgb = reinterpret_cast<uint8_t *>(base + 7*cap);
+	f.nviews = f.rgb + 3*cap; f.flags = f.nviews + cap;
+	return f;
+}
+
+extern "C" int srh_mvs_fuse(srh_context *c, const int32_t *slots, int nviews, const srh_params *p, const srh_fuse_params *fp,
+                            srh_fuse_info *info)
+{
+	int rc;
+	if (!c) return fail(SRH_E_INVALID, "null context");
+	if ((rc = check_params(p))) return rc;
+	if (!slots || nviews < 1 || nviews > SRH_MAX_VIEWS) return fail(SRH_E_INVALID, "bad view list");
+	srh_fuse_params f;
+	srh_fuse_params_defaults(&f);
+	if (fp) f = *fp;
+	if (f.min_views < 1) return fail(SRH_E_INVALID, "min_views %d < 1", f.min_views);
+	for (int i = 0; i < nviews; ++i) {
+		if ((rc = check_slot(c, slots[i], true))) return rc;
+		for (int k = 0; k < i; ++k) if (slots[k] == slots[i]) return fail(SRH_E_INVALID, "view slot %d listed twice", slots[i]);
+	}
+	HIP_TRY(hipSetDevice(c->device));
+	c->fuse_valid = false; c->fuse_n = 0;
+	if ((rc = slots_to_device(c, slots, nviews))) return rc;
+	const double thr = f.dist_threshold > 0 ? f.dist_threshold : p->cross_check_threshold;
+	const double gap = f.normal_depth_gap > 0 ? f.normal_depth_gap : 2*(p->max_depth - p->min_depth)/(p->num_depth_levels - 1);
+
+	// scratch, in doubles: point maps (3T) | staging xyz, normals (3M each) | block offsets (NB) | counters (8) | point-cloud
+	// counters (4) | view table (3 per view) | block counts (NB u32) | bytes: has-a-point (T), claimed (T), emit (M), staging
+	// rgb (3M), nviews (M), flags (M) -- T = pixels of all views, M = of the largest, NB = its blocks
+	size_t T = 0, M = 0;
+	for (int i = 0; i < nviews; ++i) { const ViewHost &v = c->views[slots[i]]; const size_t n = (size_t)v.w*v.h; T += n; M = std::max(M, n); }
+	const size_t NB = (M + SRH_FUSE_BLOCK - 1)/SRH_FUSE_BLOCK;
+	static_assert(sizeof(FuseViewDev) == 3*sizeof(double), "view table entries are three pointers");
+	const size_t need = 3*T + 6*M + NB + 8 + 4 + 3*(size_t)nviews + (NB + 1)/2 + (2*T + 6*M + 7)/8;
+	if ((rc = c->fuse_scratch.ensure(need))) return rc;
+	double *q = c->fuse_scratch;
+	double *d_pts = q; q += 3*T;
+	FuseCloud stage = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+	stage.xyz = q; q += 3*M;
+	stage.nrm = q; q += 3*M;
+	unsigned long long *d_offs = reinterpret_cast<unsigned long long *>(q); q += NB;
+	unsigned long long *d_counters = reinterpret_cast<unsigned long long *>(q); q += 8;
+	unsigned long long *d_pc = reinterpret_cast<unsigned long long *>(q); q += 4;
+	FuseViewDev *d_fv = reinterpret_cast<FuseViewDev *>(q); q += 3*(size_t)nviews;
+	uint32_t *d_bcount = reinterpret_cast<uint32_t *>(q); q += (NB + 1)/2;
+	uint8_t *d_valid = reinterpret_cast<uint8_t *>(q), *d_claimed = d_valid + T, *d_emit = d_claimed + T;
+	stage.rgb = d_emit + M; stage.nviews = stage.rgb + 3*M; stage.flags = stage.nviews + M;
+
+	std::vector<FuseViewDev> fv((size_t)nviews);
+	{
+		size_t off = 0;
+		for (int i = 0; i < nviews; ++i) {
+			const ViewHost &v = c->views[slots[i]];
+			fv[i].pts = d_pts + 3*off; fv[i].valid = d_valid + off; fv[i].claimed = d_claimed + off;
+			off += (size_t)v.w*v.h;
+		}
+	}
+	HIP_TRY(hipMemcpyAsync(d_fv, fv.data(), sizeof(FuseViewDev)*nviews, hipMemcpyHostToDevice, c->stream));
+	HIP_TRY(hipMemsetAsync(d_counters, 0, 12*sizeof(unsigned long long), c->stream));   // the counters and the point-cloud counters
+	HIP_TRY(hipMemsetAsync(d_claimed, 0, T, c->stream));
+	// stage 0: every view's point map, by the kernel of srh_view_point_cloud
+	for (int i = 0; i < nviews; ++i) {
+		const ViewHost &v = c->views[slots[i]];
+		Scope s(c, "point_cloud_kernel");
+		launch_point_cloud(c->stream, c->d_views, slots[i], v.w, v.h, *p, const_cast<double *>(fv[i].pts), nullptr,
+		                   const_cast<uint8_t *>(fv[i].valid), d_pc);
+	}
+	HIP_TRY(hipGetLastError());
+	unsigned long long pc[3] = { 0, 0, 0 };
+	HIP_TRY(hipMemcpyAsync(pc, d_pc, sizeof(pc), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	// the result: room for every pixel with a point (what min_views = 1 and disjoint views would emit)
+	const size_t cap = (size_t)pc[0];
+	FuseCloud out = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+	if (cap) {
+		if ((rc = c->fuse_result.ensure(fuse_cloud_doubles(cap)))) return rc;
+		out = fuse_cloud_carve(c->fuse_result, cap);
+	}
+	// stage 1: the list's entries in order on the one stream
+	for (int i = 0; i < nviews; ++i) {
+		if (cancelled(c)) {
+			(void)hipStreamSynchronize(c->stream);
+			c->fuse_scratch.release();
+			return fail(SRH_E_CANCELLED, "cancelled");
+		}
+		const ViewHost &v = c->views[slots[i]];
+		const size_t n = (size_t)v.w*v.h;
+		{ Scope s(c, "fuse_view_kernel");
+		  launch_fuse_view(c->stream, c->d_views, c->d_slots, nviews, i, v.w, v.h, *p, thr, gap, f.min_views, d_fv, d_emit, stage,
+		                   d_bcount, d_counters); }
+		{ Scope s(c, "fuse_scan_kernel");
+		  launch_fuse_scan(c->stream, d_bcount, (int)((n + SRH_FUSE_BLOCK - 1)/SRH_FUSE_BLOCK), d_offs, d_counters); }
+		{ Scope s(c, "fuse_scatter_kernel");
+		  launch_fuse_scatter(c->stream, i, n, d_emit, stage, d_offs, out, cap); }
+	}
+	HIP_TRY(hipGetLastError());
+	unsigned long long hc[5] = { 0, 0, 0, 0, 0 };
+	HIP_TRY(hipMemcpyAsync(hc, d_counters, sizeof(hc), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	c->fuse_scratch.release();                                      // (idle: the stream has just been waited for)
+	if (hc[4] != hc[0] || hc[0] > cap) return fail(SRH_E_DEVICE, "fusion: %llu points counted, %llu placed, room for %zu", hc[0], hc[4], cap);
+	c->fuse_out = out; c->fuse_n = (int64_t)hc[0]; c->fuse_valid = true;
+	if (info) {
+		info->n_points = (int64_t)hc[0]; info->n_candidates = (int64_t)pc[0]; info->n_claimed = (int64_t)hc[1];
+		info->n_unsupported = (int64_t)hc[2]; info->n_normals = (int64_t)hc[3];
+	}
+	return SRH_OK;
+}
+
+static int fuse_result_check(srh_context *c) {
+	if (!c) return fail(SRH_E_INVALID, "null context");
+	if (!c->fuse_valid) return fail(SRH_E_INVALID, "the context holds no fused cloud (no srh_mvs_fuse yet, or the last one failed)");
+	return SRH_OK;
+}
+
+extern "C" int srh_mvs_fused_count(srh_context *c, int64_t *n) {
+	int rc;
+	if ((rc = fuse_result_check(c))) return rc;
+	if (!n) return fail(SRH_E_INVALID, "null n");
+	*n = c->fuse_n;
+	return SRH_OK;
+}
+
+extern "C" int srh_mvs_fused_download(srh_context *c, int64_t first, int64_t count, double *xyz, double *normals, uint8_t *rgb,
+                                      uint8_t *nviews, uint8_t *flags, int32_t *src)
+{
+	int rc;
+	if ((rc = fuse_result_check(c))) return rc;
+	if (first < 0 || count < 0 || first > c->fuse_n || count > c->fuse_n - first)
+		return fail(SRH_E_INVALID, "points [%lld, %lld + %lld) outside [0, %lld]", (long long)first, (long long)first, (long long)count, (long long)c->fuse_n);
+	if (count == 0) return SRH_OK;
+	HIP_TRY(hipSetDevice(c->device));
+	const FuseCloud &o = c->fuse_out;
+	const size_t a = (size_t)first, k = (size_t)count;
+	if (xyz)     HIP_TRY(hipMemcpyAsync(xyz, o.xyz + 3*a, 3*k*sizeof(double), hipMemcpyDeviceToHost, c->stream));
+	if (normals) HIP_TRY(hipMemcpyAsync(normals, o.nrm + 3*a, 3*k*sizeof(double), hipMemcpyDeviceToHost, c->stream));
+	if (rgb)     HIP_TRY(hipMemcpyAsync(rgb, o.rgb + 3*a, 3*k, hipMemcpyDeviceToHost, c->stream));
+	if (nviews)  HIP_TRY(hipMemcpyAsync(nviews, o.nviews + a, k, hipMemcpyDeviceToHost, c->stream));
+	if (flags)   HIP_TRY(hipMemcpyAsync(flags, o.flags + a, k, hipMemcpyDeviceToHost, c->stream));
+	if (src)     HIP_TRY(hipMemcpyAsync(src, o.src + 2*a, 2*k*sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	return SRH_OK;
+}
+
+extern "C" int srh_mvs_fused_device(srh_context *c, void **xyz, void **normals, void **rgb, void **nviews, void **flags, void **src) {
+	int rc;
+	if ((rc = fuse_result_check(c))) return rc;
+	const bool any = c->fuse_n > 0;
+	const FuseCloud &o = c->fuse_out;
+	if (xyz) *xyz = any ? o.xyz : nullptr;
+	if (normals) *normals = any ? o.nrm : nullptr;
+	if (rgb) *rgb = any ? o.rgb : nullptr;
+	if (nviews) *nviews = any ? o.nviews : nullptr;
+	if (flags) *flags = any ? o.flags : nullptr;
+	if (src) *src = any ? (void *)o.src : nullptr;
 	return SRH_OK;
 }
 

@@ -380,6 +380,24 @@ void launch_pair_costs(hipStream_t st, const ViewDev *views, int ref, int oth, c
                        const int32_t *xy, double *out);
 void launch_point_cloud(hipStream_t st, const ViewDev *views, int slot, int w, int h, const srh_params &P,
                         double *xyz, uint8_t *rgb, uint8_t *valid, unsigned long long *counts);
+// depth-map fusion (srh_fuse.hip).  Per entry of the slot list: its point map (3 doubles per pixel, from
+// point_cloud_kernel), the "has a point" bytes and the "claimed by an earlier entry" bytes.
+struct FuseViewDev { const double *pts; const uint8_t *valid; uint8_t *claimed; };
+// one point per element: the staging planes of a view (indexed by pixel) and the compacted result
+struct FuseCloud { double *xyz, *nrm; int32_t *src; uint8_t *rgb, *nviews, *flags; };
+#define SRH_FUSE_BLOCK 256
+// counters: [0] points, [1] claimed, [2] unsupported, [3] normals, [4] running total of emitted points (the scan's base)
+// entry `vi` of the list: every pixel's decision (emit[pixel] = 1: a point goes out) and the point into `stage`, the
+// emitted pixels of every block of SRH_FUSE_BLOCK into block_counts; flags of later entries are claimed
+void launch_fuse_view(hipStream_t st, const ViewDev *views, const int32_t *slots_dev, int nviews, int vi, int w, int h,
+                      const srh_params &P, double thr, double gap, int min_views, const FuseViewDev *fv,
+                      uint8_t *emit, FuseCloud stage, uint32_t *block_counts, unsigned long long *counters);
+// exclusive scan of the block counts on top of counters[4], which then moves on by their sum
+void launch_fuse_scan(hipStream_t st, const uint32_t *block_counts, int nblocks, unsigned long long *block_offs,
+                      unsigned long long *counters);
+// the emitted pixels of every block to block_offs[block] + their rank in the block (wave64 ballots), in pixel order
+void launch_fuse_scatter(hipStream_t st, int vi, size_t npix, const uint8_t *emit, FuseCloud stage,
+                         const unsigned long long *block_offs, FuseCloud out, unsigned long long cap);
 // MRF stage (srh_mrf.hip): one scratch buffer, carved the same way by every launch
 struct MrfLayout {
 	double *pz, *D, *Mh, *Mv, *partial, *energy;

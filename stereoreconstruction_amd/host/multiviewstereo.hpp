@@ -17,6 +17,14 @@
 
 struct PLYPoint { double p[3]; uint8_t rgb[3]; };
 void outputPLYFile(const std::string &path, const std::vector<PLYPoint> &points);   // multiviewstereo.cpp:291-315
+// One point of the fused cloud (srh_mvs_fuse): position, unit normal, colour, the number of views that agree on it, flags
+// (bit 0: the normal comes from the surface, else it points at the camera), and where it comes from: the index of the view
+// in the run and the pixel index y*w + x in that view.
+struct FusedPoint { double p[3], n[3]; uint8_t rgb[3], nviews, flags; int view, pixel; };
+// The same file with normals: the header of the overload above with "property float nx", "ny", "nz" between z and the
+// colours, lines "x y z nx ny nz r g b" -- what the reference's viewer reads (gui/mainwindow.cpp:304-461), which otherwise
+// sets every normal to (0, 0, 1).
+void outputPLYFile(const std::string &path, const std::vector<FusedPoint> &points);
 
 class MultiViewStereo : public Task {
 public:
@@ -66,6 +74,11 @@ public:
 	// The view's current depth map as coloured 3-D points (pixels with a WHITE mask and a finite depth; the point
 	// is the cross-checks' construction, multiviewstereo.cpp:688-692) -- what outputPLYFile takes.
 	std::vector<PLYPoint> pointCloud(CameraPtr view);
+	// The depth maps of all views of the last run, in their order, fused into one oriented cloud (srh_mvs_fuse with
+	// fuseParams(); not in the reference): every surface patch once, with the views that confirm it averaged;
+	// by default (min_views 2) points no second view confirms are left out.  Empty with lastError() set when it fails.
+	std::vector<FusedPoint> fusedPointCloud();
+	srh_fuse_params &fuseParams() { return fuseParams_; }
 	// "percent of pixels have depth hypotheses": finite depths among the masked-in pixels (:402-421)
 	double coverage(CameraPtr view) const;
 	const std::vector<std::vector<int> > &neighbourViews() const { return neighbours; }
@@ -100,6 +113,7 @@ private:
 	int numDepthLevels;
 	srh_params params_;
 	srh_mrf_params mrfParams_;
+	srh_fuse_params fuseParams_;
 	bool useMrf_ = false;
 	srh_context *ctx_;
 	std::string error_;

@@ -51,6 +51,24 @@ void writePLY(const std::string &path, size_t npoints, const double *xyz, const 
 		lout << xyz[i*3] << ' ' << xyz[i*3 + 1] << ' ' << xyz[i*3 + 2] << ' ' << rgb[i*3] << ' ' << rgb[i*3 + 1] << ' ' << rgb[i*3 + 2] << '\n';
 }
 
+} // namespace srq
+
+void outputPLYFile(const std::string &path, const std::vector<FusedPoint> &points) {
+	std::ofstream lout(path.c_str());
+	lout << "ply\n" << "format ascii 1.0\n" << "element vertex " << points.size() << "\n"
+	     << "property float x\n" << "property float y\n" << "property float z\n"
+	     << "property float nx\n" << "property float ny\n" << "property float nz\n"
+	     << "property uchar diffuse_red\n" << "property uchar diffuse_green\n" << "property uchar diffuse_blue\n"
+	     << "end_header\n";
+	for (size_t i = 0; i < points.size(); ++i) {
+		const FusedPoint &pp = points[i];
+		lout << pp.p[0] << ' ' << pp.p[1] << ' ' << pp.p[2] << ' ' << pp.n[0] << ' ' << pp.n[1] << ' ' << pp.n[2] << ' '
+		     << static_cast<int>(pp.rgb[0]) << ' ' << static_cast<int>(pp.rgb[1]) << ' ' << static_cast<int>(pp.rgb[2]) << '\n';
+	}
+}
+
+namespace srq {
+
 std::vector<unsigned char> whiteMask(const Raster &m) {
 	std::vector<unsigned char> out(static_cast<size_t>(m.w)*m.h);
 	for (size_t i = 0; i < out.size(); ++i) {
@@ -285,6 +303,7 @@ MultiViewStereo::MultiViewStereo()
 	const int deviceOrdinal = g_device;
 	srh_params_mvs_defaults(&params_);
 	srh_mrf_params_defaults(&mrfParams_);
+	srh_fuse_params_defaults(&fuseParams_);
 	if (srh_create(deviceOrdinal, &ctx_) != SRH_OK) { error_ = srh_last_error(); ctx_ = nullptr; }
 }
 
@@ -392,6 +411,38 @@ void MultiViewStereo::runTask() {
 		if (srh_view_depth_download(ctx_, v, computedDepths[v].data()) != SRH_OK) { error_ = srh_last_error(); return; }
 	emit stageUpdate(tr("Constructing depth maps"));
 	for (int v = 0; v < V; ++v) colorize(v);
+}
+
+std::vector<FusedPoint> MultiViewStereo::fusedPointCloud() {
+	std::vector<FusedPoint> pts;
+	const int V = static_cast<int>(views_.size());
+	if (!ctx_ || V == 0) return pts;
+	params_.min_depth = minDepth; params_.max_depth = maxDepth; params_.num_depth_levels = numDepthLevels;
+	params_.image_scale = imageScale; params_.cross_check_threshold = crossCheckThreshold;
+	std::vector<int32_t> slotIds(V);
+	for (int v = 0; v < V; ++v) {
+		slotIds[v] = v;
+		if (srh_view_depth_upload(ctx_, v, computedDepths[v].data()) != SRH_OK) { error_ = srh_last_error(); return pts; }
+	}
+	int64_t n = 0;
+	if (srh_mvs_fuse(ctx_, slotIds.data(), V, &params_, &fuseParams_, nullptr) != SRH_OK ||
+	    srh_mvs_fused_count(ctx_, &n) != SRH_OK) { error_ = srh_last_error(); return pts; }
+	const size_t k = static_cast<size_t>(n);
+	std::vector<double> xyz(3*k), nrm(3*k);
+	std::vector<unsigned char> rgb(3*k), nviews(k), flags(k);
+	std::vector<int32_t> src(2*k);
+	if (srh_mvs_fused_download(ctx_, 0, n, xyz.data(), nrm.data(), rgb.data(), nviews.data(), flags.data(), src.data()) != SRH_OK) {
+		error_ = srh_last_error();
+		return pts;
+	}
+	pts.resize(k);
+	for (size_t i = 0; i < k; ++i) {
+		FusedPoint &q = pts[i];
+		for (int c = 0; c < 3; ++c) { q.p[c] = xyz[3*i + c]; q.n[c] = nrm[3*i + c]; q.rgb[c] = rgb[3*i + c]; }
+		q.nviews = nviews[i]; q.flags = flags[i];
+		q.view = src[2*i]; q.pixel = src[2*i + 1];
+	}
+	return pts;
 }
 
 QImage MultiViewStereo::depthMap(CameraPtr view) const {

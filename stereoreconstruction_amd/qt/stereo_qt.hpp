@@ -47,6 +47,13 @@ typedef std::pair<Eigen::Vector3d, RGBA> PLYPoint;
 //! Output a set of points to a PLY file
 void outputPLYFile(const std::string &path, const std::vector<PLYPoint> &points);
 
+// One point of the fused cloud (srh_mvs_fuse; not in the reference): position, unit normal, colour, the number
+// of views that agree on it, flags (bit 0: the normal comes from the surface), the view's index in the run and the pixel.
+struct FusedPoint { double p[3], n[3]; unsigned char rgb[3], nviews, flags; int view, pixel; };
+// the PLY file with normals ("x y z nx ny nz r g b", the properties nx, ny, nz between z and the colours): what the
+// reference's viewer reads (gui/mainwindow.cpp:304-461)
+void outputPLYFile(const std::string &path, const std::vector<FusedPoint> &points);
+
 namespace srq {
 
 // the text outputPLYFile writes (multiviewstereo.cpp:291-315): ASCII header, then "x y z r g b" per point through
@@ -226,6 +233,9 @@ public:
 	// CONFIG+=mrf of the reference (USE_MRF, StereoReconstruction.pro:100-103) as a run-time switch; off by default
 	void setUseMRF(bool on) { useMrf_ = on; }
 	srh_mrf_params &mrfParams() { return mrfParams_; }
+	// the depth maps of the last run's views, in their order, fused into one oriented cloud (srh_mvs_fuse with fuseParams())
+	std::vector<FusedPoint> fusedPointCloud();
+	srh_fuse_params &fuseParams() { return fuseParams_; }
 	QString lastError() const { return error_; }
 
 protected:
@@ -244,6 +254,7 @@ private:
 	int numDepthLevels;
 	srh_params params_;
 	srh_mrf_params mrfParams_;
+	srh_fuse_params fuseParams_;
 	bool useMrf_ = false;
 	srh_context *ctx_;
 	QString error_;
