@@ -92,7 +92,8 @@ def fuse(ocams, op, rgbas, masks, depths, thr, gap=None, min_views=2, maps=None)
     """The rule of srh_mvs_fuse over the views in the order given (the slot list).  -> dict with the output arrays (xyz,
     normals, rgb, nviews, flags, src), the info counters, `claimed` (list of (h, w) bool), and the margins the tests
     ask about: member_margin = min |nrm - thr| / thr over every member test made, orient_margin = min
-    |dot(n, C - P)| / (|n| |C - P|) over every orientation test made."""
+    |dot(n, C - P)| / (|n| |C - P|) over every orientation test made, gap_margin = min ||depth' - depth| - gap| / gap over
+    every usable-neighbour test made (a neighbour inside the image that has a point)."""
     n = len(ocams)
     if gap is None:
         gap = default_gap(op)
@@ -103,7 +104,7 @@ def fuse(ocams, op, rgbas, masks, depths, thr, gap=None, min_views=2, maps=None)
     claimed = [np.zeros(m[1].shape, dtype=bool) for m in maps]
     xyz, nrm, rgb, nvw, flg, src = [], [], [], [], [], []
     n_claimed = n_unsup = n_normals = 0
-    member_margin = orient_margin = math.inf
+    member_margin = orient_margin = gap_margin = math.inf
     q = np.zeros(3)
     for v in range(n):
         pts, valid = maps[v]
@@ -157,7 +158,12 @@ def fuse(ocams, op, rgbas, masks, depths, thr, gap=None, min_views=2, maps=None)
             depth = float(depths[v][y, x])
 
             def usable(yy, xx):
-                return 0 <= xx < w and 0 <= yy < h and bool(valid[yy, xx]) and abs(float(depths[v][yy, xx]) - depth) <= gap
+                nonlocal gap_margin
+                if not (0 <= xx < w and 0 <= yy < h and bool(valid[yy, xx])):
+                    return False
+                dd = abs(float(depths[v][yy, xx]) - depth)
+                gap_margin = min(gap_margin, abs(dd - gap) / gap)
+                return dd <= gap
 
             def tangent(lo, hi):
                 lo_ok, hi_ok = usable(*lo), usable(*hi)
@@ -197,7 +203,8 @@ def fuse(ocams, op, rgbas, masks, depths, thr, gap=None, min_views=2, maps=None)
         rgb=np.array(rgb, dtype=np.uint8).reshape(k, 3), nviews=np.array(nvw, dtype=np.uint8),
         flags=np.array(flg, dtype=np.uint8), src=np.array(src, dtype=np.int32).reshape(k, 2),
         n_points=k, n_candidates=int(sum(int(m[1].sum()) for m in maps)), n_claimed=n_claimed, n_unsupported=n_unsup,
-        n_normals=n_normals, claimed=claimed, member_margin=member_margin, orient_margin=orient_margin)
+        n_normals=n_normals, claimed=claimed, member_margin=member_margin, orient_margin=orient_margin,
+        gap_margin=gap_margin)
 
 
 # ---------------------------------------------------------------- the inputs the GPU tests and the host tests share
@@ -205,17 +212,28 @@ def fuse(ocams, op, rgbas, masks, depths, thr, gap=None, min_views=2, maps=None)
 # (case name, threshold as a multiple of the pixel footprint at the sphere's centre: depth / focal length)
 FUSE_CASES = ["mvs_geodesic", "mvs_distorted", "mvs_refractive", "mvs_mixed_sizes", "mvs_scaled"]
 THRESHOLD_FOOTPRINTS = 0.75
+# the full rule at sizes that cross the boundaries of fuse_scan_kernel (256 threads, thread t sums a run of `per` blocks
+# of 256 pixels): 304x216 is 257 blocks, per 2; 432x304 is 513 blocks, per 3; the last run is ragged in both
+FUSE_SIZE_CASES = [("mvs_distorted", dict(nviews=2, w=304, h=216)), ("mvs_geodesic", dict(nviews=2, w=432, h=304))]
+# srh_fuse_params.normal_depth_gap as the default gap divided by these (mvs_geodesic)
+GAP_FRACTIONS = [4, 12]
+# mvs_mixed_sizes with the largest view (view 0) not first: at the default size (9, 7 and 7 blocks) and at 120x80,
+# 112x76, 104x80 (38, 34 and 33 blocks) in ascending size and with the largest in the middle
+MIXED_ORDERS = [({}, (2, 1, 0)), ({}, (1, 2, 0)), ({}, (1, 0, 2)),
+                (dict(w=120, h=80), (2, 1, 0)), (dict(w=120, h=80), (1, 0, 2))]
 
 _inputs = {}
 
 
-def case_inputs(name):
-    """-> dict(case, ocams, op, rgbas, masks, depths, thr): tests/cases.py's scene `name` with analytic, hole-punched depth
-    maps and a threshold of THRESHOLD_FOOTPRINTS pixel footprints.  Computed once per process."""
-    if name in _inputs:
-        return _inputs[name]
+def case_inputs(name, **over):
+    """-> dict(case, ocams, op, rgbas, masks, depths, thr): tests/cases.py's scene `name` (`over`: get_mvs's overrides, such
+    as w, h, nviews) with analytic, hole-punched depth maps and a threshold of THRESHOLD_FOOTPRINTS pixel footprints.
+    Computed once per process."""
+    key = (name, tuple(sorted(over.items())))
+    if key in _inputs:
+        return _inputs[key]
     import cases
-    case = cases.get_mvs(name)
+    case = cases.get_mvs(name, **over)
     imgs, ocams, op = cases.oracle_inputs(case)
     rgbas = [v[0] for v in case["views"]]
     masks = [v[1] for v in case["views"]]
@@ -226,21 +244,234 @@ def case_inputs(name):
     # footprint of a pixel of the images handed over, at the distance of the sphere's centre
     focal = float(case["views"][0][2][0][0, 0]) * op.image_scale
     thr = THRESHOLD_FOOTPRINTS * 10.0 / focal
-    _inputs[name] = dict(case=case, ocams=ocams, op=op, rgbas=rgbas, masks=masks, depths=depths, thr=thr)
-    return _inputs[name]
+    _inputs[key] = dict(case=case, ocams=ocams, op=op, rgbas=rgbas, masks=masks, depths=depths, thr=thr)
+    return _inputs[key]
 
 
 _results = {}
 
 
-def case_result(name, order=None, min_views=2):
-    """fuse() on case_inputs(name) with the views listed in `order` (default: as they are); cached."""
-    I = case_inputs(name)
+def case_result(name, order=None, min_views=2, gap=None, **over):
+    """fuse() on case_inputs(name, **over) with the views listed in `order` (default: as they are); cached."""
+    I = case_inputs(name, **over)
     n = len(I["ocams"])
     order = tuple(range(n)) if order is None else tuple(order)
-    key = (name, order, min_views)
+    key = (name, tuple(sorted(over.items())), order, min_views, gap)
     if key not in _results:
         pick = lambda a: [a[v] for v in order]
         _results[key] = fuse(pick(I["ocams"]), I["op"], pick(I["rgbas"]), pick(I["masks"]), pick(I["depths"]), I["thr"],
-                             min_views=min_views)
+                             gap=gap, min_views=min_views)
     return _results[key]
+
+
+# ---------------------------------------------------------------- the compaction alone: inputs with a closed-form cloud
+#
+# Every slot holds the SAME pinhole camera and the same smooth depth map, with its own image and its own set of holes (NaN
+# depths).  A pixel's point then projects into its own pixel of every other slot (tests/test_fuse_host.py checks that with
+# the oracle, with a quarter of a pixel to spare) and meets the very same bits there, so the members of a pixel are the
+# slots in which it has a point, its owner is the first of them, and the whole cloud follows from the validity planes in
+# numpy: no per-pixel Python.  The holes are laid out by blocks of FUSE_BLOCK pixels, the unit of fuse_scan_kernel and
+# fuse_scatter_kernel, at sizes on the scan's boundaries.
+
+FUSE_BLOCK = 256                                        # SRH_FUSE_BLOCK (test_fuse_host.py reads it from csrc/srh_internal.hpp)
+COMPACTION_SIZES = [(256, 256), (257, 256), (363, 362)]  # 256 blocks, per 1 | 257 blocks, per 2 | 514 blocks, per 3, ragged
+TWIN_SIZE = (257, 256)
+MANY_SIZE, MANY_VIEWS = (16, 16), 64
+COMPACTION_GAP = 100.0                                  # beyond any depth difference: only validity decides a tangent
+COMPACTION_THR = 1e-3                                   # the members' distance is exactly 0
+
+
+def scan_layout(npix):
+    """-> (blocks, blocks per run of one thread of fuse_scan_kernel, runs that hold a block)."""
+    nb = (npix + FUSE_BLOCK - 1) // FUSE_BLOCK
+    per = (nb + FUSE_BLOCK - 1) // FUSE_BLOCK
+    return nb, per, (nb + per - 1) // per
+
+
+def where_in_scan(pixel, npix):
+    """'block b, run t, wave k' of a pixel, for assertion messages."""
+    _, per, _ = scan_layout(npix)
+    b = int(pixel) // FUSE_BLOCK
+    return "pixel %d: block %d, run %d, wave %d" % (pixel, b, b // per, b // per // 64)
+
+
+def hole_pattern(w, h, seed, empty_wave=1):
+    """(h, w) bool, True where the pixel keeps its depth.  Blocks are full, empty, half filled or nearly empty at random;
+    block 0 is empty, block 1 full, block 2 half filled; the 64 runs of wave `empty_wave` of the scan are empty (None: no
+    such wave); the last block, ragged where w*h is no multiple of FUSE_BLOCK, is half filled and not empty."""
+    npix = w * h
+    nb, per, _ = scan_layout(npix)
+    rng = np.random.default_rng(seed)
+    density = np.array([1.0, 0.0, 0.5, 0.02])[rng.integers(0, 4, nb)]
+    r = rng.random((nb, FUSE_BLOCK))
+    blocks = r < density[:, None]
+    blocks[0] = False
+    blocks[1] = True
+    blocks[2] = r[2] < 0.5
+    if empty_wave is not None:
+        blocks[64 * per * empty_wave:64 * per * (empty_wave + 1)] = False
+    blocks[nb - 1] = r[nb - 1] < 0.5
+    blocks[nb - 1, 3] = True
+    return blocks.ravel()[:npix].reshape(h, w).copy()
+
+
+def block_counts(valid_flat):
+    """Points per block of FUSE_BLOCK pixels (the last block padded with zeros)."""
+    nb = (valid_flat.size + FUSE_BLOCK - 1) // FUSE_BLOCK
+    padded = np.zeros(nb * FUSE_BLOCK, dtype=np.int64)
+    padded[:valid_flat.size] = valid_flat
+    return padded.reshape(nb, FUSE_BLOCK).sum(1)
+
+
+_compaction = {}
+
+
+def compaction_inputs(kind, w, h):
+    """kind "twin": two slots, the first with hole_pattern(seed 1, the scan's wave 1 empty), the second with another image
+    and hole_pattern(seed 2, no empty wave); "many": MANY_VIEWS slots without holes.  -> dict(case, ocams, op, rgbas,
+    masks, depth (the shared map, no holes), valids, depths (with the holes), C); cached."""
+    key = (kind, w, h)
+    if key in _compaction:
+        return _compaction[key]
+    import cases
+    from stereoreconstruction_amd import synthetic as S
+    K, R, t = S.semicircle_rig(1, w, h, radius=10.0, focal=1.4 * w)[0]
+    ys, xs = np.mgrid[0:h, 0:w]
+    depth = 9.0 + 0.9 * np.sin(1.5 * 2 * np.pi * (xs + 0.5) / w) * np.cos(2 * np.pi * (ys + 0.5) / h)
+    if kind == "twin":
+        valids = [hole_pattern(w, h, 1, 1), hole_pattern(w, h, 2, None)]
+    elif kind == "many":
+        valids = [np.ones((h, w), dtype=bool)] * MANY_VIEWS
+    else:
+        raise ValueError(kind)
+    n = len(valids)
+    rng = np.random.default_rng(1000 * w + h + n)
+    rgbas = []
+    for _ in range(n):
+        im = rng.integers(0, 256, (h, w, 4), dtype=np.uint8)
+        im[..., 3] = 255
+        rgbas.append(im)
+    masks = [np.ones((h, w), dtype=np.uint8) for _ in range(n)]
+    views = [(rgbas[v], masks[v], (K, R, t), None, None) for v in range(n)]
+    params = dict(min_depth=7.5, max_depth=10.5, num_depth_levels=24, window_radius=2, weight_kind=1, image_scale=1.0,
+                  cross_check_threshold=0.25)
+    case = dict(name="compaction_" + kind, kind="mvs", views=views, params=params)
+    _, ocams, op = cases.oracle_inputs(case)
+    assert depth.min() >= op.min_depth and depth.max() <= op.max_depth
+    _compaction[key] = dict(case=case, ocams=ocams, op=op, rgbas=rgbas, masks=masks, depth=depth, valids=valids,
+                            depths=[np.where(v, depth, np.nan) for v in valids], C=np.array(ocams[0].C[:]))
+    return _compaction[key]
+
+
+def _shift(a, dy, dx, fill):
+    """b[y, x] = a[y + dy, x + dx], `fill` outside."""
+    h, w = a.shape[:2]
+    b = np.full_like(a, fill)
+    ys, yd = (slice(dy, h), slice(0, h - dy)) if dy >= 0 else (slice(0, h + dy), slice(-dy, h))
+    xs, xd = (slice(dx, w), slice(0, w - dx)) if dx >= 0 else (slice(0, w + dx), slice(-dx, w))
+    b[yd, xd] = a[ys, xs]
+    return b
+
+
+def _norm(a):
+    return np.sqrt((a[..., 0] * a[..., 0] + a[..., 1] * a[..., 1]) + a[..., 2] * a[..., 2])
+
+
+def tangent_normals(pts, valid, C):
+    """fuse_view_kernel's normal for every pixel of a view whose neighbours are usable exactly where they have a point:
+    pts (h, w, 3), valid (h, w) bool, C the camera centre -> (normals (h, w, 3), flags (h, w) uint8, orientation margin
+    over the pixels with a point).  Garbage where valid is False."""
+    with np.errstate(all="ignore"):
+        ok = {k: _shift(valid, dy, dx, False) for k, (dy, dx) in dict(l=(0, -1), r=(0, 1), u=(-1, 0), d=(1, 0)).items()}
+        pt = {k: _shift(pts, dy, dx, np.nan) for k, (dy, dx) in dict(l=(0, -1), r=(0, 1), u=(-1, 0), d=(1, 0)).items()}
+
+        def tangent(lo, hi):
+            both, only_hi = (ok[lo] & ok[hi])[..., None], ok[hi][..., None]
+            return np.where(both, pt[hi] - pt[lo], np.where(only_hi, pt[hi] - pts, pts - pt[lo])), ok[lo] | ok[hi]
+        th, have_h = tangent("l", "r")
+        tv, have_v = tangent("u", "d")
+        cr = np.stack([th[..., 1] * tv[..., 2] - th[..., 2] * tv[..., 1], th[..., 2] * tv[..., 0] - th[..., 0] * tv[..., 2],
+                       th[..., 0] * tv[..., 1] - th[..., 1] * tv[..., 0]], axis=-1)
+        ln = _norm(cr)
+        has = have_h & have_v & np.isfinite(ln) & (ln > 0)
+        nv = cr / ln[..., None]
+        to_cam = C[None, None, :] - pts
+        d = (nv[..., 0] * to_cam[..., 0] + nv[..., 1] * to_cam[..., 1]) + nv[..., 2] * to_cam[..., 2]
+        margin = np.abs(d) / (_norm(nv) * _norm(to_cam))
+        nv = np.where((d < 0)[..., None], -nv, nv)
+        nv = np.where(has[..., None], nv, to_cam / _norm(to_cam)[..., None])
+    sel = has & valid
+    return nv, has.astype(np.uint8), (float(margin[sel].min()) if sel.any() else math.inf)
+
+
+def same_camera_cloud(pts, valids, rgbas, C, min_views):
+    """The fused cloud of slots that share camera and depth map (see above), in numpy: pts (h, w, 3) the point of every
+    pixel, valids / rgbas per slot.  -> the dict of fuse(), without `claimed` and the member and gap margins."""
+    n = len(valids)
+    V = np.stack([v.ravel() for v in valids])
+    P = pts.reshape(-1, 3)
+    m = V.sum(0)
+    first = V.argmax(0)
+    acc = np.zeros_like(P)
+    started = np.zeros(P.shape[0], dtype=bool)
+    col = np.zeros((P.shape[0], 3), dtype=np.int64)
+    with np.errstate(all="ignore"):
+        for u in range(n):
+            acc = np.where(V[u][:, None], np.where(started[:, None], acc + P, P), acc)
+            started |= V[u]
+            col += V[u][:, None] * rgbas[u].reshape(-1, 4)[:, :3].astype(np.int64)
+        mean = acc / m[:, None].astype(np.float64)
+        mm = np.maximum(m, 1)[:, None]
+        colour = ((2 * col + mm) // (2 * mm)).astype(np.uint8)
+    out = {k: [] for k in ("xyz", "normals", "rgb", "nviews", "flags", "src")}
+    orient_margin = math.inf
+    for v in range(n):
+        idx = np.flatnonzero(V[v] & (first == v) & (m >= min_views))
+        if idx.size == 0 and not V[v].any():
+            continue
+        nrm, flg, margin = tangent_normals(pts, valids[v], C)
+        orient_margin = min(orient_margin, margin)
+        out["xyz"].append(mean[idx])
+        out["normals"].append(nrm.reshape(-1, 3)[idx])
+        out["rgb"].append(colour[idx])
+        out["nviews"].append(m[idx].astype(np.uint8))
+        out["flags"].append(flg.ravel()[idx])
+        out["src"].append(np.stack([np.full(idx.size, v), idx], axis=1).astype(np.int32))
+    empty = dict(xyz=np.zeros((0, 3)), normals=np.zeros((0, 3)), rgb=np.zeros((0, 3), np.uint8), nviews=np.zeros(0, np.uint8),
+                 flags=np.zeros(0, np.uint8), src=np.zeros((0, 2), np.int32))
+    out = {k: (np.concatenate(a) if a else empty[k]) for k, a in out.items()}
+    supported = m >= min_views
+    out.update(n_points=int(out["src"].shape[0]), n_candidates=int(V.sum()), n_claimed=int((m[supported] - 1).sum()),
+               n_unsupported=int(m[~supported].sum()), n_normals=int(out["flags"].sum()), orient_margin=orient_margin)
+    return out
+
+
+# ---------------------------------------------------------------- the comparison of the GPU tests
+
+COUNTERS = ("n_points", "n_candidates", "n_claimed", "n_unsupported", "n_normals")
+
+
+def _first_difference(got, want, bad, npix):
+    """Where the clouds first differ: the output position and, from the source the restatement expects there, the block
+    of SRH_FUSE_BLOCK pixels, the scan's run and its wave (npix: the pixels of every list entry, or None)."""
+    bad = bad.reshape(bad.shape[0], -1).any(axis=1)
+    k = int(np.flatnonzero(bad)[0])
+    v, i = (int(q) for q in want["src"][k])
+    msg = "first at output position %d of %d (%d positions differ): expected source entry %d" % (k, bad.size, int(bad.sum()), v)
+    msg += ", " + (where_in_scan(i, npix[v]) if npix is not None else "pixel %d" % i)
+    return msg + "; the device has source (%d, %d) there" % tuple(int(q) for q in got["src"][k])
+
+
+def assert_equal(got, want, tag="", npix=None):
+    for k in COUNTERS:
+        assert got[k] == want[k], "%s %s: %d != %d" % (tag, k, got[k], want[k])
+    assert got["normals"].shape == want["normals"].shape
+    for k in ("src", "nviews", "flags", "rgb"):
+        assert got[k].shape == want[k].shape, "%s %s" % (tag, k)
+        bad = got[k] != want[k]
+        assert not bad.any(), "%s %s: %s" % (tag, k, _first_difference(got, want, bad, npix))
+    bad = got["xyz"].view(np.uint64) != want["xyz"].view(np.uint64)
+    assert not bad.any(), "%s xyz bits: %s" % (tag, _first_difference(got, want, bad, npix))
+    if want["n_points"]:
+        bad = ~(np.abs(got["normals"] - want["normals"]) <= 1e-12)
+        assert not bad.any(), "%s normals: %s" % (tag, _first_difference(got, want, bad, npix))

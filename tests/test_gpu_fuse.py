@@ -32,25 +32,24 @@ def _upload(ctx, I, order=None, depths=None):
     return p
 
 
-def _assert_equal(got, want, tag=""):
-    for k in COUNTERS:
-        assert got[k] == want[k], "%s %s: %d != %d" % (tag, k, got[k], want[k])
-    for k in ("src", "nviews", "flags", "rgb"):
-        assert np.array_equal(got[k], want[k]), "%s %s" % (tag, k)
-    assert np.array_equal(got["xyz"].view(np.uint64), want["xyz"].view(np.uint64)), tag + " xyz bits"
-    assert got["normals"].shape == want["normals"].shape
-    if want["n_points"]:
-        assert np.abs(got["normals"] - want["normals"]).max() <= 1e-12, tag + " normals"
+_assert_equal = F.assert_equal
 
 
-@pytest.mark.parametrize("name", F.FUSE_CASES)
-def test_fusion_equals_the_restatement(hip_ctx, name):
-    I = F.case_inputs(name)
-    want = F.case_result(name)
+def _npix(I, order=None):
+    n = [m.size for m in I["masks"]]
+    return n if order is None else [n[v] for v in order]
+
+
+@pytest.mark.parametrize("name,over", [pytest.param(name, {}, id=name) for name in F.FUSE_CASES]
+                         + [pytest.param(name, over, id="%s-%dx%dx%d" % (name, over["nviews"], over["w"], over["h"]))
+                            for name, over in F.FUSE_SIZE_CASES])
+def test_fusion_equals_the_restatement(hip_ctx, name, over):
+    I = F.case_inputs(name, **over)
+    want = F.case_result(name, **over)
     p = _upload(hip_ctx, I)
     n = len(I["ocams"])
     got = hip_ctx.mvs_fuse(list(range(n)), p, capi.fuse_params(dist_threshold=I["thr"]))
-    _assert_equal(got, want, name)
+    _assert_equal(got, want, name, _npix(I))
     assert got["n_candidates"] == got["n_points"] + got["n_claimed"] + got["n_unsupported"]
     assert hip_ctx.mvs_fused_count() == want["n_points"]
 
@@ -64,6 +63,46 @@ def test_list_order_and_slots(hip_ctx):
     p = _upload(hip_ctx, I)
     got = hip_ctx.mvs_fuse(rev, p, capi.fuse_params(dist_threshold=I["thr"]))
     _assert_equal(got, F.case_result(name, order=rev), "reversed")
+
+
+@pytest.mark.parametrize("min_views", [3, 4])
+def test_more_than_two_views_required(hip_ctx, min_views):
+    name = "mvs_geodesic"
+    I = F.case_inputs(name)
+    n = len(I["ocams"])
+    assert n == 4
+    want = F.case_result(name, min_views=min_views)
+    p = _upload(hip_ctx, I)
+    got = hip_ctx.mvs_fuse(list(range(n)), p, capi.fuse_params(dist_threshold=I["thr"], min_views=min_views))
+    _assert_equal(got, want, "min_views %d" % min_views, _npix(I))
+    assert got["n_points"] > 0 and got["nviews"].min() >= min_views and got["nviews"].max() == n
+
+
+@pytest.mark.parametrize("fraction", F.GAP_FRACTIONS)
+def test_explicit_normal_depth_gap(hip_ctx, fraction):
+    """srh_fuse_params.normal_depth_gap below the default: fewer neighbours are usable, fewer points have a tangent."""
+    name = "mvs_geodesic"
+    I = F.case_inputs(name)
+    n = len(I["ocams"])
+    gap = F.default_gap(I["op"]) / fraction
+    want = F.case_result(name, gap=gap)
+    p = _upload(hip_ctx, I)
+    got = hip_ctx.mvs_fuse(list(range(n)), p, capi.fuse_params(dist_threshold=I["thr"], normal_depth_gap=gap))
+    _assert_equal(got, want, "gap 1/%d of the default" % fraction, _npix(I))
+    assert 0 < got["n_normals"] < F.case_result(name)["n_normals"]
+
+
+@pytest.mark.parametrize("over,order", F.MIXED_ORDERS, ids=[
+    "%s-%d%d%d" % (("%dx%d" % (o["w"], o["h"]) if o else "default",) + tuple(q)) for o, q in F.MIXED_ORDERS])
+def test_largest_view_not_first(hip_ctx, over, order):
+    """Lists whose first entry is not the largest view: the scratch is sized by the largest (pixels and blocks), and a short
+    view's scan runs over a block_counts array that still holds a longer view's counts behind its own."""
+    name = "mvs_mixed_sizes"
+    I = F.case_inputs(name, **over)
+    want = F.case_result(name, order=order, **over)
+    p = _upload(hip_ctx, I)                                            # view v in slot v; the list gives the order
+    got = hip_ctx.mvs_fuse(list(order), p, capi.fuse_params(dist_threshold=I["thr"]))
+    _assert_equal(got, want, "order %s" % (order,), _npix(I, order))
 
 
 def test_single_view_is_the_views_own_cloud(hip_ctx):

@@ -62,8 +62,10 @@ def test_premultiply_every_channel_alpha_pair(hip_ctx):
 
 # 333x251 at 0.41: a ragged tile edge in both axes; 1175x881 at 0.3: a shape whose fast-scaled rows an integer step misplaces;
 # 17x9 at 0.6: a target smaller than a tile; 300x200 at 0.2: a target exactly one tile wide (60 columns of the 64);
-# 2600x45 at 0.025: a tile whose source rows and columns go by in several chunks and staged pieces
-@pytest.mark.parametrize("w,h,scale", [(333, 251, 0.41), (1175, 881, 0.3), (17, 9, 0.6), (300, 200, 0.2), (2600, 45, 0.025)])
+# 2600x45 at 0.025: a tile whose source rows and columns go by in several chunks and staged pieces; 4200x6 at 0.5: a target
+# of 2100 columns, so that the fast scale with alpha re-places its columns once, at target column 2048
+@pytest.mark.parametrize("w,h,scale", [(333, 251, 0.41), (1175, 881, 0.3), (17, 9, 0.6), (300, 200, 0.2), (2600, 45, 0.025),
+                                       (4200, 6, 0.5)])
 def test_shapes_against_restatement(hip_ctx, w, h, scale):
     rng = np.random.default_rng(w*1000 + h)
     src = rng.integers(0, 256, (h, w, 4), dtype=np.uint8)
