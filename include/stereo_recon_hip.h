@@ -39,6 +39,11 @@ enum {
 
 enum { SRH_WEIGHT_ADAPTIVE = 0, SRH_WEIGHT_GEODESIC = 1 };
 enum { SRH_MAX_VIEWS = 64 };
+/* The largest width and the largest height of a view.  srh_view_upload and srh_view_upload_scaled (by the scaled size)
+ * refuse anything larger with SRH_E_UNSUPPORTED before they allocate or launch, and leave the slot as it was.  It is the
+ * smallest per-kernel limit of DESIGN.md 4h (the row-run lists keep columns and row origins as 16-bit signed numbers):
+ * whatever upload accepts, every path computes what the reference computes. */
+#define SRH_MAX_VIEW_DIM 32767
 
 /* Snapshot of a reference `Camera` (project/camera.hpp:168-185): the adapter
  * copies these at TwoViewStereo construction / MultiViewStereo::initialize so the
@@ -256,7 +261,8 @@ int  srh_set_option(srh_context *ctx, const char *name, long value);
 
 /* ---- views: what VectorImage::fromQImage + the mask test hold (util/vectorimage.cpp:48-64) ----
  * rgba: w*h*4 bytes R,G,B,A of the ALREADY SCALED image; mask: w*h bytes,
- * 1 <=> mask.pixel(x,y)==WHITE, NULL = all WHITE.  Host pointers; copied. */
+ * 1 <=> mask.pixel(x,y)==WHITE, NULL = all WHITE.  Host pointers; copied.
+ * w or h above SRH_MAX_VIEW_DIM: SRH_E_UNSUPPORTED, the slot keeps what it held. */
 int  srh_view_upload(srh_context *ctx, int slot, int w, int h,
                      const uint8_t *rgba, const uint8_t *mask, const srh_camera *cam);
 int  srh_view_size(srh_context *ctx, int slot, int *w, int *h);

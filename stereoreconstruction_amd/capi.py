@@ -17,6 +17,7 @@ SRH_OK = 0
 SRH_E_INVALID, SRH_E_DEVICE, SRH_E_NO_DEVICE, SRH_E_CANCELLED, SRH_E_UNSUPPORTED = -1, -2, -3, -4, -5
 WEIGHT_ADAPTIVE, WEIGHT_GEODESIC = 0, 1
 MAX_VIEWS = 64
+MAX_VIEW_DIM = 32767              # SRH_MAX_VIEW_DIM: the largest width / height upload accepts
 
 c_double_p = C.POINTER(C.c_double)
 c_int32_p = C.POINTER(C.c_int32)

@@ -851,6 +851,8 @@ static int view_install(srh_context *c, int slot, int w, int h, const void *rgba
 {
 	if (w <= 0 || h <= 0 || (size_t)w*h > ((size_t)1 << 30)) return fail(SRH_E_INVALID, "bad image size %dx%d", w, h);
 	if (!rgba || !cam) return fail(SRH_E_INVALID, "null rgba / camera");
+	// (before anything is allocated or launched: the slot keeps what it held)
+	if (w > SRH_MAX_VIEW_DIM || h > SRH_MAX_VIEW_DIM) return fail(SRH_E_UNSUPPORTED, "view of %dx%d: a side above %d (SRH_MAX_VIEW_DIM)", w, h, SRH_MAX_VIEW_DIM);
 	HIP_TRY(hipSetDevice(c->device));
 	ViewHost &v = c->views[slot];
 	const size_t n = (size_t)w*h;
@@ -1004,6 +1006,8 @@ extern "C" int srh_view_upload_scaled(srh_context *c, int slot, int src_w, int s
 	// every refusal of a shape comes before the slot is touched
 	int dw = 0, dh = 0, mw = 0, mh = 0;
 	if ((rc = srh_scaled_size(src_w, src_h, image_scale, SRH_SCALE_SMOOTH, &dw, &dh))) return rc;
+	if (dw > SRH_MAX_VIEW_DIM || dh > SRH_MAX_VIEW_DIM)
+		return fail(SRH_E_UNSUPPORTED, "%dx%d at scale %g: a view of %dx%d, a side above %d (SRH_MAX_VIEW_DIM)", src_w, src_h, image_scale, dw, dh, SRH_MAX_VIEW_DIM);
 	const bool alpha_mask = mask_rule == SRH_MASK_ALPHA_FAST && has_alpha;
 	const bool image_mask = mask_rule == SRH_MASK_IMAGE_SMOOTH && mask_rgba;
 	if (alpha_mask && (rc = srh_scaled_size(src_w, src_h, image_scale, SRH_SCALE_FAST, &mw, &mh))) return rc;
