@@ -109,6 +109,9 @@ typedef struct srh_stats {
 	/* last TwoView pass on the dense path: 64-pixel tiles whose pixels all verified the pass's candidate template and were
 	 * scanned over it (twoview_tscan_kernel) / tiles left to the per-pixel curve walk (twoview_scan_kernel) */
 	int64_t scan_tiles_template, scan_tiles_walked;
+	/* of scan_tiles_template: tiles whose pixels were all settled by the per-pixel bound (option "tscan_bound", DESIGN.md
+	 * 2d), without the label-by-label verification */
+	int64_t scan_tiles_bound;
 } srh_stats;
 
 typedef struct srh_context srh_context;
@@ -156,6 +159,20 @@ typedef struct srh_cert_info {
 } srh_cert_info;
 int    srh_cert_bound(const srh_params *p, int mvs, srh_cert_info *out);
 double srh_cert_sigma3(const srh_params *p, int mvs, double sum2);
+/* The template scan's per-pixel bound (option "tscan_bound"), host arithmetic only, for pixel (x, y) of the
+ * reference view against the template pixel (tx, ty) (the scan takes the middle of the view's row band):
+ * |x2(x, y, d) - x2(tx, ty, d) - (x - tx)| <= E for every label d, x2 the reference's projection of label d into the other
+ * view; eU / eU_template: the bound of either pixel's fast form against the reference's arithmetic; dyU: any two labels'
+ * y2 differ by at most that; room_col / room_one / room_proj: the smallest room of the template pixel's column, one-pixel
+ * and projectability decisions; pixel_ok / template_ok: the pixel's / the template's own conditions hold; passes: the
+ * pixel's candidate list is certainly the template's. */
+typedef struct srh_tscan_bound_info {
+	double E, eU, eU_template, dyU;
+	double room_col, room_one, room_proj;
+	int32_t pixel_ok, template_ok, passes, pad_;
+} srh_tscan_bound_info;
+int    srh_tscan_bound(const srh_camera *refcam, const srh_camera *othcam, const srh_params *p,
+                       int tx, int ty, int x, int y, srh_tscan_bound_info *out);
 /* MultiViewStereo::runTask neighbour selection (multiviewstereo.cpp:335-360):
  * neigh[v*p->num_neighbours + k], count[v]. */
 int  srh_mvs_neighbours(int nviews, const srh_camera *cams, const srh_params *p,
@@ -207,6 +224,10 @@ enum { SRH_WTA_WINNERS = 1, SRH_WTA_COSTS = 2 };
  *   "tscan"           1 (default): on the dense path the scan makes the candidate sequence once per pass and every pixel verifies
  *                     its own curve against it (template scan; a tile with a pixel that does not verify is walked per pixel);
  *                     0: every tile by the per-pixel curve walk.  Identical bits (srh_stats.scan_tiles_template / _walked).
+ *   "tscan_bound"     1 (default): the template scan settles a pixel by ONE error bound for all its labels, held against
+ *                     the room the template pixel found in its own decisions (srh_tscan_bound is the same arithmetic on the
+ *                     host); a tile with a pixel the bound does not settle is verified label by label.  0: every tile label
+ *                     by label.  Identical bits (srh_stats.scan_tiles_bound).
  *   "geodma"          1 (default): on the dense path (GeodesicWeight, radius 5) the support windows come from the persistent
  *                     kernel that fetches its tiles by LDS-DMA from a second copy of the view's edge / tap / mask planes with
  *                     their borders written out (made on first use after an upload: 42 bytes per pixel of device memory; no

@@ -84,7 +84,8 @@ class Stats(C.Structure):
                 ("used_strip_kernel", C.c_int32), ("band_retries", C.c_int32),
                 ("n_certified", C.c_int64), ("n_flagged", C.c_int64), ("band_budget_bytes", C.c_int64),
                 ("mvs_waves_staged", C.c_int64), ("mvs_waves_listed", C.c_int64),
-                ("scan_tiles_template", C.c_int64), ("scan_tiles_walked", C.c_int64)]
+                ("scan_tiles_template", C.c_int64), ("scan_tiles_walked", C.c_int64),
+                ("scan_tiles_bound", C.c_int64)]
 
 
 class FilterInfo(C.Structure):
@@ -126,7 +127,7 @@ PROGRESS_FN = C.CFUNCTYPE(None, C.c_int, C.c_char_p, C.c_void_p)
 EXPORTS = [
     "srh_abi_version", "srh_build_id", "srh_last_error", "srh_device_count", "srh_hw_queues_requested",
     "srh_params_twoview_defaults", "srh_params_mvs_defaults", "srh_camera_from_krt", "srh_camera_from_p",
-    "srh_mvs_neighbours", "srh_cert_bound", "srh_cert_sigma3",
+    "srh_mvs_neighbours", "srh_cert_bound", "srh_cert_sigma3", "srh_tscan_bound",
     "srh_create", "srh_destroy", "srh_set_stream", "srh_set_hooks", "srh_synchronize", "srh_set_option",
     "srh_view_upload", "srh_view_size", "srh_scaled_size", "srh_image_scale", "srh_view_upload_scaled", "srh_view_image_download",
     "srh_view_depth_download", "srh_view_depth_upload",
@@ -151,6 +152,13 @@ EXPORTS = [
 class CertInfo(C.Structure):
     _fields_ = [("e0", C.c_double), ("k1", C.c_double), ("k2", C.c_double), ("k3", C.c_double), ("zmax2", C.c_double),
                 ("m_hi", C.c_double), ("ok", C.c_int32), ("taps", C.c_int32)]
+
+
+class TscanBoundInfo(C.Structure):
+    """srh_tscan_bound_info"""
+    _fields_ = [("E", C.c_double), ("eU", C.c_double), ("eU_template", C.c_double), ("dyU", C.c_double),
+                ("room_col", C.c_double), ("room_one", C.c_double), ("room_proj", C.c_double),
+                ("pixel_ok", C.c_int32), ("template_ok", C.c_int32), ("passes", C.c_int32), ("pad_", C.c_int32)]
 
 
 class StereoHipError(RuntimeError):
@@ -383,6 +391,18 @@ def cert_bound(p, mvs=False):
     ci = CertInfo()
     _check(lib().srh_cert_bound(C.byref(p), 1 if mvs else 0, C.byref(ci)))
     return {k: getattr(ci, k) for k, _ in CertInfo._fields_}
+
+
+def tscan_bound(ref_cam, oth_cam, p, template_xy, xy):
+    """srh_tscan_bound: the template scan's per-pixel bound for pixel xy of the reference view against the template pixel
+    template_xy (host arithmetic, no GPU), as a dict: E, eU, eU_template, dyU, the three rooms, pixel_ok, template_ok, passes."""
+    L = lib()
+    L.srh_tscan_bound.argtypes = [C.POINTER(Camera), C.POINTER(Camera), C.POINTER(Params), C.c_int, C.c_int, C.c_int, C.c_int,
+                                  C.POINTER(TscanBoundInfo)]
+    bi = TscanBoundInfo()
+    _check(L.srh_tscan_bound(C.byref(ref_cam), C.byref(oth_cam), C.byref(p), int(template_xy[0]), int(template_xy[1]),
+                             int(xy[0]), int(xy[1]), C.byref(bi)))
+    return {k: getattr(bi, k) for k, _ in TscanBoundInfo._fields_ if k != "pad_"}
 
 
 def cert_sigma3(p, sum2, mvs=False):
@@ -864,7 +884,8 @@ class Context:
                     used_strip_kernel=bool(s.used_strip_kernel), band_retries=s.band_retries,
                     n_certified=s.n_certified, n_flagged=s.n_flagged, band_budget_bytes=s.band_budget_bytes,
                     mvs_waves_staged=s.mvs_waves_staged, mvs_waves_listed=s.mvs_waves_listed,
-                    scan_tiles_template=s.scan_tiles_template, scan_tiles_walked=s.scan_tiles_walked)
+                    scan_tiles_template=s.scan_tiles_template, scan_tiles_walked=s.scan_tiles_walked,
+                    scan_tiles_bound=s.scan_tiles_bound)
 
     def profile_enable(self, on=True):
         _check(lib().srh_profile_enable(self._h, int(on)))

@@ -4,6 +4,7 @@
 // a HIP device srh_create fails with SRH_E_NO_DEVICE.
 #include "srh_internal.hpp"
 #include "srh_geom.hpp"
+#include "srh_walk.hpp"
 
 #include <algorithm>
 #include <cassert>
@@ -280,6 +281,7 @@ struct srh_context {
 	int tvmrf_w = 0, tvmrf_h = 0, tvmrf_l = 0;          // what the last single-direction run left in them
 	bool tvmrf_own_costs = false;                       //   (its data costs are in tvmrf_costs, not in a caller's volume)
 	int geodma = 1;                                     // option "geodma": 1 = the dense path's r = 5 geodesic windows by the persistent LDS-DMA kernel (default), 0 = geodesic_reg_kernel
+	int tscan_bound = 1;                                // option "tscan_bound": 1 = the template scan settles a pixel by ONE bound for all its labels (default), 0 = label by label
 	int tscan = 1;                                      // option "tscan": 1 = template scan on the dense path (default), 0 = every tile through twoview_scan_kernel
 	int strip = 1;                                      // option "strip": 1 = persistent strip cost kernel (default), 0 = one workgroup per tile, 4 / 8 = force the 4- / 8-wave form
 	int num_cus = 256;
@@ -485,6 +487,53 @@ extern "C" int srh_cert_bound(const srh_params *p, int mvs, srh_cert_info *out) 
 extern "C" double srh_cert_sigma3(const srh_params *p, int mvs, double sum2) {
 	if (!p || p->window_radius < 1 || p->window_radius > 15) return __builtin_nan("");
 	return cert_bound(*p, mvs != 0).sigma3(sum2);
+}
+
+// The template scan's per-pixel bound (srh_walk.hpp: ts_pixel_setup, ts_pixel_E, ts_pixel_passes) for ONE
+// pixel against ONE template pixel, host arithmetic only: the template's keep chain by the reference's own operations, its
+// rooms, the pixel's bound and verdict -- what tests/test_tscan_bound_host.py holds against exact rationals.
+extern "C" int srh_tscan_bound(const srh_camera *refcam, const srh_camera *othcam, const srh_params *p,
+                               int tx, int ty, int x, int y, srh_tscan_bound_info *out) {
+	if (!refcam || !othcam || !p || !out) return fail(SRH_E_INVALID, "null argument");
+	const int D = p->num_depth_levels;
+	if (D < 1 || D > 1024) return fail(SRH_E_INVALID, "num_depth_levels %d outside [1,1024]", D);
+	if (refcam->is_distorted || refcam->is_refractive || othcam->is_distorted || othcam->is_refractive)
+		return fail(SRH_E_UNSUPPORTED, "the template scan serves pinhole pairs");
+	const double sc = p->image_scale;
+	std::vector<double> tnum(D);
+	double tabs = 0.0, tmn = __builtin_inf(), tmx = -__builtin_inf();
+	for (int d = 0; d < D; ++d) {
+		tnum[d] = pinhole_label_tnum(*refcam, *p, false, d);
+		tabs = fmax(tabs, fabs(tnum[d])); tmn = fmin(tmn, tnum[d]); tmx = fmax(tmx, tnum[d]);
+	}
+	// the template pixel: twoview_template_kernel's keep chain
+	const Ray tray = cam_unproject(*refcam, (tx + 0.5)/sc, (ty + 0.5)/sc);
+	const double tnd = dot(normalized(load3(refcam->pdir)), tray.dir);
+	TsRooms rooms;
+	rooms.init();
+	bool allproj = !(fabs(tnd) < 1e-10), chain_ok = allproj;
+	double x1 = __builtin_nan(""), y1 = 0.0;
+	for (int d = 0; d < D && chain_ok; ++d) {
+		double x2, y2;
+		if (!pinhole_project_label(tray, tnd, tnum[d], *othcam, sc, x2, y2)) { allproj = false; continue; }
+		if (isnan_d(x1)) { rooms.point(x2); x1 = x2; y1 = y2; if (trunc_sat(y2) != ty) chain_ok = false; continue; }
+		const double dx = x2 - x1, dy = y2 - y1;
+		if (!(dx*dx + dy*dy >= 1)) { rooms.step(dx, false); continue; }
+		rooms.step(dx, true); rooms.point(x2);
+		if (trunc_sat(y2) != ty) chain_ok = false;
+		x1 = x2; y1 = y2;
+	}
+	TsTemplateHdr hdr;
+	const TsPixel tp = ts_pixel_setup(tray, *refcam, *othcam, sc, tabs, tmn, tmx, ty);
+	ts_template_hdr(tp, rooms, allproj && chain_ok, sc, hdr);
+	const Ray ray = cam_unproject(*refcam, (x + 0.5)/sc, (y + 0.5)/sc);
+	const TsPixel pp = ts_pixel_setup(ray, *refcam, *othcam, sc, tabs, tmn, tmx, y);
+	const double E = pp.ok ? ts_pixel_E(pp, hdr, sc, (double)(x - tx)) : __builtin_inf();
+	out->E = E; out->eU = pp.eU; out->eU_template = hdr.eU; out->dyU = pp.dyU;
+	out->room_col = hdr.room_col; out->room_one = hdr.room_one; out->room_proj = hdr.room_proj;
+	out->pixel_ok = pp.ok ? 1 : 0; out->template_ok = hdr.ok;
+	out->passes = ts_pixel_passes(pp, hdr, E) ? 1 : 0; out->pad_ = 0;
+	return SRH_OK;
 }
 
 static bool near_zero(double x) { return (x <= 1e-10 && x >= -1e-10); }   // camera.cpp:51-52
@@ -818,6 +867,7 @@ extern "C" int srh_set_option(srh_context *c, const char *name, long value) {
 		c->wta_outputs = (int)value; return SRH_OK;
 	}
 	if (!strcmp(name, "tscan")) { c->tscan = value != 0; return SRH_OK; }
+	if (!strcmp(name, "tscan_bound")) { c->tscan_bound = value != 0; return SRH_OK; }
 	if (!strcmp(name, "geodma")) { c->geodma = value != 0; return SRH_OK; }
 	if (!strcmp(name, "f32_form")) { c->f32_form = value != 0; return SRH_OK; }
 	if (!strcmp(name, "rows_masked")) { c->rows_masked = (int)value; return SRH_OK; }   // 0 off, 1 by the other view's share of fully usable windows (default), 2 always
@@ -1242,6 +1292,7 @@ static int fetch_counters(srh_context *c, int used_dense) {
 	c->stats.n_eval_device = (int64_t)h.n_eval_device;
 	c->stats.scan_tiles_template = (int64_t)h.scan_tiles_template;
 	c->stats.scan_tiles_walked = (int64_t)h.scan_tiles_walked;
+	c->stats.scan_tiles_bound = (int64_t)h.scan_tiles_bound;
 	c->stats.mvs_waves_staged = (int64_t)h.mvs_waves_staged;
 	c->stats.mvs_waves_listed = (int64_t)h.mvs_waves_listed;
 	c->stats.used_dense_path = used_dense;
@@ -1910,7 +1961,7 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 				if ((rc = cost_pass(cost_arith))) return rc;
 				{ Scope s(c, "twoview_scan_kernel");
 				  launch_twoview_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.tnum, c->band.cost, cstride, c->d_cnt, c->band.prange,
-				                      cert ? c->band.cflag : nullptr, -1, cert && strip ? c->band.pconst : nullptr, tscan ? c->band.stpl : nullptr, c->band.tileflag, c->num_cus, wout); }
+				                      cert ? c->band.cflag : nullptr, -1, cert && strip ? c->band.pconst : nullptr, tscan ? c->band.stpl : nullptr, c->band.tileflag, c->num_cus, wout, c->tscan_bound); }
 				if (cert) {
 					// the pixels whose decisions the bound does not cover, in the reference's arithmetic: their cost rows are
 					// refilled and they are scanned again -- launched for a capacity, the count stays on the device

@@ -1881,12 +1881,17 @@ void twoview_scan_kernel(const ViewDev *__restrict__ views, int ref, int oth, sr
 // tile reading one 256-byte line of the cost rows per entry.  A wave with a pixel that does not pass (a decision inside
 // its bound, a range that does not match) puts its tile on a list, and twoview_scan_kernel -- launched behind this
 // kernel for exactly those tiles -- does them the old way.  Nothing is trusted that is not checked per pixel.
+// The label-by-label verification is the SECOND tier: it confirms 256 times what is one statement -- this pixel's x2(d)
+// is the template pixel's shifted by x - x_T -- so a pixel first tries ONE bound E on that difference for all labels
+// (ts_pixel_E, srh_walk.hpp; the proof in DESIGN.md 2d), held against the room the template pixel recorded for its own
+// decisions (TsRooms); a tile whose pixels all pass goes straight to the look-ups (option "tscan_bound").
 #define TS_MAXD 1024                   // labels a template holds (more: the old kernel)
 #define TS_MAXS 6144                   // candidate entries
 #define TS_MAXSPAN 1024                // smax - smin + 1
 struct ScanTemplate {
 	int32_t ok, nS, smin, smax, x0, y0, nF, pad_;
 	double tabs, tmin, tmax;            // max |tnum[d]| (bound of |t| for fast_proj_setup), smallest and largest tnum[d]
+	TsTemplateHdr m;                    // the template pixel's fast form and the room of its decisions (the per-pixel bound, srh_walk.hpp)
 	// (32-bit entries: a wave reads them with SCALAR loads -- the index is uniform -- eight at a time; bytes and shorts
 	// would come through the vector memory path, a dependent round trip per label)
 	alignas(32) int32_t lab[TS_MAXD + 8];   // per label: state | offset << 8; state 0 not projectable, 1 first point, 2 dropped
@@ -1940,12 +1945,16 @@ void twoview_template_kernel(const ViewDev *__restrict__ views, int ref, int oth
 		int ok = fabs(nd) < 1e-10 ? 0 : 1, nS = 0, nseg = 0, smin = 2147483647, smax = -2147483647;
 		double x1 = __builtin_nan(""), y1 = 0.0;
 		int jx1 = 0, jy1 = 0;
+		TsRooms rooms;                                                 // the room of every decision below (the per-pixel bound)
+		rooms.init();
+		bool allproj = true;
 		double nx = D > 0 ? sx[0] : 0.0, ny = D > 0 ? sy[0] : 0.0;
 		for (int d = 0; d < D && ok; ++d) {
 			const double x2 = nx, y2 = ny;
 			if (d + 1 < D) { nx = sx[d + 1]; ny = sy[d + 1]; }
-			if (isnan_d(x2)) { s_lab[d] = 0; continue; }                  // (a projection that succeeds is never NaN: finite cameras, t >= 1e-10)
+			if (isnan_d(x2)) { s_lab[d] = 0; allproj = false; continue; } // (a projection that succeeds is never NaN: finite cameras, t >= 1e-10)
 			if (isnan_d(x1)) {
+				rooms.point(x2);
 				// (FLOOR columns: the template pixel's own coordinates may be negative, where the reference's truncation towards
 				// zero is one column off the floor; the scan applies the truncation per pixel, see the entries' bit 30)
 				x1 = x2; y1 = y2; jx1 = fabs(x2) < 0x1p28 ? (int)floor(x2) : 1 << 30; jy1 = trunc_sat(y2);
@@ -1954,7 +1963,8 @@ void twoview_template_kernel(const ViewDev *__restrict__ views, int ref, int oth
 				continue;
 			}
 			const double dx = x2 - x1, dy = y2 - y1;
-			if (!(dx*dx + dy*dy >= 1)) { s_lab[d] = 2; continue; }
+			if (!(dx*dx + dy*dy >= 1)) { s_lab[d] = 2; rooms.step(dx, false); continue; }
+			rooms.step(dx, true); rooms.point(x2);
 			const int ix0 = jx1, ix1 = fabs(x2) < 0x1p28 ? (int)floor(x2) : 1 << 30, iy1 = trunc_sat(y2);
 			if (jy1 != py || iy1 != py || abs(ix1 - px) > 30000) { ok = 0; break; }   // a segment off the row: not this kernel's case
 			jx1 = ix1; jy1 = iy1;
@@ -1974,6 +1984,11 @@ void twoview_template_kernel(const ViewDev *__restrict__ views, int ref, int oth
 		if (nS > 0 && smax - smin + 1 > TS_MAXSPAN) ok = 0;
 		s_hdr[0] = ok; s_hdr[1] = nS; s_hdr[2] = nseg; s_hdr[3] = smin; s_hdr[4] = smax;
 		tpl->ok = ok; tpl->nS = nS; tpl->smin = smin; tpl->smax = smax; tpl->x0 = px; tpl->y0 = py; tpl->tabs = tabs; tpl->tmin = tmn; tpl->tmax = tmx;
+		if (ok) {
+			TsTemplateHdr hdr;
+			ts_template_hdr(ts_pixel_setup(ray, L.cam, Rv.cam, P.image_scale, tabs, tmn, tmx, py), rooms, allproj, P.image_scale, hdr);
+			tpl->m = hdr;
+		}
 	}
 	__syncthreads();
 	// ---- everything else by all lanes: the label words, the candidate entries segment by segment.
@@ -2032,6 +2047,56 @@ void twoview_template_kernel(const ViewDev *__restrict__ views, int ref, int oth
 	for (int j = nF + tid; j < ((nF + 7) & ~7); j += 256) tpl->F[j] = smin & 0xffffff;   // (padding: multiplicity 0)
 }
 
+// tier 2 of the template scan's verification: label by label, the pixel's own curve against the template (see
+// twoview_tscan_tile).  (Inlined: as a called routine it cost the kernel scratch memory.)
+__device__ __forceinline__
+bool tscan_verify_labels(const FastProj fp, const double nd, const double eU, const double dyU, const double rsc,
+                         const int x, const int D, const ScanTemplate *__restrict__ tpl, const double *__restrict__ tnum)
+{
+	const SharedDivisor nd_sd = shared_divisor(nd);
+	bool good = true;
+	const double se = 2*eU;
+	const double c1 = 2.02*se, c0 = __builtin_fma(2.02*se, se, dyU*dyU);   // |dd_reference - dx^2| <= 2|dx|se + se^2 + dyU^2 (+ roundings)
+	double x1 = 0.0;
+	for (int d0 = 0; d0 < D; d0 += 8) {
+		// (uniform addresses, whole eights, aligned: two s_load_dwordx4 and two s_load_dwordx8 per eight labels)
+		int lab[8];
+		double tn[8];
+		{
+			const int4 la = reinterpret_cast<const int4 *>(&tpl->lab[d0])[0], lb = reinterpret_cast<const int4 *>(&tpl->lab[d0])[1];
+			lab[0] = la.x; lab[1] = la.y; lab[2] = la.z; lab[3] = la.w; lab[4] = lb.x; lab[5] = lb.y; lab[6] = lb.z; lab[7] = lb.w;
+			const double4 ta4 = reinterpret_cast<const double4 *>(&tnum[d0])[0], tb4 = reinterpret_cast<const double4 *>(&tnum[d0])[1];
+			tn[0] = ta4.x; tn[1] = ta4.y; tn[2] = ta4.z; tn[3] = ta4.w; tn[4] = tb4.x; tn[5] = tb4.y; tn[6] = tb4.z; tn[7] = tb4.w;
+		}
+#pragma unroll
+		for (int u = 0; u < 8; ++u) {
+			const int st = lab[u] & 255, off = lab[u] >> 8;
+			if (st == 4) continue;
+			const double t = div_by(tn[u], nd_sd);                     // the reference's own t (pinhole_project_label_sd)
+			const bool tv = !(t < 1e-10);
+			if (st == 0) { good = good && !tv; continue; }
+			// fast_project's x coordinate (srh_walk.hpp): within eU of the reference's
+			const double kx = __builtin_fma(t, fp.B.x, fp.A.x), kz = __builtin_fma(t, fp.B.z, fp.A.z);
+			double r = __builtin_amdgcn_rcp(kz);
+			r = __builtin_fma(r, __builtin_fma(-kz, r, 1.0), r);
+			r = __builtin_fma(r, __builtin_fma(-kz, r, 1.0), r);
+			const double x2 = kx*(r*rsc);
+			const double dx = x2 - x1;
+			const double dd = dx*dx;
+			const bool certain = fabs(dd - 1.0) > __builtin_fma(dd, 0x1p-48, __builtin_fma(c1, fabs(dx), c0));
+			if (st == 2) { good = good && tv && certain && !(dd >= 1); continue; }
+			// first / kept point: x truncates certainly and to the template's column.  The reference truncates towards zero:
+			// left of the image (x2 < 0) its integer is the template's (floor) column + 1, which changes the in-image part of a
+			// segment only when the segment's high end is column -1 (the look-up loop handles that case)
+			const int ti = (int)x2;
+			const bool colok = ti == x + off + (x2 < 0.0 ? 1 : 0);
+			good = good && tv && (st == 1 || (certain && dd >= 1)) && trunc_certain(x2, eU) && colok;
+			x1 = x2;
+		}
+	}
+	return good;
+}
+
 #define TS_U 8                         // look-ups in flight per lane
 // one tile; returns false when the tile is left to twoview_scan_kernel
 template <bool CERT, bool WTA>
@@ -2042,7 +2107,7 @@ bool twoview_tscan_tile(const int bid, const ViewDev *__restrict__ views, int re
                         Counters *__restrict__ cnt, const PixRange *__restrict__ prange,
                         uint32_t *__restrict__ cflag, const CertBound &cb, const double *__restrict__ pexact,
                         const ScanTemplate *__restrict__ tpl, unsigned char *smask, unsigned &n_eval_acc, unsigned &n_pix_acc, unsigned &n_flag_acc,
-                        int32_t *__restrict__ wout)
+                        int32_t *__restrict__ wout, const int use_bound, bool &by_bound)
 {
 	const ViewDev &L = views[ref];
 	const ViewDev &Rv = views[oth];
@@ -2059,12 +2124,47 @@ bool twoview_tscan_tile(const int bid, const ViewDev *__restrict__ views, int re
 	const int nS = tpl->nS, smin = tpl->smin, smax = tpl->smax;
 	const bool active = x < W && L.mask[(size_t)y*W + x] == 1;
 	bool good = true;
-	Ray ray;
-	int lo = 0, hi = -1;
+	bool verify = true;
+#ifdef SRH_EXPERIMENT
+	verify = g_exp_scan_mode != 3 && g_exp_scan_mode != 5;           // timing experiment: no verification
+#endif
+	by_bound = false;
+	if (verify) {
+		// ---- one bound for the pixel instead of one per label.  Every label's t = fl(tnum[d] / nd) lies in [tlo, thi] (the
+		// correctly rounded division is monotone; tnum's extremes come with the template).  On that interval k(t) = A + t*B is
+		// linear: |k_x|, |k_y| are largest at an end, |k_z| smallest at an end (same sign at both ends: no pole inside), so
+		// fast_project's bound e(t) <= eU, its formula evaluated with those extremes.  The y coordinate of the fast form is a
+		// Moebius function of t, monotone between the ends: the reference's y2 of EVERY label lies within eU of [ylo, yhi], made
+		// from the two end values -- inside [y, y + 1) means every kept point truncates to row y, and any two labels' y2 differ
+		// by at most dyU = yhi - ylo (ts_pixel_setup, srh_walk.hpp).  What is left is the x coordinate:
+		// tier 1 (ts_pixel_E): ONE bound E on |x2(d) - x2_template(d) - (x - x_T)| for every label, from three evaluations of
+		//   the two fast forms; below the room the template pixel found in its own decisions, every label's state and column
+		//   are the template's.  Pixel-uniform work, no loop over the labels;
+		// tier 2 (tscan_verify_labels), the whole tile when one of its pixels does not pass tier 1: label by label.
+		// (the ray and the set-up are made again where they are needed again -- tier 2, the winner's depth -- instead of
+		// being carried: the registers of the common path)
+		bool bpass = false;
+		if (active) {
+			const Ray ray = cam_unproject(L.cam, (x + 0.5) / P.image_scale, (y + 0.5) / P.image_scale);
+			const TsPixel pp = ts_pixel_setup(ray, L.cam, Rv.cam, P.image_scale, tpl->tabs, tpl->tmin, tpl->tmax, y);
+			good = good && pp.ok;
+			if (use_bound && good) bpass = ts_pixel_passes(pp, tpl->m, ts_pixel_E(pp, tpl->m, P.image_scale, (double)(x - tpl->x0)));
+		}
+		if (__any(active && !good)) return false;                     // twoview_scan_kernel does this tile
+		if (!use_bound || __any(active && !bpass)) {
+			if (active) {
+				const Ray ray = cam_unproject(L.cam, (x + 0.5) / P.image_scale, (y + 0.5) / P.image_scale);
+				const TsPixel pp = ts_pixel_setup(ray, L.cam, Rv.cam, P.image_scale, tpl->tabs, tpl->tmin, tpl->tmax, y);
+				good = tscan_verify_labels(pp.fp, pp.nd, pp.eU, pp.dyU, P.image_scale, x, D, tpl, tnum);
+			}
+			if (__any(active && !good)) return false;
+		} else by_bound = true;
+	}
+	int lo = 0;
 	if (active) {
-		ray = cam_unproject(L.cam, (x + 0.5) / P.image_scale, (y + 0.5) / P.image_scale);
 		const PixRange pr = prange[(size_t)trow*W + x];
-		lo = pr.lo; hi = pr.hi;
+		lo = pr.lo;
+		const int hi = pr.hi;
 		// the range the cost rows were made for must be the template's, clipped to the image
 		int wlo = x + smin, whi = x + smax;
 		// (truncation towards zero: a segment whose high end is column -1 ends ON column 0 in the reference -- the look-ups
@@ -2072,80 +2172,11 @@ bool twoview_tscan_tile(const int bid, const ViewDev *__restrict__ views, int re
 		if (whi == -1) whi = 0;
 		if (wlo < 0) wlo = 0;
 		if (whi > OW - 1) whi = OW - 1;
+		good = true;
 		if (nS > 0 && whi >= wlo) good = lo <= wlo && hi >= whi;       // (every candidate column has its cost)
 		if (y < 0 || y >= OH) good = false;
-		const Vec3 nrm = normalized(load3(L.cam.pdir));
-		const double nd = dot(nrm, ray.dir);
-		if (fabs(nd) < 1e-10) good = false;
-		const SharedDivisor nd_sd = shared_divisor(nd);
-		bool verify = true;
-#ifdef SRH_EXPERIMENT
-		verify = g_exp_scan_mode != 3 && g_exp_scan_mode != 5;        // timing experiment: no verification
-#endif
-		if (verify) {
-		const FastProj fp = fast_proj_setup(ray, Rv.cam, (tpl->tabs/fabs(nd))*1.000001);
-		// ---- one bound for the pixel instead of one per label.  Every label's t = fl(tnum[d] / nd) lies in [tlo, thi] (the
-		// correctly rounded division is monotone; tnum's extremes come with the template).  On that interval k(t) = A + t*B is
-		// linear: |k_x|, |k_y| are largest at an end, |k_z| smallest at an end (same sign at both ends: no pole inside), so
-		// fast_project's bound e(t) <= eU, its formula evaluated with those extremes.  The y coordinate of the fast form is a
-		// Moebius function of t, monotone between the ends: the reference's y2 of EVERY label lies within eU of [ylo, yhi], made
-		// from the two end values -- inside [y, y + 1) means every kept point truncates to row y, and any two labels' y2 differ
-		// by at most dyU = yhi - ylo.  What is left per label is the x coordinate.
-		const double ta = div_by(tpl->tmin, nd_sd), tb = div_by(tpl->tmax, nd_sd);
-		const double tlo = fmin(ta, tb), thi = fmax(ta, tb);
-		const double kzl = __builtin_fma(tlo, fp.B.z, fp.A.z), kzh = __builtin_fma(thi, fp.B.z, fp.A.z);
-		const double kyl = __builtin_fma(tlo, fp.B.y, fp.A.y), kyh = __builtin_fma(thi, fp.B.y, fp.A.y);
-		const double kxm = fmax(fabs(__builtin_fma(tlo, fp.B.x, fp.A.x)), fabs(__builtin_fma(thi, fp.B.x, fp.A.x)));
-		const double kzmin = fmin(fabs(kzl), fabs(kzh));
-		const double rU = (1.0/kzmin)*1.000001;
-		const double amU = fmax(kxm, fmax(fabs(kyl), fabs(kyh)))*rU;
-		const double eU = __builtin_fma(amU*P.image_scale, 0x1p-49, (fp.ek + amU*fp.ekz)*(rU*P.image_scale*1.002))*1.0001;
-		const double yfl = (kyl/kzl)*P.image_scale, yfh = (kyh/kzh)*P.image_scale;
-		const double ylo = fmin(yfl, yfh) - 2*eU, yhi = fmax(yfl, yfh) + 2*eU, dyU = yhi - ylo;
-		good = good && kzl*kzh > 0.0 && fp.ekz*rU <= 0x1p-10 && eU < 0x1p-20 && ylo >= (double)y && yhi < (double)(y + 1);
-		const double se = 2*eU;
-		const double c1 = 2.02*se, c0 = __builtin_fma(2.02*se, se, dyU*dyU);   // |dd_reference - dx^2| <= 2|dx|se + se^2 + dyU^2 (+ roundings)
-		const double rsc = P.image_scale;
-		double x1 = 0.0;
-		for (int d0 = 0; d0 < D; d0 += 8) {
-			// (uniform addresses, whole eights, aligned: two s_load_dwordx4 and two s_load_dwordx8 per eight labels)
-			int lab[8];
-			double tn[8];
-			{
-				const int4 la = reinterpret_cast<const int4 *>(&tpl->lab[d0])[0], lb = reinterpret_cast<const int4 *>(&tpl->lab[d0])[1];
-				lab[0] = la.x; lab[1] = la.y; lab[2] = la.z; lab[3] = la.w; lab[4] = lb.x; lab[5] = lb.y; lab[6] = lb.z; lab[7] = lb.w;
-				const double4 ta4 = reinterpret_cast<const double4 *>(&tnum[d0])[0], tb4 = reinterpret_cast<const double4 *>(&tnum[d0])[1];
-				tn[0] = ta4.x; tn[1] = ta4.y; tn[2] = ta4.z; tn[3] = ta4.w; tn[4] = tb4.x; tn[5] = tb4.y; tn[6] = tb4.z; tn[7] = tb4.w;
-			}
-#pragma unroll
-			for (int u = 0; u < 8; ++u) {
-				const int st = lab[u] & 255, off = lab[u] >> 8;
-				if (st == 4) continue;
-				const double t = div_by(tn[u], nd_sd);                     // the reference's own t (pinhole_project_label_sd)
-				const bool tv = !(t < 1e-10);
-				if (st == 0) { good = good && !tv; continue; }
-				// fast_project's x coordinate (srh_walk.hpp): within eU of the reference's
-				const double kx = __builtin_fma(t, fp.B.x, fp.A.x), kz = __builtin_fma(t, fp.B.z, fp.A.z);
-				double r = __builtin_amdgcn_rcp(kz);
-				r = __builtin_fma(r, __builtin_fma(-kz, r, 1.0), r);
-				r = __builtin_fma(r, __builtin_fma(-kz, r, 1.0), r);
-				const double x2 = kx*(r*rsc);
-				const double dx = x2 - x1;
-				const double dd = dx*dx;
-				const bool certain = fabs(dd - 1.0) > __builtin_fma(dd, 0x1p-48, __builtin_fma(c1, fabs(dx), c0));
-				if (st == 2) { good = good && tv && certain && !(dd >= 1); continue; }
-				// first / kept point: x truncates certainly and to the template's column.  The reference truncates towards zero:
-				// left of the image (x2 < 0) its integer is the template's (floor) column + 1, which changes the in-image part of a
-				// segment only when the segment's high end is column -1 (the look-up loop handles that case)
-				const int ti = (int)x2;
-				const bool colok = ti == x + off + (x2 < 0.0 ? 1 : 0);
-				good = good && tv && (st == 1 || (certain && dd >= 1)) && trunc_certain(x2, eU) && colok;
-				x1 = x2;
-			}
-		}
-		}
 	}
-	if (__any(active && !good)) return false;                        // twoview_scan_kernel does this tile
+	if (__any(active && !good)) return false;
 
 	// mask bytes of row y of the other view, columns [xt + smin, xt + SC_TW + smax] -- one more than the offsets reach: the
 	// left-border look-ups move an entry from column -1 to column 0, which for the tile's last pixel (x + smax = -1) is
@@ -2234,7 +2265,7 @@ bool twoview_tscan_tile(const int bid, const ViewDev *__restrict__ views, int re
 		// (first visits only: sound while wta_margin >= 0 -- with a negative margin a revisited winner would "beat" itself and
 		// move secondBest -- so a negative margin walks every visit like the left-border tiles)
 		if (xt + smin < 0 || !(P.wta_margin >= 0.0)) lookups(std::true_type()); else lookups(std::false_type());
-		if (wcol >= 0) depth = candidate_depth(L.cam, Rv.cam, P, ray, lo + wcol, y);
+		if (wcol >= 0) depth = candidate_depth(L.cam, Rv.cam, P, cam_unproject(L.cam, (x + 0.5) / P.image_scale, (y + 0.5) / P.image_scale), lo + wcol, y);
 		if (minCost > P.second_best_factor*secondBest) depth = __builtin_inf();
 		if (CERT && wcol >= 0) {
 			const double rhs = P.second_best_factor*secondBest;
@@ -2256,24 +2287,25 @@ bool twoview_tscan_tile(const int bid, const ViewDev *__restrict__ views, int re
 // the counters travel in registers and are added once per workgroup.  A tile that does not verify goes on `tilelist`
 // = [count | tile indices] for twoview_scan_kernel.
 template <bool CERT, bool WTA>
-__global__ __launch_bounds__(SC_TW, 4)
+__global__ __launch_bounds__(SC_TW, (CERT && WTA) ? 6 : 7)
 void twoview_tscan_kernel(const ViewDev *__restrict__ views, int ref, int oth, srh_params P,
                           int y0, int nrows, const double *__restrict__ tnum,
                           const double *__restrict__ cost, int cstride,
                           Counters *__restrict__ cnt, const PixRange *__restrict__ prange,
                           uint32_t *__restrict__ cflag, CertBound cb, const double *__restrict__ pexact,
-                          const ScanTemplate *__restrict__ tpl, uint32_t *__restrict__ tilelist, int32_t *__restrict__ wout)
+                          const ScanTemplate *__restrict__ tpl, uint32_t *__restrict__ tilelist, int32_t *__restrict__ wout, int use_bound)
 {
 	__shared__ unsigned char smask[SC_TW + TS_MAXSPAN + 16];
 	const int W = views[ref].w;
 	const int ntiles = ((W + SC_TW - 1)/SC_TW)*nrows;
 	const int tid = threadIdx.x;
 	const bool tok = tpl->ok != 0;
-	unsigned n_eval = 0, n_pix = 0, n_flag = 0, n_tpl = 0, n_walk = 0;
+	unsigned n_eval = 0, n_pix = 0, n_flag = 0, n_tpl = 0, n_walk = 0, n_bound = 0;
 	for (int bid = blockIdx.x; bid < ntiles; bid += gridDim.x) {
+		bool by_bound = false;
 		const bool done = tok && twoview_tscan_tile<CERT, WTA>(bid, views, ref, oth, P, y0, nrows, tnum, cost, cstride, cnt, prange, cflag, cb, pexact,
-		                                                      tpl, smask, n_eval, n_pix, n_flag, wout);
-		if (!done) { if (tid == 0) tilelist[1 + atomicAdd(&tilelist[0], 1u)] = (uint32_t)bid; ++n_walk; } else ++n_tpl;
+		                                                      tpl, smask, n_eval, n_pix, n_flag, wout, use_bound, by_bound);
+		if (!done) { if (tid == 0) tilelist[1 + atomicAdd(&tilelist[0], 1u)] = (uint32_t)bid; ++n_walk; } else { ++n_tpl; n_bound += by_bound ? 1u : 0u; }
 		__syncthreads();                                              // (smask is reused)
 	}
 	if (!cnt) return;
@@ -2285,6 +2317,7 @@ void twoview_tscan_kernel(const ViewDev *__restrict__ views, int ref, int oth, s
 		if (CERT && n_flag) atomicAdd(&cnt->n_flagged, (unsigned long long)n_flag);
 		if (n_tpl) atomicAdd(&cnt->scan_tiles_template, (unsigned long long)n_tpl);
 		if (n_walk) atomicAdd(&cnt->scan_tiles_walked, (unsigned long long)n_walk);
+		if (n_bound) atomicAdd(&cnt->scan_tiles_bound, (unsigned long long)n_bound);
 	}
 }
 
@@ -2413,7 +2446,7 @@ void launch_scan_template(hipStream_t st, const ViewDev *views, int ref, int oth
 void launch_twoview_scan(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P,
                          int y0, int nrows, const double *tnum, const double *cost, int cstride,
                          Counters *cnt, const PixRange *prange, uint32_t *cflag, int nlist, const double *pexact,
-                         const void *tpl, uint32_t *tilelist, int num_cus, int32_t *wout)
+                         const void *tpl, uint32_t *tilelist, int num_cus, int32_t *wout, int tscan_bound)
 {
 	const int tiles = (width + SC_TW - 1)/SC_TW;
 	const CertBound cb = cert_bound(P);
@@ -2426,7 +2459,7 @@ void launch_twoview_scan(hipStream_t st, const ViewDev *views, int ref, int oth,
 	// (wout: the WTA = true instantiations, option "wta_outputs"; without it the kernels as they were)
 #define SRH_TSCAN(C_, W_, FLAG_, PEX_)                                                                         \
 	hipLaunchKernelGGL((twoview_tscan_kernel<C_, W_>), dim3(pgrid), dim3(SC_TW), 0, st,                        \
-	                   views, ref, oth, P, y0, nrows, tnum, cost, cstride, cnt, prange, FLAG_, cb, PEX_, tp, tilelist, wout)
+	                   views, ref, oth, P, y0, nrows, tnum, cost, cstride, cnt, prange, FLAG_, cb, PEX_, tp, tilelist, wout, tscan_bound)
 #define SRH_SCAN(C_, L_, W_, GRID_, FLAG_, NL_, PEX_, TL_)                                                     \
 	hipLaunchKernelGGL((twoview_scan_kernel<C_, L_, W_>), dim3(GRID_), dim3(SC_TW), 0, st,                     \
 	                   views, ref, oth, P, y0, nrows, tnum, cost, cstride, cnt, prange, FLAG_, NL_, cb, PEX_, TL_, wout)

@@ -95,11 +95,11 @@ __device__ __forceinline__ void walk_curve(const Ray &ray, const srh_camera &ref
 // camera centre for every pixel -- and one division by  n . dir  per pixel and label.  The
 // operands and operations are those of point_from_depth(), so the results are bit-identical;
 // only the redundant recomputation (normalising the plane normal, the label depth, ...) goes.
-__device__ __forceinline__ Vec3 pinhole_ray_source(const srh_camera &cam) {
+SRH_HD Vec3 pinhole_ray_source(const srh_camera &cam) {
 	return matvec(cam.Rinv, v3(0, 0, 0) - load3(cam.t));        // cam_unproject: out.src
 }
 
-__device__ __forceinline__ double pinhole_label_tnum(const srh_camera &refcam, const srh_params &P, bool mvs, int label) {
+SRH_HD double pinhole_label_tnum(const srh_camera &refcam, const srh_params &P, bool mvs, int label) {
 	const Vec3 normal = load3(refcam.pdir);
 	const Vec3 n = normalized(normal);                          // Plane3d ctor
 	const double depth = depth_from_label(P, mvs, label);
@@ -110,7 +110,7 @@ __device__ __forceinline__ double pinhole_label_tnum(const srh_camera &refcam, c
 }
 
 // projection of label `d` of the ray into the other (pinhole) view, in scaled pixels
-__device__ __forceinline__ bool pinhole_project_label(const Ray &ray, double nd, double tnum, const srh_camera &oth,
+SRH_HD bool pinhole_project_label(const Ray &ray, double nd, double tnum, const srh_camera &oth,
                                                       double scale, double &x2, double &y2)
 {
 	const double t = tnum / nd;
@@ -133,19 +133,24 @@ __device__ __forceinline__ bool pinhole_project_label(const Ray &ray, double nd,
 // other operand takes the ordinary division.  The scan kernel divides 256 label numerators by one n.dir per
 // pixel and two image coordinates by one z per label.
 struct SharedDivisor { double b, r; bool ok; };
-__device__ __forceinline__ SharedDivisor shared_divisor(double b) {
+SRH_HD SharedDivisor shared_divisor(double b) {
 	SharedDivisor q;
 	q.b = b;
 	const double ab = fabs(b);
 	q.ok = ab > 0x1p-300 && ab < 0x1p300;
+#ifdef __HIP_DEVICE_COMPILE__
 	double r = __builtin_amdgcn_rcp(b);
 	double e = __builtin_fma(-b, r, 1.0);
 	r = __builtin_fma(r, e, r);
 	e = __builtin_fma(-b, r, 1.0);
 	q.r = __builtin_fma(r, e, r);
+#else
+	q.ok = false;                                               // host code (srh_tscan_bound): the plain division, the same quotient
+	q.r = 0.0;
+#endif
 	return q;
 }
-__device__ __forceinline__ double div_by(double a, const SharedDivisor &q) {
+SRH_HD double div_by(double a, const SharedDivisor &q) {
 	const double aa = fabs(a);
 	if (q.ok && aa > 0x1p-300 && aa < 0x1p300) {
 		const double m = a*q.r;
@@ -182,7 +187,7 @@ __device__ __forceinline__ bool pinhole_project_label_sd(const Ray &ray, const S
 // other label is projected once more by the reference's own operations (exact_label_point), so the candidate lists
 // are the reference's lists.
 struct FastProj { Vec3 A, B; double ek, ekz; };              // ek: the larger of the x and y bounds (one register pair less)
-__device__ __forceinline__ FastProj fast_proj_setup(const Ray &ray, const srh_camera &oth, double tmax) {
+SRH_HD FastProj fast_proj_setup(const Ray &ray, const srh_camera &oth, double tmax) {
 	FastProj f;
 	f.A = matvec(oth.K, matvec(oth.R, ray.src) + load3(oth.t));
 	f.B = matvec(oth.K, matvec(oth.R, ray.dir));
@@ -229,6 +234,122 @@ __device__ __noinline__ double2 exact_label_point(const srh_camera &refcam, cons
 }
 // is truncation of v certain under the bound e?  (every integer counts as a boundary; far outside any image: no)
 __device__ __forceinline__ bool trunc_certain(double v, double e) { return fabs(v) < 0x1p28 && fabs(v - __builtin_rint(v)) > e; }
+
+// ---- template scan: one pixel's set-up and its ONE bound for all labels ------------------------------
+// Host and device code: twoview_tscan_kernel / twoview_template_kernel run it per pixel, srh_tscan_bound on the host
+// (tests/test_tscan_bound_host.py holds it against the reference's projection chain in exact rationals).
+//
+// the fast form's x coordinate, scale*(A.x + t B.x)/(A.z + t B.z), as the label-by-label verification evaluates it: within
+// 10u|x| (u = 2^-53) of the real-number value -- one rounding each in k_x, k_z, r*scale and the product, r = 1/k_z to 2 ulp
+SRH_HD double ts_fast_x(const Vec3 &A, const Vec3 &B, double t, double scale) {
+	const double kx = __builtin_fma(t, B.x, A.x), kz = __builtin_fma(t, B.z, A.z);
+#ifdef __HIP_DEVICE_COMPILE__
+	double r = __builtin_amdgcn_rcp(kz);
+	r = __builtin_fma(r, __builtin_fma(-kz, r, 1.0), r);
+	r = __builtin_fma(r, __builtin_fma(-kz, r, 1.0), r);
+#else
+	const double r = 1.0/kz;
+#endif
+	return kx*(r*scale);
+}
+// What a pixel knows about ALL its labels from the two ends of the label range (the 2d paragraph on eU):
+// ok: no pole in the range, 2c's condition on ekz, eU < 2^-20, every label's y2 certainly in [y, y + 1).
+struct TsPixel {
+	FastProj fp;
+	double nd;                         // n . dir
+	double tlo, thi;                   // every label's t = fl(tnum/nd) lies in [tlo, thi]
+	double eU, dyU;                    // |x2, y2 of the reference - fast form| <= eU for every label; any two labels' y2 differ by <= dyU
+	double kxm, kzmin, kzmax, rU;      // max |k_x|, min and max |k_z| on [tlo, thi]; rU >= 1/kzmin
+	bool ok;
+};
+SRH_HD TsPixel ts_pixel_setup(const Ray &ray, const srh_camera &refcam, const srh_camera &oth, double scale,
+                              double tabs, double tmin, double tmax, int y)
+{
+	TsPixel p;
+	const Vec3 nrm = normalized(load3(refcam.pdir));
+	const double nd = dot(nrm, ray.dir);
+	p.nd = nd;
+	const SharedDivisor nd_sd = shared_divisor(nd);
+	const FastProj fp = fast_proj_setup(ray, oth, (tabs/fabs(nd))*1.000001);
+	p.fp = fp;
+	const double ta = div_by(tmin, nd_sd), tb = div_by(tmax, nd_sd);
+	const double tlo = fmin(ta, tb), thi = fmax(ta, tb);
+	p.tlo = tlo; p.thi = thi;
+	const double kzl = __builtin_fma(tlo, fp.B.z, fp.A.z), kzh = __builtin_fma(thi, fp.B.z, fp.A.z);
+	const double kyl = __builtin_fma(tlo, fp.B.y, fp.A.y), kyh = __builtin_fma(thi, fp.B.y, fp.A.y);
+	const double kxm = fmax(fabs(__builtin_fma(tlo, fp.B.x, fp.A.x)), fabs(__builtin_fma(thi, fp.B.x, fp.A.x)));
+	const double kzmin = fmin(fabs(kzl), fabs(kzh));
+	const double rU = (1.0/kzmin)*1.000001;
+	const double amU = fmax(kxm, fmax(fabs(kyl), fabs(kyh)))*rU;
+	const double eU = __builtin_fma(amU*scale, 0x1p-49, (fp.ek + amU*fp.ekz)*(rU*scale*1.002))*1.0001;
+	const double yfl = (kyl/kzl)*scale, yfh = (kyh/kzh)*scale;
+	const double ylo = fmin(yfl, yfh) - 2*eU, yhi = fmax(yfl, yfh) + 2*eU;
+	p.eU = eU; p.dyU = yhi - ylo;
+	p.kxm = kxm; p.kzmin = kzmin; p.kzmax = fmax(fabs(kzl), fabs(kzh)); p.rU = rU;
+	p.ok = !(fabs(nd) < 1e-10) && kzl*kzh > 0.0 && fp.ekz*rU <= 0x1p-10 && eU < 0x1p-20 && ylo >= (double)y && yhi < (double)(y + 1);
+	return p;
+}
+// The room of the template's decisions (twoview_template_kernel's keep chain; the minima over the labels):
+// col: distance of a first / kept label's x2 from the nearest integer (x2 - floor(x2) is exact; a negative x2 above -2^-53
+//      gives 0: conservative).  Floor columns and "not an integer" settle the truncation towards zero on either side of 0.
+// one: | |dx| - 1 | of every label behind the first, dx = fl(x2 - x1) to the last kept point; 0 when a label is kept with
+//      |dx| < 1 (kept by its dy: no bound on dx alone decides that).
+struct TsRooms {
+	double col, one;
+	SRH_HD void init() { col = 0.5; one = __builtin_inf(); }
+	SRH_HD void point(double x2) { const double fr = x2 - floor(x2); col = fmin(col, fmin(fr, 1.0 - fr)); }
+	SRH_HD void step(double dx, bool kept) {
+		const double adx = fabs(dx);
+		one = fmin(one, (kept && adx < 1.0) ? 0.0 : fabs(adx - 1.0));
+	}
+};
+// what the template pixel hands to every other pixel: the part of its own TsPixel the bound needs, evaluated as far as it
+// goes without the other pixel (uniform values: made once by the template kernel, read by scalar loads), and its rooms
+struct TsTemplateHdr {
+	double nd, tlo, tm, thi;           // n . dir; the t interval of its labels and the t whose 1/t is the middle of the 1/t interval
+	double x0, x1, x2;                 // its fast form's x at tlo, tm, thi
+	double xm, dmin, dmax;             // max |x| on the interval; smallest and largest |k_z(t)/t| (at an end: linear in 1/t, one sign)
+	double eU;
+	double room_col, room_one, room_proj;   // room_proj: smallest t of a label - 1e-10 (reported; a pixel tests its OWN smallest t exactly)
+	int32_t ok, pad_;                  // the template pixel's own set-up holds, every label is projectable, the interval is usable
+};
+SRH_HD void ts_template_hdr(const TsPixel &t, const TsRooms &r, bool all_projectable, double scale, TsTemplateHdr &h) {
+	h.nd = t.nd; h.tlo = t.tlo; h.thi = t.thi; h.eU = t.eU;
+	h.tm = (2.0*t.tlo*t.thi)/(t.tlo + t.thi);
+	h.x0 = ts_fast_x(t.fp.A, t.fp.B, h.tlo, scale); h.x1 = ts_fast_x(t.fp.A, t.fp.B, h.tm, scale); h.x2 = ts_fast_x(t.fp.A, t.fp.B, h.thi, scale);
+	h.xm = scale*t.kxm*t.rU;
+	const double d0 = fabs(__builtin_fma(t.tlo, t.fp.B.z, t.fp.A.z))/t.tlo, d2 = fabs(__builtin_fma(t.thi, t.fp.B.z, t.fp.A.z))/t.thi;
+	h.dmin = fmin(d0, d2); h.dmax = fmax(d0, d2);
+	h.room_col = r.col; h.room_one = r.one; h.room_proj = all_projectable ? t.tlo - 1e-10 : 0.0;
+	// (s = 1/t in ts_pixel_E: t > 0; the middle node certainly near the middle: an interval of some width)
+	h.ok = (t.ok && all_projectable && t.tlo >= 1e-10 && t.thi - t.tlo > 0x1p-40*t.thi && h.dmin > 0.0) ? 1 : 0; h.pad_ = 0;
+}
+// E with |x2_ref(pixel, d) - x2_ref(template, d) - delta| <= E for EVERY label d (delta = x - x_T); DESIGN.md 2d has the
+// proof, term by term.  +inf when a condition of the proof does not hold.
+SRH_HD double ts_pixel_E(const TsPixel &p, const TsTemplateHdr &h, double scale, double delta) {
+	const double inf = __builtin_inf();
+	const double rho = h.nd/p.nd;                                  // t_pixel(d) = rho*t_template(d)*(1 + 3u)
+	const double Az = fabs(p.fp.A.z), Ax = fabs(p.fp.A.x);
+	if (!h.ok || !(rho > 0.0) || !(rho < inf) || !((p.kzmax + Az)*p.rU <= 0x1p20)) return inf;
+	// g(t) = x_pixel(rho t) - x_template(t) - delta at the two ends and the middle of the template's interval of s = 1/t
+	// (in s both x are Moebius functions with the denominators k_z/t -- on a rectified rig constants)
+	const double g0 = (ts_fast_x(p.fp.A, p.fp.B, rho*h.tlo, scale) - h.x0) - delta;
+	const double g1 = (ts_fast_x(p.fp.A, p.fp.B, rho*h.tm, scale) - h.x1) - delta;
+	const double g2 = (ts_fast_x(p.fp.A, p.fp.B, rho*h.thi, scale) - h.x2) - delta;
+	const double gmax = fmax(fabs(g0), fmax(fabs(g1), fabs(g2)));
+	const double xmp = scale*p.kxm*p.rU;                                            // max |x| of the pixel on its interval
+	const double TM = (scale*(p.kxm + Ax)*p.rU + xmp*(1.0 + Az*p.rU))*1.01;           // max |t dx/dt| of the pixel
+	const double R = 0x1p-53*(6.0*TM + 16.0*((xmp + h.xm) + fabs(delta)));
+	// the pixel's denominator at the ends of the interval (linear in s, of one sign: largest and smallest there)
+	const double dp0 = fabs(__builtin_fma(rho*h.tlo, p.fp.B.z, p.fp.A.z))/h.tlo, dp2 = fabs(__builtin_fma(rho*h.thi, p.fp.B.z, p.fp.A.z))/h.thi;
+	const double kr = ((fmax(dp0, dp2)*h.dmax)/(fmin(dp0, dp2)*h.dmin))*1.0001;
+	const double E = (((p.eU + h.eU) + 1.3*kr*(gmax + R)) + R)*1.0001;
+	return E == E ? E : inf;
+}
+// the pixel's verdict: every label's state and column are the template's
+SRH_HD bool ts_pixel_passes(const TsPixel &p, const TsTemplateHdr &h, double E) {
+	return p.ok && h.ok != 0 && p.tlo >= 1e-10 && E + 0x1p-50 < h.room_col && (2.0*E + p.dyU*p.dyU) + 0x1p-48 < h.room_one;
+}
 
 template <class Visitor>
 __device__ __forceinline__ void walk_curve_pinhole(const Ray &ray, const srh_camera &refcam, const ViewDev &oth,
