@@ -1,0 +1,112 @@
+"""How many times each kernel is launched by one TwoViewStereo call, on every path of the pass driver (csrc/srh_api.hip):
+the proof that a change to the driver's host code queues what its parent queued.  Every entry is one call on a fresh
+context (learnt list capacities do not leak between entries; a `compute` entry is two calls on one context, so that the
+guessed and the learnt deferred list passes both appear): {kernel name: launches} from Context.profile() and the path
+counters of Context.stats().  Writes sorted JSON: run it on two builds and compare the files byte for byte.
+usage: python3 profiles/launch_census.py [out.json]      (from the repository root; default profiles/launch_census.json)"""
+import json
+import os
+import sys
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import cases
+import small_shapes as SS
+from stereoreconstruction_amd import capi
+
+# the option sets of RECT_PATHS / GENERAL_PATHS in tests/test_gpu_wta_outputs.py (copied: that module needs the oracle)
+RECT_PATHS = [("defaults", dict()), ("arith 0", dict(arith=0)), ("strip 0", dict(strip=0)), ("strip 4", dict(strip=4)),
+              ("strip 8", dict(strip=8)), ("tscan 0", dict(tscan=0)), ("fused", dict(fused=1)),
+              ("row-run lists", dict(force_generic=1, list_rows=1)), ("list order", dict(force_generic=1, list_rows=0))]
+GENERAL_PATHS = [("defaults", dict()), ("list order", dict(list_rows=0)), ("arith 0", dict(arith=0))]
+RECT_EXTRA = [("sad lists", dict(cost=capi.COST_SAD, sad_dense=0)), ("sad dense", dict(cost=capi.COST_SAD, sad_dense=1)),
+              ("wta_outputs 3", dict(wta_outputs=3)), ("walk", dict(force_generic=2))]
+BANDED = [("defaults", dict()), ("row-run lists", dict(force_generic=1)), ("list order", dict(force_generic=1, list_rows=0)),
+          ("walk", dict(force_generic=2))]
+RECT_SHAPES = [(33, 9, 40), (65, 12, 8), (40, 3, 64)]
+GENERAL_SHAPES = [(33, 7, 12), (65, 6, 8)]
+DIRECTIONS = ((0, 1), (1, 0))
+STATS = ("used_dense_path", "used_strip_kernel", "used_fused_kernel", "n_certified", "n_flagged", "n_eval")
+
+
+def record(ctx, call):
+    """one profiled call -> {launches, stats} or, where the library declines it, {error}"""
+    ctx.profile_reset()
+    try:
+        call()
+    except capi.StereoHipError as e:
+        return dict(error=e.code)
+    st = ctx.stats()
+    return dict(launches={k: n for k, (_, n) in ctx.profile().items()}, stats={k: int(st[k]) for k in STATS})
+
+
+def entry(case, opts, calls):
+    """a fresh context with the case's views and the options -> the records of `calls`, in turn"""
+    cams, p = cases.hip_inputs(case)
+    with capi.Context(0) as ctx:
+        cases.upload_case(ctx, case, cams)
+        for k, v in opts.items():
+            ctx.set_option(k, v)
+        ctx.synchronize()
+        ctx.profile_enable(True)
+        out = [record(ctx, lambda: fn(ctx, p)) for fn in calls]
+    return out[0] if len(out) == 1 else out
+
+
+def wta(ref, oth):
+    return lambda ctx, p: ctx.twoview_wta(ref, oth, p)
+
+
+def compute(ctx, p):
+    ctx.twoview_compute(0, 1, p)
+
+
+def cost_rows(form, h):
+    return lambda ctx, p: ctx.twoview_cost_rows(0, 1, p, 0, h, form)
+
+
+def census():
+    out = {}
+
+    def passes(case, tag, opts):
+        for ref, oth in DIRECTIONS:
+            out["%s | %s | wta %d>%d" % (case["name"], tag, ref, oth)] = entry(case, opts, [wta(ref, oth)])
+
+    for radius, kind in SS.TWOVIEW_KINDS:
+        for shape in RECT_SHAPES:
+            case = SS.small_twoview(*shape, radius, kind)
+            for tag, opts in RECT_PATHS + RECT_EXTRA:
+                passes(case, tag, opts)
+            if shape == (65, 12, 8):
+                for tag, opts in BANDED:
+                    passes(case, tag + ", band_budget_mb 1", dict(opts, band_budget_mb=1))
+            for overlap in (1, 0):
+                out["%s | tv_overlap %d | compute twice" % (case["name"], overlap)] = entry(case, dict(tv_overlap=overlap), [compute, compute])
+            for strip in (0, 8):
+                for form in (0, 3, 5):
+                    out["%s | strip %d | cost_rows form %d" % (case["name"], strip, form)] = entry(case, dict(strip=strip), [cost_rows(form, shape[1])])
+        for shape in GENERAL_SHAPES:
+            case = SS.small_twoview(*shape, radius, kind, masks=True, verged=True, distortion=True)
+            for side in (0, 1):
+                for tag, opts in GENERAL_PATHS:
+                    passes(case, "%s, side_weights %d" % (tag, side), dict(opts, side_weights=side))
+            out["%s | defaults | compute twice" % case["name"]] = entry(case, dict(), [compute, compute])
+    # many bands on every path: the issue's small shapes fit one band of the smallest budget on the dense plan
+    case = cases.get_twoview("geodesic_masks", w=160, h=96, D=24, radius=5)
+    for tag, opts in RECT_PATHS + RECT_EXTRA:
+        out["%s | %s, band_budget_mb 1 | wta 0>1" % (case["name"], tag)] = entry(case, dict(opts, band_budget_mb=1), [wta(0, 1)])
+    # a dense plan the device refutes: proposed for a verged pinhole pair, redone on the general kernels
+    case = cases.get_twoview("adaptive_verged", w=72, h=44, D=20, radius=5)
+    passes(case, "force_dense 1", dict(force_dense=1))
+    out["%s | force_dense 1 | compute twice" % case["name"]] = entry(case, dict(force_dense=1), [compute, compute])
+    return out
+
+
+if __name__ == "__main__":
+    path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "launch_census.json")
+    result = census()
+    with open(path, "w") as f:
+        json.dump(result, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("%d entries -> %s" % (len(result), path))

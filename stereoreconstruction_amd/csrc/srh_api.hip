@@ -345,9 +345,6 @@ struct srh_context {
 	int side_weights = 1;                               // option "side_weights": 0 = the row-run path computes its support windows on the pass's own stream, behind the list kernel (profiling: every kernel's own duration)
 	int cert_form = 1;                                  // option "cert_form": certified strip kernel in 1 = the one-pass form (default), 2 = two fused sweeps
 	bool force_dense = false;                           // option "force_dense": propose the dense plan for any pinhole pair
-	// srh_twoview_cost_rows (diagnostic): the dense plan stops after the cost kernel of its one band and hands the rows out
-	struct Diag { int form = 0; bool raw = false; double *cost = nullptr; size_t cost_doubles = 0; int32_t *range = nullptr;
-	              int cstride = 0, rows = 0; bool done = false, strip = false; } *diag = nullptr;
 	std::map<std::string, ProfEntry> prof;
 	std::vector<PendingEvt> pending;
 	srh_stats stats;
@@ -1283,10 +1280,17 @@ static int band_rows(srh_context *c, int W, int H, int T) {
 	return (int)rows;
 }
 
+// `bytes` of device memory to the host, behind everything queued on c->stream, and the wait for them
+static int read_back(srh_context *c, void *host, const void *dev, size_t bytes) {
+	HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	return SRH_OK;
+}
+
 static int fetch_counters(srh_context *c, int used_dense) {
 	Counters h;
-	HIP_TRY(hipMemcpyAsync(&h, c->d_cnt, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-	HIP_TRY(hipStreamSynchronize(c->stream));
+	int rc;
+	if ((rc = read_back(c, &h, c->d_cnt, sizeof(h)))) return rc;
 	c->stats.n_pixels = (int64_t)h.n_pixels;
 	c->stats.n_eval = (int64_t)h.n_eval;
 	c->stats.n_eval_device = (int64_t)h.n_eval_device;
@@ -1399,8 +1403,6 @@ static bool rig_is_row_aligned(const srh_camera &a, const srh_camera &b, double 
 	return true;
 }
 
-static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p, int y0, int y1);
-
 // The WTA by-products of a pass ref -> oth (option "wta_outputs"): the planes exist and hold either what an earlier pass of
 // the same kind left (a pass over some rows writes those rows only, as it does in the depth map) or the "none" values.
 // Allocated like the view's other planes; a refusal is a clean SRH_E_DEVICE before the pass queues anything.  Option off:
@@ -1471,29 +1473,53 @@ static void estimate_list_capacity(const srh_camera &rc, const srh_camera &oc, i
 	smax = (int)((sm + 7) & ~7L);
 }
 
-// The planes twoview_strip_sad_kernel stages from (option "sad_dense"), made on first use after an upload, on c->stream:
-// the NaN-bordered gray_tv plane (the reference side's taps), the NaN-bordered masked gray plane (the other side's) and the
-// zero-bordered copy of cost_sad's "window fully usable" plane of radius R
-static int ensure_sad_planes(srh_context *c, ViewHost &v, int R) {
+// The NaN-bordered gray_tv plane of a view (the strip kernels' taps; the general cost of the left-out columns and of the
+// certified redo reads it without bound tests), made on first use after an upload, on c->stream
+static int ensure_tvp(srh_context *c, ViewHost &v) {
 	if (!v.tvp) HIP_TRY(v.tvp.alloc(padded_size(v.w, v.h)));
 	if (!v.tvp_valid) {
 		Scope s(c, "padded_plane_kernel");
 		launch_padded_plane(c->stream, v.gray_tv, v.w, v.h, v.tvp);
 		v.tvp_valid = true;
 	}
+	return SRH_OK;
+}
+
+// cost_sad's "window fully usable" plane of radius R (its zero-bordered copy, if any, is stale then)
+static int ensure_fulls(srh_context *c, ViewHost &v, int R) {
+	if (v.fulls_r == R) return SRH_OK;
+	if (!v.fulls) HIP_TRY(v.fulls.alloc((size_t)v.w*v.h));
+	Scope s(c, "sad_full_window_kernel");
+	launch_sad_full_window(c->stream, v.mask, v.w, v.h, R, v.fulls);
+	v.fulls_r = R;
+	v.fullsp_r = 0;
+	return SRH_OK;
+}
+
+// cost_ncc's "window fully usable" plane of radius R, with its two counts behind it (option "rows_masked")
+static int ensure_full(srh_context *c, ViewHost &v, int R) {
+	if (v.full_r == R) return SRH_OK;
+	Scope s(c, "full_window_kernel");
+	uint32_t *stat = (uint32_t *)(v.full + full_stat_offset((size_t)v.w*v.h));
+	HIP_TRY(hipMemsetAsync(stat, 0, 2*sizeof(uint32_t), c->stream));
+	launch_full_window(c->stream, v.gray_tv, v.w, v.h, R, v.full, stat);
+	v.full_r = R;
+	return SRH_OK;
+}
+
+// The planes twoview_strip_sad_kernel stages from (option "sad_dense"), made on first use after an upload, on c->stream:
+// the NaN-bordered gray_tv plane (the reference side's taps), the NaN-bordered masked gray plane (the other side's) and the
+// zero-bordered copy of cost_sad's "window fully usable" plane of radius R
+static int ensure_sad_planes(srh_context *c, ViewHost &v, int R) {
+	int rc;
+	if ((rc = ensure_tvp(c, v))) return rc;
 	if (!v.grayp) HIP_TRY(v.grayp.alloc(padded_size(v.w, v.h)));
 	if (!v.grayp_valid) {
 		Scope s(c, "padded_gray_kernel");
 		launch_padded_gray(c->stream, v.gray, v.mask, v.w, v.h, v.grayp);
 		v.grayp_valid = true;
 	}
-	if (v.fulls_r != R) {
-		if (!v.fulls) HIP_TRY(v.fulls.alloc((size_t)v.w*v.h));
-		Scope s(c, "sad_full_window_kernel");
-		launch_sad_full_window(c->stream, v.mask, v.w, v.h, R, v.fulls);
-		v.fulls_r = R;
-		v.fullsp_r = 0;
-	}
+	if ((rc = ensure_fulls(c, v, R))) return rc;
 	if (!v.fullsp) HIP_TRY(v.fullsp.alloc(padded_size(v.w, v.h)));
 	if (v.fullsp_r != R) {
 		Scope s(c, "padded_bytes_kernel");
@@ -1503,513 +1529,616 @@ static int ensure_sad_planes(srh_context *c, ViewHost &v, int R) {
 	return SRH_OK;
 }
 
-extern "C" int srh_twoview_wta(srh_context *c, int ref, int oth, const srh_params *p, int y0, int y1) {
-	int rc;
-	if ((rc = check_slot(c, ref, true)) || (rc = check_slot(c, oth, true)) || (rc = check_params(p))) return rc;
-	return with_thinner_bands(c, [&] { return twoview_wta_run(c, ref, oth, p, y0, y1); });
-}
+// ---- the TwoView WTA pass driver: a pass descriptor, a plan that launches nothing, one runner per path (fused kernel,
+// candidate lists, dense plan, walk kernel) and a controller that reads their outcomes (twoview_wta_run) ----------------
 
-static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p, int y0, int y1) {
-	int rc;
+// dense: the row-aligned kernels are *proposed* (the scan kernel verifies every candidate), cost rows of cstride doubles;
+// fused: the candidate range fits an LDS cost row of srh_fused.hip
+struct TvPlan { bool dense = false; int cstride = 0; bool fused = false; };
+// The candidate lists of a pass: capacities cmax = candidates, smax = cost slots (row runs in 8-column blocks) per pixel;
+// guessed: they are the host's first guess; rows_mode: row runs (srh_rows.hip), else list order (srh_list.hip); cert: row
+// runs in the certified arithmetic; lrows: rows per band
+struct TvLists { int cmax = 0, smax = 0; bool rows_mode = false, guessed = false, cert = false; size_t lrows = 0; };
+// An attempt of the dense plan: the plan's cstride; strip: the persistent strip form of the cost kernel, the band's windows
+// in the LDS image's layout then; cert: certified arithmetic (fused cost loops + the certified scan and redo); rows per band
+struct TvDense { int cstride = 0; bool strip = false, cert = false, tscan = false; size_t rows = 0; int lanes = 8; };
+
+// One pass ref -> oth over rows [y0, y1) of equal-sized views (clamped to the view: y1 <= y0, nothing to do): what every
+// runner needs.  R, T: window radius and taps; budget: bytes of band scratch.
+// wout, the by-products of the scan (option "wta_outputs"): every scan kernel of the pass stores winner and runner-up where
+// it stores the depth, and twoview_winner_costs_kernel follows the band's last scan with their exact costs.  A repeated
+// attempt rewrites every row of the pass, so the planes hold what the attempt whose depth map stands wrote.
+struct TvPass {
+	srh_context *c = nullptr;
+	int ref = 0, oth = 0;
+	const srh_params *p = nullptr;
+	int W = 0, H = 0, y0 = 0, y1 = 0, R = 0, T = 0;
+	size_t budget = 0;
+	bool sad = false;
+	int32_t *wout = nullptr;
+
+	size_t rows_per_band(size_t bytes) const;
+	void winner_costs(int by, int nr, bool wimg_layout) const;
+	TvPlan plan() const;
+	int run_fused(bool &stands) const;
+	int lists_prepare(TvLists &S) const;
+	int lists_rows_band(const TvLists &S, int by, int nr) const;
+	int lists_pass(TvLists &S) const;
+	int run_lists(bool cert_ok, srh_context::TvDefer *defer) const;
+	int dense_prepare(TvDense &D) const;
+	void dense_band_inputs(const TvDense &D, int by, int nr) const;
+	int dense_cost_pass(const TvDense &D, int by, int nr, int arith, bool raw) const;
+	int run_dense(TvDense &D) const;
+	int run_walk() const;
+};
+
+static int tv_pass_init(TvPass &P, srh_context *c, int ref, int oth, const srh_params *p, int y0, int y1) {
 	if (ref == oth) return fail(SRH_E_INVALID, "ref and other view are the same slot");
 	const ViewHost &L = c->views[ref], &Rv = c->views[oth];
 	if (L.w != Rv.w || L.h != Rv.h)
 		return fail(SRH_E_INVALID, "TwoViewStereo needs equal-sized views (%dx%d vs %dx%d; twoviewstereo.cpp:116-119)",
 		            L.w, L.h, Rv.w, Rv.h);
 	HIP_TRY(hipSetDevice(c->device));
-	const int W = L.w, H = L.h;
-	if (y0 < 0) y0 = 0;
-	if (y1 <= 0 || y1 > H) y1 = H;
-	if (y1 <= y0) return SRH_OK;
-	const int R = p->window_radius;
-	const int T = (2*R + 1)*(2*R + 1);
-	const size_t budget = band_budget(c);
-	// by-products of the scan (option "wta_outputs"): every scan kernel of the pass stores winner and runner-up where it
-	// stores the depth (wout), and twoview_winner_costs_kernel follows the band's last scan with their exact costs.  A
-	// repeated attempt rewrites every row of the pass, so the planes hold what the attempt whose depth map stands wrote.
-	if (!c->diag && (rc = ensure_wta_planes(c, ref, oth))) return rc;
-	int32_t *const wout = (c->wta_outputs && !c->diag) ? (int32_t *)c->views[ref].wta_xy : nullptr;
-	auto winner_costs = [&](int by, int nr, bool wimg_layout) {
-		if (!wout || !(c->wta_outputs & SRH_WTA_COSTS)) return;
-		Scope s(c, "twoview_winner_costs_kernel");
-		double *mc = c->views[ref].wta_cost;
-		launch_twoview_winner_costs(c->stream, c->d_views, ref, oth, W, *p, c->cost_kind == SRH_COST_SAD, by, nr, c->band.wbuf, wimg_layout,
-		                            wout, mc, mc + (size_t)W*H);
-	};
+	P.c = c; P.ref = ref; P.oth = oth; P.p = p;
+	P.W = L.w; P.H = L.h;
+	P.y0 = y0 < 0 ? 0 : y0;
+	P.y1 = (y1 <= 0 || y1 > P.H) ? P.H : y1;
+	P.R = p->window_radius;
+	P.T = (2*P.R + 1)*(2*P.R + 1);
+	P.sad = c->cost_kind == SRH_COST_SAD;
+	if (P.y1 > P.y0) P.budget = band_budget(c);
+	return SRH_OK;
+}
 
-	// ---- plan: dense row-aligned kernels, or the general curve-walk kernel
-	// (cost_sad: the dense plan only with option "sad_dense", its cost rows filled by twoview_strip_sad_kernel; no per-tile
-	// and no fused kernel -- without the option rectified rigs take the row-run lists too)
-	const bool sad = c->cost_kind == SRH_COST_SAD;
-	bool dense = !c->force_generic && (!sad || c->sad_dense) && (R == 5 || R == 2);
-	int cstride = 0;
+// rows per band: what the budget holds at `bytes` per pixel, at least one, at most the pass
+size_t TvPass::rows_per_band(size_t bytes) const {
+	return std::min(std::max<size_t>(budget/(bytes*(size_t)W), 1), (size_t)(y1 - y0));
+}
+
+void TvPass::winner_costs(int by, int nr, bool wimg_layout) const {
+	if (!wout || !(c->wta_outputs & SRH_WTA_COSTS)) return;
+	Scope s(c, "twoview_winner_costs_kernel");
+	double *mc = c->views[ref].wta_cost;
+	launch_twoview_winner_costs(c->stream, c->d_views, ref, oth, W, *p, sad, by, nr, c->band.wbuf, wimg_layout,
+	                            wout, mc, mc + (size_t)W*H);
+}
+
+// The exact redo of flagged pixels is launched for a CAPACITY -- the whole band: the list buffer holds every pixel of it,
+// the redo kernels share the list in grid-stride loops and read the count on the device -- so however many pixels flag
+// (adversarial images: exact ties everywhere) each is redone once, the host never waits for the count, and no pass is
+// ever repeated as a whole for it.  (Round 4 launched for 1/32 of the band, at most 16 384 pixels, and repeated the
+// whole pass in mode 0 beyond that: a cliff at 0.79 % of C3.)
+static int redo_capacity(size_t band_pixels) { return (int)std::min<size_t>(band_pixels, (size_t)1 << 30); }
+
+// widest candidate range a pixel of a row-aligned rig can have, in columns: disparity(min_depth) - disparity(max_depth)
+static double disparity_span(const srh_params &p, double fx_bx) {
+	return fx_bx*p.image_scale*fabs(1.0/p.min_depth - 1.0/p.max_depth);
+}
+
+// ---- plan: dense row-aligned kernels (or the fused kernel), or the general kernels.  Launches nothing.
+// (cost_sad: the dense plan only with option "sad_dense", its cost rows filled by twoview_strip_sad_kernel; no per-tile
+// and no fused kernel -- without the option rectified rigs take the row-run lists too)
+TvPlan TvPass::plan() const {
+	const ViewHost &L = c->views[ref], &Rv = c->views[oth];
+	TvPlan pl;
+	pl.dense = !c->force_generic && (!sad || c->sad_dense) && (R == 5 || R == 2);
 	double fx_bx = 0;
-	if (dense && !rig_is_row_aligned(L.cam, Rv.cam, &fx_bx)) {
-		// test hook: any pinhole pair may be *proposed* (the scan kernel refutes the proposal, see the redo below)
+	if (pl.dense && !rig_is_row_aligned(L.cam, Rv.cam, &fx_bx)) {
+		// test hook: any pinhole pair may be *proposed* (the scan kernel refutes the proposal, see the controller's redo)
 		const bool pinhole = !L.cam.is_distorted && !Rv.cam.is_distorted && !L.cam.is_refractive && !Rv.cam.is_refractive;
-		if (c->force_dense && pinhole) fx_bx = (double)(W + 8)/(p->image_scale*fabs(1.0/p->min_depth - 1.0/p->max_depth));
-		else dense = false;
+		if (c->force_dense && pinhole) fx_bx = (double)(W + 8)/disparity_span(*p, 1.0);
+		else pl.dense = false;
 	}
-	if (dense) {
-		// widest candidate range a pixel can have: disparity(min_depth) - disparity(max_depth) + margins
-		const double span = fx_bx*p->image_scale*fabs(1.0/p->min_depth - 1.0/p->max_depth);
-		if (!(p->min_depth > 0) || !(p->max_depth > 0) || !(span < 4096.0)) dense = false;
-		else cstride = (((int)ceil(span) + 3) + 7) & ~7;
-		if (cstride > W + 8) cstride = (W + 8 + 7) & ~7;
-		// cost_sad has the strip form only: a range wider than its chunk takes the candidate lists
-		if (sad && dense && cstride + SRH_WTILE > strip_chunk_columns()) dense = false;
-	}
+	if (!pl.dense) return pl;
+	const double span = disparity_span(*p, fx_bx);                // (+ margins: the stride)
+	if (!(p->min_depth > 0) || !(p->max_depth > 0) || !(span < 4096.0)) pl.dense = false;
+	else pl.cstride = (((int)ceil(span) + 3) + 7) & ~7;
+	if (pl.cstride > W + 8) pl.cstride = (W + 8 + 7) & ~7;
+	// cost_sad has the strip form only: a range wider than its chunk takes the candidate lists
+	if (sad && pl.dense && pl.cstride + SRH_WTILE > strip_chunk_columns()) pl.dense = false;
+	pl.fused = pl.dense && !sad && c->use_fused && (c->arith == 0 || c->arith == 3) &&
+	           p->num_depth_levels <= SRH_FUSED_MAXC && span + 1.0 <= (double)SRH_FUSED_MAXC;
+	return pl;
+}
 
-	c->last_fused = false;
-	// ---- row-aligned rig whose candidate range fits an LDS cost row: one fused kernel per band (srh_fused.hip)
-	if (dense && !sad && c->use_fused && (c->arith == 0 || c->arith == 3) && p->num_depth_levels <= SRH_FUSED_MAXC &&
-	    fx_bx*p->image_scale*fabs(1.0/p->min_depth - 1.0/p->max_depth) + 1.0 <= (double)SRH_FUSED_MAXC) {
-		HIP_TRY(hipMemsetAsync(c->d_cnt, 0, sizeof(Counters), c->stream));
-		if ((rc = c->band.tnum.ensure((size_t)p->num_depth_levels))) return rc;
-		{ Scope s(c, "pinhole_label_table_kernel");
-		  launch_pinhole_label_table(c->stream, c->d_views, ref, *p, false, c->band.tnum); }
-		size_t rows = budget / ((size_t)T*sizeof(double)*(size_t)W);
-		if (rows < 1) rows = 1;
-		if (rows > (size_t)(y1 - y0)) rows = (size_t)(y1 - y0);
-		if ((rc = c->band.wbuf.ensure(wbuf_doubles(W, (int)rows, T)))) return rc;
-		bool launched = true;
-		for (int by = y0; by < y1 && launched; by += (int)rows) {
-			if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
-			const int nr = std::min((int)rows, y1 - by);
+// ---- row-aligned rig whose candidate range fits an LDS cost row: one fused kernel per band (srh_fused.hip).
+// stands: the kernel had an instantiation and every curve was monotone, on its row and inside the LDS tile
+int TvPass::run_fused(bool &stands) const {
+	int rc;
+	stands = false;
+	HIP_TRY(hipMemsetAsync(c->d_cnt, 0, sizeof(Counters), c->stream));
+	if ((rc = c->band.tnum.ensure((size_t)p->num_depth_levels))) return rc;
+	{ Scope s(c, "pinhole_label_table_kernel");
+	  launch_pinhole_label_table(c->stream, c->d_views, ref, *p, false, c->band.tnum); }
+	const int rows = (int)rows_per_band((size_t)T*sizeof(double));
+	if ((rc = c->band.wbuf.ensure(wbuf_doubles(W, rows, T)))) return rc;
+	bool launched = true;
+	for (int by = y0; by < y1 && launched; by += rows) {
+		if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
+		const int nr = std::min(rows, y1 - by);
+		run_weights(c, ref, W, *p, by, nr, SRH_WTILE);
+		Scope s(c, "twoview_fused_kernel");
+		launched = launch_twoview_fused(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, c->band.tnum, c->d_cnt, wout);
+		if (launched) winner_costs(by, nr, false);
+	}
+	HIP_TRY(hipGetLastError());
+	if (!launched) return SRH_OK;
+	Counters hc;
+	if ((rc = read_back(c, &hc, c->d_cnt, sizeof(hc)))) return rc;
+	stands = hc.not_row_aligned == 0;
+	return SRH_OK;
+}
+
+// ---- arbitrary geometry: candidate lists, evaluated in row runs (srh_rows.hip) or in list order (srh_list.hip)
+
+// every list and every pixel's cost slots fitted the capacities, no curve crossed more than SRH_ROWS_NR rows
+// (mx: the kernels' maxima in d_span -- longest list, most cost slots, a curve over too many rows)
+static bool tv_lists_fit(const int *mx, int cmax, int smax) {
+	return mx[0] <= cmax && ((mx[1] + 7) & ~7) <= smax && mx[2] == 0;
+}
+
+// A standing row-run pass teaches the context its capacities, what later runs of the pair are queued with: the
+// capacities the pass stood on -- or, when they were a guess, what the pass measured (the tight strides a counting pass
+// would have given) -- and how the pair's lists are best evaluated: short spans (steep curves) fill their 8-column blocks
+// badly, a slot costs ~0.4 of a candidate evaluated in list order, so beyond 2.2 slots per candidate the other path wins
+static void tv_learn_lists(srh_context *c, int ref, int oth, bool guessed, int cmax, int smax, const int *mx, const Counters &h) {
+	const int cm = guessed ? std::max(8, (mx[0] + 7) & ~7) : cmax;
+	const int sm = guessed ? std::max(cm + 64, (mx[1] + 7) & ~7) : smax;
+	if (cm > c->list_cmax_hint) c->list_cmax_hint = cm;
+	if (sm > c->list_smax_hint) c->list_smax_hint = sm;
+	c->views[ref].list_mode[oth] = (h.n_slots > 2.2*(double)h.n_listed) ? 2 : 1;
+}
+
+// srh_twoview_compute's optimistic passes: the counters (lists: and the kernels' maxima) travel to pinned memory behind
+// the kernels, and the record says what the pass stood on; the caller verifies both passes with one wait (tv_pass_stands)
+static int tv_defer_queue(srh_context *c, srh_context::TvDefer &d, bool lists, bool strip, bool cert) {
+	HIP_TRY(hipMemcpyAsync(d.host, c->d_cnt, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
+	if (lists) HIP_TRY(hipMemcpyAsync(d.span, c->d_span, 4*sizeof(int), hipMemcpyDeviceToHost, c->stream));
+	d.queued = true; d.lists = lists; d.strip = strip; d.cert = cert;
+	return SRH_OK;
+}
+
+// what no pass of the lists repeats: the other view's "window fully usable" plane, the label table, the first capacities
+int TvPass::lists_prepare(TvLists &S) const {
+	int rc;
+	if ((rc = c->band.lcount.ensure((size_t)(y1 - y0)*W))) return rc;
+	ViewHost &O = c->views[oth];
+	if ((rc = sad ? ensure_fulls(c, O, R) : ensure_full(c, O, R))) return rc;
+	// the label-only part of pointFromDepth, once per pass instead of once per pixel and label
+	if ((rc = c->band.tnum.ensure((size_t)p->num_depth_levels))) return rc;
+	{ Scope s(c, "label_plane_table_kernel");
+	  launch_label_plane_table(c->stream, c->d_views, ref, *p, false, c->band.tnum); }
+	// list capacity: the longest list seen so far on this context (hint); the FIRST time a guess from the geometry
+	// (estimate_list_capacity: a few dozen curves' coarse polylines projected on the host -- round 5 ran a counting pass
+	// there, twoview_count_kernel, 10 ms of a C5 pair's first call, and then sized the slots too tightly, so that the
+	// pass was repeated: 104 ms for a pair whose steady state is 61).  A run that overflows its capacity is repeated
+	// with the true maximum: the guess decides how long a pair's first call takes, never what it computes.
+	int smax_guess = 0;
+	S.cmax = c->list_cmax_hint;
+	if (S.cmax <= 0 && c->list_count_pass) {
+		HIP_TRY(hipMemsetAsync(c->d_span, 0, sizeof(int), c->stream));
+		{ Scope s(c, "twoview_count_kernel");
+		  launch_twoview_count(c->stream, c->d_views, ref, oth, W, *p, y0, y1 - y0, c->band.lcount, c->d_cnt, c->d_span, c->band.tnum); }
+		int maxc = 0;
+		if ((rc = read_back(c, &maxc, c->d_span, sizeof(int)))) return rc;
+		S.cmax = std::max(8, (maxc + 7) & ~7);
+	} else if (S.cmax <= 0) {
+		estimate_list_capacity(c->views[ref].cam, O.cam, W, H, O.w, O.h, *p, y0, y1, S.cmax, smax_guess);
+		S.guessed = true;
+	}
+	S.rows_mode = c->list_rows && W < 32768 && H < 32768;     // spans and row origins are stored as 16-bit signed
+	if (c->views[ref].list_mode[oth] == 2) S.rows_mode = false;   // learnt: steep curves, list order is cheaper
+	S.smax = c->list_smax_hint > 0 ? c->list_smax_hint : (S.guessed ? smax_guess : S.cmax + 64);
+	return SRH_OK;
+}
+
+// one band of the row-run lists: list kernel, support windows beside it, cost, scan, the certified redo
+int TvPass::lists_rows_band(const TvLists &S, int by, int nr) const {
+	ViewHost &O = c->views[oth];
+	int32_t *cnt_band = c->band.lcount + (size_t)(by - y0)*W;
+	// the row-run cost kernel takes the pixels' constants (meanL, totalWeight, sum2, 1/totalWeight, SA) from the weights
+	// kernel, which has the window in registers anyway, instead of making them on one lane in eight per tile
+	double *pconst = sad ? nullptr : (double *)c->band.pconst;
+	// The list kernel does not need the support windows, and its last waves drain for long (a wave walks
+	// its 64 curves for ~2 ms): the windows are computed on a side stream queued behind it -- the geodesic
+	// kernel's register-heavy waves only find room on a SIMD once the list kernel's have left it.
+	if (!c->side_stream) {
+		HIP_TRY(hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking));
+		HIP_TRY(hipEventCreateWithFlags(&c->side_go, hipEventDisableTiming));
+		HIP_TRY(hipEventCreateWithFlags(&c->side_done, hipEventDisableTiming));
+	}
+	HIP_TRY(hipEventRecord(c->side_go, c->stream));               // the window buffer's last readers are done by then
+	{ Scope s(c, "twoview_rows_list_kernel");
+	  launch_twoview_rows_list(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.lcand, S.cmax,
+	                           cnt_band, c->band.lrowinfo, c->band.lmeta, S.smax, c->d_cnt, c->d_span, c->band.tnum); }
+	if (c->side_weights) {
+		HIP_TRY(hipStreamWaitEvent(c->side_stream, c->side_go, 0));
+		std::swap(c->stream, c->side_stream);                     // (Scope and the launchers read c->stream)
+		run_weights(c, ref, W, *p, by, nr, SRH_WTILE, pconst, true);
+		std::swap(c->stream, c->side_stream);
+		HIP_TRY(hipEventRecord(c->side_done, c->side_stream));
+		HIP_TRY(hipStreamWaitEvent(c->stream, c->side_done, 0));
+	} else run_weights(c, ref, W, *p, by, nr, SRH_WTILE, pconst, true);
+	if (S.cert) HIP_TRY(hipMemsetAsync(c->band.cflag, 0, sizeof(uint32_t), c->stream));
+	HIP_TRY(hipMemsetAsync(&c->d_cnt->strip_ticket, 0, 2*sizeof(unsigned int), c->stream));   // the cost kernel's waves draw their tiles from it
+	if (sad) {
+		Scope s(c, "twoview_rows_sad_kernel");
+		launch_twoview_rows_sad(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, O.fulls,
+		                        c->band.lrowinfo, c->band.lmeta, c->band.cost, S.smax, c->d_cnt);
+	} else {
+		Scope s(c, "twoview_rows_cost_kernel");
+		launch_twoview_rows_cost(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, O.full,
+		                         c->band.lrowinfo, c->band.lmeta, c->band.cost, S.smax, c->d_cnt, S.cert ? (c->cert_form == 1 ? 5 : 3) : 0,
+		                         pconst, S.cert && c->rows_masked ? O.tvp : nullptr, c->num_cus,
+		                         c->rows_masked == 1 ? (const uint32_t *)(O.full + full_stat_offset((size_t)O.w*O.h)) : nullptr);
+	}
+	{ Scope s(c, "twoview_rows_scan_kernel");
+	  launch_twoview_rows_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, cnt_band, c->band.lcand, S.cmax,
+	                           c->band.lrowinfo, c->band.lmeta, c->band.cost, S.smax, S.cert ? c->band.cflag : nullptr, -1, c->d_cnt, wout); }
+	if (S.cert) {
+		// certified arithmetic: the flagged pixels once more in the reference's arithmetic, launched for a capacity
+		// (a list cut by a too small capacity is harmless here: the pass is repeated anyway)
+		const int cap = redo_capacity((size_t)nr*W);
+		{ Scope s(c, "twoview_rows_refill_kernel");
+		  launch_twoview_rows_refill(c->stream, W, O.w, *p, by, c->band.cflag, cap, c->band.wbuf, c->views[ref].tvp, O.tvp,
+		                             c->band.lrowinfo, c->band.lmeta, c->band.cost, S.smax, c->d_cnt); }
+		Scope s(c, "twoview_rows_rescan_kernel");
+		launch_twoview_rows_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, cnt_band, c->band.lcand, S.cmax,
+		                         c->band.lrowinfo, c->band.lmeta, c->band.cost, S.smax, c->band.cflag, cap, c->d_cnt, wout);
+	}
+	winner_costs(by, nr, true);
+	return SRH_OK;
+}
+
+// one pass of the lists with the capacities and in the mode of S: counters and maxima reset, buffers, every band queued
+int TvPass::lists_pass(TvLists &S) const {
+	int rc;
+	HIP_TRY(hipMemsetAsync(c->d_cnt, 0, sizeof(Counters), c->stream));
+	HIP_TRY(hipMemsetAsync(c->d_span, 0, 4*sizeof(int), c->stream));
+	const bool rows_mode = S.rows_mode;
+	const int ccap = rows_mode ? S.smax : S.cmax;                 // cost values per pixel
+	// (row runs: the windows in the LDS-image layout, window rows padded to an even tap count -- the cost kernel's
+	// waves fetch them by LDS-DMA)
+	const size_t per_px = (size_t)(rows_mode ? (2*R + 1)*wimg_wp(R) : T)*sizeof(double) + (size_t)ccap*sizeof(double) + (size_t)S.cmax*sizeof(uint32_t)
+	                      + (rows_mode ? (SRH_ROWS_NR + 1)*sizeof(uint32_t) : 0);
+	const size_t lrows = S.lrows = rows_per_band(per_px);
+	if ((rc = c->band.wbuf.ensure(rows_mode ? wimg_doubles(W, (int)lrows, R) : wbuf_doubles(W, (int)lrows, T)))) return rc;
+	// row runs: lists and row tables are tiled per 64 pixels, cost slots per 32-pixel tile of a row
+	const size_t px64 = (lrows*W + 63) & ~(size_t)63, px32 = lrows*(size_t)((W + 7)/8)*8;        /* (cost slots: tiles of 8 pixels) */
+	if ((rc = c->band.cost.ensure((rows_mode ? px32 : lrows*W)*(size_t)ccap))) return rc;
+	if ((rc = c->band.lcand.ensure((rows_mode ? px64 : lrows*W)*(size_t)S.cmax))) return rc;
+	if (rows_mode && !sad && (rc = c->band.pconst.ensure((lrows*(size_t)W + SRH_WTILE)*SRH_PC))) return rc;
+	if (rows_mode) {
+		if ((rc = c->band.lrowinfo.ensure(px64*(size_t)SRH_ROWS_NR))) return rc;
+		if ((rc = c->band.lmeta.ensure(lrows*W))) return rc;
+		if (S.cert && (rc = c->band.cflag.ensure(lrows*W + 1))) return rc;
+		// NaN-bordered planes of both views: the general cost of the certified redo reads them without bound tests
+		if (S.cert && ((rc = ensure_tvp(c, c->views[ref])) || (rc = ensure_tvp(c, c->views[oth])))) return rc;
+	}
+	for (int by = y0; by < y1; by += (int)lrows) {
+		if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
+		const int nr = std::min((int)lrows, y1 - by);
+		if (rows_mode) {
+			if ((rc = lists_rows_band(S, by, nr))) return rc;
+			continue;
+		}
+			int32_t *cnt_band = c->band.lcount + (size_t)(by - y0)*W;
 			run_weights(c, ref, W, *p, by, nr, SRH_WTILE);
-			Scope s(c, "twoview_fused_kernel");
-			launched = launch_twoview_fused(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, c->band.tnum, c->d_cnt, wout);
-			if (launched) winner_costs(by, nr, false);
-		}
-		HIP_TRY(hipGetLastError());
-		if (launched) {
-			// the result stands only if every curve was monotone, on its row and inside the LDS tile
-			Counters hc;
-			HIP_TRY(hipMemcpyAsync(&hc, c->d_cnt, sizeof(hc), hipMemcpyDeviceToHost, c->stream));
-			HIP_TRY(hipStreamSynchronize(c->stream));
-			if (hc.not_row_aligned == 0) {
-				c->stats.used_dense_path = 1;
-				c->last_fused = true;
-				return SRH_OK;
+			{ Scope s(c, "twoview_list_kernel");
+			  launch_twoview_list(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.lcand, S.cmax,
+			                      cnt_band, c->d_cnt, c->d_span, c->band.tnum); }
+			if (sad) {
+				Scope s(c, "twoview_list_sad_kernel");
+				launch_twoview_list_sad(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf,
+				                        cnt_band, c->band.lcand, c->band.cost, S.cmax, c->d_cnt);
+			} else {
+				Scope s(c, "twoview_list_cost_kernel");
+				launch_twoview_list_cost(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, c->views[oth].full,
+				                         cnt_band, c->band.lcand, c->band.cost, S.cmax, c->d_cnt);
 			}
-		}
+			{ Scope s(c, "twoview_list_scan_kernel");
+			  launch_twoview_list_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, cnt_band, c->band.lcand, c->band.cost, S.cmax, wout); }
+			winner_costs(by, nr, false);
 	}
+	return SRH_OK;
+}
 
-	// the persistent strip form of the cost kernel (srh_strip.hip): exact / fma arithmetic, candidate ranges of a
-	// 32-pixel tile inside one LDS chunk; anything else, or a range that turns out wider, takes the per-tile kernel
-	// (and enough tiles to keep every persistent workgroup busy for dozens of tiles: a small image is better served by
-	// one workgroup per tile; option strip = 4 / 8 forces the strip kernel for tests)
-	bool strip = dense && (sad || (c->strip != 0 && c->arith != 2)) && cstride + SRH_WTILE <= strip_chunk_columns();
-	// certified arithmetic (arith = 3, the default): fused cost loops in the strip kernel + the certified scan; where the
-	// strip kernel does not run, or the parameters leave the bound no room, the reference's arithmetic
-	bool cert_ok = c->arith == 3 && !sad && cert_bound(*p).ok != 0;
-	c->stats.n_certified = c->stats.n_flagged = 0;
-	// The exact redo of flagged pixels is launched for a CAPACITY -- the whole band: the list buffer holds every pixel of it,
-	// the redo kernels share the list in grid-stride loops and read the count on the device -- so however many pixels flag
-	// (adversarial images: exact ties everywhere) each is redone once, the host never waits for the count, and no pass is
-	// ever repeated as a whole for it.  (Round 4 launched for 1/32 of the band, at most 16 384 pixels, and repeated the
-	// whole pass in mode 0 beyond that: a cliff at 0.79 % of C3.)
-	auto redo_capacity = [](size_t band_pixels) { return (int)std::min<size_t>(band_pixels, (size_t)1 << 30); };
-	for (int attempt = 0; attempt < 4; ++attempt) {
-		HIP_TRY(hipMemsetAsync(c->d_cnt, 0, sizeof(Counters), c->stream));
-		// ---- arbitrary geometry: candidate lists (the one-thread-per-pixel walk kernel is the last resort)
-		// (a negative wta_margin -- not the reference's: its margin is the constant +1e-10, twoviewstereo.cpp:293 -- makes a
-		// revisited winner beat itself, so the candidate lists' dropped joint duplicates would matter: the walk kernel, which
-		// visits every point, takes such a run)
-		if (!dense && !c->force_walk && R <= 5 && W < 65536 && H < 65536 && p->wta_margin >= 0) {
-			const size_t npix = (size_t)(y1 - y0)*W;
-			if ((rc = c->band.lcount.ensure(npix))) return rc;
-			ViewHost &O = c->views[oth];
-			if (sad && O.fulls_r != R) {
-				if (!O.fulls) HIP_TRY(O.fulls.alloc((size_t)O.w*O.h));
-				Scope s(c, "sad_full_window_kernel");
-				launch_sad_full_window(c->stream, O.mask, O.w, O.h, R, O.fulls);
-				O.fulls_r = R;
-			}
-			if (!sad && O.full_r != R) {
-				Scope s(c, "full_window_kernel");
-				uint32_t *stat = (uint32_t *)(O.full + full_stat_offset((size_t)O.w*O.h));
-				HIP_TRY(hipMemsetAsync(stat, 0, 2*sizeof(uint32_t), c->stream));
-				launch_full_window(c->stream, O.gray_tv, O.w, O.h, R, O.full, stat);
-				O.full_r = R;
-			}
-			// the label-only part of pointFromDepth, once per pass instead of once per pixel and label
-			if ((rc = c->band.tnum.ensure((size_t)p->num_depth_levels))) return rc;
-			{ Scope s(c, "label_plane_table_kernel");
-			  launch_label_plane_table(c->stream, c->d_views, ref, *p, false, c->band.tnum); }
-			// list capacity: the longest list seen so far on this context (hint); the FIRST time a guess from the geometry
-			// (estimate_list_capacity: a few dozen curves' coarse polylines projected on the host -- round 5 ran a counting pass
-			// there, twoview_count_kernel, 10 ms of a C5 pair's first call, and then sized the slots too tightly, so that the
-			// pass was repeated: 104 ms for a pair whose steady state is 61).  A run that overflows its capacity is repeated
-			// with the true maximum: the guess decides how long a pair's first call takes, never what it computes.
-			int cmax = c->list_cmax_hint, smax_guess = 0;
-			bool guessed = false;
-			if (cmax <= 0 && c->list_count_pass) {
-				HIP_TRY(hipMemsetAsync(c->d_span, 0, sizeof(int), c->stream));
-				{ Scope s(c, "twoview_count_kernel");
-				  launch_twoview_count(c->stream, c->d_views, ref, oth, W, *p, y0, y1 - y0, c->band.lcount, c->d_cnt, c->d_span, c->band.tnum); }
-				int maxc = 0;
-				HIP_TRY(hipMemcpyAsync(&maxc, c->d_span, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-				HIP_TRY(hipStreamSynchronize(c->stream));
-				cmax = std::max(8, (maxc + 7) & ~7);
-			} else if (cmax <= 0) {
-				estimate_list_capacity(c->views[ref].cam, O.cam, W, H, O.w, O.h, *p, y0, y1, cmax, smax_guess);
-				guessed = true;
-			}
-			bool rows_mode = c->list_rows && W < 32768 && H < 32768;       // spans and row origins are stored as 16-bit signed
-			if (c->views[ref].list_mode[oth] == 2) rows_mode = false;      // learnt: steep curves, list order is cheaper
-			int smax = c->list_smax_hint > 0 ? c->list_smax_hint : (guessed ? smax_guess : cmax + 64);
-			for (int pass = 0; pass < 6; ++pass) {
-				HIP_TRY(hipMemsetAsync(c->d_cnt, 0, sizeof(Counters), c->stream));
-				HIP_TRY(hipMemsetAsync(c->d_span, 0, 4*sizeof(int), c->stream));
-				const int ccap = rows_mode ? smax : cmax;             // cost values per pixel
-				// (row runs: the windows in the LDS-image layout, window rows padded to an even tap count -- the cost kernel's
-				// waves fetch them by LDS-DMA)
-				const size_t per_px = (size_t)(rows_mode ? (2*p->window_radius + 1)*wimg_wp(p->window_radius) : T)*sizeof(double) + (size_t)ccap*sizeof(double) + (size_t)cmax*sizeof(uint32_t)
-				                      + (rows_mode ? (SRH_ROWS_NR + 1)*sizeof(uint32_t) : 0);
-				size_t lrows = budget / (per_px*(size_t)W);
-				if (lrows < 1) lrows = 1;
-				if (lrows > (size_t)(y1 - y0)) lrows = (size_t)(y1 - y0);
-				if ((rc = c->band.wbuf.ensure(rows_mode ? wimg_doubles(W, (int)lrows, p->window_radius) : wbuf_doubles(W, (int)lrows, T)))) return rc;
-				// row runs: lists and row tables are tiled per 64 pixels, cost slots per 32-pixel tile of a row
-				const size_t px64 = (lrows*W + 63) & ~(size_t)63, px32 = lrows*(size_t)((W + 7)/8)*8;        /* (cost slots: tiles of 8 pixels) */
-				if ((rc = c->band.cost.ensure((rows_mode ? px32 : lrows*W)*(size_t)ccap))) return rc;
-				if ((rc = c->band.lcand.ensure((rows_mode ? px64 : lrows*W)*(size_t)cmax))) return rc;
-				const bool rows_cert = rows_mode && cert_ok;
-				// the row-run cost kernel takes the pixels' constants (meanL, totalWeight, sum2, 1/totalWeight, SA) from the weights
-				// kernel, which has the window in registers anyway, instead of making them on one lane in eight per tile
-				const bool rows_pc = rows_mode && !sad;
-				if (rows_pc && (rc = c->band.pconst.ensure((lrows*(size_t)W + SRH_WTILE)*SRH_PC))) return rc;
-				if (rows_mode) {
-					if ((rc = c->band.lrowinfo.ensure(px64*(size_t)SRH_ROWS_NR))) return rc;
-					if ((rc = c->band.lmeta.ensure(lrows*W))) return rc;
-					if (rows_cert && (rc = c->band.cflag.ensure(lrows*W + 1))) return rc;
-					if (rows_cert) {
-						// NaN-bordered planes of both views: the general cost of the certified redo reads them without bound tests
-						for (int k = 0; k < 2; ++k) {
-							ViewHost &v = c->views[k == 0 ? ref : oth];
-							if (!v.tvp) HIP_TRY(v.tvp.alloc(padded_size(v.w, v.h)));
-							if (!v.tvp_valid) {
-								Scope s(c, "padded_plane_kernel");
-								launch_padded_plane(c->stream, v.gray_tv, v.w, v.h, v.tvp);
-								v.tvp_valid = true;
-							}
-						}
-					}
-				}
-				for (int by = y0; by < y1; by += (int)lrows) {
-					if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
-					const int nr = std::min((int)lrows, y1 - by);
-					int32_t *cnt_band = c->band.lcount + (size_t)(by - y0)*W;
-					if (rows_mode) {
-						// The list kernel does not need the support windows, and its last waves drain for long (a wave walks
-						// its 64 curves for ~2 ms): the windows are computed on a side stream queued behind it -- the geodesic
-						// kernel's register-heavy waves only find room on a SIMD once the list kernel's have left it.
-						if (!c->side_stream) {
-							HIP_TRY(hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking));
-							HIP_TRY(hipEventCreateWithFlags(&c->side_go, hipEventDisableTiming));
-							HIP_TRY(hipEventCreateWithFlags(&c->side_done, hipEventDisableTiming));
-						}
-						HIP_TRY(hipEventRecord(c->side_go, c->stream));             // the window buffer's last readers are done by then
-						{ Scope s(c, "twoview_rows_list_kernel");
-						  launch_twoview_rows_list(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.lcand, cmax,
-						                           cnt_band, c->band.lrowinfo, c->band.lmeta, smax, c->d_cnt, c->d_span, c->band.tnum); }
-						if (c->side_weights) {
-							HIP_TRY(hipStreamWaitEvent(c->side_stream, c->side_go, 0));
-							std::swap(c->stream, c->side_stream);
-							run_weights(c, ref, W, *p, by, nr, SRH_WTILE, rows_pc ? c->band.pconst : nullptr, true);
-							std::swap(c->stream, c->side_stream);
-							HIP_TRY(hipEventRecord(c->side_done, c->side_stream));
-							HIP_TRY(hipStreamWaitEvent(c->stream, c->side_done, 0));
-						} else run_weights(c, ref, W, *p, by, nr, SRH_WTILE, rows_pc ? c->band.pconst : nullptr, true);
-						if (rows_cert) HIP_TRY(hipMemsetAsync(c->band.cflag, 0, sizeof(uint32_t), c->stream));
-						HIP_TRY(hipMemsetAsync(&c->d_cnt->strip_ticket, 0, 2*sizeof(unsigned int), c->stream));   // the cost kernel's waves draw their tiles from it
-						if (sad) {
-							Scope s(c, "twoview_rows_sad_kernel");
-							launch_twoview_rows_sad(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, O.fulls,
-							                        c->band.lrowinfo, c->band.lmeta, c->band.cost, smax, c->d_cnt);
-						} else
-						{ Scope s(c, "twoview_rows_cost_kernel");
-						  launch_twoview_rows_cost(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, O.full,
-						                           c->band.lrowinfo, c->band.lmeta, c->band.cost, smax, c->d_cnt, rows_cert ? (c->cert_form == 1 ? 5 : 3) : 0,
-						                           rows_pc ? c->band.pconst : nullptr, rows_cert && c->rows_masked ? O.tvp : nullptr, c->num_cus,
-						                           c->rows_masked == 1 ? (const uint32_t *)(O.full + full_stat_offset((size_t)O.w*O.h)) : nullptr); }
-						{ Scope s(c, "twoview_rows_scan_kernel");
-						  launch_twoview_rows_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, cnt_band, c->band.lcand, cmax,
-						                           c->band.lrowinfo, c->band.lmeta, c->band.cost, smax, rows_cert ? c->band.cflag : nullptr, -1, c->d_cnt, wout); }
-						if (rows_cert) {
-							// certified arithmetic: the flagged pixels once more in the reference's arithmetic, launched for a capacity
-							// (a list cut by a too small capacity is harmless here: the pass is repeated anyway)
-							const int cap = redo_capacity((size_t)nr*W);
-							{ Scope s(c, "twoview_rows_refill_kernel");
-							  launch_twoview_rows_refill(c->stream, W, O.w, *p, by, c->band.cflag, cap, c->band.wbuf, c->views[ref].tvp, O.tvp,
-							                             c->band.lrowinfo, c->band.lmeta, c->band.cost, smax, c->d_cnt); }
-							Scope s(c, "twoview_rows_rescan_kernel");
-							launch_twoview_rows_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, cnt_band, c->band.lcand, cmax,
-							                         c->band.lrowinfo, c->band.lmeta, c->band.cost, smax, c->band.cflag, cap, c->d_cnt, wout);
-						}
-						winner_costs(by, nr, true);
-						continue;
-					}
-					run_weights(c, ref, W, *p, by, nr, SRH_WTILE);
-					{ Scope s(c, "twoview_list_kernel");
-					  launch_twoview_list(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.lcand, cmax,
-					                      cnt_band, c->d_cnt, c->d_span, c->band.tnum); }
-					if (sad) {
-						Scope s(c, "twoview_list_sad_kernel");
-						launch_twoview_list_sad(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf,
-						                        cnt_band, c->band.lcand, c->band.cost, cmax, c->d_cnt);
-					} else
-					{ Scope s(c, "twoview_list_cost_kernel");
-					  launch_twoview_list_cost(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, O.full,
-					                           cnt_band, c->band.lcand, c->band.cost, cmax, c->d_cnt); }
-					{ Scope s(c, "twoview_list_scan_kernel");
-					  launch_twoview_list_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, cnt_band, c->band.lcand, c->band.cost, cmax, wout); }
-					winner_costs(by, nr, false);
-				}
-				if (c->defer && attempt == 0 && pass == 0 && rows_mode &&
-				    ((c->list_cmax_hint > 0 && c->list_smax_hint > 0 && c->views[ref].list_mode[oth] == 1) ||
-				     (guessed && c->views[ref].list_mode[oth] == 0))) {
-					// optimistic (srh_twoview_compute): capacities and path are those earlier runs of this pair learnt -- or, for a
-					// pair's FIRST call, the host's guess and the row-run path --; the maxima
-					// and counters travel to pinned memory behind the kernels, the caller verifies both passes with one wait (a
-					// pass that does not stand -- a longer list after a re-upload, say -- is redone with the wait per pass)
-					HIP_TRY(hipMemcpyAsync(c->defer->host, c->d_cnt, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
-					HIP_TRY(hipMemcpyAsync(c->defer->span, c->d_span, 4*sizeof(int), hipMemcpyDeviceToHost, c->stream));
-					c->defer->queued = true; c->defer->lists = true; c->defer->strip = false; c->defer->cert = rows_cert;
-					c->defer->cmax = cmax; c->defer->smax = smax;
-					c->defer->guessed = guessed; c->defer->ref = ref; c->defer->oth = oth;
-					if (c->debug_trace) fprintf(stderr, "[srh trace] lists %d>%d queued unverified: cmax %d smax %d guessed %d\n", ref, oth, cmax, smax, (int)guessed);
-					c->stats.used_strip_kernel = 0;
-					c->stats.used_dense_path = 0;
-					HIP_TRY(hipGetLastError());
-					return SRH_OK;
-				}
-				int mx[4] = { 0, 0, 0, 0 };
-				HIP_TRY(hipMemcpyAsync(mx, c->d_span, 4*sizeof(int), hipMemcpyDeviceToHost, c->stream));
-				HIP_TRY(hipStreamSynchronize(c->stream));
-				const int maxc = mx[0];
-				if (c->debug_trace) fprintf(stderr, "[srh trace] lists %d>%d verified pass %d: cmax %d smax %d guessed %d -> longest list %d, slots %d, rows over %d\n",
-				                            ref, oth, pass, cmax, smax, (int)guessed, mx[0], mx[1], mx[2]);
-				if (rows_mode) {
-					// a curve crossing more than SRH_ROWS_NR rows, or more slots than the 16-bit slot base
-					// holds: this pair is evaluated in list order instead
-					const int need = (mx[1] + 7) & ~7;
-					if (mx[2] || need > 65528) {
-						rows_mode = false; c->views[ref].list_mode[oth] = 2;
-						if (maxc > cmax) cmax = (maxc + 7) & ~7;
-						continue;
-					}
-					if (maxc <= cmax && need <= smax) {
-						// what later runs of the pair are queued with: the capacities this pass stood on -- or, when they were a
-						// guess, what the pass measured (the tight strides a counting pass would have given)
-						const int cm = guessed ? std::max(8, (maxc + 7) & ~7) : cmax;
-						const int sm = guessed ? std::max(cm + 64, need) : smax;
-						if (cm > c->list_cmax_hint) c->list_cmax_hint = cm;
-						if (sm > c->list_smax_hint) c->list_smax_hint = sm;
-						// short spans (steep curves) fill their 8-column blocks badly: a slot costs ~0.4 of a
-						// candidate evaluated in list order, so beyond 2.2 slots per candidate the other path wins
-						Counters hc;
-						HIP_TRY(hipMemcpyAsync(&hc, c->d_cnt, sizeof(hc), hipMemcpyDeviceToHost, c->stream));
-						HIP_TRY(hipStreamSynchronize(c->stream));
-						c->views[ref].list_mode[oth] = (hc.n_slots > 2.2*(double)hc.n_listed) ? 2 : 1;
-						if (hc.cert_overflow != 0) { cert_ok = false; continue; }   // more flagged pixels than the redo covers: mode 0
-						if (rows_cert) { c->stats.n_certified = (int64_t)hc.n_pixels; c->stats.n_flagged = (int64_t)hc.n_flagged; }
-						break;
-					}
-					if (maxc > cmax) { cmax = (maxc + 7) & ~7; if (need <= smax) smax = std::max(smax, cmax + 64); }
-					if (need > smax) smax = need;
-					guessed = false;                                      // (the repeat runs on measured maxima)
-					continue;
-				}
-				if (maxc <= cmax) {
-					const int cm = guessed ? std::max(8, (maxc + 7) & ~7) : cmax;
-					if (cm > c->list_cmax_hint) c->list_cmax_hint = cm;
-					break;
-				}
-				cmax = (maxc + 7) & ~7;                               // hint too small: repeat with the true maximum
-				guessed = false;
-			}
+// The candidate lists, with the capacity loop: a pass whose lists or cost slots overflowed is repeated with the measured
+// maxima, a pair whose curves do not suit row runs in list order, a certified pass with more flagged pixels than the redo
+// covers in the reference's arithmetic.  defer (srh_twoview_compute, a call's first attempt): a first row-run pass on
+// learnt or guessed capacities is handed over unverified (defer->queued) instead of being waited for.
+int TvPass::run_lists(bool cert_ok, srh_context::TvDefer *defer) const {
+	int rc;
+	TvLists S;
+	if ((rc = lists_prepare(S))) return rc;
+	for (int pass = 0; pass < 6; ++pass) {
+		S.cert = S.rows_mode && cert_ok;
+		if ((rc = lists_pass(S))) return rc;
+		if (defer && pass == 0 && S.rows_mode &&
+		    ((c->list_cmax_hint > 0 && c->list_smax_hint > 0 && c->views[ref].list_mode[oth] == 1) ||
+		     (S.guessed && c->views[ref].list_mode[oth] == 0))) {
+			// optimistic: capacities and path are those earlier runs of this pair learnt -- or, for a pair's FIRST call, the
+			// host's guess and the row-run path -- (a pass that does not stand -- a longer list after a re-upload, say -- is
+			// redone with the wait per pass)
+			if ((rc = tv_defer_queue(c, *defer, true, false, S.cert))) return rc;
+			defer->cmax = S.cmax; defer->smax = S.smax;
+			defer->guessed = S.guessed; defer->ref = ref; defer->oth = oth;
+			if (c->debug_trace) fprintf(stderr, "[srh trace] lists %d>%d queued unverified: cmax %d smax %d guessed %d\n", ref, oth, S.cmax, S.smax, (int)S.guessed);
+			c->stats.used_strip_kernel = 0;
+			c->stats.used_dense_path = 0;
 			HIP_TRY(hipGetLastError());
+			return SRH_OK;
+		}
+		int mx[4] = { 0, 0, 0, 0 };
+		if ((rc = read_back(c, mx, c->d_span, sizeof(mx)))) return rc;
+		const int maxc = mx[0];
+		if (c->debug_trace) fprintf(stderr, "[srh trace] lists %d>%d verified pass %d: cmax %d smax %d guessed %d -> longest list %d, slots %d, rows over %d\n",
+		                            ref, oth, pass, S.cmax, S.smax, (int)S.guessed, mx[0], mx[1], mx[2]);
+		if (S.rows_mode) {
+			// a curve crossing more than SRH_ROWS_NR rows, or more slots than the 16-bit slot base
+			// holds: this pair is evaluated in list order instead
+			const int need = (mx[1] + 7) & ~7;
+			if (mx[2] || need > 65528) {
+				S.rows_mode = false; c->views[ref].list_mode[oth] = 2;
+				if (maxc > S.cmax) S.cmax = (maxc + 7) & ~7;
+				continue;
+			}
+			if (tv_lists_fit(mx, S.cmax, S.smax)) {
+				Counters hc;
+				if ((rc = read_back(c, &hc, c->d_cnt, sizeof(hc)))) return rc;
+				tv_learn_lists(c, ref, oth, S.guessed, S.cmax, S.smax, mx, hc);
+				if (hc.cert_overflow != 0) { cert_ok = false; continue; }   // more flagged pixels than the redo covers: mode 0
+				if (S.cert) { c->stats.n_certified = (int64_t)hc.n_pixels; c->stats.n_flagged = (int64_t)hc.n_flagged; }
+				break;
+			}
+			if (maxc > S.cmax) { S.cmax = (maxc + 7) & ~7; if (need <= S.smax) S.smax = std::max(S.smax, S.cmax + 64); }
+			if (need > S.smax) S.smax = need;
+			S.guessed = false;                                    // (the repeat runs on measured maxima)
+			continue;
+		}
+		if (maxc <= S.cmax) {
+			const int cm = S.guessed ? std::max(8, (maxc + 7) & ~7) : S.cmax;
+			if (cm > c->list_cmax_hint) c->list_cmax_hint = cm;
 			break;
 		}
-		const bool tscan = dense && c->tscan != 0;
-		if (dense) {
-			if ((rc = c->band.tnum.ensure((size_t)p->num_depth_levels + 8))) return rc;   // (+ 8: the template scan reads the table in whole eights)
-			{ Scope s(c, "pinhole_label_table_kernel");
-			  launch_pinhole_label_table(c->stream, c->d_views, ref, *p, false, c->band.tnum); }
-			if (tscan) {
-				// the pass's candidate template: the reference's walk at one pixel (srh_dense.hip, "template scan")
-				if ((rc = c->band.stpl.ensure(scan_template_bytes()))) return rc;
-				Scope s(c, "twoview_template_kernel");
-				launch_scan_template(c->stream, c->d_views, ref, oth, *p, y0, y1 - y0, c->band.tnum, c->band.stpl);
-			}
-		}
-		size_t rows = 0;
-		for (int pass = 0; pass < 2; ++pass) {
-			const int wdoubles = strip ? (2*R + 1)*wimg_wp(R) : T;     // doubles per pixel window in the band buffer
-			const size_t per_pixel = (size_t)wdoubles*sizeof(double) + (dense ? (size_t)cstride*sizeof(double) : 0);
-			rows = budget / (per_pixel*(size_t)W);
-			if (rows < 1) rows = 1;
-			if (rows > (size_t)(y1 - y0)) rows = (size_t)(y1 - y0);
-			// the strip kernel wants dozens of tiles per persistent workgroup and launch; thin bands take the per-tile kernel
-			if (strip && !sad && c->strip == 1 && (size_t)((W + SRH_WTILE - 1)/SRH_WTILE)*rows < (size_t)48*2*c->num_cus) strip = false;
-			else break;
-		}
-		const bool wimg = strip;                                       // the band's windows in the LDS image's layout
-		const size_t wstride = SRH_WTILE;
-		if ((rc = c->band.wbuf.ensure(wimg ? wimg_doubles(W, (int)rows, R) : wbuf_doubles(W, (int)rows, T)))) return rc;
-		if (dense && (rc = c->band.cost.ensure(rows*(size_t)((W + 31)/32)*32*(size_t)cstride))) return rc;   // 32-pixel tiles
-		// (+ one tile of slack: the strip kernel copies whole 32-pixel pieces of these rows)
-		if (dense && (rc = c->band.pconst.ensure((rows*(size_t)W + SRH_WTILE)*SRH_PC))) return rc;
-		int lanes = 8;
-		if (dense && (rc = c->band.prange.ensure(rows*(size_t)W + SRH_WTILE))) return rc;
-		if (tscan && (rc = c->band.tileflag.ensure(rows*(size_t)((W + 63)/64) + 1))) return rc;
-		const bool cert = dense && cert_ok;
-		// (the strip kernel's certified form: 5 = one sweep over the window, 3 = the reference's two sweeps fused; option "cert_form")
-		const int cost_arith = c->arith == 3 ? (cert ? (c->cert_form == 1 ? 5 : 3) : 0) : c->arith;
-		if (cert && (rc = c->band.cflag.ensure(rows*(size_t)W + 1))) return rc;
-		const bool planes = dense && (R == 5 || R == 2);
-		if (strip) lanes = strip_block_lanes(cstride, c->strip == 1 ? 0 : c->strip);
-		if (planes) {
-			// NaN-bordered gray_tv planes of both views (strip kernel; the general cost of the left-out columns and of the
-			// certified redo on either dense path)
-			for (int k = 0; k < 2; ++k) {
-				ViewHost &v = c->views[k == 0 ? ref : oth];
-				if (!v.tvp) HIP_TRY(v.tvp.alloc(padded_size(v.w, v.h)));
-				if (!v.tvp_valid) {
-					Scope s(c, "padded_plane_kernel");
-					launch_padded_plane(c->stream, v.gray_tv, v.w, v.h, v.tvp);
-					v.tvp_valid = true;
-				}
-			}
-		}
-		if (strip && sad) {
-			if ((rc = ensure_sad_planes(c, c->views[oth], R))) return rc;
-		} else if (strip) {
-			// zero-bordered "window fully usable" plane of the other view
-			ViewHost &O = c->views[oth];
-			if (!O.fullp) HIP_TRY(O.fullp.alloc(padded_size(O.w, O.h)));
-			if (O.fullp_r != R) {
-				Scope s(c, "padded_full_kernel");
-				launch_padded_full(c->stream, O.gray_tv, O.w, O.h, R, O.fullp);
-				O.fullp_r = R;
-			}
-		}
+		S.cmax = (maxc + 7) & ~7;                                 // hint too small: repeat with the true maximum
+		S.guessed = false;
+	}
+	HIP_TRY(hipGetLastError());
+	return SRH_OK;
+}
 
-		for (int by = y0; by < y1; by += (int)rows) {
-			if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
-			const int nr = std::min((int)rows, y1 - by);
-			run_weights(c, ref, W, *p, by, nr, wstride, dense && !sad ? c->band.pconst : nullptr, wimg);
-			if (dense) {
-				Scope s(c, "pixel_range_kernel");
-				launch_pixel_range(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.tnum, cstride, c->band.prange);
-			}
-			if (dense) {
-				// the band's cost rows under one arithmetic: strip kernel or one workgroup per tile, then the left-out columns
-				auto cost_pass = [&](int arith) -> int {
-					if (sad) {
-						// (every column of [lo, hi] is written: no fill launch, which would evaluate cost_ncc)
-						HIP_TRY(hipMemsetAsync(&c->d_cnt->strip_ticket, 0, 2*sizeof(unsigned int), c->stream));
-						Scope s(c, "twoview_strip_sad_kernel");
-						if (!launch_twoview_strip_sad(c->stream, W, H, *p, by, nr, c->band.wbuf, c->band.prange, c->views[ref].tvp,
-						                              c->views[oth].grayp, c->views[oth].fullsp, c->band.cost, cstride, c->d_cnt, c->num_cus))
-							return fail(SRH_E_UNSUPPORTED, "twoview_strip_sad_kernel: no instantiation for radius %d", R);
-					} else if (strip) {
-						HIP_TRY(hipMemsetAsync(&c->d_cnt->strip_ticket, 0, 2*sizeof(unsigned int), c->stream));
-						{ Scope s(c, "twoview_strip_cost_kernel");
-						  launch_twoview_strip_cost(c->stream, c->d_views, ref, oth, W, H, *p, by, nr, c->band.wbuf, c->band.pconst, c->band.prange,
-						                            c->views[ref].tvp, c->views[oth].tvp, c->views[oth].fullp, c->band.cost, cstride,
-						                            c->d_cnt, arith, c->num_cus, lanes, c->diag && c->diag->raw); }
-						Scope s(c, "twoview_lazy_fill_kernel");
-						launch_twoview_lazy_fill(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.prange, c->band.wbuf, wstride,
-						                         c->views[ref].tvp, c->views[oth].tvp, true, lanes, lanes == 8, c->band.cost, cstride, c->d_cnt);
-					} else {
-						{ Scope s(c, "twoview_dense_cost_kernel");
-						  if (arith == 2)
-							launch_twoview_dense_cost_f32(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, wstride,
-							                              c->band.tnum, c->band.cost, cstride, c->d_cnt, c->band.pconst, c->f32_form);
-						  else
-							launch_twoview_dense_cost(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, wstride,
-							                          c->band.tnum, c->band.cost, cstride, c->d_cnt, c->band.pconst, arith, c->band.prange); }
-						Scope s(c, "twoview_lazy_fill_kernel");
-						launch_twoview_lazy_fill(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.prange, c->band.wbuf, wstride,
-						                         planes ? c->views[ref].tvp : nullptr, planes ? c->views[oth].tvp : nullptr, false, 8,
-						                         arith != 5, c->band.cost, cstride, c->d_cnt);   // (the one-pass form leaves no column out)
-					}
-					return SRH_OK;
-				};
-				if (c->diag) {
-					// diagnostic: this band's cost rows under the arithmetic asked for, as the cost kernel leaves them (raw: the
-					// certified forms without the in-kernel exact redo, NaN where uncertified), and the pixels' column ranges
-					srh_context::Diag &dg = *c->diag;
-					dg.cstride = cstride; dg.rows = nr; dg.strip = strip;
-					const size_t nd = (size_t)nr*((W + 31)/32)*32*(size_t)cstride;
-					if (by != y0 || nr != y1 - y0) return fail(SRH_E_UNSUPPORTED, "cost rows: the rows asked for do not fit one band (%d of %d)", nr, y1 - y0);
-					if (dg.cost) {
-						if (dg.cost_doubles < nd) return fail(SRH_E_INVALID, "cost rows: buffer of %zu doubles, %zu needed", dg.cost_doubles, nd);
-						HIP_TRY(hipMemsetAsync(c->band.cost, 0xff, nd*sizeof(double), c->stream));   // (never-written entries read as a NaN with payload -1)
-						if ((rc = cost_pass(dg.form))) return rc;
-						HIP_TRY(hipMemcpyAsync(dg.cost, c->band.cost, nd*sizeof(double), hipMemcpyDeviceToHost, c->stream));
-						if (dg.range) HIP_TRY(hipMemcpyAsync(dg.range, c->band.prange, (size_t)nr*W*sizeof(PixRange), hipMemcpyDeviceToHost, c->stream));
-						HIP_TRY(hipStreamSynchronize(c->stream));
-					}
-					dg.done = true;
-					return SRH_OK;
-				}
-				if (cert) HIP_TRY(hipMemsetAsync(c->band.cflag, 0, sizeof(uint32_t), c->stream));
-				if ((rc = cost_pass(cost_arith))) return rc;
-				{ Scope s(c, "twoview_scan_kernel");
-				  launch_twoview_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.tnum, c->band.cost, cstride, c->d_cnt, c->band.prange,
-				                      cert ? c->band.cflag : nullptr, -1, cert && strip ? c->band.pconst : nullptr, tscan ? c->band.stpl : nullptr, c->band.tileflag, c->num_cus, wout, c->tscan_bound); }
-				if (cert) {
-					// the pixels whose decisions the bound does not cover, in the reference's arithmetic: their cost rows are
-					// refilled and they are scanned again -- launched for a capacity, the count stays on the device
-					const int cap = redo_capacity((size_t)nr*W);
-					{ Scope s(c, "twoview_refill_kernel");
-					  launch_twoview_refill(c->stream, W, *p, by, c->band.prange, c->band.cflag, cap, c->band.wbuf, wimg, c->views[ref].tvp,
-					                        c->views[oth].tvp, c->band.cost, cstride, c->d_cnt); }
-					Scope s(c, "twoview_rescan_kernel");
-					launch_twoview_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.tnum, c->band.cost, cstride, c->d_cnt, c->band.prange,
-					                    c->band.cflag, cap, nullptr, nullptr, nullptr, c->num_cus, wout);
-				}
-				winner_costs(by, nr, wimg);
-			} else {
-				{ Scope s(c, "twoview_generic_kernel");
-				  launch_twoview_generic(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, wstride, c->d_cnt, sad, wout); }
-				winner_costs(by, nr, false);
-			}
+// ---- the dense plan (row-aligned rig): cost rows by the persistent strip kernel (srh_strip.hip, cost_sad:
+// srh_sad_strip.hip) or by one workgroup per tile, then the scan over them
+
+// What an attempt of the dense plan queues before its bands: label table, scan template, band buffers, the views' padded
+// planes.  D.strip falls back to the per-tile kernel for thin bands: the strip kernel wants dozens of tiles per
+// persistent workgroup and launch (option strip = 4 / 8 forces it for tests)
+int TvPass::dense_prepare(TvDense &D) const {
+	int rc;
+	D.tscan = c->tscan != 0;
+	if ((rc = c->band.tnum.ensure((size_t)p->num_depth_levels + 8))) return rc;   // (+ 8: the template scan reads the table in whole eights)
+	{ Scope s(c, "pinhole_label_table_kernel");
+	  launch_pinhole_label_table(c->stream, c->d_views, ref, *p, false, c->band.tnum); }
+	if (D.tscan) {
+		// the pass's candidate template: the reference's walk at one pixel (srh_dense.hip, "template scan")
+		if ((rc = c->band.stpl.ensure(scan_template_bytes()))) return rc;
+		Scope s(c, "twoview_template_kernel");
+		launch_scan_template(c->stream, c->d_views, ref, oth, *p, y0, y1 - y0, c->band.tnum, c->band.stpl);
+	}
+	for (int pass = 0; pass < 2; ++pass) {
+		const int wdoubles = D.strip ? (2*R + 1)*wimg_wp(R) : T;    // doubles per pixel window in the band buffer
+		D.rows = rows_per_band((size_t)wdoubles*sizeof(double) + (size_t)D.cstride*sizeof(double));
+		if (D.strip && !sad && c->strip == 1 && (size_t)((W + SRH_WTILE - 1)/SRH_WTILE)*D.rows < (size_t)48*2*c->num_cus) D.strip = false;
+		else break;
+	}
+	const size_t rows = D.rows;
+	if ((rc = c->band.wbuf.ensure(D.strip ? wimg_doubles(W, (int)rows, R) : wbuf_doubles(W, (int)rows, T)))) return rc;
+	if ((rc = c->band.cost.ensure(rows*(size_t)((W + 31)/32)*32*(size_t)D.cstride))) return rc;   // 32-pixel tiles
+	// (+ one tile of slack: the strip kernel copies whole 32-pixel pieces of these rows)
+	if ((rc = c->band.pconst.ensure((rows*(size_t)W + SRH_WTILE)*SRH_PC))) return rc;
+	if ((rc = c->band.prange.ensure(rows*(size_t)W + SRH_WTILE))) return rc;
+	if (D.tscan && (rc = c->band.tileflag.ensure(rows*(size_t)((W + 63)/64) + 1))) return rc;
+	if (D.cert && (rc = c->band.cflag.ensure(rows*(size_t)W + 1))) return rc;
+	D.lanes = D.strip ? strip_block_lanes(D.cstride, c->strip == 1 ? 0 : c->strip) : 8;
+	// NaN-bordered gray_tv planes of both views (strip kernel; the general cost of the left-out columns and of the
+	// certified redo on either dense path)
+	if ((rc = ensure_tvp(c, c->views[ref])) || (rc = ensure_tvp(c, c->views[oth]))) return rc;
+	if (D.strip && sad) {
+		if ((rc = ensure_sad_planes(c, c->views[oth], R))) return rc;
+	} else if (D.strip) {
+		// zero-bordered "window fully usable" plane of the other view
+		ViewHost &O = c->views[oth];
+		if (!O.fullp) HIP_TRY(O.fullp.alloc(padded_size(O.w, O.h)));
+		if (O.fullp_r != R) {
+			Scope s(c, "padded_full_kernel");
+			launch_padded_full(c->stream, O.gray_tv, O.w, O.h, R, O.fullp);
+			O.fullp_r = R;
 		}
-		HIP_TRY(hipGetLastError());
-		if (!dense) break;
-		if (c->defer && attempt == 0) {
-			// optimistic (srh_twoview_compute): the counters travel to pinned memory behind the kernels, the caller looks at them
-			HIP_TRY(hipMemcpyAsync(c->defer->host, c->d_cnt, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
-			c->defer->queued = true; c->defer->strip = strip; c->defer->cert = cert_ok;
-			c->stats.used_strip_kernel = strip ? 1 : 0;
+	}
+	return SRH_OK;
+}
+
+// a band's support windows (with the pixels' constants for cost_ncc) and the pixels' column ranges
+void TvPass::dense_band_inputs(const TvDense &D, int by, int nr) const {
+	run_weights(c, ref, W, *p, by, nr, SRH_WTILE, !sad ? (double *)c->band.pconst : nullptr, D.strip);
+	Scope s(c, "pixel_range_kernel");
+	launch_pixel_range(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.tnum, D.cstride, c->band.prange);
+}
+
+// the band's cost rows under one arithmetic: strip kernel or one workgroup per tile, then the left-out columns
+// (raw, diagnostics: the certified strip forms without the in-kernel exact redo)
+int TvPass::dense_cost_pass(const TvDense &D, int by, int nr, int arith, bool raw) const {
+	const int cstride = D.cstride;
+	const size_t wstride = SRH_WTILE;
+	if (sad) {
+		// (every column of [lo, hi] is written: no fill launch, which would evaluate cost_ncc)
+		HIP_TRY(hipMemsetAsync(&c->d_cnt->strip_ticket, 0, 2*sizeof(unsigned int), c->stream));
+		Scope s(c, "twoview_strip_sad_kernel");
+		if (!launch_twoview_strip_sad(c->stream, W, H, *p, by, nr, c->band.wbuf, c->band.prange, c->views[ref].tvp,
+		                              c->views[oth].grayp, c->views[oth].fullsp, c->band.cost, cstride, c->d_cnt, c->num_cus))
+			return fail(SRH_E_UNSUPPORTED, "twoview_strip_sad_kernel: no instantiation for radius %d", R);
+		return SRH_OK;
+	}
+	if (D.strip) {
+		HIP_TRY(hipMemsetAsync(&c->d_cnt->strip_ticket, 0, 2*sizeof(unsigned int), c->stream));
+		{ Scope s(c, "twoview_strip_cost_kernel");
+		  launch_twoview_strip_cost(c->stream, c->d_views, ref, oth, W, H, *p, by, nr, c->band.wbuf, c->band.pconst, c->band.prange,
+		                            c->views[ref].tvp, c->views[oth].tvp, c->views[oth].fullp, c->band.cost, cstride,
+		                            c->d_cnt, arith, c->num_cus, D.lanes, raw); }
+	} else {
+		{ Scope s(c, "twoview_dense_cost_kernel");
+		  if (arith == 2)
+			launch_twoview_dense_cost_f32(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, wstride,
+			                              c->band.tnum, c->band.cost, cstride, c->d_cnt, c->band.pconst, c->f32_form);
+		  else
+			launch_twoview_dense_cost(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, wstride,
+			                          c->band.tnum, c->band.cost, cstride, c->d_cnt, c->band.pconst, arith, c->band.prange); }
+	}
+	// the left-out columns (per-tile kernel: its one-pass form leaves none out; D.lanes is 8 there)
+	Scope s(c, "twoview_lazy_fill_kernel");
+	launch_twoview_lazy_fill(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.prange, c->band.wbuf, wstride, c->views[ref].tvp,
+	                         c->views[oth].tvp, D.strip, D.lanes, D.strip ? D.lanes == 8 : arith != 5, c->band.cost, cstride, c->d_cnt);
+	return SRH_OK;
+}
+
+// one attempt of the dense plan: every band queued; the counters say whether it stands (tv_dense_verdict)
+int TvPass::run_dense(TvDense &D) const {
+	int rc;
+	if ((rc = dense_prepare(D))) return rc;
+	// (the strip kernel's certified form: 5 = one sweep over the window, 3 = the reference's two sweeps fused; option "cert_form")
+	const int cost_arith = c->arith == 3 ? (D.cert ? (c->cert_form == 1 ? 5 : 3) : 0) : c->arith;
+	for (int by = y0; by < y1; by += (int)D.rows) {
+		if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
+		const int nr = std::min((int)D.rows, y1 - by);
+		dense_band_inputs(D, by, nr);
+		if (D.cert) HIP_TRY(hipMemsetAsync(c->band.cflag, 0, sizeof(uint32_t), c->stream));
+		if ((rc = dense_cost_pass(D, by, nr, cost_arith, false))) return rc;
+		{ Scope s(c, "twoview_scan_kernel");
+		  launch_twoview_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.tnum, c->band.cost, D.cstride, c->d_cnt, c->band.prange,
+		                      D.cert ? c->band.cflag : nullptr, -1, D.cert && D.strip ? c->band.pconst : nullptr, D.tscan ? c->band.stpl : nullptr, c->band.tileflag, c->num_cus, wout, c->tscan_bound); }
+		if (D.cert) {
+			// the pixels whose decisions the bound does not cover, in the reference's arithmetic: their cost rows are
+			// refilled and they are scanned again -- launched for a capacity, the count stays on the device
+			const int cap = redo_capacity((size_t)nr*W);
+			{ Scope s(c, "twoview_refill_kernel");
+			  launch_twoview_refill(c->stream, W, *p, by, c->band.prange, c->band.cflag, cap, c->band.wbuf, D.strip, c->views[ref].tvp,
+			                        c->views[oth].tvp, c->band.cost, D.cstride, c->d_cnt); }
+			Scope s(c, "twoview_rescan_kernel");
+			launch_twoview_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.tnum, c->band.cost, D.cstride, c->d_cnt, c->band.prange,
+			                    c->band.cflag, cap, nullptr, nullptr, nullptr, c->num_cus, wout);
+		}
+		winner_costs(by, nr, D.strip);
+	}
+	HIP_TRY(hipGetLastError());
+	return SRH_OK;
+}
+
+// what the counters of a dense attempt say: the result stands only if no candidate left its row / column range
+enum TvVerdict { TV_STANDS, TV_STRIP_OVERFLOW, TV_CERT_OVERFLOW, TV_NOT_ROW_ALIGNED };
+static TvVerdict tv_dense_verdict(const Counters &h, bool strip) {
+	if (strip && h.strip_overflow != 0) return TV_STRIP_OVERFLOW;   // a tile's ranges did not fit one LDS chunk
+	if (h.cert_overflow != 0) return TV_CERT_OVERFLOW;              // more flagged pixels than the redo covers
+	return h.not_row_aligned == 0 ? TV_STANDS : TV_NOT_ROW_ALIGNED;
+}
+
+// ---- the last resort: the one-thread-per-pixel walk kernel, which visits every point of every curve
+int TvPass::run_walk() const {
+	int rc;
+	const int rows = (int)rows_per_band((size_t)T*sizeof(double));
+	if ((rc = c->band.wbuf.ensure(wbuf_doubles(W, rows, T)))) return rc;
+	for (int by = y0; by < y1; by += rows) {
+		if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
+		const int nr = std::min(rows, y1 - by);
+		run_weights(c, ref, W, *p, by, nr, SRH_WTILE);
+		{ Scope s(c, "twoview_generic_kernel");
+		  launch_twoview_generic(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, SRH_WTILE, c->d_cnt, sad, wout); }
+		winner_costs(by, nr, false);
+	}
+	HIP_TRY(hipGetLastError());
+	return SRH_OK;
+}
+
+// The controller: the plan's first choice, then at most four attempts, each read by its counters -- a strip overflow takes
+// the per-tile kernel (cost_sad, which has the strip form only: the candidate lists), a certified pass with more flagged
+// pixels than its redo covers the reference's arithmetic, a dense plan the device refutes the general kernels.  On a
+// call's first attempt srh_twoview_compute's passes (c->defer) are handed over unverified instead.
+// (a HIP error or a refused band buffer returns straight out: with_thinner_bands retries the whole call)
+static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p, int y0, int y1) {
+	int rc;
+	TvPass P;
+	if ((rc = tv_pass_init(P, c, ref, oth, p, y0, y1))) return rc;
+	if (P.y1 <= P.y0) return SRH_OK;
+	if ((rc = ensure_wta_planes(c, ref, oth))) return rc;
+	P.wout = c->wta_outputs ? (int32_t *)c->views[ref].wta_xy : nullptr;
+	const TvPlan plan = P.plan();
+
+	c->last_fused = false;
+	if (plan.fused) {
+		bool stands = false;
+		if ((rc = P.run_fused(stands))) return rc;
+		if (stands) {
+			c->stats.used_dense_path = 1;
+			c->last_fused = true;
+			return SRH_OK;
+		}
+	}
+
+	bool dense = plan.dense;
+	TvDense D;
+	D.cstride = plan.cstride;
+	// the persistent strip form of the cost kernel: exact / fma arithmetic, candidate ranges of a 32-pixel tile inside one
+	// LDS chunk; anything else, or a range that turns out wider, takes the per-tile kernel
+	D.strip = dense && (P.sad || (c->strip != 0 && c->arith != 2)) && plan.cstride + SRH_WTILE <= strip_chunk_columns();
+	// certified arithmetic (arith = 3, the default): fused cost loops in the strip kernel + the certified scan; where the
+	// strip kernel does not run, or the parameters leave the bound no room, the reference's arithmetic
+	bool cert_ok = c->arith == 3 && !P.sad && cert_bound(*p).ok != 0;
+	c->stats.n_certified = c->stats.n_flagged = 0;
+	// (a negative wta_margin -- not the reference's: its margin is the constant +1e-10, twoviewstereo.cpp:293 -- makes a
+	// revisited winner beat itself, so the candidate lists' dropped joint duplicates would matter: the walk kernel, which
+	// visits every point, takes such a run)
+	const bool lists = !c->force_walk && P.R <= 5 && P.W < 65536 && P.H < 65536 && p->wta_margin >= 0;
+	for (int attempt = 0; attempt < 4; ++attempt) {
+		HIP_TRY(hipMemsetAsync(c->d_cnt, 0, sizeof(Counters), c->stream));
+		srh_context::TvDefer *defer = attempt == 0 ? c->defer : nullptr;
+		if (!dense) {
+			if ((rc = lists ? P.run_lists(cert_ok, defer) : P.run_walk())) return rc;
+			if (lists && defer && defer->queued) return SRH_OK;
+			break;
+		}
+		D.cert = cert_ok;
+		if ((rc = P.run_dense(D))) return rc;
+		if (defer) {
+			if ((rc = tv_defer_queue(c, *defer, false, D.strip, cert_ok))) return rc;
+			c->stats.used_strip_kernel = D.strip ? 1 : 0;
 			c->stats.used_dense_path = 1;
 			return SRH_OK;
 		}
-		// the dense result stands only if no candidate left its row / column range
 		Counters hc;
-		HIP_TRY(hipMemcpyAsync(&hc, c->d_cnt, sizeof(hc), hipMemcpyDeviceToHost, c->stream));
-		HIP_TRY(hipStreamSynchronize(c->stream));
-		if (strip && sad && hc.strip_overflow != 0) { strip = false; dense = false; continue; }   // (cost_sad: the candidate lists)
-		if (strip && hc.strip_overflow != 0) { strip = false; continue; }   // a tile's ranges did not fit one chunk: per-tile kernel
-		if (hc.cert_overflow != 0) { cert_ok = false; continue; }           // more flagged pixels than the redo covers: mode 0
+		if ((rc = read_back(c, &hc, c->d_cnt, sizeof(hc)))) return rc;
+		const TvVerdict v = tv_dense_verdict(hc, D.strip);
+		if (v == TV_STRIP_OVERFLOW) { D.strip = false; if (P.sad) dense = false; continue; }
+		if (v == TV_CERT_OVERFLOW) { cert_ok = false; continue; }
 		c->stats.n_certified = (int64_t)hc.n_certified; c->stats.n_flagged = (int64_t)hc.n_flagged;
-		if (hc.not_row_aligned == 0) break;
-		dense = false;                                              // redo with the general kernel
-		strip = false;
+		if (v == TV_STANDS) break;
+		dense = false;                                            // redo with the general kernels
+		D.strip = false;
 	}
-	c->stats.used_strip_kernel = strip ? 1 : 0;
+	c->stats.used_strip_kernel = D.strip ? 1 : 0;
 	c->stats.used_dense_path = dense ? 1 : 0;
 	return SRH_OK;
 }
 
+extern "C" int srh_twoview_wta(srh_context *c, int ref, int oth, const srh_params *p, int y0, int y1) {
+	int rc;
+	if ((rc = check_slot(c, ref, true)) || (rc = check_slot(c, oth, true)) || (rc = check_params(p))) return rc;
+	return with_thinner_bands(c, [&] { return twoview_wta_run(c, ref, oth, p, y0, y1); });
+}
+
 // Diagnostic (tests/test_gpu_cert_rows.py): the cost rows of rows [y0, y1) on the row-aligned dense plan, straight from the
 // cost kernel -- what the scan would look up.  form: 0 the reference's arithmetic, 3 two fused sweeps, 5 one-pass (the
-// certified forms); raw != 0: without the in-kernel exact redo (uncertified candidates are NaN).
+// certified forms); raw != 0: without the in-kernel exact redo (uncertified candidates are NaN).  The plan and the
+// preparation are the pass's (tv_plan, tv_dense_prepare); the rows have to fit one band, whose cost pass runs alone.
 extern "C" int srh_twoview_cost_rows(srh_context *c, int ref, int oth, const srh_params *p, int y0, int y1, int form, int raw,
                                      double *cost_out, size_t cost_doubles, int32_t *range_out, int *cstride_out, int *used_strip)
 {
@@ -2020,18 +2149,35 @@ extern "C" int srh_twoview_cost_rows(srh_context *c, int ref, int oth, const srh
 	const bool sad = c->cost_kind == SRH_COST_SAD;
 	if (sad && !c->sad_dense) return fail(SRH_E_UNSUPPORTED, "cost rows of cost_sad exist on the dense plan only (option sad_dense)");
 	if (sad && form != 0) return fail(SRH_E_INVALID, "cost_sad has the reference's arithmetic only: form must be 0");
-	srh_context::Diag dg;
-	dg.form = form; dg.raw = raw != 0; dg.cost = cost_out; dg.cost_doubles = cost_doubles; dg.range = range_out;
-	c->diag = &dg;
-	const int keep_arith = c->arith; const bool keep_fused = c->use_fused;
-	c->arith = form == 0 ? 0 : 3; c->use_fused = false;
-	rc = twoview_wta_run(c, ref, oth, p, y0, y1);
-	c->arith = keep_arith; c->use_fused = keep_fused;
-	c->diag = nullptr;
-	if (rc) return rc;
-	if (!dg.done) return fail(SRH_E_UNSUPPORTED, "cost rows exist on the row-aligned dense plan only (radius 5 or 2, rectified pinhole pair)");
-	if (cstride_out) *cstride_out = dg.cstride;
-	if (used_strip) *used_strip = dg.strip ? 1 : 0;
+	TvPass P;
+	if ((rc = tv_pass_init(P, c, ref, oth, p, y0, y1))) return rc;
+	const TvPlan plan = P.plan();
+	if (P.y1 <= P.y0 || !plan.dense)
+		return fail(SRH_E_UNSUPPORTED, "cost rows exist on the row-aligned dense plan only (radius 5 or 2, rectified pinhole pair)");
+	c->last_fused = false;
+	c->stats.n_certified = c->stats.n_flagged = 0;
+	HIP_TRY(hipMemsetAsync(c->d_cnt, 0, sizeof(Counters), c->stream));
+	TvDense D;
+	D.cstride = plan.cstride;
+	D.strip = (sad || c->strip != 0) && plan.cstride + SRH_WTILE <= strip_chunk_columns();
+	D.cert = form != 0 && !sad && cert_bound(*p).ok != 0;
+	if ((rc = P.dense_prepare(D))) return rc;
+	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
+	const int nr = std::min((int)D.rows, P.y1 - P.y0);
+	P.dense_band_inputs(D, P.y0, nr);
+	if (nr != P.y1 - P.y0) return fail(SRH_E_UNSUPPORTED, "cost rows: the rows asked for do not fit one band (%d of %d)", nr, P.y1 - P.y0);
+	if (cost_out) {
+		// the band's cost rows under the arithmetic asked for, as the cost kernel leaves them, and the pixels' column ranges
+		const size_t nd = (size_t)nr*((P.W + 31)/32)*32*(size_t)D.cstride;
+		if (cost_doubles < nd) return fail(SRH_E_INVALID, "cost rows: buffer of %zu doubles, %zu needed", cost_doubles, nd);
+		HIP_TRY(hipMemsetAsync(c->band.cost, 0xff, nd*sizeof(double), c->stream));   // (never-written entries read as a NaN with payload -1)
+		if ((rc = P.dense_cost_pass(D, P.y0, nr, form, raw != 0))) return rc;
+		HIP_TRY(hipMemcpyAsync(cost_out, c->band.cost, nd*sizeof(double), hipMemcpyDeviceToHost, c->stream));
+		if (range_out) HIP_TRY(hipMemcpyAsync(range_out, c->band.prange, (size_t)nr*P.W*sizeof(PixRange), hipMemcpyDeviceToHost, c->stream));
+		HIP_TRY(hipStreamSynchronize(c->stream));
+	}
+	if (cstride_out) *cstride_out = D.cstride;
+	if (used_strip) *used_strip = D.strip ? 1 : 0;
 	return SRH_OK;
 }
 
@@ -2104,9 +2250,8 @@ static void tv_slot_swap(srh_context *c) {
 
 static bool tv_pass_stands(const srh_context::TvDefer &d) {
 	const Counters &h = *d.host;
-	if (d.lists)                                                   // every list and every pixel's cost slots fitted, no curve over too many rows
-		return d.span[0] <= d.cmax && ((d.span[1] + 7) & ~7) <= d.smax && d.span[2] == 0 && h.cert_overflow == 0;
-	return !(d.strip && h.strip_overflow != 0) && h.cert_overflow == 0 && h.not_row_aligned == 0;
+	if (d.lists) return tv_lists_fit(d.span, d.cmax, d.smax) && h.cert_overflow == 0;
+	return tv_dense_verdict(h, d.strip) == TV_STANDS;
 }
 
 static int twoview_filter(srh_context *c, int left, int right, const srh_params *p);
@@ -2131,30 +2276,21 @@ extern "C" int srh_twoview_compute(srh_context *c, int left, int right, const sr
 			HIP_TRY(T.d_cnt.alloc(1));
 			HIP_TRY(T.d_span.alloc(4));
 		}
-		// the NaN-bordered planes both passes read (twoview_wta_run makes them on demand, on its own stream) exist at `go`
+		// the NaN-bordered planes both passes read (tv_dense_prepare makes them on demand, on its own stream) exist at `go`
 		if (c->cost_kind == SRH_COST_SAD && c->sad_dense && (p->window_radius == 5 || p->window_radius == 2))
 			for (int k = 0; k < 2; ++k)
 				if ((rc = ensure_sad_planes(c, c->views[k == 0 ? left : right], p->window_radius))) return rc;
-		if (p->window_radius == 5 || p->window_radius == 2)
-			for (int k = 0; k < 2; ++k) {
-				ViewHost &v = c->views[k == 0 ? left : right];
-				if (!v.tvp) HIP_TRY(v.tvp.alloc(padded_size(v.w, v.h)));
-				if (!v.tvp_valid) {
-					Scope s(c, "padded_plane_kernel");
-					launch_padded_plane(c->stream, v.gray_tv, v.w, v.h, v.tvp);
-					v.tvp_valid = true;
-				}
-			}
+		if ((p->window_radius == 5 || p->window_radius == 2) &&
+		    ((rc = ensure_tvp(c, c->views[left])) || (rc = ensure_tvp(c, c->views[right])))) return rc;
 		// (and the WTA by-products' planes of both views, option "wta_outputs", are allocated and hold their "none" values there)
 		if ((rc = ensure_wta_planes(c, left, right)) || (rc = ensure_wta_planes(c, right, left))) return rc;
 		HIP_TRY(hipEventRecord(T.go, c->stream));
 	}
 	// progress steps as TwoViewStereo emits them (twoviewstereo.cpp:234,405,597,225)
 	progress(c, 1, "Computing cost volume for left image...");
-	c->defer = &c->tv_defer[0];
-	rc = srh_twoview_wta(c, left, right, p, 0, 0);
-	c->defer = nullptr;
-	if (rc) return rc;
+	// (a pass whose verdict may wait: twoview_wta_run hands it over through c->defer)
+	auto deferred_wta = [&](int k, int ref, int oth) { c->defer = &c->tv_defer[k]; const int r = srh_twoview_wta(c, ref, oth, p, 0, 0); c->defer = nullptr; return r; };
+	if ((rc = deferred_wta(0, left, right))) return rc;
 	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
 	progress(c, 3, "Computing cost volume for right image...");
 	if (c->tv_overlap && c->tv_defer[0].queued) {
@@ -2163,9 +2299,7 @@ extern "C" int srh_twoview_compute(srh_context *c, int left, int right, const sr
 		srh_context::TvSlot &T = c->tv_slot;
 		HIP_TRY(hipStreamWaitEvent(T.stream, T.go, 0));
 		tv_slot_swap(c);
-		c->defer = &c->tv_defer[1];
-		rc = srh_twoview_wta(c, right, left, p, 0, 0);
-		c->defer = nullptr;
+		rc = deferred_wta(1, right, left);
 		const hipError_t e = rc ? hipStreamSynchronize(c->stream) : hipEventRecord(T.done, c->stream);   // (c->stream: the slot's, still)
 		tv_slot_swap(c);
 		if (rc) return rc;
@@ -2174,10 +2308,7 @@ extern "C" int srh_twoview_compute(srh_context *c, int left, int right, const sr
 		// (srh_get_stats reads the context's counters and reports the last pass's, as it does without the overlap)
 		HIP_TRY(hipMemcpyAsync(c->d_cnt, T.d_cnt, sizeof(Counters), hipMemcpyDeviceToDevice, c->stream));
 	} else {
-		c->defer = &c->tv_defer[1];
-		rc = srh_twoview_wta(c, right, left, p, 0, 0);
-		c->defer = nullptr;
-		if (rc) return rc;
+		if ((rc = deferred_wta(1, right, left))) return rc;
 	}
 	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
 	srh_context::TvDefer &d0 = c->tv_defer[0], &d1 = c->tv_defer[1];
@@ -2199,10 +2330,7 @@ extern "C" int srh_twoview_compute(srh_context *c, int left, int right, const sr
 			// strides a verified pass would have recorded), and how the pair's lists are best evaluated
 			for (srh_context::TvDefer *d : { &d0, &d1 })
 				if (d->lists && d->guessed) {
-					const int cm = std::max(8, (d->span[0] + 7) & ~7), sm = std::max(cm + 64, (d->span[1] + 7) & ~7);
-					if (cm > c->list_cmax_hint) c->list_cmax_hint = cm;
-					if (sm > c->list_smax_hint) c->list_smax_hint = sm;
-					c->views[d->ref].list_mode[d->oth] = (d->host->n_slots > 2.2*(double)d->host->n_listed) ? 2 : 1;
+					tv_learn_lists(c, d->ref, d->oth, true, d->cmax, d->smax, d->span, *d->host);
 					d->guessed = false;
 				}
 			// (every counter of srh_stats is the LAST pass's -- right -> left -- on this path as on the verified ones and in
@@ -2303,61 +2431,61 @@ static int mvs_list_launch(srh_context *c, int view, const int32_t *neigh, int n
 		Scope s(c, "pinhole_label_table_kernel");
 		launch_pinhole_label_table(c->stream, c->d_views, view, *p, true, c->band.tnum);
 	}
-		HIP_TRY(hipMemsetAsync(c->d_cnt, 0, sizeof(Counters), c->stream));
-		HIP_TRY(hipMemsetAsync(c->d_span, 0, 4*sizeof(int), c->stream));
-		const size_t per_px = (size_t)T*sizeof(double) + (size_t)nneigh*((size_t)cmax*sizeof(uint32_t) + sizeof(int32_t) + 2*sizeof(double)
-		                      + (peaks_dev ? (size_t)p->top_k*2*sizeof(double) : 0));
-		size_t lrows = band_budget(c) / (per_px*(size_t)W);
-		if (lrows < 1) lrows = 1;
-		{
-			// the budget is a target, not a limit: no sliver band for a few rows over it, and bands of equal height
-			const size_t rows = (size_t)(y1 - y0);
-			if (rows <= lrows + lrows/4) lrows = rows;
-			else { const size_t nb = (rows + lrows - 1)/lrows; lrows = (rows + nb - 1)/nb; }
-		}
-		const size_t units = lrows*W*(size_t)nneigh;
-		// the list kernels' units: the masked-in pixels of a band, padded to whole 128-pixel blocks per link
-		size_t lunits = 0;
-		for (int by = y0; by < y1; by += (int)lrows) {
-			const int nr = std::min((int)lrows, y1 - by);
-			const size_t na = (size_t)A.act_row[by + nr] - A.act_row[by];
-			lunits = std::max(lunits, ((na + 127) & ~(size_t)127)*(size_t)nneigh);
-		}
-		if ((rc = c->band.wbuf.ensure(wbuf_doubles(W, (int)lrows, T)))) return rc;
-		if ((rc = c->band.cost.ensure(units*2 + (peaks_dev ? units*(size_t)p->top_k*2 : 0)))) return rc;   // best pairs + per-unit top-K, by pixel
-		if ((rc = c->band.lcand.ensure(std::max<size_t>(lunits, 128)*(size_t)cmax))) return rc;   // wave-tiled lists
-		if ((rc = c->band.lcount.ensure(std::max<size_t>(lunits, 128)))) return rc;
-		const bool staged = c->mvs_staged != 0;
+	HIP_TRY(hipMemsetAsync(c->d_cnt, 0, sizeof(Counters), c->stream));
+	HIP_TRY(hipMemsetAsync(c->d_span, 0, 4*sizeof(int), c->stream));
+	const size_t per_px = (size_t)T*sizeof(double) + (size_t)nneigh*((size_t)cmax*sizeof(uint32_t) + sizeof(int32_t) + 2*sizeof(double)
+	                      + (peaks_dev ? (size_t)p->top_k*2*sizeof(double) : 0));
+	size_t lrows = band_budget(c) / (per_px*(size_t)W);
+	if (lrows < 1) lrows = 1;
+	{
+		// the budget is a target, not a limit: no sliver band for a few rows over it, and bands of equal height
+		const size_t rows = (size_t)(y1 - y0);
+		if (rows <= lrows + lrows/4) lrows = rows;
+		else { const size_t nb = (rows + lrows - 1)/lrows; lrows = (rows + nb - 1)/nb; }
+	}
+	const size_t units = lrows*W*(size_t)nneigh;
+	// the list kernels' units: the masked-in pixels of a band, padded to whole 128-pixel blocks per link
+	size_t lunits = 0;
+	for (int by = y0; by < y1; by += (int)lrows) {
+		const int nr = std::min((int)lrows, y1 - by);
+		const size_t na = (size_t)A.act_row[by + nr] - A.act_row[by];
+		lunits = std::max(lunits, ((na + 127) & ~(size_t)127)*(size_t)nneigh);
+	}
+	if ((rc = c->band.wbuf.ensure(wbuf_doubles(W, (int)lrows, T)))) return rc;
+	if ((rc = c->band.cost.ensure(units*2 + (peaks_dev ? units*(size_t)p->top_k*2 : 0)))) return rc;   // best pairs + per-unit top-K, by pixel
+	if ((rc = c->band.lcand.ensure(std::max<size_t>(lunits, 128)*(size_t)cmax))) return rc;   // wave-tiled lists
+	if ((rc = c->band.lcount.ensure(std::max<size_t>(lunits, 128)))) return rc;
+	const bool staged = c->mvs_staged != 0;
+	if (staged) {
+		int maxw; size_t words;
+		mvs_staging_shape(&maxw, &words);
+		const size_t waves = std::max<size_t>(lunits, 128)/64;
+		if ((rc = c->band.mvs_wdesc.ensure(waves*words))) return rc;
+		if ((rc = c->band.mvs_nwin.ensure(waves))) return rc;
+	}
+	for (int by = y0; by < y1; by += (int)lrows) {
+		if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
+		const int nr = std::min((int)lrows, y1 - by);
+		const uint32_t *act = A.act ? A.act + A.act_row[by] : nullptr;
+		const int nact = (int)(A.act_row[by + nr] - A.act_row[by]);
+		run_weights(c, view, W, *p, by, nr, wstride);
+		{ Scope s(c, "mvs_walk_kernel");
+		  launch_mvs_walk(c->stream, c->d_views, view, neigh, nneigh, W, *p, by, nr, table ? c->band.tnum : nullptr, c->band.lcand, cmax, c->band.lcount,
+		                  c->d_cnt, c->d_span, staged ? c->band.mvs_wdesc : nullptr, staged ? c->band.mvs_nwin : nullptr, act, nact,
+		                  peaks_dev != nullptr, neigh_pinhole && c->arith == 3); }
+		double *const upk = peaks_dev ? c->band.cost + units*2 : nullptr;
 		if (staged) {
-			int maxw; size_t words;
-			mvs_staging_shape(&maxw, &words);
-			const size_t waves = std::max<size_t>(lunits, 128)/64;
-			if ((rc = c->band.mvs_wdesc.ensure(waves*words))) return rc;
-			if ((rc = c->band.mvs_nwin.ensure(waves))) return rc;
+			Scope s(c, "mvs_staged_cost_kernel");
+			launch_mvs_staged_cost(c->stream, c->d_views, view, neigh, nneigh, W, *p, by, nr, c->band.wbuf, wstride,
+			                       c->band.lcand, cmax, c->band.lcount, c->band.cost, c->band.mvs_wdesc, c->band.mvs_nwin, c->d_cnt, act, nact, upk,
+			                       c->arith == 3 && !peaks_dev);
 		}
-		for (int by = y0; by < y1; by += (int)lrows) {
-			if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
-			const int nr = std::min((int)lrows, y1 - by);
-			const uint32_t *act = A.act ? A.act + A.act_row[by] : nullptr;
-			const int nact = (int)(A.act_row[by + nr] - A.act_row[by]);
-			run_weights(c, view, W, *p, by, nr, wstride);
-			{ Scope s(c, "mvs_walk_kernel");
-			  launch_mvs_walk(c->stream, c->d_views, view, neigh, nneigh, W, *p, by, nr, table ? c->band.tnum : nullptr, c->band.lcand, cmax, c->band.lcount,
-			                  c->d_cnt, c->d_span, staged ? c->band.mvs_wdesc : nullptr, staged ? c->band.mvs_nwin : nullptr, act, nact,
-			                  peaks_dev != nullptr, neigh_pinhole && c->arith == 3); }
-			double *const upk = peaks_dev ? c->band.cost + units*2 : nullptr;
-			if (staged) {
-				Scope s(c, "mvs_staged_cost_kernel");
-				launch_mvs_staged_cost(c->stream, c->d_views, view, neigh, nneigh, W, *p, by, nr, c->band.wbuf, wstride,
-				                       c->band.lcand, cmax, c->band.lcount, c->band.cost, c->band.mvs_wdesc, c->band.mvs_nwin, c->d_cnt, act, nact, upk,
-				                       c->arith == 3 && !peaks_dev);
-			}
-			{ Scope s(c, "mvs_list_cost_kernel");
-			  launch_mvs_list_cost(c->stream, c->d_views, view, neigh, nneigh, W, *p, by, nr, c->band.wbuf, wstride,
-			                       c->band.lcand, cmax, c->band.lcount, c->band.cost, upk, peaks_dev != nullptr, staged ? c->band.mvs_nwin : nullptr, act, nact); }
-			{ Scope s(c, "mvs_combine_kernel");
-			  launch_mvs_combine(c->stream, c->d_views, view, nneigh, W, *p, by, nr, c->band.cost, upk, (double *)peaks_dev); }
-		}
+		{ Scope s(c, "mvs_list_cost_kernel");
+		  launch_mvs_list_cost(c->stream, c->d_views, view, neigh, nneigh, W, *p, by, nr, c->band.wbuf, wstride,
+		                       c->band.lcand, cmax, c->band.lcount, c->band.cost, upk, peaks_dev != nullptr, staged ? c->band.mvs_nwin : nullptr, act, nact); }
+		{ Scope s(c, "mvs_combine_kernel");
+		  launch_mvs_combine(c->stream, c->d_views, view, nneigh, W, *p, by, nr, c->band.cost, upk, (double *)peaks_dev); }
+	}
 	HIP_TRY(hipGetLastError());
 	return SRH_OK;
 }
@@ -2452,7 +2580,6 @@ static int mvs_initial_estimate_run(srh_context *c, int view, const int32_t *nei
 	if (y1 <= y0) return SRH_OK;
 
 	const size_t wstride = SRH_WTILE;
-	if (y1 <= y0) return SRH_OK;
 
 	// ---- default: walk kernel -> candidate lists -> cost kernel -> maximum (and merged top-K lists) over the
 	// neighbours.  Other radii stay on the one-thread-per-pixel kernels.

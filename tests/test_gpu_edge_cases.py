@@ -167,7 +167,7 @@ def _twoview_vs_oracle(ctx, case, expect_dense):
 def test_dense_plan_refuted_on_device_is_redone_on_the_general_kernels(hip_ctx):
     """srh_twoview_wta proposes the dense row-aligned plan from a host-side rig check and lets the scan kernel
     verify every candidate; a candidate off its row makes the host redo the pass on the general kernels
-    (srh_api.hip, `not_row_aligned`).  The host check is strict enough that no real rig reaches the redo, so the
+    (srh_api.hip, twoview_wta_run: `TV_NOT_ROW_ALIGNED`).  The host check is strict enough that no real rig reaches the redo, so the
     plan is forced ("force_dense") on a verged pinhole pair: the result must still equal the oracle."""
     case = cases.get_twoview("adaptive_verged", w=72, h=44, D=20, radius=5)
     hip_ctx.set_option("force_dense", 1)
@@ -183,7 +183,7 @@ def test_dense_plan_refuted_on_device_is_redone_on_the_general_kernels(hip_ctx):
                          ids=["span_wider_than_the_image", "span_4096_or_more"])
 def test_dense_plan_span_limits(hip_ctx, zmin, dense):
     """Candidate ranges wider than the image clamp the cost-row stride to W+8 (still the dense kernels);
-    a nominal span of 4096 columns or more is left to the general kernels (srh_api.hip plan)."""
+    a nominal span of 4096 columns or more is left to the general kernels (srh_api.hip, TvPass::plan)."""
     case = cases.get_twoview("geodesic_rect", w=64, h=36, D=24)
     case["params"]["min_depth"] = zmin
     _twoview_vs_oracle(hip_ctx, case, expect_dense=dense)

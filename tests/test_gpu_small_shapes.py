@@ -121,7 +121,7 @@ WINDOW_KERNELS = {
     "strip 0": ("geodesic_reg_kernel", "geodesic_dma_kernel"), "defaults": ("geodesic_reg_kernel", "geodesic_dma_kernel"),
 }
 GROUPS = ("w<=2r", "h<=2r", "D>w", "tile edge")
-# (shape, radius, path) the library declines, by a rule of twoview_wta_run (csrc/srh_api.hip) quoted here; the depth maps
+# (shape, radius, path) the library declines, by a rule of the TwoView pass driver (TvPass::plan, twoview_wta_run; csrc/srh_api.hip) quoted here; the depth maps
 # and planes of a declined pair are still the walk kernel's bits
 DECLINES = {
 }
@@ -290,7 +290,7 @@ def test_exact_cost_rows_against_the_oracle(hip_ctx, shape, radius, kind, masks)
         assert us == (strip != 0), tag
         nonempty = rng[..., 1] >= rng[..., 0]
         assert (rng[..., 0][nonempty] >= 0).all() and (rng[..., 1][nonempty] < c.w).all(), tag
-        # the plan's stride (twoview_wta_run): the widest range + margins in whole eights, clamped to the image's width + 8
+        # the plan's stride (TvPass::plan): the widest range + margins in whole eights, clamped to the image's width + 8
         span = float(c.w) * c.p.image_scale * abs(1.0 / c.p.min_depth - 1.0 / c.p.max_depth)
         cstride = (math.ceil(span) + 3 + 7) & ~7
         if cstride > c.w + 8:

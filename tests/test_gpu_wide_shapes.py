@@ -116,7 +116,7 @@ def test_whole_maps_against_the_oracle(hip_ctx, shape, masks, radius, kind):
 
 # ---------------------------------------------------------------------------------------------- b. every rectified path
 PATHS = G.PATHS
-# (shape, path) the library declines, by a rule of twoview_wta_run (csrc/srh_api.hip) quoted here; the depth maps and planes
+# (shape, path) the library declines, by a rule of the TwoView pass driver (TvPass::plan, twoview_wta_run; csrc/srh_api.hip) quoted here; the depth maps and planes
 # of a declined pair are still the walk kernel's bits.  Only LONG declines anything, and that is what it is in the table for:
 # its cstride is ((300 - 1) + 3 + 7) & ~7 = 304.
 _CHUNK = "`cstride + SRH_WTILE <= strip_chunk_columns()`: 304 + 32 > 320, the per-tile kernel takes the pass"
