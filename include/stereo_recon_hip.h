@@ -522,6 +522,67 @@ int  srh_twoview_compute_mrf(srh_context *ctx, int left_slot, int right_slot, co
 int  srh_twoview_mrf_dims(srh_context *ctx, int *w, int *h, int *L);
 int  srh_twoview_mrf_state(srh_context *ctx, int w, int h, int L, int32_t *labels, double *data_costs, double *messages);
 
+/* ---- TwoViewStereo, semi-global aggregation over the label cost volume ----
+ * NOT IN THE REFERENCE.  Between the winner-take-all and TRW-S: one pass along up to 8 path directions over the volume of
+ * the MRF stage, with that stage's smoothness term -- a second, non-iterative minimiser of the same energy (compare
+ * srh_sgm_info.energy with srh_mrf_info.energy_final on the same volume).  No iteration, no stopping rule.
+ * DEFINITION (the device reproduces it bit for bit; tests/sgm_ref.py restates it):
+ *   C          the data costs [pixel][label], w*h*L finite doubles, what srh_twoview_label_costs produces; masked-out
+ *              pixels are nodes and carry the fill value, as in the MRF stage.
+ *   directions (dx, dy) = (+1,0) (-1,0) (0,+1) (0,-1) (+1,+1) (-1,-1) (+1,-1) (-1,+1); bit k of path_mask enables
+ *              direction k (0xFF: all; 0x0F: classic 4-path SGM).
+ *   per enabled direction r, pixels in path order, q = p - r:
+ *              q outside the image:  L_r(p, .) = C(p, .)
+ *              otherwise, with prev = L_r(q, .):
+ *                g    = min_k prev[k]
+ *                M[d] = min( min over integers j with |j| < smooth_max and 0 <= d+j < L of (prev[d+j] + lambda*|j|),
+ *                            g + lambda*smooth_max )
+ *                L_r(p, d) = C(p, d) + (M[d] - g)
+ *              every + and - is one IEEE double operation, lambda*|j| and lambda*smooth_max one product each, nothing is
+ *              contracted.  With smooth_max = 2 this is Hirschmueller's recurrence with P1 = lambda, P2 = 2*lambda.  (The
+ *              window form above and the direct form min_k (prev[k] + lambda*min(|d - k|, smooth_max)) are the same bits.)
+ *   S(p, d)    the sum of L_r(p, d) over the enabled directions in ascending k, left to right: ((L_a + L_b) + L_c) + ...
+ *   label(p)   the lowest d that attains min_d S(p, d)
+ *   depth(p)   depthFromLabel(label) where the mask is WHITE, NaN elsewhere; crossCheck follows unchanged; no ratio test.
+ *   energy     E(label) under the MRF stage's energy (the 4-connected grid, lambda*min(|l_p - l_q|, smooth_max)).
+ * LIMITS: those of srh_twoview_mrf_params with their status codes: 2 <= L <= 256, smooth_exp == 1, 0 < smooth_max <= 4
+ * (else SRH_E_UNSUPPORTED); lambda >= 0; path_mask 0 or any bit above bit 7: SRH_E_INVALID. */
+typedef struct srh_twoview_sgm_params {
+	int32_t smooth_exp;           /* 1 */
+	double  smooth_max, lambda;   /* 2, 0.25: the MRF stage's */
+	int32_t path_mask;            /* 0xFF */
+} srh_twoview_sgm_params;
+void srh_twoview_sgm_params_defaults(srh_twoview_sgm_params *m);   /* needs no device */
+typedef struct srh_sgm_info {
+	int32_t paths;                /* directions aggregated (the bits set in path_mask) */
+	double  energy;               /* E(label) */
+} srh_sgm_info;
+/* The aggregation on a caller's DEVICE volume (w*h*L doubles, [pixel][label], L == p->num_depth_levels; read only): writes
+ * the slot's depth map with the depth range of p.  The counterpart of srh_twoview_mrf_optimize, with its argument checks.
+ * A run needs one volume S of w*h*L doubles (+ the labels) beside the data costs; when that does not fit the free device
+ * memory (option "mem_limit_mb" honoured) the call fails with SRH_E_DEVICE and a message that names the bytes needed,
+ * before anything is queued, and the depth map stays untouched.  The cancel flag is polled between directions.  (Volumes
+ * on a 16-byte boundary with L a multiple of an even number of labels per lane, ceil(L/64), are moved 16 bytes at a time:
+ * same bits.)  info may be NULL. */
+int  srh_twoview_sgm_aggregate(srh_context *ctx, int view_slot, const srh_params *p, int L, const void *costs_dev,
+                               const srh_twoview_sgm_params *m, srh_sgm_info *info);
+/* One direction of the pair: the label cost volume in the context's scratch (two volumes in all: 8.5 GB at 1920x1080x256),
+ * the aggregation, the depth map of ref_slot. */
+int  srh_twoview_sgm(srh_context *ctx, int ref_slot, int oth_slot, const srh_params *p,
+                     const srh_twoview_sgm_params *m, srh_sgm_info *info);
+/* Both directions one after the other, then the cross-check; progress steps 1, 2 "Aggregating...", 3, 4 "Aggregating...",
+ * 5, 8 (option "filter_invalid": 6 and 7 where srh_twoview_compute_mrf puts them); option "cost" selects NCC or SAD as it
+ * does there; synchronous; host outputs and infos (two entries: left, right) may be NULL. */
+int  srh_twoview_compute_sgm(srh_context *ctx, int left_slot, int right_slot, const srh_params *p,
+                             const srh_twoview_sgm_params *m, double *left_depth_out, double *right_depth_out,
+                             srh_sgm_info *infos);
+/* State of the last srh_twoview_sgm / srh_twoview_sgm_aggregate on this context (the semantics of srh_twoview_mrf_state),
+ * to HOST buffers (each may be NULL): labels (w*h), data_costs (w*h*L; only after srh_twoview_sgm -- the volume of
+ * srh_twoview_sgm_aggregate is the caller's: SRH_E_INVALID), sums (w*h*L: S).  Forgotten when the view is uploaded again.
+ * After srh_twoview_compute_sgm the state is that of its second (right) direction. */
+int  srh_twoview_sgm_dims(srh_context *ctx, int *w, int *h, int *L);
+int  srh_twoview_sgm_state(srh_context *ctx, int w, int h, int L, int32_t *labels, double *data_costs, double *sums);
+
 /* ---- depth map -> point cloud ----
  * The output side of the path (the reference keeps only the PLY writer, multiviewstereo.cpp:291-315,
  * and the per-view coverage figure it logs, :402-421).  For every pixel of `slot` whose mask is WHITE and whose depth is

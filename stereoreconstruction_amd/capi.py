@@ -69,6 +69,16 @@ class SrhTwoviewMrfParams(C.Structure):
                 ("max_iters", C.c_int32), ("min_energy_drop", C.c_double)]
 
 
+class SrhTwoviewSgmParams(C.Structure):
+    """srh_twoview_sgm_params"""
+    _fields_ = [("smooth_exp", C.c_int32), ("smooth_max", C.c_double), ("lambda_", C.c_double), ("path_mask", C.c_int32)]
+
+
+class SrhSgmInfo(C.Structure):
+    """srh_sgm_info"""
+    _fields_ = [("paths", C.c_int32), ("energy", C.c_double)]
+
+
 # what srh_twoview_label_costs writes for a label without a pixel (SRH_LABEL_PIXEL_NONE)
 LABEL_PIXEL_NONE = -2147483648
 
@@ -142,6 +152,8 @@ EXPORTS = [
     "srh_mvs_initial_estimate_peaks", "srh_mvs_mrf_estimate_views",
     "srh_twoview_mrf_params_defaults", "srh_twoview_label_costs", "srh_twoview_mrf_optimize", "srh_twoview_mrf",
     "srh_twoview_compute_mrf", "srh_twoview_mrf_dims", "srh_twoview_mrf_state",
+    "srh_twoview_sgm_params_defaults", "srh_twoview_sgm_aggregate", "srh_twoview_sgm", "srh_twoview_compute_sgm",
+    "srh_twoview_sgm_dims", "srh_twoview_sgm_state",
     "srh_comm_unique_id", "srh_comm_init", "srh_comm_gather_depth", "srh_comm_allgather_depth", "srh_comm_allgather_host",
     "srh_comm_allgather_views",
     "srh_comm_destroy", "srh_comm_set_timeout_ms", "srh_comm_version", "srh_comm_info",
@@ -233,6 +245,14 @@ def lib():
     L.srh_twoview_compute_mrf.argtypes = [vp, C.c_int, C.c_int, C.POINTER(Params), tmp, c_double_p, c_double_p, C.POINTER(SrhMrfInfo)]
     L.srh_twoview_mrf_dims.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.srh_twoview_mrf_state.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_int32_p, c_double_p, c_double_p]
+    tsp = C.POINTER(SrhTwoviewSgmParams)
+    L.srh_twoview_sgm_params_defaults.argtypes = [tsp]
+    L.srh_twoview_sgm_params_defaults.restype = None
+    L.srh_twoview_sgm_aggregate.argtypes = [vp, C.c_int, C.POINTER(Params), C.c_int, C.c_void_p, tsp, C.POINTER(SrhSgmInfo)]
+    L.srh_twoview_sgm.argtypes = [vp, C.c_int, C.c_int, C.POINTER(Params), tsp, C.POINTER(SrhSgmInfo)]
+    L.srh_twoview_compute_sgm.argtypes = [vp, C.c_int, C.c_int, C.POINTER(Params), tsp, c_double_p, c_double_p, C.POINTER(SrhSgmInfo)]
+    L.srh_twoview_sgm_dims.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.srh_twoview_sgm_state.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_int32_p, c_double_p, c_double_p]
     L.srh_comm_allgather_views.argtypes = [vp, c_int32_p, C.c_int]
     L.srh_hw_queues_requested.restype = C.c_int
     L.srh_epipolar_preview.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, c_double_p, c_double_p, c_int32_p]
@@ -314,6 +334,22 @@ def twoview_mrf_params(**kw):
             raise AttributeError(k)
         setattr(m, k, v)
     return m
+
+
+def twoview_sgm_params(**kw):
+    """srh_twoview_sgm_params with its defaults (smooth_exp 1, smooth_max 2, lambda 0.25, path_mask 0xFF)."""
+    m = SrhTwoviewSgmParams()
+    lib().srh_twoview_sgm_params_defaults(C.byref(m))
+    for k, v in kw.items():
+        k = "lambda_" if k == "lambda" else k
+        if not hasattr(m, k):
+            raise AttributeError(k)
+        setattr(m, k, v)
+    return m
+
+
+def _sgm_info(info):
+    return dict(paths=info.paths, energy=info.energy)
 
 
 def fuse_params(**kw):
@@ -806,6 +842,46 @@ class Context:
         """(w, h, L) of the run whose state twoview_mrf_state reports."""
         w, h, k = C.c_int(), C.c_int(), C.c_int()
         _check(lib().srh_twoview_mrf_dims(self._h, C.byref(w), C.byref(h), C.byref(k)))
+        return w.value, h.value, k.value
+
+    def twoview_sgm_aggregate(self, view_slot, p, L, costs_dev, m=None):
+        """Semi-global aggregation on a device volume (w*h*L doubles, [pixel][label], read only); writes the slot's depth
+        map -> dict(paths, energy)."""
+        m = m if m is not None else twoview_sgm_params()
+        info = SrhSgmInfo()
+        _check(lib().srh_twoview_sgm_aggregate(self._h, view_slot, C.byref(p), L, C.c_void_p(costs_dev), C.byref(m), C.byref(info)))
+        return _sgm_info(info)
+
+    def twoview_sgm(self, ref_slot, oth_slot, p, m=None):
+        """One direction of the pair: label costs, aggregation, depth map of ref_slot."""
+        m = m if m is not None else twoview_sgm_params()
+        info = SrhSgmInfo()
+        _check(lib().srh_twoview_sgm(self._h, ref_slot, oth_slot, C.byref(p), C.byref(m), C.byref(info)))
+        return _sgm_info(info)
+
+    def twoview_compute_sgm(self, left_slot, right_slot, p, m=None):
+        """Both directions, then the cross-check -> (left map, right map, [left info, right info])."""
+        m = m if m is not None else twoview_sgm_params()
+        w, h = self.view_size(left_slot)
+        dl = np.empty((h, w), dtype=np.float64)
+        dr = np.empty((h, w), dtype=np.float64)
+        infos = (SrhSgmInfo * 2)()
+        _check(lib().srh_twoview_compute_sgm(self._h, left_slot, right_slot, C.byref(p), C.byref(m), _dptr(dl), _dptr(dr), infos))
+        return dl, dr, [_sgm_info(i) for i in infos]
+
+    def twoview_sgm_state(self, w, h, L, want_costs=False):
+        """(labels (h,w) int32, data_costs (h,w,L) or None, sums (h,w,L)) of the last single-direction run."""
+        labels = np.zeros((h, w), dtype=np.int32)
+        D = np.zeros((h, w, L), dtype=np.float64) if want_costs else None
+        S = np.zeros((h, w, L), dtype=np.float64)
+        _check(lib().srh_twoview_sgm_state(self._h, w, h, L, labels.ctypes.data_as(c_int32_p),
+                                           _dptr(D) if want_costs else None, _dptr(S)))
+        return labels, D, S
+
+    def twoview_sgm_dims(self):
+        """(w, h, L) of the run whose state twoview_sgm_state reports."""
+        w, h, k = C.c_int(), C.c_int(), C.c_int()
+        _check(lib().srh_twoview_sgm_dims(self._h, C.byref(w), C.byref(h), C.byref(k)))
         return w.value, h.value, k.value
 
     def epipolar_preview(self, ref_slot, oth_slot, min_depth, max_depth, num_depths, xy):

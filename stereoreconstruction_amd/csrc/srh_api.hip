@@ -280,6 +280,10 @@ struct srh_context {
 	DevBuf<double> tvmrf_costs;                         //   and the label cost volume of srh_twoview_mrf
 	int tvmrf_w = 0, tvmrf_h = 0, tvmrf_l = 0;          // what the last single-direction run left in them
 	bool tvmrf_own_costs = false;                       //   (its data costs are in tvmrf_costs, not in a caller's volume)
+	DevBuf<double> tvsgm;                               // TwoViewStereo semi-global aggregation (srh_twoview_sgm.hip): sums, labels
+	DevBuf<double> tvsgm_costs;                         //   and the label cost volume of srh_twoview_sgm
+	int tvsgm_w = 0, tvsgm_h = 0, tvsgm_l = 0;          // what the last single-direction run left in them
+	bool tvsgm_own_costs = false;
 	int geodma = 1;                                     // option "geodma": 1 = the dense path's r = 5 geodesic windows by the persistent LDS-DMA kernel (default), 0 = geodesic_reg_kernel
 	int tscan_bound = 1;                                // option "tscan_bound": 1 = the template scan settles a pixel by ONE bound for all its labels (default), 0 = label by label
 	int tscan = 1;                                      // option "tscan": 1 = template scan on the dense path (default), 0 = every tile through twoview_scan_kernel
@@ -776,6 +780,7 @@ extern "C" void srh_destroy(srh_context *c) {
 	}
 	c->mrf.release(); c->mrf_peaks.release();
 	c->tvmrf.release(); c->tvmrf_costs.release();
+	c->tvsgm.release(); c->tvsgm_costs.release();
 	c->fuse_result.release(); c->fuse_scratch.release();
 	for (int i = 0; i < SRH_MAX_VIEWS; ++i) if (c->mrf_stream[i]) hipStreamDestroy(c->mrf_stream[i]);
 	if (c->mrf_host) hipHostFree(c->mrf_host);
@@ -922,6 +927,7 @@ static int view_install(srh_context *c, int slot, int w, int h, const void *rgba
 	v.wta_flags = 0; v.wta_oth = -1;                            // and so did the WTA by-products
 	if (c->mrf_w == w && c->mrf_h == h) c->mrf_w = c->mrf_h = c->mrf_k = 0;
 	if (c->tvmrf_w == w && c->tvmrf_h == h) c->tvmrf_w = c->tvmrf_h = c->tvmrf_l = 0;
+	if (c->tvsgm_w == w && c->tvsgm_h == h) c->tvsgm_w = c->tvsgm_h = c->tvsgm_l = 0;
 	for (int j = 0; j < SRH_MAX_VIEWS; ++j) { v.list_mode[j] = 0; c->views[j].list_mode[slot] = 0; }   // new geometry
 	HIP_TRY(hipMemcpyAsync(v.rgba, rgba, n*4, kind, c->stream));
 	if (mask) HIP_TRY(hipMemcpyAsync(v.mask, mask, n, kind, c->stream));
@@ -3439,6 +3445,187 @@ extern "C" int srh_twoview_mrf_state(srh_context *c, int bw, int bh, int bl, int
 		HIP_TRY(hipMemcpy2DAsync(messages, 2*L*sizeof(double), lay.Mh, L*sizeof(double), L*sizeof(double), n, hipMemcpyDeviceToHost, c->stream));
 		HIP_TRY(hipMemcpy2DAsync(messages + L, 2*L*sizeof(double), lay.Mv, L*sizeof(double), L*sizeof(double), n, hipMemcpyDeviceToHost, c->stream));
 	}
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	return SRH_OK;
+}
+
+// ------------------------------------------------------------------ TwoViewStereo, semi-global aggregation (srh_twoview_sgm.hip)
+extern "C" void srh_twoview_sgm_params_defaults(srh_twoview_sgm_params *m)
+{
+	if (!m) return;
+	m->smooth_exp = 1; m->smooth_max = 2; m->lambda = 0.25;          // the MRF stage's smoothness term
+	m->path_mask = 0xFF;
+}
+
+static int check_tvsgm_params(const srh_twoview_sgm_params *m, int L)
+{
+	if (!m) return fail(SRH_E_INVALID, "null SGM params");
+	if (L < 2 || L > 256) return fail(SRH_E_UNSUPPORTED, "%d labels outside [2,256] (64 lanes per pixel, up to 4 labels per lane)", L);
+	if (m->smooth_exp != 1) return fail(SRH_E_UNSUPPORTED, "smooth_exp %d: only the truncated-linear term (1) is built", m->smooth_exp);
+	if (!(m->smooth_max > 0 && m->smooth_max <= 4)) return fail(SRH_E_UNSUPPORTED, "smooth_max %g outside (0,4] (the message window reaches 3 labels)", m->smooth_max);
+	if (!(m->lambda >= 0 && m->lambda < __builtin_inf())) return fail(SRH_E_INVALID, "lambda %g must be finite and >= 0", m->lambda);
+	if (m->path_mask <= 0 || m->path_mask > 0xFF) return fail(SRH_E_INVALID, "path_mask 0x%x: bits 0..7 enable the 8 directions, at least one", (unsigned)m->path_mask);
+	return SRH_OK;
+}
+
+// bytes of device memory a run still has to find: the sums (+ labels), and the cost volume when it is ours
+static int tvsgm_reserve(srh_context *c, int w, int h, int L, bool own_costs)
+{
+	const size_t scratch = twoview_sgm_scratch_doubles(w, h, L), vol = own_costs ? (size_t)w*h*L : 0;
+	const size_t need = (scratch + vol)*sizeof(double);
+	size_t missing = 0;
+	if (c->tvsgm.n < scratch) missing += scratch*sizeof(double);
+	if (c->tvsgm_costs.n < vol) missing += vol*sizeof(double);
+	size_t free_b = 0, total_b = 0;
+	if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+		size_t avail = free_b + pool_bytes_on(c->device);
+		if (c->tvsgm.n < scratch) avail += c->tvsgm.bytes();            // (an outgrown buffer is released first)
+		if (c->tvsgm_costs.n < vol) avail += c->tvsgm_costs.bytes();
+		size_t want = missing;
+		if (c->mem_limit) { want = need; if (avail > c->mem_limit) avail = c->mem_limit; }   // the pretended device holds the whole run
+		if (want > avail)
+			return fail(SRH_E_DEVICE, "the semi-global aggregation of a %dx%dx%d volume needs %zu bytes of device memory (%s: %zu per volume, no bands: a path crosses the whole grid), %zu are available",
+			            w, h, L, need, own_costs ? "costs and sums" : "sums", (size_t)w*h*L*sizeof(double), avail);
+	} else (void)hipGetLastError();
+	int rc;
+	if ((rc = c->tvsgm.ensure(scratch))) return rc;
+	if (vol && (rc = c->tvsgm_costs.ensure(vol))) return rc;
+	return SRH_OK;
+}
+
+// the aggregation on `costs` (device, [pixel][L]); the scratch is reserved
+static int tvsgm_run(srh_context *c, int slot, const srh_params *p, int L, const double *costs, const srh_twoview_sgm_params *m, srh_sgm_info *info)
+{
+	ViewHost &v = c->views[slot];
+	const int w = v.w, h = v.h;
+	c->tvsgm_w = c->tvsgm_h = c->tvsgm_l = 0;
+	TvSgmLayout lay;
+	twoview_sgm_layout(c->tvsgm, w, h, L, lay);
+	// (a profile entry per direction: rows, columns and diagonals stream differently)
+	static const char *const names[8] = { "twoview_sgm_path_kernel[+1,0]", "twoview_sgm_path_kernel[-1,0]", "twoview_sgm_path_kernel[0,+1]",
+	                                      "twoview_sgm_path_kernel[0,-1]", "twoview_sgm_path_kernel[+1,+1]", "twoview_sgm_path_kernel[-1,-1]",
+	                                      "twoview_sgm_path_kernel[+1,-1]", "twoview_sgm_path_kernel[-1,+1]" };
+	int paths = 0;
+	for (int k = 0; k < 8; ++k) {
+		if (!(m->path_mask >> k & 1)) continue;
+		// (nothing of the slot has been written yet: the depth map is the read-off's, after the last direction)
+		if (cancelled(c)) { HIP_TRY(hipStreamSynchronize(c->stream)); return fail(SRH_E_CANCELLED, "cancelled"); }
+		{ Scope s(c, names[k]);
+		  HIP_TRY(launch_twoview_sgm_path(c->stream, c->tvsgm, costs, w, h, L, m->lambda, m->smooth_max, k, paths == 0)); }
+		++paths;
+	}
+	v.wta_flags = 0;                                            // no scan made this depth map: the WTA by-products are stale
+	{ Scope s(c, "twoview_sgm_readoff_kernel");
+	  HIP_TRY(launch_twoview_sgm_readoff(c->stream, c->d_views, slot, *p, c->tvsgm, w, h, L)); }
+	{ Scope s(c, "twoview_mrf_energy_kernel");
+	  HIP_TRY(launch_twoview_sgm_energy(c->stream, c->tvsgm, costs, w, h, L, m->lambda, m->smooth_max)); }
+	double e = 0.0;
+	HIP_TRY(hipMemcpyAsync(&e, lay.energy, sizeof(e), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	c->tvsgm_w = w; c->tvsgm_h = h; c->tvsgm_l = L;
+	if (info) { info->paths = paths; info->energy = e; }
+	return SRH_OK;
+}
+
+extern "C" int srh_twoview_sgm_aggregate(srh_context *c, int slot, const srh_params *p, int L, const void *costs_dev,
+                                         const srh_twoview_sgm_params *m, srh_sgm_info *info)
+{
+	int rc;
+	if ((rc = check_slot(c, slot, true)) || (rc = check_params(p))) return rc;
+	if (!costs_dev) return fail(SRH_E_INVALID, "null cost volume");
+	if ((rc = check_tvsgm_params(m, L))) return rc;
+	if (L != p->num_depth_levels) return fail(SRH_E_INVALID, "%d labels, but num_depth_levels is %d (depthFromLabel needs the label count)", L, p->num_depth_levels);
+	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
+	HIP_TRY(hipSetDevice(c->device));
+	const ViewHost &v = c->views[slot];
+	c->tvsgm_w = c->tvsgm_h = c->tvsgm_l = 0;
+	if ((rc = tvsgm_reserve(c, v.w, v.h, L, false))) return rc;
+	c->tvsgm_own_costs = false;
+	return tvsgm_run(c, slot, p, L, static_cast<const double *>(costs_dev), m, info);
+}
+
+// the label cost volume of ref against oth into the context's own buffer
+static int tvsgm_costs(srh_context *c, int ref, int oth, const srh_params *p)
+{
+	int rc;
+	const ViewHost &v = c->views[ref];
+	c->tvsgm_w = c->tvsgm_h = c->tvsgm_l = 0;
+	if ((rc = tvsgm_reserve(c, v.w, v.h, p->num_depth_levels, true))) return rc;
+	c->tvsgm_own_costs = true;
+	Scope s(c, "twoview_label_costs_kernel");
+	HIP_TRY(launch_twoview_label_costs(c->stream, c->d_views, ref, oth, v.w, *p, c->cost_kind == SRH_COST_SAD, 0, v.h,
+	                                   (2*p->window_radius + 1)*p->bad_ret, c->tvsgm_costs, nullptr));
+	return SRH_OK;
+}
+
+extern "C" int srh_twoview_sgm(srh_context *c, int ref, int oth, const srh_params *p, const srh_twoview_sgm_params *m, srh_sgm_info *info)
+{
+	int rc;
+	if ((rc = check_label_costs(c, ref, oth, p))) return rc;
+	const int L = p->num_depth_levels;
+	if ((rc = check_tvsgm_params(m, L))) return rc;
+	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
+	HIP_TRY(hipSetDevice(c->device));
+	if ((rc = tvsgm_costs(c, ref, oth, p))) return rc;
+	return tvsgm_run(c, ref, p, L, c->tvsgm_costs, m, info);
+}
+
+extern "C" int srh_twoview_compute_sgm(srh_context *c, int left, int right, const srh_params *p, const srh_twoview_sgm_params *m,
+                                       double *left_out, double *right_out, srh_sgm_info *infos)
+{
+	int rc;
+	if ((rc = check_label_costs(c, left, right, p))) return rc;
+	if ((rc = check_tvsgm_params(m, p->num_depth_levels))) return rc;
+	const ViewHost &L = c->views[left], &Rv = c->views[right];
+	if (L.w != Rv.w || L.h != Rv.h) return fail(SRH_E_INVALID, "TwoViewStereo needs equal-sized views");
+	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
+	// the progress steps of srh_twoview_compute_mrf, the optimiser's stage renamed
+	for (int k = 0; k < 2; ++k) {
+		const int ref = k == 0 ? left : right, oth = k == 0 ? right : left;
+		progress(c, 1 + 2*k, k == 0 ? "Computing cost volume for left image..." : "Computing cost volume for right image...");
+		HIP_TRY(hipSetDevice(c->device));
+		if ((rc = tvsgm_costs(c, ref, oth, p))) return rc;
+		if (cancelled(c)) { HIP_TRY(hipStreamSynchronize(c->stream)); return fail(SRH_E_CANCELLED, "cancelled"); }
+		progress(c, 2 + 2*k, "Aggregating...");
+		if ((rc = tvsgm_run(c, ref, p, p->num_depth_levels, c->tvsgm_costs, m, infos ? infos + k : nullptr))) return rc;
+		if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
+	}
+	progress(c, 5, "Detecting inconsistencies...");
+	if ((rc = srh_twoview_cross_check(c, left, right, p))) return rc;
+	if (c->filter_invalid && (rc = twoview_filter(c, left, right, p))) return rc;
+	if (left_out && (rc = srh_view_depth_download(c, left, left_out))) return rc;
+	if (right_out && (rc = srh_view_depth_download(c, right, right_out))) return rc;
+	if ((rc = srh_synchronize(c))) return rc;
+	progress(c, 8, "Finished!");
+	return SRH_OK;
+}
+
+extern "C" int srh_twoview_sgm_dims(srh_context *c, int *w, int *h, int *L)
+{
+	if (!c) return fail(SRH_E_INVALID, "null context");
+	if (!c->tvsgm_w) return fail(SRH_E_INVALID, "no finished TwoView SGM run on this context");
+	if (w) *w = c->tvsgm_w;
+	if (h) *h = c->tvsgm_h;
+	if (L) *L = c->tvsgm_l;
+	return SRH_OK;
+}
+
+extern "C" int srh_twoview_sgm_state(srh_context *c, int bw, int bh, int bl, int32_t *labels, double *data_costs, double *sums)
+{
+	if (!c) return fail(SRH_E_INVALID, "null context");
+	if (!c->tvsgm_w) return fail(SRH_E_INVALID, "no finished TwoView SGM run on this context");
+	if (bw != c->tvsgm_w || bh != c->tvsgm_h || bl != c->tvsgm_l)
+		return fail(SRH_E_INVALID, "buffers sized for %dx%d, L = %d, the last TwoView SGM run was %dx%d, L = %d", bw, bh, bl, c->tvsgm_w, c->tvsgm_h, c->tvsgm_l);
+	if (data_costs && !c->tvsgm_own_costs)
+		return fail(SRH_E_INVALID, "the data costs of srh_twoview_sgm_aggregate are the caller's volume: the context keeps none");
+	HIP_TRY(hipSetDevice(c->device));
+	const int w = c->tvsgm_w, h = c->tvsgm_h, L = c->tvsgm_l;
+	const size_t n = (size_t)w*h;
+	TvSgmLayout lay;
+	twoview_sgm_layout(c->tvsgm, w, h, L, lay);
+	if (labels) HIP_TRY(hipMemcpyAsync(labels, lay.ans, n*sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+	if (data_costs) HIP_TRY(hipMemcpyAsync(data_costs, c->tvsgm_costs, n*L*sizeof(double), hipMemcpyDeviceToHost, c->stream));
+	if (sums) HIP_TRY(hipMemcpyAsync(sums, lay.S, n*L*sizeof(double), hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	return SRH_OK;
 }

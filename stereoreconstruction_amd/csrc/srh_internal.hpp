@@ -432,6 +432,21 @@ hipError_t launch_twoview_mrf_setup(hipStream_t st, double *buf, int w, int h, i
 hipError_t launch_twoview_mrf_sweep(hipStream_t st, double *buf, const double *costs, int w, int h, int L, double lambda, double smax, int sweep);
 hipError_t launch_twoview_mrf_energy(hipStream_t st, double *buf, const double *costs, int w, int h, int L, double lambda, double smax);
 hipError_t launch_twoview_mrf_depth(hipStream_t st, const ViewDev *views, int slot, const srh_params &P, double *buf, int w, int h, int L);
+hipError_t launch_twoview_labels_energy(hipStream_t st, const double *costs, const int32_t *ans, double *partial, int nparts, double *energy,
+                                        int w, int h, int L, double lambda, double smax);
+// semi-global aggregation over the label cost volume (srh_twoview_sgm.hip): the sums S, the energy's partials and the labels
+// in one scratch buffer; the data costs ([pixel][L] doubles) are a buffer of their own
+struct TvSgmLayout {
+	double *S, *partial, *energy;
+	int32_t *ans;
+	int nparts;
+	size_t total_doubles;
+};
+size_t twoview_sgm_scratch_doubles(int w, int h, int L);
+void twoview_sgm_layout(double *buf, int w, int h, int L, TvSgmLayout &lay);
+hipError_t launch_twoview_sgm_path(hipStream_t st, double *buf, const double *costs, int w, int h, int L, double lambda, double smax, int k, bool first);
+hipError_t launch_twoview_sgm_readoff(hipStream_t st, const ViewDev *views, int slot, const srh_params &P, double *buf, int w, int h, int L);
+hipError_t launch_twoview_sgm_energy(hipStream_t st, double *buf, const double *costs, int w, int h, int L, double lambda, double smax);
 // the label cost volume of rows [y0, y0 + nrows): cost [pixel][label], pixel (optional) [pixel][label][x2, y2]
 hipError_t launch_twoview_label_costs(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P, bool sad,
                                       int y0, int nrows, double fill, double *cost, int32_t *pixel);

@@ -28,6 +28,7 @@
 #include "srh_geom.hpp"
 #include "srh_walk.hpp"
 #include "srh_window.hpp"
+#include "srh_labels.hpp"
 
 namespace srh {
 
@@ -51,7 +52,6 @@ __device__ __forceinline__ void tm_step_barrier() {
 	asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
-typedef unsigned long long u64;
 // a double as two granules {tag, low half}, {tag, high half}: each one aligned 8-byte store (srh_mrf.hip)
 __device__ __forceinline__ void put_granules(u64 *g, unsigned tag, double v) {
 	const u64 bits = (u64)__double_as_longlong(v), t = (u64)tag << 32;
@@ -62,99 +62,10 @@ __device__ __forceinline__ u64 get_granule(const u64 *g) { return __hip_atomic_l
 __device__ __forceinline__ bool granules_ok(u64 g0, u64 g1, unsigned tag) { return (unsigned)(g0 >> 32) == tag && (unsigned)(g1 >> 32) == tag; }
 __device__ __forceinline__ double granules_value(u64 g0, u64 g1) { return __longlong_as_double((long long)((g0 & 0xffffffffull) | (g1 << 32))); }
 
-// Wave-wide reductions by DPP (no LDS round trips in the step's dependent chain): row_shr 1, 2, 4, 8 leave a row's result
-// in its lane 15 (min is idempotent: the overlapping spans do no harm), row_bcast:15 into rows 1 and 3 and row_bcast:31 into
-// rows 2 and 3 leave the wave's in lane 63, which every lane then reads.  A lane without a source keeps its own value.
-template <int CTRL, int ROW_MASK> __device__ __forceinline__ double dpp_keep(double v) {
-	return __builtin_amdgcn_update_dpp(v, v, CTRL, ROW_MASK, 0xf, false);
-}
-template <int CTRL, int ROW_MASK> __device__ __forceinline__ int dpp_keep(int v) {
-	return __builtin_amdgcn_update_dpp(v, v, CTRL, ROW_MASK, 0xf, false);
-}
-__device__ __forceinline__ double read_lane63(double v) {
-	const long long b = __double_as_longlong(v);
-	const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)b, 63), hi = (unsigned)__builtin_amdgcn_readlane((int)(b >> 32), 63);
-	return __longlong_as_double((long long)(((u64)hi << 32) | lo));
-}
-#define TM_DPP_STEPS(F) F(0x111, 0xf) F(0x112, 0xf) F(0x114, 0xf) F(0x118, 0xf) F(0x142, 0xa) F(0x143, 0xc)
-// the smallest of the wave's 64 values, in every lane
-__device__ __forceinline__ double wave_min(double v) {
-#define TM_MIN_STEP(CTRL, RM) { const double t = dpp_keep<CTRL, RM>(v); v = v > t ? t : v; }
-	TM_DPP_STEPS(TM_MIN_STEP)
-#undef TM_MIN_STEP
-	return read_lane63(v);
-}
-// the smallest value and, among equal ones, the lowest index
-__device__ __forceinline__ void wave_argmin(double &v, int &i) {
-#define TM_ARG_STEP(CTRL, RM) { const double t = dpp_keep<CTRL, RM>(v); const int ti = dpp_keep<CTRL, RM>(i); \
-	                            if (v > t || (v == t && ti < i)) { v = t; i = ti; } }
-	TM_DPP_STEPS(TM_ARG_STEP)
-#undef TM_ARG_STEP
-	v = read_lane63(v);
-	i = __builtin_amdgcn_readlane(i, 63);
-}
-
 // smoothness cost between labels a and k: lambda * min(|a - k|, smooth_max) -- one product
 __device__ __forceinline__ double tm_V(int a, int k, double lambda, double smax) {
 	const double d = (double)(a > k ? a - k : k - a);
 	return lambda*(d < smax ? d : smax);
-}
-
-// the truncated-linear message of buf (a lane's labels lane*NL .. lane*NL + NL - 1; +inf on labels that do not exist):
-// c[d] = lambda*d, cmax = lambda*smooth_max, nwin = the largest d < smooth_max
-template <int NL>
-__device__ __forceinline__ void trunc_message(const double (&buf)[NL], int lane, int nwin, const double (&c)[4], double cmax, double (&M)[NL])
-{
-	const double inf = __builtin_inf();
-	double ext[NL + 6];                                          // labels lane*NL - 3 .. lane*NL + NL + 2
-#pragma unroll
-	for (int j = 0; j < NL; ++j) ext[3 + j] = buf[j];
-#pragma unroll
-	for (int k = 1; k <= 3; ++k) {
-		{	// label lane*NL - k = (lane - off)*NL + jj
-			const int off = (k + NL - 1)/NL, jj = off*NL - k;
-			const double t = __shfl(buf[jj], (lane - off) & 63);
-			ext[3 - k] = lane >= off ? t : inf;
-		}
-		{	// label lane*NL + NL - 1 + k = (lane + off)*NL + jj
-			const int idx = NL - 1 + k, off = idx/NL, jj = idx % NL;
-			const double t = __shfl(buf[jj], (lane + off) & 63);
-			ext[3 + NL - 1 + k] = lane + off < 64 ? t : inf;
-		}
-	}
-	double g = buf[0];
-#pragma unroll
-	for (int j = 1; j < NL; ++j) g = g > buf[j] ? buf[j] : g;
-	g = wave_min(g);
-	const double gm = g + cmax;
-#pragma unroll
-	for (int j = 0; j < NL; ++j) {
-		double m = ext[3 + j] + c[0];
-#pragma unroll
-		for (int d = 1; d <= 3; ++d) {
-			if (d <= nwin) {
-				const double t1 = ext[3 + j - d] + c[d], t2 = ext[3 + j + d] + c[d];
-				m = m > t1 ? t1 : m;
-				m = m > t2 ? t2 : m;
-			}
-		}
-		M[j] = m > gm ? gm : m;
-	}
-}
-
-// a lane's NL consecutive labels as 16-byte pieces (NL even, L a multiple of NL: the lane's labels exist or do not together,
-// and its piece of every [pixel][L] row starts on an even double)
-template <int NL> __device__ __forceinline__ void load_pieces(const double *p, bool c, double (&o)[NL]) {
-#pragma unroll
-	for (int j = 0; j < NL; j += 2) {
-		double2 v = make_double2(0.0, 0.0);
-		if (c) v = *reinterpret_cast<const double2 *>(p + j);
-		o[j] = v.x; o[j + 1] = v.y;
-	}
-}
-template <int NL> __device__ __forceinline__ void store_pieces(double *p, const double (&v)[NL]) {
-#pragma unroll
-	for (int j = 0; j < NL; j += 2) *reinterpret_cast<double2 *>(p + j) = make_double2(v[j], v[j + 1]);
 }
 
 template <int NL> struct Step {
@@ -615,6 +526,15 @@ hipError_t launch_twoview_mrf_energy(hipStream_t st, double *buf, const double *
 	carve(buf, w, h, L, lay);
 	hipLaunchKernelGGL(twoview_mrf_energy_kernel, dim3((unsigned)lay.nparts), dim3(256), 0, st, w, h, L, lambda, smax, costs, lay.ans, lay.partial);
 	hipLaunchKernelGGL(twoview_mrf_energy_sum_kernel, dim3(1), dim3(1024), 0, st, lay.nparts, lay.partial, lay.energy);
+	return hipGetLastError();
+}
+
+// the same energy of any labelling `ans` of the grid (srh_twoview_sgm.hip): partial holds nparts = ceil(w*h/256) doubles
+hipError_t launch_twoview_labels_energy(hipStream_t st, const double *costs, const int32_t *ans, double *partial, int nparts, double *energy,
+                                        int w, int h, int L, double lambda, double smax)
+{
+	hipLaunchKernelGGL(twoview_mrf_energy_kernel, dim3((unsigned)nparts), dim3(256), 0, st, w, h, L, lambda, smax, costs, ans, partial);
+	hipLaunchKernelGGL(twoview_mrf_energy_sum_kernel, dim3(1), dim3(1024), 0, st, nparts, partial, energy);
 	return hipGetLastError();
 }
 

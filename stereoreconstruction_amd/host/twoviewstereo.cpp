@@ -50,6 +50,8 @@ void TwoViewStereo::setUp(int deviceOrdinal) {
 	params_.num_depth_levels = numDepthLevels; params_.image_scale = imageScale;
 	srh_twoview_mrf_params_defaults(&mrfParams_);
 	mrfInfo_[0] = mrfInfo_[1] = srh_mrf_info();
+	srh_twoview_sgm_params_defaults(&sgmParams_);
+	sgmInfo_[0] = sgmInfo_[1] = srh_sgm_info();
 	if (!ctx_ && error_.empty() && srh_create(deviceOrdinal, &ctx_) != SRH_OK) { error_ = srh_last_error(); ctx_ = nullptr; }
 }
 
@@ -245,7 +247,7 @@ double TwoViewStereo::depthFromLabel(int label) const {
 }
 
 void TwoViewStereo::computeDepthMaps() {
-	// twoviewstereo.cpp:150-227: cost volumes (steps 1,3; setUseMRF: + the optimiser, 2,4), cross-check (5), colourise, finished (8)
+	// twoviewstereo.cpp:150-227: cost volumes (steps 1,3; setUseMRF / setUseSGM: + the optimiser / the aggregation, 2,4), cross-check (5), colourise, finished (8)
 	if (!ctx_) { if (error_.empty()) error_ = "no device context"; return; }
 	if (!leftView || !rightView || left.isNull() || right.isNull()) { error_ = "missing view"; return; }
 	if (!uploadViews()) return;
@@ -259,7 +261,9 @@ void TwoViewStereo::computeDepthMaps() {
 		return;
 	}
 	mrfInfo_[0] = mrfInfo_[1] = srh_mrf_info();
-	const int rc_ = useMrf ? srh_twoview_compute_mrf(ctx_, 0, 1, &params_, &mrfParams_, computedDepthLeft.data(), computedDepthRight.data(), mrfInfo_)
+	sgmInfo_[0] = sgmInfo_[1] = srh_sgm_info();
+	const int rc_ = useSgm ? srh_twoview_compute_sgm(ctx_, 0, 1, &params_, &sgmParams_, computedDepthLeft.data(), computedDepthRight.data(), sgmInfo_)
+	              : useMrf ? srh_twoview_compute_mrf(ctx_, 0, 1, &params_, &mrfParams_, computedDepthLeft.data(), computedDepthRight.data(), mrfInfo_)
 	                       : srh_twoview_compute(ctx_, 0, 1, &params_, computedDepthLeft.data(), computedDepthRight.data());
 	srh_set_hooks(ctx_, nullptr, nullptr, nullptr);
 	if (rc_ == SRH_E_CANCELLED) return;              // reference: silent return on cancel

@@ -58,7 +58,7 @@ public:
 	// map, the candidate pixel of the other view that won and the one that held the minimum before it (its cost is the
 	// ratio test's secondBest); SRH_WTA_WINNERS | SRH_WTA_COSTS (3) also their costs in the reference's arithmetic.  0
 	// (default): nothing is kept.  After computeDepthMaps(): (x, y) pairs, (-1, -1) = none; costs, +INF = none.  Empty
-	// vectors when the outputs were not kept, or under setUseMRF(true) (no scan makes those maps).
+	// vectors when the outputs were not kept, or under setUseMRF(true) / setUseSGM(true) (no scan makes those maps).
 	void setKeepWtaOutputs(int flags) { wtaFlags = flags; }
 	int keepWtaOutputs() const { return wtaFlags; }
 	const std::vector<int32_t> &leftWinners() const { return winners_[0]; }
@@ -74,11 +74,21 @@ public:
 	// stereo_recon_hip.h): off (default) computeDepthMaps is the WTA of the reference as it is compiled; on, each direction's
 	// depth map comes from TRW-S over the full label cost volume (srh_twoview_compute_mrf: progress 1, 2 "Optimizing...",
 	// 3, 4 "Optimizing...", 5, 8), the cross-check and the optional hole filling unchanged.  numSteps() stays 8.
-	void setUseMRF(bool on) { useMrf = on; }
+	void setUseMRF(bool on) { useMrf = on; if (on) useSgm = false; }
 	bool useMRF() const { return useMrf; }
 	srh_twoview_mrf_params &mrfParams() { return mrfParams_; }     // SMOOTHNESS_EXP / _MAX / _LAMBDA, 50 sweeps, drop 5
 	// what the optimiser of the last computeDepthMaps reported for the left / right map (iterations 0: none ran)
 	const srh_mrf_info &mrfInfo(bool left = true) const { return mrfInfo_[left ? 0 : 1]; }
+
+	// Semi-global aggregation (NOT IN THE REFERENCE; stereo_recon_hip.h): between the WTA and the MRF stage --
+	// each direction's depth map comes from one pass along up to 8 path directions over the label cost volume, with the MRF
+	// stage's smoothness term (srh_twoview_compute_sgm: progress 1, 2 "Aggregating...", 3, 4 "Aggregating...", 5, 8), the
+	// cross-check and the optional hole filling unchanged.  One of the two switches at most is on: the last call wins.
+	void setUseSGM(bool on) { useSgm = on; if (on) useMrf = false; }
+	bool useSGM() const { return useSgm; }
+	srh_twoview_sgm_params &sgmParams() { return sgmParams_; }     // smoothness term 1 / 2 / 0.25, path_mask 0xFF
+	// what the aggregation of the last computeDepthMaps reported for the left / right map (paths 0: none ran)
+	const srh_sgm_info &sgmInfo(bool left = true) const { return sgmInfo_[left ? 0 : 1]; }
 
 	// Candidate pixels, in visiting order, of pixel (x,y) of the left (fromLeft) or right view in the
 	// other view.  The reference's public epipolarCurve (twoviewstereo.hpp:66-70) takes the unprojected
@@ -151,6 +161,9 @@ private:
 	bool useMrf = false;
 	srh_twoview_mrf_params mrfParams_;
 	srh_mrf_info mrfInfo_[2];
+	bool useSgm = false;
+	srh_twoview_sgm_params sgmParams_;
+	srh_sgm_info sgmInfo_[2];
 	srh_context *ctx_;
 	std::string error_;
 };

@@ -126,6 +126,8 @@ TwoViewStereo::TwoViewStereo(CameraPtr leftView_, QImage left_, QImage leftMask_
 	srh_params_twoview_defaults(&params_);
 	srh_twoview_mrf_params_defaults(&mrfParams_);
 	mrfInfo_[0] = mrfInfo_[1] = srh_mrf_info();
+	srh_twoview_sgm_params_defaults(&sgmParams_);
+	sgmInfo_[0] = sgmInfo_[1] = srh_sgm_info();
 	if (srh_create(deviceOrdinal, &ctx_) != SRH_OK) { error_ = srh_last_error(); ctx_ = nullptr; }
 }
 
@@ -220,12 +222,15 @@ void TwoViewStereo::computeDepthMaps() {
 	srh_set_option(ctx_, "sad_dense", sadDenseOn);
 	if (srh_set_option(ctx_, "wta_outputs", wtaFlags) != SRH_OK) { error_ = srh_last_error(); return; }
 	mrfInfo_[0] = mrfInfo_[1] = srh_mrf_info();
-	if (useMrf) {
-		// a USE_MRF build: the library sequences the run and reports the steps (1, 2, 3, 4, 5, [6, 7,] 8) through its hook
+	sgmInfo_[0] = sgmInfo_[1] = srh_sgm_info();
+	if (useMrf || useSgm) {
+		// a USE_MRF build, or the semi-global aggregation: the library sequences the run and reports the steps
+		// (1, 2, 3, 4, 5, [6, 7,] 8) through its hook
 		cancelWord_ = isCancelled() ? 1 : 0;
 		srh_set_hooks(ctx_, &cancelWord_, relayToTwoView, this);
 		srh_set_option(ctx_, "filter_invalid", filterFlags);
-		const int rc = srh_twoview_compute_mrf(ctx_, 0, 1, &params_, &mrfParams_, computedDepthLeft.data(), computedDepthRight.data(), mrfInfo_);
+		const int rc = useSgm ? srh_twoview_compute_sgm(ctx_, 0, 1, &params_, &sgmParams_, computedDepthLeft.data(), computedDepthRight.data(), sgmInfo_)
+		                      : srh_twoview_compute_mrf(ctx_, 0, 1, &params_, &mrfParams_, computedDepthLeft.data(), computedDepthRight.data(), mrfInfo_);
 		srh_set_option(ctx_, "filter_invalid", 0);
 		srh_set_hooks(ctx_, nullptr, nullptr, nullptr);
 		if (rc == SRH_E_CANCELLED) return;

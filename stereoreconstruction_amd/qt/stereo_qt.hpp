@@ -147,10 +147,20 @@ public:
 	// the MRF stage (a USE_MRF build of the reference; PARITY UNPINNED, stereo_recon_hip.h): off (default) = the WTA; on, each
 	// map comes from TRW-S over the label cost volume (srh_twoview_compute_mrf: progress 1, 2 "Optimizing...", 3, 4, 5, 8),
 	// cross-check and optional hole filling unchanged.  Cancellation is observed at every progress step.
-	void setUseMRF(bool on) { useMrf = on; }
+	void setUseMRF(bool on) { useMrf = on; if (on) useSgm = false; }
 	bool useMRF() const { return useMrf; }
 	srh_twoview_mrf_params &mrfParams() { return mrfParams_; }
 	const srh_mrf_info &mrfInfo(bool left = true) const { return mrfInfo_[left ? 0 : 1]; }
+
+	// Semi-global aggregation (NOT IN THE REFERENCE; stereo_recon_hip.h): between the WTA and the MRF stage --
+	// each direction's depth map comes from one pass along up to 8 path directions over the label cost volume, with the MRF
+	// stage's smoothness term (srh_twoview_compute_sgm: progress 1, 2 "Aggregating...", 3, 4 "Aggregating...", 5, 8), the
+	// cross-check and the optional hole filling unchanged.  One of the two switches at most is on: the last call wins.
+	void setUseSGM(bool on) { useSgm = on; if (on) useMrf = false; }
+	bool useSGM() const { return useSgm; }
+	srh_twoview_sgm_params &sgmParams() { return sgmParams_; }     // smoothness term 1 / 2 / 0.25, path_mask 0xFF
+	// what the aggregation of the last computeDepthMaps reported for the left / right map (paths 0: none ran)
+	const srh_sgm_info &sgmInfo(bool left = true) const { return sgmInfo_[left ? 0 : 1]; }
 	void relayProgress(int step, const char *stage);       // (the library's progress hook lands here)
 
 public: // Task implementation continued: public in the reference as well (stereo/twoviewstereo.hpp:50-52)
@@ -190,6 +200,9 @@ private:
 	bool useMrf = false;
 	srh_twoview_mrf_params mrfParams_;
 	srh_mrf_info mrfInfo_[2];
+	bool useSgm = false;
+	srh_twoview_sgm_params sgmParams_;
+	srh_sgm_info sgmInfo_[2];
 	volatile int cancelWord_ = 0;                          // what the library polls: set from isCancelled() at progress steps
 	srh_context *ctx_;
 	mutable bool uploaded_ = false;                        // views resident on the device (epipolarCurve before computeDepthMaps)
