@@ -583,6 +583,68 @@ int  srh_twoview_compute_sgm(srh_context *ctx, int left_slot, int right_slot, co
 int  srh_twoview_sgm_dims(srh_context *ctx, int *w, int *h, int *L);
 int  srh_twoview_sgm_state(srh_context *ctx, int w, int h, int L, int32_t *labels, double *data_costs, double *sums);
 
+/* ---- MultiViewStereo, semi-global aggregation over the top-K peak labels ----
+ * NOT IN THE REFERENCE.  The step between "best peak wins" and the MRF branch: one pass along up to 8 path directions over
+ * the label space and the energy of the MRF branch above -- a second, non-iterative minimiser of that energy (compare
+ * srh_sgm_info.energy with srh_mrf_info.energy_final on the same peaks).  No iteration, no stopping rule, no host round
+ * trips between directions.
+ * DEFINITION (the device reproduces it bit for bit; tests/mvs_sgm_ref.py restates it):
+ *   labels     0 .. K-1 are the pixel's peaks as srh_mvs_initial_estimate writes them (sorted ascending, (0, -1) as
+ *              placeholders), K is "unknown"; 1 <= K = top_k <= 15 as in the MRF branch, with its status codes.  Every pixel
+ *              is a node, masked-out pixels included, as in the MRF branch.
+ *   D(p, l)    the MRF branch's dataCost, by its kernel: lambda*exp(-beta*cost) for a peak, lambda for a placeholder
+ *              (depth < 0), phi_u for "unknown" -- the bits srh_mvs_mrf_state reports after an MRF run on the same peaks.
+ *   V(q, k; p, d)  the MRF branch's smoothnessCost between label k of pixel q and label d of pixel p: 0 when both are
+ *              "unknown", psi_u when exactly one is, 2*psi_u when both are peaks and either depth is < 0, otherwise
+ *              2.0*fabs(zq - zp)/(zq + zp): one subtraction, one addition, one product and one IEEE division, nothing
+ *              contracted.
+ *   directions (dx, dy) = (+1,0) (-1,0) (0,+1) (0,-1) (+1,+1) (-1,-1) (+1,-1) (-1,+1), the order of srh_twoview_sgm_params;
+ *              bit k of path_mask enables direction k.
+ *   per enabled direction r, pixels in path order, q = p - r:
+ *              q outside the image:  L_r(p, .) = D(p, .)
+ *              otherwise, with prev = L_r(q, .):
+ *                g    = min_k prev[k]
+ *                M[d] = min over k = 0 .. K of (prev[k] + V(q, k; p, d))
+ *                L_r(p, d) = D(p, d) + (M[d] - g)
+ *              every + and - is one IEEE double operation.
+ *   S(p, d)    the sum of L_r(p, d) over the enabled directions in ascending k, left to right: ((L_a + L_b) + L_c) + ...
+ *   label(p)   the lowest d that attains min_d S(p, d)
+ *   depth(p)   the MRF branch's rule: where the mask is WHITE the chosen peak's depth if label < K and that depth is > 0,
+ *              else +INF; untouched elsewhere.  srh_mvs_cross_check follows unchanged.
+ *   energy     totalEnergy() of the labels under the MRF branch's energy (its kernels): comparable with
+ *              srh_mrf_info.energy_final on the same peaks.
+ * PRECONDITIONS: lambda, phi_u, psi_u >= 0 and beta finite, else SRH_E_INVALID; path_mask 0 or any bit above bit 7:
+ * SRH_E_INVALID.  Results are defined bit for bit for finite costs and peak depths that are never exactly 0 (the MRF
+ * branch's precondition); with these in force no negative zero can arise, so the order in which a minimum is reduced does
+ * not affect the bits. */
+typedef struct srh_mvs_sgm_params {
+	double  beta, lambda;         /* 1, 1: the MRF branch's */
+	double  phi_u, psi_u;         /* 0.5, 0.002 */
+	int32_t path_mask;            /* 0xFF */
+} srh_mvs_sgm_params;
+void srh_mvs_sgm_params_defaults(srh_mvs_sgm_params *m);   /* needs no device */
+/* The aggregation on the peaks srh_mvs_initial_estimate filled for this view (DEVICE buffer, w*h*top_k (cost, depth)
+ * pairs; read only): writes the slot's depth map.  The counterpart of srh_mvs_mrf_estimate, with its argument checks.  A run
+ * needs three blocks of w*h*16 doubles (peak depths, data costs, sums) + the labels in a scratch of its own (a later MRF run
+ * leaves the state below alone and vice versa); when that does not fit the free device memory (option "mem_limit_mb"
+ * honoured) the call fails with SRH_E_DEVICE and a message that names the bytes needed, before anything is queued, and the
+ * depth map stays untouched.  The cancel flag is polled between directions; the depth map is written only by the read-off
+ * after the last one.  info (paths, energy) may be NULL. */
+int  srh_mvs_sgm_estimate(srh_context *ctx, int view_slot, int top_k, const void *peaks_dev,
+                          const srh_mvs_sgm_params *m, srh_sgm_info *info);
+/* srh_mvs_initial_estimate with the peaks kept in the context's own scratch, then srh_mvs_sgm_estimate on them. */
+int  srh_mvs_initial_estimate_sgm(srh_context *ctx, int view_slot, const int32_t *neigh_slots, int nneigh,
+                                  const srh_params *p, const srh_mvs_sgm_params *m, srh_sgm_info *info);
+/* The same for several views at once, on the peaks kept by srh_mvs_initial_estimate_peaks: the views run side by side on the
+ * per-view streams of srh_mvs_mrf_estimate_views, each with scratch of its own (one direction of one view does not fill the
+ * chip), and each gets the bits of its single-view run.  infos: nviews entries, may be NULL. */
+int  srh_mvs_sgm_estimate_views(srh_context *ctx, const int32_t *view_slots, int nviews, const srh_mvs_sgm_params *m, srh_sgm_info *infos);
+/* State of the last srh_mvs_sgm_estimate on this context (the semantics and refusals of srh_mvs_mrf_state), to HOST buffers
+ * (each may be NULL): labels (w*h), data_costs (w*h*(top_k+1): D), sums (w*h*(top_k+1): S).  There is no such state after
+ * srh_mvs_sgm_estimate_views or after the view was uploaded again. */
+int  srh_mvs_sgm_dims(srh_context *ctx, int *w, int *h, int *top_k);
+int  srh_mvs_sgm_state(srh_context *ctx, int w, int h, int top_k, int32_t *labels, double *data_costs, double *sums);
+
 /* ---- depth map -> point cloud ----
  * The output side of the path (the reference keeps only the PLY writer, multiviewstereo.cpp:291-315,
  * and the per-view coverage figure it logs, :402-421).  For every pixel of `slot` whose mask is WHITE and whose depth is

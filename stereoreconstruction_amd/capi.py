@@ -79,6 +79,12 @@ class SrhSgmInfo(C.Structure):
     _fields_ = [("paths", C.c_int32), ("energy", C.c_double)]
 
 
+class SrhMvsSgmParams(C.Structure):
+    """srh_mvs_sgm_params"""
+    _fields_ = [("beta", C.c_double), ("lambda_", C.c_double), ("phi_u", C.c_double), ("psi_u", C.c_double),
+                ("path_mask", C.c_int32)]
+
+
 # what srh_twoview_label_costs writes for a label without a pixel (SRH_LABEL_PIXEL_NONE)
 LABEL_PIXEL_NONE = -2147483648
 
@@ -154,6 +160,8 @@ EXPORTS = [
     "srh_twoview_compute_mrf", "srh_twoview_mrf_dims", "srh_twoview_mrf_state",
     "srh_twoview_sgm_params_defaults", "srh_twoview_sgm_aggregate", "srh_twoview_sgm", "srh_twoview_compute_sgm",
     "srh_twoview_sgm_dims", "srh_twoview_sgm_state",
+    "srh_mvs_sgm_params_defaults", "srh_mvs_sgm_estimate", "srh_mvs_initial_estimate_sgm", "srh_mvs_sgm_estimate_views",
+    "srh_mvs_sgm_dims", "srh_mvs_sgm_state",
     "srh_comm_unique_id", "srh_comm_init", "srh_comm_gather_depth", "srh_comm_allgather_depth", "srh_comm_allgather_host",
     "srh_comm_allgather_views",
     "srh_comm_destroy", "srh_comm_set_timeout_ms", "srh_comm_version", "srh_comm_info",
@@ -253,6 +261,14 @@ def lib():
     L.srh_twoview_compute_sgm.argtypes = [vp, C.c_int, C.c_int, C.POINTER(Params), tsp, c_double_p, c_double_p, C.POINTER(SrhSgmInfo)]
     L.srh_twoview_sgm_dims.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.srh_twoview_sgm_state.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_int32_p, c_double_p, c_double_p]
+    msp = C.POINTER(SrhMvsSgmParams)
+    L.srh_mvs_sgm_params_defaults.argtypes = [msp]
+    L.srh_mvs_sgm_params_defaults.restype = None
+    L.srh_mvs_sgm_estimate.argtypes = [vp, C.c_int, C.c_int, C.c_void_p, msp, C.POINTER(SrhSgmInfo)]
+    L.srh_mvs_initial_estimate_sgm.argtypes = [vp, C.c_int, c_int32_p, C.c_int, C.POINTER(Params), msp, C.POINTER(SrhSgmInfo)]
+    L.srh_mvs_sgm_estimate_views.argtypes = [vp, c_int32_p, C.c_int, msp, C.POINTER(SrhSgmInfo)]
+    L.srh_mvs_sgm_dims.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.srh_mvs_sgm_state.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_int32_p, c_double_p, c_double_p]
     L.srh_comm_allgather_views.argtypes = [vp, c_int32_p, C.c_int]
     L.srh_hw_queues_requested.restype = C.c_int
     L.srh_epipolar_preview.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, c_double_p, c_double_p, c_int32_p]
@@ -340,6 +356,18 @@ def twoview_sgm_params(**kw):
     """srh_twoview_sgm_params with its defaults (smooth_exp 1, smooth_max 2, lambda 0.25, path_mask 0xFF)."""
     m = SrhTwoviewSgmParams()
     lib().srh_twoview_sgm_params_defaults(C.byref(m))
+    for k, v in kw.items():
+        k = "lambda_" if k == "lambda" else k
+        if not hasattr(m, k):
+            raise AttributeError(k)
+        setattr(m, k, v)
+    return m
+
+
+def mvs_sgm_params(**kw):
+    """srh_mvs_sgm_params with its defaults (beta 1, lambda 1, phi_u 0.5, psi_u 0.002, path_mask 0xFF)."""
+    m = SrhMvsSgmParams()
+    lib().srh_mvs_sgm_params_defaults(C.byref(m))
     for k, v in kw.items():
         k = "lambda_" if k == "lambda" else k
         if not hasattr(m, k):
@@ -789,6 +817,45 @@ class Context:
         """(w, h, top_k) of the single-view MRF run whose state mvs_mrf_state reports."""
         w, h, k = C.c_int(), C.c_int(), C.c_int()
         _check(lib().srh_mvs_mrf_dims(self._h, C.byref(w), C.byref(h), C.byref(k)))
+        return w.value, h.value, k.value
+
+    # -- MultiViewStereo, semi-global aggregation over the peak labels
+    def mvs_sgm_estimate(self, view_slot, top_k, peaks_dev, m=None):
+        """The aggregation on the device peaks buffer; writes the slot's depth map -> dict(paths, energy)."""
+        m = m if m is not None else mvs_sgm_params()
+        info = SrhSgmInfo()
+        _check(lib().srh_mvs_sgm_estimate(self._h, view_slot, top_k, C.c_void_p(peaks_dev), C.byref(m), C.byref(info)))
+        return _sgm_info(info)
+
+    def mvs_initial_estimate_sgm(self, view_slot, neigh_slots, p, m=None):
+        """Peaks of the view, then the aggregation on them -> dict(paths, energy)."""
+        m = m if m is not None else mvs_sgm_params()
+        info = SrhSgmInfo()
+        nb = np.ascontiguousarray(neigh_slots, dtype=np.int32)
+        _check(lib().srh_mvs_initial_estimate_sgm(self._h, view_slot, nb.ctypes.data_as(c_int32_p), len(nb), C.byref(p),
+                                                  C.byref(m), C.byref(info)))
+        return _sgm_info(info)
+
+    def mvs_sgm_estimate_views(self, view_slots, m=None):
+        """The aggregation of several views side by side (peaks kept by mvs_initial_estimate_peaks) -> list of dict(paths, energy)."""
+        m = m if m is not None else mvs_sgm_params()
+        sl = np.ascontiguousarray(view_slots, dtype=np.int32)
+        infos = (SrhSgmInfo * len(sl))()
+        _check(lib().srh_mvs_sgm_estimate_views(self._h, sl.ctypes.data_as(c_int32_p), len(sl), C.byref(m), infos))
+        return [_sgm_info(i) for i in infos]
+
+    def mvs_sgm_state(self, w, h, top_k):
+        """(labels (h,w) int32, data_costs (h,w,K+1), sums (h,w,K+1)) of the last single-view aggregation."""
+        labels = np.zeros((h, w), dtype=np.int32)
+        D = np.zeros((h, w, top_k + 1), dtype=np.float64)
+        S = np.zeros((h, w, top_k + 1), dtype=np.float64)
+        _check(lib().srh_mvs_sgm_state(self._h, w, h, top_k, labels.ctypes.data_as(c_int32_p), _dptr(D), _dptr(S)))
+        return labels, D, S
+
+    def mvs_sgm_dims(self):
+        """(w, h, top_k) of the single-view aggregation whose state mvs_sgm_state reports."""
+        w, h, k = C.c_int(), C.c_int(), C.c_int()
+        _check(lib().srh_mvs_sgm_dims(self._h, C.byref(w), C.byref(h), C.byref(k)))
         return w.value, h.value, k.value
 
     # -- TwoViewStereo, MRF stage

@@ -238,6 +238,7 @@ struct ViewHost {
 	int wta_flags = 0, wta_oth = -1;            // what the planes hold (SRH_WTA_*; 0: nothing, or stale) and against which slot
 	DevBuf<double> peaks; int peaks_k = 0;      // top-K peaks of the last initial estimate
 	DevBuf<double> mrf;                         // this view's own TRW-S scratch
+	DevBuf<double> sgm;                         // this view's own aggregation scratch (srh_mvs_sgm_estimate_views)
 };
 
 struct ProfEntry { double ms = 0; int64_t n = 0; };
@@ -276,6 +277,9 @@ struct srh_context {
 	DevBuf<double> mrf_peaks;                           // top-K peaks of srh_mvs_initial_estimate_mrf
 	DevBuf<double> mrf;                                 // MRF stage scratch (srh_mrf.hip); mrf_w/h/k: what the last run left in it
 	int mrf_w = 0, mrf_h = 0, mrf_k = 0;
+	DevBuf<double> mvsgm;                               // MultiViewStereo semi-global aggregation scratch (srh_mvs_sgm.hip): depths, data costs, sums, labels
+	int mvsgm_w = 0, mvsgm_h = 0, mvsgm_k = 0;          // what the last single-view run left in it
+	double *mvsgm_host = nullptr;                       // pinned: one energy per view of srh_mvs_sgm_estimate_views
 	DevBuf<double> tvmrf;                               // TwoViewStereo MRF stage scratch (srh_twoview_mrf.hip): messages, granules, labels
 	DevBuf<double> tvmrf_costs;                         //   and the label cost volume of srh_twoview_mrf
 	int tvmrf_w = 0, tvmrf_h = 0, tvmrf_l = 0;          // what the last single-direction run left in them
@@ -739,7 +743,7 @@ extern "C" int srh_create(int device, srh_context **out) {
 static void free_view(ViewHost &v) {
 	if (v.rgba || v.gray || v.edges || v.tvp || v.geo5) (void)hipDeviceSynchronize();
 	v.rgba.release(); v.mask.release(); v.gray.release(); v.gray_tv.release(); v.depth.release(); v.edges.release();
-	v.full.release(); v.fulls.release(); v.grayp.release(); v.fullsp.release(); v.tvp.release(); v.geo5.release(); v.fullp.release(); v.act.release(); v.peaks.release(); v.mrf.release();
+	v.full.release(); v.fulls.release(); v.grayp.release(); v.fullsp.release(); v.tvp.release(); v.geo5.release(); v.fullp.release(); v.act.release(); v.peaks.release(); v.mrf.release(); v.sgm.release();
 	v.wta_xy.release(); v.wta_cost.release();
 	v = ViewHost();
 }
@@ -778,12 +782,13 @@ extern "C" void srh_destroy(srh_context *c) {
 		if (T.done) hipEventDestroy(T.done);
 		T.d_cnt.release(); T.d_span.release(); T.band.release();
 	}
-	c->mrf.release(); c->mrf_peaks.release();
+	c->mrf.release(); c->mrf_peaks.release(); c->mvsgm.release();
 	c->tvmrf.release(); c->tvmrf_costs.release();
 	c->tvsgm.release(); c->tvsgm_costs.release();
 	c->fuse_result.release(); c->fuse_scratch.release();
 	for (int i = 0; i < SRH_MAX_VIEWS; ++i) if (c->mrf_stream[i]) hipStreamDestroy(c->mrf_stream[i]);
 	if (c->mrf_host) hipHostFree(c->mrf_host);
+	if (c->mvsgm_host) hipHostFree(c->mvsgm_host);
 	if (c->comm) (void)rccl_comm_destroy(c->comm);
 	if (c->own_stream) hipStreamDestroy(c->own_stream);
 	delete c;
@@ -926,6 +931,7 @@ static int view_install(srh_context *c, int slot, int w, int h, const void *rgba
 	v.peaks_k = 0;                                              // the top-K peaks belonged to the previous image
 	v.wta_flags = 0; v.wta_oth = -1;                            // and so did the WTA by-products
 	if (c->mrf_w == w && c->mrf_h == h) c->mrf_w = c->mrf_h = c->mrf_k = 0;
+	if (c->mvsgm_w == w && c->mvsgm_h == h) c->mvsgm_w = c->mvsgm_h = c->mvsgm_k = 0;
 	if (c->tvmrf_w == w && c->tvmrf_h == h) c->tvmrf_w = c->tvmrf_h = c->tvmrf_l = 0;
 	if (c->tvsgm_w == w && c->tvsgm_h == h) c->tvsgm_w = c->tvsgm_h = c->tvsgm_l = 0;
 	for (int j = 0; j < SRH_MAX_VIEWS; ++j) { v.list_mode[j] = 0; c->views[j].list_mode[slot] = 0; }   // new geometry
@@ -3218,6 +3224,197 @@ extern "C" int srh_mvs_mrf_state(srh_context *c, int bw, int bh, int bk, int32_t
 		HIP_TRY(hipMemcpy2DAsync(messages, 2*L*sizeof(double), lay.Mh, 16*sizeof(double), L*sizeof(double), n, hipMemcpyDeviceToHost, c->stream));
 		HIP_TRY(hipMemcpy2DAsync(messages + L, 2*L*sizeof(double), lay.Mv, 16*sizeof(double), L*sizeof(double), n, hipMemcpyDeviceToHost, c->stream));
 	}
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	return SRH_OK;
+}
+
+// ------------------------------------------------------------------ MultiViewStereo, semi-global aggregation (srh_mvs_sgm.hip)
+extern "C" void srh_mvs_sgm_params_defaults(srh_mvs_sgm_params *m)
+{
+	if (!m) return;
+	m->beta = 1; m->lambda = 1; m->phi_u = 0.5; m->psi_u = 0.002;     // the MRF branch's
+	m->path_mask = 0xFF;
+}
+
+static int check_mvsgm_params(const srh_mvs_sgm_params *m)
+{
+	if (!m) return fail(SRH_E_INVALID, "null SGM params");
+	if (!(m->lambda >= 0 && m->phi_u >= 0 && m->psi_u >= 0)) return fail(SRH_E_INVALID, "lambda %g, phi_u %g, psi_u %g must be >= 0", m->lambda, m->phi_u, m->psi_u);
+	if (!(m->beta > -__builtin_inf() && m->beta < __builtin_inf())) return fail(SRH_E_INVALID, "beta %g must be finite", m->beta);
+	if (m->path_mask <= 0 || m->path_mask > 0xFF) return fail(SRH_E_INVALID, "path_mask 0x%x: bits 0..7 enable the 8 directions, at least one", (unsigned)m->path_mask);
+	return SRH_OK;
+}
+
+// The scratch of `nviews` runs (bufs[i] for a w[i] x h[i] view), checked against the free device memory before anything is
+// queued, then reserved
+static int mvsgm_reserve(srh_context *c, int nviews, DevBuf<double> *const *bufs, const int *w, const int *h)
+{
+	size_t need = 0, missing = 0, held = 0;
+	for (int i = 0; i < nviews; ++i) {
+		const size_t scratch = mvs_sgm_scratch_doubles(w[i], h[i]);
+		need += scratch*sizeof(double);
+		if (bufs[i]->n < scratch) { missing += scratch*sizeof(double); held += bufs[i]->bytes(); }   // (an outgrown buffer is released first)
+	}
+	size_t free_b = 0, total_b = 0;
+	if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+		size_t avail = free_b + pool_bytes_on(c->device) + held;
+		size_t want = missing;
+		if (c->mem_limit) { want = need; if (avail > c->mem_limit) avail = c->mem_limit; }   // the pretended device holds the whole run
+		if (want > avail)
+			return fail(SRH_E_DEVICE, "the semi-global aggregation of %d view(s) (the first %dx%d) needs %zu bytes of device memory (per view peak depths, data costs and sums, %zu each at 16 doubles per pixel, + the labels; no bands: a path crosses the whole grid), %zu are available",
+			            nviews, w[0], h[0], need, (size_t)w[0]*h[0]*16*sizeof(double), avail);
+	} else (void)hipGetLastError();
+	int rc;
+	for (int i = 0; i < nviews; ++i) if ((rc = bufs[i]->ensure(mvs_sgm_scratch_doubles(w[i], h[i])))) return rc;
+	return SRH_OK;
+}
+
+// (a profile entry per direction: rows, columns and diagonals stream differently)
+static const char *const mvsgm_names[8] = { "mvs_sgm_path_kernel[+1,0]", "mvs_sgm_path_kernel[-1,0]", "mvs_sgm_path_kernel[0,+1]",
+                                            "mvs_sgm_path_kernel[0,-1]", "mvs_sgm_path_kernel[+1,+1]", "mvs_sgm_path_kernel[-1,-1]",
+                                            "mvs_sgm_path_kernel[+1,-1]", "mvs_sgm_path_kernel[-1,+1]" };
+
+extern "C" int srh_mvs_sgm_estimate(srh_context *c, int slot, int K, const void *peaks_dev, const srh_mvs_sgm_params *m, srh_sgm_info *info)
+{
+	int rc;
+	if ((rc = check_slot(c, slot, true))) return rc;
+	if (!peaks_dev || !m) return fail(SRH_E_INVALID, "null peaks / params");
+	if (K < 1 || K > 15) return fail(SRH_E_UNSUPPORTED, "top_k %d outside [1,15] (one lane per label, 16 lanes per pixel)", K);
+	if ((rc = check_mvsgm_params(m))) return rc;
+	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
+	HIP_TRY(hipSetDevice(c->device));
+	const ViewHost &v = c->views[slot];
+	const int w = v.w, h = v.h;
+	c->mvsgm_w = c->mvsgm_h = c->mvsgm_k = 0;
+	DevBuf<double> *buf = &c->mvsgm;
+	if ((rc = mvsgm_reserve(c, 1, &buf, &w, &h))) return rc;
+	{ Scope s(c, "mrf_data_kernel");
+	  HIP_TRY(launch_mvs_sgm_setup(c->stream, c->mvsgm, w, h, K, m->beta, m->lambda, m->phi_u, static_cast<const double *>(peaks_dev))); }
+	int paths = 0;
+	for (int k = 0; k < 8; ++k) {
+		if (!(m->path_mask >> k & 1)) continue;
+		// (nothing of the slot has been written yet: the depth map is the read-off's, after the last direction)
+		if (cancelled(c)) { HIP_TRY(hipStreamSynchronize(c->stream)); return fail(SRH_E_CANCELLED, "cancelled"); }
+		{ Scope s(c, mvsgm_names[k]);
+		  HIP_TRY(launch_mvs_sgm_path(c->stream, c->mvsgm, w, h, K, m->psi_u, k, paths == 0)); }
+		++paths;
+	}
+	{ Scope s(c, "mvs_sgm_readoff_kernel");
+	  HIP_TRY(launch_mvs_sgm_readoff(c->stream, c->d_views, slot, c->mvsgm, w, h, K)); }
+	{ Scope s(c, "mrf_energy_kernel");
+	  HIP_TRY(launch_mvs_sgm_energy(c->stream, c->mvsgm, w, h, K, m->psi_u)); }
+	MvsSgmLayout lay;
+	mvs_sgm_layout(c->mvsgm, w, h, lay);
+	double e = 0.0;
+	HIP_TRY(hipMemcpyAsync(&e, lay.energy, sizeof(e), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	c->mvsgm_w = w; c->mvsgm_h = h; c->mvsgm_k = K;
+	if (info) { info->paths = paths; info->energy = e; }
+	return SRH_OK;
+}
+
+extern "C" int srh_mvs_initial_estimate_sgm(srh_context *c, int slot, const int32_t *neigh, int nneigh, const srh_params *p,
+                                            const srh_mvs_sgm_params *m, srh_sgm_info *info)
+{
+	int rc;
+	if ((rc = check_slot(c, slot, true)) || (rc = check_params(p))) return rc;
+	if (!m) return fail(SRH_E_INVALID, "null SGM params");
+	if (p->top_k < 1 || p->top_k > 15) return fail(SRH_E_UNSUPPORTED, "top_k %d outside [1,15]", p->top_k);
+	if ((rc = check_mvsgm_params(m))) return rc;
+	HIP_TRY(hipSetDevice(c->device));
+	const ViewHost &v = c->views[slot];
+	if ((rc = c->mrf_peaks.ensure((size_t)v.w*v.h*p->top_k*2))) return rc;
+	if ((rc = srh_mvs_initial_estimate(c, slot, neigh, nneigh, p, 0, 0, c->mrf_peaks))) return rc;
+	return srh_mvs_sgm_estimate(c, slot, p->top_k, c->mrf_peaks, m, info);
+}
+
+// The aggregation of several views at once.  One direction of one 1280x960 view is a few hundred waves' worth of lines on a
+// chip of 1024 SIMDs, so the views run side by side, each on a stream of its own (the MRF branch's) with its own scratch:
+// everything is queued direction by direction, and the host waits once, at the end.
+extern "C" int srh_mvs_sgm_estimate_views(srh_context *c, const int32_t *slots, int nviews, const srh_mvs_sgm_params *m, srh_sgm_info *infos)
+{
+	int rc;
+	if (!c) return fail(SRH_E_INVALID, "null context");
+	if (!slots || nviews < 1 || nviews > SRH_MAX_VIEWS || !m) return fail(SRH_E_INVALID, "bad view list / params");
+	if ((rc = check_mvsgm_params(m))) return rc;
+	for (int i = 0; i < nviews; ++i) {
+		if ((rc = check_slot(c, slots[i], true))) return rc;
+		if (c->views[slots[i]].peaks_k < 1) return fail(SRH_E_INVALID, "view slot %d has no peaks (srh_mvs_initial_estimate_peaks first)", slots[i]);
+		for (int j = 0; j < i; ++j) if (slots[j] == slots[i]) return fail(SRH_E_INVALID, "view slot %d listed twice", slots[i]);
+	}
+	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
+	HIP_TRY(hipSetDevice(c->device));
+	c->mvsgm_w = c->mvsgm_h = c->mvsgm_k = 0;                 // the per-view runs leave no state srh_mvs_sgm_state could report
+	std::vector<DevBuf<double> *> bufs(nviews);
+	std::vector<int> ws(nviews), hs(nviews);
+	for (int i = 0; i < nviews; ++i) { ViewHost &v = c->views[slots[i]]; bufs[i] = &v.sgm; ws[i] = v.w; hs[i] = v.h; }
+	if ((rc = mvsgm_reserve(c, nviews, bufs.data(), ws.data(), hs.data()))) return rc;
+	if (!c->mvsgm_host) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->mvsgm_host), sizeof(double)*SRH_MAX_VIEWS, hipHostMallocDefault));
+	for (int i = 0; i < nviews; ++i)
+		if (!c->mrf_stream[i]) HIP_TRY(hipStreamCreateWithFlags(&c->mrf_stream[i], hipStreamNonBlocking));
+	hipEvent_t ev = nullptr;
+	HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+	auto cleanup = [&](int code) { for (int i = 0; i < nviews; ++i) hipStreamSynchronize(c->mrf_stream[i]); hipEventDestroy(ev); return code; };
+	if (hipEventRecord(ev, c->stream) != hipSuccess) return cleanup(fail(SRH_E_DEVICE, "event record failed")); // the peaks were written on the context's stream
+	for (int i = 0; i < nviews; ++i) {
+		ViewHost &v = c->views[slots[i]];
+		if (hipStreamWaitEvent(c->mrf_stream[i], ev, 0) != hipSuccess ||
+		    launch_mvs_sgm_setup(c->mrf_stream[i], v.sgm, v.w, v.h, v.peaks_k, m->beta, m->lambda, m->phi_u, v.peaks) != hipSuccess)
+			return cleanup(fail(SRH_E_DEVICE, "SGM setup of view slot %d failed: %s", slots[i], hipGetErrorString(hipGetLastError())));
+	}
+	int paths = 0;
+	for (int k = 0; k < 8; ++k) {
+		if (!(m->path_mask >> k & 1)) continue;
+		if (cancelled(c)) return cleanup(fail(SRH_E_CANCELLED, "cancelled"));      // (no depth map has been written yet)
+		for (int i = 0; i < nviews; ++i) {
+			ViewHost &v = c->views[slots[i]];
+			if (launch_mvs_sgm_path(c->mrf_stream[i], v.sgm, v.w, v.h, v.peaks_k, m->psi_u, k, paths == 0) != hipSuccess)
+				return cleanup(fail(SRH_E_DEVICE, "SGM direction %d of view slot %d failed: %s", k, slots[i], hipGetErrorString(hipGetLastError())));
+		}
+		++paths;
+	}
+	for (int i = 0; i < nviews; ++i) {
+		ViewHost &v = c->views[slots[i]];
+		MvsSgmLayout lay;
+		mvs_sgm_layout(v.sgm, v.w, v.h, lay);
+		if (launch_mvs_sgm_readoff(c->mrf_stream[i], c->d_views, slots[i], v.sgm, v.w, v.h, v.peaks_k) != hipSuccess ||
+		    launch_mvs_sgm_energy(c->mrf_stream[i], v.sgm, v.w, v.h, v.peaks_k, m->psi_u) != hipSuccess ||
+		    hipMemcpyAsync(&c->mvsgm_host[i], lay.energy, sizeof(double), hipMemcpyDeviceToHost, c->mrf_stream[i]) != hipSuccess)
+			return cleanup(fail(SRH_E_DEVICE, "SGM read-off of view slot %d failed: %s", slots[i], hipGetErrorString(hipGetLastError())));
+	}
+	for (int i = 0; i < nviews; ++i) {
+		if (hipStreamSynchronize(c->mrf_stream[i]) != hipSuccess) return cleanup(fail(SRH_E_DEVICE, "SGM of view slot %d failed", slots[i]));
+		if (infos) { infos[i].paths = paths; infos[i].energy = c->mvsgm_host[i]; }
+	}
+	hipEventDestroy(ev);
+	return SRH_OK;
+}
+
+extern "C" int srh_mvs_sgm_dims(srh_context *c, int *w, int *h, int *top_k)
+{
+	if (!c) return fail(SRH_E_INVALID, "null context");
+	if (!c->mvsgm_w) return fail(SRH_E_INVALID, "no finished single-view SGM run on this context");
+	if (w) *w = c->mvsgm_w;
+	if (h) *h = c->mvsgm_h;
+	if (top_k) *top_k = c->mvsgm_k;
+	return SRH_OK;
+}
+
+extern "C" int srh_mvs_sgm_state(srh_context *c, int bw, int bh, int bk, int32_t *labels, double *data_costs, double *sums)
+{
+	if (!c) return fail(SRH_E_INVALID, "null context");
+	if (!c->mvsgm_w) return fail(SRH_E_INVALID, "no finished single-view SGM run on this context");
+	if (bw != c->mvsgm_w || bh != c->mvsgm_h || bk != c->mvsgm_k)
+		return fail(SRH_E_INVALID, "buffers sized for %dx%d, K = %d, the last SGM run was %dx%d, K = %d", bw, bh, bk, c->mvsgm_w, c->mvsgm_h, c->mvsgm_k);
+	HIP_TRY(hipSetDevice(c->device));
+	const int w = c->mvsgm_w, h = c->mvsgm_h, K = c->mvsgm_k, L = K + 1;
+	const size_t n = (size_t)w*h;
+	MvsSgmLayout lay;
+	mvs_sgm_layout(c->mvsgm, w, h, lay);
+	if (labels) HIP_TRY(hipMemcpyAsync(labels, lay.ans, n*sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+	// device rows are 16 labels wide: copy the first L of each
+	if (data_costs) HIP_TRY(hipMemcpy2DAsync(data_costs, L*sizeof(double), lay.D, 16*sizeof(double), L*sizeof(double), n, hipMemcpyDeviceToHost, c->stream));
+	if (sums) HIP_TRY(hipMemcpy2DAsync(sums, L*sizeof(double), lay.S, 16*sizeof(double), L*sizeof(double), n, hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	return SRH_OK;
 }

@@ -416,6 +416,25 @@ hipError_t launch_mrf_setup(hipStream_t st, double *buf, int w, int h, int K, do
 hipError_t launch_mrf_sweep(hipStream_t st, double *buf, int w, int h, int K, double psiu, int sweep);
 hipError_t launch_mrf_energy(hipStream_t st, double *buf, int w, int h, int K, double psiu);
 hipError_t launch_mrf_depth(hipStream_t st, const ViewDev *views, int slot, double *buf, int w, int h, int K);
+// the same data, energy and depth kernels on a caller's own blocks (rows of 16 doubles per pixel), for a stage with a layout of its own
+hipError_t launch_mrf_data(hipStream_t st, size_t n, int K, double beta, double lambda, double phiu, const double *peaks, double *D, double *pz);
+hipError_t launch_mrf_labels_energy(hipStream_t st, int w, int h, int K, double psiu, const double *D, const double *pz, const int32_t *ans,
+                                    double *partial, int nparts, double *energy);
+hipError_t launch_mrf_labels_depth(hipStream_t st, const ViewDev *views, int slot, int K, const double *pz, const int32_t *ans, size_t n);
+// semi-global aggregation over MultiViewStereo's peak labels (srh_mvs_sgm.hip): peak depths, data costs and sums (rows of 16
+// doubles per pixel), the energy's partials and the labels in one scratch buffer of its own
+struct MvsSgmLayout {
+	double *pz, *D, *S, *partial, *energy;
+	int32_t *ans;
+	int nparts;
+	size_t total_doubles;
+};
+size_t mvs_sgm_scratch_doubles(int w, int h);
+void mvs_sgm_layout(double *buf, int w, int h, MvsSgmLayout &lay);
+hipError_t launch_mvs_sgm_setup(hipStream_t st, double *buf, int w, int h, int K, double beta, double lambda, double phiu, const double *peaks);
+hipError_t launch_mvs_sgm_path(hipStream_t st, double *buf, int w, int h, int K, double psiu, int k, bool first);
+hipError_t launch_mvs_sgm_readoff(hipStream_t st, const ViewDev *views, int slot, double *buf, int w, int h, int K);
+hipError_t launch_mvs_sgm_energy(hipStream_t st, double *buf, int w, int h, int K, double psiu);
 // MRF stage of TwoViewStereo (srh_twoview_mrf.hip): the message planes, hand-over granules, labels and control words in one
 // scratch buffer carved the same way by every launch; the data costs ([pixel][L] doubles) are a buffer of their own
 struct TvMrfLayout {

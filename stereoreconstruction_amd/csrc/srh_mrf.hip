@@ -25,6 +25,7 @@
 // The smoothness cost 2|z1 - z2| / (z1 + z2) is evaluated where it is used (an IEEE division per label pair): the
 // table the CPU library caches would be 1.6 KB per pixel.
 #include "srh_internal.hpp"
+#include "srh_peaks.hpp"
 
 // (the any-K variant keeps a run-time exit in its 16-trip label loops; clang then reports the unroll request as not honoured)
 #pragma clang diagnostic ignored "-Wpass-failed"
@@ -56,10 +57,6 @@ __device__ __forceinline__ void mrf_step_barrier() {
 	asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
-template <int I> __device__ __forceinline__ double bc16(double v) {
-	return __builtin_amdgcn_update_dpp(0.0, v, 0x150 + I, 0xf, 0xf, false);      // row_newbcast:I
-}
-
 typedef unsigned long long u64;
 // a double as two granules {tag, low half}, {tag, high half}: each one aligned 8-byte write-through store
 __device__ __forceinline__ void put_granules(u64 *g, unsigned tag, double v) {
@@ -70,20 +67,6 @@ __device__ __forceinline__ void put_granules(u64 *g, unsigned tag, double v) {
 __device__ __forceinline__ u64 get_granule(const u64 *g) { return __hip_atomic_load(g, RLX_AGENT); }
 __device__ __forceinline__ bool granules_ok(u64 g0, u64 g1, unsigned tag) { return (unsigned)(g0 >> 32) == tag && (unsigned)(g1 >> 32) == tag; }
 __device__ __forceinline__ double granules_value(u64 g0, u64 g1) { return __longlong_as_double((long long)((g0 & 0xffffffffull) | (g1 << 32))); }
-
-// smoothnessCost (multiviewstereo.cpp:499-514) between a peak label of one pixel (depth z1) and label kd of another (z2)
-// (written as selects over an unconditional quotient: the divisions of one step are independent of each other and of
-// the messages, and only straight-line code lets the scheduler overlap them)
-__device__ __forceinline__ double smooth_peak(double z1, double z2, bool kd_unknown, double psi, double psi2) {
-	const double q = 2.0 * fabs(z1 - z2) / (z1 + z2);
-	const double r = (z1 < 0 || z2 < 0) ? psi2 : q;
-	return kd_unknown ? psi : r;
-}
-// the same with the first label given as a carried value: NaN = "unknown", otherwise that label's depth
-__device__ __forceinline__ double smooth_carried(double c, double z2, bool kd_unknown, double psi, double psi2) {
-	if (c != c) return kd_unknown ? 0.0 : psi;
-	return smooth_peak(c, z2, kd_unknown, psi, psi2);
-}
 
 struct Chunk {
 	double D[MRF_CH], oH[MRF_CH], oV[MRF_CH], zs[MRF_CH + 1], zV[MRF_CH];
@@ -442,8 +425,7 @@ hipError_t launch_mrf_setup(hipStream_t st, double *buf, int w, int h, int K, do
 	if ((e = hipMemsetAsync(lay.ans, 0, n*sizeof(int32_t), st)) != hipSuccess) return e;         // clearAnswer(): label 0
 	if ((e = hipMemsetAsync(lay.energy, 0, 4*sizeof(double), st)) != hipSuccess) return e;       // energy + status words
 	if ((e = hipMemsetAsync(lay.hand, 0, lay.hand_words*sizeof(unsigned long long), st)) != hipSuccess) return e;   // no tag is 0
-	hipLaunchKernelGGL(mrf_data_kernel, dim3((unsigned)((n*16 + 255)/256)), dim3(256), 0, st, (long)n, K, beta, lambda, phiu, peaks, lay.D, lay.pz);
-	return hipGetLastError();
+	return launch_mrf_data(st, n, K, beta, lambda, phiu, peaks, lay.D, lay.pz);
 }
 
 template <int MODE, int LT> static hipError_t launch_pass_lt(hipStream_t st, const MrfPassArgs &a, const MrfLayout &lay)
@@ -480,9 +462,7 @@ hipError_t launch_mrf_energy(hipStream_t st, double *buf, int w, int h, int K, d
 {
 	MrfLayout lay;
 	carve(buf, w, h, K, psiu, lay);
-	hipLaunchKernelGGL(mrf_energy_kernel, dim3((unsigned)lay.nparts), dim3(256), 0, st, w, h, K, psiu, 2*psiu, lay.D, lay.pz, lay.ans, lay.partial);
-	hipLaunchKernelGGL(mrf_energy_sum_kernel, dim3(1), dim3(1024), 0, st, lay.nparts, lay.partial, lay.energy);
-	return hipGetLastError();
+	return launch_mrf_labels_energy(st, w, h, K, psiu, lay.D, lay.pz, lay.ans, lay.partial, lay.nparts, lay.energy);
 }
 
 hipError_t launch_mrf_depth(hipStream_t st, const ViewDev *views, int slot, double *buf, int w, int h, int K)
@@ -490,7 +470,28 @@ hipError_t launch_mrf_depth(hipStream_t st, const ViewDev *views, int slot, doub
 	MrfLayout lay;
 	carve(buf, w, h, K, 0.0, lay);
 	const size_t n = (size_t)w*h;
-	hipLaunchKernelGGL(mrf_depth_kernel, dim3((unsigned)((n + 255)/256)), dim3(256), 0, st, views, slot, K, lay.pz, lay.ans);
+	return launch_mrf_labels_depth(st, views, slot, K, lay.pz, lay.ans, n);
+}
+
+// the one launch site of the data, energy and depth kernels: on the blocks a caller names (this file's layout above, or that of
+// srh_mvs_sgm.hip)
+hipError_t launch_mrf_data(hipStream_t st, size_t n, int K, double beta, double lambda, double phiu, const double *peaks, double *D, double *pz)
+{
+	hipLaunchKernelGGL(mrf_data_kernel, dim3((unsigned)((n*16 + 255)/256)), dim3(256), 0, st, (long)n, K, beta, lambda, phiu, peaks, D, pz);
+	return hipGetLastError();
+}
+
+hipError_t launch_mrf_labels_energy(hipStream_t st, int w, int h, int K, double psiu, const double *D, const double *pz, const int32_t *ans,
+                                    double *partial, int nparts, double *energy)
+{
+	hipLaunchKernelGGL(mrf_energy_kernel, dim3((unsigned)nparts), dim3(256), 0, st, w, h, K, psiu, 2*psiu, D, pz, ans, partial);
+	hipLaunchKernelGGL(mrf_energy_sum_kernel, dim3(1), dim3(1024), 0, st, nparts, partial, energy);
+	return hipGetLastError();
+}
+
+hipError_t launch_mrf_labels_depth(hipStream_t st, const ViewDev *views, int slot, int K, const double *pz, const int32_t *ans, size_t n)
+{
+	hipLaunchKernelGGL(mrf_depth_kernel, dim3((unsigned)((n + 255)/256)), dim3(256), 0, st, views, slot, K, pz, ans);
 	return hipGetLastError();
 }
 

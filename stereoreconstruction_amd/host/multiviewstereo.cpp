@@ -38,6 +38,7 @@ MultiViewStereo::MultiViewStereo(int deviceOrdinal)
 {
 	srh_params_mvs_defaults(&params_);
 	srh_mrf_params_defaults(&mrfParams_);
+	srh_mvs_sgm_params_defaults(&sgmParams_);
 	srh_fuse_params_defaults(&fuseParams_);
 	if (srh_create(deviceOrdinal, &ctx_) != SRH_OK) { error_ = srh_last_error(); ctx_ = nullptr; }
 }
@@ -65,6 +66,7 @@ void MultiViewStereo::initialize(const std::vector<CameraPtr> &views_, const std
 		views.push_back(views_[i]);
 	}
 	neighbours.assign(views.size(), std::vector<int>());
+	sgmInfos_.assign(views.size(), srh_sgm_info());
 }
 
 void MultiViewStereo::initialize(ProjectPtr project_, ImageSetPtr imageSet__, const std::vector<CameraPtr> &views_,
@@ -179,8 +181,8 @@ void MultiViewStereo::runTask() {
 		const int32_t *nb = &neigh[static_cast<size_t>(v)*params_.num_neighbours];
 		// #ifdef USE_MRF (:610-652): the peaks are kept and the MRF stage of all views runs afterwards, side by side
 		// (the views' estimates do not depend on each other: the same results as one view after the other)
-		const int rc = useMrf_ ? srh_mvs_initial_estimate_peaks(ctx_, v, nb, count[v], &params_)
-		                       : srh_mvs_initial_estimate(ctx_, v, nb, count[v], &params_, 0, 0, nullptr);
+		const int rc = useMrf_ || useSgm_ ? srh_mvs_initial_estimate_peaks(ctx_, v, nb, count[v], &params_)
+		                                  : srh_mvs_initial_estimate(ctx_, v, nb, count[v], &params_, 0, 0, nullptr);
 		if (rc == SRH_E_CANCELLED || isCancelled()) { srh_set_hooks(ctx_, nullptr, nullptr, nullptr); return; }
 		if (rc != SRH_OK) { error_ = srh_last_error(); srh_set_hooks(ctx_, nullptr, nullptr, nullptr); return; }
 	}
@@ -188,6 +190,14 @@ void MultiViewStereo::runTask() {
 		std::vector<int32_t> all(nv);
 		for (int v = 0; v < nv; ++v) all[v] = v;
 		const int rc = srh_mvs_mrf_estimate_views(ctx_, all.data(), nv, &mrfParams_, nullptr);
+		if (rc == SRH_E_CANCELLED || isCancelled()) { srh_set_hooks(ctx_, nullptr, nullptr, nullptr); return; }
+		if (rc != SRH_OK) { error_ = srh_last_error(); srh_set_hooks(ctx_, nullptr, nullptr, nullptr); return; }
+	}
+	if (useSgm_) {                                     // the aggregation where the MRF branch sits: all views side by side
+		std::vector<int32_t> all(nv);
+		for (int v = 0; v < nv; ++v) all[v] = v;
+		sgmInfos_.assign(nv, srh_sgm_info());
+		const int rc = srh_mvs_sgm_estimate_views(ctx_, all.data(), nv, &sgmParams_, sgmInfos_.data());
 		if (rc == SRH_E_CANCELLED || isCancelled()) { srh_set_hooks(ctx_, nullptr, nullptr, nullptr); return; }
 		if (rc != SRH_OK) { error_ = srh_last_error(); srh_set_hooks(ctx_, nullptr, nullptr, nullptr); return; }
 	}
@@ -211,6 +221,12 @@ void MultiViewStereo::runTask() {
 		colorize(v);
 	}
 	srh_set_hooks(ctx_, nullptr, nullptr, nullptr);
+}
+
+srh_sgm_info MultiViewStereo::sgmInfo(CameraPtr view) const {
+	for (size_t v = 0; v < views.size() && v < sgmInfos_.size(); ++v)
+		if (views[v] == view) return sgmInfos_[v];
+	return srh_sgm_info();
 }
 
 Image MultiViewStereo::depthMap(CameraPtr view) const {

@@ -90,9 +90,17 @@ public:
 	srh_params &params() { return params_; }
 	// The reference picks the MRF branch of computeInitialEstimate at build time (CONFIG+=mrf -> USE_MRF,
 	// StereoReconstruction.pro:100-103); here it is a run-time switch, off by default like the reference's default build.
-	void setUseMRF(bool on) { useMrf_ = on; }
+	void setUseMRF(bool on) { useMrf_ = on; if (on) useSgm_ = false; }
 	bool useMRF() const { return useMrf_; }
 	srh_mrf_params &mrfParams() { return mrfParams_; }
+	// Semi-global aggregation over the peak labels (srh_mvs_sgm_estimate_views; not in the reference): one
+	// pass along the directions of sgmParams().path_mask where the MRF branch sweeps until its energy settles.  Off by
+	// default; setUseSGM(true) and setUseMRF(true) switch each other off (the last call wins).  sgmInfo(view): the
+	// directions aggregated and the labelling's MRF energy of the last run (paths 0 before one, or for an unknown view).
+	void setUseSGM(bool on) { useSgm_ = on; if (on) useMrf_ = false; }
+	bool useSGM() const { return useSgm_; }
+	srh_mvs_sgm_params &sgmParams() { return sgmParams_; }
+	srh_sgm_info sgmInfo(CameraPtr view) const;
 	const std::string &lastError() const { return error_; }
 
 protected:
@@ -113,8 +121,10 @@ private:
 	int numDepthLevels;
 	srh_params params_;
 	srh_mrf_params mrfParams_;
+	srh_mvs_sgm_params sgmParams_;
+	std::vector<srh_sgm_info> sgmInfos_;
 	srh_fuse_params fuseParams_;
-	bool useMrf_ = false;
+	bool useMrf_ = false, useSgm_ = false;
 	srh_context *ctx_;
 	std::string error_;
 };

@@ -308,6 +308,7 @@ MultiViewStereo::MultiViewStereo()
 	const int deviceOrdinal = g_device;
 	srh_params_mvs_defaults(&params_);
 	srh_mrf_params_defaults(&mrfParams_);
+	srh_mvs_sgm_params_defaults(&sgmParams_);
 	srh_fuse_params_defaults(&fuseParams_);
 	if (srh_create(deviceOrdinal, &ctx_) != SRH_OK) { error_ = srh_last_error(); ctx_ = nullptr; }
 }
@@ -394,13 +395,19 @@ void MultiViewStereo::runTask() {
 		emit progressUpdate(step++);
 		emit stageUpdate(tr("Computing cost volume for camera %1").arg(views_[v].name));
 		const int32_t *nb = &neigh[static_cast<size_t>(v)*nn];
-		if ((useMrf_ ? srh_mvs_initial_estimate_peaks(ctx_, v, nb, count[v], &params_)                        // #ifdef USE_MRF: peaks kept,
+		if ((useMrf_ || useSgm_ ? srh_mvs_initial_estimate_peaks(ctx_, v, nb, count[v], &params_)                        // #ifdef USE_MRF: peaks kept,
 		             : srh_mvs_initial_estimate(ctx_, v, nb, count[v], &params_, 0, 0, nullptr)) != SRH_OK) { error_ = srh_last_error(); return; }
 	}
 	if (useMrf_) {                                                                                            // ... the MRF stage of all views side by side
 		std::vector<int32_t> all(V);
 		for (int v = 0; v < V; ++v) all[v] = v;
 		if (srh_mvs_mrf_estimate_views(ctx_, all.data(), V, &mrfParams_, nullptr) != SRH_OK) { error_ = srh_last_error(); return; }
+	}
+	if (useSgm_) {                                                                                            // the aggregation in its place
+		std::vector<int32_t> all(V);
+		for (int v = 0; v < V; ++v) all[v] = v;
+		sgmInfos_.assign(V, srh_sgm_info());
+		if (srh_mvs_sgm_estimate_views(ctx_, all.data(), V, &sgmParams_, sgmInfos_.data()) != SRH_OK) { error_ = srh_last_error(); return; }
 	}
 	for (int v = 0; v < V; ++v)
 		if (srh_view_depth_download(ctx_, v, computedDepths[v].data()) != SRH_OK) { error_ = srh_last_error(); return; }

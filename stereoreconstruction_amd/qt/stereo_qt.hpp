@@ -244,8 +244,15 @@ public:
 	const std::vector<unsigned char> &mask(int viewIndex) const { return masks[viewIndex]; }
 	srh_params &params() { return params_; }
 	// CONFIG+=mrf of the reference (USE_MRF, StereoReconstruction.pro:100-103) as a run-time switch; off by default
-	void setUseMRF(bool on) { useMrf_ = on; }
+	void setUseMRF(bool on) { useMrf_ = on; if (on) useSgm_ = false; }
 	srh_mrf_params &mrfParams() { return mrfParams_; }
+	// Semi-global aggregation over the peak labels (NOT IN THE REFERENCE; stereo_recon_hip.h): one pass along
+	// the directions of sgmParams().path_mask where the MRF branch sweeps (srh_mvs_sgm_estimate_views).  Off by default;
+	// setUseSGM(true) and setUseMRF(true) switch each other off.  sgmInfo(viewIndex): paths and energy of the last run.
+	void setUseSGM(bool on) { useSgm_ = on; if (on) useMrf_ = false; }
+	bool useSGM() const { return useSgm_; }
+	srh_mvs_sgm_params &sgmParams() { return sgmParams_; }
+	srh_sgm_info sgmInfo(int viewIndex) const { return viewIndex >= 0 && viewIndex < static_cast<int>(sgmInfos_.size()) ? sgmInfos_[viewIndex] : srh_sgm_info(); }
 	// the depth maps of the last run's views, in their order, fused into one oriented cloud (srh_mvs_fuse with fuseParams())
 	std::vector<FusedPoint> fusedPointCloud();
 	srh_fuse_params &fuseParams() { return fuseParams_; }
@@ -267,8 +274,10 @@ private:
 	int numDepthLevels;
 	srh_params params_;
 	srh_mrf_params mrfParams_;
+	srh_mvs_sgm_params sgmParams_;
+	std::vector<srh_sgm_info> sgmInfos_;
 	srh_fuse_params fuseParams_;
-	bool useMrf_ = false;
+	bool useMrf_ = false, useSgm_ = false;
 	srh_context *ctx_;
 	QString error_;
 };
