@@ -181,6 +181,7 @@ struct BandBuffers {
 	DevBuf<double> tnum;            // per-label table of the pinhole walk
 	DevBuf<double> pconst;          // per-pixel constants of the dense kernel's fast form (4 doubles per pixel of a band)
 	DevBuf<PixRange> prange;        // per-pixel candidate column range of a band (strip kernel, scan)
+	DevBuf<uint32_t> filllist;      // [count | band pixels whose last columns the cost kernel leaves out] (pixel_range_kernel -> fill kernels)
 	DevBuf<uint32_t> cflag;         // certified arithmetic: [count | band pixels whose decisions the bound does not cover]
 	DevBuf<uint8_t> stpl;           // template scan: the pass's candidate template (twoview_template_kernel)
 	DevBuf<uint32_t> tileflag;      //   and the tiles it leaves to twoview_scan_kernel: [count | tile indices]
@@ -191,7 +192,7 @@ struct BandBuffers {
 	DevBuf<uint32_t> mvs_wdesc;     // window descriptors of the MultiViewStereo walk kernel's waves
 	DevBuf<int32_t> mvs_nwin;
 	template <class F> void each(F f) {
-		f(wbuf); f(cost); f(tnum); f(pconst); f(prange); f(cflag); f(stpl); f(tileflag);
+		f(wbuf); f(cost); f(tnum); f(pconst); f(prange); f(filllist); f(cflag); f(stpl); f(tileflag);
 		f(lcount); f(lcand); f(lrowinfo); f(lmeta); f(mvs_wdesc); f(mvs_nwin);
 	}
 	size_t bytes() { size_t b = 0; each([&](auto &x) { b += x.bytes(); }); return b; }
@@ -301,6 +302,7 @@ struct srh_context {
 	// side stream of the row-run list path: the support windows are computed while the list kernel's last waves drain
 	hipStream_t side_stream = nullptr;
 	hipEvent_t side_go = nullptr, side_done = nullptr;
+	hipEvent_t side_tpl = nullptr;                      // dense plan: the scan template, made on the side stream behind the range kernel
 	int mvs_async = 1;                                  // option "mvs_async": srh_mvs_initial_estimate queues a view on one of two side streams and returns (default); 0 = waits for each view
 	MvsSlot mvs_slot[SRH_MVS_SLOTS];
 	int mvs_turn = 0, mvs_last = -1;
@@ -759,6 +761,7 @@ extern "C" void srh_destroy(srh_context *c) {
 	if (c->side_stream) { hipStreamSynchronize(c->side_stream); hipStreamDestroy(c->side_stream); }
 	if (c->side_go) hipEventDestroy(c->side_go);
 	if (c->side_done) hipEventDestroy(c->side_done);
+	if (c->side_tpl) hipEventDestroy(c->side_tpl);
 	drain_profile(c);
 	for (MvsSlot &S : c->mvs_slot) {
 		if (S.stream) hipStreamDestroy(S.stream);
@@ -1321,6 +1324,10 @@ static int fetch_counters(srh_context *c, int used_dense) {
 			fprintf(stderr, "[srh prof] geodesic kernel: %llu waves, cycles per wave: staging %.0f  sweeps %.0f  exp %.0f  rows out %.0f  pconst: first sweep %.0f  second sweep %.0f  rest %.0f\n",
 			        g[7], (double)g[0]/g[7], (double)g[1]/g[7], (double)g[2]/g[7], (double)g[4]/g[7], (double)g[5]/g[7], (double)g[6]/g[7], (double)g[3]/g[7]);
 	}
+	if (h.dbg_redo[4])
+		fprintf(stderr, "[srh prof] redo kernel: %llu pixels, cycles per pixel (first wave): projections + mask %.0f  walk %.0f  wait for the columns %.0f  "
+		        "running minimum %.0f | second wave: columns %.0f\n", h.dbg_redo[4], (double)h.dbg_redo[0]/h.dbg_redo[4], (double)h.dbg_redo[1]/h.dbg_redo[4],
+		        (double)h.dbg_redo[2]/h.dbg_redo[4], (double)h.dbg_redo[3]/h.dbg_redo[4], (double)h.dbg_redo[5]/h.dbg_redo[4]);
 	if (h.dbg_waves && h.dbg_blocks && h.dbg_phase[3] && h.strip_ticket) {
 		const double nw = (double)h.dbg_waves, nt = (double)h.dbg_blocks/nw;
 		fprintf(stderr, "[srh dbg] strip: waves %llu, tiles/wave %.1f (%.1f with phase 2), cycles/wave %.0f | per tile: ticket %.0f  own requests %.0f  barriers %.0f  setup %.0f  "
@@ -1553,7 +1560,10 @@ struct TvPlan { bool dense = false; int cstride = 0; bool fused = false; };
 struct TvLists { int cmax = 0, smax = 0; bool rows_mode = false, guessed = false, cert = false; size_t lrows = 0; };
 // An attempt of the dense plan: the plan's cstride; strip: the persistent strip form of the cost kernel, the band's windows
 // in the LDS image's layout then; cert: certified arithmetic (fused cost loops + the certified scan and redo); rows per band
-struct TvDense { int cstride = 0; bool strip = false, cert = false, tscan = false; size_t rows = 0; int lanes = 8; };
+// tables_pending: label table and scan template are still to be queued, on the side stream beside the first band's windows;
+// tpl_wait: the template is queued there and the pass's stream has not waited for it yet (the first scan does)
+struct TvDense { int cstride = 0; bool strip = false, cert = false, tscan = false; size_t rows = 0; int lanes = 8;
+                 bool tables_pending = false, tpl_wait = false; };
 
 // One pass ref -> oth over rows [y0, y1) of equal-sized views (clamped to the view: y1 <= y0, nothing to do): what every
 // runner needs.  R, T: window radius and taps; budget: bytes of band scratch.
@@ -1578,7 +1588,9 @@ struct TvPass {
 	int lists_pass(TvLists &S) const;
 	int run_lists(bool cert_ok, srh_context::TvDefer *defer) const;
 	int dense_prepare(TvDense &D) const;
-	void dense_band_inputs(const TvDense &D, int by, int nr) const;
+	void dense_tables(const TvDense &D, bool table, bool tpl) const;
+	bool dense_fill_padded(const TvDense &D, int arith) const;
+	int dense_band_inputs(TvDense &D, int by, int nr, int arith) const;
 	int dense_cost_pass(const TvDense &D, int by, int nr, int arith, bool raw) const;
 	int run_dense(TvDense &D) const;
 	int run_walk() const;
@@ -1930,14 +1942,11 @@ int TvPass::dense_prepare(TvDense &D) const {
 	int rc;
 	D.tscan = c->tscan != 0;
 	if ((rc = c->band.tnum.ensure((size_t)p->num_depth_levels + 8))) return rc;   // (+ 8: the template scan reads the table in whole eights)
-	{ Scope s(c, "pinhole_label_table_kernel");
-	  launch_pinhole_label_table(c->stream, c->d_views, ref, *p, false, c->band.tnum); }
-	if (D.tscan) {
-		// the pass's candidate template: the reference's walk at one pixel (srh_dense.hip, "template scan")
-		if ((rc = c->band.stpl.ensure(scan_template_bytes()))) return rc;
-		Scope s(c, "twoview_template_kernel");
-		launch_scan_template(c->stream, c->d_views, ref, oth, *p, y0, y1 - y0, c->band.tnum, c->band.stpl);
-	}
+	if (D.tscan && (rc = c->band.stpl.ensure(scan_template_bytes()))) return rc;
+	// (option side_weights: the first band queues them on the side stream, behind its windows kernel -- dense_band_inputs)
+	D.tables_pending = c->side_weights != 0;
+	D.tpl_wait = false;
+	if (!D.tables_pending) dense_tables(D, true, true);
 	for (int pass = 0; pass < 2; ++pass) {
 		const int wdoubles = D.strip ? (2*R + 1)*wimg_wp(R) : T;    // doubles per pixel window in the band buffer
 		D.rows = rows_per_band((size_t)wdoubles*sizeof(double) + (size_t)D.cstride*sizeof(double));
@@ -1950,6 +1959,7 @@ int TvPass::dense_prepare(TvDense &D) const {
 	// (+ one tile of slack: the strip kernel copies whole 32-pixel pieces of these rows)
 	if ((rc = c->band.pconst.ensure((rows*(size_t)W + SRH_WTILE)*SRH_PC))) return rc;
 	if ((rc = c->band.prange.ensure(rows*(size_t)W + SRH_WTILE))) return rc;
+	if (!sad && (rc = c->band.filllist.ensure(rows*(size_t)W + 1))) return rc;    // (capacity: the band's pixels)
 	if (D.tscan && (rc = c->band.tileflag.ensure(rows*(size_t)((W + 63)/64) + 1))) return rc;
 	if (D.cert && (rc = c->band.cflag.ensure(rows*(size_t)W + 1))) return rc;
 	D.lanes = D.strip ? strip_block_lanes(D.cstride, c->strip == 1 ? 0 : c->strip) : 8;
@@ -1971,11 +1981,67 @@ int TvPass::dense_prepare(TvDense &D) const {
 	return SRH_OK;
 }
 
-// a band's support windows (with the pixels' constants for cost_ncc) and the pixels' column ranges
-void TvPass::dense_band_inputs(const TvDense &D, int by, int nr) const {
+// the label-only part of the pinhole walk and the pass's candidate template: the reference's walk at one pixel
+// (srh_dense.hip, "template scan")
+void TvPass::dense_tables(const TvDense &D, bool table, bool tpl) const {
+	if (table) {
+		Scope s(c, "pinhole_label_table_kernel");
+		launch_pinhole_label_table(c->stream, c->d_views, ref, *p, false, c->band.tnum);
+	}
+	if (tpl && D.tscan) {
+		Scope s(c, "twoview_template_kernel");
+		launch_scan_template(c->stream, c->d_views, ref, oth, *p, y0, y1 - y0, c->band.tnum, c->band.stpl);
+	}
+}
+
+// the cost kernel's form under `arith`: its blocks start on even columns (what the fill launch and the fill list go by)
+bool TvPass::dense_fill_padded(const TvDense &D, int arith) const { return D.strip ? D.lanes == 8 : arith != 5; }
+
+// A band's support windows (with the pixels' constants for cost_ncc), the pixels' column ranges and the list of the pixels
+// whose last columns the cost kernel under `arith` leaves out.
+// Option side_weights: the windows kernel is queued first, on the pass's stream; label table, range kernel and scan
+// template (table and template: the first band's) run on the context's side stream -- one stream for both passes of
+// srh_twoview_compute, in order, each band waiting (side_go) for what its pass's stream held when the band began: the last
+// readers of the tables and ranges it overwrites.  The pass's stream takes table and ranges back (side_done) before the
+// cost kernel, the template (side_tpl) before the first scan: table and range kernel find room on a compute unit beside the
+// windows kernel's waves, the template's workgroup (80 registers per lane, 45 KB of LDS) does not and starts when the
+// windows kernel leaves -- behind the range kernel it holds nothing up (profiles/dense_tail_timeline.txt).
+int TvPass::dense_band_inputs(TvDense &D, int by, int nr, int arith) const {
+	uint32_t *filllist = sad ? nullptr : (uint32_t *)c->band.filllist;
+	const bool side = c->side_weights != 0;
+	if (side) {
+		if (!c->side_stream) {
+			HIP_TRY(hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking));
+			HIP_TRY(hipEventCreateWithFlags(&c->side_go, hipEventDisableTiming));
+			HIP_TRY(hipEventCreateWithFlags(&c->side_done, hipEventDisableTiming));
+		}
+		if (!c->side_tpl) HIP_TRY(hipEventCreateWithFlags(&c->side_tpl, hipEventDisableTiming));
+		HIP_TRY(hipEventRecord(c->side_go, c->stream));
+	}
 	run_weights(c, ref, W, *p, by, nr, SRH_WTILE, !sad ? (double *)c->band.pconst : nullptr, D.strip);
-	Scope s(c, "pixel_range_kernel");
-	launch_pixel_range(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.tnum, D.cstride, c->band.prange);
+	const bool tables = side && D.tables_pending;
+	D.tables_pending = false;
+	if (side) {
+		HIP_TRY(hipStreamWaitEvent(c->side_stream, c->side_go, 0));
+		std::swap(c->stream, c->side_stream);                     // (Scope and the launchers read c->stream)
+		if (tables) dense_tables(D, true, false);
+	}
+	hipError_t e = filllist ? hipMemsetAsync(filllist, 0, sizeof(uint32_t), c->stream) : hipSuccess;
+	{ Scope s(c, "pixel_range_kernel");
+	  launch_pixel_range(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.tnum, D.cstride, c->band.prange,
+	                     D.lanes, dense_fill_padded(D, arith), filllist); }
+	if (side) {
+		if (e == hipSuccess) e = hipEventRecord(c->side_done, c->stream);
+		if (tables && D.tscan) {
+			dense_tables(D, false, true);
+			if (e == hipSuccess) e = hipEventRecord(c->side_tpl, c->stream);
+			D.tpl_wait = true;
+		}
+		std::swap(c->stream, c->side_stream);
+		if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, c->side_done, 0);
+	}
+	if (e != hipSuccess) return fail(SRH_E_DEVICE, "dense band inputs: %s", hipGetErrorString(e));
+	return SRH_OK;
 }
 
 // the band's cost rows under one arithmetic: strip kernel or one workgroup per tile, then the left-out columns
@@ -2007,10 +2073,11 @@ int TvPass::dense_cost_pass(const TvDense &D, int by, int nr, int arith, bool ra
 			launch_twoview_dense_cost(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, wstride,
 			                          c->band.tnum, c->band.cost, cstride, c->d_cnt, c->band.pconst, arith, c->band.prange); }
 	}
-	// the left-out columns (per-tile kernel: its one-pass form leaves none out; D.lanes is 8 there)
+	// the left-out columns (per-tile kernel: its one-pass form leaves none out; D.lanes is 8 there), from the list the range
+	// kernel made for this form
 	Scope s(c, "twoview_lazy_fill_kernel");
-	launch_twoview_lazy_fill(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.prange, c->band.wbuf, wstride, c->views[ref].tvp,
-	                         c->views[oth].tvp, D.strip, D.lanes, D.strip ? D.lanes == 8 : arith != 5, c->band.cost, cstride, c->d_cnt);
+	launch_twoview_lazy_fill(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.prange, c->band.filllist, c->band.wbuf, wstride, c->views[ref].tvp,
+	                         c->views[oth].tvp, D.strip, D.lanes, dense_fill_padded(D, arith), c->band.cost, cstride, c->d_cnt);
 	return SRH_OK;
 }
 
@@ -2023,22 +2090,30 @@ int TvPass::run_dense(TvDense &D) const {
 	for (int by = y0; by < y1; by += (int)D.rows) {
 		if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
 		const int nr = std::min((int)D.rows, y1 - by);
-		dense_band_inputs(D, by, nr);
+		if ((rc = dense_band_inputs(D, by, nr, cost_arith))) return rc;
 		if (D.cert) HIP_TRY(hipMemsetAsync(c->band.cflag, 0, sizeof(uint32_t), c->stream));
 		if ((rc = dense_cost_pass(D, by, nr, cost_arith, false))) return rc;
+		if (D.tpl_wait) { HIP_TRY(hipStreamWaitEvent(c->stream, c->side_tpl, 0)); D.tpl_wait = false; }
 		{ Scope s(c, "twoview_scan_kernel");
 		  launch_twoview_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.tnum, c->band.cost, D.cstride, c->d_cnt, c->band.prange,
 		                      D.cert ? c->band.cflag : nullptr, -1, D.cert && D.strip ? c->band.pconst : nullptr, D.tscan ? c->band.stpl : nullptr, c->band.tileflag, c->num_cus, wout, c->tscan_bound); }
 		if (D.cert) {
 			// the pixels whose decisions the bound does not cover, in the reference's arithmetic: their cost rows are
 			// refilled and they are scanned again -- launched for a capacity, the count stays on the device
+			// (one kernel does both where the wave form of the rescan is eligible: twoview_redo_kernel, the columns beside the walk)
 			const int cap = redo_capacity((size_t)nr*W);
-			{ Scope s(c, "twoview_refill_kernel");
-			  launch_twoview_refill(c->stream, W, *p, by, c->band.prange, c->band.cflag, cap, c->band.wbuf, D.strip, c->views[ref].tvp,
-			                        c->views[oth].tvp, c->band.cost, D.cstride, c->d_cnt); }
-			Scope s(c, "twoview_rescan_kernel");
-			launch_twoview_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.tnum, c->band.cost, D.cstride, c->d_cnt, c->band.prange,
-			                    c->band.cflag, cap, nullptr, nullptr, nullptr, c->num_cus, wout);
+			if (twoview_redo_takes(*p, D.cstride)) {
+				Scope s(c, "twoview_redo_kernel");
+				launch_twoview_redo(c->stream, c->d_views, ref, oth, W, *p, by, c->band.tnum, c->band.wbuf, D.strip, c->views[ref].tvp,
+				                    c->views[oth].tvp, c->band.cost, D.cstride, c->band.prange, c->band.cflag, cap, c->d_cnt, wout);
+			} else {
+				{ Scope s(c, "twoview_refill_kernel");
+				  launch_twoview_refill(c->stream, W, *p, by, c->band.prange, c->band.cflag, cap, c->band.wbuf, D.strip, c->views[ref].tvp,
+				                        c->views[oth].tvp, c->band.cost, D.cstride, c->d_cnt); }
+				Scope s(c, "twoview_rescan_kernel");
+				launch_twoview_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.tnum, c->band.cost, D.cstride, c->d_cnt, c->band.prange,
+				                    c->band.cflag, cap, nullptr, nullptr, nullptr, c->num_cus, wout);
+			}
 		}
 		winner_costs(by, nr, D.strip);
 	}
@@ -2176,7 +2251,7 @@ extern "C" int srh_twoview_cost_rows(srh_context *c, int ref, int oth, const srh
 	if ((rc = P.dense_prepare(D))) return rc;
 	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
 	const int nr = std::min((int)D.rows, P.y1 - P.y0);
-	P.dense_band_inputs(D, P.y0, nr);
+	if ((rc = P.dense_band_inputs(D, P.y0, nr, form))) return rc;
 	if (nr != P.y1 - P.y0) return fail(SRH_E_UNSUPPORTED, "cost rows: the rows asked for do not fit one band (%d of %d)", nr, P.y1 - P.y0);
 	if (cost_out) {
 		// the band's cost rows under the arithmetic asked for, as the cost kernel leaves them, and the pixels' column ranges

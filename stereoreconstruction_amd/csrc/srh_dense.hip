@@ -1472,32 +1472,35 @@ bool launch_twoview_dense_cost(hipStream_t st, const ViewDev *views, int ref, in
 #define SC_MW 1024
 
 // The columns the cost kernel leaves out (dense_cover_hi: a last block that would cost its lanes a whole extra round
-// for one or two columns) are evaluated here, one thread per pixel, with the general cost -- so that the scan kernel
-// only ever looks costs up.  (Inlined at every slot of the scan's flushes, that general cost made the scan kernel
-// 27 000 instructions long, far beyond the instruction cache.)  Radii without a template instance: tv_cost through the views.
+// for one or two columns) are evaluated here with the general cost -- so that the scan kernel only ever looks costs up.
+// (Inlined at every slot of the scan's flushes, that general cost made the scan kernel 27 000 instructions long, far
+// beyond the instruction cache.)  The pixels come from pixel_range_kernel's list for the same form, filllist = [count |
+// band pixel indices], in whatever order its atomics left them: a fixed grid shares it, one thread per listed pixel, the
+// count is read here -- an empty list (C3 in the 8-wave strip form) costs the launch and nothing else.
+// Radii without a template instance: tv_cost through the views.
+#define LF_BLOCKS 512
 __global__ void twoview_lazy_fill_kernel(const ViewDev *__restrict__ views, int ref, int oth, srh_params P, int y0, int nrows,
-                                         const PixRange *__restrict__ prange, const double *__restrict__ wbuf, size_t wstride,
+                                         const PixRange *__restrict__ prange, const uint32_t *__restrict__ filllist,
+                                         const double *__restrict__ wbuf, size_t wstride,
                                          int ncb, int lanes, int pad, double *__restrict__ cost, int cstride, Counters *__restrict__ cnt)
 {
+	const uint32_t nfill = filllist[0];
+	if (nfill == 0) return;
 	const ViewDev &L = views[ref];
 	const ViewDev &Rv = views[oth];
 	const int W = L.w;
-	const size_t q = (size_t)blockIdx.x*blockDim.x + threadIdx.x;
 	unsigned n_lazy = 0;
-	if (q < (size_t)nrows*W) {
-		const int x = (int)(q % W), trow = (int)(q / W), y = y0 + trow;
+	for (uint32_t f = blockIdx.x*blockDim.x + threadIdx.x; f < nfill; f += gridDim.x*blockDim.x) {
+		const uint32_t q = filllist[1 + f];
+		const int x = (int)(q % (uint32_t)W), trow = (int)(q / (uint32_t)W), y = y0 + trow;
 		const PixRange pr = prange[q];
-		if (pr.hi >= pr.lo) {
-			const int cover = dense_cover_hi(pr.lo, pr.hi, ncb, lanes, pad != 0);
-			if (cover < pr.hi) {
-				const int R = P.window_radius, T = (2*R + 1)*(2*R + 1);
-				const double *wq = wbuf + wbuf_offset(W, T, trow, x);
-				double *crow = cost + ((size_t)trow*((W + DC_TP - 1)/DC_TP) + (x/DC_TP))*(size_t)cstride*DC_TP + (x % DC_TP);
-				for (int c = cover + 1; c <= pr.hi; ++c) {
-					crow[(size_t)(c - pr.lo)*DC_TP] = tv_cost(L, Rv, wq, wstride, P, x, y, c, y);
-					++n_lazy;
-				}
-			}
+		const int cover = dense_cover_hi(pr.lo, pr.hi, ncb, lanes, pad != 0);
+		const int R = P.window_radius, T = (2*R + 1)*(2*R + 1);
+		const double *wq = wbuf + wbuf_offset(W, T, trow, x);
+		double *crow = cost + ((size_t)trow*((W + DC_TP - 1)/DC_TP) + (x/DC_TP))*(size_t)cstride*DC_TP + (x % DC_TP);
+		for (int c = cover + 1; c <= pr.hi; ++c) {
+			crow[(size_t)(c - pr.lo)*DC_TP] = tv_cost(L, Rv, wq, wstride, P, x, y, c, y);
+			++n_lazy;
 		}
 	}
 	block_count_add(&cnt->n_eval_device, n_lazy);
@@ -1506,26 +1509,27 @@ __global__ void twoview_lazy_fill_kernel(const ViewDev *__restrict__ views, int 
 template <int R>
 __global__ __launch_bounds__(256)
 void twoview_lazy_fill_planes_kernel(int W, srh_params P, int y0, int nrows, const PixRange *__restrict__ prange,
+                                     const uint32_t *__restrict__ filllist,
                                      const double *__restrict__ wbuf, int wimg, const double *__restrict__ ref_tvp,
                                      const double *__restrict__ oth_tvp, int ncb, int lanes, int pad,
                                      double *__restrict__ cost, int cstride, Counters *__restrict__ cnt)
 {
-	const size_t q = (size_t)blockIdx.x*blockDim.x + threadIdx.x;
+	const uint32_t nfill = filllist[0];
+	if (nfill == 0) return;
 	unsigned n_lazy = 0;
-	if (q < (size_t)nrows*W) {
-		const int x = (int)(q % W), trow = (int)(q / W), y = y0 + trow;
+	for (uint32_t f = blockIdx.x*blockDim.x + threadIdx.x; f < nfill; f += gridDim.x*blockDim.x) {
+		const uint32_t q = filllist[1 + f];
+		const int x = (int)(q % (uint32_t)W), trow = (int)(q / (uint32_t)W), y = y0 + trow;
 		const PixRange pr = prange[q];
-		const int cover = pr.hi >= pr.lo ? dense_cover_hi(pr.lo, pr.hi, ncb, lanes, pad != 0) : pr.hi;
-		if (cover < pr.hi) {
-			const int SP = padded_stride(W);
-			const WindowAt wa = window_at<R>(wbuf, wimg, W, trow, x);
-			const double *lp = ref_tvp + (size_t)(y + SRH_PADY - R)*SP + (x + SRH_PADL - R);
-			double *crow = cost + ((size_t)trow*((W + DC_TP - 1)/DC_TP) + (x/DC_TP))*(size_t)cstride*DC_TP + (x % DC_TP);
-			for (int c = cover + 1; c <= pr.hi; ++c) {
-				const double *rp = oth_tvp + (size_t)(y + SRH_PADY - R)*SP + (c + SRH_PADL - R);
-				crow[(size_t)(c - pr.lo)*DC_TP] = window_exact_cost<R>(wa.wq, wa.wrow, wa.wcol, lp, rp, SP, SP, P);
-				++n_lazy;
-			}
+		const int cover = dense_cover_hi(pr.lo, pr.hi, ncb, lanes, pad != 0);
+		const int SP = padded_stride(W);
+		const WindowAt wa = window_at<R>(wbuf, wimg, W, trow, x);
+		const double *lp = ref_tvp + (size_t)(y + SRH_PADY - R)*SP + (x + SRH_PADL - R);
+		double *crow = cost + ((size_t)trow*((W + DC_TP - 1)/DC_TP) + (x/DC_TP))*(size_t)cstride*DC_TP + (x % DC_TP);
+		for (int c = cover + 1; c <= pr.hi; ++c) {
+			const double *rp = oth_tvp + (size_t)(y + SRH_PADY - R)*SP + (c + SRH_PADL - R);
+			crow[(size_t)(c - pr.lo)*DC_TP] = window_exact_cost<R>(wa.wq, wa.wrow, wa.wcol, lp, rp, SP, SP, P);
+			++n_lazy;
 		}
 	}
 	block_count_add(&cnt->n_eval_device, n_lazy);
@@ -1576,19 +1580,19 @@ bool launch_twoview_refill(hipStream_t st, int width, const srh_params &P, int y
 // ref_tvp / oth_tvp: the NaN-bordered planes (radius 5 or 2: the fast general cost); null: tv_cost through the views.
 // wimg: the band buffer holds the strip path's LDS-image windows (lanes / pad as that kernel's form), else tile-major.
 void launch_twoview_lazy_fill(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P,
-                              int y0, int nrows, const PixRange *prange, const double *wbuf, size_t wstride,
+                              int y0, int nrows, const PixRange *prange, const uint32_t *filllist, const double *wbuf, size_t wstride,
                               const double *ref_tvp, const double *oth_tvp, bool wimg,
                               int lanes, bool padded, double *cost, int cstride, Counters *cnt)
 {
 	const size_t n = (size_t)nrows*width;
-	const dim3 grid((unsigned)((n + 255)/256)), block(256);
+	const dim3 grid((unsigned)std::min<size_t>((n + 255)/256, LF_BLOCKS)), block(256);
 	const int pad = padded ? 1 : 0;
 	if (ref_tvp && P.window_radius == 5)
-		hipLaunchKernelGGL(twoview_lazy_fill_planes_kernel<5>, grid, block, 0, st, width, P, y0, nrows, prange, wbuf, wimg ? 1 : 0, ref_tvp, oth_tvp, 8, lanes, pad, cost, cstride, cnt);
+		hipLaunchKernelGGL(twoview_lazy_fill_planes_kernel<5>, grid, block, 0, st, width, P, y0, nrows, prange, filllist, wbuf, wimg ? 1 : 0, ref_tvp, oth_tvp, 8, lanes, pad, cost, cstride, cnt);
 	else if (ref_tvp && P.window_radius == 2)
-		hipLaunchKernelGGL(twoview_lazy_fill_planes_kernel<2>, grid, block, 0, st, width, P, y0, nrows, prange, wbuf, wimg ? 1 : 0, ref_tvp, oth_tvp, 8, lanes, pad, cost, cstride, cnt);
+		hipLaunchKernelGGL(twoview_lazy_fill_planes_kernel<2>, grid, block, 0, st, width, P, y0, nrows, prange, filllist, wbuf, wimg ? 1 : 0, ref_tvp, oth_tvp, 8, lanes, pad, cost, cstride, cnt);
 	else
-		hipLaunchKernelGGL(twoview_lazy_fill_kernel, grid, block, 0, st, views, ref, oth, P, y0, nrows, prange, wbuf, wstride, 8, lanes, pad, cost, cstride, cnt);
+		hipLaunchKernelGGL(twoview_lazy_fill_kernel, grid, block, 0, st, views, ref, oth, P, y0, nrows, prange, filllist, wbuf, wstride, 8, lanes, pad, cost, cstride, cnt);
 }
 
 // sums / minima over the 64 lanes of the scan kernel's one-wave workgroup (no LDS, no barrier)
@@ -2321,32 +2325,51 @@ void twoview_tscan_kernel(const ViewDev *__restrict__ views, int ref, int oth, s
 	}
 }
 
-// The exact scan of the FLAGGED pixels, one WAVE per pixel.  twoview_scan_kernel<false, true> gives a flagged pixel one lane:
-// a handful of pixels then cost a whole pixel's serial walk (256 dependent label projections, every cost a dependent
-// load: 0.25 ms on C3, whatever their number).  Here the wave splits the pixel's work: (1) the label projections, one
-// label per lane; (2) the other view's mask bytes of the pixel's column range; (3) ONE lane replays the reference's walk
-// over the projected points and writes the candidate columns in visiting order (twoviewstereo.cpp:999-1054: the cheap,
-// strictly sequential part); (4) all lanes fetch the candidates' costs; (5) one lane runs the running-min rule
-// (twoviewstereo.cpp:293-305) over them.  Same functions, same order, same bits as the one-lane form.
-#define RSW_MAXD 1024                  // labels (else: the one-lane form)
+// The certified redo of the FLAGGED pixels in one kernel, a workgroup per pixel.  twoview_scan_kernel<false, true> gives a
+// flagged pixel one lane: a handful of pixels then cost a whole pixel's serial walk (256 dependent label projections, every
+// cost a dependent load: 0.25 ms on C3, whatever their number), behind a launch of twoview_refill_kernel for their cost
+// rows.  Here the workgroup splits the pixel's work.  All lanes: (1) the label projections, one label per lane; (2) the
+// other view's mask bytes of the pixel's column range.  Then ONE lane (3) replays the reference's walk over the projected
+// points and writes the candidate columns in visiting order (twoviewstereo.cpp:999-1054: the cheap, strictly sequential
+// part) WHILE the other waves evaluate the columns [lo, hi] in the reference's arithmetic -- window_exact_cost as the refill
+// kernel calls it, 121 dependent taps each -- into the band's cost row (which holds afterwards what the refill kernel
+// leaves there) and into LDS; neither needs the other before the look-ups.  (5) One lane runs the running-minimum rule
+// (twoviewstereo.cpp:293-305) over the candidates, their costs read from LDS.  Same functions, same order, same bits as
+// the pair refill + one-lane scan; Counters::cert_overflow is raised where the pair raises it (more flagged pixels than the
+// capacity) and for a pixel with more than RSW_MAXC candidates.  A fixed grid shares the list; the count is read here.
+#define RSW_MAXD 1024                  // labels (else: the pair refill + one-lane scan)
 #define RSW_MAXC 6144                  // candidates of a pixel (more: Counters::cert_overflow, the pass is repeated in mode 0)
-template <bool WTA>
-__global__ __launch_bounds__(64)
-void twoview_rescan_wave_kernel(const ViewDev *__restrict__ views, int ref, int oth, srh_params P, int y0,
-                                const double *__restrict__ tnum, const double *__restrict__ cost, int cstride,
-                                const PixRange *__restrict__ prange, const uint32_t *__restrict__ cflag, int cap,
-                                Counters *__restrict__ cnt, int32_t *__restrict__ wout)
+#define RD_THREADS 512
+#define RD_GRID 512
+template <int R, bool WTA>
+__global__ __launch_bounds__(RD_THREADS)
+void twoview_redo_kernel(const ViewDev *__restrict__ views, int ref, int oth, srh_params P, int y0,
+                         const double *__restrict__ tnum, const double *__restrict__ wbuf, int wimg,
+                         const double *__restrict__ ref_tvp, const double *__restrict__ oth_tvp,
+                         double *__restrict__ cost, int cstride,
+                         const PixRange *__restrict__ prange, const uint32_t *__restrict__ cflag, int cap,
+                         Counters *__restrict__ cnt, int32_t *__restrict__ wout)
 {
 	const ViewDev &L = views[ref];
 	const ViewDev &Rv = views[oth];
 	const int W = L.w, OW = Rv.w, OH = Rv.h;
-	const int lane = threadIdx.x;
+	const int tid = threadIdx.x;
 	__shared__ double sx[RSW_MAXD], sy[RSW_MAXD];
 	__shared__ unsigned short scol[RSW_MAXC];
-	__shared__ double scost[RSW_MAXC];
+	__shared__ double srow[4096];                                     // the pixel's cost row, by column - lo (cstride <= 4096)
 	__shared__ unsigned char smask[4096 + 64];
 	__shared__ int s_n;
 	const uint32_t nflag = cflag[0];
+	if (blockIdx.x == 0 && tid == 0 && nflag > (uint32_t)cap) atomicAdd(&cnt->cert_overflow, 1ull);
+	unsigned n_cols = 0;
+#ifdef SRH_PROFILE_PHASES
+	// diagnostic build: wave 0's clocks in cnt->dbg_redo: 0 set-up + projections + mask, 1 walk (lane 0) or columns, 2 the
+	// wait for the other side, 3 running minimum and stores, [4] pixels; wave 1's column time in [5]
+	unsigned long long rph[6] = {0, 0, 0, 0, 0, 0}, rt = __builtin_readcyclecounter();
+#define RD_STAMP(k) do { const unsigned long long tn_ = __builtin_readcyclecounter(); rph[k] += tn_ - rt; rt = tn_; } while (0)
+#else
+#define RD_STAMP(k)
+#endif
 	for (uint32_t f = blockIdx.x; f < nflag && f < (uint32_t)cap; f += gridDim.x) {
 		const uint32_t q = cflag[1 + f];
 		const int x = (int)(q % (uint32_t)W), trow = (int)(q / (uint32_t)W), y = y0 + trow;
@@ -2359,7 +2382,7 @@ void twoview_rescan_wave_kernel(const ViewDev *__restrict__ views, int ref, int 
 		// (1) label projections
 		if (walk) {
 			const SharedDivisor nd_sd = shared_divisor(nd);
-			for (int d = lane; d < P.num_depth_levels; d += 64) {
+			for (int d = tid; d < P.num_depth_levels; d += RD_THREADS) {
 				double x2, y2;
 				const bool ok = pinhole_project_label_sd(ray, nd_sd, tnum[d], Rv.cam, P.image_scale, x2, y2);
 				sx[d] = ok ? x2 : __builtin_nan("");              // (a projection is never NaN when it succeeds: t >= 1e-10, finite cameras;
@@ -2368,10 +2391,12 @@ void twoview_rescan_wave_kernel(const ViewDev *__restrict__ views, int ref, int 
 		}
 		// (2) mask bytes of row y of the other view over the pixel's column range
 		const int span = hi >= lo ? hi - lo + 1 : 0;
-		for (int k = lane; k < span && k < 4096; k += 64) smask[k] = (y >= 0 && y < OH) ? Rv.mask[(size_t)y*OW + lo + k] : 0;
+		for (int k = tid; k < span && k < 4096; k += RD_THREADS) smask[k] = (y >= 0 && y < OH) ? Rv.mask[(size_t)y*OW + lo + k] : 0;
 		__syncthreads();
-		// (3) the walk: candidate columns in visiting order
-		if (lane == 0) {
+		RD_STAMP(0);
+		double *crow = cost + ((size_t)trow*((W + DC_TP - 1)/DC_TP) + (x/DC_TP))*(size_t)cstride*DC_TP + (x % DC_TP);
+		if (tid == 0) {
+			// (3) the walk: candidate columns in visiting order
 			int n = 0;
 			bool over = false;
 			if (walk) {
@@ -2409,19 +2434,29 @@ void twoview_rescan_wave_kernel(const ViewDev *__restrict__ views, int ref, int 
 			}
 			if (over) { atomicAdd(&cnt->cert_overflow, 1ull); n = RSW_MAXC; }
 			s_n = n;
+		} else if (tid >= 64) {
+			// the pixel's columns in the reference's arithmetic (twoview_refill_kernel's loop, a lane per column)
+			const int SP = padded_stride(W);
+			const WindowAt wa = window_at<R>(wbuf, wimg, W, trow, x);
+			const double *lp = ref_tvp + (size_t)(y + SRH_PADY - R)*SP + (x + SRH_PADL - R);
+			for (int c = lo + (tid - 64); c <= hi; c += RD_THREADS - 64) {
+				const double *rp = oth_tvp + (size_t)(y + SRH_PADY - R)*SP + (c + SRH_PADL - R);
+				const double cv = window_exact_cost<R>(wa.wq, wa.wrow, wa.wcol, lp, rp, SP, SP, P);
+				crow[(size_t)(c - lo)*DC_TP] = cv;
+				if (c - lo < 4096) srow[c - lo] = cv;
+				++n_cols;
+			}
 		}
+		RD_STAMP(1);
 		__syncthreads();
-		const int n = s_n;
-		// (4) the candidates' costs
-		const double *crow = cost + ((size_t)trow*((W + DC_TP - 1)/DC_TP) + (x/DC_TP))*(size_t)cstride*DC_TP + (x % DC_TP);
-		for (int k = lane; k < n; k += 64) scost[k] = crow[(size_t)scol[k]*DC_TP];
-		__syncthreads();
+		RD_STAMP(2);
 		// (5) running minimum, ratio test, depth of the winner
-		if (lane == 0) {
+		if (tid == 0) {
+			const int n = s_n;
 			double minCost = __builtin_inf(), secondBest = __builtin_inf();
 			int wcol = -1, pcol = -1;
 			for (int k = 0; k < n; ++k) {
-				const double cv = scost[k];
+				const double cv = srow[scol[k]];
 				if (cv + P.wta_margin < minCost) { secondBest = minCost; minCost = cv; if (WTA) pcol = wcol; wcol = scol[k]; }   // twoviewstereo.cpp:293-301
 			}
 			double depth = __builtin_nan("");
@@ -2431,8 +2466,39 @@ void twoview_rescan_wave_kernel(const ViewDev *__restrict__ views, int ref, int 
 			if (WTA) wta_store(wout, (size_t)W*L.h, (size_t)y*W + x, wcol >= 0 ? lo + wcol : -1, wcol >= 0 ? y : -1,
 			                   pcol >= 0 ? lo + pcol : -1, pcol >= 0 ? y : -1);
 		}
-		__syncthreads();
+		__syncthreads();                                              // (the LDS arrays are reused)
+		RD_STAMP(3);
+#ifdef SRH_PROFILE_PHASES
+		++rph[4];
+#endif
 	}
+#ifdef SRH_PROFILE_PHASES
+	if (tid == 0) for (int k = 0; k < 5; ++k) atomicAdd(&cnt->dbg_redo[k], rph[k]);
+	if (tid == 64) atomicAdd(&cnt->dbg_redo[5], rph[1]);
+#endif
+#undef RD_STAMP
+	block_count_add(&cnt->n_eval_device, n_cols);
+}
+
+// both jobs of the certified redo on the listed pixels where the kernel is eligible (radius 5 or 2, labels <= RSW_MAXD,
+// cstride <= 4096); false: the caller launches the pair refill + one-lane scan
+bool twoview_redo_takes(const srh_params &P, int cstride) {
+	return P.num_depth_levels <= RSW_MAXD && cstride <= 4096 && (P.window_radius == 5 || P.window_radius == 2);
+}
+
+bool launch_twoview_redo(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P, int y0,
+                         const double *tnum, const double *wbuf, bool wimg, const double *ref_tvp, const double *oth_tvp,
+                         double *cost, int cstride, const PixRange *prange, const uint32_t *cflag, int cap, Counters *cnt, int32_t *wout)
+{
+	if (!twoview_redo_takes(P, cstride)) return false;
+	if (cap <= 0) return true;
+	const dim3 grid((unsigned)(cap < RD_GRID ? cap : RD_GRID)), block(RD_THREADS);
+#define SRH_REDO(R_, W_) hipLaunchKernelGGL((twoview_redo_kernel<R_, W_>), grid, block, 0, st, views, ref, oth, P, y0, tnum, wbuf, wimg ? 1 : 0, \
+                                            ref_tvp, oth_tvp, cost, cstride, prange, cflag, cap, cnt, wout)
+	if (P.window_radius == 5) { if (wout) SRH_REDO(5, true); else SRH_REDO(5, false); }
+	else                      { if (wout) SRH_REDO(2, true); else SRH_REDO(2, false); }
+#undef SRH_REDO
+	return true;
 }
 
 // cflag == nullptr: the exact scan.  cflag, nlist < 0: the certified scan (flags into cflag).  cflag, nlist >= 0: the
@@ -2471,14 +2537,8 @@ void launch_twoview_scan(hipStream_t st, const ViewDev *views, int ref, int oth,
 		if (tp) { if (wout) SRH_TSCAN(true, true, cflag, pexact); else SRH_TSCAN(true, false, cflag, pexact); }
 		if (wout) SRH_SCAN(true, false, true, wgrid, cflag, 0, pexact, tilelist);
 		else      SRH_SCAN(true, false, false, wgrid, cflag, 0, pexact, tilelist);
-	} else if (nlist > 0 && P.num_depth_levels <= RSW_MAXD && cstride <= 4096) {
-		// (the list may hold up to the band's pixels: workgroups share it in a grid-stride loop, the count is read on the device)
-		const dim3 rgrid((unsigned)(nlist < 2048 ? nlist : 2048));
-		if (wout) hipLaunchKernelGGL(twoview_rescan_wave_kernel<true>, rgrid, dim3(64), 0, st,
-		                             views, ref, oth, P, y0, tnum, cost, cstride, prange, cflag, nlist, cnt, wout);
-		else      hipLaunchKernelGGL(twoview_rescan_wave_kernel<false>, rgrid, dim3(64), 0, st,
-		                             views, ref, oth, P, y0, tnum, cost, cstride, prange, cflag, nlist, cnt, wout);
 	} else if (nlist > 0) {
+		// (the one-lane form: what launch_twoview_redo does not take)
 		const unsigned lgrid = (unsigned)((nlist + SC_TW - 1)/SC_TW);
 		if (wout) SRH_SCAN(false, true, true, lgrid, cflag, nlist, nullptr, nullptr);
 		else      SRH_SCAN(false, true, false, lgrid, cflag, nlist, nullptr, nullptr);

@@ -200,6 +200,7 @@ struct Counters {
 	unsigned long long dbg_cycles, dbg_blocks, dbg_total_cycles, dbg_waves;   // SRH_DENSE_DBG=2 instrumentation
 	unsigned long long dbg_phase[8];
 	unsigned long long dbg_wave[64];      // diagnostic build: phase k of wave w of a workgroup at [8*k + w]
+	unsigned long long dbg_redo[6];       // diagnostic build: twoview_redo_kernel's phase clocks (srh_dense.hip)
 };
 
 // Neighbour views of one MultiViewStereo estimate, passed to the kernels by value
@@ -279,9 +280,16 @@ void launch_scan_template(hipStream_t st, const ViewDev *views, int ref, int oth
 // a count above cap is reported in Counters::cert_overflow); wimg: LDS-image windows, else tile-major
 bool launch_twoview_refill(hipStream_t st, int width, const srh_params &P, int y0, const PixRange *prange, const uint32_t *cflag, int cap,
                            const double *wbuf, bool wimg, const double *ref_tvp, const double *oth_tvp, double *cost, int cstride, Counters *cnt);
-// columns the cost kernel leaves out (dense_cover_hi with `lanes` block lanes per pixel), filled in before the scan
+// refill + exact rescan of the flagged pixels in one kernel (twoview_redo_kernel: the columns beside the walk), a fixed grid of
+// 512 workgroups (RD_GRID) over the list; false (nothing launched): not eligible, the caller launches the pair
+bool twoview_redo_takes(const srh_params &P, int cstride);
+bool launch_twoview_redo(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P, int y0,
+                         const double *tnum, const double *wbuf, bool wimg, const double *ref_tvp, const double *oth_tvp,
+                         double *cost, int cstride, const PixRange *prange, const uint32_t *cflag, int cap, Counters *cnt, int32_t *wout);
+// columns the cost kernel leaves out (dense_cover_hi with `lanes` block lanes per pixel), filled in before the scan:
+// a fixed small grid over filllist = [count | band pixel indices], pixel_range_kernel's list for the same form
 void launch_twoview_lazy_fill(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P,
-                              int y0, int nrows, const PixRange *prange, const double *wbuf, size_t wstride,
+                              int y0, int nrows, const PixRange *prange, const uint32_t *filllist, const double *wbuf, size_t wstride,
                               const double *ref_tvp, const double *oth_tvp,      // NaN-bordered planes (radius 5 / 2), else null
                               bool wimg,                                         // LDS-image windows (strip path), else tile-major
                               int lanes, bool padded,                            // the cost kernel's form: block lanes per pixel, blocks on even columns
@@ -291,7 +299,9 @@ void launch_twoview_lazy_fill(hipStream_t st, const ViewDev *views, int ref, int
 void launch_padded_plane(hipStream_t st, const double *gray_tv, int w, int h, double *out);
 void launch_padded_full(hipStream_t st, const double *gray_tv, int w, int h, int R, uint8_t *out);
 void launch_pixel_range(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P,
-                        int y0, int nrows, const double *tnum, int cstride, PixRange *prange);
+                        int y0, int nrows, const double *tnum, int cstride, PixRange *prange,
+                        int lanes = 8, bool padded = true,     // the cost kernel's form, as launch_twoview_lazy_fill gets it
+                        uint32_t *filllist = nullptr);         // [count (cleared by the caller) | pixels with left-out columns]; null: no list
 int  strip_chunk_columns();
 int  strip_block_lanes(int cstride, int form);
 bool launch_twoview_strip_cost(hipStream_t st, const ViewDev *views, int ref, int oth, int width, int height,

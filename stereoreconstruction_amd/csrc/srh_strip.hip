@@ -87,29 +87,45 @@ void launch_padded_full(hipStream_t st, const double *gray_tv, int w, int h, int
 // ------------------------------------------------------------------ candidate ranges
 // The column range of every reference pixel of the band (pinhole_column_range, srh_walk.hpp), once, with every lane
 // busy: twoview_dense_cost_kernel works it out on one lane in eight per tile, twoview_scan_kernel again per pixel.
+// filllist (null: none is kept) = [count | band-relative indices] of the pixels whose last columns the cost kernel of the
+// form (ncb, lanes, pad) leaves out (dense_cover_hi): what the fill kernels of srh_dense.hip evaluate.  The caller clears
+// the count; a wave appends its pixels with one atomic, so the list's order differs from run to run.
 __global__ void pixel_range_kernel(const ViewDev *__restrict__ views, int ref, int oth, srh_params P, int y0, int nrows,
-                                   const double *__restrict__ tnum, int cstride, PixRange *__restrict__ prange)
+                                   const double *__restrict__ tnum, int cstride, PixRange *__restrict__ prange,
+                                   int ncb, int lanes, int pad, uint32_t *__restrict__ filllist)
 {
 	const ViewDev &L = views[ref];
 	const int W = L.w;
 	const size_t q = (size_t)blockIdx.x*blockDim.x + threadIdx.x;
-	if (q >= (size_t)nrows*W) return;
-	const int x = (int)(q % W), y = y0 + (int)(q / W);
+	const bool in = q < (size_t)nrows*W;
 	int lo = 0, hi = -1;
-	if (L.mask[(size_t)y*W + x] == 1) {
-		const Ray ray = cam_unproject(L.cam, (x + 0.5) / P.image_scale, (y + 0.5) / P.image_scale);
-		pinhole_column_range(ray, L.cam, views[oth], P, tnum, cstride, lo, hi);
+	if (in) {
+		const int x = (int)(q % W), y = y0 + (int)(q / W);
+		if (L.mask[(size_t)y*W + x] == 1) {
+			const Ray ray = cam_unproject(L.cam, (x + 0.5) / P.image_scale, (y + 0.5) / P.image_scale);
+			pinhole_column_range(ray, L.cam, views[oth], P, tnum, cstride, lo, hi);
+		}
+		PixRange r; r.lo = lo; r.hi = hi;
+		prange[q] = r;
 	}
-	PixRange r; r.lo = lo; r.hi = hi;
-	prange[q] = r;
+	if (!filllist) return;
+	const bool left = in && hi >= lo && dense_cover_hi(lo, hi, ncb, lanes, pad != 0) < hi;
+	const unsigned long long m = __ballot(left);
+	if (m == 0) return;
+	const int lane = (int)(threadIdx.x & 63), leader = __ffsll((long long)m) - 1;
+	unsigned base = 0;
+	if (lane == leader) base = atomicAdd(&filllist[0], (unsigned)__popcll(m));
+	base = (unsigned)__shfl((int)base, leader);
+	if (left) filllist[1 + base + (unsigned)__popcll(m & ((1ull << lane) - 1ull))] = (uint32_t)q;
 }
 
 void launch_pixel_range(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P,
-                        int y0, int nrows, const double *tnum, int cstride, PixRange *prange)
+                        int y0, int nrows, const double *tnum, int cstride, PixRange *prange,
+                        int lanes, bool padded, uint32_t *filllist)
 {
 	const size_t n = (size_t)nrows*width;
 	hipLaunchKernelGGL(pixel_range_kernel, dim3((unsigned)((n + 255)/256)), dim3(256), 0, st,
-	                   views, ref, oth, P, y0, nrows, tnum, cstride, prange);
+	                   views, ref, oth, P, y0, nrows, tnum, cstride, prange, 8, lanes, padded ? 1 : 0, filllist);
 }
 
 int strip_chunk_columns() { return ST_CHUNK; }
