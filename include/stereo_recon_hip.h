@@ -369,7 +369,9 @@ int  srh_twoview_wta(srh_context *ctx, int ref_slot, int oth_slot, const srh_par
  * filtered left map; in place on the two slots' depth maps. */
 /* DIAGNOSTIC (evidence for the certified arithmetic, tests/test_gpu_cert_rows.py): the cost rows of reference rows
  * [y0, y1) on the row-aligned dense plan as the cost kernel leaves them -- what the scan looks up.  form: 0 = the
- * reference's arithmetic, 3 = two fused sweeps, 5 = one-pass (the certified forms), 1 = fused unchecked; raw != 0: the
+ * reference's arithmetic, 3 = two fused sweeps, 5 = one-pass (the certified forms), 1 = fused unchecked, 2 = the
+ * single-precision kernel ("arith" = 2) in the form option "f32_form" selects: always the per-tile kernel
+ * (*used_strip_kernel = 0 whatever "strip" says), raw is ignored (tests/test_gpu_f32_rows.py); raw != 0: the
  * certified forms WITHOUT their in-kernel exact redo (an uncertified candidate is NaN).  Layout of cost_out (doubles):
  * [row][tile of 32 pixels][k = column - range.lo, < *cstride_out][pixel of the tile]; an entry the kernels never wrote
  * reads as a NaN with all bits set.  range_out: (lo, hi) per pixel, hi < lo = no candidates.  cost_out == NULL: only

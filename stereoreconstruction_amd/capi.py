@@ -691,7 +691,9 @@ class Context:
     # -- MultiViewStereo
     def twoview_cost_rows(self, ref, oth, p, y0, y1, form, raw=False):
         """srh_twoview_cost_rows (diagnostic) -> (cost (rows, w, cstride) float64 with cost[r, x, k] the cost of column
-        lo + k, range (rows, w, 2) int32, used_strip_kernel).  Under set_option("cost", COST_SAD) the rows are cost_sad's and
+        lo + k, range (rows, w, 2) int32, used_strip_kernel).  form: 0 the reference's arithmetic, 3 / 5 the certified
+        forms, 1 fused unchecked, 2 the single-precision kernel in the form of option "f32_form" (per tile:
+        used_strip_kernel is False; raw is ignored).  Under set_option("cost", COST_SAD) the rows are cost_sad's and
         need set_option("sad_dense", 1) and form 0 (anything else raises); an entry no kernel wrote is a NaN with all bits set."""
         w, h = self.view_size(ref)
         cs, us = C.c_int(0), C.c_int(0)

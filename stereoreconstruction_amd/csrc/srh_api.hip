@@ -2224,14 +2224,15 @@ extern "C" int srh_twoview_wta(srh_context *c, int ref, int oth, const srh_param
 
 // Diagnostic (tests/test_gpu_cert_rows.py): the cost rows of rows [y0, y1) on the row-aligned dense plan, straight from the
 // cost kernel -- what the scan would look up.  form: 0 the reference's arithmetic, 3 two fused sweeps, 5 one-pass (the
-// certified forms); raw != 0: without the in-kernel exact redo (uncertified candidates are NaN).  The plan and the
+// certified forms), 1 fused unchecked, 2 the single-precision kernel (srh_dense_f32.hip, option f32_form; per tile whatever
+// option strip says); raw != 0: without the in-kernel exact redo (uncertified candidates are NaN).  The plan and the
 // preparation are the pass's (tv_plan, tv_dense_prepare); the rows have to fit one band, whose cost pass runs alone.
 extern "C" int srh_twoview_cost_rows(srh_context *c, int ref, int oth, const srh_params *p, int y0, int y1, int form, int raw,
                                      double *cost_out, size_t cost_doubles, int32_t *range_out, int *cstride_out, int *used_strip)
 {
 	int rc;
 	if ((rc = check_slot(c, ref, true)) || (rc = check_slot(c, oth, true)) || (rc = check_params(p))) return rc;
-	if (form != 0 && form != 3 && form != 5 && form != 1) return fail(SRH_E_INVALID, "form must be 0, 1, 3 or 5");
+	if (form != 0 && form != 3 && form != 5 && form != 1 && form != 2) return fail(SRH_E_INVALID, "form must be 0, 1, 2, 3 or 5");
 	if ((form == 3 || form == 5) && !cert_bound(*p).ok) return fail(SRH_E_UNSUPPORTED, "the parameters leave the error bound no room");
 	const bool sad = c->cost_kind == SRH_COST_SAD;
 	if (sad && !c->sad_dense) return fail(SRH_E_UNSUPPORTED, "cost rows of cost_sad exist on the dense plan only (option sad_dense)");
@@ -2248,6 +2249,7 @@ extern "C" int srh_twoview_cost_rows(srh_context *c, int ref, int oth, const srh
 	D.cstride = plan.cstride;
 	D.strip = (sad || c->strip != 0) && plan.cstride + SRH_WTILE <= strip_chunk_columns();
 	D.cert = form != 0 && !sad && cert_bound(*p).ok != 0;
+	if (form == 2) D.strip = D.cert = false;                      // (the f32 kernel is a per-tile kernel, as in the pass under arith = 2)
 	if ((rc = P.dense_prepare(D))) return rc;
 	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
 	const int nr = std::min((int)D.rows, P.y1 - P.y0);

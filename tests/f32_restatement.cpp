@@ -1,0 +1,287 @@
+// f32_restatement.cpp -- CPU restatement of the single-precision cost kernel of the row-aligned dense TwoView plan
+// (stereoreconstruction_amd/csrc/srh_dense_f32.hip, option "arith" = 2, both "f32_form"s), operation by operation in the
+// kernel's order: float, fmaf, / and sqrtf.  The library is built without contraction, its float division and square root
+// are correctly rounded and denormals are kept, so this program is the kernel's image to the bit wherever its inputs --
+// doubles the device and the oracle agree on to a few units in the last place -- round to the same floats (`stable`).
+// Beside every fast-form value: the same cost in double (sro_twoview_cost_ncc) and a first-order forward error bound B of
+// the float evaluation against it, derived below and evaluated in double.  Nothing in it is fitted to the kernel's output.
+// Built with g++ -O1 -ffp-contract=off at test time (tests/f32_ref.py), linked to the oracle (sro_weights, sro_to_gray,
+// sro_twoview_cost_ncc).  tests/test_f32_restatement_host.py pins it on the CPU, tests/test_gpu_f32_rows.py holds the
+// kernel's cost rows against it.
+#include <cmath>
+#include <cstdint>
+#include <cstdlib>
+#include <vector>
+
+extern "C" {
+#include "sr_oracle.h"
+}
+
+namespace {
+
+const double U24 = 1.0/16777216.0;          // u = 2^-24, the unit roundoff of float
+
+// gray of a TwoView tap, NaN where cost_ncc skips it on that side: outside the image, in the last row or column
+// (sample() is invalid there), or masked out.  toGray sums 0.11 r + 0.59 g + 0.3 b left to right (sro_to_gray).
+void gray_plane(const sro_image *img, std::vector<double> &g) {
+	g.resize((size_t)img->w*img->h);
+	for (int y = 0; y < img->h; ++y)
+		for (int x = 0; x < img->w; ++x) {
+			const size_t i = (size_t)y*img->w + x;
+			const uint8_t *px = img->rgba + 4*i;
+			const bool ok = (!img->mask || img->mask[i] == 1) && x + 1 < img->w && y + 1 < img->h;
+			g[i] = ok ? sro_to_gray((double)px[0], (double)px[1], (double)px[2]) : NAN;
+		}
+}
+
+double tap(const std::vector<double> &g, int w, int h, int x, int y) {
+	return (x < 0 || y < 0 || x >= w || y >= h) ? NAN : g[(size_t)y*w + x];
+}
+
+// the pixel constants of the fast form, in double, taps row-major (weights_kernel of srh_kernels.hip; the windows
+// kernels of srh_dense.hip sum the same terms in other orders: `stable` allows for that)
+struct PixConst { double mL, tw, s2, SA; bool all; };
+
+PixConst pix_const(const double *w, const double *l, int T, double cutoff) {
+	PixConst c = { 0, 0, 0, 0, true };
+	for (int t = 0; t < T; ++t) {
+		if (!(l[t] == l[t] && w[t] > cutoff)) c.all = false;
+		c.mL += w[t]*l[t];
+		c.tw += w[t];
+	}
+	if (c.all && !(c.tw < 1e-10)) {
+		c.mL /= c.tw;
+		for (int t = 0; t < T; ++t) {
+			const double d = w[t]*l[t] - c.mL;
+			c.s2 += d*d;
+			c.SA += fma(w[t], l[t], -c.mL);
+		}
+	} else c.all = false;
+	return c;
+}
+
+// what the kernel stores: v below the clamp as it is, anything else -- a NaN included -- the clamp
+double store(float v, double max_color_diff) {
+	return (v < (float)max_color_diff) ? (double)v : max_color_diff;
+}
+
+// the fast form: every tap usable on both sides.  form 0: the reference's two sweeps; form 1: one pass
+double fast_f32(int form, const double *w, const double *l, const double *r, int T, const PixConst &c, double max_color_diff) {
+	const float mL = (float)c.mL, tw = (float)c.tw, s2 = (float)c.s2;
+	float q1, q3;
+	if (form == 1) {
+		const float SA = (float)c.SA, itw = 1.0f/tw;
+		float P = 0.f, Q = 0.f, Uu = 0.f;
+		for (int t = 0; t < T; ++t) {
+			const float wf = (float)w[t], lf = (float)l[t], rf = (float)r[t];
+			const float q = rf*rf;
+			const float a = fmaf(wf, lf, -mL);
+			const float cc = a*wf, d = wf*wf;
+			P = fmaf(wf, rf, P);
+			Q = fmaf(cc, rf, Q);
+			Uu = fmaf(d, q, Uu);
+		}
+		const float m = P*itw;
+		q3 = fmaf(-m, fmaf(-(float)T, m, P + P), Uu);
+		q1 = fmaf(-m, SA, Q);
+	} else {
+		float acc = 0.f;
+		for (int t = 0; t < T; ++t) acc = fmaf((float)w[t], (float)r[t], acc);
+		const float mR = -(acc/tw);
+		float s1 = 0.f, s3 = 0.f;
+		for (int t = 0; t < T; ++t) {
+			const float wf = (float)w[t], lf = (float)l[t], rf = (float)r[t];
+			const float a = fmaf(wf, lf, -mL);
+			const float b = fmaf(wf, rf, mR);
+			s1 = fmaf(a, b, s1);
+			s3 = fmaf(b, b, s3);
+		}
+		q1 = s1; q3 = s3;
+	}
+	const float v = 255.0f*(1.0f - fabsf(q1)/sqrtf(s2*q3));
+	return store(v, max_color_diff);
+}
+
+// First-order forward error bound of fast_f32 against the same cost in double, u = 2^-24.
+// Inputs: each of w, l, r, mL, tw, s2, SA is rounded to float once (relative error u); a chain of T fmaf adds
+// T u sum|term|.  With a_t = w l - mL, b_t = w r - mR (exact, in double):
+//   alpha_t = u (|a_t| + 2 w l + |mL|)                      the computed a_t: one rounding, two inputs, mL
+//   two sweeps:  |d mR| <= (T + 4) u mR                     chain, two inputs per term, tw, the division
+//                beta_t = u (|b_t| + 2 w r + (T + 4) mR)
+//                |d s1| <= sum(|a_t| beta_t + |b_t| alpha_t) + T u sum|a_t b_t|
+//                |d s3| <= 2 sum|b_t| beta_t + T u s3
+//   one pass:    P = sum w r, Q = sum (a_t w) r, U = sum w^2 r^2, m = P / tw, s3 = U - m (2P - T m), s1 = Q - m SA;
+//                every term of a difference enters with its own magnitude:
+//                |d P| <= (T + 2) u P        |d U| <= (T + 6) u U        |d m| <= (T + 5) u m
+//                |d c_t| <= w alpha_t + 2 u |c_t|   (c_t = a_t w: a_t, the input w, the product)
+//                |d Q| <= sum(w r alpha_t + 3 u |c_t| r) + T u sum|c_t| r
+//                i = 2P - T m:  |d i| <= 2 |d P| + T |d m| + u |i|
+//                |d s3| <= |d U| + |d m| |i| + m |d i| + u |s3|
+//                |d s1| <= |d Q| + |d m| |SA| + m u |SA| + u |s1|
+//   finish, rho = |s1| / sqrt(s2 s3):  s2, the product, the root, the quotient: 4 u rho; 1 - x and 255 x: 2 u each at most
+//                B = 255 [ |d s1| / sqrt(s2 s3) + rho (|d s3| / (2 s3) + 4 u) ] + 510 u
+// Second-order terms are dropped: the tests allow 2 B.  Where |d s3| > s3 / 4 the expansion of 1/sqrt(s3) does not
+// hold and there is no bound (*left_out); nor is there one for a flat window (s2 or s3 zero).
+double fast_bound(int form, const double *w, const double *l, const double *r, int T, const PixConst &c, bool *left_out) {
+	const double u = U24;
+	double P = 0;
+	for (int t = 0; t < T; ++t) P += w[t]*r[t];
+	const double mR = P/c.tw;
+	double s1 = 0, s3 = 0, ds1 = 0, ds3 = 0;
+	if (form == 0) {
+		double sab = 0;
+		for (int t = 0; t < T; ++t) {
+			const double a = w[t]*l[t] - c.mL, b = w[t]*r[t] - mR;
+			const double alpha = u*(fabs(a) + 2*w[t]*l[t] + fabs(c.mL));
+			const double beta = u*(fabs(b) + 2*w[t]*r[t] + (T + 4)*mR);
+			s1 += a*b; s3 += b*b; sab += fabs(a*b);
+			ds1 += fabs(a)*beta + fabs(b)*alpha;
+			ds3 += 2*fabs(b)*beta;
+		}
+		ds1 += T*u*sab;
+		ds3 += T*u*s3;
+	} else {
+		double Uu = 0, dQ = 0, scr = 0;
+		for (int t = 0; t < T; ++t) {
+			const double a = w[t]*l[t] - c.mL, b = w[t]*r[t] - mR;
+			const double alpha = u*(fabs(a) + 2*w[t]*l[t] + fabs(c.mL));
+			const double ct = fabs(a*w[t]);
+			s1 += a*b; s3 += b*b;
+			Uu += w[t]*w[t]*r[t]*r[t];
+			dQ += w[t]*r[t]*alpha + 3*u*ct*r[t];
+			scr += ct*r[t];
+		}
+		dQ += T*u*scr;
+		const double dP = (T + 2)*u*P, dU = (T + 6)*u*Uu, m = mR, dm = (T + 5)*u*m;
+		const double i = 2*P - T*m, di = 2*dP + T*dm + u*fabs(i);
+		ds3 = dU + dm*fabs(i) + m*di + u*fabs(s3);
+		ds1 = dQ + dm*fabs(c.SA) + m*u*fabs(c.SA) + u*fabs(s1);
+	}
+	*left_out = !(ds3 <= s3/4) || !(s3 > 0) || !(c.s2 > 0);      // (a flat window on either side: rho is 0/0)
+	const double den = sqrt(c.s2*s3), rho = fabs(s1)/den;
+	return 255*(ds1/den + rho*(0.5*ds3/s3 + 4*u)) + 510*u;
+}
+
+// dense_cost_general_f32: any validity pattern, the select form in double on the values rounded to float
+double general_f32(const double *w, const double *l, const double *r, int T, double weight_cutoff, double bad_ret, double max_color_diff) {
+	double meanL = 0, meanR = 0, totalWeight = 0.0;
+	for (int t = 0; t < T; ++t) {
+		const double gl = (float)l[t], gr = (float)r[t], wt = (float)w[t];
+		const bool ok = gl == gl && gr == gr && wt > weight_cutoff;
+		meanL += ok ? wt*gl : 0.0;
+		meanR += ok ? wt*gr : 0.0;
+		totalWeight += ok ? wt : 0.0;
+	}
+	if (totalWeight < 1e-10) return bad_ret;
+	meanL /= totalWeight;
+	meanR /= totalWeight;
+	double sum1 = 0, sum2 = 0, sum3 = 0;
+	for (int t = 0; t < T; ++t) {
+		const double gl = (float)l[t], gr = (float)r[t], wt = (float)w[t];
+		const bool ok = gl == gl && gr == gr && wt > weight_cutoff;
+		const double a = wt*gl - meanL, b = wt*gr - meanR;
+		sum1 += ok ? a*b : 0.0;
+		sum2 += ok ? a*a : 0.0;
+		sum3 += ok ? b*b : 0.0;
+	}
+	const double v = 255*(1.0 - fabs(sum1) / sqrt(sum2 * sum3));
+	return (v < max_color_diff) ? v : max_color_diff;
+}
+
+// rounding to float gives one float over the whole of [v - d, v + d]
+bool one_float(double lo, double hi) { return (float)lo == (float)hi; }
+
+bool stable_rel(double v, double rel) { return one_float(v - fabs(v)*rel, v + fabs(v)*rel); }
+
+bool stable_ulps(double v, int n) {
+	double lo = v, hi = v;
+	for (int k = 0; k < n; ++k) { lo = nextafter(lo, -INFINITY); hi = nextafter(hi, INFINITY); }
+	return one_float(lo, hi);
+}
+
+}  // namespace
+
+extern "C" {
+
+// One window given tap by tap (T = (2R+1)^2 values each, row-major; NaN in l or r = unusable): the path taken (1 fast,
+// 2 general), both forms' stored values and bounds.  The hand-built cases of the host test.
+int f32r_window(const double *w, const double *l, const double *r, int T, const sro_params *p,
+                double f32[2], double B[2], int left_out[2])
+{
+	const PixConst c = pix_const(w, l, T, p->weight_cutoff);
+	bool rfull = true;
+	for (int t = 0; t < T; ++t) rfull = rfull && r[t] == r[t];
+	if (c.all && rfull) {
+		for (int form = 0; form < 2; ++form) {
+			bool lo = false;
+			f32[form] = fast_f32(form, w, l, r, T, c, p->max_color_diff);
+			B[form] = fast_bound(form, w, l, r, T, c, &lo);
+			left_out[form] = lo ? 1 : 0;
+		}
+		return 1;
+	}
+	f32[0] = f32[1] = general_f32(w, l, r, T, p->weight_cutoff, p->bad_ret, p->max_color_diff);
+	B[0] = B[1] = NAN;
+	left_out[0] = left_out[1] = 0;
+	return 2;
+}
+
+// Rows [ya, yb) of a band that starts at row band_y0.  range: (lo, hi) per pixel of the band, hi < lo = none.  Entry
+// ((y - band_y0)*W + x)*cstride + (c - lo) of f32a / f32b (two sweeps / one pass), f64, Ba / Bb, path (0 not a column of
+// the range, 1 fast form, 2 general) and noB (bit 0 / 1: form 0 / 1 has no valid first-order bound); stable per pixel.
+void f32r_rows(const sro_image *ref, const sro_image *oth, const sro_params *p, int band_y0, int ya, int yb,
+               const int32_t *range, int cstride, double *f32a, double *f32b, double *f64, double *Ba, double *Bb,
+               uint8_t *path, uint8_t *noB, uint8_t *stable)
+{
+	const int W = ref->w, H = ref->h, OW = oth->w, OH = oth->h;
+	const int R = p->window_radius, WS = 2*R + 1, T = WS*WS;
+	std::vector<double> gl, gr;
+	gray_plane(ref, gl);
+	gray_plane(oth, gr);
+	std::vector<double> w((size_t)T), l((size_t)T), r((size_t)T);
+	for (int y = ya; y < yb; ++y)
+		for (int x = 0; x < W; ++x) {
+			const size_t pix = (size_t)(y - band_y0)*W + x;
+			const int lo = range[2*pix], hi = range[2*pix + 1];
+			stable[pix] = 1;
+			if (hi < lo) continue;
+			sro_weights(ref, x, y, p, w.data());
+			for (int row = 0; row < WS; ++row)
+				for (int col = 0; col < WS; ++col) l[(size_t)row*WS + col] = tap(gl, W, H, x - R + col, y - R + row);
+			const PixConst c = pix_const(w.data(), l.data(), T, p->weight_cutoff);
+			bool st = true;
+			for (int t = 0; t < T; ++t) st = st && stable_ulps(w[t], 8);
+			if (c.all) {
+				const double rel = 1.0/1099511627776.0;      // 2^-40
+				st = st && stable_rel(c.mL, rel) && stable_rel(c.tw, rel) && stable_rel(c.s2, rel) && stable_rel(c.SA, rel);
+			}
+			stable[pix] = st ? 1 : 0;
+			for (int col_ = lo; col_ <= hi && col_ - lo < cstride; ++col_) {
+				const size_t e = pix*cstride + (size_t)(col_ - lo);
+				bool rfull = true;
+				for (int row = 0; row < WS; ++row)
+					for (int col = 0; col < WS; ++col) {
+						const double v = tap(gr, OW, OH, col_ - R + col, y - R + row);
+						r[(size_t)row*WS + col] = v;
+						rfull = rfull && v == v;
+					}
+				f64[e] = sro_twoview_cost_ncc(ref, oth, w.data(), p, x, y, col_, y);
+				if (c.all && rfull) {
+					bool la = false, lb = false;
+					path[e] = 1;
+					f32a[e] = fast_f32(0, w.data(), l.data(), r.data(), T, c, p->max_color_diff);
+					f32b[e] = fast_f32(1, w.data(), l.data(), r.data(), T, c, p->max_color_diff);
+					Ba[e] = fast_bound(0, w.data(), l.data(), r.data(), T, c, &la);
+					Bb[e] = fast_bound(1, w.data(), l.data(), r.data(), T, c, &lb);
+					noB[e] = (uint8_t)((la ? 1 : 0) | (lb ? 2 : 0));
+				} else {
+					path[e] = 2;
+					f32a[e] = f32b[e] = general_f32(w.data(), l.data(), r.data(), T, p->weight_cutoff, p->bad_ret, p->max_color_diff);
+					Ba[e] = Bb[e] = NAN;
+					noB[e] = 0;
+				}
+			}
+		}
+}
+
+}  // extern "C"

@@ -59,7 +59,8 @@ def test_f32_mode_mismatch_rate(hip_ctx, W, H, D, wkind, seed, radius, form):
     """Mode 2: the cost loops in single precision (srh_dense_f32.hip; option f32_form 1: its one-pass sums, round 6).  Costs agree to ~6 digits; the winner changes
     where two candidates are that close or the ratio test sits on its threshold.  Measured here, bounded loosely: the
     point of the test is that the mode computes the same thing (same classes, same depths almost everywhere) -- a
-    wrong tile offset or a dropped block shows up as tens of percent."""
+    wrong tile offset or a dropped block shows up as tens of percent.  What the kernel stores is pinned entry by entry, to the
+    bit, in tests/test_gpu_f32_rows.py (against tests/f32_restatement.cpp); this test measures the winners that change."""
     p = _pair(hip_ctx, W, H, D, seed, wkind)
     p.window_radius = radius
     hip_ctx.set_option("arith", 0)

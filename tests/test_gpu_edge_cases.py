@@ -403,6 +403,7 @@ def test_twoview_compute_passes_side_by_side_or_one_after_the_other(hip_ctx):
         assert hip_ctx.stats()["band_retries"] > st0["band_retries"]
     finally:
         hip_ctx.set_option("debug_alloc_limit_mb", 0)
+        hip_ctx.set_option("band_budget_mb", 32768)               # (forgets the halvings: the context is shared with later tests)
     assert np.array_equal(_bits(want[0]), _bits(got2[0])) and np.array_equal(_bits(want[1]), _bits(got2[1]))
 
 

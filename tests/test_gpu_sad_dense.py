@@ -167,7 +167,7 @@ def test_cost_rows_value_by_value(hip_ctx, name):
         want = S.pair_costs_sad(imgs[ref], imgs[oth], op, xy)
         _assert_costs(got, want, "%s %d>%d cost rows against the restatement" % (name, ref, oth))
     with _options(hip_ctx, cost=capi.COST_SAD, sad_dense=1):
-        for form in (3, 5, 1):
+        for form in (3, 5, 1, 2):
             with pytest.raises(capi.StereoHipError):
                 hip_ctx.twoview_cost_rows(0, 1, p, 0, 4, form)
     with _options(hip_ctx, cost=capi.COST_SAD, sad_dense=0):
