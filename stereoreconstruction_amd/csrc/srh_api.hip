@@ -200,6 +200,33 @@ struct BandBuffers {
 	void free() { each([](auto &x) { x.free(); }); }
 };
 
+// What a context keeps of one label-volume stage (an optimiser over a per-pixel label volume: TRW-S or semi-global
+// aggregation, for MultiViewStereo's peak labels or TwoViewStereo's depth labels): the stage's scratch, for TwoViewStereo the
+// label cost volume it computes itself, and what the last finished one-view run left in them, w x h pixels by l labels
+// (K peaks or L depth levels), for the stage's *_dims and *_state.  w = 0: nothing to report.
+struct LabelStage {
+	const char *run_name, *last_name;       // "no finished <run_name> run", "the last <last_name> run was"
+	char letter;                            // what the messages call the label count
+	DevBuf<double> scratch, costs;
+	int w = 0, h = 0, l = 0;
+	bool own_costs = false;                 // the last run's data costs are in `costs`, not in a caller's volume
+	void forget() { w = h = l = 0; }
+	void forget_if(int vw, int vh) { if (w == vw && h == vh) forget(); }     // a view of that size got new pixels
+	void finished(int w_, int h_, int l_) { w = w_; h = h_; l = l_; }
+	void release() { scratch.release(); costs.release(); }
+	int dims(int *w_out, int *h_out, int *l_out) const {                     // the last run's size, where asked for
+		if (!w) return fail(SRH_E_INVALID, "no finished %s run on this context", run_name);
+		if (w_out) *w_out = w;
+		if (h_out) *h_out = h;
+		if (l_out) *l_out = l;
+		return SRH_OK;
+	}
+	int check_dims(int bw, int bh, int bl) const {                           // the caller's buffers are sized for it
+		if (!w || (bw == w && bh == h && bl == l)) return dims(nullptr, nullptr, nullptr);
+		return fail(SRH_E_INVALID, "buffers sized for %dx%d, %c = %d, the last %s run was %dx%d, %c = %d", bw, bh, letter, bl, last_name, w, h, letter, l);
+	}
+};
+
 // ------------------------------------------------------------------ context
 struct ViewHost {
 	int w = 0, h = 0;
@@ -273,22 +300,17 @@ struct srh_context {
 	DevBuf<Counters> d_cnt;
 	DevBuf<int> d_span;
 	BandBuffers band;
-	hipStream_t mrf_stream[SRH_MAX_VIEWS] = { nullptr };            // one stream per view of srh_mvs_mrf_estimate_views
+	hipStream_t mrf_stream[SRH_MAX_VIEWS] = { nullptr };            // one stream per view of srh_mvs_mrf_estimate_views / _sgm_
+	hipEvent_t views_go = nullptr;                                  //   which start behind this event on the context's stream
 	void *mrf_host = nullptr;                                       // pinned: per view {energy, pad, status[4]}
 	DevBuf<double> mrf_peaks;                           // top-K peaks of srh_mvs_initial_estimate_mrf
-	DevBuf<double> mrf;                                 // MRF stage scratch (srh_mrf.hip); mrf_w/h/k: what the last run left in it
-	int mrf_w = 0, mrf_h = 0, mrf_k = 0;
-	DevBuf<double> mvsgm;                               // MultiViewStereo semi-global aggregation scratch (srh_mvs_sgm.hip): depths, data costs, sums, labels
-	int mvsgm_w = 0, mvsgm_h = 0, mvsgm_k = 0;          // what the last single-view run left in it
-	double *mvsgm_host = nullptr;                       // pinned: one energy per view of srh_mvs_sgm_estimate_views
-	DevBuf<double> tvmrf;                               // TwoViewStereo MRF stage scratch (srh_twoview_mrf.hip): messages, granules, labels
-	DevBuf<double> tvmrf_costs;                         //   and the label cost volume of srh_twoview_mrf
-	int tvmrf_w = 0, tvmrf_h = 0, tvmrf_l = 0;          // what the last single-direction run left in them
-	bool tvmrf_own_costs = false;                       //   (its data costs are in tvmrf_costs, not in a caller's volume)
-	DevBuf<double> tvsgm;                               // TwoViewStereo semi-global aggregation (srh_twoview_sgm.hip): sums, labels
-	DevBuf<double> tvsgm_costs;                         //   and the label cost volume of srh_twoview_sgm
-	int tvsgm_w = 0, tvsgm_h = 0, tvsgm_l = 0;          // what the last single-direction run left in them
-	bool tvsgm_own_costs = false;
+	double *mvsgm_host = nullptr;                       // pinned: one energy per view of the MultiView aggregation
+	// the label-volume stages (LabelStage above): the scratch of each is carved by its kernel file's layout
+	LabelStage mrf   { "single-view MRF", "MRF", 'K' };             // MultiViewStereo TRW-S (srh_mrf.hip)
+	LabelStage mvsgm { "single-view SGM", "SGM", 'K' };             // MultiViewStereo semi-global aggregation (srh_mvs_sgm.hip)
+	LabelStage tvmrf { "TwoView MRF", "TwoView MRF", 'L' };         // TwoViewStereo TRW-S (srh_twoview_mrf.hip)
+	LabelStage tvsgm { "TwoView SGM", "TwoView SGM", 'L' };         // TwoViewStereo semi-global aggregation (srh_twoview_sgm.hip)
+	LabelStage *const label_stages[4] = { &mrf, &mvsgm, &tvmrf, &tvsgm };
 	int geodma = 1;                                     // option "geodma": 1 = the dense path's r = 5 geodesic windows by the persistent LDS-DMA kernel (default), 0 = geodesic_reg_kernel
 	int tscan_bound = 1;                                // option "tscan_bound": 1 = the template scan settles a pixel by ONE bound for all its labels (default), 0 = label by label
 	int tscan = 1;                                      // option "tscan": 1 = template scan on the dense path (default), 0 = every tile through twoview_scan_kernel
@@ -392,7 +414,7 @@ static int drain_profile(srh_context *c) {
 // bracket one kernel launch with events when profiling
 struct Scope {
 	srh_context *c; PendingEvt p; bool on;
-	Scope(srh_context *c_, const char *name) : c(c_), on(c_->profiling) {
+	Scope(srh_context *c_, const char *name, bool wanted = true) : c(c_), on(c_->profiling && wanted) {
 		if (on) {
 			p.name = name;
 			hipEventCreate(&p.a); hipEventCreate(&p.b);
@@ -785,11 +807,11 @@ extern "C" void srh_destroy(srh_context *c) {
 		if (T.done) hipEventDestroy(T.done);
 		T.d_cnt.release(); T.d_span.release(); T.band.release();
 	}
-	c->mrf.release(); c->mrf_peaks.release(); c->mvsgm.release();
-	c->tvmrf.release(); c->tvmrf_costs.release();
-	c->tvsgm.release(); c->tvsgm_costs.release();
+	c->mrf_peaks.release();
+	for (LabelStage *S : c->label_stages) S->release();
 	c->fuse_result.release(); c->fuse_scratch.release();
 	for (int i = 0; i < SRH_MAX_VIEWS; ++i) if (c->mrf_stream[i]) hipStreamDestroy(c->mrf_stream[i]);
+	if (c->views_go) hipEventDestroy(c->views_go);
 	if (c->mrf_host) hipHostFree(c->mrf_host);
 	if (c->mvsgm_host) hipHostFree(c->mvsgm_host);
 	if (c->comm) (void)rccl_comm_destroy(c->comm);
@@ -933,10 +955,7 @@ static int view_install(srh_context *c, int slot, int w, int h, const void *rgba
 	v.tvp_valid = false; v.fullp_r = 0; v.grayp_valid = false; v.fullsp_r = 0; v.geo5_valid = false; v.geo5_denied = false;
 	v.peaks_k = 0;                                              // the top-K peaks belonged to the previous image
 	v.wta_flags = 0; v.wta_oth = -1;                            // and so did the WTA by-products
-	if (c->mrf_w == w && c->mrf_h == h) c->mrf_w = c->mrf_h = c->mrf_k = 0;
-	if (c->mvsgm_w == w && c->mvsgm_h == h) c->mvsgm_w = c->mvsgm_h = c->mvsgm_k = 0;
-	if (c->tvmrf_w == w && c->tvmrf_h == h) c->tvmrf_w = c->tvmrf_h = c->tvmrf_l = 0;
-	if (c->tvsgm_w == w && c->tvsgm_h == h) c->tvsgm_w = c->tvsgm_h = c->tvsgm_l = 0;
+	for (LabelStage *S : c->label_stages) S->forget_if(w, h);   // and so may what a label stage reports
 	for (int j = 0; j < SRH_MAX_VIEWS; ++j) { v.list_mode[j] = 0; c->views[j].list_mode[slot] = 0; }   // new geometry
 	HIP_TRY(hipMemcpyAsync(v.rgba, rgba, n*4, kind, c->stream));
 	if (mask) HIP_TRY(hipMemcpyAsync(v.mask, mask, n, kind, c->stream));
@@ -3123,6 +3142,105 @@ extern "C" void srh_mrf_params_defaults(srh_mrf_params *m)
 	m->max_iters = 50; m->min_energy_drop = 5;                       // :631, :641
 }
 
+// The label-volume stages (LabelStage; the four sections from here on) check a run's device memory before anything is
+// queued: `n` doubles in each buffer.  What is missing must fit the free memory + the pool + the outgrown buffers (released
+// first); under option mem_limit_mb the whole need must fit the pretended device.  refuse(need, avail), in bytes, words the refusal.
+struct StageWant { DevBuf<double> *buf; size_t n; };
+template <class Refuse>
+static int stage_reserve(srh_context *c, const StageWant *wants, int nwants, Refuse refuse)
+{
+	size_t need = 0, missing = 0, held = 0;
+	for (int i = 0; i < nwants; ++i) {
+		need += wants[i].n*sizeof(double);
+		if (wants[i].buf->n < wants[i].n) { missing += wants[i].n*sizeof(double); held += wants[i].buf->bytes(); }
+	}
+	size_t free_b = 0, total_b = 0;
+	if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+		size_t avail = free_b + pool_bytes_on(c->device) + held;
+		size_t want = missing;
+		if (c->mem_limit) { want = need; if (avail > c->mem_limit) avail = c->mem_limit; }
+		if (want > avail) return refuse(need, avail);
+	} else (void)hipGetLastError();
+	for (int i = 0; i < nwants; ++i) if (const int rc = wants[i].buf->ensure(wants[i].n)) return rc;
+	return SRH_OK;
+}
+
+// One view's run of a MultiViewStereo optimiser: the K peaks of the w x h view in `slot`, on stream `st` in `scratch`: the
+// context's for a one-view entry point, a stream and a scratch per view (mvs_view_runs) for the views side by side
+struct MvsRun { int slot, w, h, K; hipStream_t st; DevBuf<double> *scratch; const double *peaks; };
+
+// The runs of the listed views: run i on c->mrf_stream[i], behind what the context's stream holds (the peaks were written
+// there), on the view's own scratch, which the caller reserves
+static int mvs_view_runs(srh_context *c, const int32_t *slots, int nviews, DevBuf<double> ViewHost::*scratch, std::vector<MvsRun> &runs)
+{
+	int rc;
+	for (int i = 0; i < nviews; ++i) {
+		if ((rc = check_slot(c, slots[i], true))) return rc;
+		if (c->views[slots[i]].peaks_k < 1) return fail(SRH_E_INVALID, "view slot %d has no peaks (srh_mvs_initial_estimate_peaks first)", slots[i]);
+		for (int j = 0; j < i; ++j) if (slots[j] == slots[i]) return fail(SRH_E_INVALID, "view slot %d listed twice", slots[i]);
+	}
+	HIP_TRY(hipSetDevice(c->device));
+	if (!c->views_go) HIP_TRY(hipEventCreateWithFlags(&c->views_go, hipEventDisableTiming));
+	HIP_TRY(hipEventRecord(c->views_go, c->stream));
+	for (int i = 0; i < nviews; ++i) {
+		ViewHost &v = c->views[slots[i]];
+		if (!c->mrf_stream[i]) HIP_TRY(hipStreamCreateWithFlags(&c->mrf_stream[i], hipStreamNonBlocking));
+		HIP_TRY(hipStreamWaitEvent(c->mrf_stream[i], c->views_go, 0));
+		runs.push_back(MvsRun{ slots[i], v.w, v.h, v.peaks_k, c->mrf_stream[i], &(v.*scratch), v.peaks });
+	}
+	return SRH_OK;
+}
+
+// TRW-S on every run (their scratch is reserved here, without a pre-check), each by the reference's stopping rule for itself (multiviewstereo.cpp:627-641): sweeps while the
+// energy drops by more than min_energy_drop, max_iters + 1 at the most.  A round queues the next step of every run still
+// sweeping -- the set-up in round 0, then a sweep; behind it the energy of the labelling it leaves and that number's way
+// to the host -- before it waits for the first, so runs side by side overlap.  `prof`: profile entries (the one-view form's).
+static int mvs_mrf_drive(srh_context *c, int n, const MvsRun *runs, const srh_mrf_params *m, srh_mrf_info *infos, bool prof)
+{
+	struct HostState { double energy, pad; unsigned status[4]; };
+	for (int i = 0; i < n; ++i) if (const int rc = runs[i].scratch->ensure(mrf_scratch_doubles(runs[i].w, runs[i].h))) return rc;
+	if (!c->mrf_host) HIP_TRY(hipHostMalloc(&c->mrf_host, sizeof(HostState)*SRH_MAX_VIEWS, hipHostMallocDefault));
+	HostState *hs = static_cast<HostState *>(c->mrf_host);
+	struct Live { MrfLayout lay; double e = 0, prev = 0, e0 = 0; int iters = 0, left = 0; bool active = true; };
+	std::vector<Live> live(n);
+	auto stop = [&](int code) { for (int i = 0; i < n; ++i) hipStreamSynchronize(runs[i].st); return code; };
+	auto failed = [&](int i) { return stop(fail(SRH_E_DEVICE, "MRF of view slot %d failed after %d sweep(s): %s", runs[i].slot, live[i].iters,
+	                                            hipGetErrorString(hipGetLastError()))); };
+	for (int nactive = n, round = 0; nactive > 0; ++round) {
+		if (round && cancelled(c)) return stop(fail(SRH_E_CANCELLED, "cancelled"));
+		for (int i = 0; i < n; ++i) {
+			const MvsRun &r = runs[i]; Live &l = live[i];
+			if (!l.active) continue;
+			hipError_t e;
+			if (round == 0) { Scope s(c, "mrf_data_kernel", prof); e = launch_mrf_setup(r.st, *r.scratch, r.w, r.h, r.K, m->beta, m->lambda, m->phi_u, r.peaks, l.lay); }
+			else            { Scope s(c, "mrf_pass_kernel", prof); e = launch_mrf_sweep(r.st, *r.scratch, r.w, r.h, r.K, m->psi_u, l.iters); }
+			if (e == hipSuccess) { Scope s(c, "mrf_energy_kernel", prof); e = launch_mrf_energy(r.st, *r.scratch, r.w, r.h, r.K, m->psi_u); }
+			if (e == hipSuccess) e = hipMemcpyAsync(&hs[i], l.lay.energy, sizeof(HostState), hipMemcpyDeviceToHost, r.st);
+			if (e != hipSuccess) return failed(i);
+		}
+		for (int i = 0; i < n; ++i) {
+			const MvsRun &r = runs[i]; Live &l = live[i];
+			if (!l.active) continue;
+			if (hipStreamSynchronize(r.st) != hipSuccess) return failed(i);
+			if (hs[i].status[0])
+				return stop(fail(SRH_E_DEVICE, "MRF sweep %u of view slot %d: band %u waited too long for the band above (hand-off never arrived)",
+				                 hs[i].status[2], r.slot, hs[i].status[1] - 1));
+			l.prev = l.e; l.e = hs[i].energy;
+			if (round == 0) { l.e0 = l.e; l.left = m->max_iters; continue; }
+			++l.iters;
+			if (l.prev - l.e > m->min_energy_drop && l.left-- > 0) continue;     // do { ... } while (prev - energy > 5 && numIters-- > 0)
+			l.active = false; --nactive;
+			Scope s(c, "mrf_depth_kernel", prof);
+			if (launch_mrf_depth(r.st, c->d_views, r.slot, *r.scratch, r.w, r.h, r.K) != hipSuccess) return failed(i);
+		}
+	}
+	for (int i = 0; i < n; ++i) {
+		if (hipStreamSynchronize(runs[i].st) != hipSuccess) return failed(i);
+		if (infos) { infos[i].iterations = live[i].iters; infos[i].energy_initial = live[i].e0; infos[i].energy_final = live[i].e; }
+	}
+	return SRH_OK;
+}
+
 extern "C" int srh_mvs_mrf_estimate(srh_context *c, int slot, int K, const void *peaks_dev, const srh_mrf_params *m, srh_mrf_info *info)
 {
 	int rc;
@@ -3131,41 +3249,10 @@ extern "C" int srh_mvs_mrf_estimate(srh_context *c, int slot, int K, const void 
 	if (K < 1 || K > 15) return fail(SRH_E_UNSUPPORTED, "top_k %d outside [1,15] (one lane per label, 16 lanes per pixel)", K);
 	HIP_TRY(hipSetDevice(c->device));
 	const ViewHost &v = c->views[slot];
-	const int w = v.w, h = v.h;
-	if ((rc = c->mrf.ensure(mrf_scratch_doubles(w, h)))) return rc;
-	c->mrf_w = c->mrf_h = c->mrf_k = 0;
-	MrfLayout lay;
-	{ Scope s(c, "mrf_data_kernel");
-	  HIP_TRY(launch_mrf_setup(c->stream, c->mrf, w, h, K, m->beta, m->lambda, m->phi_u, static_cast<const double *>(peaks_dev), lay)); }
-	struct { double energy, pad; unsigned status[4]; } hs;
-	auto energy = [&](double &e) -> int {
-		{ Scope s(c, "mrf_energy_kernel");
-		  HIP_TRY(launch_mrf_energy(c->stream, c->mrf, w, h, K, m->psi_u)); }
-		HIP_TRY(hipMemcpyAsync(&hs, lay.energy, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
-		HIP_TRY(hipStreamSynchronize(c->stream));
-		if (hs.status[0])
-			return fail(SRH_E_DEVICE, "MRF sweep %u: band %u waited too long for the band above (hand-off never arrived)", hs.status[2], hs.status[1] - 1);
-		e = hs.energy;
-		return SRH_OK;
-	};
-	// multiviewstereo.cpp:627-641
-	double e = 0.0, prev = 0.0;
-	if ((rc = energy(e))) return rc;
-	const double e0 = e;
-	int num_iters = m->max_iters, iters = 0;
-	do {
-		if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
-		prev = e;
-		{ Scope s(c, "mrf_pass_kernel");
-		  HIP_TRY(launch_mrf_sweep(c->stream, c->mrf, w, h, K, m->psi_u, iters)); }
-		if ((rc = energy(e))) return rc;
-		++iters;
-	} while (prev - e > m->min_energy_drop && num_iters-- > 0);
-	{ Scope s(c, "mrf_depth_kernel");
-	  HIP_TRY(launch_mrf_depth(c->stream, c->d_views, slot, c->mrf, w, h, K)); }
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	c->mrf_w = w; c->mrf_h = h; c->mrf_k = K;
-	if (info) { info->iterations = iters; info->energy_initial = e0; info->energy_final = e; }
+	c->mrf.forget();
+	const MvsRun run = { slot, v.w, v.h, K, c->stream, &c->mrf.scratch, static_cast<const double *>(peaks_dev) };
+	if ((rc = mvs_mrf_drive(c, 1, &run, m, info, true))) return rc;
+	c->mrf.finished(v.w, v.h, K);
 	return SRH_OK;
 }
 
@@ -3205,95 +3292,26 @@ extern "C" int srh_mvs_mrf_estimate_views(srh_context *c, const int32_t *slots, 
 	int rc;
 	if (!c) return fail(SRH_E_INVALID, "null context");
 	if (!slots || nviews < 1 || nviews > SRH_MAX_VIEWS || !m) return fail(SRH_E_INVALID, "bad view list / params");
-	for (int i = 0; i < nviews; ++i) {
-		if ((rc = check_slot(c, slots[i], true))) return rc;
-		if (c->views[slots[i]].peaks_k < 1) return fail(SRH_E_INVALID, "view slot %d has no peaks (srh_mvs_initial_estimate_peaks first)", slots[i]);
-		for (int j = 0; j < i; ++j) if (slots[j] == slots[i]) return fail(SRH_E_INVALID, "view slot %d listed twice", slots[i]);
-	}
-	HIP_TRY(hipSetDevice(c->device));
-	c->mrf_w = c->mrf_h = c->mrf_k = 0;                       // the per-view runs leave no state srh_mvs_mrf_state could report
-	struct HostState { double energy, pad; unsigned status[4]; };
-	if (!c->mrf_host) HIP_TRY(hipHostMalloc(&c->mrf_host, sizeof(HostState)*SRH_MAX_VIEWS, hipHostMallocDefault));
-	HostState *hs = static_cast<HostState *>(c->mrf_host);
-	hipEvent_t ev = nullptr;
-	HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-	HIP_TRY(hipEventRecord(ev, c->stream));                         // the peaks were written on the context's stream
-	struct Run { int slot, w, h, K, iters, left; double e, prev, e0; bool active; MrfLayout lay; hipStream_t st; double *buf; };
-	std::vector<Run> runs(nviews);
-	auto cleanup = [&](int code) { for (int i = 0; i < nviews; ++i) if (runs[i].st) hipStreamSynchronize(runs[i].st); hipEventDestroy(ev); return code; };
-	for (int i = 0; i < nviews; ++i) {
-		Run &r = runs[i];
-		ViewHost &v = c->views[slots[i]];
-		r.slot = slots[i]; r.w = v.w; r.h = v.h; r.K = v.peaks_k; r.iters = 0; r.left = m->max_iters; r.active = true; r.st = nullptr;
-		if (!c->mrf_stream[i]) { if (hipStreamCreateWithFlags(&c->mrf_stream[i], hipStreamNonBlocking) != hipSuccess) return cleanup(fail(SRH_E_DEVICE, "stream creation failed")); }
-		r.st = c->mrf_stream[i];
-		if ((rc = v.mrf.ensure(mrf_scratch_doubles(r.w, r.h)))) return cleanup(rc);
-		r.buf = v.mrf;
-		if (hipStreamWaitEvent(r.st, ev, 0) != hipSuccess ||
-		    launch_mrf_setup(r.st, r.buf, r.w, r.h, r.K, m->beta, m->lambda, m->phi_u, v.peaks, r.lay) != hipSuccess ||
-		    launch_mrf_energy(r.st, r.buf, r.w, r.h, r.K, m->psi_u) != hipSuccess ||
-		    hipMemcpyAsync(&hs[i], r.lay.energy, sizeof(HostState), hipMemcpyDeviceToHost, r.st) != hipSuccess)
-			return cleanup(fail(SRH_E_DEVICE, "MRF setup of view slot %d failed: %s", r.slot, hipGetErrorString(hipGetLastError())));
-	}
-	for (int i = 0; i < nviews; ++i) {
-		if (hipStreamSynchronize(runs[i].st) != hipSuccess) return cleanup(fail(SRH_E_DEVICE, "MRF setup of view slot %d failed", runs[i].slot));
-		runs[i].e = runs[i].e0 = hs[i].energy;
-	}
-	for (int nactive = nviews; nactive > 0; ) {
-		if (cancelled(c)) return cleanup(fail(SRH_E_CANCELLED, "cancelled"));
-		for (int i = 0; i < nviews; ++i) {
-			Run &r = runs[i];
-			if (!r.active) continue;
-			r.prev = r.e;
-			if (launch_mrf_sweep(r.st, r.buf, r.w, r.h, r.K, m->psi_u, r.iters) != hipSuccess ||
-			    launch_mrf_energy(r.st, r.buf, r.w, r.h, r.K, m->psi_u) != hipSuccess ||
-			    hipMemcpyAsync(&hs[i], r.lay.energy, sizeof(HostState), hipMemcpyDeviceToHost, r.st) != hipSuccess)
-				return cleanup(fail(SRH_E_DEVICE, "MRF sweep of view slot %d failed: %s", r.slot, hipGetErrorString(hipGetLastError())));
-		}
-		for (int i = 0; i < nviews; ++i) {
-			Run &r = runs[i];
-			if (!r.active) continue;
-			if (hipStreamSynchronize(r.st) != hipSuccess) return cleanup(fail(SRH_E_DEVICE, "MRF sweep of view slot %d failed", r.slot));
-			if (hs[i].status[0])
-				return cleanup(fail(SRH_E_DEVICE, "MRF sweep %u of view slot %d: band %u waited too long for the band above", hs[i].status[2], r.slot, hs[i].status[1] - 1));
-			r.e = hs[i].energy;
-			++r.iters;
-			if (!(r.prev - r.e > m->min_energy_drop && r.left-- > 0)) {     // do { ... } while (prev - energy > 5 && numIters-- > 0)
-				r.active = false; --nactive;
-				if (launch_mrf_depth(r.st, c->d_views, r.slot, r.buf, r.w, r.h, r.K) != hipSuccess)
-					return cleanup(fail(SRH_E_DEVICE, "MRF depth of view slot %d failed", r.slot));
-			}
-		}
-	}
-	for (int i = 0; i < nviews; ++i) {
-		if (hipStreamSynchronize(runs[i].st) != hipSuccess) return cleanup(fail(SRH_E_DEVICE, "MRF depth of view slot %d failed", runs[i].slot));
-		if (infos) { infos[i].iterations = runs[i].iters; infos[i].energy_initial = runs[i].e0; infos[i].energy_final = runs[i].e; }
-	}
-	hipEventDestroy(ev);
-	return SRH_OK;
+	std::vector<MvsRun> runs;
+	if ((rc = mvs_view_runs(c, slots, nviews, &ViewHost::mrf, runs))) return rc;
+	c->mrf.forget();                                          // the per-view runs leave no state srh_mvs_mrf_state could report
+	return mvs_mrf_drive(c, nviews, runs.data(), m, infos, false);
 }
 
 extern "C" int srh_mvs_mrf_dims(srh_context *c, int *w, int *h, int *top_k)
 {
-	if (!c) return fail(SRH_E_INVALID, "null context");
-	if (!c->mrf_w) return fail(SRH_E_INVALID, "no finished single-view MRF run on this context");
-	if (w) *w = c->mrf_w;
-	if (h) *h = c->mrf_h;
-	if (top_k) *top_k = c->mrf_k;
-	return SRH_OK;
+	return !c ? fail(SRH_E_INVALID, "null context") : c->mrf.dims(w, h, top_k);
 }
 
 extern "C" int srh_mvs_mrf_state(srh_context *c, int bw, int bh, int bk, int32_t *labels, double *data_costs, double *messages)
 {
 	if (!c) return fail(SRH_E_INVALID, "null context");
-	if (!c->mrf_w) return fail(SRH_E_INVALID, "no finished single-view MRF run on this context");
-	if (bw != c->mrf_w || bh != c->mrf_h || bk != c->mrf_k)
-		return fail(SRH_E_INVALID, "buffers sized for %dx%d, K = %d, the last MRF run was %dx%d, K = %d", bw, bh, bk, c->mrf_w, c->mrf_h, c->mrf_k);
+	if (const int rc = c->mrf.check_dims(bw, bh, bk)) return rc;
 	HIP_TRY(hipSetDevice(c->device));
-	const int w = c->mrf_w, h = c->mrf_h, K = c->mrf_k, L = K + 1;
+	const int w = c->mrf.w, h = c->mrf.h, K = c->mrf.l, L = K + 1;
 	const size_t n = (size_t)w*h;
 	MrfLayout lay;
-	launch_mrf_layout(c->mrf, w, h, lay);
+	launch_mrf_layout(c->mrf.scratch, w, h, lay);
 	if (labels) HIP_TRY(hipMemcpyAsync(labels, lay.ans, n*sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
 	// device rows are 16 labels wide: copy the first L of each
 	if (data_costs) HIP_TRY(hipMemcpy2DAsync(data_costs, L*sizeof(double), lay.D, 16*sizeof(double), L*sizeof(double), n, hipMemcpyDeviceToHost, c->stream));
@@ -3322,34 +3340,57 @@ static int check_mvsgm_params(const srh_mvs_sgm_params *m)
 	return SRH_OK;
 }
 
-// The scratch of `nviews` runs (bufs[i] for a w[i] x h[i] view), checked against the free device memory before anything is
-// queued, then reserved
-static int mvsgm_reserve(srh_context *c, int nviews, DevBuf<double> *const *bufs, const int *w, const int *h)
+// The aggregation on every run, after the pre-check of all their scratch: everything is queued direction by direction for
+// all of them, and the host waits once, at the end.  `prof`: profile entries (the one-view form's).
+static int mvs_sgm_drive(srh_context *c, int n, const MvsRun *runs, const srh_mvs_sgm_params *m, srh_sgm_info *infos, bool prof)
 {
-	size_t need = 0, missing = 0, held = 0;
-	for (int i = 0; i < nviews; ++i) {
-		const size_t scratch = mvs_sgm_scratch_doubles(w[i], h[i]);
-		need += scratch*sizeof(double);
-		if (bufs[i]->n < scratch) { missing += scratch*sizeof(double); held += bufs[i]->bytes(); }   // (an outgrown buffer is released first)
-	}
-	size_t free_b = 0, total_b = 0;
-	if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-		size_t avail = free_b + pool_bytes_on(c->device) + held;
-		size_t want = missing;
-		if (c->mem_limit) { want = need; if (avail > c->mem_limit) avail = c->mem_limit; }   // the pretended device holds the whole run
-		if (want > avail)
-			return fail(SRH_E_DEVICE, "the semi-global aggregation of %d view(s) (the first %dx%d) needs %zu bytes of device memory (per view peak depths, data costs and sums, %zu each at 16 doubles per pixel, + the labels; no bands: a path crosses the whole grid), %zu are available",
-			            nviews, w[0], h[0], need, (size_t)w[0]*h[0]*16*sizeof(double), avail);
-	} else (void)hipGetLastError();
+	// (a profile entry per direction: rows, columns and diagonals stream differently)
+	static const char *const names[8] = { "mvs_sgm_path_kernel[+1,0]", "mvs_sgm_path_kernel[-1,0]", "mvs_sgm_path_kernel[0,+1]",
+	                                      "mvs_sgm_path_kernel[0,-1]", "mvs_sgm_path_kernel[+1,+1]", "mvs_sgm_path_kernel[-1,-1]",
+	                                      "mvs_sgm_path_kernel[+1,-1]", "mvs_sgm_path_kernel[-1,+1]" };
 	int rc;
-	for (int i = 0; i < nviews; ++i) if ((rc = bufs[i]->ensure(mvs_sgm_scratch_doubles(w[i], h[i])))) return rc;
+	std::vector<StageWant> wants;
+	for (int i = 0; i < n; ++i) wants.push_back({ runs[i].scratch, mvs_sgm_scratch_doubles(runs[i].w, runs[i].h) });
+	if ((rc = stage_reserve(c, wants.data(), n, [&](size_t need, size_t avail) {
+		return fail(SRH_E_DEVICE, "the semi-global aggregation of %d view(s) (the first %dx%d) needs %zu bytes of device memory (per view peak depths, data costs and sums, %zu each at 16 doubles per pixel, + the labels; no bands: a path crosses the whole grid), %zu are available",
+		            n, runs[0].w, runs[0].h, need, (size_t)runs[0].w*runs[0].h*16*sizeof(double), avail); }))) return rc;
+	if (!c->mvsgm_host) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->mvsgm_host), sizeof(double)*SRH_MAX_VIEWS, hipHostMallocDefault));
+	auto stop = [&](int code) { for (int i = 0; i < n; ++i) hipStreamSynchronize(runs[i].st); return code; };
+	auto failed = [&](const char *what, int i) { return stop(fail(SRH_E_DEVICE, "SGM %s of view slot %d failed: %s", what, runs[i].slot,
+	                                                              hipGetErrorString(hipGetLastError()))); };
+	for (int i = 0; i < n; ++i) {
+		const MvsRun &r = runs[i];
+		Scope s(c, "mrf_data_kernel", prof);
+		if (launch_mvs_sgm_setup(r.st, *r.scratch, r.w, r.h, r.K, m->beta, m->lambda, m->phi_u, r.peaks) != hipSuccess) return failed("setup", i);
+	}
+	int paths = 0;
+	for (int k = 0; k < 8; ++k) {
+		if (!(m->path_mask >> k & 1)) continue;
+		// (nothing of a slot has been written yet: the depth map is the read-off's, after the last direction)
+		if (cancelled(c)) return stop(fail(SRH_E_CANCELLED, "cancelled"));
+		for (int i = 0; i < n; ++i) {
+			const MvsRun &r = runs[i];
+			Scope s(c, names[k], prof);
+			if (launch_mvs_sgm_path(r.st, *r.scratch, r.w, r.h, r.K, m->psi_u, k, paths == 0) != hipSuccess) return failed("path", i);
+		}
+		++paths;
+	}
+	for (int i = 0; i < n; ++i) {
+		const MvsRun &r = runs[i];
+		MvsSgmLayout lay;
+		mvs_sgm_layout(*r.scratch, r.w, r.h, lay);
+		hipError_t e;
+		{ Scope s(c, "mvs_sgm_readoff_kernel", prof); e = launch_mvs_sgm_readoff(r.st, c->d_views, r.slot, *r.scratch, r.w, r.h, r.K); }
+		if (e == hipSuccess) { Scope s(c, "mrf_energy_kernel", prof); e = launch_mvs_sgm_energy(r.st, *r.scratch, r.w, r.h, r.K, m->psi_u); }
+		if (e == hipSuccess) e = hipMemcpyAsync(&c->mvsgm_host[i], lay.energy, sizeof(double), hipMemcpyDeviceToHost, r.st);
+		if (e != hipSuccess) return failed("read-off", i);
+	}
+	for (int i = 0; i < n; ++i) {
+		if (hipStreamSynchronize(runs[i].st) != hipSuccess) return failed("read-off", i);
+		if (infos) { infos[i].paths = paths; infos[i].energy = c->mvsgm_host[i]; }
+	}
 	return SRH_OK;
 }
-
-// (a profile entry per direction: rows, columns and diagonals stream differently)
-static const char *const mvsgm_names[8] = { "mvs_sgm_path_kernel[+1,0]", "mvs_sgm_path_kernel[-1,0]", "mvs_sgm_path_kernel[0,+1]",
-                                            "mvs_sgm_path_kernel[0,-1]", "mvs_sgm_path_kernel[+1,+1]", "mvs_sgm_path_kernel[-1,-1]",
-                                            "mvs_sgm_path_kernel[+1,-1]", "mvs_sgm_path_kernel[-1,+1]" };
 
 extern "C" int srh_mvs_sgm_estimate(srh_context *c, int slot, int K, const void *peaks_dev, const srh_mvs_sgm_params *m, srh_sgm_info *info)
 {
@@ -3361,32 +3402,10 @@ extern "C" int srh_mvs_sgm_estimate(srh_context *c, int slot, int K, const void 
 	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
 	HIP_TRY(hipSetDevice(c->device));
 	const ViewHost &v = c->views[slot];
-	const int w = v.w, h = v.h;
-	c->mvsgm_w = c->mvsgm_h = c->mvsgm_k = 0;
-	DevBuf<double> *buf = &c->mvsgm;
-	if ((rc = mvsgm_reserve(c, 1, &buf, &w, &h))) return rc;
-	{ Scope s(c, "mrf_data_kernel");
-	  HIP_TRY(launch_mvs_sgm_setup(c->stream, c->mvsgm, w, h, K, m->beta, m->lambda, m->phi_u, static_cast<const double *>(peaks_dev))); }
-	int paths = 0;
-	for (int k = 0; k < 8; ++k) {
-		if (!(m->path_mask >> k & 1)) continue;
-		// (nothing of the slot has been written yet: the depth map is the read-off's, after the last direction)
-		if (cancelled(c)) { HIP_TRY(hipStreamSynchronize(c->stream)); return fail(SRH_E_CANCELLED, "cancelled"); }
-		{ Scope s(c, mvsgm_names[k]);
-		  HIP_TRY(launch_mvs_sgm_path(c->stream, c->mvsgm, w, h, K, m->psi_u, k, paths == 0)); }
-		++paths;
-	}
-	{ Scope s(c, "mvs_sgm_readoff_kernel");
-	  HIP_TRY(launch_mvs_sgm_readoff(c->stream, c->d_views, slot, c->mvsgm, w, h, K)); }
-	{ Scope s(c, "mrf_energy_kernel");
-	  HIP_TRY(launch_mvs_sgm_energy(c->stream, c->mvsgm, w, h, K, m->psi_u)); }
-	MvsSgmLayout lay;
-	mvs_sgm_layout(c->mvsgm, w, h, lay);
-	double e = 0.0;
-	HIP_TRY(hipMemcpyAsync(&e, lay.energy, sizeof(e), hipMemcpyDeviceToHost, c->stream));
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	c->mvsgm_w = w; c->mvsgm_h = h; c->mvsgm_k = K;
-	if (info) { info->paths = paths; info->energy = e; }
+	c->mvsgm.forget();
+	const MvsRun run = { slot, v.w, v.h, K, c->stream, &c->mvsgm.scratch, static_cast<const double *>(peaks_dev) };
+	if ((rc = mvs_sgm_drive(c, 1, &run, m, info, true))) return rc;
+	c->mvsgm.finished(v.w, v.h, K);
 	return SRH_OK;
 }
 
@@ -3414,80 +3433,27 @@ extern "C" int srh_mvs_sgm_estimate_views(srh_context *c, const int32_t *slots, 
 	if (!c) return fail(SRH_E_INVALID, "null context");
 	if (!slots || nviews < 1 || nviews > SRH_MAX_VIEWS || !m) return fail(SRH_E_INVALID, "bad view list / params");
 	if ((rc = check_mvsgm_params(m))) return rc;
-	for (int i = 0; i < nviews; ++i) {
-		if ((rc = check_slot(c, slots[i], true))) return rc;
-		if (c->views[slots[i]].peaks_k < 1) return fail(SRH_E_INVALID, "view slot %d has no peaks (srh_mvs_initial_estimate_peaks first)", slots[i]);
-		for (int j = 0; j < i; ++j) if (slots[j] == slots[i]) return fail(SRH_E_INVALID, "view slot %d listed twice", slots[i]);
-	}
+	std::vector<MvsRun> runs;
+	if ((rc = mvs_view_runs(c, slots, nviews, &ViewHost::sgm, runs))) return rc;
 	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
-	HIP_TRY(hipSetDevice(c->device));
-	c->mvsgm_w = c->mvsgm_h = c->mvsgm_k = 0;                 // the per-view runs leave no state srh_mvs_sgm_state could report
-	std::vector<DevBuf<double> *> bufs(nviews);
-	std::vector<int> ws(nviews), hs(nviews);
-	for (int i = 0; i < nviews; ++i) { ViewHost &v = c->views[slots[i]]; bufs[i] = &v.sgm; ws[i] = v.w; hs[i] = v.h; }
-	if ((rc = mvsgm_reserve(c, nviews, bufs.data(), ws.data(), hs.data()))) return rc;
-	if (!c->mvsgm_host) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->mvsgm_host), sizeof(double)*SRH_MAX_VIEWS, hipHostMallocDefault));
-	for (int i = 0; i < nviews; ++i)
-		if (!c->mrf_stream[i]) HIP_TRY(hipStreamCreateWithFlags(&c->mrf_stream[i], hipStreamNonBlocking));
-	hipEvent_t ev = nullptr;
-	HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-	auto cleanup = [&](int code) { for (int i = 0; i < nviews; ++i) hipStreamSynchronize(c->mrf_stream[i]); hipEventDestroy(ev); return code; };
-	if (hipEventRecord(ev, c->stream) != hipSuccess) return cleanup(fail(SRH_E_DEVICE, "event record failed")); // the peaks were written on the context's stream
-	for (int i = 0; i < nviews; ++i) {
-		ViewHost &v = c->views[slots[i]];
-		if (hipStreamWaitEvent(c->mrf_stream[i], ev, 0) != hipSuccess ||
-		    launch_mvs_sgm_setup(c->mrf_stream[i], v.sgm, v.w, v.h, v.peaks_k, m->beta, m->lambda, m->phi_u, v.peaks) != hipSuccess)
-			return cleanup(fail(SRH_E_DEVICE, "SGM setup of view slot %d failed: %s", slots[i], hipGetErrorString(hipGetLastError())));
-	}
-	int paths = 0;
-	for (int k = 0; k < 8; ++k) {
-		if (!(m->path_mask >> k & 1)) continue;
-		if (cancelled(c)) return cleanup(fail(SRH_E_CANCELLED, "cancelled"));      // (no depth map has been written yet)
-		for (int i = 0; i < nviews; ++i) {
-			ViewHost &v = c->views[slots[i]];
-			if (launch_mvs_sgm_path(c->mrf_stream[i], v.sgm, v.w, v.h, v.peaks_k, m->psi_u, k, paths == 0) != hipSuccess)
-				return cleanup(fail(SRH_E_DEVICE, "SGM direction %d of view slot %d failed: %s", k, slots[i], hipGetErrorString(hipGetLastError())));
-		}
-		++paths;
-	}
-	for (int i = 0; i < nviews; ++i) {
-		ViewHost &v = c->views[slots[i]];
-		MvsSgmLayout lay;
-		mvs_sgm_layout(v.sgm, v.w, v.h, lay);
-		if (launch_mvs_sgm_readoff(c->mrf_stream[i], c->d_views, slots[i], v.sgm, v.w, v.h, v.peaks_k) != hipSuccess ||
-		    launch_mvs_sgm_energy(c->mrf_stream[i], v.sgm, v.w, v.h, v.peaks_k, m->psi_u) != hipSuccess ||
-		    hipMemcpyAsync(&c->mvsgm_host[i], lay.energy, sizeof(double), hipMemcpyDeviceToHost, c->mrf_stream[i]) != hipSuccess)
-			return cleanup(fail(SRH_E_DEVICE, "SGM read-off of view slot %d failed: %s", slots[i], hipGetErrorString(hipGetLastError())));
-	}
-	for (int i = 0; i < nviews; ++i) {
-		if (hipStreamSynchronize(c->mrf_stream[i]) != hipSuccess) return cleanup(fail(SRH_E_DEVICE, "SGM of view slot %d failed", slots[i]));
-		if (infos) { infos[i].paths = paths; infos[i].energy = c->mvsgm_host[i]; }
-	}
-	hipEventDestroy(ev);
-	return SRH_OK;
+	c->mvsgm.forget();                                        // the per-view runs leave no state srh_mvs_sgm_state could report
+	return mvs_sgm_drive(c, nviews, runs.data(), m, infos, false);
 }
 
 extern "C" int srh_mvs_sgm_dims(srh_context *c, int *w, int *h, int *top_k)
 {
-	if (!c) return fail(SRH_E_INVALID, "null context");
-	if (!c->mvsgm_w) return fail(SRH_E_INVALID, "no finished single-view SGM run on this context");
-	if (w) *w = c->mvsgm_w;
-	if (h) *h = c->mvsgm_h;
-	if (top_k) *top_k = c->mvsgm_k;
-	return SRH_OK;
+	return !c ? fail(SRH_E_INVALID, "null context") : c->mvsgm.dims(w, h, top_k);
 }
 
 extern "C" int srh_mvs_sgm_state(srh_context *c, int bw, int bh, int bk, int32_t *labels, double *data_costs, double *sums)
 {
 	if (!c) return fail(SRH_E_INVALID, "null context");
-	if (!c->mvsgm_w) return fail(SRH_E_INVALID, "no finished single-view SGM run on this context");
-	if (bw != c->mvsgm_w || bh != c->mvsgm_h || bk != c->mvsgm_k)
-		return fail(SRH_E_INVALID, "buffers sized for %dx%d, K = %d, the last SGM run was %dx%d, K = %d", bw, bh, bk, c->mvsgm_w, c->mvsgm_h, c->mvsgm_k);
+	if (const int rc = c->mvsgm.check_dims(bw, bh, bk)) return rc;
 	HIP_TRY(hipSetDevice(c->device));
-	const int w = c->mvsgm_w, h = c->mvsgm_h, K = c->mvsgm_k, L = K + 1;
+	const int w = c->mvsgm.w, h = c->mvsgm.h, K = c->mvsgm.l, L = K + 1;
 	const size_t n = (size_t)w*h;
 	MvsSgmLayout lay;
-	mvs_sgm_layout(c->mvsgm, w, h, lay);
+	mvs_sgm_layout(c->mvsgm.scratch, w, h, lay);
 	if (labels) HIP_TRY(hipMemcpyAsync(labels, lay.ans, n*sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
 	// device rows are 16 labels wide: copy the first L of each
 	if (data_costs) HIP_TRY(hipMemcpy2DAsync(data_costs, L*sizeof(double), lay.D, 16*sizeof(double), L*sizeof(double), n, hipMemcpyDeviceToHost, c->stream));
@@ -3504,39 +3470,84 @@ extern "C" void srh_twoview_mrf_params_defaults(srh_twoview_mrf_params *m)
 	m->max_iters = 50; m->min_energy_drop = 5;                       // :378, :390
 }
 
-static int check_tvmrf_params(const srh_twoview_mrf_params *m, int L)
+// the label count and the smoothness term of a TwoView label stage: the optimiser and the aggregation take the same
+template <class Params>
+static int check_tv_smoothness(const Params *m, int L, const char *stage)
 {
-	if (!m) return fail(SRH_E_INVALID, "null MRF params");
+	if (!m) return fail(SRH_E_INVALID, "null %s params", stage);
 	if (L < 2 || L > 256) return fail(SRH_E_UNSUPPORTED, "%d labels outside [2,256] (64 lanes per pixel, up to 4 labels per lane)", L);
 	if (m->smooth_exp != 1) return fail(SRH_E_UNSUPPORTED, "smooth_exp %d: only the truncated-linear term (1) is built", m->smooth_exp);
 	if (!(m->smooth_max > 0 && m->smooth_max <= 4)) return fail(SRH_E_UNSUPPORTED, "smooth_max %g outside (0,4] (the message window reaches 3 labels)", m->smooth_max);
 	if (!(m->lambda >= 0 && m->lambda < __builtin_inf())) return fail(SRH_E_INVALID, "lambda %g must be finite and >= 0", m->lambda);
+	return SRH_OK;
+}
+
+static int check_tvmrf_params(const srh_twoview_mrf_params *m, int L)
+{
+	if (const int rc = check_tv_smoothness(m, L, "MRF")) return rc;
 	if (m->max_iters < 0 || m->max_iters > (1 << 24)) return fail(SRH_E_INVALID, "max_iters %d outside [0,2^24]", m->max_iters);
 	return SRH_OK;
 }
 
-// bytes of device memory a run still has to find: the message planes (+ granules, labels), and the cost volume when it is ours
-static int tvmrf_reserve(srh_context *c, int w, int h, int L, bool own_costs)
+// What tells the two TwoView label stages apart outside their runs: the state, the scratch's size, the words of the
+// pre-check's refusal (tv_stage_reserve) and the name of the stage's step in srh_twoview_compute_*'s progress
+struct TvStage { LabelStage srh_context::*state; size_t (*scratch_doubles)(int w, int h, int L); const char *what, *planes, *why, *progress; };
+static const TvStage TV_MRF = { &srh_context::tvmrf, twoview_mrf_scratch_doubles, "MRF stage", "two message planes", "sweep needs", "Optimizing..." };
+static const TvStage TV_SGM = { &srh_context::tvsgm, twoview_sgm_scratch_doubles, "semi-global aggregation", "sums", "path crosses", "Aggregating..." };
+
+// a new run of the stage on a w x h x L volume: its scratch, and its own cost volume when the costs are not the caller's
+static int tv_stage_reserve(srh_context *c, const TvStage &T, int w, int h, int L, bool own_costs)
 {
-	const size_t scratch = twoview_mrf_scratch_doubles(w, h, L), vol = own_costs ? (size_t)w*h*L : 0;
-	const size_t need = (scratch + vol)*sizeof(double);
-	size_t missing = 0;
-	if (c->tvmrf.n < scratch) missing += scratch*sizeof(double);
-	if (c->tvmrf_costs.n < vol) missing += vol*sizeof(double);
-	size_t free_b = 0, total_b = 0;
-	if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-		size_t avail = free_b + pool_bytes_on(c->device);
-		if (c->tvmrf.n < scratch) avail += c->tvmrf.bytes();            // (an outgrown buffer is released first)
-		if (c->tvmrf_costs.n < vol) avail += c->tvmrf_costs.bytes();
-		size_t want = missing;
-		if (c->mem_limit) { want = need; if (avail > c->mem_limit) avail = c->mem_limit; }   // the pretended device holds the whole run
-		if (want > avail)
-			return fail(SRH_E_DEVICE, "the MRF stage of a %dx%dx%d volume needs %zu bytes of device memory (%s: %zu per volume, no bands: a sweep needs the whole grid), %zu are available",
-			            w, h, L, need, own_costs ? "costs and two message planes" : "two message planes", (size_t)w*h*L*sizeof(double), avail);
-	} else (void)hipGetLastError();
+	LabelStage &S = c->*T.state;
+	S.forget();
+	const size_t vol = (size_t)w*h*L;
+	const StageWant wants[2] = { { &S.scratch, T.scratch_doubles(w, h, L) }, { &S.costs, own_costs ? vol : 0 } };
+	S.own_costs = own_costs;
+	return stage_reserve(c, wants, 2, [&](size_t need, size_t avail) {
+		return fail(SRH_E_DEVICE, "the %s of a %dx%dx%d volume needs %zu bytes of device memory (%s%s: %zu per volume, no bands: a %s the whole grid), %zu are available",
+		            T.what, w, h, L, need, own_costs ? "costs and " : "", T.planes, vol*sizeof(double), T.why, avail);
+	});
+}
+
+// the label cost volume of ref against oth into the stage's own buffer
+static int tv_stage_costs(srh_context *c, const TvStage &T, int ref, int oth, const srh_params *p)
+{
 	int rc;
-	if ((rc = c->tvmrf.ensure(scratch))) return rc;
-	if (vol && (rc = c->tvmrf_costs.ensure(vol))) return rc;
+	const ViewHost &v = c->views[ref];
+	if ((rc = tv_stage_reserve(c, T, v.w, v.h, p->num_depth_levels, true))) return rc;
+	Scope s(c, "twoview_label_costs_kernel");
+	HIP_TRY(launch_twoview_label_costs(c->stream, c->d_views, ref, oth, v.w, *p, c->cost_kind == SRH_COST_SAD, 0, v.h,
+	                                   (2*p->window_radius + 1)*p->bad_ret, (c->*T.state).costs, nullptr));
+	return SRH_OK;
+}
+
+// srh_twoview_compute_mrf / _sgm: both directions through the stage, run(ref, k) on its own cost volume, then the end of
+// srh_twoview_compute.  Progress steps as a USE_MRF build of TwoViewStereo emits them (twoviewstereo.cpp:234, 337, 405, 506, 597, 225).
+template <class Run>
+static int tv_stage_compute(srh_context *c, const TvStage &T, int left, int right, const srh_params *p, double *left_out, double *right_out, Run run)
+{
+	int rc;
+	const ViewHost &L = c->views[left], &Rv = c->views[right];
+	if (L.w != Rv.w || L.h != Rv.h) return fail(SRH_E_INVALID, "TwoViewStereo needs equal-sized views");
+	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
+	for (int k = 0; k < 2; ++k) {
+		const int ref = k == 0 ? left : right, oth = k == 0 ? right : left;
+		progress(c, 1 + 2*k, k == 0 ? "Computing cost volume for left image..." : "Computing cost volume for right image...");
+		HIP_TRY(hipSetDevice(c->device));
+		if ((rc = tv_stage_costs(c, T, ref, oth, p))) return rc;
+		// (the cost kernel is queued: a cancelled call returns with the stream idle, as everywhere else)
+		if (cancelled(c)) { HIP_TRY(hipStreamSynchronize(c->stream)); return fail(SRH_E_CANCELLED, "cancelled"); }
+		progress(c, 2 + 2*k, T.progress);
+		if ((rc = run(ref, k))) return rc;
+		if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
+	}
+	progress(c, 5, "Detecting inconsistencies...");
+	if ((rc = srh_twoview_cross_check(c, left, right, p))) return rc;
+	if (c->filter_invalid && (rc = twoview_filter(c, left, right, p))) return rc;
+	if (left_out && (rc = srh_view_depth_download(c, left, left_out))) return rc;
+	if (right_out && (rc = srh_view_depth_download(c, right, right_out))) return rc;
+	if ((rc = srh_synchronize(c))) return rc;
+	progress(c, 8, "Finished!");
 	return SRH_OK;
 }
 
@@ -3546,14 +3557,14 @@ static int tvmrf_run(srh_context *c, int slot, const srh_params *p, int L, const
 	int rc;
 	ViewHost &v = c->views[slot];
 	const int w = v.w, h = v.h;
-	c->tvmrf_w = c->tvmrf_h = c->tvmrf_l = 0;
+	c->tvmrf.forget();
 	v.wta_flags = 0;                                            // no scan made this depth map: the WTA by-products are stale
 	TvMrfLayout lay;
-	HIP_TRY(launch_twoview_mrf_setup(c->stream, c->tvmrf, w, h, L, lay));
+	HIP_TRY(launch_twoview_mrf_setup(c->stream, c->tvmrf.scratch, w, h, L, lay));
 	struct { double energy, pad; unsigned status[4]; } hs;
 	auto energy = [&](double &e) -> int {
 		{ Scope s(c, "twoview_mrf_energy_kernel");
-		  HIP_TRY(launch_twoview_mrf_energy(c->stream, c->tvmrf, costs, w, h, L, m->lambda, m->smooth_max)); }
+		  HIP_TRY(launch_twoview_mrf_energy(c->stream, c->tvmrf.scratch, costs, w, h, L, m->lambda, m->smooth_max)); }
 		HIP_TRY(hipMemcpyAsync(&hs, lay.energy, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
 		HIP_TRY(hipStreamSynchronize(c->stream));
 		if (hs.status[0])
@@ -3570,14 +3581,14 @@ static int tvmrf_run(srh_context *c, int slot, const srh_params *p, int L, const
 		if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
 		prev = e;
 		{ Scope s(c, "twoview_mrf_pass_kernel");
-		  HIP_TRY(launch_twoview_mrf_sweep(c->stream, c->tvmrf, costs, w, h, L, m->lambda, m->smooth_max, iters)); }
+		  HIP_TRY(launch_twoview_mrf_sweep(c->stream, c->tvmrf.scratch, costs, w, h, L, m->lambda, m->smooth_max, iters)); }
 		if ((rc = energy(e))) return rc;
 		++iters;
 	} while (prev - e > m->min_energy_drop && num_iters-- > 0);
 	{ Scope s(c, "twoview_mrf_depth_kernel");
-	  HIP_TRY(launch_twoview_mrf_depth(c->stream, c->d_views, slot, *p, c->tvmrf, w, h, L)); }
+	  HIP_TRY(launch_twoview_mrf_depth(c->stream, c->d_views, slot, *p, c->tvmrf.scratch, w, h, L)); }
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	c->tvmrf_w = w; c->tvmrf_h = h; c->tvmrf_l = L;
+	c->tvmrf.finished(w, h, L);
 	if (info) { info->iterations = iters; info->energy_initial = e0; info->energy_final = e; }
 	return SRH_OK;
 }
@@ -3593,9 +3604,7 @@ extern "C" int srh_twoview_mrf_optimize(srh_context *c, int slot, const srh_para
 	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
 	HIP_TRY(hipSetDevice(c->device));
 	const ViewHost &v = c->views[slot];
-	c->tvmrf_w = c->tvmrf_h = c->tvmrf_l = 0;
-	if ((rc = tvmrf_reserve(c, v.w, v.h, L, false))) return rc;
-	c->tvmrf_own_costs = false;
+	if ((rc = tv_stage_reserve(c, TV_MRF, v.w, v.h, L, false))) return rc;
 	return tvmrf_run(c, slot, p, L, static_cast<const double *>(costs_dev), m, info);
 }
 
@@ -3643,14 +3652,8 @@ extern "C" int srh_twoview_mrf(srh_context *c, int ref, int oth, const srh_param
 	if ((rc = check_tvmrf_params(m, L))) return rc;
 	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
 	HIP_TRY(hipSetDevice(c->device));
-	const ViewHost &v = c->views[ref];
-	c->tvmrf_w = c->tvmrf_h = c->tvmrf_l = 0;
-	if ((rc = tvmrf_reserve(c, v.w, v.h, L, true))) return rc;
-	c->tvmrf_own_costs = true;
-	{ Scope s(c, "twoview_label_costs_kernel");
-	  HIP_TRY(launch_twoview_label_costs(c->stream, c->d_views, ref, oth, v.w, *p, c->cost_kind == SRH_COST_SAD, 0, v.h,
-	                                     (2*p->window_radius + 1)*p->bad_ret, c->tvmrf_costs, nullptr)); }
-	return tvmrf_run(c, ref, p, L, c->tvmrf_costs, m, info);
+	if ((rc = tv_stage_costs(c, TV_MRF, ref, oth, p))) return rc;
+	return tvmrf_run(c, ref, p, L, c->tvmrf.costs, m, info);
 }
 
 extern "C" int srh_twoview_compute_mrf(srh_context *c, int left, int right, const srh_params *p, const srh_twoview_mrf_params *m,
@@ -3659,62 +3662,29 @@ extern "C" int srh_twoview_compute_mrf(srh_context *c, int left, int right, cons
 	int rc;
 	if ((rc = check_label_costs(c, left, right, p))) return rc;
 	if ((rc = check_tvmrf_params(m, p->num_depth_levels))) return rc;
-	const ViewHost &L = c->views[left], &Rv = c->views[right];
-	if (L.w != Rv.w || L.h != Rv.h) return fail(SRH_E_INVALID, "TwoViewStereo needs equal-sized views");
-	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
-	// progress steps as a USE_MRF build of TwoViewStereo emits them (twoviewstereo.cpp:234, 337, 405, 506, 597, 225)
-	for (int k = 0; k < 2; ++k) {
-		const int ref = k == 0 ? left : right, oth = k == 0 ? right : left;
-		progress(c, 1 + 2*k, k == 0 ? "Computing cost volume for left image..." : "Computing cost volume for right image...");
-		HIP_TRY(hipSetDevice(c->device));
-		const ViewHost &v = c->views[ref];
-		const int D = p->num_depth_levels;
-		c->tvmrf_w = c->tvmrf_h = c->tvmrf_l = 0;
-		if ((rc = tvmrf_reserve(c, v.w, v.h, D, true))) return rc;
-		c->tvmrf_own_costs = true;
-		{ Scope s(c, "twoview_label_costs_kernel");
-		  HIP_TRY(launch_twoview_label_costs(c->stream, c->d_views, ref, oth, v.w, *p, c->cost_kind == SRH_COST_SAD, 0, v.h,
-		                                     (2*p->window_radius + 1)*p->bad_ret, c->tvmrf_costs, nullptr)); }
-		if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
-		progress(c, 2 + 2*k, "Optimizing...");
-		if ((rc = tvmrf_run(c, ref, p, D, c->tvmrf_costs, m, infos ? infos + k : nullptr))) return rc;
-		if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
-	}
-	progress(c, 5, "Detecting inconsistencies...");
-	if ((rc = srh_twoview_cross_check(c, left, right, p))) return rc;
-	if (c->filter_invalid && (rc = twoview_filter(c, left, right, p))) return rc;
-	if (left_out && (rc = srh_view_depth_download(c, left, left_out))) return rc;
-	if (right_out && (rc = srh_view_depth_download(c, right, right_out))) return rc;
-	if ((rc = srh_synchronize(c))) return rc;
-	progress(c, 8, "Finished!");
-	return SRH_OK;
+	return tv_stage_compute(c, TV_MRF, left, right, p, left_out, right_out, [&](int ref, int k) {
+		return tvmrf_run(c, ref, p, p->num_depth_levels, c->tvmrf.costs, m, infos ? infos + k : nullptr);
+	});
 }
 
 extern "C" int srh_twoview_mrf_dims(srh_context *c, int *w, int *h, int *L)
 {
-	if (!c) return fail(SRH_E_INVALID, "null context");
-	if (!c->tvmrf_w) return fail(SRH_E_INVALID, "no finished TwoView MRF run on this context");
-	if (w) *w = c->tvmrf_w;
-	if (h) *h = c->tvmrf_h;
-	if (L) *L = c->tvmrf_l;
-	return SRH_OK;
+	return !c ? fail(SRH_E_INVALID, "null context") : c->tvmrf.dims(w, h, L);
 }
 
 extern "C" int srh_twoview_mrf_state(srh_context *c, int bw, int bh, int bl, int32_t *labels, double *data_costs, double *messages)
 {
 	if (!c) return fail(SRH_E_INVALID, "null context");
-	if (!c->tvmrf_w) return fail(SRH_E_INVALID, "no finished TwoView MRF run on this context");
-	if (bw != c->tvmrf_w || bh != c->tvmrf_h || bl != c->tvmrf_l)
-		return fail(SRH_E_INVALID, "buffers sized for %dx%d, L = %d, the last TwoView MRF run was %dx%d, L = %d", bw, bh, bl, c->tvmrf_w, c->tvmrf_h, c->tvmrf_l);
-	if (data_costs && !c->tvmrf_own_costs)
+	if (const int rc = c->tvmrf.check_dims(bw, bh, bl)) return rc;
+	if (data_costs && !c->tvmrf.own_costs)
 		return fail(SRH_E_INVALID, "the data costs of srh_twoview_mrf_optimize are the caller's volume: the context keeps none");
 	HIP_TRY(hipSetDevice(c->device));
-	const int w = c->tvmrf_w, h = c->tvmrf_h, L = c->tvmrf_l;
+	const int w = c->tvmrf.w, h = c->tvmrf.h, L = c->tvmrf.l;
 	const size_t n = (size_t)w*h;
 	TvMrfLayout lay;
-	launch_twoview_mrf_layout(c->tvmrf, w, h, L, lay);
+	launch_twoview_mrf_layout(c->tvmrf.scratch, w, h, L, lay);
 	if (labels) HIP_TRY(hipMemcpyAsync(labels, lay.ans, n*sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-	if (data_costs) HIP_TRY(hipMemcpyAsync(data_costs, c->tvmrf_costs, n*L*sizeof(double), hipMemcpyDeviceToHost, c->stream));
+	if (data_costs) HIP_TRY(hipMemcpyAsync(data_costs, c->tvmrf.costs, n*L*sizeof(double), hipMemcpyDeviceToHost, c->stream));
 	if (messages) {
 		HIP_TRY(hipMemcpy2DAsync(messages, 2*L*sizeof(double), lay.Mh, L*sizeof(double), L*sizeof(double), n, hipMemcpyDeviceToHost, c->stream));
 		HIP_TRY(hipMemcpy2DAsync(messages + L, 2*L*sizeof(double), lay.Mv, L*sizeof(double), L*sizeof(double), n, hipMemcpyDeviceToHost, c->stream));
@@ -3733,37 +3703,8 @@ extern "C" void srh_twoview_sgm_params_defaults(srh_twoview_sgm_params *m)
 
 static int check_tvsgm_params(const srh_twoview_sgm_params *m, int L)
 {
-	if (!m) return fail(SRH_E_INVALID, "null SGM params");
-	if (L < 2 || L > 256) return fail(SRH_E_UNSUPPORTED, "%d labels outside [2,256] (64 lanes per pixel, up to 4 labels per lane)", L);
-	if (m->smooth_exp != 1) return fail(SRH_E_UNSUPPORTED, "smooth_exp %d: only the truncated-linear term (1) is built", m->smooth_exp);
-	if (!(m->smooth_max > 0 && m->smooth_max <= 4)) return fail(SRH_E_UNSUPPORTED, "smooth_max %g outside (0,4] (the message window reaches 3 labels)", m->smooth_max);
-	if (!(m->lambda >= 0 && m->lambda < __builtin_inf())) return fail(SRH_E_INVALID, "lambda %g must be finite and >= 0", m->lambda);
+	if (const int rc = check_tv_smoothness(m, L, "SGM")) return rc;
 	if (m->path_mask <= 0 || m->path_mask > 0xFF) return fail(SRH_E_INVALID, "path_mask 0x%x: bits 0..7 enable the 8 directions, at least one", (unsigned)m->path_mask);
-	return SRH_OK;
-}
-
-// bytes of device memory a run still has to find: the sums (+ labels), and the cost volume when it is ours
-static int tvsgm_reserve(srh_context *c, int w, int h, int L, bool own_costs)
-{
-	const size_t scratch = twoview_sgm_scratch_doubles(w, h, L), vol = own_costs ? (size_t)w*h*L : 0;
-	const size_t need = (scratch + vol)*sizeof(double);
-	size_t missing = 0;
-	if (c->tvsgm.n < scratch) missing += scratch*sizeof(double);
-	if (c->tvsgm_costs.n < vol) missing += vol*sizeof(double);
-	size_t free_b = 0, total_b = 0;
-	if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-		size_t avail = free_b + pool_bytes_on(c->device);
-		if (c->tvsgm.n < scratch) avail += c->tvsgm.bytes();            // (an outgrown buffer is released first)
-		if (c->tvsgm_costs.n < vol) avail += c->tvsgm_costs.bytes();
-		size_t want = missing;
-		if (c->mem_limit) { want = need; if (avail > c->mem_limit) avail = c->mem_limit; }   // the pretended device holds the whole run
-		if (want > avail)
-			return fail(SRH_E_DEVICE, "the semi-global aggregation of a %dx%dx%d volume needs %zu bytes of device memory (%s: %zu per volume, no bands: a path crosses the whole grid), %zu are available",
-			            w, h, L, need, own_costs ? "costs and sums" : "sums", (size_t)w*h*L*sizeof(double), avail);
-	} else (void)hipGetLastError();
-	int rc;
-	if ((rc = c->tvsgm.ensure(scratch))) return rc;
-	if (vol && (rc = c->tvsgm_costs.ensure(vol))) return rc;
 	return SRH_OK;
 }
 
@@ -3772,9 +3713,9 @@ static int tvsgm_run(srh_context *c, int slot, const srh_params *p, int L, const
 {
 	ViewHost &v = c->views[slot];
 	const int w = v.w, h = v.h;
-	c->tvsgm_w = c->tvsgm_h = c->tvsgm_l = 0;
+	c->tvsgm.forget();
 	TvSgmLayout lay;
-	twoview_sgm_layout(c->tvsgm, w, h, L, lay);
+	twoview_sgm_layout(c->tvsgm.scratch, w, h, L, lay);
 	// (a profile entry per direction: rows, columns and diagonals stream differently)
 	static const char *const names[8] = { "twoview_sgm_path_kernel[+1,0]", "twoview_sgm_path_kernel[-1,0]", "twoview_sgm_path_kernel[0,+1]",
 	                                      "twoview_sgm_path_kernel[0,-1]", "twoview_sgm_path_kernel[+1,+1]", "twoview_sgm_path_kernel[-1,-1]",
@@ -3785,18 +3726,18 @@ static int tvsgm_run(srh_context *c, int slot, const srh_params *p, int L, const
 		// (nothing of the slot has been written yet: the depth map is the read-off's, after the last direction)
 		if (cancelled(c)) { HIP_TRY(hipStreamSynchronize(c->stream)); return fail(SRH_E_CANCELLED, "cancelled"); }
 		{ Scope s(c, names[k]);
-		  HIP_TRY(launch_twoview_sgm_path(c->stream, c->tvsgm, costs, w, h, L, m->lambda, m->smooth_max, k, paths == 0)); }
+		  HIP_TRY(launch_twoview_sgm_path(c->stream, c->tvsgm.scratch, costs, w, h, L, m->lambda, m->smooth_max, k, paths == 0)); }
 		++paths;
 	}
 	v.wta_flags = 0;                                            // no scan made this depth map: the WTA by-products are stale
 	{ Scope s(c, "twoview_sgm_readoff_kernel");
-	  HIP_TRY(launch_twoview_sgm_readoff(c->stream, c->d_views, slot, *p, c->tvsgm, w, h, L)); }
+	  HIP_TRY(launch_twoview_sgm_readoff(c->stream, c->d_views, slot, *p, c->tvsgm.scratch, w, h, L)); }
 	{ Scope s(c, "twoview_mrf_energy_kernel");
-	  HIP_TRY(launch_twoview_sgm_energy(c->stream, c->tvsgm, costs, w, h, L, m->lambda, m->smooth_max)); }
+	  HIP_TRY(launch_twoview_sgm_energy(c->stream, c->tvsgm.scratch, costs, w, h, L, m->lambda, m->smooth_max)); }
 	double e = 0.0;
 	HIP_TRY(hipMemcpyAsync(&e, lay.energy, sizeof(e), hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	c->tvsgm_w = w; c->tvsgm_h = h; c->tvsgm_l = L;
+	c->tvsgm.finished(w, h, L);
 	if (info) { info->paths = paths; info->energy = e; }
 	return SRH_OK;
 }
@@ -3812,24 +3753,8 @@ extern "C" int srh_twoview_sgm_aggregate(srh_context *c, int slot, const srh_par
 	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
 	HIP_TRY(hipSetDevice(c->device));
 	const ViewHost &v = c->views[slot];
-	c->tvsgm_w = c->tvsgm_h = c->tvsgm_l = 0;
-	if ((rc = tvsgm_reserve(c, v.w, v.h, L, false))) return rc;
-	c->tvsgm_own_costs = false;
+	if ((rc = tv_stage_reserve(c, TV_SGM, v.w, v.h, L, false))) return rc;
 	return tvsgm_run(c, slot, p, L, static_cast<const double *>(costs_dev), m, info);
-}
-
-// the label cost volume of ref against oth into the context's own buffer
-static int tvsgm_costs(srh_context *c, int ref, int oth, const srh_params *p)
-{
-	int rc;
-	const ViewHost &v = c->views[ref];
-	c->tvsgm_w = c->tvsgm_h = c->tvsgm_l = 0;
-	if ((rc = tvsgm_reserve(c, v.w, v.h, p->num_depth_levels, true))) return rc;
-	c->tvsgm_own_costs = true;
-	Scope s(c, "twoview_label_costs_kernel");
-	HIP_TRY(launch_twoview_label_costs(c->stream, c->d_views, ref, oth, v.w, *p, c->cost_kind == SRH_COST_SAD, 0, v.h,
-	                                   (2*p->window_radius + 1)*p->bad_ret, c->tvsgm_costs, nullptr));
-	return SRH_OK;
 }
 
 extern "C" int srh_twoview_sgm(srh_context *c, int ref, int oth, const srh_params *p, const srh_twoview_sgm_params *m, srh_sgm_info *info)
@@ -3840,8 +3765,8 @@ extern "C" int srh_twoview_sgm(srh_context *c, int ref, int oth, const srh_param
 	if ((rc = check_tvsgm_params(m, L))) return rc;
 	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
 	HIP_TRY(hipSetDevice(c->device));
-	if ((rc = tvsgm_costs(c, ref, oth, p))) return rc;
-	return tvsgm_run(c, ref, p, L, c->tvsgm_costs, m, info);
+	if ((rc = tv_stage_costs(c, TV_SGM, ref, oth, p))) return rc;
+	return tvsgm_run(c, ref, p, L, c->tvsgm.costs, m, info);
 }
 
 extern "C" int srh_twoview_compute_sgm(srh_context *c, int left, int right, const srh_params *p, const srh_twoview_sgm_params *m,
@@ -3850,55 +3775,29 @@ extern "C" int srh_twoview_compute_sgm(srh_context *c, int left, int right, cons
 	int rc;
 	if ((rc = check_label_costs(c, left, right, p))) return rc;
 	if ((rc = check_tvsgm_params(m, p->num_depth_levels))) return rc;
-	const ViewHost &L = c->views[left], &Rv = c->views[right];
-	if (L.w != Rv.w || L.h != Rv.h) return fail(SRH_E_INVALID, "TwoViewStereo needs equal-sized views");
-	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
-	// the progress steps of srh_twoview_compute_mrf, the optimiser's stage renamed
-	for (int k = 0; k < 2; ++k) {
-		const int ref = k == 0 ? left : right, oth = k == 0 ? right : left;
-		progress(c, 1 + 2*k, k == 0 ? "Computing cost volume for left image..." : "Computing cost volume for right image...");
-		HIP_TRY(hipSetDevice(c->device));
-		if ((rc = tvsgm_costs(c, ref, oth, p))) return rc;
-		if (cancelled(c)) { HIP_TRY(hipStreamSynchronize(c->stream)); return fail(SRH_E_CANCELLED, "cancelled"); }
-		progress(c, 2 + 2*k, "Aggregating...");
-		if ((rc = tvsgm_run(c, ref, p, p->num_depth_levels, c->tvsgm_costs, m, infos ? infos + k : nullptr))) return rc;
-		if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
-	}
-	progress(c, 5, "Detecting inconsistencies...");
-	if ((rc = srh_twoview_cross_check(c, left, right, p))) return rc;
-	if (c->filter_invalid && (rc = twoview_filter(c, left, right, p))) return rc;
-	if (left_out && (rc = srh_view_depth_download(c, left, left_out))) return rc;
-	if (right_out && (rc = srh_view_depth_download(c, right, right_out))) return rc;
-	if ((rc = srh_synchronize(c))) return rc;
-	progress(c, 8, "Finished!");
-	return SRH_OK;
+	return tv_stage_compute(c, TV_SGM, left, right, p, left_out, right_out, [&](int ref, int k) {
+		return tvsgm_run(c, ref, p, p->num_depth_levels, c->tvsgm.costs, m, infos ? infos + k : nullptr);
+	});
 }
 
 extern "C" int srh_twoview_sgm_dims(srh_context *c, int *w, int *h, int *L)
 {
-	if (!c) return fail(SRH_E_INVALID, "null context");
-	if (!c->tvsgm_w) return fail(SRH_E_INVALID, "no finished TwoView SGM run on this context");
-	if (w) *w = c->tvsgm_w;
-	if (h) *h = c->tvsgm_h;
-	if (L) *L = c->tvsgm_l;
-	return SRH_OK;
+	return !c ? fail(SRH_E_INVALID, "null context") : c->tvsgm.dims(w, h, L);
 }
 
 extern "C" int srh_twoview_sgm_state(srh_context *c, int bw, int bh, int bl, int32_t *labels, double *data_costs, double *sums)
 {
 	if (!c) return fail(SRH_E_INVALID, "null context");
-	if (!c->tvsgm_w) return fail(SRH_E_INVALID, "no finished TwoView SGM run on this context");
-	if (bw != c->tvsgm_w || bh != c->tvsgm_h || bl != c->tvsgm_l)
-		return fail(SRH_E_INVALID, "buffers sized for %dx%d, L = %d, the last TwoView SGM run was %dx%d, L = %d", bw, bh, bl, c->tvsgm_w, c->tvsgm_h, c->tvsgm_l);
-	if (data_costs && !c->tvsgm_own_costs)
+	if (const int rc = c->tvsgm.check_dims(bw, bh, bl)) return rc;
+	if (data_costs && !c->tvsgm.own_costs)
 		return fail(SRH_E_INVALID, "the data costs of srh_twoview_sgm_aggregate are the caller's volume: the context keeps none");
 	HIP_TRY(hipSetDevice(c->device));
-	const int w = c->tvsgm_w, h = c->tvsgm_h, L = c->tvsgm_l;
+	const int w = c->tvsgm.w, h = c->tvsgm.h, L = c->tvsgm.l;
 	const size_t n = (size_t)w*h;
 	TvSgmLayout lay;
-	twoview_sgm_layout(c->tvsgm, w, h, L, lay);
+	twoview_sgm_layout(c->tvsgm.scratch, w, h, L, lay);
 	if (labels) HIP_TRY(hipMemcpyAsync(labels, lay.ans, n*sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-	if (data_costs) HIP_TRY(hipMemcpyAsync(data_costs, c->tvsgm_costs, n*L*sizeof(double), hipMemcpyDeviceToHost, c->stream));
+	if (data_costs) HIP_TRY(hipMemcpyAsync(data_costs, c->tvsgm.costs, n*L*sizeof(double), hipMemcpyDeviceToHost, c->stream));
 	if (sums) HIP_TRY(hipMemcpyAsync(sums, lay.S, n*L*sizeof(double), hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	return SRH_OK;
