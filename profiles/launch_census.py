@@ -1,8 +1,10 @@
-"""How many times each kernel is launched by one TwoViewStereo call, on every path of the pass driver (csrc/srh_api.hip):
-the proof that a change to the driver's host code queues what its parent queued.  Every entry is one call on a fresh
-context (learnt list capacities do not leak between entries; a `compute` entry is two calls on one context, so that the
-guessed and the learnt deferred list passes both appear): {kernel name: launches} from Context.profile() and the path
-counters of Context.stats().  Writes sorted JSON: run it on two builds and compare the files byte for byte.
+"""How many times each kernel is launched by one TwoViewStereo call, on every path of the pass driver, and by the
+MultiViewStereo initial estimates of a case's views, on every path of the estimate driver (csrc/srh_api.hip): the proof
+that a change to the drivers' host code queues what its parent queued.  Every entry is one call on a fresh context (learnt
+list capacities do not leak between entries; a `compute` entry is two calls on one context, so that the guessed and the
+learnt deferred list passes both appear; a MultiViewStereo entry is the estimates of all views and one cross-check, which
+settles the views still in flight): {kernel name: launches} from Context.profile() and the path counters of
+Context.stats().  Writes sorted JSON: run it on two builds and compare the files byte for byte.
 usage: python3 profiles/launch_census.py [out.json]      (from the repository root; default profiles/launch_census.json)"""
 import json
 import os
@@ -66,8 +68,28 @@ def cost_rows(form, h):
     return lambda ctx, p: ctx.twoview_cost_rows(0, 1, p, 0, h, form)
 
 
+# the estimate driver's paths: queued on the two slots / waited for, gathers only, many bands, the one-thread-per-pixel kernel
+MVS_PATHS = [("mvs_async 1", dict(mvs_async=1)), ("mvs_async 0", dict(mvs_async=0)), ("mvs_staged 0", dict(mvs_staged=0)),
+             ("band_budget_mb 1", dict(band_budget_mb=1)), ("force_generic 1", dict(force_generic=1))]
+
+
+def mvs_views(case, peaks):
+    """the initial estimate of every view of the case (peaks: through srh_mvs_initial_estimate_peaks), then one cross-check"""
+    def run(ctx, p):
+        n = len(case["views"])
+        neigh = capi.mvs_neighbours(cases.hip_inputs(case)[0], p)
+        for v in range(n):
+            (ctx.mvs_initial_estimate_peaks if peaks else ctx.mvs_initial_estimate)(v, neigh[v], p)
+        ctx.mvs_cross_check(list(range(n)), 0, p)
+    return run
+
+
 def census():
     out = {}
+    for case in (cases.get_mvs("mvs_five_views"), SS.small_mvs(33, 7, 12, 1, False)):
+        for tag, opts in MVS_PATHS:
+            out["%s | %s | mvs all views" % (case["name"], tag)] = entry(case, opts, [mvs_views(case, False)])
+        out["%s | peaks | mvs all views" % case["name"]] = entry(case, dict(), [mvs_views(case, True)])
 
     def passes(case, tag, opts):
         for ref, oth in DIRECTIONS:

@@ -173,8 +173,7 @@ struct DevBuf {
 };
 
 // The band buffers of one pass: scratch sized by the band height, which an out-of-memory retry gives back
-// (release_band_buffers).  The context runs on its own set; the second TwoView pass (TvSlot) and the second MultiViewStereo
-// estimate in flight (MvsSlot 1) hold one each and swap it with the context's for their launches.  each() is the one list.
+// (release_band_buffers).  each() is the one list.
 struct BandBuffers {
 	DevBuf<double> wbuf;            // support windows of the band
 	DevBuf<double> cost;            // cost rows of the band
@@ -199,6 +198,15 @@ struct BandBuffers {
 	void release() { each([](auto &x) { x.release(); }); }
 	void free() { each([](auto &x) { x.free(); }); }
 };
+// What a pass writes: its band buffers, its counters and the maxima of its list kernels (4 ints).  The context owns one
+// set; the second TwoView pass (TvSlot) and the second MultiViewStereo estimate in flight (MvsSlot 1) own one each
+// (srh_context::each_scratch is the one list).  Where a pass runs: a stream and the set it writes -- every runner, launcher
+// and helper of a pass is handed its Lane (or the lane's stream) and reads neither from the context.
+struct Scratch {
+	BandBuffers band; DevBuf<Counters> cnt; DevBuf<int> span;
+	void release() { band.release(); cnt.release(); span.release(); }
+};
+struct Lane { hipStream_t stream; Scratch *mem; };
 
 // What a context keeps of one label-volume stage (an optimiser over a per-pixel label volume: TRW-S or semi-global
 // aggregation, for MultiViewStereo's peak labels or TwoViewStereo's depth labels): the stage's scratch, for TwoViewStereo the
@@ -280,9 +288,8 @@ struct MvsSlot {
 	hipStream_t stream = nullptr;
 	hipEvent_t ev = nullptr, done = nullptr;
 	int *h_maxc = nullptr;                              // pinned: longest list of the queued pass
-	bool own_buffers = false;                           // slot 1: its own band buffers and counters, swapped into the context for its launches
-	BandBuffers band;
-	DevBuf<Counters> d_cnt; DevBuf<int> d_span;
+	bool own_buffers = false;                           // slot 1: its own scratch; slot 0 runs on the context's
+	Scratch mem;
 	bool pending = false;                               // kernels queued, capacity check outstanding
 	int view = -1, nneigh = 0, y0 = 0, y1 = 0, cmax = 0;
 	int32_t neigh[SRH_MAX_NEIGH] = {0};
@@ -297,9 +304,7 @@ struct srh_context {
 	DevBuf<ViewDev> d_views;
 	DevBuf<int32_t> d_slots;
 	int32_t slots_host[SRH_MAX_VIEWS] = {0}; int slots_n = 0;   // what d_slots holds (srh_mvs_cross_check: the same list for every view of a run)
-	DevBuf<Counters> d_cnt;
-	DevBuf<int> d_span;
-	BandBuffers band;
+	Scratch mem;                                        // the context's own scratch: with `stream`, the main lane
 	hipStream_t mrf_stream[SRH_MAX_VIEWS] = { nullptr };            // one stream per view of srh_mvs_mrf_estimate_views / _sgm_
 	hipEvent_t views_go = nullptr;                                  //   which start behind this event on the context's stream
 	void *mrf_host = nullptr;                                       // pinned: per view {energy, pad, status[4]}
@@ -328,7 +333,6 @@ struct srh_context {
 	int mvs_async = 1;                                  // option "mvs_async": srh_mvs_initial_estimate queues a view on one of two side streams and returns (default); 0 = waits for each view
 	MvsSlot mvs_slot[SRH_MVS_SLOTS];
 	int mvs_turn = 0, mvs_last = -1;
-	bool in_settle = false;
 	int mvs_staged = 1;                                 // option "mvs_staged": the list cost kernel takes its windows from LDS copies of the other view where they fit (default), 0 = gathers only
 	bool list_rows = true;                              // option "list_rows": evaluate lists in row runs (srh_rows.hip)
 	void *comm = nullptr; int comm_ranks = 0, comm_rank = 0;   // RCCL communicator (srh_comm_init)
@@ -361,15 +365,13 @@ struct srh_context {
 	struct TvDefer { Counters *host = nullptr; int *span = nullptr; bool queued = false, strip = false, cert = false, lists = false, guessed = false;
 	                 int cmax = 0, smax = 0, ref = -1, oth = -1; };
 	TvDefer tv_defer[2];
-	TvDefer *defer = nullptr;
-	// ... and runs the second pass on a stream of its own with its own band buffers (swapped into the context for its
-	// launches, tv_slot_swap): the two passes share nothing but the views, and one pass alone leaves the device idle between
-	// its kernels (~10 us each, a dozen per pass), in their tails and -- the weights kernels, one wave per SIMD -- inside them
+	// ... and runs the second pass on a lane of its own (this stream, this scratch): the two passes share nothing but the
+	// views, and one pass alone leaves the device idle between its kernels (~10 us each, a dozen per pass), in their tails
+	// and -- the weights kernels, one wave per SIMD -- inside them
 	struct TvSlot {
 		hipStream_t stream = nullptr;
 		hipEvent_t go = nullptr, done = nullptr;
-		DevBuf<Counters> d_cnt; DevBuf<int> d_span;
-		BandBuffers band;
+		Scratch mem;
 	} tv_slot;
 	int tv_overlap = 1;                                 // option "tv_overlap": 0 = both passes on the context's stream, one after the other
 	int f32_form = 0;                                   // option "f32_form" (f32 mode only, not a parity mode): 1 = the one-pass sums in single precision (priced in DESIGN.md 9.0'' (i))
@@ -393,6 +395,17 @@ struct srh_context {
 	FuseCloud fuse_out = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
 	int64_t fuse_n = 0;
 	bool fuse_valid = false;
+	// where the context's own work runs, and the lists of everything a context may have in flight or hold as scratch
+	Lane main_lane() { return { stream, &mem }; }
+	Lane slot_lane(MvsSlot &S) { return { S.stream, S.own_buffers ? &S.mem : &mem }; }
+	template <class F> void each_scratch(F f) { f(mem); f(tv_slot.mem); for (MvsSlot &S : mvs_slot) f(S.mem); }
+	template <class F> void each_stream(F f) {
+		for (MvsSlot &S : mvs_slot) if (S.stream) f(S.stream);
+		if (side_stream) f(side_stream);
+		f(stream);
+		if (tv_slot.stream) f(tv_slot.stream);
+	}
+	void wait_streams() { each_stream([](hipStream_t s) { (void)hipStreamSynchronize(s); }); }
 };
 
 static bool cancelled(srh_context *c) { return c->cancel && *c->cancel; }
@@ -413,17 +426,17 @@ static int drain_profile(srh_context *c) {
 
 // bracket one kernel launch with events when profiling
 struct Scope {
-	srh_context *c; PendingEvt p; bool on;
-	Scope(srh_context *c_, const char *name, bool wanted = true) : c(c_), on(c_->profiling && wanted) {
+	srh_context *c; hipStream_t st; PendingEvt p; bool on;
+	Scope(srh_context *c_, hipStream_t st_, const char *name, bool wanted = true) : c(c_), st(st_), on(c_->profiling && wanted) {
 		if (on) {
 			p.name = name;
 			hipEventCreate(&p.a); hipEventCreate(&p.b);
-			hipEventRecord(p.a, c->stream);
+			hipEventRecord(p.a, st);
 		}
 	}
 	~Scope() {
 		if (on) {
-			hipEventRecord(p.b, c->stream);
+			hipEventRecord(p.b, st);
 			c->pending.push_back(p);
 			if (c->pending.size() > 4096) drain_profile(c);
 		}
@@ -748,13 +761,13 @@ extern "C" int srh_create(int device, srh_context **out) {
 	if (e2 != hipSuccess) { delete c; return fail(SRH_E_DEVICE, "hipStreamCreate: %s", hipGetErrorString(e2)); }
 	c->stream = c->own_stream;
 	if (c->d_views.alloc(SRH_MAX_VIEWS) != hipSuccess || c->d_slots.alloc(SRH_MAX_VIEWS) != hipSuccess ||
-	    c->d_cnt.alloc(1) != hipSuccess || c->d_span.alloc(4) != hipSuccess) {
+	    c->mem.cnt.alloc(1) != hipSuccess || c->mem.span.alloc(4) != hipSuccess) {
 		srh_destroy(c);
 		return fail(SRH_E_DEVICE, "allocating the context tables failed");
 	}
 	// ordered on the context's own (non-blocking) stream, which the null stream does not synchronise with
 	if (hipMemsetAsync(c->d_views, 0, sizeof(ViewDev)*SRH_MAX_VIEWS, c->stream) != hipSuccess ||
-	    hipMemsetAsync(c->d_cnt, 0, sizeof(Counters), c->stream) != hipSuccess ||
+	    hipMemsetAsync(c->mem.cnt, 0, sizeof(Counters), c->stream) != hipSuccess ||
 	    hipStreamSynchronize(c->stream) != hipSuccess) {
 		srh_destroy(c);
 		return fail(SRH_E_DEVICE, "initialising the context tables failed");
@@ -776,11 +789,9 @@ extern "C" void srh_destroy(srh_context *c) {
 	if (!c) return;
 	hipSetDevice(c->device);
 	if (c->own_stream) hipStreamSynchronize(c->own_stream);
-	for (MvsSlot &S : c->mvs_slot) {
-		if (S.stream) { hipStreamSynchronize(S.stream); }
-		S.pending = false;
-	}
-	if (c->side_stream) { hipStreamSynchronize(c->side_stream); hipStreamDestroy(c->side_stream); }
+	if (c->stream) c->wait_streams();
+	for (MvsSlot &S : c->mvs_slot) S.pending = false;
+	if (c->side_stream) hipStreamDestroy(c->side_stream);
 	if (c->side_go) hipEventDestroy(c->side_go);
 	if (c->side_done) hipEventDestroy(c->side_done);
 	if (c->side_tpl) hipEventDestroy(c->side_tpl);
@@ -790,22 +801,18 @@ extern "C" void srh_destroy(srh_context *c) {
 		if (S.ev) hipEventDestroy(S.ev);
 		if (S.done) hipEventDestroy(S.done);
 		if (S.h_maxc) hipHostFree(S.h_maxc);
-		S.band.release(); S.d_cnt.release(); S.d_span.release();
 	}
 	for (auto &v : c->views) free_view(v);
-	c->d_views.release(); c->d_slots.release(); c->d_cnt.release(); c->d_span.release();
-	// (every stream of the context has been waited for above: its band buffers are idle and go to the process's pool)
+	c->d_views.release(); c->d_slots.release();
+	// (every stream of the context has been waited for above: its scratch is idle and goes to the process's pool)
 	(void)hipDeviceSynchronize();
-	(void)hipStreamSynchronize(c->stream);
-	if (c->tv_slot.stream) (void)hipStreamSynchronize(c->tv_slot.stream);
-	c->band.release();
+	c->each_scratch([](Scratch &m) { m.release(); });
 	for (auto &d : c->tv_defer) { if (d.host) hipHostFree(d.host); if (d.span) hipHostFree(d.span); }
 	{
 		srh_context::TvSlot &T = c->tv_slot;
-		if (T.stream) { hipStreamSynchronize(T.stream); hipStreamDestroy(T.stream); }
+		if (T.stream) hipStreamDestroy(T.stream);
 		if (T.go) hipEventDestroy(T.go);
 		if (T.done) hipEventDestroy(T.done);
-		T.d_cnt.release(); T.d_span.release(); T.band.release();
 	}
 	c->mrf_peaks.release();
 	for (LabelStage *S : c->label_stages) S->release();
@@ -875,9 +882,7 @@ extern "C" int srh_set_option(srh_context *c, const char *name, long value) {
 	if (!strcmp(name, "debug_alloc_limit_mb")) {
 		c->alloc_limit = g_alloc_limit = value > 0 ? (size_t)value << 20 : 0;
 		// the band buffers a bigger run left behind would serve every later request without an allocation: start afresh
-		for (MvsSlot &S : c->mvs_slot) if (S.stream) HIP_TRY(hipStreamSynchronize(S.stream));
-		if (c->side_stream) HIP_TRY(hipStreamSynchronize(c->side_stream));
-		HIP_TRY(hipStreamSynchronize(c->stream));
+		c->wait_streams();
 		release_band_buffers(c);
 		return SRH_OK;
 	}
@@ -962,8 +967,8 @@ static int view_install(srh_context *c, int slot, int w, int h, const void *rgba
 	else      HIP_TRY(hipMemsetAsync(v.mask, 1, n, c->stream));
 	if (mask) v.hmask.assign(hmask, hmask + n); else v.hmask.clear();
 	v.act_valid = false;
-	{ Scope s(c, "prep_view_kernel"); launch_prep_view(c->stream, v.rgba, v.mask, w, h, v.gray, v.gray_tv); }
-	{ Scope s(c, "edge_planes_kernel"); launch_edge_planes(c->stream, v.rgba, w, h, v.edges); }
+	{ Scope s(c, c->stream, "prep_view_kernel"); launch_prep_view(c->stream, v.rgba, v.mask, w, h, v.gray, v.gray_tv); }
+	{ Scope s(c, c->stream, "edge_planes_kernel"); launch_edge_planes(c->stream, v.rgba, w, h, v.edges); }
 	launch_fill(c->stream, v.depth, n, __builtin_nan(""));
 	ViewDev d;
 	d.w = w; d.h = h; d.rgba = v.rgba; d.mask = v.mask; d.gray = v.gray; d.gray_tv = v.gray_tv; d.depth = v.depth;
@@ -1019,8 +1024,8 @@ static int scale_staged(srh_context *c, ScaleStage &st, int sw, int sh, bool has
 		if (!(scale_axis_inside(sw, dw) && scale_axis_inside(sh, dh)))
 			return fail(SRH_E_UNSUPPORTED, "%dx%d -> %dx%d: a run of the smooth scale would leave the image", sw, sh, dw, dh);
 		HIP_TRY(out.alloc((size_t)dw*dh));
-		{ Scope s(c, "premultiply_kernel"); launch_premultiply(c->stream, st.src, ns, has_alpha); }
-		{ Scope s(c, "smooth_scale_kernel"); launch_smooth_scale(c->stream, st.src, sw, sh, out, dw, dh); }
+		{ Scope s(c, c->stream, "premultiply_kernel"); launch_premultiply(c->stream, st.src, ns, has_alpha); }
+		{ Scope s(c, c->stream, "smooth_scale_kernel"); launch_smooth_scale(c->stream, st.src, sw, sh, out, dw, dh); }
 	} else {
 		std::vector<int32_t> &map = st.hmap;
 		map.assign((size_t)dw + dh, 0);
@@ -1029,7 +1034,7 @@ static int scale_staged(srh_context *c, ScaleStage &st, int sw, int sh, bool has
 		HIP_TRY(out.alloc((size_t)dw*dh));
 		HIP_TRY(st.dmap.alloc(map.size()));
 		HIP_TRY(hipMemcpyAsync(st.dmap, map.data(), map.size()*sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-		{ Scope s(c, "fast_scale_kernel"); launch_fast_scale(c->stream, st.src, sw, out, dw, dh, st.dmap, has_alpha); }
+		{ Scope s(c, c->stream, "fast_scale_kernel"); launch_fast_scale(c->stream, st.src, sw, out, dw, dh, st.dmap, has_alpha); }
 	}
 	HIP_TRY(hipGetLastError());
 	return SRH_OK;
@@ -1037,7 +1042,7 @@ static int scale_staged(srh_context *c, ScaleStage &st, int sw, int sh, bool has
 
 // the identity (dw == sw): the staged source itself becomes `out`; an opaque source gets alpha 255
 static int scale_identity(srh_context *c, ScaleStage &st, int sw, int sh, bool has_alpha, DevBuf<uint32_t> &out) {
-	if (!has_alpha) { Scope s(c, "premultiply_kernel"); launch_premultiply(c->stream, st.src, (size_t)sw*sh, false); }
+	if (!has_alpha) { Scope s(c, c->stream, "premultiply_kernel"); launch_premultiply(c->stream, st.src, (size_t)sw*sh, false); }
 	out = std::move(st.src);
 	return SRH_OK;
 }
@@ -1118,7 +1123,7 @@ extern "C" int srh_view_upload_scaled(srh_context *c, int slot, int src_w, int s
 			HIP_TRY(dmask.alloc(n));
 			// (the identity under MultiViewStereo's rule: the fast copy is the image itself)
 			const uint32_t *msrc = alpha_mask && identity ? img.p : mimg.p;
-			{ Scope s(c, "scale_mask_kernel"); launch_scale_mask(c->stream, msrc, mw, mh, alpha_mask, dmask, dw, dh); }
+			{ Scope s(c, c->stream, "scale_mask_kernel"); launch_scale_mask(c->stream, msrc, mw, mh, alpha_mask, dmask, dw, dh); }
 			hmask.resize(n);
 			HIP_TRY(hipMemcpyAsync(hmask.data(), dmask, n, hipMemcpyDeviceToHost, c->stream));
 			HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1243,8 +1248,8 @@ extern "C" int srh_view_depth_copy_from_device(srh_context *c, int slot, const v
 // ------------------------------------------------------------------ runs
 // bytes of device memory the band buffers hold now (they are re-used or re-allocated by the next run)
 static size_t held_band_bytes(srh_context *c) {
-	size_t b = c->band.bytes() + c->tv_slot.band.bytes();
-	for (MvsSlot &S : c->mvs_slot) b += S.band.bytes();
+	size_t b = 0;
+	c->each_scratch([&](Scratch &m) { b += m.band.bytes(); });
 	for (const ViewHost &v : c->views) b += v.geo5.bytes();                 // (released with the band buffers)
 	return b;
 }
@@ -1269,11 +1274,7 @@ static size_t band_budget(srh_context *c) {
 
 static void release_band_buffers(srh_context *c) {
 	pool_flush(c->device);                                        // (out of memory: the pool's blocks go back to the driver first)
-	c->band.free();
-	for (MvsSlot &S : c->mvs_slot) S.band.free();
-	// (called with everything drained; while the second TwoView pass is being queued the slot holds the FIRST pass's
-	// buffers, which may be in use: with_thinner_bands waits for that stream as well)
-	c->tv_slot.band.free();
+	c->each_scratch([](Scratch &m) { m.band.free(); });           // (called with every stream of the context drained)
 	// the geodesic_dma_kernel's second copy of the edge / tap planes (42 B per pixel and view, made on first use): memory an
 	// out-of-memory retry must be able to reclaim -- the register-staged kernel needs no such copy and serves the view until
 	// it is uploaded again
@@ -1297,10 +1298,7 @@ static int with_thinner_bands(srh_context *c, F body) {
 		// slot stays PENDING: its kernels are complete now, but its list-capacity check (mvs_settle_slot: h_maxc is pinned
 		// and stays valid) has not been made -- the retried call, or whichever entry point comes next, settles it and
 		// redoes the view if a list was cut.
-		for (MvsSlot &S : c->mvs_slot) if (S.stream) (void)hipStreamSynchronize(S.stream);
-		if (c->side_stream) (void)hipStreamSynchronize(c->side_stream);
-		(void)hipStreamSynchronize(c->stream);
-		if (c->tv_slot.stream) (void)hipStreamSynchronize(c->tv_slot.stream);   // (either of the two is the other pass's)
+		c->wait_streams();                                          // (either TwoView pass's, the slots', the side stream)
 		release_band_buffers(c);
 		c->budget_cap = used/2;
 		c->stats.band_retries += 1;
@@ -1314,17 +1312,17 @@ static int band_rows(srh_context *c, int W, int H, int T) {
 	return (int)rows;
 }
 
-// `bytes` of device memory to the host, behind everything queued on c->stream, and the wait for them
-static int read_back(srh_context *c, void *host, const void *dev, size_t bytes) {
-	HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->stream));
-	HIP_TRY(hipStreamSynchronize(c->stream));
+// `bytes` of device memory to the host, behind everything queued on `st`, and the wait for them
+static int read_back(hipStream_t st, void *host, const void *dev, size_t bytes) {
+	HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
 	return SRH_OK;
 }
 
-static int fetch_counters(srh_context *c, int used_dense) {
+static int fetch_counters(srh_context *c, const Lane &lane, int used_dense) {
 	Counters h;
 	int rc;
-	if ((rc = read_back(c, &h, c->d_cnt, sizeof(h)))) return rc;
+	if ((rc = read_back(lane.stream, &h, lane.mem->cnt, sizeof(h)))) return rc;
 	c->stats.n_pixels = (int64_t)h.n_pixels;
 	c->stats.n_eval = (int64_t)h.n_eval;
 	c->stats.n_eval_device = (int64_t)h.n_eval_device;
@@ -1391,8 +1389,8 @@ static int fetch_counters(srh_context *c, int used_dense) {
 	return SRH_OK;
 }
 
-// support windows of rows [by, by+nr) of view `ref` into c->band.wbuf
-static void run_weights(srh_context *c, int ref, int W, const srh_params &p, int by, int nr, size_t wstride,
+// support windows of rows [by, by+nr) of view `ref` into the lane's wbuf
+static void run_weights(srh_context *c, const Lane &lane, int ref, int W, const srh_params &p, int by, int nr, size_t wstride,
                         double *pconst = nullptr, bool wimg = false) {
 	if (p.weight_kind == SRH_WEIGHT_GEODESIC && !c->force_generic && wimg && c->geodma && p.window_radius == 5 && !c->views[ref].geo5_denied) {
 		// the dense path's windows: tiles by LDS-DMA from planes with their borders written out (made once per uploaded view)
@@ -1403,25 +1401,25 @@ static void run_weights(srh_context *c, int ref, int W, const srh_params &p, int
 			v.geo5_valid = false;
 		}
 		if (ok && !v.geo5_valid) {
-			Scope s(c, "geo5_planes_kernel");
-			launch_geo5_planes(c->stream, v.edges, v.gray_tv, v.mask, v.w, v.h, v.geo5);
+			Scope s(c, lane.stream, "geo5_planes_kernel");
+			launch_geo5_planes(lane.stream, v.edges, v.gray_tv, v.mask, v.w, v.h, v.geo5);
 			v.geo5_valid = true;
 		}
 		if (ok) {
-			Scope s(c, "geodesic_dma_kernel");
-			if (launch_geodesic_dma(c->stream, c->d_views, ref, W, v.geo5, p, by, nr, c->band.wbuf, pconst, c->num_cus)) return;
+			Scope s(c, lane.stream, "geodesic_dma_kernel");
+			if (launch_geodesic_dma(lane.stream, c->d_views, ref, W, v.geo5, p, by, nr, lane.mem->band.wbuf, pconst, c->num_cus)) return;
 		}
 	}
 	if (p.weight_kind == SRH_WEIGHT_GEODESIC && !c->force_generic) {
-		Scope s(c, "geodesic_reg_kernel");
-		if (launch_geodesic_reg(c->stream, c->d_views, ref, W, c->views[ref].edges, p, by, nr, c->band.wbuf, wstride, pconst, wimg)) return;
+		Scope s(c, lane.stream, "geodesic_reg_kernel");
+		if (launch_geodesic_reg(lane.stream, c->d_views, ref, W, c->views[ref].edges, p, by, nr, lane.mem->band.wbuf, wstride, pconst, wimg)) return;
 	}
 	if (p.weight_kind == SRH_WEIGHT_ADAPTIVE && !c->force_generic) {
-		Scope s(c, "adaptive_reg_kernel");
-		if (launch_adaptive_reg(c->stream, c->d_views, ref, W, p, by, nr, c->band.wbuf, wstride, pconst, wimg)) return;
+		Scope s(c, lane.stream, "adaptive_reg_kernel");
+		if (launch_adaptive_reg(lane.stream, c->d_views, ref, W, p, by, nr, lane.mem->band.wbuf, wstride, pconst, wimg)) return;
 	}
-	Scope s(c, "weights_kernel");
-	launch_weights(c->stream, c->d_views, ref, W, p, by, nr, c->band.wbuf, wstride, pconst, wimg);
+	Scope s(c, lane.stream, "weights_kernel");
+	launch_weights(lane.stream, c->d_views, ref, W, p, by, nr, lane.mem->band.wbuf, wstride, pconst, wimg);
 }
 
 // Can every epipolar curve of `a` in `b` stay on its own image row?  Undistorted, non-refractive
@@ -1445,15 +1443,15 @@ static bool rig_is_row_aligned(const srh_camera &a, const srh_camera &b, double 
 // the same kind left (a pass over some rows writes those rows only, as it does in the depth map) or the "none" values.
 // Allocated like the view's other planes; a refusal is a clean SRH_E_DEVICE before the pass queues anything.  Option off:
 // no allocation, no launch -- the slot's planes, if any, no longer describe its depth map.
-static int ensure_wta_planes(srh_context *c, int ref, int oth) {
+static int ensure_wta_planes(srh_context *c, hipStream_t st, int ref, int oth) {
 	ViewHost &v = c->views[ref];
 	if (!c->wta_outputs) { v.wta_flags = 0; return SRH_OK; }
 	const size_t n = (size_t)v.w*v.h;
 	if (v.wta_flags == c->wta_outputs && v.wta_oth == oth) return SRH_OK;
 	if (!v.wta_xy) HIP_TRY(v.wta_xy.alloc(4*n));
 	if ((c->wta_outputs & SRH_WTA_COSTS) && !v.wta_cost) HIP_TRY(v.wta_cost.alloc(2*n));
-	HIP_TRY(hipMemsetAsync(v.wta_xy, 0xff, 4*n*sizeof(int32_t), c->stream));           // (-1, -1): no winner, no runner-up
-	if (c->wta_outputs & SRH_WTA_COSTS) launch_fill(c->stream, v.wta_cost, 2*n, __builtin_inf());
+	HIP_TRY(hipMemsetAsync(v.wta_xy, 0xff, 4*n*sizeof(int32_t), st));           // (-1, -1): no winner, no runner-up
+	if (c->wta_outputs & SRH_WTA_COSTS) launch_fill(st, v.wta_cost, 2*n, __builtin_inf());
 	v.wta_flags = c->wta_outputs; v.wta_oth = oth;
 	return SRH_OK;
 }
@@ -1512,56 +1510,56 @@ static void estimate_list_capacity(const srh_camera &rc, const srh_camera &oc, i
 }
 
 // The NaN-bordered gray_tv plane of a view (the strip kernels' taps; the general cost of the left-out columns and of the
-// certified redo reads it without bound tests), made on first use after an upload, on c->stream
-static int ensure_tvp(srh_context *c, ViewHost &v) {
+// certified redo reads it without bound tests), made on first use after an upload, on `st`
+static int ensure_tvp(srh_context *c, hipStream_t st, ViewHost &v) {
 	if (!v.tvp) HIP_TRY(v.tvp.alloc(padded_size(v.w, v.h)));
 	if (!v.tvp_valid) {
-		Scope s(c, "padded_plane_kernel");
-		launch_padded_plane(c->stream, v.gray_tv, v.w, v.h, v.tvp);
+		Scope s(c, st, "padded_plane_kernel");
+		launch_padded_plane(st, v.gray_tv, v.w, v.h, v.tvp);
 		v.tvp_valid = true;
 	}
 	return SRH_OK;
 }
 
 // cost_sad's "window fully usable" plane of radius R (its zero-bordered copy, if any, is stale then)
-static int ensure_fulls(srh_context *c, ViewHost &v, int R) {
+static int ensure_fulls(srh_context *c, hipStream_t st, ViewHost &v, int R) {
 	if (v.fulls_r == R) return SRH_OK;
 	if (!v.fulls) HIP_TRY(v.fulls.alloc((size_t)v.w*v.h));
-	Scope s(c, "sad_full_window_kernel");
-	launch_sad_full_window(c->stream, v.mask, v.w, v.h, R, v.fulls);
+	Scope s(c, st, "sad_full_window_kernel");
+	launch_sad_full_window(st, v.mask, v.w, v.h, R, v.fulls);
 	v.fulls_r = R;
 	v.fullsp_r = 0;
 	return SRH_OK;
 }
 
 // cost_ncc's "window fully usable" plane of radius R, with its two counts behind it (option "rows_masked")
-static int ensure_full(srh_context *c, ViewHost &v, int R) {
+static int ensure_full(srh_context *c, hipStream_t st, ViewHost &v, int R) {
 	if (v.full_r == R) return SRH_OK;
-	Scope s(c, "full_window_kernel");
+	Scope s(c, st, "full_window_kernel");
 	uint32_t *stat = (uint32_t *)(v.full + full_stat_offset((size_t)v.w*v.h));
-	HIP_TRY(hipMemsetAsync(stat, 0, 2*sizeof(uint32_t), c->stream));
-	launch_full_window(c->stream, v.gray_tv, v.w, v.h, R, v.full, stat);
+	HIP_TRY(hipMemsetAsync(stat, 0, 2*sizeof(uint32_t), st));
+	launch_full_window(st, v.gray_tv, v.w, v.h, R, v.full, stat);
 	v.full_r = R;
 	return SRH_OK;
 }
 
-// The planes twoview_strip_sad_kernel stages from (option "sad_dense"), made on first use after an upload, on c->stream:
+// The planes twoview_strip_sad_kernel stages from (option "sad_dense"), made on first use after an upload, on `st`:
 // the NaN-bordered gray_tv plane (the reference side's taps), the NaN-bordered masked gray plane (the other side's) and the
 // zero-bordered copy of cost_sad's "window fully usable" plane of radius R
-static int ensure_sad_planes(srh_context *c, ViewHost &v, int R) {
+static int ensure_sad_planes(srh_context *c, hipStream_t st, ViewHost &v, int R) {
 	int rc;
-	if ((rc = ensure_tvp(c, v))) return rc;
+	if ((rc = ensure_tvp(c, st, v))) return rc;
 	if (!v.grayp) HIP_TRY(v.grayp.alloc(padded_size(v.w, v.h)));
 	if (!v.grayp_valid) {
-		Scope s(c, "padded_gray_kernel");
-		launch_padded_gray(c->stream, v.gray, v.mask, v.w, v.h, v.grayp);
+		Scope s(c, st, "padded_gray_kernel");
+		launch_padded_gray(st, v.gray, v.mask, v.w, v.h, v.grayp);
 		v.grayp_valid = true;
 	}
-	if ((rc = ensure_fulls(c, v, R))) return rc;
+	if ((rc = ensure_fulls(c, st, v, R))) return rc;
 	if (!v.fullsp) HIP_TRY(v.fullsp.alloc(padded_size(v.w, v.h)));
 	if (v.fullsp_r != R) {
-		Scope s(c, "padded_bytes_kernel");
-		launch_padded_bytes(c->stream, v.fulls, v.w, v.h, v.fullsp);
+		Scope s(c, st, "padded_bytes_kernel");
+		launch_padded_bytes(st, v.fulls, v.w, v.h, v.fullsp);
 		v.fullsp_r = R;
 	}
 	return SRH_OK;
@@ -1585,12 +1583,14 @@ struct TvDense { int cstride = 0; bool strip = false, cert = false, tscan = fals
                  bool tables_pending = false, tpl_wait = false; };
 
 // One pass ref -> oth over rows [y0, y1) of equal-sized views (clamped to the view: y1 <= y0, nothing to do): what every
-// runner needs.  R, T: window radius and taps; budget: bytes of band scratch.
+// runner needs.  lane: the stream the pass is queued on and the scratch it writes; R, T: window radius and taps; budget:
+// bytes of band scratch.
 // wout, the by-products of the scan (option "wta_outputs"): every scan kernel of the pass stores winner and runner-up where
 // it stores the depth, and twoview_winner_costs_kernel follows the band's last scan with their exact costs.  A repeated
 // attempt rewrites every row of the pass, so the planes hold what the attempt whose depth map stands wrote.
 struct TvPass {
 	srh_context *c = nullptr;
+	Lane lane = { nullptr, nullptr };
 	int ref = 0, oth = 0;
 	const srh_params *p = nullptr;
 	int W = 0, H = 0, y0 = 0, y1 = 0, R = 0, T = 0;
@@ -1607,7 +1607,7 @@ struct TvPass {
 	int lists_pass(TvLists &S) const;
 	int run_lists(bool cert_ok, srh_context::TvDefer *defer) const;
 	int dense_prepare(TvDense &D) const;
-	void dense_tables(const TvDense &D, bool table, bool tpl) const;
+	void dense_tables(const Lane &on, const TvDense &D, bool table, bool tpl) const;
 	bool dense_fill_padded(const TvDense &D, int arith) const;
 	int dense_band_inputs(TvDense &D, int by, int nr, int arith) const;
 	int dense_cost_pass(const TvDense &D, int by, int nr, int arith, bool raw) const;
@@ -1615,14 +1615,14 @@ struct TvPass {
 	int run_walk() const;
 };
 
-static int tv_pass_init(TvPass &P, srh_context *c, int ref, int oth, const srh_params *p, int y0, int y1) {
+static int tv_pass_init(TvPass &P, srh_context *c, const Lane &lane, int ref, int oth, const srh_params *p, int y0, int y1) {
 	if (ref == oth) return fail(SRH_E_INVALID, "ref and other view are the same slot");
 	const ViewHost &L = c->views[ref], &Rv = c->views[oth];
 	if (L.w != Rv.w || L.h != Rv.h)
 		return fail(SRH_E_INVALID, "TwoViewStereo needs equal-sized views (%dx%d vs %dx%d; twoviewstereo.cpp:116-119)",
 		            L.w, L.h, Rv.w, Rv.h);
 	HIP_TRY(hipSetDevice(c->device));
-	P.c = c; P.ref = ref; P.oth = oth; P.p = p;
+	P.c = c; P.lane = lane; P.ref = ref; P.oth = oth; P.p = p;
 	P.W = L.w; P.H = L.h;
 	P.y0 = y0 < 0 ? 0 : y0;
 	P.y1 = (y1 <= 0 || y1 > P.H) ? P.H : y1;
@@ -1640,9 +1640,9 @@ size_t TvPass::rows_per_band(size_t bytes) const {
 
 void TvPass::winner_costs(int by, int nr, bool wimg_layout) const {
 	if (!wout || !(c->wta_outputs & SRH_WTA_COSTS)) return;
-	Scope s(c, "twoview_winner_costs_kernel");
+	Scope s(c, lane.stream, "twoview_winner_costs_kernel");
 	double *mc = c->views[ref].wta_cost;
-	launch_twoview_winner_costs(c->stream, c->d_views, ref, oth, W, *p, sad, by, nr, c->band.wbuf, wimg_layout,
+	launch_twoview_winner_costs(lane.stream, c->d_views, ref, oth, W, *p, sad, by, nr, lane.mem->band.wbuf, wimg_layout,
 	                            wout, mc, mc + (size_t)W*H);
 }
 
@@ -1689,25 +1689,25 @@ TvPlan TvPass::plan() const {
 int TvPass::run_fused(bool &stands) const {
 	int rc;
 	stands = false;
-	HIP_TRY(hipMemsetAsync(c->d_cnt, 0, sizeof(Counters), c->stream));
-	if ((rc = c->band.tnum.ensure((size_t)p->num_depth_levels))) return rc;
-	{ Scope s(c, "pinhole_label_table_kernel");
-	  launch_pinhole_label_table(c->stream, c->d_views, ref, *p, false, c->band.tnum); }
+	HIP_TRY(hipMemsetAsync(lane.mem->cnt, 0, sizeof(Counters), lane.stream));
+	if ((rc = lane.mem->band.tnum.ensure((size_t)p->num_depth_levels))) return rc;
+	{ Scope s(c, lane.stream, "pinhole_label_table_kernel");
+	  launch_pinhole_label_table(lane.stream, c->d_views, ref, *p, false, lane.mem->band.tnum); }
 	const int rows = (int)rows_per_band((size_t)T*sizeof(double));
-	if ((rc = c->band.wbuf.ensure(wbuf_doubles(W, rows, T)))) return rc;
+	if ((rc = lane.mem->band.wbuf.ensure(wbuf_doubles(W, rows, T)))) return rc;
 	bool launched = true;
 	for (int by = y0; by < y1 && launched; by += rows) {
 		if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
 		const int nr = std::min(rows, y1 - by);
-		run_weights(c, ref, W, *p, by, nr, SRH_WTILE);
-		Scope s(c, "twoview_fused_kernel");
-		launched = launch_twoview_fused(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, c->band.tnum, c->d_cnt, wout);
+		run_weights(c, lane, ref, W, *p, by, nr, SRH_WTILE);
+		Scope s(c, lane.stream, "twoview_fused_kernel");
+		launched = launch_twoview_fused(lane.stream, c->d_views, ref, oth, W, *p, by, nr, lane.mem->band.wbuf, lane.mem->band.tnum, lane.mem->cnt, wout);
 		if (launched) winner_costs(by, nr, false);
 	}
 	HIP_TRY(hipGetLastError());
 	if (!launched) return SRH_OK;
 	Counters hc;
-	if ((rc = read_back(c, &hc, c->d_cnt, sizeof(hc)))) return rc;
+	if ((rc = read_back(lane.stream, &hc, lane.mem->cnt, sizeof(hc)))) return rc;
 	stands = hc.not_row_aligned == 0;
 	return SRH_OK;
 }
@@ -1715,7 +1715,7 @@ int TvPass::run_fused(bool &stands) const {
 // ---- arbitrary geometry: candidate lists, evaluated in row runs (srh_rows.hip) or in list order (srh_list.hip)
 
 // every list and every pixel's cost slots fitted the capacities, no curve crossed more than SRH_ROWS_NR rows
-// (mx: the kernels' maxima in d_span -- longest list, most cost slots, a curve over too many rows)
+// (mx: the kernels' maxima in the lane's span -- longest list, most cost slots, a curve over too many rows)
 static bool tv_lists_fit(const int *mx, int cmax, int smax) {
 	return mx[0] <= cmax && ((mx[1] + 7) & ~7) <= smax && mx[2] == 0;
 }
@@ -1734,9 +1734,9 @@ static void tv_learn_lists(srh_context *c, int ref, int oth, bool guessed, int c
 
 // srh_twoview_compute's optimistic passes: the counters (lists: and the kernels' maxima) travel to pinned memory behind
 // the kernels, and the record says what the pass stood on; the caller verifies both passes with one wait (tv_pass_stands)
-static int tv_defer_queue(srh_context *c, srh_context::TvDefer &d, bool lists, bool strip, bool cert) {
-	HIP_TRY(hipMemcpyAsync(d.host, c->d_cnt, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
-	if (lists) HIP_TRY(hipMemcpyAsync(d.span, c->d_span, 4*sizeof(int), hipMemcpyDeviceToHost, c->stream));
+static int tv_defer_queue(const Lane &lane, srh_context::TvDefer &d, bool lists, bool strip, bool cert) {
+	HIP_TRY(hipMemcpyAsync(d.host, lane.mem->cnt, sizeof(Counters), hipMemcpyDeviceToHost, lane.stream));
+	if (lists) HIP_TRY(hipMemcpyAsync(d.span, lane.mem->span, 4*sizeof(int), hipMemcpyDeviceToHost, lane.stream));
 	d.queued = true; d.lists = lists; d.strip = strip; d.cert = cert;
 	return SRH_OK;
 }
@@ -1744,13 +1744,13 @@ static int tv_defer_queue(srh_context *c, srh_context::TvDefer &d, bool lists, b
 // what no pass of the lists repeats: the other view's "window fully usable" plane, the label table, the first capacities
 int TvPass::lists_prepare(TvLists &S) const {
 	int rc;
-	if ((rc = c->band.lcount.ensure((size_t)(y1 - y0)*W))) return rc;
+	if ((rc = lane.mem->band.lcount.ensure((size_t)(y1 - y0)*W))) return rc;
 	ViewHost &O = c->views[oth];
-	if ((rc = sad ? ensure_fulls(c, O, R) : ensure_full(c, O, R))) return rc;
+	if ((rc = sad ? ensure_fulls(c, lane.stream, O, R) : ensure_full(c, lane.stream, O, R))) return rc;
 	// the label-only part of pointFromDepth, once per pass instead of once per pixel and label
-	if ((rc = c->band.tnum.ensure((size_t)p->num_depth_levels))) return rc;
-	{ Scope s(c, "label_plane_table_kernel");
-	  launch_label_plane_table(c->stream, c->d_views, ref, *p, false, c->band.tnum); }
+	if ((rc = lane.mem->band.tnum.ensure((size_t)p->num_depth_levels))) return rc;
+	{ Scope s(c, lane.stream, "label_plane_table_kernel");
+	  launch_label_plane_table(lane.stream, c->d_views, ref, *p, false, lane.mem->band.tnum); }
 	// list capacity: the longest list seen so far on this context (hint); the FIRST time a guess from the geometry
 	// (estimate_list_capacity: a few dozen curves' coarse polylines projected on the host -- round 5 ran a counting pass
 	// there, twoview_count_kernel, 10 ms of a C5 pair's first call, and then sized the slots too tightly, so that the
@@ -1759,11 +1759,11 @@ int TvPass::lists_prepare(TvLists &S) const {
 	int smax_guess = 0;
 	S.cmax = c->list_cmax_hint;
 	if (S.cmax <= 0 && c->list_count_pass) {
-		HIP_TRY(hipMemsetAsync(c->d_span, 0, sizeof(int), c->stream));
-		{ Scope s(c, "twoview_count_kernel");
-		  launch_twoview_count(c->stream, c->d_views, ref, oth, W, *p, y0, y1 - y0, c->band.lcount, c->d_cnt, c->d_span, c->band.tnum); }
+		HIP_TRY(hipMemsetAsync(lane.mem->span, 0, sizeof(int), lane.stream));
+		{ Scope s(c, lane.stream, "twoview_count_kernel");
+		  launch_twoview_count(lane.stream, c->d_views, ref, oth, W, *p, y0, y1 - y0, lane.mem->band.lcount, lane.mem->cnt, lane.mem->span, lane.mem->band.tnum); }
 		int maxc = 0;
-		if ((rc = read_back(c, &maxc, c->d_span, sizeof(int)))) return rc;
+		if ((rc = read_back(lane.stream, &maxc, lane.mem->span, sizeof(int)))) return rc;
 		S.cmax = std::max(8, (maxc + 7) & ~7);
 	} else if (S.cmax <= 0) {
 		estimate_list_capacity(c->views[ref].cam, O.cam, W, H, O.w, O.h, *p, y0, y1, S.cmax, smax_guess);
@@ -1778,10 +1778,10 @@ int TvPass::lists_prepare(TvLists &S) const {
 // one band of the row-run lists: list kernel, support windows beside it, cost, scan, the certified redo
 int TvPass::lists_rows_band(const TvLists &S, int by, int nr) const {
 	ViewHost &O = c->views[oth];
-	int32_t *cnt_band = c->band.lcount + (size_t)(by - y0)*W;
+	int32_t *cnt_band = lane.mem->band.lcount + (size_t)(by - y0)*W;
 	// the row-run cost kernel takes the pixels' constants (meanL, totalWeight, sum2, 1/totalWeight, SA) from the weights
 	// kernel, which has the window in registers anyway, instead of making them on one lane in eight per tile
-	double *pconst = sad ? nullptr : (double *)c->band.pconst;
+	double *pconst = sad ? nullptr : (double *)lane.mem->band.pconst;
 	// The list kernel does not need the support windows, and its last waves drain for long (a wave walks
 	// its 64 curves for ~2 ms): the windows are computed on a side stream queued behind it -- the geodesic
 	// kernel's register-heavy waves only find room on a SIMD once the list kernel's have left it.
@@ -1790,44 +1790,42 @@ int TvPass::lists_rows_band(const TvLists &S, int by, int nr) const {
 		HIP_TRY(hipEventCreateWithFlags(&c->side_go, hipEventDisableTiming));
 		HIP_TRY(hipEventCreateWithFlags(&c->side_done, hipEventDisableTiming));
 	}
-	HIP_TRY(hipEventRecord(c->side_go, c->stream));               // the window buffer's last readers are done by then
-	{ Scope s(c, "twoview_rows_list_kernel");
-	  launch_twoview_rows_list(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.lcand, S.cmax,
-	                           cnt_band, c->band.lrowinfo, c->band.lmeta, S.smax, c->d_cnt, c->d_span, c->band.tnum); }
+	HIP_TRY(hipEventRecord(c->side_go, lane.stream));               // the window buffer's last readers are done by then
+	{ Scope s(c, lane.stream, "twoview_rows_list_kernel");
+	  launch_twoview_rows_list(lane.stream, c->d_views, ref, oth, W, *p, by, nr, lane.mem->band.lcand, S.cmax,
+	                           cnt_band, lane.mem->band.lrowinfo, lane.mem->band.lmeta, S.smax, lane.mem->cnt, lane.mem->span, lane.mem->band.tnum); }
 	if (c->side_weights) {
 		HIP_TRY(hipStreamWaitEvent(c->side_stream, c->side_go, 0));
-		std::swap(c->stream, c->side_stream);                     // (Scope and the launchers read c->stream)
-		run_weights(c, ref, W, *p, by, nr, SRH_WTILE, pconst, true);
-		std::swap(c->stream, c->side_stream);
+		run_weights(c, { c->side_stream, lane.mem }, ref, W, *p, by, nr, SRH_WTILE, pconst, true);
 		HIP_TRY(hipEventRecord(c->side_done, c->side_stream));
-		HIP_TRY(hipStreamWaitEvent(c->stream, c->side_done, 0));
-	} else run_weights(c, ref, W, *p, by, nr, SRH_WTILE, pconst, true);
-	if (S.cert) HIP_TRY(hipMemsetAsync(c->band.cflag, 0, sizeof(uint32_t), c->stream));
-	HIP_TRY(hipMemsetAsync(&c->d_cnt->strip_ticket, 0, 2*sizeof(unsigned int), c->stream));   // the cost kernel's waves draw their tiles from it
+		HIP_TRY(hipStreamWaitEvent(lane.stream, c->side_done, 0));
+	} else run_weights(c, lane, ref, W, *p, by, nr, SRH_WTILE, pconst, true);
+	if (S.cert) HIP_TRY(hipMemsetAsync(lane.mem->band.cflag, 0, sizeof(uint32_t), lane.stream));
+	HIP_TRY(hipMemsetAsync(&lane.mem->cnt->strip_ticket, 0, 2*sizeof(unsigned int), lane.stream));   // the cost kernel's waves draw their tiles from it
 	if (sad) {
-		Scope s(c, "twoview_rows_sad_kernel");
-		launch_twoview_rows_sad(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, O.fulls,
-		                        c->band.lrowinfo, c->band.lmeta, c->band.cost, S.smax, c->d_cnt);
+		Scope s(c, lane.stream, "twoview_rows_sad_kernel");
+		launch_twoview_rows_sad(lane.stream, c->d_views, ref, oth, W, *p, by, nr, lane.mem->band.wbuf, O.fulls,
+		                        lane.mem->band.lrowinfo, lane.mem->band.lmeta, lane.mem->band.cost, S.smax, lane.mem->cnt);
 	} else {
-		Scope s(c, "twoview_rows_cost_kernel");
-		launch_twoview_rows_cost(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, O.full,
-		                         c->band.lrowinfo, c->band.lmeta, c->band.cost, S.smax, c->d_cnt, S.cert ? (c->cert_form == 1 ? 5 : 3) : 0,
+		Scope s(c, lane.stream, "twoview_rows_cost_kernel");
+		launch_twoview_rows_cost(lane.stream, c->d_views, ref, oth, W, *p, by, nr, lane.mem->band.wbuf, O.full,
+		                         lane.mem->band.lrowinfo, lane.mem->band.lmeta, lane.mem->band.cost, S.smax, lane.mem->cnt, S.cert ? (c->cert_form == 1 ? 5 : 3) : 0,
 		                         pconst, S.cert && c->rows_masked ? O.tvp : nullptr, c->num_cus,
 		                         c->rows_masked == 1 ? (const uint32_t *)(O.full + full_stat_offset((size_t)O.w*O.h)) : nullptr);
 	}
-	{ Scope s(c, "twoview_rows_scan_kernel");
-	  launch_twoview_rows_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, cnt_band, c->band.lcand, S.cmax,
-	                           c->band.lrowinfo, c->band.lmeta, c->band.cost, S.smax, S.cert ? c->band.cflag : nullptr, -1, c->d_cnt, wout); }
+	{ Scope s(c, lane.stream, "twoview_rows_scan_kernel");
+	  launch_twoview_rows_scan(lane.stream, c->d_views, ref, oth, W, *p, by, nr, cnt_band, lane.mem->band.lcand, S.cmax,
+	                           lane.mem->band.lrowinfo, lane.mem->band.lmeta, lane.mem->band.cost, S.smax, S.cert ? lane.mem->band.cflag : nullptr, -1, lane.mem->cnt, wout); }
 	if (S.cert) {
 		// certified arithmetic: the flagged pixels once more in the reference's arithmetic, launched for a capacity
 		// (a list cut by a too small capacity is harmless here: the pass is repeated anyway)
 		const int cap = redo_capacity((size_t)nr*W);
-		{ Scope s(c, "twoview_rows_refill_kernel");
-		  launch_twoview_rows_refill(c->stream, W, O.w, *p, by, c->band.cflag, cap, c->band.wbuf, c->views[ref].tvp, O.tvp,
-		                             c->band.lrowinfo, c->band.lmeta, c->band.cost, S.smax, c->d_cnt); }
-		Scope s(c, "twoview_rows_rescan_kernel");
-		launch_twoview_rows_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, cnt_band, c->band.lcand, S.cmax,
-		                         c->band.lrowinfo, c->band.lmeta, c->band.cost, S.smax, c->band.cflag, cap, c->d_cnt, wout);
+		{ Scope s(c, lane.stream, "twoview_rows_refill_kernel");
+		  launch_twoview_rows_refill(lane.stream, W, O.w, *p, by, lane.mem->band.cflag, cap, lane.mem->band.wbuf, c->views[ref].tvp, O.tvp,
+		                             lane.mem->band.lrowinfo, lane.mem->band.lmeta, lane.mem->band.cost, S.smax, lane.mem->cnt); }
+		Scope s(c, lane.stream, "twoview_rows_rescan_kernel");
+		launch_twoview_rows_scan(lane.stream, c->d_views, ref, oth, W, *p, by, nr, cnt_band, lane.mem->band.lcand, S.cmax,
+		                         lane.mem->band.lrowinfo, lane.mem->band.lmeta, lane.mem->band.cost, S.smax, lane.mem->band.cflag, cap, lane.mem->cnt, wout);
 	}
 	winner_costs(by, nr, true);
 	return SRH_OK;
@@ -1836,8 +1834,8 @@ int TvPass::lists_rows_band(const TvLists &S, int by, int nr) const {
 // one pass of the lists with the capacities and in the mode of S: counters and maxima reset, buffers, every band queued
 int TvPass::lists_pass(TvLists &S) const {
 	int rc;
-	HIP_TRY(hipMemsetAsync(c->d_cnt, 0, sizeof(Counters), c->stream));
-	HIP_TRY(hipMemsetAsync(c->d_span, 0, 4*sizeof(int), c->stream));
+	HIP_TRY(hipMemsetAsync(lane.mem->cnt, 0, sizeof(Counters), lane.stream));
+	HIP_TRY(hipMemsetAsync(lane.mem->span, 0, 4*sizeof(int), lane.stream));
 	const bool rows_mode = S.rows_mode;
 	const int ccap = rows_mode ? S.smax : S.cmax;                 // cost values per pixel
 	// (row runs: the windows in the LDS-image layout, window rows padded to an even tap count -- the cost kernel's
@@ -1845,18 +1843,18 @@ int TvPass::lists_pass(TvLists &S) const {
 	const size_t per_px = (size_t)(rows_mode ? (2*R + 1)*wimg_wp(R) : T)*sizeof(double) + (size_t)ccap*sizeof(double) + (size_t)S.cmax*sizeof(uint32_t)
 	                      + (rows_mode ? (SRH_ROWS_NR + 1)*sizeof(uint32_t) : 0);
 	const size_t lrows = S.lrows = rows_per_band(per_px);
-	if ((rc = c->band.wbuf.ensure(rows_mode ? wimg_doubles(W, (int)lrows, R) : wbuf_doubles(W, (int)lrows, T)))) return rc;
+	if ((rc = lane.mem->band.wbuf.ensure(rows_mode ? wimg_doubles(W, (int)lrows, R) : wbuf_doubles(W, (int)lrows, T)))) return rc;
 	// row runs: lists and row tables are tiled per 64 pixels, cost slots per 32-pixel tile of a row
 	const size_t px64 = (lrows*W + 63) & ~(size_t)63, px32 = lrows*(size_t)((W + 7)/8)*8;        /* (cost slots: tiles of 8 pixels) */
-	if ((rc = c->band.cost.ensure((rows_mode ? px32 : lrows*W)*(size_t)ccap))) return rc;
-	if ((rc = c->band.lcand.ensure((rows_mode ? px64 : lrows*W)*(size_t)S.cmax))) return rc;
-	if (rows_mode && !sad && (rc = c->band.pconst.ensure((lrows*(size_t)W + SRH_WTILE)*SRH_PC))) return rc;
+	if ((rc = lane.mem->band.cost.ensure((rows_mode ? px32 : lrows*W)*(size_t)ccap))) return rc;
+	if ((rc = lane.mem->band.lcand.ensure((rows_mode ? px64 : lrows*W)*(size_t)S.cmax))) return rc;
+	if (rows_mode && !sad && (rc = lane.mem->band.pconst.ensure((lrows*(size_t)W + SRH_WTILE)*SRH_PC))) return rc;
 	if (rows_mode) {
-		if ((rc = c->band.lrowinfo.ensure(px64*(size_t)SRH_ROWS_NR))) return rc;
-		if ((rc = c->band.lmeta.ensure(lrows*W))) return rc;
-		if (S.cert && (rc = c->band.cflag.ensure(lrows*W + 1))) return rc;
+		if ((rc = lane.mem->band.lrowinfo.ensure(px64*(size_t)SRH_ROWS_NR))) return rc;
+		if ((rc = lane.mem->band.lmeta.ensure(lrows*W))) return rc;
+		if (S.cert && (rc = lane.mem->band.cflag.ensure(lrows*W + 1))) return rc;
 		// NaN-bordered planes of both views: the general cost of the certified redo reads them without bound tests
-		if (S.cert && ((rc = ensure_tvp(c, c->views[ref])) || (rc = ensure_tvp(c, c->views[oth])))) return rc;
+		if (S.cert && ((rc = ensure_tvp(c, lane.stream, c->views[ref])) || (rc = ensure_tvp(c, lane.stream, c->views[oth])))) return rc;
 	}
 	for (int by = y0; by < y1; by += (int)lrows) {
 		if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
@@ -1865,22 +1863,22 @@ int TvPass::lists_pass(TvLists &S) const {
 			if ((rc = lists_rows_band(S, by, nr))) return rc;
 			continue;
 		}
-			int32_t *cnt_band = c->band.lcount + (size_t)(by - y0)*W;
-			run_weights(c, ref, W, *p, by, nr, SRH_WTILE);
-			{ Scope s(c, "twoview_list_kernel");
-			  launch_twoview_list(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.lcand, S.cmax,
-			                      cnt_band, c->d_cnt, c->d_span, c->band.tnum); }
+			int32_t *cnt_band = lane.mem->band.lcount + (size_t)(by - y0)*W;
+			run_weights(c, lane, ref, W, *p, by, nr, SRH_WTILE);
+			{ Scope s(c, lane.stream, "twoview_list_kernel");
+			  launch_twoview_list(lane.stream, c->d_views, ref, oth, W, *p, by, nr, lane.mem->band.lcand, S.cmax,
+			                      cnt_band, lane.mem->cnt, lane.mem->span, lane.mem->band.tnum); }
 			if (sad) {
-				Scope s(c, "twoview_list_sad_kernel");
-				launch_twoview_list_sad(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf,
-				                        cnt_band, c->band.lcand, c->band.cost, S.cmax, c->d_cnt);
+				Scope s(c, lane.stream, "twoview_list_sad_kernel");
+				launch_twoview_list_sad(lane.stream, c->d_views, ref, oth, W, *p, by, nr, lane.mem->band.wbuf,
+				                        cnt_band, lane.mem->band.lcand, lane.mem->band.cost, S.cmax, lane.mem->cnt);
 			} else {
-				Scope s(c, "twoview_list_cost_kernel");
-				launch_twoview_list_cost(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, c->views[oth].full,
-				                         cnt_band, c->band.lcand, c->band.cost, S.cmax, c->d_cnt);
+				Scope s(c, lane.stream, "twoview_list_cost_kernel");
+				launch_twoview_list_cost(lane.stream, c->d_views, ref, oth, W, *p, by, nr, lane.mem->band.wbuf, c->views[oth].full,
+				                         cnt_band, lane.mem->band.lcand, lane.mem->band.cost, S.cmax, lane.mem->cnt);
 			}
-			{ Scope s(c, "twoview_list_scan_kernel");
-			  launch_twoview_list_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, cnt_band, c->band.lcand, c->band.cost, S.cmax, wout); }
+			{ Scope s(c, lane.stream, "twoview_list_scan_kernel");
+			  launch_twoview_list_scan(lane.stream, c->d_views, ref, oth, W, *p, by, nr, cnt_band, lane.mem->band.lcand, lane.mem->band.cost, S.cmax, wout); }
 			winner_costs(by, nr, false);
 	}
 	return SRH_OK;
@@ -1903,7 +1901,7 @@ int TvPass::run_lists(bool cert_ok, srh_context::TvDefer *defer) const {
 			// optimistic: capacities and path are those earlier runs of this pair learnt -- or, for a pair's FIRST call, the
 			// host's guess and the row-run path -- (a pass that does not stand -- a longer list after a re-upload, say -- is
 			// redone with the wait per pass)
-			if ((rc = tv_defer_queue(c, *defer, true, false, S.cert))) return rc;
+			if ((rc = tv_defer_queue(lane, *defer, true, false, S.cert))) return rc;
 			defer->cmax = S.cmax; defer->smax = S.smax;
 			defer->guessed = S.guessed; defer->ref = ref; defer->oth = oth;
 			if (c->debug_trace) fprintf(stderr, "[srh trace] lists %d>%d queued unverified: cmax %d smax %d guessed %d\n", ref, oth, S.cmax, S.smax, (int)S.guessed);
@@ -1913,7 +1911,7 @@ int TvPass::run_lists(bool cert_ok, srh_context::TvDefer *defer) const {
 			return SRH_OK;
 		}
 		int mx[4] = { 0, 0, 0, 0 };
-		if ((rc = read_back(c, mx, c->d_span, sizeof(mx)))) return rc;
+		if ((rc = read_back(lane.stream, mx, lane.mem->span, sizeof(mx)))) return rc;
 		const int maxc = mx[0];
 		if (c->debug_trace) fprintf(stderr, "[srh trace] lists %d>%d verified pass %d: cmax %d smax %d guessed %d -> longest list %d, slots %d, rows over %d\n",
 		                            ref, oth, pass, S.cmax, S.smax, (int)S.guessed, mx[0], mx[1], mx[2]);
@@ -1928,7 +1926,7 @@ int TvPass::run_lists(bool cert_ok, srh_context::TvDefer *defer) const {
 			}
 			if (tv_lists_fit(mx, S.cmax, S.smax)) {
 				Counters hc;
-				if ((rc = read_back(c, &hc, c->d_cnt, sizeof(hc)))) return rc;
+				if ((rc = read_back(lane.stream, &hc, lane.mem->cnt, sizeof(hc)))) return rc;
 				tv_learn_lists(c, ref, oth, S.guessed, S.cmax, S.smax, mx, hc);
 				if (hc.cert_overflow != 0) { cert_ok = false; continue; }   // more flagged pixels than the redo covers: mode 0
 				if (S.cert) { c->stats.n_certified = (int64_t)hc.n_pixels; c->stats.n_flagged = (int64_t)hc.n_flagged; }
@@ -1960,12 +1958,12 @@ int TvPass::run_lists(bool cert_ok, srh_context::TvDefer *defer) const {
 int TvPass::dense_prepare(TvDense &D) const {
 	int rc;
 	D.tscan = c->tscan != 0;
-	if ((rc = c->band.tnum.ensure((size_t)p->num_depth_levels + 8))) return rc;   // (+ 8: the template scan reads the table in whole eights)
-	if (D.tscan && (rc = c->band.stpl.ensure(scan_template_bytes()))) return rc;
+	if ((rc = lane.mem->band.tnum.ensure((size_t)p->num_depth_levels + 8))) return rc;   // (+ 8: the template scan reads the table in whole eights)
+	if (D.tscan && (rc = lane.mem->band.stpl.ensure(scan_template_bytes()))) return rc;
 	// (option side_weights: the first band queues them on the side stream, behind its windows kernel -- dense_band_inputs)
 	D.tables_pending = c->side_weights != 0;
 	D.tpl_wait = false;
-	if (!D.tables_pending) dense_tables(D, true, true);
+	if (!D.tables_pending) dense_tables(lane, D, true, true);
 	for (int pass = 0; pass < 2; ++pass) {
 		const int wdoubles = D.strip ? (2*R + 1)*wimg_wp(R) : T;    // doubles per pixel window in the band buffer
 		D.rows = rows_per_band((size_t)wdoubles*sizeof(double) + (size_t)D.cstride*sizeof(double));
@@ -1973,27 +1971,27 @@ int TvPass::dense_prepare(TvDense &D) const {
 		else break;
 	}
 	const size_t rows = D.rows;
-	if ((rc = c->band.wbuf.ensure(D.strip ? wimg_doubles(W, (int)rows, R) : wbuf_doubles(W, (int)rows, T)))) return rc;
-	if ((rc = c->band.cost.ensure(rows*(size_t)((W + 31)/32)*32*(size_t)D.cstride))) return rc;   // 32-pixel tiles
+	if ((rc = lane.mem->band.wbuf.ensure(D.strip ? wimg_doubles(W, (int)rows, R) : wbuf_doubles(W, (int)rows, T)))) return rc;
+	if ((rc = lane.mem->band.cost.ensure(rows*(size_t)((W + 31)/32)*32*(size_t)D.cstride))) return rc;   // 32-pixel tiles
 	// (+ one tile of slack: the strip kernel copies whole 32-pixel pieces of these rows)
-	if ((rc = c->band.pconst.ensure((rows*(size_t)W + SRH_WTILE)*SRH_PC))) return rc;
-	if ((rc = c->band.prange.ensure(rows*(size_t)W + SRH_WTILE))) return rc;
-	if (!sad && (rc = c->band.filllist.ensure(rows*(size_t)W + 1))) return rc;    // (capacity: the band's pixels)
-	if (D.tscan && (rc = c->band.tileflag.ensure(rows*(size_t)((W + 63)/64) + 1))) return rc;
-	if (D.cert && (rc = c->band.cflag.ensure(rows*(size_t)W + 1))) return rc;
+	if ((rc = lane.mem->band.pconst.ensure((rows*(size_t)W + SRH_WTILE)*SRH_PC))) return rc;
+	if ((rc = lane.mem->band.prange.ensure(rows*(size_t)W + SRH_WTILE))) return rc;
+	if (!sad && (rc = lane.mem->band.filllist.ensure(rows*(size_t)W + 1))) return rc;    // (capacity: the band's pixels)
+	if (D.tscan && (rc = lane.mem->band.tileflag.ensure(rows*(size_t)((W + 63)/64) + 1))) return rc;
+	if (D.cert && (rc = lane.mem->band.cflag.ensure(rows*(size_t)W + 1))) return rc;
 	D.lanes = D.strip ? strip_block_lanes(D.cstride, c->strip == 1 ? 0 : c->strip) : 8;
 	// NaN-bordered gray_tv planes of both views (strip kernel; the general cost of the left-out columns and of the
 	// certified redo on either dense path)
-	if ((rc = ensure_tvp(c, c->views[ref])) || (rc = ensure_tvp(c, c->views[oth]))) return rc;
+	if ((rc = ensure_tvp(c, lane.stream, c->views[ref])) || (rc = ensure_tvp(c, lane.stream, c->views[oth]))) return rc;
 	if (D.strip && sad) {
-		if ((rc = ensure_sad_planes(c, c->views[oth], R))) return rc;
+		if ((rc = ensure_sad_planes(c, lane.stream, c->views[oth], R))) return rc;
 	} else if (D.strip) {
 		// zero-bordered "window fully usable" plane of the other view
 		ViewHost &O = c->views[oth];
 		if (!O.fullp) HIP_TRY(O.fullp.alloc(padded_size(O.w, O.h)));
 		if (O.fullp_r != R) {
-			Scope s(c, "padded_full_kernel");
-			launch_padded_full(c->stream, O.gray_tv, O.w, O.h, R, O.fullp);
+			Scope s(c, lane.stream, "padded_full_kernel");
+			launch_padded_full(lane.stream, O.gray_tv, O.w, O.h, R, O.fullp);
 			O.fullp_r = R;
 		}
 	}
@@ -2002,14 +2000,14 @@ int TvPass::dense_prepare(TvDense &D) const {
 
 // the label-only part of the pinhole walk and the pass's candidate template: the reference's walk at one pixel
 // (srh_dense.hip, "template scan")
-void TvPass::dense_tables(const TvDense &D, bool table, bool tpl) const {
+void TvPass::dense_tables(const Lane &on, const TvDense &D, bool table, bool tpl) const {
 	if (table) {
-		Scope s(c, "pinhole_label_table_kernel");
-		launch_pinhole_label_table(c->stream, c->d_views, ref, *p, false, c->band.tnum);
+		Scope s(c, on.stream, "pinhole_label_table_kernel");
+		launch_pinhole_label_table(on.stream, c->d_views, ref, *p, false, on.mem->band.tnum);
 	}
 	if (tpl && D.tscan) {
-		Scope s(c, "twoview_template_kernel");
-		launch_scan_template(c->stream, c->d_views, ref, oth, *p, y0, y1 - y0, c->band.tnum, c->band.stpl);
+		Scope s(c, on.stream, "twoview_template_kernel");
+		launch_scan_template(on.stream, c->d_views, ref, oth, *p, y0, y1 - y0, on.mem->band.tnum, on.mem->band.stpl);
 	}
 }
 
@@ -2026,7 +2024,7 @@ bool TvPass::dense_fill_padded(const TvDense &D, int arith) const { return D.str
 // windows kernel's waves, the template's workgroup (80 registers per lane, 45 KB of LDS) does not and starts when the
 // windows kernel leaves -- behind the range kernel it holds nothing up (profiles/dense_tail_timeline.txt).
 int TvPass::dense_band_inputs(TvDense &D, int by, int nr, int arith) const {
-	uint32_t *filllist = sad ? nullptr : (uint32_t *)c->band.filllist;
+	uint32_t *filllist = sad ? nullptr : (uint32_t *)lane.mem->band.filllist;
 	const bool side = c->side_weights != 0;
 	if (side) {
 		if (!c->side_stream) {
@@ -2035,29 +2033,29 @@ int TvPass::dense_band_inputs(TvDense &D, int by, int nr, int arith) const {
 			HIP_TRY(hipEventCreateWithFlags(&c->side_done, hipEventDisableTiming));
 		}
 		if (!c->side_tpl) HIP_TRY(hipEventCreateWithFlags(&c->side_tpl, hipEventDisableTiming));
-		HIP_TRY(hipEventRecord(c->side_go, c->stream));
+		HIP_TRY(hipEventRecord(c->side_go, lane.stream));
 	}
-	run_weights(c, ref, W, *p, by, nr, SRH_WTILE, !sad ? (double *)c->band.pconst : nullptr, D.strip);
+	run_weights(c, lane, ref, W, *p, by, nr, SRH_WTILE, !sad ? (double *)lane.mem->band.pconst : nullptr, D.strip);
 	const bool tables = side && D.tables_pending;
 	D.tables_pending = false;
+	// where table, ranges and template are made: the pass's scratch, on the side stream or on the pass's own
+	const Lane on = { side ? c->side_stream : lane.stream, lane.mem };
 	if (side) {
-		HIP_TRY(hipStreamWaitEvent(c->side_stream, c->side_go, 0));
-		std::swap(c->stream, c->side_stream);                     // (Scope and the launchers read c->stream)
-		if (tables) dense_tables(D, true, false);
+		HIP_TRY(hipStreamWaitEvent(on.stream, c->side_go, 0));
+		if (tables) dense_tables(on, D, true, false);
 	}
-	hipError_t e = filllist ? hipMemsetAsync(filllist, 0, sizeof(uint32_t), c->stream) : hipSuccess;
-	{ Scope s(c, "pixel_range_kernel");
-	  launch_pixel_range(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.tnum, D.cstride, c->band.prange,
+	hipError_t e = filllist ? hipMemsetAsync(filllist, 0, sizeof(uint32_t), on.stream) : hipSuccess;
+	{ Scope s(c, on.stream, "pixel_range_kernel");
+	  launch_pixel_range(on.stream, c->d_views, ref, oth, W, *p, by, nr, on.mem->band.tnum, D.cstride, on.mem->band.prange,
 	                     D.lanes, dense_fill_padded(D, arith), filllist); }
 	if (side) {
-		if (e == hipSuccess) e = hipEventRecord(c->side_done, c->stream);
+		if (e == hipSuccess) e = hipEventRecord(c->side_done, on.stream);
 		if (tables && D.tscan) {
-			dense_tables(D, false, true);
-			if (e == hipSuccess) e = hipEventRecord(c->side_tpl, c->stream);
+			dense_tables(on, D, false, true);
+			if (e == hipSuccess) e = hipEventRecord(c->side_tpl, on.stream);
 			D.tpl_wait = true;
 		}
-		std::swap(c->stream, c->side_stream);
-		if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, c->side_done, 0);
+		if (e == hipSuccess) e = hipStreamWaitEvent(lane.stream, c->side_done, 0);
 	}
 	if (e != hipSuccess) return fail(SRH_E_DEVICE, "dense band inputs: %s", hipGetErrorString(e));
 	return SRH_OK;
@@ -2070,33 +2068,33 @@ int TvPass::dense_cost_pass(const TvDense &D, int by, int nr, int arith, bool ra
 	const size_t wstride = SRH_WTILE;
 	if (sad) {
 		// (every column of [lo, hi] is written: no fill launch, which would evaluate cost_ncc)
-		HIP_TRY(hipMemsetAsync(&c->d_cnt->strip_ticket, 0, 2*sizeof(unsigned int), c->stream));
-		Scope s(c, "twoview_strip_sad_kernel");
-		if (!launch_twoview_strip_sad(c->stream, W, H, *p, by, nr, c->band.wbuf, c->band.prange, c->views[ref].tvp,
-		                              c->views[oth].grayp, c->views[oth].fullsp, c->band.cost, cstride, c->d_cnt, c->num_cus))
+		HIP_TRY(hipMemsetAsync(&lane.mem->cnt->strip_ticket, 0, 2*sizeof(unsigned int), lane.stream));
+		Scope s(c, lane.stream, "twoview_strip_sad_kernel");
+		if (!launch_twoview_strip_sad(lane.stream, W, H, *p, by, nr, lane.mem->band.wbuf, lane.mem->band.prange, c->views[ref].tvp,
+		                              c->views[oth].grayp, c->views[oth].fullsp, lane.mem->band.cost, cstride, lane.mem->cnt, c->num_cus))
 			return fail(SRH_E_UNSUPPORTED, "twoview_strip_sad_kernel: no instantiation for radius %d", R);
 		return SRH_OK;
 	}
 	if (D.strip) {
-		HIP_TRY(hipMemsetAsync(&c->d_cnt->strip_ticket, 0, 2*sizeof(unsigned int), c->stream));
-		{ Scope s(c, "twoview_strip_cost_kernel");
-		  launch_twoview_strip_cost(c->stream, c->d_views, ref, oth, W, H, *p, by, nr, c->band.wbuf, c->band.pconst, c->band.prange,
-		                            c->views[ref].tvp, c->views[oth].tvp, c->views[oth].fullp, c->band.cost, cstride,
-		                            c->d_cnt, arith, c->num_cus, D.lanes, raw); }
+		HIP_TRY(hipMemsetAsync(&lane.mem->cnt->strip_ticket, 0, 2*sizeof(unsigned int), lane.stream));
+		{ Scope s(c, lane.stream, "twoview_strip_cost_kernel");
+		  launch_twoview_strip_cost(lane.stream, c->d_views, ref, oth, W, H, *p, by, nr, lane.mem->band.wbuf, lane.mem->band.pconst, lane.mem->band.prange,
+		                            c->views[ref].tvp, c->views[oth].tvp, c->views[oth].fullp, lane.mem->band.cost, cstride,
+		                            lane.mem->cnt, arith, c->num_cus, D.lanes, raw); }
 	} else {
-		{ Scope s(c, "twoview_dense_cost_kernel");
+		{ Scope s(c, lane.stream, "twoview_dense_cost_kernel");
 		  if (arith == 2)
-			launch_twoview_dense_cost_f32(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, wstride,
-			                              c->band.tnum, c->band.cost, cstride, c->d_cnt, c->band.pconst, c->f32_form);
+			launch_twoview_dense_cost_f32(lane.stream, c->d_views, ref, oth, W, *p, by, nr, lane.mem->band.wbuf, wstride,
+			                              lane.mem->band.tnum, lane.mem->band.cost, cstride, lane.mem->cnt, lane.mem->band.pconst, c->f32_form);
 		  else
-			launch_twoview_dense_cost(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, wstride,
-			                          c->band.tnum, c->band.cost, cstride, c->d_cnt, c->band.pconst, arith, c->band.prange); }
+			launch_twoview_dense_cost(lane.stream, c->d_views, ref, oth, W, *p, by, nr, lane.mem->band.wbuf, wstride,
+			                          lane.mem->band.tnum, lane.mem->band.cost, cstride, lane.mem->cnt, lane.mem->band.pconst, arith, lane.mem->band.prange); }
 	}
 	// the left-out columns (per-tile kernel: its one-pass form leaves none out; D.lanes is 8 there), from the list the range
 	// kernel made for this form
-	Scope s(c, "twoview_lazy_fill_kernel");
-	launch_twoview_lazy_fill(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.prange, c->band.filllist, c->band.wbuf, wstride, c->views[ref].tvp,
-	                         c->views[oth].tvp, D.strip, D.lanes, dense_fill_padded(D, arith), c->band.cost, cstride, c->d_cnt);
+	Scope s(c, lane.stream, "twoview_lazy_fill_kernel");
+	launch_twoview_lazy_fill(lane.stream, c->d_views, ref, oth, W, *p, by, nr, lane.mem->band.prange, lane.mem->band.filllist, lane.mem->band.wbuf, wstride, c->views[ref].tvp,
+	                         c->views[oth].tvp, D.strip, D.lanes, dense_fill_padded(D, arith), lane.mem->band.cost, cstride, lane.mem->cnt);
 	return SRH_OK;
 }
 
@@ -2110,28 +2108,28 @@ int TvPass::run_dense(TvDense &D) const {
 		if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
 		const int nr = std::min((int)D.rows, y1 - by);
 		if ((rc = dense_band_inputs(D, by, nr, cost_arith))) return rc;
-		if (D.cert) HIP_TRY(hipMemsetAsync(c->band.cflag, 0, sizeof(uint32_t), c->stream));
+		if (D.cert) HIP_TRY(hipMemsetAsync(lane.mem->band.cflag, 0, sizeof(uint32_t), lane.stream));
 		if ((rc = dense_cost_pass(D, by, nr, cost_arith, false))) return rc;
-		if (D.tpl_wait) { HIP_TRY(hipStreamWaitEvent(c->stream, c->side_tpl, 0)); D.tpl_wait = false; }
-		{ Scope s(c, "twoview_scan_kernel");
-		  launch_twoview_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.tnum, c->band.cost, D.cstride, c->d_cnt, c->band.prange,
-		                      D.cert ? c->band.cflag : nullptr, -1, D.cert && D.strip ? c->band.pconst : nullptr, D.tscan ? c->band.stpl : nullptr, c->band.tileflag, c->num_cus, wout, c->tscan_bound); }
+		if (D.tpl_wait) { HIP_TRY(hipStreamWaitEvent(lane.stream, c->side_tpl, 0)); D.tpl_wait = false; }
+		{ Scope s(c, lane.stream, "twoview_scan_kernel");
+		  launch_twoview_scan(lane.stream, c->d_views, ref, oth, W, *p, by, nr, lane.mem->band.tnum, lane.mem->band.cost, D.cstride, lane.mem->cnt, lane.mem->band.prange,
+		                      D.cert ? lane.mem->band.cflag : nullptr, -1, D.cert && D.strip ? lane.mem->band.pconst : nullptr, D.tscan ? lane.mem->band.stpl : nullptr, lane.mem->band.tileflag, c->num_cus, wout, c->tscan_bound); }
 		if (D.cert) {
 			// the pixels whose decisions the bound does not cover, in the reference's arithmetic: their cost rows are
 			// refilled and they are scanned again -- launched for a capacity, the count stays on the device
 			// (one kernel does both where the wave form of the rescan is eligible: twoview_redo_kernel, the columns beside the walk)
 			const int cap = redo_capacity((size_t)nr*W);
 			if (twoview_redo_takes(*p, D.cstride)) {
-				Scope s(c, "twoview_redo_kernel");
-				launch_twoview_redo(c->stream, c->d_views, ref, oth, W, *p, by, c->band.tnum, c->band.wbuf, D.strip, c->views[ref].tvp,
-				                    c->views[oth].tvp, c->band.cost, D.cstride, c->band.prange, c->band.cflag, cap, c->d_cnt, wout);
+				Scope s(c, lane.stream, "twoview_redo_kernel");
+				launch_twoview_redo(lane.stream, c->d_views, ref, oth, W, *p, by, lane.mem->band.tnum, lane.mem->band.wbuf, D.strip, c->views[ref].tvp,
+				                    c->views[oth].tvp, lane.mem->band.cost, D.cstride, lane.mem->band.prange, lane.mem->band.cflag, cap, lane.mem->cnt, wout);
 			} else {
-				{ Scope s(c, "twoview_refill_kernel");
-				  launch_twoview_refill(c->stream, W, *p, by, c->band.prange, c->band.cflag, cap, c->band.wbuf, D.strip, c->views[ref].tvp,
-				                        c->views[oth].tvp, c->band.cost, D.cstride, c->d_cnt); }
-				Scope s(c, "twoview_rescan_kernel");
-				launch_twoview_scan(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.tnum, c->band.cost, D.cstride, c->d_cnt, c->band.prange,
-				                    c->band.cflag, cap, nullptr, nullptr, nullptr, c->num_cus, wout);
+				{ Scope s(c, lane.stream, "twoview_refill_kernel");
+				  launch_twoview_refill(lane.stream, W, *p, by, lane.mem->band.prange, lane.mem->band.cflag, cap, lane.mem->band.wbuf, D.strip, c->views[ref].tvp,
+				                        c->views[oth].tvp, lane.mem->band.cost, D.cstride, lane.mem->cnt); }
+				Scope s(c, lane.stream, "twoview_rescan_kernel");
+				launch_twoview_scan(lane.stream, c->d_views, ref, oth, W, *p, by, nr, lane.mem->band.tnum, lane.mem->band.cost, D.cstride, lane.mem->cnt, lane.mem->band.prange,
+				                    lane.mem->band.cflag, cap, nullptr, nullptr, nullptr, c->num_cus, wout);
 			}
 		}
 		winner_costs(by, nr, D.strip);
@@ -2152,13 +2150,13 @@ static TvVerdict tv_dense_verdict(const Counters &h, bool strip) {
 int TvPass::run_walk() const {
 	int rc;
 	const int rows = (int)rows_per_band((size_t)T*sizeof(double));
-	if ((rc = c->band.wbuf.ensure(wbuf_doubles(W, rows, T)))) return rc;
+	if ((rc = lane.mem->band.wbuf.ensure(wbuf_doubles(W, rows, T)))) return rc;
 	for (int by = y0; by < y1; by += rows) {
 		if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
 		const int nr = std::min(rows, y1 - by);
-		run_weights(c, ref, W, *p, by, nr, SRH_WTILE);
-		{ Scope s(c, "twoview_generic_kernel");
-		  launch_twoview_generic(c->stream, c->d_views, ref, oth, W, *p, by, nr, c->band.wbuf, SRH_WTILE, c->d_cnt, sad, wout); }
+		run_weights(c, lane, ref, W, *p, by, nr, SRH_WTILE);
+		{ Scope s(c, lane.stream, "twoview_generic_kernel");
+		  launch_twoview_generic(lane.stream, c->d_views, ref, oth, W, *p, by, nr, lane.mem->band.wbuf, SRH_WTILE, lane.mem->cnt, sad, wout); }
 		winner_costs(by, nr, false);
 	}
 	HIP_TRY(hipGetLastError());
@@ -2168,14 +2166,14 @@ int TvPass::run_walk() const {
 // The controller: the plan's first choice, then at most four attempts, each read by its counters -- a strip overflow takes
 // the per-tile kernel (cost_sad, which has the strip form only: the candidate lists), a certified pass with more flagged
 // pixels than its redo covers the reference's arithmetic, a dense plan the device refutes the general kernels.  On a
-// call's first attempt srh_twoview_compute's passes (c->defer) are handed over unverified instead.
+// call's first attempt srh_twoview_compute's passes (defer) are handed over unverified instead.
 // (a HIP error or a refused band buffer returns straight out: with_thinner_bands retries the whole call)
-static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p, int y0, int y1) {
+static int twoview_wta_run(srh_context *c, const Lane &lane, srh_context::TvDefer *first_defer, int ref, int oth, const srh_params *p, int y0, int y1) {
 	int rc;
 	TvPass P;
-	if ((rc = tv_pass_init(P, c, ref, oth, p, y0, y1))) return rc;
+	if ((rc = tv_pass_init(P, c, lane, ref, oth, p, y0, y1))) return rc;
 	if (P.y1 <= P.y0) return SRH_OK;
-	if ((rc = ensure_wta_planes(c, ref, oth))) return rc;
+	if ((rc = ensure_wta_planes(c, lane.stream, ref, oth))) return rc;
 	P.wout = c->wta_outputs ? (int32_t *)c->views[ref].wta_xy : nullptr;
 	const TvPlan plan = P.plan();
 
@@ -2205,8 +2203,8 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 	// visits every point, takes such a run)
 	const bool lists = !c->force_walk && P.R <= 5 && P.W < 65536 && P.H < 65536 && p->wta_margin >= 0;
 	for (int attempt = 0; attempt < 4; ++attempt) {
-		HIP_TRY(hipMemsetAsync(c->d_cnt, 0, sizeof(Counters), c->stream));
-		srh_context::TvDefer *defer = attempt == 0 ? c->defer : nullptr;
+		HIP_TRY(hipMemsetAsync(lane.mem->cnt, 0, sizeof(Counters), lane.stream));
+		srh_context::TvDefer *defer = attempt == 0 ? first_defer : nullptr;
 		if (!dense) {
 			if ((rc = lists ? P.run_lists(cert_ok, defer) : P.run_walk())) return rc;
 			if (lists && defer && defer->queued) return SRH_OK;
@@ -2215,13 +2213,13 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 		D.cert = cert_ok;
 		if ((rc = P.run_dense(D))) return rc;
 		if (defer) {
-			if ((rc = tv_defer_queue(c, *defer, false, D.strip, cert_ok))) return rc;
+			if ((rc = tv_defer_queue(lane, *defer, false, D.strip, cert_ok))) return rc;
 			c->stats.used_strip_kernel = D.strip ? 1 : 0;
 			c->stats.used_dense_path = 1;
 			return SRH_OK;
 		}
 		Counters hc;
-		if ((rc = read_back(c, &hc, c->d_cnt, sizeof(hc)))) return rc;
+		if ((rc = read_back(lane.stream, &hc, lane.mem->cnt, sizeof(hc)))) return rc;
 		const TvVerdict v = tv_dense_verdict(hc, D.strip);
 		if (v == TV_STRIP_OVERFLOW) { D.strip = false; if (P.sad) dense = false; continue; }
 		if (v == TV_CERT_OVERFLOW) { cert_ok = false; continue; }
@@ -2238,7 +2236,7 @@ static int twoview_wta_run(srh_context *c, int ref, int oth, const srh_params *p
 extern "C" int srh_twoview_wta(srh_context *c, int ref, int oth, const srh_params *p, int y0, int y1) {
 	int rc;
 	if ((rc = check_slot(c, ref, true)) || (rc = check_slot(c, oth, true)) || (rc = check_params(p))) return rc;
-	return with_thinner_bands(c, [&] { return twoview_wta_run(c, ref, oth, p, y0, y1); });
+	return with_thinner_bands(c, [&] { return twoview_wta_run(c, c->main_lane(), nullptr, ref, oth, p, y0, y1); });
 }
 
 // Diagnostic (tests/test_gpu_cert_rows.py): the cost rows of rows [y0, y1) on the row-aligned dense plan, straight from the
@@ -2257,13 +2255,13 @@ extern "C" int srh_twoview_cost_rows(srh_context *c, int ref, int oth, const srh
 	if (sad && !c->sad_dense) return fail(SRH_E_UNSUPPORTED, "cost rows of cost_sad exist on the dense plan only (option sad_dense)");
 	if (sad && form != 0) return fail(SRH_E_INVALID, "cost_sad has the reference's arithmetic only: form must be 0");
 	TvPass P;
-	if ((rc = tv_pass_init(P, c, ref, oth, p, y0, y1))) return rc;
+	if ((rc = tv_pass_init(P, c, c->main_lane(), ref, oth, p, y0, y1))) return rc;
 	const TvPlan plan = P.plan();
 	if (P.y1 <= P.y0 || !plan.dense)
 		return fail(SRH_E_UNSUPPORTED, "cost rows exist on the row-aligned dense plan only (radius 5 or 2, rectified pinhole pair)");
 	c->last_fused = false;
 	c->stats.n_certified = c->stats.n_flagged = 0;
-	HIP_TRY(hipMemsetAsync(c->d_cnt, 0, sizeof(Counters), c->stream));
+	HIP_TRY(hipMemsetAsync(c->mem.cnt, 0, sizeof(Counters), c->stream));
 	TvDense D;
 	D.cstride = plan.cstride;
 	D.strip = (sad || c->strip != 0) && plan.cstride + SRH_WTILE <= strip_chunk_columns();
@@ -2278,10 +2276,10 @@ extern "C" int srh_twoview_cost_rows(srh_context *c, int ref, int oth, const srh
 		// the band's cost rows under the arithmetic asked for, as the cost kernel leaves them, and the pixels' column ranges
 		const size_t nd = (size_t)nr*((P.W + 31)/32)*32*(size_t)D.cstride;
 		if (cost_doubles < nd) return fail(SRH_E_INVALID, "cost rows: buffer of %zu doubles, %zu needed", cost_doubles, nd);
-		HIP_TRY(hipMemsetAsync(c->band.cost, 0xff, nd*sizeof(double), c->stream));   // (never-written entries read as a NaN with payload -1)
+		HIP_TRY(hipMemsetAsync(c->mem.band.cost, 0xff, nd*sizeof(double), c->stream));   // (never-written entries read as a NaN with payload -1)
 		if ((rc = P.dense_cost_pass(D, P.y0, nr, form, raw != 0))) return rc;
-		HIP_TRY(hipMemcpyAsync(cost_out, c->band.cost, nd*sizeof(double), hipMemcpyDeviceToHost, c->stream));
-		if (range_out) HIP_TRY(hipMemcpyAsync(range_out, c->band.prange, (size_t)nr*P.W*sizeof(PixRange), hipMemcpyDeviceToHost, c->stream));
+		HIP_TRY(hipMemcpyAsync(cost_out, c->mem.band.cost, nd*sizeof(double), hipMemcpyDeviceToHost, c->stream));
+		if (range_out) HIP_TRY(hipMemcpyAsync(range_out, c->mem.band.prange, (size_t)nr*P.W*sizeof(PixRange), hipMemcpyDeviceToHost, c->stream));
 		HIP_TRY(hipStreamSynchronize(c->stream));
 	}
 	if (cstride_out) *cstride_out = D.cstride;
@@ -2309,7 +2307,7 @@ extern "C" int srh_twoview_pair_costs(srh_context *c, int ref, int oth, const sr
 	HIP_TRY(dxy.alloc((size_t)4*n));
 	HIP_TRY(dout.alloc((size_t)n));
 	HIP_TRY(hipMemcpyAsync(dxy, xy, (size_t)4*n*sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-	{ Scope s(c, "pair_costs_kernel");
+	{ Scope s(c, c->stream, "pair_costs_kernel");
 	  launch_pair_costs(c->stream, c->d_views, ref, oth, *p, kind == SRH_COST_SAD, n, dxy, dout); }
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(out, dout, (size_t)n*sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -2342,18 +2340,10 @@ extern "C" int srh_twoview_cross_check(srh_context *c, int left, int right, cons
 	if (L.w != Rv.w || L.h != Rv.h) return fail(SRH_E_INVALID, "TwoViewStereo needs equal-sized views");
 	HIP_TRY(hipSetDevice(c->device));
 	// left pass completes (stream order) before the right pass reads the filtered left map
-	{ Scope s(c, "twoview_cross_check_kernel"); launch_twoview_cross_check(c->stream, c->d_views, left, right, L.w, L.h, *p); }
-	{ Scope s(c, "twoview_cross_check_kernel"); launch_twoview_cross_check(c->stream, c->d_views, right, left, L.w, L.h, *p); }
+	{ Scope s(c, c->stream, "twoview_cross_check_kernel"); launch_twoview_cross_check(c->stream, c->d_views, left, right, L.w, L.h, *p); }
+	{ Scope s(c, c->stream, "twoview_cross_check_kernel"); launch_twoview_cross_check(c->stream, c->d_views, right, left, L.w, L.h, *p); }
 	HIP_TRY(hipGetLastError());
 	return SRH_OK;
-}
-
-// the context's stream and TwoView band buffers <-> the second pass's
-static void tv_slot_swap(srh_context *c) {
-	srh_context::TvSlot &T = c->tv_slot;
-	std::swap(c->stream, T.stream);
-	std::swap(c->band, T.band);
-	std::swap(c->d_cnt, T.d_cnt); std::swap(c->d_span, T.d_span);
 }
 
 static bool tv_pass_stands(const srh_context::TvDefer &d) {
@@ -2381,24 +2371,26 @@ extern "C" int srh_twoview_compute(srh_context *c, int left, int right, const sr
 			HIP_TRY(hipStreamCreateWithFlags(&T.stream, hipStreamNonBlocking));
 			HIP_TRY(hipEventCreateWithFlags(&T.go, hipEventDisableTiming));
 			HIP_TRY(hipEventCreateWithFlags(&T.done, hipEventDisableTiming));
-			HIP_TRY(T.d_cnt.alloc(1));
-			HIP_TRY(T.d_span.alloc(4));
+			HIP_TRY(T.mem.cnt.alloc(1));
+			HIP_TRY(T.mem.span.alloc(4));
 		}
 		// the NaN-bordered planes both passes read (tv_dense_prepare makes them on demand, on its own stream) exist at `go`
 		if (c->cost_kind == SRH_COST_SAD && c->sad_dense && (p->window_radius == 5 || p->window_radius == 2))
 			for (int k = 0; k < 2; ++k)
-				if ((rc = ensure_sad_planes(c, c->views[k == 0 ? left : right], p->window_radius))) return rc;
+				if ((rc = ensure_sad_planes(c, c->stream, c->views[k == 0 ? left : right], p->window_radius))) return rc;
 		if ((p->window_radius == 5 || p->window_radius == 2) &&
-		    ((rc = ensure_tvp(c, c->views[left])) || (rc = ensure_tvp(c, c->views[right])))) return rc;
+		    ((rc = ensure_tvp(c, c->stream, c->views[left])) || (rc = ensure_tvp(c, c->stream, c->views[right])))) return rc;
 		// (and the WTA by-products' planes of both views, option "wta_outputs", are allocated and hold their "none" values there)
-		if ((rc = ensure_wta_planes(c, left, right)) || (rc = ensure_wta_planes(c, right, left))) return rc;
+		if ((rc = ensure_wta_planes(c, c->stream, left, right)) || (rc = ensure_wta_planes(c, c->stream, right, left))) return rc;
 		HIP_TRY(hipEventRecord(T.go, c->stream));
 	}
 	// progress steps as TwoViewStereo emits them (twoviewstereo.cpp:234,405,597,225)
 	progress(c, 1, "Computing cost volume for left image...");
-	// (a pass whose verdict may wait: twoview_wta_run hands it over through c->defer)
-	auto deferred_wta = [&](int k, int ref, int oth) { c->defer = &c->tv_defer[k]; const int r = srh_twoview_wta(c, ref, oth, p, 0, 0); c->defer = nullptr; return r; };
-	if ((rc = deferred_wta(0, left, right))) return rc;
+	// (a pass whose verdict may wait: twoview_wta_run hands it over through tv_defer[k])
+	auto deferred_wta = [&](int k, const Lane &lane, int ref, int oth) {
+		return with_thinner_bands(c, [&] { return twoview_wta_run(c, lane, &c->tv_defer[k], ref, oth, p, 0, 0); });
+	};
+	if ((rc = deferred_wta(0, c->main_lane(), left, right))) return rc;
 	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
 	progress(c, 3, "Computing cost volume for right image...");
 	if (c->tv_overlap && c->tv_defer[0].queued) {
@@ -2406,17 +2398,15 @@ extern "C" int srh_twoview_compute(srh_context *c, int left, int right, const sr
 		// context's stream (before the first pass: the views and their padded planes are complete there)
 		srh_context::TvSlot &T = c->tv_slot;
 		HIP_TRY(hipStreamWaitEvent(T.stream, T.go, 0));
-		tv_slot_swap(c);
-		rc = deferred_wta(1, right, left);
-		const hipError_t e = rc ? hipStreamSynchronize(c->stream) : hipEventRecord(T.done, c->stream);   // (c->stream: the slot's, still)
-		tv_slot_swap(c);
+		rc = deferred_wta(1, { T.stream, &T.mem }, right, left);
+		const hipError_t e = rc ? hipStreamSynchronize(T.stream) : hipEventRecord(T.done, T.stream);
 		if (rc) return rc;
 		if (e != hipSuccess) return fail(SRH_E_DEVICE, "second TwoView pass: %s", hipGetErrorString(e));
 		HIP_TRY(hipStreamWaitEvent(c->stream, T.done, 0));            // whatever follows on the context's stream sees both maps
 		// (srh_get_stats reads the context's counters and reports the last pass's, as it does without the overlap)
-		HIP_TRY(hipMemcpyAsync(c->d_cnt, T.d_cnt, sizeof(Counters), hipMemcpyDeviceToDevice, c->stream));
+		HIP_TRY(hipMemcpyAsync(c->mem.cnt, T.mem.cnt, sizeof(Counters), hipMemcpyDeviceToDevice, c->stream));
 	} else {
-		if ((rc = deferred_wta(1, right, left))) return rc;
+		if ((rc = deferred_wta(1, c->main_lane(), right, left))) return rc;
 	}
 	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
 	srh_context::TvDefer &d0 = c->tv_defer[0], &d1 = c->tv_defer[1];
@@ -2475,7 +2465,7 @@ extern "C" int srh_twoview_compute(srh_context *c, int left, int right, const sr
 		}
 	}
 	// (counters of the two passes for the statistics: an untimed recount is not worth a pass; the last pass's are reported)
-	if ((rc = fetch_counters(c, c->stats.used_dense_path))) return rc;
+	if ((rc = fetch_counters(c, c->main_lane(), c->stats.used_dense_path))) return rc;
 	progress(c, 5, "Detecting inconsistencies...");
 	if ((rc = srh_twoview_cross_check(c, left, right, p))) return rc;
 	if (c->filter_invalid && (rc = twoview_filter(c, left, right, p))) return rc;
@@ -2486,12 +2476,9 @@ extern "C" int srh_twoview_compute(srh_context *c, int left, int right, const sr
 	return SRH_OK;
 }
 
-extern "C" int srh_mvs_initial_estimate(srh_context *c, int view, const int32_t *neigh, int nneigh,
-                                        const srh_params *p, int y0, int y1, void *peaks_dev);
-
 // The serpentine list of a view's masked-in pixels (mask.pixel == WHITE <=> byte 1; no mask: every pixel), built when the
 // MultiViewStereo list path first needs it after an upload.  The device buffer keeps its capacity across uploads.
-static int ensure_act(srh_context *c, ViewHost &v) {
+static int ensure_act(hipStream_t st, ViewHost &v) {
 	if (v.act_valid) return SRH_OK;
 	const int w = v.w, h = v.h;
 	std::vector<uint32_t> &act = v.act_host;
@@ -2511,20 +2498,20 @@ static int ensure_act(srh_context *c, ViewHost &v) {
 			v.act.free();
 			HIP_TRY(v.act.alloc((size_t)w*h));
 		}
-		HIP_TRY(hipMemcpyAsync(v.act, act.data(), act.size()*sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-		HIP_TRY(hipStreamSynchronize(c->stream));                  // once per upload: either slot's stream may read it next
+		HIP_TRY(hipMemcpyAsync(v.act, act.data(), act.size()*sizeof(uint32_t), hipMemcpyHostToDevice, st));
+		HIP_TRY(hipStreamSynchronize(st));                  // once per upload: either slot's stream may read it next
 	}
 	v.act_valid = true;
 	return SRH_OK;
 }
 
-// One pass of the list path of srh_mvs_initial_estimate for list capacity cmax: everything is queued on c->stream with
-// c's band buffers, nothing is waited for.  d_span[0] receives the longest list (slots), for the caller to compare with cmax.
-static int mvs_list_launch(srh_context *c, int view, const int32_t *neigh, int nneigh, const srh_params *p, int y0, int y1,
+// One pass of the list path of srh_mvs_initial_estimate for list capacity cmax: everything is queued on the lane's stream with
+// its band buffers, nothing is waited for.  Its span[0] receives the longest list (slots), for the caller to compare with cmax.
+static int mvs_list_launch(srh_context *c, const Lane &lane, int view, const int32_t *neigh, int nneigh, const srh_params *p, int y0, int y1,
                            void *peaks_dev, int cmax)
 {
 	int rc;
-	if ((rc = ensure_act(c, c->views[view]))) return rc;
+	if ((rc = ensure_act(lane.stream, c->views[view]))) return rc;
 	const ViewHost &A = c->views[view];
 	const int W = A.w;
 	const int T = (2*p->window_radius + 1)*(2*p->window_radius + 1);
@@ -2535,12 +2522,12 @@ static int mvs_list_launch(srh_context *c, int view, const int32_t *neigh, int n
 	bool neigh_pinhole = true;                                  // (certified label projections: plain pinhole neighbours only)
 	for (int i = 0; i < nneigh; ++i) { const srh_camera &nc = c->views[neigh[i]].cam; if (nc.is_refractive || nc.is_distorted) neigh_pinhole = false; }
 	if (table) {
-		if ((rc = c->band.tnum.ensure((size_t)p->num_depth_levels))) return rc;
-		Scope s(c, "pinhole_label_table_kernel");
-		launch_pinhole_label_table(c->stream, c->d_views, view, *p, true, c->band.tnum);
+		if ((rc = lane.mem->band.tnum.ensure((size_t)p->num_depth_levels))) return rc;
+		Scope s(c, lane.stream, "pinhole_label_table_kernel");
+		launch_pinhole_label_table(lane.stream, c->d_views, view, *p, true, lane.mem->band.tnum);
 	}
-	HIP_TRY(hipMemsetAsync(c->d_cnt, 0, sizeof(Counters), c->stream));
-	HIP_TRY(hipMemsetAsync(c->d_span, 0, 4*sizeof(int), c->stream));
+	HIP_TRY(hipMemsetAsync(lane.mem->cnt, 0, sizeof(Counters), lane.stream));
+	HIP_TRY(hipMemsetAsync(lane.mem->span, 0, 4*sizeof(int), lane.stream));
 	const size_t per_px = (size_t)T*sizeof(double) + (size_t)nneigh*((size_t)cmax*sizeof(uint32_t) + sizeof(int32_t) + 2*sizeof(double)
 	                      + (peaks_dev ? (size_t)p->top_k*2*sizeof(double) : 0));
 	size_t lrows = band_budget(c) / (per_px*(size_t)W);
@@ -2559,49 +2546,49 @@ static int mvs_list_launch(srh_context *c, int view, const int32_t *neigh, int n
 		const size_t na = (size_t)A.act_row[by + nr] - A.act_row[by];
 		lunits = std::max(lunits, ((na + 127) & ~(size_t)127)*(size_t)nneigh);
 	}
-	if ((rc = c->band.wbuf.ensure(wbuf_doubles(W, (int)lrows, T)))) return rc;
-	if ((rc = c->band.cost.ensure(units*2 + (peaks_dev ? units*(size_t)p->top_k*2 : 0)))) return rc;   // best pairs + per-unit top-K, by pixel
-	if ((rc = c->band.lcand.ensure(std::max<size_t>(lunits, 128)*(size_t)cmax))) return rc;   // wave-tiled lists
-	if ((rc = c->band.lcount.ensure(std::max<size_t>(lunits, 128)))) return rc;
+	if ((rc = lane.mem->band.wbuf.ensure(wbuf_doubles(W, (int)lrows, T)))) return rc;
+	if ((rc = lane.mem->band.cost.ensure(units*2 + (peaks_dev ? units*(size_t)p->top_k*2 : 0)))) return rc;   // best pairs + per-unit top-K, by pixel
+	if ((rc = lane.mem->band.lcand.ensure(std::max<size_t>(lunits, 128)*(size_t)cmax))) return rc;   // wave-tiled lists
+	if ((rc = lane.mem->band.lcount.ensure(std::max<size_t>(lunits, 128)))) return rc;
 	const bool staged = c->mvs_staged != 0;
 	if (staged) {
 		int maxw; size_t words;
 		mvs_staging_shape(&maxw, &words);
 		const size_t waves = std::max<size_t>(lunits, 128)/64;
-		if ((rc = c->band.mvs_wdesc.ensure(waves*words))) return rc;
-		if ((rc = c->band.mvs_nwin.ensure(waves))) return rc;
+		if ((rc = lane.mem->band.mvs_wdesc.ensure(waves*words))) return rc;
+		if ((rc = lane.mem->band.mvs_nwin.ensure(waves))) return rc;
 	}
 	for (int by = y0; by < y1; by += (int)lrows) {
 		if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
 		const int nr = std::min((int)lrows, y1 - by);
 		const uint32_t *act = A.act ? A.act + A.act_row[by] : nullptr;
 		const int nact = (int)(A.act_row[by + nr] - A.act_row[by]);
-		run_weights(c, view, W, *p, by, nr, wstride);
-		{ Scope s(c, "mvs_walk_kernel");
-		  launch_mvs_walk(c->stream, c->d_views, view, neigh, nneigh, W, *p, by, nr, table ? c->band.tnum : nullptr, c->band.lcand, cmax, c->band.lcount,
-		                  c->d_cnt, c->d_span, staged ? c->band.mvs_wdesc : nullptr, staged ? c->band.mvs_nwin : nullptr, act, nact,
+		run_weights(c, lane, view, W, *p, by, nr, wstride);
+		{ Scope s(c, lane.stream, "mvs_walk_kernel");
+		  launch_mvs_walk(lane.stream, c->d_views, view, neigh, nneigh, W, *p, by, nr, table ? lane.mem->band.tnum : nullptr, lane.mem->band.lcand, cmax, lane.mem->band.lcount,
+		                  lane.mem->cnt, lane.mem->span, staged ? lane.mem->band.mvs_wdesc : nullptr, staged ? lane.mem->band.mvs_nwin : nullptr, act, nact,
 		                  peaks_dev != nullptr, neigh_pinhole && c->arith == 3); }
-		double *const upk = peaks_dev ? c->band.cost + units*2 : nullptr;
+		double *const upk = peaks_dev ? lane.mem->band.cost + units*2 : nullptr;
 		if (staged) {
-			Scope s(c, "mvs_staged_cost_kernel");
-			launch_mvs_staged_cost(c->stream, c->d_views, view, neigh, nneigh, W, *p, by, nr, c->band.wbuf, wstride,
-			                       c->band.lcand, cmax, c->band.lcount, c->band.cost, c->band.mvs_wdesc, c->band.mvs_nwin, c->d_cnt, act, nact, upk,
+			Scope s(c, lane.stream, "mvs_staged_cost_kernel");
+			launch_mvs_staged_cost(lane.stream, c->d_views, view, neigh, nneigh, W, *p, by, nr, lane.mem->band.wbuf, wstride,
+			                       lane.mem->band.lcand, cmax, lane.mem->band.lcount, lane.mem->band.cost, lane.mem->band.mvs_wdesc, lane.mem->band.mvs_nwin, lane.mem->cnt, act, nact, upk,
 			                       c->arith == 3 && !peaks_dev);
 		}
-		{ Scope s(c, "mvs_list_cost_kernel");
-		  launch_mvs_list_cost(c->stream, c->d_views, view, neigh, nneigh, W, *p, by, nr, c->band.wbuf, wstride,
-		                       c->band.lcand, cmax, c->band.lcount, c->band.cost, upk, peaks_dev != nullptr, staged ? c->band.mvs_nwin : nullptr, act, nact); }
-		{ Scope s(c, "mvs_combine_kernel");
-		  launch_mvs_combine(c->stream, c->d_views, view, nneigh, W, *p, by, nr, c->band.cost, upk, (double *)peaks_dev); }
+		{ Scope s(c, lane.stream, "mvs_list_cost_kernel");
+		  launch_mvs_list_cost(lane.stream, c->d_views, view, neigh, nneigh, W, *p, by, nr, lane.mem->band.wbuf, wstride,
+		                       lane.mem->band.lcand, cmax, lane.mem->band.lcount, lane.mem->band.cost, upk, peaks_dev != nullptr, staged ? lane.mem->band.mvs_nwin : nullptr, act, nact); }
+		{ Scope s(c, lane.stream, "mvs_combine_kernel");
+		  launch_mvs_combine(lane.stream, c->d_views, view, nneigh, W, *p, by, nr, lane.mem->band.cost, upk, (double *)peaks_dev); }
 	}
 	HIP_TRY(hipGetLastError());
 	return SRH_OK;
 }
 
 #ifdef SRH_PROFILE_PHASES
-static void mvs_print_phases(srh_context *c) {
+static void mvs_print_phases(const Lane &lane) {
 	Counters h;
-	if (hipMemcpy(&h, c->d_cnt, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return;
+	if (hipMemcpy(&h, lane.mem->cnt, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return;
 	if (h.dbg_waves)
 		fprintf(stderr, "[srh prof] staged MVS cost: %llu waves, %.1f windows and %.1f slots per wave; cycles per wave: life %.0f = "
 		        "set-up %.0f + copies %.0f + slots %.0f (%.0f per slot) + end %.0f\n", h.dbg_waves, (double)h.dbg_cycles/h.dbg_waves,
@@ -2618,11 +2605,26 @@ static void mvs_print_phases(srh_context *c) {
 // tails of this one's; the capacity check is made when the slot is used again or when any other entry point touches
 // the context (check_slot), and a view whose lists were cut is then redone.  Results are complete whenever a caller
 // can observe them.
-static void mvs_slot_swap(srh_context *c, MvsSlot &S) {
-	std::swap(c->stream, S.stream);
-	if (!S.own_buffers) return;
-	std::swap(c->band, S.band);
-	std::swap(c->d_cnt, S.d_cnt); std::swap(c->d_span, S.d_span);
+
+// the list path on `lane`, waited for: a pass whose lists were cut is repeated with the true maximum as the capacity
+static int mvs_run_and_wait(srh_context *c, const Lane &lane, int view, const int32_t *neigh, int nneigh, const srh_params *p,
+                            int y0, int y1, void *peaks_dev, int cmax)
+{
+	int rc;
+	for (int pass = 0; pass < 3; ++pass) {
+		if ((rc = mvs_list_launch(c, lane, view, neigh, nneigh, p, y0, y1, peaks_dev, cmax))) return rc;
+		int maxc = 0;
+		if ((rc = read_back(lane.stream, &maxc, lane.mem->span, sizeof(int)))) return rc;
+#ifdef SRH_PROFILE_PHASES
+		mvs_print_phases(lane);
+#endif
+		if (maxc <= cmax) { if (cmax > c->mvs_cmax_hint) c->mvs_cmax_hint = cmax; break; }
+		cmax = (maxc + 7) & ~7;
+	}
+	c->mvs_last = -1;
+	HIP_TRY(hipGetLastError());
+	c->stats.used_dense_path = 0;
+	return SRH_OK;
 }
 
 static int mvs_settle_slot(srh_context *c, int k) {
@@ -2631,44 +2633,32 @@ static int mvs_settle_slot(srh_context *c, int k) {
 	HIP_TRY(hipStreamSynchronize(S.stream));
 	S.pending = false;
 	if (k == c->mvs_last && S.own_buffers)                       // srh_get_stats reads the context's counters, on its stream
-		HIP_TRY(hipMemcpyAsync(c->d_cnt, S.d_cnt, sizeof(Counters), hipMemcpyDeviceToDevice, c->stream));
+		HIP_TRY(hipMemcpyAsync(c->mem.cnt, S.mem.cnt, sizeof(Counters), hipMemcpyDeviceToDevice, c->stream));
 #ifdef SRH_PROFILE_PHASES
-	mvs_slot_swap(c, S); mvs_print_phases(c); mvs_slot_swap(c, S);
+	mvs_print_phases(c->slot_lane(S));
 #endif
 	const int maxc = *S.h_maxc;
 	if (c->debug_trace) fprintf(stderr, "[srh trace] mvs view %d settled: capacity %d, longest list %d%s\n", S.view, S.cmax, maxc, maxc <= S.cmax ? "" : " -> redone");
 	if (maxc <= S.cmax) { if (S.cmax > c->mvs_cmax_hint) c->mvs_cmax_hint = S.cmax; return SRH_OK; }
-	// a list was cut: redo the view, waiting for it, with the true maximum as the capacity (on the context's own
-	// buffers, which slot 0 shares: nothing may be in flight)
+	// a list was cut: redo the view, waiting for it, with the true maximum as the capacity, on the main lane (the context's
+	// own scratch, which slot 0 shares: nothing may be in flight).  A refused band buffer returns straight out: the entry
+	// point that settles retries (with_thinner_bands) or reports it.
 	for (MvsSlot &O : c->mvs_slot) if (O.stream) HIP_TRY(hipStreamSynchronize(O.stream));
 	c->mvs_cmax_hint = std::max(c->mvs_cmax_hint, (maxc + 7) & ~7);
-	c->in_settle = true;
-	const int rc = srh_mvs_initial_estimate(c, S.view, S.neigh, S.nneigh, &S.p, S.y0, S.y1, nullptr);
-	c->in_settle = false;
-	return rc;
+	HIP_TRY(hipSetDevice(c->device));
+	return mvs_run_and_wait(c, c->main_lane(), S.view, S.neigh, S.nneigh, &S.p, S.y0, S.y1, nullptr, c->mvs_cmax_hint);
 }
 
 static int mvs_settle_all(srh_context *c) {
-	if (c->in_settle) return SRH_OK;
 	int rc;
 	for (int k = 0; k < SRH_MVS_SLOTS; ++k) if ((rc = mvs_settle_slot(c, k))) return rc;
 	return SRH_OK;
 }
 
-static int mvs_initial_estimate_run(srh_context *c, int view, const int32_t *neigh, int nneigh,
-                                    const srh_params *p, int y0, int y1, void *peaks_dev);
+// ---- the MultiViewStereo estimate driver: argument checks, a capacity guess, and one of three runners -- queue on a slot,
+// run and wait (the capacity loop), the one-thread-per-pixel kernel -- each on the lane it is handed --------
 
-extern "C" int srh_mvs_initial_estimate(srh_context *c, int view, const int32_t *neigh, int nneigh,
-                                        const srh_params *p, int y0, int y1, void *peaks_dev)
-{
-	if (!c) return fail(SRH_E_INVALID, "null context");
-	if (c->in_settle) return mvs_initial_estimate_run(c, view, neigh, nneigh, p, y0, y1, peaks_dev);   // (the redo of a settle: its caller retries)
-	return with_thinner_bands(c, [&] { return mvs_initial_estimate_run(c, view, neigh, nneigh, p, y0, y1, peaks_dev); });
-}
-
-static int mvs_initial_estimate_run(srh_context *c, int view, const int32_t *neigh, int nneigh,
-                                    const srh_params *p, int y0, int y1, void *peaks_dev)
-{
+static int mvs_check_args(srh_context *c, int view, const int32_t *neigh, int nneigh, const srh_params *p, const void *peaks_dev) {
 	int rc;
 	if ((rc = check_slot(c, view, true, false)) || (rc = check_params(p))) return rc;
 	if (nneigh < 0 || nneigh > SRH_MAX_NEIGH)
@@ -2679,113 +2669,122 @@ static int mvs_initial_estimate_run(srh_context *c, int view, const int32_t *nei
 		if ((rc = check_slot(c, neigh[i], true, false))) return rc;
 		if (neigh[i] == view) return fail(SRH_E_INVALID, "view %d listed as its own neighbour", view);
 	}
-	HIP_TRY(hipSetDevice(c->device));
+	return SRH_OK;
+}
+
+// The list capacity a view is first tried with: the longest list seen so far on this context -- or, with no hint yet, a guess
+// from the geometry: the longest coarse curve over the neighbours, estimate_list_capacity (round 5 started from 2 D, which
+// on the C4 rig cut every view's lists once: its first runTask took twice a later one)
+static int mvs_guess_cmax(srh_context *c, int view, const int32_t *neigh, int nneigh, const srh_params *p, int y0, int y1) {
+	if (c->mvs_cmax_hint > 0) return c->mvs_cmax_hint;
 	const ViewHost &A = c->views[view];
-	const int W = A.w, H = A.h;
-	if (y0 < 0) y0 = 0;
-	if (y1 <= 0 || y1 > H) y1 = H;
-	const int T = (2*p->window_radius + 1)*(2*p->window_radius + 1);
-	if (y1 <= y0) return SRH_OK;
-
-	const size_t wstride = SRH_WTILE;
-
-	// ---- default: walk kernel -> candidate lists -> cost kernel -> maximum (and merged top-K lists) over the
-	// neighbours.  Other radii stay on the one-thread-per-pixel kernels.
-	if (!c->force_generic && nneigh > 0 && p->window_radius == 2 && W < 65536 && H < 65536) {
-		// (no hint yet: a guess from the geometry -- the longest coarse curve over the neighbours, estimate_list_capacity;
-		// round 5 started from 2 D, which on the C4 rig cut every view's lists once: its first runTask took twice a later one)
-		int cmax = c->mvs_cmax_hint;
-		if (cmax <= 0) {
-			cmax = 64;
-			for (int i = 0; i < nneigh; ++i) {
-				int cm = 0, sm = 0;
-				const ViewHost &N = c->views[neigh[i]];
-				estimate_list_capacity(c->views[view].cam, N.cam, W, H, N.w, N.h, *p, y0, y1, cm, sm, true);
-				cmax = std::max(cmax, cm);
-			}
-		}
-		if (c->mvs_async && !peaks_dev && !c->in_settle) {
-			// queue the view on the next slot and return
-			const int k = c->mvs_turn;
-			c->mvs_turn = (c->mvs_turn + 1) % SRH_MVS_SLOTS;
-			MvsSlot &S = c->mvs_slot[k];
-			if ((rc = mvs_settle_slot(c, k))) return rc;
-			cmax = std::max(cmax, c->mvs_cmax_hint);
-			if (!S.stream) {
-				HIP_TRY(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
-				HIP_TRY(hipEventCreateWithFlags(&S.ev, hipEventDisableTiming));
-				HIP_TRY(hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
-				HIP_TRY(hipHostMalloc((void **)&S.h_maxc, sizeof(int)));
-				*S.h_maxc = 0;
-				S.own_buffers = k >= 1;
-				if (S.own_buffers) {
-					HIP_TRY(S.d_cnt.alloc(1));
-					HIP_TRY(S.d_span.alloc(4));
-				}
-			}
-			HIP_TRY(hipEventRecord(S.ev, c->stream));                 // after whatever the caller's stream holds
-			HIP_TRY(hipStreamWaitEvent(S.stream, S.ev, 0));
-			*S.h_maxc = 0;                                             // (a queue that fails half-way must not leave a stale length behind)
-			mvs_slot_swap(c, S);
-			rc = mvs_list_launch(c, view, neigh, nneigh, p, y0, y1, nullptr, cmax);
-			if (!rc && hipMemcpyAsync(S.h_maxc, c->d_span, sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess)
-				rc = fail(SRH_E_DEVICE, "queueing the list-length read-back failed");
-			mvs_slot_swap(c, S);
-			if (rc) {
-				// nothing of this view counts: drain what was queued, the slot is free again
-				(void)hipStreamSynchronize(S.stream);
-				S.pending = false;
-				return rc;
-			}
-			// A caller-owned stream (srh_set_stream) keeps its contract: work the caller enqueues on it after this call
-			// is ordered after the estimate.  (The context's own stream needs no such edge: every entry point settles.)
-			if (c->stream != c->own_stream) {
-				HIP_TRY(hipEventRecord(S.done, S.stream));
-				HIP_TRY(hipStreamWaitEvent(c->stream, S.done, 0));
-			}
-			S.pending = true;
-			S.view = view; S.nneigh = nneigh; S.y0 = y0; S.y1 = y1; S.cmax = cmax; S.p = *p;
-			for (int i = 0; i < nneigh; ++i) S.neigh[i] = neigh[i];
-			c->mvs_last = k;
-			c->stats.used_dense_path = 0;
-			return SRH_OK;
-		}
-		if ((rc = mvs_settle_all(c))) return rc;
-		for (int pass = 0; pass < 3; ++pass) {
-			if ((rc = mvs_list_launch(c, view, neigh, nneigh, p, y0, y1, peaks_dev, cmax))) return rc;
-			int maxc = 0;
-			HIP_TRY(hipMemcpyAsync(&maxc, c->d_span, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-			HIP_TRY(hipStreamSynchronize(c->stream));
-#ifdef SRH_PROFILE_PHASES
-			mvs_print_phases(c);
-#endif
-			if (maxc <= cmax) { if (cmax > c->mvs_cmax_hint) c->mvs_cmax_hint = cmax; break; }
-			cmax = (maxc + 7) & ~7;                                   // a list was cut: repeat with the true maximum
-		}
-		c->mvs_last = -1;
-		HIP_TRY(hipGetLastError());
-		c->stats.used_dense_path = 0;
-		return SRH_OK;
+	int cmax = 64;
+	for (int i = 0; i < nneigh; ++i) {
+		int cm = 0, sm = 0;
+		const ViewHost &N = c->views[neigh[i]];
+		estimate_list_capacity(A.cam, N.cam, A.w, A.h, N.w, N.h, *p, y0, y1, cm, sm, true);
+		cmax = std::max(cmax, cm);
 	}
-	if ((rc = mvs_settle_all(c))) return rc;
+	return cmax;
+}
 
+// queue the view's list path on the next slot's lane and return: the capacity check waits (mvs_settle_slot)
+static int mvs_queue_on_slot(srh_context *c, int view, const int32_t *neigh, int nneigh, const srh_params *p, int y0, int y1, int cmax) {
+	int rc;
+	const int k = c->mvs_turn;
+	c->mvs_turn = (c->mvs_turn + 1) % SRH_MVS_SLOTS;
+	MvsSlot &S = c->mvs_slot[k];
+	if ((rc = mvs_settle_slot(c, k))) return rc;
+	cmax = std::max(cmax, c->mvs_cmax_hint);
+	if (!S.stream) {
+		HIP_TRY(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
+		HIP_TRY(hipEventCreateWithFlags(&S.ev, hipEventDisableTiming));
+		HIP_TRY(hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
+		HIP_TRY(hipHostMalloc((void **)&S.h_maxc, sizeof(int)));
+		*S.h_maxc = 0;
+		S.own_buffers = k >= 1;
+		if (S.own_buffers) {
+			HIP_TRY(S.mem.cnt.alloc(1));
+			HIP_TRY(S.mem.span.alloc(4));
+		}
+	}
+	HIP_TRY(hipEventRecord(S.ev, c->stream));                     // after whatever the caller's stream holds
+	HIP_TRY(hipStreamWaitEvent(S.stream, S.ev, 0));
+	*S.h_maxc = 0;                                                 // (a queue that fails half-way must not leave a stale length behind)
+	const Lane lane = c->slot_lane(S);
+	rc = mvs_list_launch(c, lane, view, neigh, nneigh, p, y0, y1, nullptr, cmax);
+	if (!rc && hipMemcpyAsync(S.h_maxc, lane.mem->span, sizeof(int), hipMemcpyDeviceToHost, lane.stream) != hipSuccess)
+		rc = fail(SRH_E_DEVICE, "queueing the list-length read-back failed");
+	if (rc) {
+		// nothing of this view counts: drain what was queued, the slot is free again
+		(void)hipStreamSynchronize(S.stream);
+		S.pending = false;
+		return rc;
+	}
+	// A caller-owned stream (srh_set_stream) keeps its contract: work the caller enqueues on it after this call
+	// is ordered after the estimate.  (The context's own stream needs no such edge: every entry point settles.)
+	if (c->stream != c->own_stream) {
+		HIP_TRY(hipEventRecord(S.done, S.stream));
+		HIP_TRY(hipStreamWaitEvent(c->stream, S.done, 0));
+	}
+	S.pending = true;
+	S.view = view; S.nneigh = nneigh; S.y0 = y0; S.y1 = y1; S.cmax = cmax; S.p = *p;
+	for (int i = 0; i < nneigh; ++i) S.neigh[i] = neigh[i];
+	c->mvs_last = k;
+	c->stats.used_dense_path = 0;
+	return SRH_OK;
+}
+
+// other radii, no neighbours, option force_generic: the one-thread-per-pixel kernel, band by band
+static int mvs_generic_run(srh_context *c, const Lane &lane, int view, const int32_t *neigh, int nneigh, const srh_params *p,
+                           int y0, int y1, void *peaks_dev)
+{
+	int rc;
+	const int W = c->views[view].w, H = c->views[view].h;
+	const int T = (2*p->window_radius + 1)*(2*p->window_radius + 1);
 	const int rows = band_rows(c, W, H, T);
-	if ((rc = c->band.wbuf.ensure(wbuf_doubles(W, rows, T)))) return rc;
-	if ((rc = c->band.cost.ensure((size_t)rows*W*2*(size_t)std::max(nneigh, 1)))) return rc;   // per-neighbour best (cost, depth)
-	HIP_TRY(hipMemsetAsync(c->d_cnt, 0, sizeof(Counters), c->stream));
+	if ((rc = lane.mem->band.wbuf.ensure(wbuf_doubles(W, rows, T)))) return rc;
+	if ((rc = lane.mem->band.cost.ensure((size_t)rows*W*2*(size_t)std::max(nneigh, 1)))) return rc;   // per-neighbour best (cost, depth)
+	HIP_TRY(hipMemsetAsync(lane.mem->cnt, 0, sizeof(Counters), lane.stream));
 	for (int by = y0; by < y1; by += rows) {
 		if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
 		const int nr = std::min(rows, y1 - by);
-		run_weights(c, view, W, *p, by, nr, wstride);
-		{ Scope s(c, "mvs_generic_kernel");
-		  launch_mvs_generic(c->stream, c->d_views, view, neigh, nneigh, W, *p, by, nr, c->band.wbuf, wstride,
-		                     (double *)peaks_dev, c->force_generic ? nullptr : c->band.cost, c->d_cnt); }
+		run_weights(c, lane, view, W, *p, by, nr, SRH_WTILE);
+		{ Scope s(c, lane.stream, "mvs_generic_kernel");
+		  launch_mvs_generic(lane.stream, c->d_views, view, neigh, nneigh, W, *p, by, nr, lane.mem->band.wbuf, SRH_WTILE,
+		                     (double *)peaks_dev, c->force_generic ? nullptr : lane.mem->band.cost, lane.mem->cnt); }
 	}
 	HIP_TRY(hipGetLastError());
 	c->stats.used_dense_path = 0;
 	return SRH_OK;
 }
 
+// default: walk kernel -> candidate lists -> cost kernel -> maximum (and merged top-K lists) over the neighbours, queued on a
+// slot (option mvs_async, no peaks wanted) or waited for on the main lane.  Other radii stay on the one-thread-per-pixel kernel.
+static int mvs_initial_estimate_run(srh_context *c, int view, const int32_t *neigh, int nneigh,
+                                    const srh_params *p, int y0, int y1, void *peaks_dev)
+{
+	int rc;
+	if ((rc = mvs_check_args(c, view, neigh, nneigh, p, peaks_dev))) return rc;
+	HIP_TRY(hipSetDevice(c->device));
+	const int W = c->views[view].w, H = c->views[view].h;
+	if (y0 < 0) y0 = 0;
+	if (y1 <= 0 || y1 > H) y1 = H;
+	if (y1 <= y0) return SRH_OK;
+	const bool lists = !c->force_generic && nneigh > 0 && p->window_radius == 2 && W < 65536 && H < 65536;
+	const int cmax = lists ? mvs_guess_cmax(c, view, neigh, nneigh, p, y0, y1) : 0;
+	if (lists && c->mvs_async && !peaks_dev) return mvs_queue_on_slot(c, view, neigh, nneigh, p, y0, y1, cmax);
+	if ((rc = mvs_settle_all(c))) return rc;
+	if (lists) return mvs_run_and_wait(c, c->main_lane(), view, neigh, nneigh, p, y0, y1, peaks_dev, cmax);
+	return mvs_generic_run(c, c->main_lane(), view, neigh, nneigh, p, y0, y1, peaks_dev);
+}
+
+extern "C" int srh_mvs_initial_estimate(srh_context *c, int view, const int32_t *neigh, int nneigh,
+                                        const srh_params *p, int y0, int y1, void *peaks_dev)
+{
+	if (!c) return fail(SRH_E_INVALID, "null context");
+	return with_thinner_bands(c, [&] { return mvs_initial_estimate_run(c, view, neigh, nneigh, p, y0, y1, peaks_dev); });
+}
 // the view list travels once per run: MultiViewStereo::crossCheck is called per view with the same list, and a copy per
 // call (from caller memory: with a host wait) put a copy, two dispatch gaps and a host round trip between the kernels
 static int slots_to_device(srh_context *c, const int32_t *slots, int nviews) {
@@ -2811,7 +2810,7 @@ extern "C" int srh_mvs_cross_check(srh_context *c, const int32_t *slots, int nvi
 	HIP_TRY(hipSetDevice(c->device));
 	if ((rc = slots_to_device(c, slots, nviews))) return rc;
 	const ViewHost &A = c->views[slots[view_index]];
-	{ Scope s(c, "mvs_cross_check_kernel");
+	{ Scope s(c, c->stream, "mvs_cross_check_kernel");
 	  launch_mvs_cross_check(c->stream, c->d_views, c->d_slots, nviews, view_index, A.w, A.h, *p); }
 	HIP_TRY(hipGetLastError());
 	return SRH_OK;
@@ -2828,13 +2827,13 @@ extern "C" int srh_view_point_cloud(srh_context *c, int slot, const srh_params *
 	const size_t n = (size_t)v.w*v.h;
 	// scratch: xyz (3n doubles) | rgb (3n) | valid (n) | 3 counters, in the band buffer (free between runs)
 	const size_t need = 3*n + (3*n + n + 7)/8 + 4;
-	if ((rc = c->band.wbuf.ensure(need))) return rc;
-	double *d_xyz = c->band.wbuf;
-	uint8_t *d_rgb = reinterpret_cast<uint8_t *>(c->band.wbuf + 3*n);
+	if ((rc = c->mem.band.wbuf.ensure(need))) return rc;
+	double *d_xyz = c->mem.band.wbuf;
+	uint8_t *d_rgb = reinterpret_cast<uint8_t *>(c->mem.band.wbuf + 3*n);
 	uint8_t *d_valid = d_rgb + 3*n;
-	unsigned long long *d_counts = reinterpret_cast<unsigned long long *>(c->band.wbuf + need - 4);
+	unsigned long long *d_counts = reinterpret_cast<unsigned long long *>(c->mem.band.wbuf + need - 4);
 	HIP_TRY(hipMemsetAsync(d_counts, 0, 3*sizeof(unsigned long long), c->stream));
-	{ Scope s(c, "point_cloud_kernel");
+	{ Scope s(c, c->stream, "point_cloud_kernel");
 	  launch_point_cloud(c->stream, c->d_views, slot, v.w, v.h, *p, d_xyz, d_rgb, d_valid, d_counts); }
 	HIP_TRY(hipGetLastError());
 	unsigned long long hc[3] = { 0, 0, 0 };
@@ -2924,7 +2923,7 @@ extern "C" int srh_mvs_fuse(srh_context *c, const int32_t *slots, int nviews, co
 	// stage 0: every view's point map, by the kernel of srh_view_point_cloud
 	for (int i = 0; i < nviews; ++i) {
 		const ViewHost &v = c->views[slots[i]];
-		Scope s(c, "point_cloud_kernel");
+		Scope s(c, c->stream, "point_cloud_kernel");
 		launch_point_cloud(c->stream, c->d_views, slots[i], v.w, v.h, *p, const_cast<double *>(fv[i].pts), nullptr,
 		                   const_cast<uint8_t *>(fv[i].valid), d_pc);
 	}
@@ -2948,12 +2947,12 @@ extern "C" int srh_mvs_fuse(srh_context *c, const int32_t *slots, int nviews, co
 		}
 		const ViewHost &v = c->views[slots[i]];
 		const size_t n = (size_t)v.w*v.h;
-		{ Scope s(c, "fuse_view_kernel");
+		{ Scope s(c, c->stream, "fuse_view_kernel");
 		  launch_fuse_view(c->stream, c->d_views, c->d_slots, nviews, i, v.w, v.h, *p, thr, gap, f.min_views, d_fv, d_emit, stage,
 		                   d_bcount, d_counters); }
-		{ Scope s(c, "fuse_scan_kernel");
+		{ Scope s(c, c->stream, "fuse_scan_kernel");
 		  launch_fuse_scan(c->stream, d_bcount, (int)((n + SRH_FUSE_BLOCK - 1)/SRH_FUSE_BLOCK), d_offs, d_counters); }
-		{ Scope s(c, "fuse_scatter_kernel");
+		{ Scope s(c, c->stream, "fuse_scatter_kernel");
 		  launch_fuse_scatter(c->stream, i, n, d_emit, stage, d_offs, out, cap); }
 	}
 	HIP_TRY(hipGetLastError());
@@ -3031,18 +3030,18 @@ static int filter_view(srh_context *c, int slot, const srh_params *p, int flags,
 	// scratch: G (n doubles) | hole list (n u32) | 4 counters, in the band buffer (free between runs)
 	const size_t need = n + (n + 1)/2 + 4;
 	int rc;
-	if ((rc = c->band.wbuf.ensure(need))) return rc;
-	double *G = c->band.wbuf;
-	uint32_t *holes = reinterpret_cast<uint32_t *>(c->band.wbuf + n);
-	unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(c->band.wbuf + need - 4);
+	if ((rc = c->mem.band.wbuf.ensure(need))) return rc;
+	double *G = c->mem.band.wbuf;
+	uint32_t *holes = reinterpret_cast<uint32_t *>(c->mem.band.wbuf + n);
+	unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(c->mem.band.wbuf + need - 4);
 	HIP_TRY(hipMemsetAsync(d_cnt, 0, 4*sizeof(unsigned long long), c->stream));
 	if (gaps) {
-		Scope s(c, "filter_gap_kernel");
+		Scope s(c, c->stream, "filter_gap_kernel");
 		launch_filter_gaps(c->stream, v.depth, G, v.w, v.h, gap, d_cnt);
 	} else if (median) HIP_TRY(hipMemcpyAsync(G, v.depth, n*sizeof(double), hipMemcpyDeviceToDevice, c->stream));
 	HIP_TRY(hipGetLastError());
 	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
-	{ Scope s(c, "filter_holes_kernel");
+	{ Scope s(c, c->stream, "filter_holes_kernel");
 	  launch_filter_holes(c->stream, v.mask, v.depth, v.w, v.h, median, holes, d_cnt); }
 	HIP_TRY(hipGetLastError());
 	unsigned long long hc[4] = { 0, 0, 0, 0 };
@@ -3052,7 +3051,7 @@ static int filter_view(srh_context *c, int slot, const srh_params *p, int flags,
 		if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
 		if (emit7) progress(c, 7, "Filtering invalid pixels...");
 		// (option "filter_replay": the replay is the kernel's only selection today -- every hole takes it either way)
-		{ Scope s(c, "filter_median_kernel");
+		{ Scope s(c, c->stream, "filter_median_kernel");
 		  launch_filter_median(c->stream, c->d_views, slot, *p, G, holes, (int)hc[0], v.depth, d_cnt); }
 		HIP_TRY(hipGetLastError());
 	} else if (gaps) HIP_TRY(hipMemcpyAsync(v.depth, G, n*sizeof(double), hipMemcpyDeviceToDevice, c->stream));
@@ -3121,7 +3120,7 @@ extern "C" int srh_epipolar_curves(srh_context *c, int ref, int oth, const srh_p
 	if (e == hipSuccess && out_bytes) e = d_out.alloc((size_t)nq*2*(size_t)max_pts);
 	if (e == hipSuccess) e = hipMemcpyAsync(d_xy, xy, (size_t)nq*2*sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
 	if (e == hipSuccess) {
-		Scope s(c, "epipolar_curves_kernel");
+		Scope s(c, c->stream, "epipolar_curves_kernel");
 		launch_epipolar_curves(c->stream, c->d_views, ref, oth, *p, mvs ? 1 : 0, nq, d_xy, d_out, max_pts, d_n);
 		e = hipGetLastError();
 	}
@@ -3212,9 +3211,9 @@ static int mvs_mrf_drive(srh_context *c, int n, const MvsRun *runs, const srh_mr
 			const MvsRun &r = runs[i]; Live &l = live[i];
 			if (!l.active) continue;
 			hipError_t e;
-			if (round == 0) { Scope s(c, "mrf_data_kernel", prof); e = launch_mrf_setup(r.st, *r.scratch, r.w, r.h, r.K, m->beta, m->lambda, m->phi_u, r.peaks, l.lay); }
-			else            { Scope s(c, "mrf_pass_kernel", prof); e = launch_mrf_sweep(r.st, *r.scratch, r.w, r.h, r.K, m->psi_u, l.iters); }
-			if (e == hipSuccess) { Scope s(c, "mrf_energy_kernel", prof); e = launch_mrf_energy(r.st, *r.scratch, r.w, r.h, r.K, m->psi_u); }
+			if (round == 0) { Scope s(c, c->stream, "mrf_data_kernel", prof); e = launch_mrf_setup(r.st, *r.scratch, r.w, r.h, r.K, m->beta, m->lambda, m->phi_u, r.peaks, l.lay); }
+			else            { Scope s(c, c->stream, "mrf_pass_kernel", prof); e = launch_mrf_sweep(r.st, *r.scratch, r.w, r.h, r.K, m->psi_u, l.iters); }
+			if (e == hipSuccess) { Scope s(c, c->stream, "mrf_energy_kernel", prof); e = launch_mrf_energy(r.st, *r.scratch, r.w, r.h, r.K, m->psi_u); }
 			if (e == hipSuccess) e = hipMemcpyAsync(&hs[i], l.lay.energy, sizeof(HostState), hipMemcpyDeviceToHost, r.st);
 			if (e != hipSuccess) return failed(i);
 		}
@@ -3230,7 +3229,7 @@ static int mvs_mrf_drive(srh_context *c, int n, const MvsRun *runs, const srh_mr
 			++l.iters;
 			if (l.prev - l.e > m->min_energy_drop && l.left-- > 0) continue;     // do { ... } while (prev - energy > 5 && numIters-- > 0)
 			l.active = false; --nactive;
-			Scope s(c, "mrf_depth_kernel", prof);
+			Scope s(c, c->stream, "mrf_depth_kernel", prof);
 			if (launch_mrf_depth(r.st, c->d_views, r.slot, *r.scratch, r.w, r.h, r.K) != hipSuccess) return failed(i);
 		}
 	}
@@ -3360,7 +3359,7 @@ static int mvs_sgm_drive(srh_context *c, int n, const MvsRun *runs, const srh_mv
 	                                                              hipGetErrorString(hipGetLastError()))); };
 	for (int i = 0; i < n; ++i) {
 		const MvsRun &r = runs[i];
-		Scope s(c, "mrf_data_kernel", prof);
+		Scope s(c, c->stream, "mrf_data_kernel", prof);
 		if (launch_mvs_sgm_setup(r.st, *r.scratch, r.w, r.h, r.K, m->beta, m->lambda, m->phi_u, r.peaks) != hipSuccess) return failed("setup", i);
 	}
 	int paths = 0;
@@ -3370,7 +3369,7 @@ static int mvs_sgm_drive(srh_context *c, int n, const MvsRun *runs, const srh_mv
 		if (cancelled(c)) return stop(fail(SRH_E_CANCELLED, "cancelled"));
 		for (int i = 0; i < n; ++i) {
 			const MvsRun &r = runs[i];
-			Scope s(c, names[k], prof);
+			Scope s(c, c->stream, names[k], prof);
 			if (launch_mvs_sgm_path(r.st, *r.scratch, r.w, r.h, r.K, m->psi_u, k, paths == 0) != hipSuccess) return failed("path", i);
 		}
 		++paths;
@@ -3380,8 +3379,8 @@ static int mvs_sgm_drive(srh_context *c, int n, const MvsRun *runs, const srh_mv
 		MvsSgmLayout lay;
 		mvs_sgm_layout(*r.scratch, r.w, r.h, lay);
 		hipError_t e;
-		{ Scope s(c, "mvs_sgm_readoff_kernel", prof); e = launch_mvs_sgm_readoff(r.st, c->d_views, r.slot, *r.scratch, r.w, r.h, r.K); }
-		if (e == hipSuccess) { Scope s(c, "mrf_energy_kernel", prof); e = launch_mvs_sgm_energy(r.st, *r.scratch, r.w, r.h, r.K, m->psi_u); }
+		{ Scope s(c, c->stream, "mvs_sgm_readoff_kernel", prof); e = launch_mvs_sgm_readoff(r.st, c->d_views, r.slot, *r.scratch, r.w, r.h, r.K); }
+		if (e == hipSuccess) { Scope s(c, c->stream, "mrf_energy_kernel", prof); e = launch_mvs_sgm_energy(r.st, *r.scratch, r.w, r.h, r.K, m->psi_u); }
 		if (e == hipSuccess) e = hipMemcpyAsync(&c->mvsgm_host[i], lay.energy, sizeof(double), hipMemcpyDeviceToHost, r.st);
 		if (e != hipSuccess) return failed("read-off", i);
 	}
@@ -3515,7 +3514,7 @@ static int tv_stage_costs(srh_context *c, const TvStage &T, int ref, int oth, co
 	int rc;
 	const ViewHost &v = c->views[ref];
 	if ((rc = tv_stage_reserve(c, T, v.w, v.h, p->num_depth_levels, true))) return rc;
-	Scope s(c, "twoview_label_costs_kernel");
+	Scope s(c, c->stream, "twoview_label_costs_kernel");
 	HIP_TRY(launch_twoview_label_costs(c->stream, c->d_views, ref, oth, v.w, *p, c->cost_kind == SRH_COST_SAD, 0, v.h,
 	                                   (2*p->window_radius + 1)*p->bad_ret, (c->*T.state).costs, nullptr));
 	return SRH_OK;
@@ -3563,7 +3562,7 @@ static int tvmrf_run(srh_context *c, int slot, const srh_params *p, int L, const
 	HIP_TRY(launch_twoview_mrf_setup(c->stream, c->tvmrf.scratch, w, h, L, lay));
 	struct { double energy, pad; unsigned status[4]; } hs;
 	auto energy = [&](double &e) -> int {
-		{ Scope s(c, "twoview_mrf_energy_kernel");
+		{ Scope s(c, c->stream, "twoview_mrf_energy_kernel");
 		  HIP_TRY(launch_twoview_mrf_energy(c->stream, c->tvmrf.scratch, costs, w, h, L, m->lambda, m->smooth_max)); }
 		HIP_TRY(hipMemcpyAsync(&hs, lay.energy, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
 		HIP_TRY(hipStreamSynchronize(c->stream));
@@ -3580,12 +3579,12 @@ static int tvmrf_run(srh_context *c, int slot, const srh_params *p, int L, const
 	do {
 		if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
 		prev = e;
-		{ Scope s(c, "twoview_mrf_pass_kernel");
+		{ Scope s(c, c->stream, "twoview_mrf_pass_kernel");
 		  HIP_TRY(launch_twoview_mrf_sweep(c->stream, c->tvmrf.scratch, costs, w, h, L, m->lambda, m->smooth_max, iters)); }
 		if ((rc = energy(e))) return rc;
 		++iters;
 	} while (prev - e > m->min_energy_drop && num_iters-- > 0);
-	{ Scope s(c, "twoview_mrf_depth_kernel");
+	{ Scope s(c, c->stream, "twoview_mrf_depth_kernel");
 	  HIP_TRY(launch_twoview_mrf_depth(c->stream, c->d_views, slot, *p, c->tvmrf.scratch, w, h, L)); }
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	c->tvmrf.finished(w, h, L);
@@ -3634,7 +3633,7 @@ extern "C" int srh_twoview_label_costs(srh_context *c, int ref, int oth, const s
 	if (dcost.alloc(n) != hipSuccess || (pixel_out && dpix.alloc(2*n) != hipSuccess))
 		return done(fail(SRH_E_DEVICE, "label costs: no device memory for %zu bytes", n*(sizeof(double) + (pixel_out ? 2*sizeof(int32_t) : 0))));
 	hipError_t e;
-	{ Scope s(c, "twoview_label_costs_kernel");
+	{ Scope s(c, c->stream, "twoview_label_costs_kernel");
 	  e = launch_twoview_label_costs(c->stream, c->d_views, ref, oth, v.w, *p, c->cost_kind == SRH_COST_SAD, y0, y1 - y0,
 	                                 (2*p->window_radius + 1)*p->bad_ret, dcost, pixel_out ? (int32_t *)dpix : nullptr); }
 	if (e == hipSuccess) e = hipMemcpyAsync(cost_out, dcost, n*sizeof(double), hipMemcpyDeviceToHost, c->stream);
@@ -3725,14 +3724,14 @@ static int tvsgm_run(srh_context *c, int slot, const srh_params *p, int L, const
 		if (!(m->path_mask >> k & 1)) continue;
 		// (nothing of the slot has been written yet: the depth map is the read-off's, after the last direction)
 		if (cancelled(c)) { HIP_TRY(hipStreamSynchronize(c->stream)); return fail(SRH_E_CANCELLED, "cancelled"); }
-		{ Scope s(c, names[k]);
+		{ Scope s(c, c->stream, names[k]);
 		  HIP_TRY(launch_twoview_sgm_path(c->stream, c->tvsgm.scratch, costs, w, h, L, m->lambda, m->smooth_max, k, paths == 0)); }
 		++paths;
 	}
 	v.wta_flags = 0;                                            // no scan made this depth map: the WTA by-products are stale
-	{ Scope s(c, "twoview_sgm_readoff_kernel");
+	{ Scope s(c, c->stream, "twoview_sgm_readoff_kernel");
 	  HIP_TRY(launch_twoview_sgm_readoff(c->stream, c->d_views, slot, *p, c->tvsgm.scratch, w, h, L)); }
-	{ Scope s(c, "twoview_mrf_energy_kernel");
+	{ Scope s(c, c->stream, "twoview_mrf_energy_kernel");
 	  HIP_TRY(launch_twoview_sgm_energy(c->stream, c->tvsgm.scratch, costs, w, h, L, m->lambda, m->smooth_max)); }
 	double e = 0.0;
 	HIP_TRY(hipMemcpyAsync(&e, lay.energy, sizeof(e), hipMemcpyDeviceToHost, c->stream));
@@ -3814,11 +3813,11 @@ extern "C" int srh_epipolar_preview(srh_context *c, int ref, int oth, double zmi
 	HIP_TRY(hipSetDevice(c->device));
 	const size_t nout = (size_t)nq*nd*2;
 	// scratch in the band buffer: [xy | out | counts]
-	if ((rc = c->band.wbuf.ensure((size_t)2*nq + nout + (size_t)(nq + 1)/2 + 2))) return rc;
-	double *d_xy = c->band.wbuf, *d_out = c->band.wbuf + 2*(size_t)nq;
+	if ((rc = c->mem.band.wbuf.ensure((size_t)2*nq + nout + (size_t)(nq + 1)/2 + 2))) return rc;
+	double *d_xy = c->mem.band.wbuf, *d_out = c->mem.band.wbuf + 2*(size_t)nq;
 	int32_t *d_cnt = reinterpret_cast<int32_t *>(d_out + nout);
 	HIP_TRY(hipMemcpyAsync(d_xy, xy, (size_t)2*nq*sizeof(double), hipMemcpyHostToDevice, c->stream));
-	{ Scope s(c, "epipolar_preview_kernel");
+	{ Scope s(c, c->stream, "epipolar_preview_kernel");
 	  launch_epipolar_preview(c->stream, c->d_views, ref, oth, zmin, zmax, nd, nq, d_xy, d_out, d_cnt); }
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(out_xy, d_out, nout*sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -3836,11 +3835,11 @@ extern "C" int srh_refraction_error(srh_context *c, int v1, int v2, int n, const
 	HIP_TRY(hipSetDevice(c->device));
 	std::vector<double> err((size_t)n);
 	if (n > 0) {
-		if ((rc = c->band.wbuf.ensure((size_t)5*n))) return rc;
-		double *d1 = c->band.wbuf, *d2 = c->band.wbuf + 2*(size_t)n, *de = c->band.wbuf + 4*(size_t)n;
+		if ((rc = c->mem.band.wbuf.ensure((size_t)5*n))) return rc;
+		double *d1 = c->mem.band.wbuf, *d2 = c->mem.band.wbuf + 2*(size_t)n, *de = c->mem.band.wbuf + 4*(size_t)n;
 		HIP_TRY(hipMemcpyAsync(d1, p1, (size_t)2*n*sizeof(double), hipMemcpyHostToDevice, c->stream));
 		HIP_TRY(hipMemcpyAsync(d2, p2, (size_t)2*n*sizeof(double), hipMemcpyHostToDevice, c->stream));
-		{ Scope s(c, "refraction_error_kernel");
+		{ Scope s(c, c->stream, "refraction_error_kernel");
 		  launch_refraction_error(c->stream, c->d_views, v1, v2, n, d1, d2, de); }
 		HIP_TRY(hipGetLastError());
 		HIP_TRY(hipMemcpyAsync(err.data(), de, (size_t)n*sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -3935,11 +3934,11 @@ extern "C" int srh_comm_allgather_host(srh_context *c, const double *send_host, 
 	// windows from on its own stream: finish the estimates in flight first, like every other entry point
 	if ((rc = mvs_settle_all(c))) return rc;
 	// staging in the band scratch (free between runs): [send | recv]
-	if ((rc = c->band.wbuf.ensure(count*(size_t)(c->comm_ranks + 1)))) return rc;
-	HIP_TRY(hipMemcpyAsync(c->band.wbuf, send_host, count*sizeof(double), hipMemcpyHostToDevice, c->stream));
-	if (const char *e = rccl_allgather_f64(c->comm, c->band.wbuf, c->band.wbuf + count, count, c->stream))
+	if ((rc = c->mem.band.wbuf.ensure(count*(size_t)(c->comm_ranks + 1)))) return rc;
+	HIP_TRY(hipMemcpyAsync(c->mem.band.wbuf, send_host, count*sizeof(double), hipMemcpyHostToDevice, c->stream));
+	if (const char *e = rccl_allgather_f64(c->comm, c->mem.band.wbuf, c->mem.band.wbuf + count, count, c->stream))
 		return comm_failed(c, "all-gather", e);
-	HIP_TRY(hipMemcpyAsync(recv_host, c->band.wbuf + count, count*(size_t)c->comm_ranks*sizeof(double), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipMemcpyAsync(recv_host, c->mem.band.wbuf + count, count*(size_t)c->comm_ranks*sizeof(double), hipMemcpyDeviceToHost, c->stream));
 	if (const char *e = rccl_wait_stream(c->comm, c->stream, "the all-gather")) return comm_failed(c, "all-gather", e);   // (bounded: never a bare hipStreamSynchronize behind a collective)
 	return SRH_OK;
 }
@@ -3960,8 +3959,8 @@ extern "C" int srh_comm_allgather_views(srh_context *c, const int32_t *slots, in
 	auto shard = [&](int r, int &lo, int &hi) { const int base = nviews/world, extra = nviews % world;
 	                                            lo = r*base + std::min(r, extra); hi = lo + base + (r < extra ? 1 : 0); };
 	// [send | recv] in the band scratch (free between runs); everything below is ordered on the context's stream
-	if ((rc = c->band.wbuf.ensure((size_t)(world + 1)*per*npix))) return rc;
-	double *send = c->band.wbuf, *recv = c->band.wbuf + (size_t)per*npix;
+	if ((rc = c->mem.band.wbuf.ensure((size_t)(world + 1)*per*npix))) return rc;
+	double *send = c->mem.band.wbuf, *recv = c->mem.band.wbuf + (size_t)per*npix;
 	launch_fill(c->stream, send, (size_t)per*npix, __builtin_nan(""));
 	int lo, hi;
 	shard(rank, lo, hi);
@@ -4000,7 +3999,7 @@ extern "C" int srh_get_stats(srh_context *c, srh_stats *out) {
 	HIP_TRY(hipSetDevice(c->device));
 	int rc = mvs_settle_all(c);
 	if (rc) return rc;
-	rc = fetch_counters(c, c->stats.used_dense_path);
+	rc = fetch_counters(c, c->main_lane(), c->stats.used_dense_path);
 	if (rc) return rc;
 	c->stats.band_budget_bytes = (int64_t)c->budget_used;
 	*out = c->stats;

@@ -441,3 +441,52 @@ def test_caller_owned_stream(hip_ctx):
     finally:
         hip_ctx.set_option("mvs_async", 1)
     assert ptr and np.array_equal(_bits(ref0), _bits(got0))
+
+
+@pytest.mark.parametrize("shape, budget_mb", [((33, 9, 40), 0), ((65, 12, 8), 1)])
+def test_a_failed_second_pass_leaves_the_context_on_its_own_lane(shape, budget_mb):
+    """srh_twoview_compute runs its second pass on a stream and band buffers of its own.  A call cancelled while that pass
+    is being queued (the progress hook raises the flag at step 3) leaves nothing of it behind: the next single pass runs
+    on, and its statistics are read from, the context's own stream, buffers and counters -- the counters of a fresh
+    context's pass -- and the next srh_twoview_compute gives the bits of a context that was never cancelled.
+    budget_mb = 1: thin bands, the cancel is met inside the band loop of the second pass."""
+    import small_shapes
+    case = small_shapes.small_twoview(*shape, 5, 1)
+    cams, p = cases.hip_inputs(case)
+
+    def fresh():
+        ctx = capi.Context(0)
+        cases.upload_case(ctx, case, cams)
+        if budget_mb:
+            ctx.set_option("band_budget_mb", budget_mb)
+        return ctx
+
+    with fresh() as ctx:
+        ctx.twoview_wta(1, 0, p)
+        st = ctx.stats()
+        base = (st["n_pixels"], st["n_eval"])
+    with fresh() as ctx:
+        want = ctx.twoview_compute(0, 1, p)
+    with fresh() as ctx:
+        flag = C.c_int(0)
+        steps = []
+
+        def hook(step, stage):
+            steps.append((step, stage))
+            if step == 3:
+                flag.value = 1
+
+        ctx.set_hooks(flag, hook)
+        try:
+            with pytest.raises(capi.StereoHipError) as e:
+                ctx.twoview_compute(0, 1, p)
+            assert e.value.code == capi.SRH_E_CANCELLED
+            assert steps[-1] == (3, "Computing cost volume for right image...")
+        finally:
+            flag.value = 0
+            ctx.set_hooks(None, None)
+        ctx.twoview_wta(1, 0, p)
+        st = ctx.stats()
+        assert (st["n_pixels"], st["n_eval"]) == base
+        got = ctx.twoview_compute(0, 1, p)
+        assert np.array_equal(_bits(got[0]), _bits(want[0])) and np.array_equal(_bits(got[1]), _bits(want[1]))
