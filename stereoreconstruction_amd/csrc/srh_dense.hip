@@ -301,6 +301,32 @@ __device__ __forceinline__ void geo_pc2(const double (&w)[2*R+1][2*R+1], GeoLds 
 	double pr[4], fa[2];
 	(geo_pc2_step<R, TWD, KG, J>(w, tg, g, pr, mL, s2, fa, sa), ...);
 }
+// The constants of one pixel while its window is in registers (w; tg = the pixel's first tap in plane 4 of the tile): when
+// every tap is usable (gray value valid, weight above the cut-off), meanL, totalWeight and sum2 of twoviewstereo.cpp:917-976
+// do not depend on the candidate.  Same tap order, same operations as pixel_constants (srh_ncc.hpp).  stamp(5 / 6): the
+// profile build's clocks after each sweep.
+template <int R, int TWD, class Stamp>
+__device__ __forceinline__ PixelConstants geo_pixel_constants(const double (&w)[2*R+1][2*R+1], GeoLds tg, double weight_cutoff, Stamp &&stamp)
+{
+	constexpr int WS = 2*R + 1, NT = WS*WS, KG = GEO_AHEAD < NT ? GEO_AHEAD : NT;
+	double g[KG];
+	// every tap usable = every gray value valid (finite; NaN otherwise, and one NaN makes the sum meanL NaN: the weights are
+	// finite) and every weight above the cut-off (the smallest is): one v_min_f64 per tap instead of two compares and the
+	// mask arithmetic (which the compiler kept as 121 lane masks parked in VGPR lanes until the end)
+	double mL = 0, tw = 0, wmin = __builtin_inf();
+	geo_pc_fill<R, TWD, KG>(tg, g, std::make_integer_sequence<int, KG>{});
+	geo_pc1<R, TWD, KG>(w, tg, g, mL, tw, wmin, std::make_integer_sequence<int, NT + 2>{});
+	bool all = mL == mL && wmin > weight_cutoff;
+	stamp(5);
+	double s2 = 0, sa = 0;
+	if (all && !(tw < 1e-10)) {
+		mL /= tw;
+		geo_pc_fill<R, TWD, KG>(tg, g, std::make_integer_sequence<int, KG>{});
+		geo_pc2<R, TWD, KG>(w, tg, g, mL, s2, sa, std::make_integer_sequence<int, NT + 3>{});
+		stamp(6);
+	} else all = false;
+	return PixelConstants{ mL, tw, s2, sa, all };
+}
 
 template <int R, bool WIMG>
 __global__ __launch_bounds__(GW_TW*GW_ROWS)
@@ -464,32 +490,9 @@ void geodesic_reg_kernel(const ViewDev *__restrict__ views, int ref, const doubl
 		}
 	}
 	GEO_STAMP(2)
-	if (pconst && active) {
-		// Per-pixel constants of the dense kernel's fast cost form, while the window is in registers: when every tap
-		// is usable (gray value valid, weight above the cut-off), meanL, totalWeight and sum2 of
-		// twoviewstereo.cpp:917-976 do not depend on the candidate.  Same tap order, same operations.
-		constexpr int NT = WS*WS, KG = GEO_AHEAD < NT ? GEO_AHEAD : NT;
-		const GeoLds tg = (GeoLds)&tile[4][wv][i];
-		double g[KG];
-		// every tap usable = every gray value valid (finite; NaN otherwise, and one NaN makes the sum meanL NaN: the weights are
-		// finite) and every weight above the cut-off (the smallest is): one v_min_f64 per tap instead of two compares and the
-		// mask arithmetic (which the compiler kept as 121 lane masks parked in VGPR lanes until the end)
-		double mL = 0, tw = 0, wmin = __builtin_inf();
-		geo_pc_fill<R, TWD, KG>(tg, g, std::make_integer_sequence<int, KG>{});
-		geo_pc1<R, TWD, KG>(w, tg, g, mL, tw, wmin, std::make_integer_sequence<int, NT + 2>{});
-		bool all = mL == mL && wmin > P.weight_cutoff;
-		GEO_STAMP(5)
-		double s2 = 0, sa = 0;
-		if (all && !(tw < 1e-10)) {
-			mL /= tw;
-			geo_pc_fill<R, TWD, KG>(tg, g, std::make_integer_sequence<int, KG>{});
-			geo_pc2<R, TWD, KG>(w, tg, g, mL, s2, sa, std::make_integer_sequence<int, NT + 3>{});
-			GEO_STAMP(6)
-		} else all = false;
-		double *pc = pconst + ((size_t)trow*W + cx)*SRH_PC;
-		pc[0] = mL; pc[1] = tw; pc[2] = s2; pc[3] = all ? 1.0/tw : 0.0;   // all taps usable: != 0, and then 1/totalWeight (the one-pass form multiplies by it)
-		pc[4] = sa; pc[5] = 0.0;
-	}
+	if (pconst && active)
+		pconst_store(pconst + ((size_t)trow*W + cx)*SRH_PC,
+		             geo_pixel_constants<R, TWD>(w, (GeoLds)&tile[4][wv][i], P.weight_cutoff, [&](int k) { GEO_STAMP(k) }));
 #ifdef SRH_PROFILE_PHASES
 	GEO_STAMP(3)
 	if (i == 0 && rowok) {
@@ -673,24 +676,9 @@ void geodesic_dma_kernel(const ViewDev *__restrict__ views, int ref, const doubl
 					if (st[k]) { typedef double d2v __attribute__((ext_vector_type(2))); d2v t; t.x = v[k].x; t.y = v[k].y; __builtin_nontemporal_store(t, reinterpret_cast<d2v *>(wrow + goff[k])); }
 			}
 		}
-		if (pconst && active) {
-			constexpr int NT = WS*WS, KG = GEO_AHEAD < NT ? GEO_AHEAD : NT;
-			const GeoLds tg = (GeoLds)&tile[buf][4][wv][i];
-			double g[KG];
-			double mL = 0, tw = 0, wmin = __builtin_inf();
-			geo_pc_fill<R, TWD, KG>(tg, g, std::make_integer_sequence<int, KG>{});
-			geo_pc1<R, TWD, KG>(w, tg, g, mL, tw, wmin, std::make_integer_sequence<int, NT + 2>{});
-			bool all = mL == mL && wmin > P.weight_cutoff;
-			double s2 = 0, sa = 0;
-			if (all && !(tw < 1e-10)) {
-				mL /= tw;
-				geo_pc_fill<R, TWD, KG>(tg, g, std::make_integer_sequence<int, KG>{});
-				geo_pc2<R, TWD, KG>(w, tg, g, mL, s2, sa, std::make_integer_sequence<int, NT + 3>{});
-			} else all = false;
-			double *pc = pconst + ((size_t)trow*W + cx)*SRH_PC;
-			pc[0] = mL; pc[1] = tw; pc[2] = s2; pc[3] = all ? 1.0/tw : 0.0;   // all taps usable: != 0, and then 1/totalWeight (the one-pass form multiplies by it)
-			pc[4] = sa; pc[5] = 0.0;
-		}
+		if (pconst && active)
+			pconst_store(pconst + ((size_t)trow*W + cx)*SRH_PC,
+			             geo_pixel_constants<R, TWD>(w, (GeoLds)&tile[buf][4][wv][i], P.weight_cutoff, [](int) {}));
 	}
 }
 
@@ -777,21 +765,10 @@ void adaptive_reg_kernel(const ViewDev *__restrict__ views, int ref, srh_params 
 		}
 	}
 	if (pconst) {
-		double s2 = 0, sa = 0;
-		if (all && !(tw < 1e-10)) {
-			mL /= tw;
-#pragma unroll 1
-			for (int a = 0; a < WS; ++a) {
-				double wr[WS];
+		pconst_store(pconst + ((size_t)trow*W + cx)*SRH_PC, pixel_constants_finish<WS, true>([&](int a, double *gl, double *wt) {
 #pragma unroll
-				for (int b = 0; b < WS; ++b) wr[b] = wb[(size_t)a*wra + (size_t)b*wcb];
-#pragma unroll
-				for (int b = 0; b < WS; ++b) { const double t = wr[b]*gt[a][i + b] - mL; s2 += t*t; sa += __builtin_fma(wr[b], gt[a][i + b], -mL); }   // (sa: fused terms, SRH_PC)
-			}
-		} else all = false;
-		double *pc = pconst + ((size_t)trow*W + cx)*SRH_PC;
-		pc[0] = mL; pc[1] = tw; pc[2] = s2; pc[3] = all ? 1.0/tw : 0.0;   // all taps usable: != 0, and then 1/totalWeight (the one-pass form multiplies by it)
-		pc[4] = sa; pc[5] = 0.0;
+			for (int b = 0; b < WS; ++b) { wt[b] = wb[(size_t)a*wra + (size_t)b*wcb]; gl[b] = gt[a][i + b]; }
+		}, mL, tw, all));
 	}
 }
 
@@ -895,52 +872,15 @@ struct DenseSmem {
 	int glist_n;
 };
 
-// general (any validity pattern) cost of one candidate from the LDS tiles.  Skipped taps add
-// +0.0 to every sum, which leaves each partial sum bit-for-bit unchanged, so the selects
-// below are the reference's "continue" (twoviewstereo.cpp:920-938, 955-972).
+// general (any validity pattern) cost of one candidate from the LDS tiles: window_exact_cost (srh_walk.hpp) with the
+// tiles' strides
 template <int R, int DC_NCB, int DC_CHUNK>
 __device__ __noinline__ double dense_cost_general(const DenseSmem<R, DC_NCB, DC_CHUNK> &S, int i, int rc,
                                                   double weight_cutoff, double bad_ret, double max_color_diff)
 {
-	constexpr int WS = 2*R + 1;
-	constexpr int WP = DenseSmem<R, DC_NCB, DC_CHUNK>::WP;
-	double meanL = 0, meanR = 0, totalWeight = 0.0;
-#pragma unroll 1
-	for (int row = 0; row < WS; ++row) {
-		double gl[WS], gr[WS], wt[WS];
-#pragma unroll
-		for (int col = 0; col < WS; ++col) { gl[col] = S.lt[row][i + col]; gr[col] = S.rt[row][rc + col]; wt[col] = S.w[i][row*WP + col]; }
-#pragma unroll
-		for (int col = 0; col < WS; ++col) {
-			const bool ok = gl[col] == gl[col] && gr[col] == gr[col] && wt[col] > weight_cutoff;
-			const double pl = wt[col]*gl[col], pr = wt[col]*gr[col];
-			meanL += ok ? pl : 0.0;
-			meanR += ok ? pr : 0.0;
-			totalWeight += ok ? wt[col] : 0.0;
-		}
-	}
-	if (totalWeight < 1e-10) return bad_ret;
-	meanL /= totalWeight;
-	meanR /= totalWeight;
-	double sum1 = 0, sum2 = 0, sum3 = 0;
-#pragma unroll 1
-	for (int row = 0; row < WS; ++row) {
-		double gl[WS], gr[WS], wt[WS];
-#pragma unroll
-		for (int col = 0; col < WS; ++col) { gl[col] = S.lt[row][i + col]; gr[col] = S.rt[row][rc + col]; wt[col] = S.w[i][row*WP + col]; }
-#pragma unroll
-		for (int col = 0; col < WS; ++col) {
-			const bool ok = gl[col] == gl[col] && gr[col] == gr[col] && wt[col] > weight_cutoff;
-			const double a = wt[col]*gl[col] - meanL;
-			const double b = wt[col]*gr[col] - meanR;
-			const double ab = a*b, aa = a*a, bb = b*b;
-			sum1 += ok ? ab : 0.0;
-			sum2 += ok ? aa : 0.0;
-			sum3 += ok ? bb : 0.0;
-		}
-	}
-	const double v = 255*(1.0 - fabs(sum1) / sqrt(sum2 * sum3));
-	return (v < max_color_diff) ? v : max_color_diff;
+	typedef DenseSmem<R, DC_NCB, DC_CHUNK> Smem;
+	return window_exact_cost<R>(&S.w[i][0], Smem::WP, 1, &S.lt[0][i], &S.rt[0][rc], Smem::LW, Smem::RW,
+	                            weight_cutoff, bad_ret, max_color_diff);
 }
 
 #ifdef SRH_EXPERIMENT

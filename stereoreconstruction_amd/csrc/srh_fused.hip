@@ -64,51 +64,14 @@ struct FusedSmem {
 	__device__ __forceinline__ static int slot(int p, int k) { return p*MAXC + ((k + 2*p) & (MAXC - 1)); }
 };
 
-// cost of one candidate from the LDS tiles, any validity pattern (twoviewstereo.cpp:909-977): skipped taps
-// add +0.0 to every sum, which leaves each partial sum bit-for-bit unchanged.
+// cost of one candidate from the LDS tiles, any validity pattern: window_exact_cost (srh_walk.hpp) with the tiles' strides
 template <int R, int MAXC>
 __device__ __noinline__ double fused_cost_general(const FusedSmem<R, MAXC> &S, int p, int rc,
                                                   double weight_cutoff, double bad_ret, double max_color_diff)
 {
-	constexpr int WS = 2*R + 1;
-	constexpr int WP = FusedSmem<R, MAXC>::WP;
-	double meanL = 0, meanR = 0, totalWeight = 0.0;
-#pragma unroll 1
-	for (int row = 0; row < WS; ++row) {
-		double gl[WS], gr[WS], wt[WS];
-#pragma unroll
-		for (int col = 0; col < WS; ++col) { gl[col] = S.lt[row][p + col]; gr[col] = S.rt[row][rc + col]; wt[col] = S.w[p][row*WP + col]; }
-#pragma unroll
-		for (int col = 0; col < WS; ++col) {
-			const bool ok = gl[col] == gl[col] && gr[col] == gr[col] && wt[col] > weight_cutoff;
-			const double pl = wt[col]*gl[col], pr = wt[col]*gr[col];
-			meanL += ok ? pl : 0.0;
-			meanR += ok ? pr : 0.0;
-			totalWeight += ok ? wt[col] : 0.0;
-		}
-	}
-	if (totalWeight < 1e-10) return bad_ret;
-	meanL /= totalWeight;
-	meanR /= totalWeight;
-	double sum1 = 0, sum2 = 0, sum3 = 0;
-#pragma unroll 1
-	for (int row = 0; row < WS; ++row) {
-		double gl[WS], gr[WS], wt[WS];
-#pragma unroll
-		for (int col = 0; col < WS; ++col) { gl[col] = S.lt[row][p + col]; gr[col] = S.rt[row][rc + col]; wt[col] = S.w[p][row*WP + col]; }
-#pragma unroll
-		for (int col = 0; col < WS; ++col) {
-			const bool ok = gl[col] == gl[col] && gr[col] == gr[col] && wt[col] > weight_cutoff;
-			const double a = wt[col]*gl[col] - meanL;
-			const double b = wt[col]*gr[col] - meanR;
-			const double ab = a*b, aa = a*a, bb = b*b;
-			sum1 += ok ? ab : 0.0;
-			sum2 += ok ? aa : 0.0;
-			sum3 += ok ? bb : 0.0;
-		}
-	}
-	const double v = 255*(1.0 - fabs(sum1) / sqrt(sum2 * sum3));
-	return (v < max_color_diff) ? v : max_color_diff;
+	typedef FusedSmem<R, MAXC> Smem;
+	return window_exact_cost<R>(&S.w[p][0], Smem::WP, 1, &S.lt[0][p], &S.rt[0][rc], Smem::LW, Smem::RW,
+	                            weight_cutoff, bad_ret, max_color_diff);
 }
 
 // next set joint bit at index >= from, or -1
@@ -289,33 +252,11 @@ void twoview_fused_kernel(const ViewDev *__restrict__ views, int ref, int oth, s
 	// ---- D (wave 1, meanwhile): per-pixel constants of the fast form -- meanL, totalWeight, sum2 do not depend on
 	// the candidate when every tap of the window is usable on both sides (same tap order as twoviewstereo.cpp:917-976)
 	if (seqD) {
-		bool all = (x0 + q < W);
-		double mL = 0, tw = 0;
-#pragma unroll 1
-		for (int row = 0; row < WS; ++row) {
-			double gl[WS], wt[WS];
+		const PixelConstants c = pixel_constants<WS, false>([&](int row, double *gl, double *wt) {
 #pragma unroll
 			for (int col = 0; col < WS; ++col) { gl[col] = S.lt[row][q + col]; wt[col] = S.w[q][row*WP + col]; }
-#pragma unroll
-			for (int col = 0; col < WS; ++col) {
-				if (!(gl[col] == gl[col] && wt[col] > P.weight_cutoff)) all = false;
-				mL += wt[col]*gl[col];
-				tw += wt[col];
-			}
-		}
-		double s2 = 0;
-		if (all && !(tw < 1e-10)) {
-			mL /= tw;
-#pragma unroll 1
-			for (int row = 0; row < WS; ++row) {
-				double gl[WS], wt[WS];
-#pragma unroll
-				for (int col = 0; col < WS; ++col) { gl[col] = S.lt[row][q + col]; wt[col] = S.w[q][row*WP + col]; }
-#pragma unroll
-				for (int col = 0; col < WS; ++col) { const double a = wt[col]*gl[col] - mL; s2 += a*a; }
-			}
-		} else all = false;
-		S.meanL[q] = mL; S.totalW[q] = tw; S.sum2[q] = s2; S.lall[q] = all ? 1 : 0;
+		}, P.weight_cutoff, x0 + q < W);
+		S.meanL[q] = c.mL; S.totalW[q] = c.tw; S.sum2[q] = c.s2; S.lall[q] = c.all ? 1 : 0;
 	}
 	FZ_STAMP(1);
 	__syncthreads();

@@ -106,9 +106,7 @@ __global__ void weights_kernel(const ViewDev *__restrict__ views, int ref, srh_p
 					sa += __builtin_fma(wt_, gl_, -mL);                      // (fused: srh_internal.hpp, SRH_PC)
 				}
 		} else all = false;
-		double *pc = pconst + ((size_t)(q / W)*W + cx)*SRH_PC;
-		pc[0] = mL; pc[1] = tw; pc[2] = s2; pc[3] = all ? 1.0/tw : 0.0;   // all taps usable: != 0, and then 1/totalWeight (the one-pass form multiplies by it)
-		pc[4] = sa; pc[5] = 0.0;
+		pconst_store(pconst + ((size_t)(q / W)*W + cx)*SRH_PC, PixelConstants{ mL, tw, s2, sa, all });
 	}
 #undef WTAP
 }

@@ -236,30 +236,11 @@ void twoview_list_cost_kernel(const ViewDev *__restrict__ views, int ref, int ot
 
 	// ---- per-pixel constants of the all-taps-usable form (one lane per pixel)
 	if (g == 0) {
-		bool all = (x < W) && S.count[i] > 0;
-		double mL = 0, tw = 0;
-#pragma unroll 1
-		for (int row = 0; row < WS; ++row)
+		const PixelConstants c = pixel_constants<WS, false>([&](int row, double *gl, double *wt) {
 #pragma unroll
-			for (int col = 0; col < WS; ++col) {
-				const double gl = S.lt[row][i + col];
-				const double wt = S.w[i][row*WP + col];
-				if (!(gl == gl && wt > P.weight_cutoff)) all = false;
-				mL += wt*gl;
-				tw += wt;
-			}
-		double s2 = 0;
-		if (all && !(tw < 1e-10)) {
-			mL /= tw;
-#pragma unroll 1
-			for (int row = 0; row < WS; ++row)
-#pragma unroll
-				for (int col = 0; col < WS; ++col) {
-					const double a = S.w[i][row*WP + col]*S.lt[row][i + col] - mL;
-					s2 += a*a;
-				}
-		} else all = false;
-		S.meanL[i] = mL; S.totalW[i] = tw; S.sum2[i] = s2; S.lall[i] = all ? 1 : 0;
+			for (int col = 0; col < WS; ++col) { gl[col] = S.lt[row][i + col]; wt[col] = S.w[i][row*WP + col]; }
+		}, P.weight_cutoff, (x < W) && S.count[i] > 0);
+		S.meanL[i] = c.mL; S.totalW[i] = c.tw; S.sum2[i] = c.s2; S.lall[i] = c.all ? 1 : 0;
 	}
 	__syncthreads();
 
@@ -324,53 +305,16 @@ void twoview_list_cost_kernel(const ViewDev *__restrict__ views, int ref, int ot
 				const double v = 255*(1.0 - fabs(s1) / sqrt(s2 * s3));
 				result = (v < P.max_color_diff) ? v : P.max_color_diff;
 			} else {
-				// any validity pattern; a skipped tap adds +0.0
-				double meanL = 0, meanR = 0, totalWeight = 0.0;
-#pragma unroll 1
-				for (int row = 0; row < WS; ++row) {
-					double gr[WS];
+				// any validity pattern (ncc_select_cost, srh_ncc.hpp); the other view's taps by bounds-checked gathers
+				result = ncc_select_cost<WS>([&](int row, double *gl, double *gr, double *wt) {
 #pragma unroll
 					for (int col = 0; col < WS; ++col) {
 						const int gx = cx - R + col, gy = cy - R + row;
 						gr[col] = (gx >= 0 && gy >= 0 && gx < OW && gy < OH) ? Rv.gray_tv[(size_t)gy*OW + gx] : nan;
 					}
 #pragma unroll
-					for (int col = 0; col < WS; ++col) {
-						const double gl = CS.lt[row][i + col], wt = CS.w[i][row*WP + col];
-						const bool ok = gl == gl && gr[col] == gr[col] && wt > P.weight_cutoff;
-						const double pl = wt*gl, pr = wt*gr[col];
-						meanL += ok ? pl : 0.0;
-						meanR += ok ? pr : 0.0;
-						totalWeight += ok ? wt : 0.0;
-					}
-				}
-				if (totalWeight < 1e-10) result = P.bad_ret;
-				else {
-					meanL /= totalWeight;
-					meanR /= totalWeight;
-					double sum1 = 0, sum2 = 0, sum3 = 0;
-#pragma unroll 1
-					for (int row = 0; row < WS; ++row) {
-						double gr[WS];
-#pragma unroll
-						for (int col = 0; col < WS; ++col) {
-							const int gx = cx - R + col, gy = cy - R + row;
-							gr[col] = (gx >= 0 && gy >= 0 && gx < OW && gy < OH) ? Rv.gray_tv[(size_t)gy*OW + gx] : nan;
-						}
-#pragma unroll
-						for (int col = 0; col < WS; ++col) {
-							const double gl = CS.lt[row][i + col], wt = CS.w[i][row*WP + col];
-							const bool ok = gl == gl && gr[col] == gr[col] && wt > P.weight_cutoff;
-							const double a = wt*gl - meanL, b = wt*gr[col] - meanR;
-							const double ab = a*b, aa = a*a, bb = b*b;
-							sum1 += ok ? ab : 0.0;
-							sum2 += ok ? aa : 0.0;
-							sum3 += ok ? bb : 0.0;
-						}
-					}
-					const double v = 255*(1.0 - fabs(sum1) / sqrt(sum2 * sum3));
-					result = (v < P.max_color_diff) ? v : P.max_color_diff;
-				}
+					for (int col = 0; col < WS; ++col) { gl[col] = CS.lt[row][i + col]; wt[col] = CS.w[i][row*WP + col]; }
+				}, P.weight_cutoff, P.bad_ret, P.max_color_diff);
 			}
 			crow[k] = result;
 		}

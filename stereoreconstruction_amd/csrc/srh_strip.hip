@@ -210,53 +210,19 @@ __device__ __forceinline__ void st_dma4(const void *src, void *dst, int nbytes, 
 	}
 }
 
-// general (any validity pattern) cost of one candidate from the LDS tiles: dense_cost_general of srh_dense.hip
-// with the rows taken from the rings.  Skipped taps add +0.0 to every sum (twoviewstereo.cpp:920-938, 955-972).
+// general (any validity pattern) cost of one candidate from the LDS tiles: ncc_select_cost (srh_ncc.hpp) with the rows
+// taken from the rings
 template <int R, int NBUF>
 __device__ __noinline__ double strip_cost_general(const StripSmem<R, NBUF> &S, int wb, int s0, int i, int rc,
                                                   double weight_cutoff, double bad_ret, double max_color_diff)
 {
 	typedef StripSmem<R, NBUF> Smem;
 	constexpr int WS = Smem::WS, NS = Smem::NS;
-	double meanL = 0, meanR = 0, totalWeight = 0.0;
-#pragma unroll 1
-	for (int row = 0; row < WS; ++row) {
+	return ncc_select_cost<WS>([&](int row, double *gl, double *gr, double *wt) {
 		const int sl = s0 + row >= NS ? s0 + row - NS : s0 + row;
-		double gl[WS], gr[WS], wt[WS];
 #pragma unroll
 		for (int col = 0; col < WS; ++col) { gl[col] = S.lt[sl][i + col]; gr[col] = S.rt[sl][rc + col]; wt[col] = S.w[wb][row][i][col]; }
-#pragma unroll
-		for (int col = 0; col < WS; ++col) {
-			const bool ok = gl[col] == gl[col] && gr[col] == gr[col] && wt[col] > weight_cutoff;
-			const double pl = wt[col]*gl[col], pr = wt[col]*gr[col];
-			meanL += ok ? pl : 0.0;
-			meanR += ok ? pr : 0.0;
-			totalWeight += ok ? wt[col] : 0.0;
-		}
-	}
-	if (totalWeight < 1e-10) return bad_ret;
-	meanL /= totalWeight;
-	meanR /= totalWeight;
-	double sum1 = 0, sum2 = 0, sum3 = 0;
-#pragma unroll 1
-	for (int row = 0; row < WS; ++row) {
-		const int sl = s0 + row >= NS ? s0 + row - NS : s0 + row;
-		double gl[WS], gr[WS], wt[WS];
-#pragma unroll
-		for (int col = 0; col < WS; ++col) { gl[col] = S.lt[sl][i + col]; gr[col] = S.rt[sl][rc + col]; wt[col] = S.w[wb][row][i][col]; }
-#pragma unroll
-		for (int col = 0; col < WS; ++col) {
-			const bool ok = gl[col] == gl[col] && gr[col] == gr[col] && wt[col] > weight_cutoff;
-			const double a = wt[col]*gl[col] - meanL;
-			const double b = wt[col]*gr[col] - meanR;
-			const double ab = a*b, aa = a*a, bb = b*b;
-			sum1 += ok ? ab : 0.0;
-			sum2 += ok ? aa : 0.0;
-			sum3 += ok ? bb : 0.0;
-		}
-	}
-	const double v = 255*(1.0 - fabs(sum1) / sqrt(sum2 * sum3));
-	return (v < max_color_diff) ? v : max_color_diff;
+	}, weight_cutoff, bad_ret, max_color_diff);
 }
 
 // One 8-column block of pixel `pi` in the BLOCKED select form: any validity pattern (image border, masked taps,
@@ -591,29 +557,11 @@ void twoview_strip_cost_kernel(const StripArgs A)
 				}
 				// ... and the pixel's constants over [bra, brb), one lane per pixel, in the reference's order and operations
 				if (g == 0) {
-					bool all = x < W;
-					double mL = 0, tw = 0;
-					for (int row = bra; row < brb; ++row) {
+					const PixelConstants c = pixel_constants<WS, false>([&](int row, double *gl, double *wt) {
 						const int sl = s0 + row >= NS ? s0 + row - NS : s0 + row;
-						for (int col = 0; col < WS; ++col) {
-							const double gl = CS.lt[sl][i + col], wt = CS.w[wcur][row][i][col];
-							all = all && gl == gl && wt > A.weight_cutoff;
-							mL += wt*gl;
-							tw += wt;
-						}
-					}
-					double s2 = 0;
-					if (all && !(tw < 1e-10)) {
-						mL /= tw;
-						for (int row = bra; row < brb; ++row) {
-							const int sl = s0 + row >= NS ? s0 + row - NS : s0 + row;
-							for (int col = 0; col < WS; ++col) {
-								const double t = CS.w[wcur][row][i][col]*CS.lt[sl][i + col] - mL;
-								s2 += t*t;
-							}
-						}
-					} else all = false;
-					S.pc[cur][i][0] = mL; S.pc[cur][i][1] = tw; S.pc[cur][i][2] = s2; S.pc[cur][i][3] = all ? 1.0/tw : 0.0;
+						for (int col = 0; col < WS; ++col) { gl[col] = CS.lt[sl][i + col]; wt[col] = CS.w[wcur][row][i][col]; }
+					}, A.weight_cutoff, x < W, bra, brb);
+					S.pc[cur][i][0] = c.mL; S.pc[cur][i][1] = c.tw; S.pc[cur][i][2] = c.s2; S.pc[cur][i][3] = c.all ? 1.0/c.tw : 0.0;
 				}
 				__syncthreads();
 				// candidate column cs + k: its window covers staged columns k .. k + 2R

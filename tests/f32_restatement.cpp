@@ -203,6 +203,19 @@ bool stable_ulps(double v, int n) {
 
 extern "C" {
 
+// gray_plane and pix_const as they stand above, for tests/ncc_host.cpp (which holds the library's srh_ncc.hpp to them):
+// out = w*h doubles; c = mL, tw, s2, SA
+void f32r_gray_plane(const sro_image *img, double *out) {
+	std::vector<double> g;
+	gray_plane(img, g);
+	for (size_t i = 0; i < g.size(); ++i) out[i] = g[i];
+}
+int f32r_pix_const(const double *w, const double *l, int T, double cutoff, double c[4]) {
+	const PixConst p = pix_const(w, l, T, cutoff);
+	c[0] = p.mL; c[1] = p.tw; c[2] = p.s2; c[3] = p.SA;
+	return p.all ? 1 : 0;
+}
+
 // One window given tap by tap (T = (2R+1)^2 values each, row-major; NaN in l or r = unusable): the path taken (1 fast,
 // 2 general), both forms' stored values and bounds.  The hand-built cases of the host test.
 int f32r_window(const double *w, const double *l, const double *r, int T, const sro_params *p,
