@@ -515,7 +515,7 @@ extern "C" void srh_params_mvs_defaults(srh_params *p) {
 	p->window_radius = 2;                 // multiviewstereo.cpp:91
 }
 
-// The constants of the certified arithmetic's error bound for these parameters (srh_internal.hpp, CertBound; DESIGN.md
+// The constants of the certified arithmetic's error bound for these parameters (srh_wta.hpp, CertBound; DESIGN.md
 // 2b): host arithmetic only -- what tests/test_cert_bound.py checks against an exact replay of the three arithmetics.
 extern "C" int srh_cert_bound(const srh_params *p, int mvs, srh_cert_info *out) {
 	if (!p || !out) return fail(SRH_E_INVALID, "null argument");

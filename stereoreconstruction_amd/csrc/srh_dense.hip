@@ -902,7 +902,7 @@ void exp_set(int repeat, int lds_pad) {
 // fused (one rounding instead of two): half the FP64 instructions, costs differ from the reference's in the last
 // bits (|delta cost| ~ 1e-13), which can flip a winner only between near-tied candidates -- the mismatch rate is
 // measured, not assumed (bench.py --arith fma, tests/test_gpu_arith_modes.py).
-// AR = 3: the certified mode (srh_internal.hpp, CertBound): fused loops, and every fast-form value stored
+// AR = 3: the certified mode (srh_wta.hpp, CertBound): fused loops, and every fast-form value stored
 // by the rule of the certified scan -- NaN for a candidate the bound does not cover, the clamp itself above clamp + e0,
 // anything else unclamped.
 template <int R, int DC_NCB, int DC_CHUNK, int MINW, int AR>
@@ -913,7 +913,7 @@ void twoview_dense_cost_kernel(const ViewDev *__restrict__ views, int ref, int o
                                Counters *__restrict__ cnt, const double *__restrict__ pconst, const CertBound cb,
                                const PixRange *__restrict__ prange)
 {
-	constexpr bool FMA = AR != 0, CERT = AR == 3 || AR == 5, ONEPASS = AR == 5;   // 5: the certified one-pass form (srh_internal.hpp, CertBound)
+	constexpr bool FMA = AR != 0, CERT = AR == 3 || AR == 5, ONEPASS = AR == 5;   // 5: the certified one-pass form (srh_wta.hpp, CertBound)
 	constexpr int WS = 2*R + 1;
 	constexpr int T = WS*WS;
 	typedef DenseSmem<R, DC_NCB, DC_CHUNK> Smem;
@@ -1552,27 +1552,11 @@ __device__ __forceinline__ int wave_max_i32(int v) {
 	return v;
 }
 
-struct TwoViewScanState {
-	double minCost, secondBest;
-	int wcol;                 // winning column relative to lo, -1 = none
-	int pcol;                 // WTA: the column that held minCost before the last improvement (its cost is secondBest), -1 = none
-};
-
+// The scans below keep the reference's rule in a WtaState<int, WTA> (srh_wta.hpp): candidates are columns relative to
+// lo, -1 = none.
 // CERT: the cost rows hold FUSED costs (twoview_strip_cost_kernel<.., 3>): the reference's decisions are replayed on
 // them, and a pixel is FLAGGED -- appended to cflag[1..], count in cflag[0] -- when a decision is not covered by the
-// error bound (CertBound, srh_internal.hpp).  What a stored value x says about the cost in the reference's arithmetic:
-//   x == max_color_diff, or x > max_color_diff + e0 (bad_ret)   the very same number ("sure": the strip kernel stores the
-//                                                               clamp itself only when the fused value is above it by more
-//                                                               than e0; larger values come from the exact select forms);
-//   x NaN                                                       an uncertified candidate: the pixel is flagged;
-//   anything else                                               within e0 of it (select-form candidates are exact and
-//                                                               counted as e0; a fused value in (clamp, clamp + e0] stands
-//                                                               for a reference value in [x - e0, clamp]).
-// A comparison a < b on fused values is the reference's when |a - b| exceeds the two bounds (+ the rounding of cost +
-// margin), or when both sides are sure (the same numbers go through the same operations).  The state (minCost,
-// secondBest, winner) then evolves identically, by induction over the candidate sequence; an unflagged pixel made every
-// comparison the way the reference's arithmetic makes it, so its winner -- and its depth, which is geometry -- are the
-// reference's bits.
+// error bound: cert_step_doubt and cert_ratio_doubt of srh_wta.hpp, where the argument is written out.
 // LISTED: the exact scan of the flagged pixels only (lane k takes pixel cflag[1 + k]; their cost rows were refilled in
 // the reference's arithmetic by twoview_refill_kernel).
 // one tile (64 pixels of a row; LISTED: 64 listed pixels) of twoview_scan_kernel; `bid` = its index in the band
@@ -1651,7 +1635,7 @@ void twoview_scan_tile(const int bid, const ViewDev *__restrict__ views, int ref
 	if (active) {
 		n_pix = 1;
 		const double *crow = cost + ((size_t)trow*((W + DC_TP - 1)/DC_TP) + (x/DC_TP))*(size_t)cstride*DC_TP + (x % DC_TP);
-		TwoViewScanState st = { __builtin_inf(), __builtin_inf(), -1, -1 };
+		WtaState<int, WTA> st(-1);
 		int qn = 0;
 		// pexact (the band's per-pixel constants, given when the cost kernel redoes uncovered candidates in place): a pixel the
 		// cost kernel evaluated in the reference's arithmetic throughout (cert_pixel_exact) -- every stored cost is the
@@ -1675,23 +1659,9 @@ void twoview_scan_tile(const int bid, const ViewDev *__restrict__ views, int ref
 #pragma unroll
 			for (int k = 0; k < SC_QN; ++k) {
 				if (k < count) {
-					const double cv = c[k];
-					if (CERT) {
-						// (a candidate column seen again while it is the winner compares its own cost with itself: false in
-						// either arithmetic since wta_margin >= 0)
-						// (tolerance: the two bounds + the rounding of cost + margin, 2u|t| <= e0/2: a side that is not sure is a
-						// cost, a clamp or a bad_ret of magnitude <= 1e5 -- CertBound::ok)
-						const double t = cv + P.wta_margin;
-						if (!(fabs(t - st.minCost) > 2.5*cb.e0) && col[k] != st.wcol &&
-						    !(cert_sure(cv, P.max_color_diff, cb.m_hi) && cert_sure(st.minCost, P.max_color_diff, cb.m_hi)) &&
-						    !(px_sure && cv == cv)) n_flag = 1;              // (NaN: flagged, whatever the pixel)
-					}
-					if (cv + P.wta_margin < st.minCost) {           // twoviewstereo.cpp:293-301
-						st.secondBest = st.minCost;
-						st.minCost = cv;
-						if (WTA) st.pcol = st.wcol;
-						st.wcol = col[k];
-					}
+					const double cv = c[k], t = cv + P.wta_margin;
+					if (CERT && cert_step_doubt(cv, t, st.minCost, col[k] == st.win, px_sure, cb, P.max_color_diff)) n_flag = 1;
+					st.take_sum(t, cv, col[k]);
 				}
 			}
 		};
@@ -1754,19 +1724,13 @@ void twoview_scan_tile(const int bid, const ViewDev *__restrict__ views, int ref
 		}
 		if (qn > 0) flush(qn);
 
-		if (st.wcol >= 0)
-			depth = candidate_depth(L.cam, Rv.cam, P, ray, lo + st.wcol, y);
-		if (st.minCost > P.second_best_factor*st.secondBest)
+		if (st.win >= 0)
+			depth = candidate_depth(L.cam, Rv.cam, P, ray, lo + st.win, y);
+		if (st.rejected(P.second_best_factor))
 			depth = __builtin_inf();
-		if (CERT && st.wcol >= 0) {
-			// the ratio test (twoviewstereo.cpp:303-305) on fused values: minCost within e0, factor*secondBest within |factor|*e0
-			const double rhs = P.second_best_factor*st.secondBest;
-			const double tol = __builtin_fma(fmin(fabs(rhs), 1e300), 1e-15, (1.0 + fabs(P.second_best_factor))*cb.e0);
-			if (!(fabs(st.minCost - rhs) > tol) && !px_sure &&
-			    !(cert_sure(st.minCost, P.max_color_diff, cb.m_hi) && cert_sure(st.secondBest, P.max_color_diff, cb.m_hi))) n_flag = 1;
-		}
+		if (CERT && st.win >= 0 && cert_ratio_doubt(st.minCost, st.secondBest, P.second_best_factor, px_sure, cb, P.max_color_diff)) n_flag = 1;
 		if (CERT && n_flag) cflag[1 + atomicAdd(&cflag[0], 1u)] = (uint32_t)((size_t)trow*W + x);
-		if (WTA) { owin = st.wcol >= 0 ? lo + st.wcol : -1; orun = st.pcol >= 0 ? lo + st.pcol : -1; }
+		if (WTA) { owin = st.win >= 0 ? lo + st.win : -1; orun = st.run >= 0 ? lo + st.run : -1; }
 	}
 	if (listed_on && x < W) L.depth[(size_t)y*W + x] = depth;
 	if (WTA && listed_on && x < W) wta_store(wout, (size_t)W*L.h, (size_t)y*W + x, owin, owin >= 0 ? y : -1, orun, orun >= 0 ? y : -1);
@@ -2138,8 +2102,7 @@ bool twoview_tscan_tile(const int bid, const ViewDev *__restrict__ views, int re
 	if (active) {
 		n_pix_acc += 1;
 		const double *crow = cost + ((size_t)trow*((W + DC_TP - 1)/DC_TP) + (x/DC_TP))*(size_t)cstride*DC_TP + (x % DC_TP);
-		double minCost = __builtin_inf(), secondBest = __builtin_inf();
-		int wcol = -1, pcol = -1;                                      // (pcol, WTA: who held minCost before the last improvement)
+		WtaState<int, WTA> st(-1);
 		bool px_sure = false;
 		if (CERT && pexact) { const double *pc = pexact + ((size_t)trow*W + x)*SRH_PC; px_sure = cert_pixel_exact(cb, pc[2], pc[3]); }
 		const int xm = tid - smin;                                     // smask index of column x + s: tid + (s - smin)
@@ -2193,32 +2156,23 @@ bool twoview_tscan_tile(const int bid, const ViewDev *__restrict__ views, int re
 					const double cv = c[u];
 					const double t = on ? cv + P.wta_margin : __builtin_inf();
 					if (CERT) {
-						// (twoview_scan_kernel<true, false>'s test; the comparison is decided beyond the bound almost always: the rest
-						// of the test only when some lane's is not)
-						const bool nearby = on && !(fabs(t - minCost) > 2.5*cb.e0);
-						if (__any(nearby)) {
-							if (nearby && kk[u] != wcol &&
-							    !(cert_sure(cv, P.max_color_diff, cb.m_hi) && cert_sure(minCost, P.max_color_diff, cb.m_hi)) &&
-							    !(px_sure && cv == cv)) n_flag = 1;
+						// (the comparison is decided beyond the bound almost always: the rest of the test only when some lane's is not)
+						if (__any(on && cert_step_near(t, st.minCost, cb))) {
+							if (on && cert_step_doubt(cv, t, st.minCost, kk[u] == st.win, px_sure, cb, P.max_color_diff)) n_flag = 1;
 						}
 					}
-					if (t < minCost) { secondBest = minCost; minCost = cv; if (WTA) pcol = wcol; wcol = kk[u]; }   // twoviewstereo.cpp:293-301
+					st.take_sum(t, cv, kk[u]);                              // (a lane that is off: t = +inf, never taken)
 				}
 			}
 		};
 		// (first visits only: sound while wta_margin >= 0 -- with a negative margin a revisited winner would "beat" itself and
 		// move secondBest -- so a negative margin walks every visit like the left-border tiles)
 		if (xt + smin < 0 || !(P.wta_margin >= 0.0)) lookups(std::true_type()); else lookups(std::false_type());
-		if (wcol >= 0) depth = candidate_depth(L.cam, Rv.cam, P, cam_unproject(L.cam, (x + 0.5) / P.image_scale, (y + 0.5) / P.image_scale), lo + wcol, y);
-		if (minCost > P.second_best_factor*secondBest) depth = __builtin_inf();
-		if (CERT && wcol >= 0) {
-			const double rhs = P.second_best_factor*secondBest;
-			const double tol = __builtin_fma(fmin(fabs(rhs), 1e300), 1e-15, (1.0 + fabs(P.second_best_factor))*cb.e0);
-			if (!(fabs(minCost - rhs) > tol) && !px_sure &&
-			    !(cert_sure(minCost, P.max_color_diff, cb.m_hi) && cert_sure(secondBest, P.max_color_diff, cb.m_hi))) n_flag = 1;
-		}
+		if (st.win >= 0) depth = candidate_depth(L.cam, Rv.cam, P, cam_unproject(L.cam, (x + 0.5) / P.image_scale, (y + 0.5) / P.image_scale), lo + st.win, y);
+		if (st.rejected(P.second_best_factor)) depth = __builtin_inf();
+		if (CERT && st.win >= 0 && cert_ratio_doubt(st.minCost, st.secondBest, P.second_best_factor, px_sure, cb, P.max_color_diff)) n_flag = 1;
 		if (CERT && n_flag) cflag[1 + atomicAdd(&cflag[0], 1u)] = (uint32_t)((size_t)trow*W + x);
-		if (WTA) { owin = wcol >= 0 ? lo + wcol : -1; orun = pcol >= 0 ? lo + pcol : -1; }
+		if (WTA) { owin = st.win >= 0 ? lo + st.win : -1; orun = st.run >= 0 ? lo + st.run : -1; }
 	}
 	if (x < W) L.depth[(size_t)y*W + x] = depth;
 	if (WTA && x < W) wta_store(wout, (size_t)W*L.h, (size_t)y*W + x, owin, owin >= 0 ? y : -1, orun, orun >= 0 ? y : -1);
@@ -2393,18 +2347,14 @@ void twoview_redo_kernel(const ViewDev *__restrict__ views, int ref, int oth, sr
 		// (5) running minimum, ratio test, depth of the winner
 		if (tid == 0) {
 			const int n = s_n;
-			double minCost = __builtin_inf(), secondBest = __builtin_inf();
-			int wcol = -1, pcol = -1;
-			for (int k = 0; k < n; ++k) {
-				const double cv = srow[scol[k]];
-				if (cv + P.wta_margin < minCost) { secondBest = minCost; minCost = cv; if (WTA) pcol = wcol; wcol = scol[k]; }   // twoviewstereo.cpp:293-301
-			}
+			WtaState<int, WTA> st(-1);
+			for (int k = 0; k < n; ++k) st.take(srow[scol[k]], scol[k], P.wta_margin);
 			double depth = __builtin_nan("");
-			if (wcol >= 0) depth = candidate_depth(L.cam, Rv.cam, P, ray, lo + wcol, y);
-			if (minCost > P.second_best_factor*secondBest) depth = __builtin_inf();
+			if (st.win >= 0) depth = candidate_depth(L.cam, Rv.cam, P, ray, lo + st.win, y);
+			if (st.rejected(P.second_best_factor)) depth = __builtin_inf();
 			L.depth[(size_t)y*W + x] = depth;
-			if (WTA) wta_store(wout, (size_t)W*L.h, (size_t)y*W + x, wcol >= 0 ? lo + wcol : -1, wcol >= 0 ? y : -1,
-			                   pcol >= 0 ? lo + pcol : -1, pcol >= 0 ? y : -1);
+			if (WTA) wta_store(wout, (size_t)W*L.h, (size_t)y*W + x, st.win >= 0 ? lo + st.win : -1, st.win >= 0 ? y : -1,
+			                   st.run >= 0 ? lo + st.run : -1, st.run >= 0 ? y : -1);
 		}
 		__syncthreads();                                              // (the LDS arrays are reused)
 		RD_STAMP(3);

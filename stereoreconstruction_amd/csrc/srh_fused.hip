@@ -657,17 +657,18 @@ void twoview_fused_kernel(const ViewDev *__restrict__ views, int ref, int oth, s
 		double depth = nan;                                       // twoviewstereo.cpp:269
 		int ocol = -2147483647, rcol = -2147483647;
 		if (active) {
-			double minCost = owner ? Pm : inf, secondBest = owner ? sec : inf;
-			int wcol = wc;
-			if (pix && (ambs || WTA)) {
+			WtaState<int, WTA> st(-2147483647);                    // the rule's state (srh_wta.hpp)
+			if (!(pix && (ambs || WTA))) {
+				// no lane saw an improvement inside the margin: every step of the rule was a step of the plain running
+				// minimum (F above), so the owner's last record is the state the rule ends in
+				st.minCost = owner ? Pm : inf; st.secondBest = owner ? sec : inf; st.win = wc;
+			} else {
 				// replay with the reference's margin rule, sequentially (rare: two costs within 1e-10 of each other)
 				const int ilast = S.ilast[p], K0 = S.k0[p], dirp = S.dir[p], ca = S.ca[p], cb = S.cb[p], corg = S.corg[p];
-				minCost = inf; secondBest = inf; wcol = -2147483647;
 				auto visit = [&](int c) {
 					if (c < ca || c > cb) return;
 					if (S.mrow[c - cmin] != 1) return;
-					const double cv = S.cost[Smem::slot(p, c - corg)];
-					if (cv + P.wta_margin < minCost) { secondBest = minCost; minCost = cv; if (WTA) rcol = wcol; wcol = c; }   // twoviewstereo.cpp:293-301
+					st.take(S.cost[Smem::slot(p, c - corg)], c, P.wta_margin);
 				};
 				if (dirp > 0) {
 					for (int i = 0; i <= ilast; ++i) visit(K0 + i);
@@ -681,12 +682,12 @@ void twoview_fused_kernel(const ViewDev *__restrict__ views, int ref, int oth, s
 					}
 				}
 			}
-			if (wcol != -2147483647) {
+			if (st.win != -2147483647) {
 				const Ray ray = cam_unproject(L.cam, (x + 0.5) / P.image_scale, (y + 0.5) / P.image_scale);
-				depth = candidate_depth(L.cam, Rv.cam, P, ray, wcol, y);
+				depth = candidate_depth(L.cam, Rv.cam, P, ray, st.win, y);
 			}
-			if (minCost > P.second_best_factor*secondBest) depth = inf;   // twoviewstereo.cpp:304-305
-			ocol = wcol;
+			if (st.rejected(P.second_best_factor)) depth = inf;
+			ocol = st.win; rcol = st.run;
 		}
 		if (x < W) L.depth[(size_t)y*W + x] = depth;
 		if (WTA && x < W) wta_store(wout, (size_t)W*L.h, (size_t)y*W + x, ocol == -2147483647 ? -1 : ocol, ocol == -2147483647 ? -1 : y,

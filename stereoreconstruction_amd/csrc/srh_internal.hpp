@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "stereo_recon_hip.h"
+#include "srh_wta.hpp"
 
 namespace srh {
 
@@ -64,57 +65,9 @@ __host__ __device__ inline size_t padded_size(int w, int h) { return (size_t)pad
 // candidate column range of a reference pixel on its own row of the other view (empty: hi < lo)
 struct PixRange { int32_t lo, hi; };
 
-// ---- certified fused arithmetic (option "arith" = 3; derivation: DESIGN.md section 2b) ---------------------------
-// The dense cost loops run with fused multiply-adds (half the FP64 instructions); a depth map depends on costs only
-// through comparisons (cost + wta_margin < minCost, minCost > second_best_factor*secondBest, the max_color_diff clamp;
-// twoviewstereo.cpp:292-305, 976), so the fused costs may stand in for the reference's wherever no comparison's
-// margin is inside the error bound.  For a fast-form candidate (all T taps usable; weights in (0,1], grays in
-// [0,255]; meanL, totalWeight and sum2 are the SAME bits in both arithmetics), with u = 2^-53, gamma_k = k*u/(1-k*u),
-// G = 256, A = sqrt(sum2), B = sqrt(sum3):
-//     eps_b = gamma_(T+4)*G   (error of w*g_R - meanR: the mean's T-term sum and division, the product, the subtraction)
-//     eps_a = 2*u*G           (error of w*g_L - meanL: meanL is shared)
-//     |cost_fused - cost_exact| <= 2*255*1.01*(3*eps_b*sqrt(T)/B + eps_a*sqrt(T)/A + 2*gamma_T) + 2600*u
-//                                =  k1/B + k2/A + k3
-// (either arithmetic is within half of that of the real-number value of the formula; 1.01 covers every second-order
-// term once A > 0.3 and B > 60, which the thresholds below imply).  A candidate is CERTIFIED when that is <= e0, i.e.
-// when sum3 >= sigma3(sum2); the cost kernel stores NaN for the others, and the certified scan flags every pixel
-// that meets a NaN or a comparison whose two sides are closer than the sum of their bounds: flagged pixels are
-// re-evaluated in the reference's arithmetic (twoview_refill_kernel + the exact scan).
-// ONE-PASS form (strip kernel, AR = 5).  Nothing obliges the fused kernel to follow the reference's two sweeps: any
-// arithmetic within e0 of the reference's will do.  With c_t = (w_t*l_t - meanL)*w_t, d_t = w_t^2, q = r^2 it accumulates
-// P = sum w_t r_t, Q = sum c_t r_t, U = sum d_t q_t in ONE sweep over the window (3 fused multiply-adds per tap and
-// candidate instead of 4, and 40 instead of 69 LDS values per window row and block), and finishes with m = P/tw,
-// sum3 = U - m*(2P - T*m), sum1 = Q - m*SA (SA = sum of w_t*l_t - meanL).  The price is cancellation in sum3: with
-// Q3 = U + 2mP + T*m^2 (every term >= 0) and z^2 = Q3/sum3, the one-pass value is within
-//     255*1.01*(3*gamma_(T+4)*z + 2.002*gamma_(T+3)*z^2) + 1300u
-// of the real-number cost, the reference's arithmetic within half of k1/B + k2/A + k3: a candidate is
-// certified when sum3 >= sigma3(sum2) (the latter <= e0/2) and Q3 <= zmax2*sum3 (the former <= e0/2).
-// Round 6: the FINISH is free of IEEE divisions and of the IEEE square root as well (onepass_finish below: they were 77 of the
-// ~93 instructions a candidate's finish took, a sixth of a block).  m = P*itw with itw = fl(1/tw) from the weights kernels
-// (one more rounding on m: every gamma index of the derivation goes up by one; the code takes gamma_(T+6) for both terms),
-// 1/sqrt(sum2*sum3) by v_rsq_f64 and ONE third-order Newton step whose own residual e = 1 - x*y0^2 is part of the
-// certificate (|e| <= 2^-20, whatever the seed's accuracy: y1 = y0*(1 + e/2 + 3e^2/8) is then within 2u of 1/sqrt(x)), and
-// v = fma(-255, |sum1|*y1, 255): x, the product and the last fma round once each, so the finish's share of the bound is
-// 255*1.001*(0.5u + 2u + u) + 255u < 1150u; the constant stays at 2600u.
-struct CertBound {
-	double e0, m_hi, k1, k2, room;
-	double zmax2;
-	int ok;                                 // 0: the parameters leave the bound no room / weights are not in (0,1]: exact arithmetic
-	__host__ __device__ inline double sigma3(double s2) const {
-		const double d = room - k2/sqrt(s2);                      // (NaN or zero sum2: d is NaN or -inf)
-		if (!(d > 0)) return __builtin_inf();
-		const double b = k1/d;
-		return b*b*(1.0 + 0x1p-20);                               // (+ the roundings of this very computation)
-	}
-};
-// certified scan: is this stored cost the very number the reference's arithmetic gives?  (+inf: the initial minCost / secondBest)
-__host__ __device__ inline bool cert_sure(double x, double clamp, double m_hi) { return x == clamp || x > m_hi; }
-// certified cost kernels with the in-kernel redo (strip kernel): a pixel with unusable taps of its own (every candidate in
-// a select form) or whose own window leaves the bound no room (sigma3 = +inf) is evaluated in the reference's arithmetic
-// throughout -- the certified scan treats every stored cost of such a pixel as the reference's very number
-__host__ __device__ inline bool cert_pixel_exact(const CertBound &cb, double sum2, double all_taps_usable) {
-	return !(all_taps_usable != 0.0) || !(cb.sigma3(sum2) < __builtin_inf());
-}
+// ---- certified fused arithmetic (option "arith" = 3): CertBound, cert_bound(), cert_sure, cert_pixel_exact and the scans'
+// doubt tests live in srh_wta.hpp (host-clean: the CPU suite compiles it), with the derivation; DESIGN.md section 2b
+
 // The finish of a one-pass candidate (strip, per-tile and row-run cost kernels): the sums recovered from P, Q, U, the cost
 // without an IEEE division or square root, and the certificate.  itw = fl(1/totalWeight) (pconst slot 3), TT = T.
 // A non-positive or NaN sum3 gives a NaN residual and fails the certificate; an uncertified value is never used.
@@ -135,35 +88,6 @@ __device__ __forceinline__ double onepass_finish(double P, double Q, double U, d
 	return __builtin_fma(-255.0, __builtin_fabs(s1)*y1, 255.0);
 }
 #endif
-// mvs: the free cost_ncc of MultiViewStereo (multiviewstereo.cpp:113-189): the score sum1/sqrt(sum2*sum3) itself (no factor
-// 255, no clamp), 25 taps at the reference's radius; e0 = 2^-36 there (scores live in [-1, 1])
-inline CertBound cert_bound(const srh_params &P, bool mvs = false) {
-	const double u = 0x1p-53, G = 256.0;
-	const int T = (2*P.window_radius + 1)*(2*P.window_radius + 1);
-	auto gamma = [&](int k) { return k*u/(1.0 - k*u); };
-	const double eps_b = gamma(T + 4)*G, eps_a = 2*u*G, rt = sqrt((double)T);
-	const double scale = mvs ? 1.0 : 255.0;
-	CertBound c;
-	c.e0 = mvs ? 0x1p-36 : 0x1p-26;                               // TwoView: 1.5e-8, a comparison needs 3.7e-8 of margin (costs live in [0, 120])
-	c.k1 = 2*scale*1.01*3*eps_b*rt;
-	c.k2 = 2*scale*1.01*eps_a*rt;
-	const double k3 = 2*scale*1.01*2*gamma(T) + (mvs ? 40 : 2600)*u;
-	c.room = c.e0 - k3;
-	c.m_hi = P.max_color_diff + c.e0;
-	{	// one-pass form: 255*1.01*g*(3z + 2.002 z^2) + 2600u = e0/2  (g = gamma_(T+6): the finish multiplies by fl(1/tw))
-		const double g = gamma(T + 6), rhs = (c.e0/2 - 2600*u)/(scale*1.01*g);
-		const double z = rhs > 0 ? (-3.0 + sqrt(9.0 + 4*2.002*rhs))/(2*2.002) : 0.0;
-		c.zmax2 = z*z*(1.0 - 0x1p-20);
-	}
-	const bool weights_ok = P.weight_kind == SRH_WEIGHT_GEODESIC ? P.geodesic_sigma > 0 : P.adaptive_color_sigma > 0;   // exp(-distance/sigma) <= 1
-	if (mvs) { c.ok = c.room > 0 && weights_ok && fabs(P.peak_threshold) <= 1e5; return c; }
-	// the clamp test needs max_color_diff + e0 > max_color_diff (so below 2^22); the duplicate rule of the scan needs
-	// wta_margin >= 0
-	// (and magnitudes <= 1e5, so that the rounding of cost + margin stays below e0/2 in the scan's tolerance)
-	c.ok = c.room > 0 && c.m_hi > P.max_color_diff && P.max_color_diff <= 1e5 && fabs(P.bad_ret) <= 1e5 &&
-	       P.wta_margin >= 0 && P.wta_margin <= 1e5 && fabs(P.second_best_factor) <= 1e5 && weights_ok;
-	return c;
-}
 
 // ---- by-products of the winner-take-all scan (option "wta_outputs") ------------------------------------------
 // Two int32 pairs per pixel of the reference view, planes back to back in one allocation: win_xy[npix][2] -- the candidate

@@ -120,7 +120,7 @@ void launch_weights(hipStream_t st, const ViewDev *views, int ref, int width, co
 }
 
 // ------------------------------------------------------------------ TwoView, general geometry
-// WTA (option "wta_outputs"): the candidate that held minCost before the last improvement travels along (px, py)
+// the rule and its state: srh_wta.hpp (WTA, option "wta_outputs": the runner-up travels along)
 template <bool SAD, bool WTA>
 struct TwoViewDirectVisitor {
 	const ViewDev &L, &Rv;
@@ -128,19 +128,12 @@ struct TwoViewDirectVisitor {
 	size_t wstride;
 	const srh_params &P;
 	int x, y;
-	double minCost, secondBest;
-	int wx, wy;
+	WtaState<WtaXY, WTA> st;
 	unsigned n;
-	int px, py;
 	__device__ __forceinline__ void operator()(int cx, int cy) {
 		const double cost = SAD ? tv_cost_sad(L, Rv, wq, wstride, P, x, y, cx, cy) : tv_cost(L, Rv, wq, wstride, P, x, y, cx, cy);
 		++n;
-		if (cost + P.wta_margin < minCost) {                   // twoviewstereo.cpp:293-301
-			secondBest = minCost;
-			minCost = cost;
-			if (WTA) { px = wx; py = wy; }
-			wx = cx; wy = cy;
-		}
+		st.take(cost, WtaXY{ cx, cy }, P.wta_margin);
 	}
 };
 
@@ -165,13 +158,13 @@ __global__ void twoview_generic_kernel(const ViewDev *__restrict__ views, int re
 			const Ray ray = cam_unproject(L.cam, (x + 0.5) / P.image_scale, (y + 0.5) / P.image_scale);
 			const int T = (2*P.window_radius + 1)*(2*P.window_radius + 1);
 			TwoViewDirectVisitor<SAD, WTA> vis = { L, Rv, wbuf + wbuf_offset(W, T, (int)(q / W), x), wstride, P, x, y,
-			                             __builtin_inf(), __builtin_inf(), -1, -1, 0, -1, -1 };
+			                             WtaState<WtaXY, WTA>(WtaXY{ -1, -1 }), 0 };
 			walk_curve<false>(ray, L.cam, Rv, P, vis);
 			n_eval = vis.n;
-			if (WTA) { ox = vis.wx; oy = vis.wy; rx = vis.px; ry = vis.py; }
-			if (vis.wx >= 0)                                       // at least one candidate was scanned
-				depth = candidate_depth(L.cam, Rv.cam, P, ray, vis.wx, vis.wy);
-			if (vis.minCost > P.second_best_factor*vis.secondBest)   // twoviewstereo.cpp:304-305
+			if (WTA) { ox = vis.st.win.x; oy = vis.st.win.y; rx = vis.st.run.x; ry = vis.st.run.y; }
+			if (vis.st.win.x >= 0)                                 // at least one candidate was scanned
+				depth = candidate_depth(L.cam, Rv.cam, P, ray, vis.st.win.x, vis.st.win.y);
+			if (vis.st.rejected(P.second_best_factor))
 				depth = __builtin_inf();
 		}
 		L.depth[pv] = depth;
@@ -1149,7 +1142,7 @@ void mvs_list_cost_kernel(const ViewDev *__restrict__ views, int ref, NeighList 
 
 // PEAKS: the top-K request (every pair above the threshold into the unit's sorted K-list upk[unit][K][2], as in
 // mvs_list_cost_kernel<R, true>); its LDS share of the box is smaller by the queue of pairs waiting for their depth.
-// CERT (not with PEAKS): the certified fused arithmetic (srh_internal.hpp, CertBound).  The two sweeps run
+// CERT (not with PEAKS): the certified fused arithmetic (srh_wta.hpp, CertBound).  The two sweeps run
 // with fused multiply-adds; a unit's result depends on the scores only through "which candidate has the largest score
 // above the threshold" (multiviewstereo.cpp:589-604, 654-660), so the unit keeps, beside its fused maximum, whether any
 // OTHER candidate's fused score came within 2*e0 of it (or any score within e0 of the threshold, or a candidate the

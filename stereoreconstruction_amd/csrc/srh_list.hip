@@ -351,7 +351,7 @@ bool launch_twoview_list_cost(hipStream_t st, const ViewDev *views, int ref, int
 // ------------------------------------------------------------------ list scan
 #define LS_QN 16
 
-// WTA: winner and runner-up into wout (wta_store, srh_internal.hpp)
+// the rule: srh_wta.hpp, candidates as y << 16 | x.  WTA: winner and runner-up into wout (wta_store, srh_internal.hpp)
 template <bool WTA>
 __global__ void twoview_list_scan_kernel(const ViewDev *__restrict__ views, int ref, int oth, srh_params P,
                                          int y0, int nrows, const int32_t *__restrict__ count,
@@ -371,8 +371,8 @@ __global__ void twoview_list_scan_kernel(const ViewDev *__restrict__ views, int 
 		const int n = count[q] < cmax ? count[q] : cmax;
 		const uint32_t *clist = cand + q*(size_t)cmax;
 		const double *crow = cost + q*(size_t)cmax;
-		double minCost = __builtin_inf(), secondBest = __builtin_inf();
-		uint32_t win = 0xffffffffu, prev = 0xffffffffu;
+		WtaState<uint32_t, WTA> st(0xffffffffu);
+		uint32_t prev = 0xffffffffu;
 		for (int k0 = 0; k0 < n; k0 += LS_QN) {
 			uint32_t e[LS_QN];
 			double c[LS_QN];
@@ -384,24 +384,17 @@ __global__ void twoview_list_scan_kernel(const ViewDev *__restrict__ views, int 
 			}
 #pragma unroll
 			for (int j = 0; j < LS_QN; ++j) {
-				if (k0 + j < n && e[j] != prev) {
-					if (c[j] + P.wta_margin < minCost) {               // twoviewstereo.cpp:293-301
-						secondBest = minCost;
-						minCost = c[j];
-						if (WTA) wrun = win;
-						win = e[j];
-					}
-				}
+				if (k0 + j < n && e[j] != prev) st.take(c[j], e[j], P.wta_margin);
 				if (k0 + j < n) prev = e[j];
 			}
 		}
-		if (win != 0xffffffffu) {
+		if (st.win != 0xffffffffu) {
 			const Ray ray = cam_unproject(L.cam, (x + 0.5) / P.image_scale, (y + 0.5) / P.image_scale);
-			depth = candidate_depth(L.cam, Rv.cam, P, ray, (int)(win & 0xffffu), (int)(win >> 16));
+			depth = candidate_depth(L.cam, Rv.cam, P, ray, (int)(st.win & 0xffffu), (int)(st.win >> 16));
 		}
-		if (minCost > P.second_best_factor*secondBest)                 // twoviewstereo.cpp:304-305
+		if (st.rejected(P.second_best_factor))
 			depth = __builtin_inf();
-		wwin = win;
+		wwin = st.win; wrun = st.run;
 	}
 	L.depth[pv] = depth;
 	if (WTA) wta_store(wout, (size_t)W*L.h, pv, wwin == 0xffffffffu ? -1 : (int)(wwin & 0xffffu), wwin == 0xffffffffu ? -1 : (int)(wwin >> 16),

@@ -17,9 +17,13 @@
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#endif
+#ifndef SRH_NHD                        // (srh_wta.hpp has the same definition)
+#if defined(__HIPCC__)
 #define SRH_NHD __host__ __device__ __forceinline__
 #else
 #define SRH_NHD inline
+#endif
 #endif
 
 namespace srh {

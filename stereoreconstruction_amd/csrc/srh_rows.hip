@@ -317,7 +317,7 @@ struct RowsSmem {
 };
 
 // AR: 0 = the reference's arithmetic; 3 = certified: the two sweeps of the fast form run with fused multiply-adds and
-// every value is stored by the rule of the certified scan (srh_internal.hpp, CertBound; twoview_strip_cost_kernel): NaN
+// every value is stored by the rule of the certified scan (srh_wta.hpp, CertBound; twoview_strip_cost_kernel): NaN
 // for a candidate whose error bound is not below e0, the clamp itself above clamp + e0, anything else unclamped.  The
 // per-pixel constants (meanL, totalWeight, sum2) and the select form stay in the reference's arithmetic.
 template <int R, int AR>
@@ -329,7 +329,7 @@ void twoview_rows_cost_kernel(const ViewDev *__restrict__ views, int ref, int ot
                               double *__restrict__ cost, int smax, Counters *__restrict__ cnt, const CertBound cb,
                               const double *__restrict__ pconst, const double *__restrict__ oth_tvp, const uint32_t *__restrict__ full_stat)
 {
-	constexpr bool FMA = AR != 0, CERT = AR == 3 || AR == 5, ONEPASS = AR == 5;   // 5: the certified ONE-PASS form (srh_internal.hpp, CertBound)
+	constexpr bool FMA = AR != 0, CERT = AR == 3 || AR == 5, ONEPASS = AR == 5;   // 5: the certified ONE-PASS form (srh_wta.hpp, CertBound)
 	constexpr int WS = 2*R + 1;
 	constexpr int T = WS*WS;
 	typedef RowsSmem<R> Smem;
@@ -966,7 +966,7 @@ bool launch_twoview_rows_refill(hipStream_t st, int width, int oth_width, const 
 #define RS_QN 16
 
 // CERT / LISTED: as twoview_scan_kernel (srh_dense.hip): the certified scan on fused costs flags the pixels with a decision
-// the error bound does not cover; the listed scan is the exact scan of those pixels after twoview_rows_refill_kernel.
+// the error bound does not cover (the rule and the doubt tests: srh_wta.hpp, candidates as y << 16 | x); the listed scan is the exact scan of those pixels after twoview_rows_refill_kernel.
 // WTA: winner and runner-up into wout (wta_store, srh_internal.hpp); a listed pixel's pairs are written again by its exact scan
 template <bool CERT, bool LISTED, bool WTA>
 __global__ __launch_bounds__(RW_LT)
@@ -1004,8 +1004,7 @@ void twoview_rows_scan_kernel(const ViewDev *__restrict__ views, int ref, int ot
 		const uint32_t *clist = cand + (q >> 6)*(size_t)cmax*64 + (q & 63);
 		const int tiles_per_row = (W + 7) >> 3;
 		const double *crow = cost + ((size_t)(q / W)*tiles_per_row + (x >> 3))*(size_t)smax*8 + (x & 7);
-		double minCost = __builtin_inf(), secondBest = __builtin_inf();
-		uint32_t win = 0xffffffffu;
+		WtaState<uint32_t, WTA> st(0xffffffffu);
 		bool flag = false;
 		for (int k0 = 0; k0 < n; k0 += RS_QN) {
 			uint32_t e[RS_QN];
@@ -1022,34 +1021,23 @@ void twoview_rows_scan_kernel(const ViewDev *__restrict__ views, int ref, int ot
 			}
 #pragma unroll
 			for (int j = 0; j < RS_QN; ++j) {
-				if (CERT && k0 + j < n) {
-					// (srh_dense.hip, twoview_scan_kernel: tolerance, "sure" values, the winner seen again)
+				if (k0 + j < n) {
+					// (px_sure = false: this path's cost kernel evaluates no pixel exactly throughout, srh_wta.hpp)
 					const double t = c[j] + P.wta_margin;
-					if (!(fabs(t - minCost) > 2.5*cb.e0) && e[j] != win &&
-					    !(cert_sure(c[j], P.max_color_diff, cb.m_hi) && cert_sure(minCost, P.max_color_diff, cb.m_hi))) flag = true;
-				}
-				if (k0 + j < n && c[j] + P.wta_margin < minCost) {     // twoviewstereo.cpp:293-301
-					secondBest = minCost;
-					minCost = c[j];
-					if (WTA) wrun = win;
-					win = e[j];
+					if (CERT && cert_step_doubt(c[j], t, st.minCost, e[j] == st.win, false, cb, P.max_color_diff)) flag = true;
+					st.take_sum(t, c[j], e[j]);
 				}
 			}
 		}
-		wwin = win;
-		if (win != 0xffffffffu) {
+		wwin = st.win; wrun = st.run;
+		if (st.win != 0xffffffffu) {
 			const Ray ray = cam_unproject(L.cam, (x + 0.5) / P.image_scale, (y + 0.5) / P.image_scale);
-			depth = candidate_depth(L.cam, Rv.cam, P, ray, (int)(win & 0xffffu), (int)(win >> 16));
+			depth = candidate_depth(L.cam, Rv.cam, P, ray, (int)(st.win & 0xffffu), (int)(st.win >> 16));
 		}
-		if (minCost > P.second_best_factor*secondBest)                 // twoviewstereo.cpp:304-305
+		if (st.rejected(P.second_best_factor))
 			depth = __builtin_inf();
 		if (CERT) {
-			if (win != 0xffffffffu) {
-				const double rhs = P.second_best_factor*secondBest;
-				const double tol = __builtin_fma(fmin(fabs(rhs), 1e300), 1e-15, (1.0 + fabs(P.second_best_factor))*cb.e0);
-				if (!(fabs(minCost - rhs) > tol) &&
-				    !(cert_sure(minCost, P.max_color_diff, cb.m_hi) && cert_sure(secondBest, P.max_color_diff, cb.m_hi))) flag = true;
-			}
+			if (st.win != 0xffffffffu && cert_ratio_doubt(st.minCost, st.secondBest, P.second_best_factor, false, cb, P.max_color_diff)) flag = true;
 			if (flag) { cflag[1 + atomicAdd(&cflag[0], 1u)] = (uint32_t)q; atomicAdd(&cnt->n_flagged, 1ull); }
 		}
 	}

@@ -315,7 +315,7 @@ __device__ __noinline__ void strip_select_block(const StripSmem<R, NBUF> &S, int
 // NWV waves: 4 (block lanes per pixel G = 8, NBUF = 1) or 8 (G = 16, NBUF = 2)
 // AR: 0 = the reference's arithmetic (no contraction), 1 = fused multiply-adds, 5 = certified ONE-PASS form (below),
 // 3 = fused two sweeps AND certified: a candidate
-// whose error bound (srh_internal.hpp, CertBound) is not below cb.e0 is stored as NaN, a value above max_color_diff + e0
+// whose error bound (srh_wta.hpp, CertBound) is not below cb.e0 is stored as NaN, a value above max_color_diff + e0
 // as max_color_diff itself (the exact cost is then max_color_diff too), anything else unclamped -- the certified scan
 // does the rest.  Candidates of the select forms are evaluated in the reference's arithmetic in every mode.
 //
@@ -766,7 +766,7 @@ void twoview_strip_cost_kernel(const StripArgs A)
 					if (BORDER) {
 						if (fast) two_sweeps(std::false_type(), std::false_type());   // (the select forms' arithmetic, in every mode)
 					} else if (fast && ONEPASS && !pix_exact) {
-						// ---- certified ONE-PASS form (srh_internal.hpp, CertBound): P = sum w r, Q = sum ((w l - meanL) w) r,
+						// ---- certified ONE-PASS form (srh_wta.hpp, CertBound): P = sum w r, Q = sum ((w l - meanL) w) r,
 						// U = sum w^2 r^2 in one sweep over the window; registers are refilled in place a row ahead, as below
 						const double mL = CS.pc[cur][i][0], itw = CS.pc[cur][i][3], s2 = CS.pc[cur][i][2];   // (slot 3 of a pixel with every tap usable: 1/totalWeight)
 						double r_[NR], q_[NR], w_[WS], l_[WS], P_[NCB], Q_[NCB], U_[NCB];
