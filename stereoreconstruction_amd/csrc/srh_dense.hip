@@ -12,6 +12,7 @@
 #include "srh_internal.hpp"
 #include "srh_geom.hpp"
 #include "srh_walk.hpp"
+#include "srh_block.hpp"
 
 #include <algorithm>
 #include <type_traits>
@@ -883,6 +884,28 @@ __device__ __noinline__ double dense_cost_general(const DenseSmem<R, DC_NCB, DC_
 	                            weight_cutoff, bad_ret, max_color_diff);
 }
 
+// The row source of the block loops (srh_block.hpp) for the block at tile column rc of pixel i.  PAIRS: the other view's
+// segment is read 16 bytes at a time (rc even); else 8 bytes at a time (ds_read2_b64: no alignment beyond 8 bytes).
+template <class Smem, bool PAIRS>
+struct DenseRows {
+	static constexpr bool LDS_WAIT = true;
+	const Smem &S;
+	int i, rc;
+	struct Row {
+		const double *rp, *wp, *lp;
+		__device__ __forceinline__ void r2(int m, double &a, double &b) const {
+			if (PAIRS) { const double2 v = reinterpret_cast<const double2 *>(rp)[m]; a = v.x; b = v.y; }
+			else { a = rp[2*m]; b = rp[2*m + 1]; }
+		}
+		__device__ __forceinline__ void w2(int m, double &a, double &b) const { const double2 v = reinterpret_cast<const double2 *>(wp)[m]; a = v.x; b = v.y; }
+		__device__ __forceinline__ double w(int col) const { return wp[col]; }           // (the pad tap is never read)
+		__device__ __forceinline__ double l(int col) const { return lp[col]; }
+	};
+	__device__ __forceinline__ Row row(int row) const { return Row{ &S.rt[row][rc], &S.w[i][row*Smem::WP], &S.lt[row][i] }; }
+	__device__ __forceinline__ int row_begin(int) const { return 0; }
+	__device__ __forceinline__ void row_end(int) const {}
+};
+
 #ifdef SRH_EXPERIMENT
 // timing experiments only (make exp): repeat the block loops of every tile `g_exp_repeat` times (the marginal
 // time of a repetition is the pure loop time), pad the dynamic LDS so that fewer workgroups fit a CU
@@ -1136,171 +1159,27 @@ void twoview_dense_cost_kernel(const ViewDev *__restrict__ views, int ref, int o
 					// certified one-pass form (twoview_strip_cost_kernel): P = sum w r, Q = sum ((w l - meanL) w) r, U = sum w^2 r^2
 					const double mL = CS.meanL[i], itw = CS.totalW[i], s2 = CS.sum2[i];   // (this form keeps 1/totalWeight there)
 					const double sig3 = cb.sigma3(s2);
-					double r[NR], q[NR], wv[WS], lv[WS], P_[DC_NCB], Q_[DC_NCB], U_[DC_NCB];
-					{
-						const double *rp = &CS.rt[0][rc];
-						const double2 *wp = reinterpret_cast<const double2 *>(&CS.w[i][0]);
-#pragma unroll
-						for (int k = 0; k < NR; ++k) r[k] = rp[k];
-#pragma unroll
-						for (int m = 0; m < (WS - 1)/2; ++m) { const double2 v = wp[m]; wv[2*m] = v.x; wv[2*m + 1] = v.y; }
-						wv[WS - 1] = CS.w[i][WS - 1];
-#pragma unroll
-						for (int col = 0; col < WS; ++col) lv[col] = CS.lt[0][i + col];
-					}
-#pragma unroll
-					for (int j = 0; j < DC_NCB; ++j) { P_[j] = 0.0; Q_[j] = 0.0; U_[j] = 0.0; }
-					__builtin_amdgcn_s_waitcnt(0xC07F);
-#pragma unroll 1
-					for (int row = 0; row < WS; ++row) {
-						const int nrow = row + 1 < WS ? row + 1 : 0;          // (the last refill is never used)
-						const double *rp = &CS.rt[nrow][rc];
-						const double2 *wp = reinterpret_cast<const double2 *>(&CS.w[i][nrow*WP]);
-						const double *lp = &CS.lt[nrow][i];
-#pragma unroll
-						for (int k = 0; k < DC_NCB - 1; ++k) q[k] = r[k]*r[k];
-#pragma unroll
-						for (int col = 0; col < WS; ++col) {
-							q[col + DC_NCB - 1] = r[col + DC_NCB - 1]*r[col + DC_NCB - 1];
-							const double a = __builtin_fma(wv[col], lv[col], -mL);
-							const double c = a*wv[col], d = wv[col]*wv[col];
-							__builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-							for (int j = 0; j < DC_NCB; ++j) P_[j] = __builtin_fma(wv[col], r[col + j], P_[j]);
-#pragma unroll
-							for (int j = 0; j < DC_NCB; ++j) Q_[j] = __builtin_fma(c, r[col + j], Q_[j]);
-#pragma unroll
-							for (int j = 0; j < DC_NCB; ++j) U_[j] = __builtin_fma(d, q[col + j], U_[j]);
-							__builtin_amdgcn_sched_barrier(0);
-							lv[col] = lp[col];
-							if (col & 1) {
-								r[col - 1] = rp[col - 1]; r[col] = rp[col];
-								const double2 u = wp[col >> 1]; wv[col - 1] = u.x; wv[col] = u.y;
-							}
-							__builtin_amdgcn_sched_barrier(0);
-						}
-#pragma unroll
-						for (int k = WS - 1; k < NR; ++k) r[k] = rp[k];
-						wv[WS - 1] = CS.w[i][nrow*WP + WS - 1];
-					}
+					double P_[DC_NCB], Q_[DC_NCB], U_[DC_NCB];
+					DenseRows<Smem, false> rows{ CS, i, rc };          // (8 bytes at a time: rc may be odd)
+					block_onepass<WS, DC_NCB>(rows, mL, P_, Q_, U_);
 					constexpr double TT = (double)T;
 #pragma unroll
 					for (int j = 0; j < DC_NCB; ++j) {
 						bool okc;                              // (every candidate finished, only the store masked: as in the strip kernel)
 						const double v = onepass_finish(P_[j], Q_[j], U_[j], CS.sumA[i], itw, s2, TT, sig3, cb.zmax2, okc);
-						if ((vm >> j) & 1u) crow[(size_t)(c0 + j - e.xmin)*DC_TP] = !okc ? __builtin_nan("") : (v > cb.m_hi ? P.max_color_diff : v);
+						if ((vm >> j) & 1u) crow[(size_t)(c0 + j - e.xmin)*DC_TP] = block_stored<true>(v, okc, cb.m_hi, P.max_color_diff);
 					}
 				} else if (fast) {
 					const double mL = CS.meanL[i], tw = CS.totalW[i], s2 = CS.sum2[i];
 					const double sig3 = CERT ? cb.sigma3(s2) : 0.0;
-					// Both passes are modulo-scheduled by hand: r[] / wv[] / av[] hold the current
-					// window row; as soon as a value has had its last use, the same register is
-					// refilled with the next row's value, so the LDS latency is always a row ahead.
-					static_assert(WS % 2 == 1, "odd window");
-					double r[NR], wv[WS], acc[DC_NCB];
-					{
-						const double2 *rp = reinterpret_cast<const double2 *>(&CS.rt[0][rc]);
-						const double2 *wp = reinterpret_cast<const double2 *>(&CS.w[i][0]);
-#pragma unroll
-						for (int m = 0; m < NR/2; ++m) { const double2 v = rp[m]; r[2*m] = v.x; r[2*m + 1] = v.y; }
-#pragma unroll
-						for (int m = 0; m < (WS - 1)/2; ++m) { const double2 v = wp[m]; wv[2*m] = v.x; wv[2*m + 1] = v.y; }
-						wv[WS - 1] = CS.w[i][WS - 1];
-					}
-#pragma unroll
-					for (int j = 0; j < DC_NCB; ++j) acc[j] = 0.0;
-					// all LDS reads of the loop pre-header have landed: inside the loop the compiler can
-					// then count only the reads of the previous iteration (lgkmcnt(N) instead of 0)
-					__builtin_amdgcn_s_waitcnt(0xC07F);
-#pragma unroll 1
-					for (int row = 0; row < WS; ++row) {
-						const int nrow = row + 1 < WS ? row + 1 : 0;          // last refill = row 0, for pass 2
-						const double2 *rp = reinterpret_cast<const double2 *>(&CS.rt[nrow][rc]);
-						const double2 *wp = reinterpret_cast<const double2 *>(&CS.w[i][nrow*WP]);
-#pragma unroll
-						for (int col = 0; col < WS; ++col) {
-							// products first, sums second: no instruction waits on its predecessor, so a
-							// wave keeps the FP64 pipe full even when it is alone on its SIMD
-							if (FMA) {
-#pragma unroll
-								for (int j = 0; j < DC_NCB; ++j) acc[j] = __builtin_fma(wv[col], r[col + j], acc[j]);
-							} else {
-								double pr[DC_NCB];
-#pragma unroll
-								for (int j = 0; j < DC_NCB; ++j) pr[j] = wv[col]*r[col + j];
-								__builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-								for (int j = 0; j < DC_NCB; ++j) acc[j] += pr[j];        // meanR += weight*gray
-							}
-							__builtin_amdgcn_sched_barrier(0);              // keep each refill where it is written
-							if (col & 1) {                                  // r[col-1], r[col], wv[col-1], wv[col] are dead
-								const double2 v = rp[col >> 1]; r[col - 1] = v.x; r[col] = v.y;
-								const double2 u = wp[col >> 1]; wv[col - 1] = u.x; wv[col] = u.y;
-								__builtin_amdgcn_sched_barrier(0);
-							}
-						}
-#pragma unroll
-						for (int m = (WS - 1)/2; m < NR/2; ++m) { const double2 v = rp[m]; r[2*m] = v.x; r[2*m + 1] = v.y; }
-						wv[WS - 1] = CS.w[i][nrow*WP + WS - 1];           // (the pad tap is never read)
-					}
-					double mR[DC_NCB], s1[DC_NCB], s3[DC_NCB], av[WS];
-#pragma unroll
-					for (int col = 0; col < WS; ++col) av[col] = CS.lt[0][i + col];
-#pragma unroll
-					for (int j = 0; j < DC_NCB; ++j) { mR[j] = acc[j]/tw; s1[j] = 0.0; s3[j] = 0.0; }
-					__builtin_amdgcn_s_waitcnt(0xC07F);
-#pragma unroll 1
-					for (int row = 0; row < WS; ++row) {
-						const int nrow = row + 1 < WS ? row + 1 : 0;
-						const double2 *rp = reinterpret_cast<const double2 *>(&CS.rt[nrow][rc]);
-						const double2 *wp = reinterpret_cast<const double2 *>(&CS.w[i][nrow*WP]);
-						const double *lp = &CS.lt[nrow][i];
-#pragma unroll
-						for (int col = 0; col < WS; ++col) {
-							const double wt = wv[col];
-							if (FMA) {
-								const double a = __builtin_fma(wt, av[col], -mL);
-								double bb[DC_NCB];
-#pragma unroll
-								for (int j = 0; j < DC_NCB; ++j) bb[j] = __builtin_fma(wt, r[col + j], -mR[j]);
-								__builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-								for (int j = 0; j < DC_NCB; ++j) { s1[j] = __builtin_fma(a, bb[j], s1[j]); s3[j] = __builtin_fma(bb[j], bb[j], s3[j]); }
-							} else {
-							double bb[DC_NCB], u1[DC_NCB], u3[DC_NCB];
-							const double pa = wt*av[col];
-#pragma unroll
-							for (int j = 0; j < DC_NCB; ++j) bb[j] = wt*r[col + j];
-							__builtin_amdgcn_sched_barrier(0);
-							const double a = pa - mL;                         // pixel_gray_l - meanL
-#pragma unroll
-							for (int j = 0; j < DC_NCB; ++j) bb[j] = bb[j] - mR[j];   // pixel_gray_r - meanR
-							__builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-							for (int j = 0; j < DC_NCB; ++j) { u1[j] = a*bb[j]; u3[j] = bb[j]*bb[j]; }
-							__builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-							for (int j = 0; j < DC_NCB; ++j) { s1[j] += u1[j]; s3[j] += u3[j]; }
-							}
-							__builtin_amdgcn_sched_barrier(0);
-							av[col] = lp[col];
-							if (col & 1) {
-								const double2 v = rp[col >> 1]; r[col - 1] = v.x; r[col] = v.y;
-								const double2 u = wp[col >> 1]; wv[col - 1] = u.x; wv[col] = u.y;
-							}
-							__builtin_amdgcn_sched_barrier(0);
-						}
-#pragma unroll
-						for (int m = (WS - 1)/2; m < NR/2; ++m) { const double2 v = rp[m]; r[2*m] = v.x; r[2*m + 1] = v.y; }
-						wv[WS - 1] = CS.w[i][nrow*WP + WS - 1];           // (the pad tap is never read)
-					}
+					double s1[DC_NCB], s3[DC_NCB];
+					DenseRows<Smem, true> rows{ CS, i, rc };           // (16-byte reads: rc is even)
+					block_two_sweeps<WS, DC_NCB, FMA>(rows, 0, WS, mL, tw, s1, s3);
 #pragma unroll
 					for (int j = 0; j < DC_NCB; ++j) {
 						const int c = c0 + j;
 						if (c >= lo && c <= hi && CS.rfull[rc + j] != 0) {
-							const double v = 255*(1.0 - fabs(s1[j]) / sqrt(s2 * s3[j]));
-							if (CERT) crow[(size_t)(c - e.xmin)*DC_TP] = !(s3[j] >= sig3) ? __builtin_nan("") : (v > cb.m_hi ? P.max_color_diff : v);
-							else crow[(size_t)(c - e.xmin)*DC_TP] = (v < P.max_color_diff) ? v : P.max_color_diff;
+							crow[(size_t)(c - e.xmin)*DC_TP] = block_stored<CERT, const double &>(two_sweep_finish(s1[j], s2, s3[j]), s3[j] >= sig3, cb.m_hi, P.max_color_diff);
 						}
 						__builtin_amdgcn_sched_barrier(0);
 					}

@@ -24,6 +24,7 @@
 #include "srh_internal.hpp"
 #include "srh_geom.hpp"
 #include "srh_walk.hpp"
+#include "srh_block.hpp"
 
 #include <cstdio>
 
@@ -73,6 +74,24 @@ __device__ __noinline__ double fused_cost_general(const FusedSmem<R, MAXC> &S, i
 	return window_exact_cost<R>(&S.w[p][0], Smem::WP, 1, &S.lt[0][p], &S.rt[0][rc], Smem::LW, Smem::RW,
 	                            weight_cutoff, bad_ret, max_color_diff);
 }
+
+// the row source of the block loops (srh_block.hpp) for the block at tile column rc (even: 16-byte reads) of pixel p
+template <class Smem>
+struct FusedRows {
+	static constexpr bool LDS_WAIT = true;
+	const Smem &S;
+	int p, rc;
+	struct Row {
+		const double *rp, *wp, *lp;
+		__device__ __forceinline__ void r2(int m, double &a, double &b) const { const double2 v = reinterpret_cast<const double2 *>(rp)[m]; a = v.x; b = v.y; }
+		__device__ __forceinline__ void w2(int m, double &a, double &b) const { const double2 v = reinterpret_cast<const double2 *>(wp)[m]; a = v.x; b = v.y; }
+		__device__ __forceinline__ double w(int col) const { return wp[col]; }
+		__device__ __forceinline__ double l(int col) const { return lp[col]; }
+	};
+	__device__ __forceinline__ Row row(int row) const { return Row{ &S.rt[row][rc], &S.w[p][row*Smem::WP], &S.lt[row][p] }; }
+	__device__ __forceinline__ int row_begin(int) const { return 0; }
+	__device__ __forceinline__ void row_end(int) const {}
+};
 
 // next set joint bit at index >= from, or -1
 template <int JW>
@@ -421,92 +440,14 @@ void twoview_fused_kernel(const ViewDev *__restrict__ views, int ref, int oth, s
 					if (c >= ca && c <= cb && CS.rfull[rc + j] != 0) { fast = true; ++n_dev; }
 				}
 				if (!fast) continue;
-				// Both passes are modulo-scheduled by hand (see srh_dense.hip): r[] / wv[] hold the current window
-				// row; a register is refilled with the next row's value right after its last use.
-				double r[NR], wv[WS], acc[NCB];
-				{
-					const double2 *rp = reinterpret_cast<const double2 *>(&CS.rt[0][rc]);
-					const double2 *wp = reinterpret_cast<const double2 *>(&CS.w[p][0]);
-#pragma unroll
-					for (int m = 0; m < NR/2; ++m) { const double2 v = rp[m]; r[2*m] = v.x; r[2*m + 1] = v.y; }
-#pragma unroll
-					for (int m = 0; m < (WS - 1)/2; ++m) { const double2 v = wp[m]; wv[2*m] = v.x; wv[2*m + 1] = v.y; }
-					wv[WS - 1] = CS.w[p][WS - 1];
-				}
-#pragma unroll
-				for (int j = 0; j < NCB; ++j) acc[j] = 0.0;
-				__builtin_amdgcn_s_waitcnt(0xC07F);
-#pragma unroll 1
-				for (int row = 0; row < WS; ++row) {
-					const int nrow = row + 1 < WS ? row + 1 : 0;          // last refill = row 0, for pass 2
-					const double2 *rp = reinterpret_cast<const double2 *>(&CS.rt[nrow][rc]);
-					const double2 *wp = reinterpret_cast<const double2 *>(&CS.w[p][nrow*WP]);
-#pragma unroll
-					for (int col = 0; col < WS; ++col) {
-						double pr[NCB];
-#pragma unroll
-						for (int j = 0; j < NCB; ++j) pr[j] = wv[col]*r[col + j];
-						__builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-						for (int j = 0; j < NCB; ++j) acc[j] += pr[j];            // meanR += weight*gray
-						__builtin_amdgcn_sched_barrier(0);
-						if (col & 1) {
-							const double2 v = rp[col >> 1]; r[col - 1] = v.x; r[col] = v.y;
-							const double2 u = wp[col >> 1]; wv[col - 1] = u.x; wv[col] = u.y;
-							__builtin_amdgcn_sched_barrier(0);
-						}
-					}
-#pragma unroll
-					for (int m = (WS - 1)/2; m < NR/2; ++m) { const double2 v = rp[m]; r[2*m] = v.x; r[2*m + 1] = v.y; }
-					wv[WS - 1] = CS.w[p][nrow*WP + WS - 1];
-				}
-				double mR[NCB], s1[NCB], s3[NCB], av[WS];
-#pragma unroll
-				for (int col = 0; col < WS; ++col) av[col] = CS.lt[0][p + col];
-#pragma unroll
-				for (int j = 0; j < NCB; ++j) { mR[j] = acc[j]/tw; s1[j] = 0.0; s3[j] = 0.0; }
-				__builtin_amdgcn_s_waitcnt(0xC07F);
-#pragma unroll 1
-				for (int row = 0; row < WS; ++row) {
-					const int nrow = row + 1 < WS ? row + 1 : 0;
-					const double2 *rp = reinterpret_cast<const double2 *>(&CS.rt[nrow][rc]);
-					const double2 *wp = reinterpret_cast<const double2 *>(&CS.w[p][nrow*WP]);
-					const double *lp = &CS.lt[nrow][p];
-#pragma unroll
-					for (int col = 0; col < WS; ++col) {
-						const double wt = wv[col];
-						double bb[NCB], u1[NCB], u3[NCB];
-						const double pa = wt*av[col];
-#pragma unroll
-						for (int j = 0; j < NCB; ++j) bb[j] = wt*r[col + j];
-						__builtin_amdgcn_sched_barrier(0);
-						const double a = pa - mL;                         // pixel_gray_l - meanL
-#pragma unroll
-						for (int j = 0; j < NCB; ++j) bb[j] = bb[j] - mR[j];   // pixel_gray_r - meanR
-						__builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-						for (int j = 0; j < NCB; ++j) { u1[j] = a*bb[j]; u3[j] = bb[j]*bb[j]; }
-						__builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-						for (int j = 0; j < NCB; ++j) { s1[j] += u1[j]; s3[j] += u3[j]; }
-						__builtin_amdgcn_sched_barrier(0);
-						av[col] = lp[col];
-						if (col & 1) {
-							const double2 v = rp[col >> 1]; r[col - 1] = v.x; r[col] = v.y;
-							const double2 u = wp[col >> 1]; wv[col - 1] = u.x; wv[col] = u.y;
-						}
-						__builtin_amdgcn_sched_barrier(0);
-					}
-#pragma unroll
-					for (int m = (WS - 1)/2; m < NR/2; ++m) { const double2 v = rp[m]; r[2*m] = v.x; r[2*m + 1] = v.y; }
-					wv[WS - 1] = CS.w[p][nrow*WP + WS - 1];
-				}
+				double s1[NCB], s3[NCB];
+				FusedRows<Smem> rows{ CS, p, rc };
+				block_two_sweeps<WS, NCB, false>(rows, 0, WS, mL, tw, s1, s3);
 #pragma unroll
 				for (int j = 0; j < NCB; ++j) {
 					const int c = c0 + j;
 					if (c >= ca && c <= cb && CS.rfull[rc + j] != 0) {
-						const double v = 255*(1.0 - fabs(s1[j]) / sqrt(s2 * s3[j]));
-						S.cost[Smem::slot(p, c - corg)] = (v < P.max_color_diff) ? v : P.max_color_diff;
+						S.cost[Smem::slot(p, c - corg)] = block_stored<false, const double &>(two_sweep_finish(s1[j], s2, s3[j]), true, P.max_color_diff, P.max_color_diff);   // (exact form: certified and m_hi are not read)
 					}
 					__builtin_amdgcn_sched_barrier(0);
 				}

@@ -68,26 +68,7 @@ struct PixRange { int32_t lo, hi; };
 // ---- certified fused arithmetic (option "arith" = 3): CertBound, cert_bound(), cert_sure, cert_pixel_exact and the scans'
 // doubt tests live in srh_wta.hpp (host-clean: the CPU suite compiles it), with the derivation; DESIGN.md section 2b
 
-// The finish of a one-pass candidate (strip, per-tile and row-run cost kernels): the sums recovered from P, Q, U, the cost
-// without an IEEE division or square root, and the certificate.  itw = fl(1/totalWeight) (pconst slot 3), TT = T.
-// A non-positive or NaN sum3 gives a NaN residual and fails the certificate; an uncertified value is never used.
-#ifdef __HIPCC__
-__device__ __forceinline__ double onepass_finish(double P, double Q, double U, double SA, double itw, double s2, double TT,
-                                                 double sig3, double zmax2, bool &okc)
-{
-	const double m = P*itw, p2 = P + P;
-	const double s3 = __builtin_fma(-m, __builtin_fma(-TT, m, p2), U);    // U - m*(2P - T*m)
-	const double s1 = __builtin_fma(-m, SA, Q);
-	const double q3 = __builtin_fma(m, __builtin_fma(TT, m, p2), U);      // U + m*(2P + T*m)
-	const double x = s2*s3;
-	const double y0 = __builtin_amdgcn_rsq(x);                            // v_rsq_f64: a seed, trusted for nothing
-	const double e = __builtin_fma(-(x*y0), y0, 1.0);                     // 1 - x*y0^2
-	const double y1 = __builtin_fma(y0*e, __builtin_fma(0.375, e, 0.5), y0);
-	const bool c1 = s3 >= sig3, c2 = s3*zmax2 >= q3, c3 = __builtin_fabs(e) <= 0x1p-20;
-	okc = c1 & c2 & c3;                                                   // (no short circuit: three compares, no branch)
-	return __builtin_fma(-255.0, __builtin_fabs(s1)*y1, 255.0);
-}
-#endif
+// the finish of a one-pass candidate (onepass_finish) and what a cost kernel stores for a fast-form candidate: srh_block.hpp
 
 // ---- by-products of the winner-take-all scan (option "wta_outputs") ------------------------------------------
 // Two int32 pairs per pixel of the reference view, planes back to back in one allocation: win_xy[npix][2] -- the candidate

@@ -16,6 +16,7 @@
 #include "srh_internal.hpp"
 #include "srh_geom.hpp"
 #include "srh_walk.hpp"
+#include "srh_block.hpp"
 
 #include <cstdio>
 
@@ -314,6 +315,30 @@ struct RowsSmem {
 	static constexpr int GS_CAP = 256;
 	unsigned int gsingle[GS_CAP];
 	int gsingle_n;
+};
+
+// The row source of the block loops (srh_block.hpp) for pixel i of the wave tile: the other view's segment of window row
+// `row` starts at rbase + row*rs, read 8 bytes at a time through a global pointer, not a generic one (flat loads would share
+// the LDS counter, and every wait for a weight would then also wait for the row segments in flight); the weights and the
+// reference row come from LDS.  No LDS wait before the loops: the segment's loads are in flight as well.
+template <int R>
+struct RowsRows {
+	typedef const __attribute__((address_space(1))) double *gptr;
+	static constexpr bool LDS_WAIT = false;
+	const RowsSmem<R> &S;
+	gptr rbase;
+	int rs, i;
+	struct Row {
+		gptr rp;
+		const double *wp, *lp;
+		__device__ __forceinline__ void r2(int m, double &a, double &b) const { a = rp[2*m]; b = rp[2*m + 1]; }
+		__device__ __forceinline__ void w2(int m, double &a, double &b) const { const double2 v = reinterpret_cast<const double2 *>(wp)[m]; a = v.x; b = v.y; }
+		__device__ __forceinline__ double w(int col) const { return wp[col]; }
+		__device__ __forceinline__ double l(int col) const { return lp[col]; }
+	};
+	__device__ __forceinline__ Row row(int row) const { return Row{ rbase + (size_t)row*rs, &S.w[row][i][0], &S.lt[row][i] }; }
+	__device__ __forceinline__ int row_begin(int) const { return 0; }
+	__device__ __forceinline__ void row_end(int) const {}
 };
 
 // AR: 0 = the reference's arithmetic; 3 = certified: the two sweeps of the fast form run with fused multiply-adds and
@@ -642,168 +667,30 @@ void twoview_rows_cost_kernel(const ViewDev *__restrict__ views, int ref, int ot
 					// (twoview_strip_cost_kernel); the other view's row segments come from L1 / L2 once instead of twice
 					const gptr rbase = rplane + (size_t)cy*rs + c0s;
 					const double SA = CS.sumA[i];
-					double r[NR_], q[NR_], wv[WS], lv[WS], P_[RC_NCB], Q_[RC_NCB], U_[RC_NCB];
-					{
-						const double2 *wp = reinterpret_cast<const double2 *>(&CS.w[0][i][0]);
-#pragma unroll
-						for (int k = 0; k < NR_; ++k) r[k] = rbase[k];
-#pragma unroll
-						for (int m = 0; m < (WS - 1)/2; ++m) { const double2 v = wp[m]; wv[2*m] = v.x; wv[2*m + 1] = v.y; }
-						wv[WS - 1] = CS.w[0][i][WS - 1];
-#pragma unroll
-						for (int col = 0; col < WS; ++col) lv[col] = CS.lt[0][i + col];
-					}
-#pragma unroll
-					for (int j = 0; j < RC_NCB; ++j) { P_[j] = 0.0; Q_[j] = 0.0; U_[j] = 0.0; }
-#pragma unroll 1
-					for (int row = 0; row < WS; ++row) {
-						const int nrow = row + 1 < WS ? row + 1 : 0;          // (the last refill is never used)
-						const gptr rp = rbase + (size_t)nrow*rs;
-						const double2 *wp = reinterpret_cast<const double2 *>(&CS.w[nrow][i][0]);
-						const double *lp = &CS.lt[nrow][i];
-#pragma unroll
-						for (int k = 0; k < RC_NCB - 1; ++k) q[k] = r[k]*r[k];
-#pragma unroll
-						for (int col = 0; col < WS; ++col) {
-							q[col + RC_NCB - 1] = r[col + RC_NCB - 1]*r[col + RC_NCB - 1];
-							const double a = __builtin_fma(wv[col], lv[col], -mL);
-							const double c = a*wv[col], d = wv[col]*wv[col];
-							__builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-							for (int j = 0; j < RC_NCB; ++j) P_[j] = __builtin_fma(wv[col], r[col + j], P_[j]);
-#pragma unroll
-							for (int j = 0; j < RC_NCB; ++j) Q_[j] = __builtin_fma(c, r[col + j], Q_[j]);
-#pragma unroll
-							for (int j = 0; j < RC_NCB; ++j) U_[j] = __builtin_fma(d, q[col + j], U_[j]);
-							__builtin_amdgcn_sched_barrier(0);
-							lv[col] = lp[col];
-							if (col & 1) {
-								r[col - 1] = rp[col - 1]; r[col] = rp[col];
-								const double2 u = wp[col >> 1]; wv[col - 1] = u.x; wv[col] = u.y;
-							}
-							__builtin_amdgcn_sched_barrier(0);
-						}
-#pragma unroll
-						for (int k = WS - 1; k < NR_; ++k) r[k] = rp[k];
-						wv[WS - 1] = CS.w[nrow][i][WS - 1];
-					}
+					double P_[RC_NCB], Q_[RC_NCB], U_[RC_NCB];
+					RowsRows<R> rows{ CS, rbase, rs, i };
+					block_onepass<WS, RC_NCB>(rows, mL, P_, Q_, U_);
 					constexpr double TT = (double)T;
 #pragma unroll
 					for (int j = 0; j < RC_NCB; ++j) {
 						if ((vm >> j) & 1u) {
 							bool okc;
 							const double v = onepass_finish(P_[j], Q_[j], U_[j], SA, tw, s2, TT, sig3, cb.zmax2, okc);   // (tw: 1/totalWeight in this form)
-							dst[(j - sh)*RC_WT] = !okc ? __builtin_nan("") : (v > cb.m_hi ? P.max_color_diff : v);
+							dst[(j - sh)*RC_WT] = block_stored<true>(v, okc, cb.m_hi, P.max_color_diff);
 						}
 					}
 				} else if (fast) {
 					// blocked fast form (srh_dense.hip): a row segment of NCB+2R values of the other view is
-					// read once per window row and shared by the NCB candidates and 2R+1 taps
-					// (a global pointer, not a generic one: flat loads would share the LDS counter, and every wait for a
-					// weight would then also wait for the row segments in flight)
+					// read once per window row and shared by the NCB candidates and 2R+1 taps; the loads are always a row ahead
+					// (srh_block.hpp): the segment from L1/L2, the weights and the reference row from LDS
 					const gptr rbase = rplane + (size_t)cy*rs + c0s;
-					// Both sweeps are scheduled by hand like the dense kernel's (srh_dense.hip): r[] / wv[] / av[] hold the
-					// current window row; as soon as a value has had its last use its register is refilled with the next
-					// row's value (the other view's segment from L1/L2, the weights and the reference row from LDS), so the
-					// loads are always a row ahead; products first, sums second, so that no instruction waits on its neighbour.
 					static_assert(WS % 2 == 1 && WP % 2 == 0, "odd window, window rows padded to 16 bytes");
-					double r[NR_], wv[WS], acc[RC_NCB];
-					{
-						const double2 *wp = reinterpret_cast<const double2 *>(&CS.w[0][i][0]);
-#pragma unroll
-						for (int k = 0; k < NR_; ++k) r[k] = rbase[k];
-#pragma unroll
-						for (int m = 0; m < (WS - 1)/2; ++m) { const double2 v = wp[m]; wv[2*m] = v.x; wv[2*m + 1] = v.y; }
-						wv[WS - 1] = CS.w[0][i][WS - 1];
-					}
-#pragma unroll
-					for (int j = 0; j < RC_NCB; ++j) acc[j] = 0.0;
-#pragma unroll 1
-					for (int row = 0; row < WS; ++row) {
-						const int nrow = row + 1 < WS ? row + 1 : 0;          // last refill = row 0, for the second sweep
-						const gptr rp = rbase + (size_t)nrow*rs;
-						const double2 *wp = reinterpret_cast<const double2 *>(&CS.w[nrow][i][0]);
-#pragma unroll
-						for (int col = 0; col < WS; ++col) {
-							if (FMA) {
-#pragma unroll
-								for (int j = 0; j < RC_NCB; ++j) acc[j] = __builtin_fma(wv[col], r[col + j], acc[j]);
-							} else {
-								double pr[RC_NCB];
-#pragma unroll
-								for (int j = 0; j < RC_NCB; ++j) pr[j] = wv[col]*r[col + j];
-								__builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-								for (int j = 0; j < RC_NCB; ++j) acc[j] += pr[j];            // meanR += weight*gray
-							}
-							__builtin_amdgcn_sched_barrier(0);                  // keep each refill where it is written
-							if (col & 1) {                                      // r[col-1], r[col], wv[col-1], wv[col] are dead
-								r[col - 1] = rp[col - 1]; r[col] = rp[col];
-								const double2 u = wp[col >> 1]; wv[col - 1] = u.x; wv[col] = u.y;
-								__builtin_amdgcn_sched_barrier(0);
-							}
-						}
-#pragma unroll
-						for (int k = WS - 1; k < NR_; ++k) r[k] = rp[k];
-						wv[WS - 1] = CS.w[nrow][i][WS - 1];
-					}
-					double mR[RC_NCB], s1[RC_NCB], s3[RC_NCB], av[WS];
-#pragma unroll
-					for (int col = 0; col < WS; ++col) av[col] = CS.lt[0][i + col];
-#pragma unroll
-					for (int j = 0; j < RC_NCB; ++j) { mR[j] = acc[j]/tw; s1[j] = 0.0; s3[j] = 0.0; }
-#pragma unroll 1
-					for (int row = 0; row < WS; ++row) {
-						const int nrow = row + 1 < WS ? row + 1 : 0;
-						const gptr rp = rbase + (size_t)nrow*rs;
-						const double2 *wp = reinterpret_cast<const double2 *>(&CS.w[nrow][i][0]);
-						const double *lp = &CS.lt[nrow][i];
-#pragma unroll
-						for (int col = 0; col < WS; ++col) {
-							const double wt = wv[col];
-							if (FMA) {
-								const double a = __builtin_fma(wt, av[col], -mL);
-								double bb[RC_NCB];
-#pragma unroll
-								for (int j = 0; j < RC_NCB; ++j) bb[j] = __builtin_fma(wt, r[col + j], -mR[j]);
-								__builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-								for (int j = 0; j < RC_NCB; ++j) { s1[j] = __builtin_fma(a, bb[j], s1[j]); s3[j] = __builtin_fma(bb[j], bb[j], s3[j]); }
-							} else {
-								double bb[RC_NCB], u1[RC_NCB], u3[RC_NCB];
-								const double pa = wt*av[col];
-#pragma unroll
-								for (int j = 0; j < RC_NCB; ++j) bb[j] = wt*r[col + j];
-								__builtin_amdgcn_sched_barrier(0);
-								const double a = pa - mL;                           // pixel_gray_l - meanL
-#pragma unroll
-								for (int j = 0; j < RC_NCB; ++j) bb[j] = bb[j] - mR[j];   // pixel_gray_r - meanR
-								__builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-								for (int j = 0; j < RC_NCB; ++j) { u1[j] = a*bb[j]; u3[j] = bb[j]*bb[j]; }
-								__builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-								for (int j = 0; j < RC_NCB; ++j) { s1[j] += u1[j]; s3[j] += u3[j]; }
-							}
-							__builtin_amdgcn_sched_barrier(0);
-							av[col] = lp[col];
-							if (col & 1) {
-								r[col - 1] = rp[col - 1]; r[col] = rp[col];
-								const double2 u = wp[col >> 1]; wv[col - 1] = u.x; wv[col] = u.y;
-							}
-							__builtin_amdgcn_sched_barrier(0);
-						}
-#pragma unroll
-						for (int k = WS - 1; k < NR_; ++k) r[k] = rp[k];
-						wv[WS - 1] = CS.w[nrow][i][WS - 1];
-					}
+					double s1[RC_NCB], s3[RC_NCB];
+					RowsRows<R> rows{ CS, rbase, rs, i };
+					block_two_sweeps<WS, RC_NCB, FMA>(rows, 0, WS, mL, tw, s1, s3);
 #pragma unroll
 					for (int j = 0; j < RC_NCB; ++j) {
-						if ((vm >> j) & 1u) {
-							const double v = 255*(1.0 - fabs(s1[j]) / sqrt(s2 * s3[j]));
-							if (CERT) dst[(j - sh)*RC_WT] = !(s3[j] >= sig3) ? __builtin_nan("") : (v > cb.m_hi ? P.max_color_diff : v);
-							else dst[(j - sh)*RC_WT] = (v < P.max_color_diff) ? v : P.max_color_diff;
-						}
+						if ((vm >> j) & 1u) dst[(j - sh)*RC_WT] = block_stored<CERT, const double &>(two_sweep_finish(s1[j], s2, s3[j]), s3[j] >= sig3, cb.m_hi, P.max_color_diff);
 					}
 				}
 				// what the fast form has left.  Masked form: the candidates of a pixel with a fully usable window of its own whose

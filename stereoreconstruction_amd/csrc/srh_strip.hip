@@ -22,6 +22,7 @@
 #include "srh_internal.hpp"
 #include "srh_geom.hpp"
 #include "srh_walk.hpp"
+#include "srh_block.hpp"
 
 #include <type_traits>
 
@@ -327,6 +328,50 @@ __device__ __noinline__ void strip_select_block(const StripSmem<R, NBUF> &S, int
 // The pixel's meanL, totalWeight and sum2 over those rows and the per-column "usable" bytes are worked out per tile into
 // the LDS copies of pconst and `full`; the band buffers are not touched (pconst slot 3 stays 0 there), so the certified
 // scan keeps treating the pixel's costs as the reference's very numbers (cert_pixel_exact) -- which they are, in every mode.
+// The row source of the block loops (srh_block.hpp) for the block at staged column rc of pixel i: window row `row` is ring
+// slot (s0 + row) mod NS; the other view's segment is read 16 bytes at a time from rbase (the rows, or their copy shifted by
+// one column for an odd rc); the weights from window buffer wb.
+// 8-wave form: at the start of a window row the wave publishes its progress and looks at its SIMD partner's; at the end it
+// yields (s_setprio 0) while ahead of the partner, 1 otherwise.  One asm statement with its own branch: the row loops stay
+// single basic blocks for the compiler's scheduler and register allocator.
+template <int R, int NWV, int NBUF>
+struct StripRows {
+	typedef StripSmem<R, NBUF> Smem;
+	static constexpr bool LDS_WAIT = true;
+	Smem &S;
+	const double *rbase;
+	int s0, wb, i, rc, wv, lane, partner;
+	int &prog;
+	struct Row {
+		const double2 *rp, *wp;
+		const double *lp;
+		__device__ __forceinline__ void r2(int m, double &a, double &b) const { const double2 v = rp[m]; a = v.x; b = v.y; }
+		__device__ __forceinline__ void w2(int m, double &a, double &b) const { const double2 v = wp[m]; a = v.x; b = v.y; }
+		__device__ __forceinline__ double w(int col) const { return reinterpret_cast<const double *>(wp)[col]; }
+		__device__ __forceinline__ double l(int col) const { return lp[col]; }
+	};
+	__device__ __forceinline__ Row row(int row) const {
+		const int sl = s0 + row >= Smem::NS ? s0 + row - Smem::NS : s0 + row;
+		return Row{ reinterpret_cast<const double2 *>(rbase + sl*Smem::RW + rc), reinterpret_cast<const double2 *>(&S.w[wb][row][i][0]), &S.lt[sl][i] };
+	}
+	__device__ __forceinline__ int row_begin(int units) const {
+		int seen = 0;
+		if (NWV == 8) {
+			prog += units;
+			*(st_lds_vint *)&S.prog[wv][lane] = prog;
+			seen = *(st_lds_vint *)&S.prog[partner][lane];
+		}
+		return seen;
+	}
+	__device__ __forceinline__ void row_end(int seen) const {
+		if (NWV == 8) {
+			const int ps = __builtin_amdgcn_readfirstlane(seen), pm = __builtin_amdgcn_readfirstlane(prog);
+			asm volatile("s_nop 0\n\ts_cmp_gt_i32 %0, %1\n\ts_cbranch_scc1 1f\n\ts_setprio 1\n\ts_branch 2f\n1:\n\ts_setprio 0\n2:"
+			             :: "s"(pm), "s"(ps) : "scc");
+		}
+	}
+};
+
 template <int R, int NWV, int NBUF, int AR, bool BORDER>
 __global__ __launch_bounds__(NWV*64, 2)
 void twoview_strip_cost_kernel(const StripArgs A)
@@ -369,24 +414,7 @@ void twoview_strip_cost_kernel(const StripArgs A)
 		for (int j = 0; j < NWV; ++j) if (j != wv && CS.simd[j] == simd) { partner = j; break; }
 		partner = __builtin_amdgcn_readfirstlane(partner);
 	}
-	int prog = 0;
-	// publish own progress, look at the partner's (value used by prog_yield at the end of the window row)
-	auto prog_step = [&](int units, int &seen) {
-		if (NWV == 8) {
-			prog += units;
-			*(st_lds_vint *)&S.prog[wv][lane] = prog;
-			seen = *(st_lds_vint *)&S.prog[partner][lane];
-		}
-	};
-	// s_setprio 0 while ahead of the partner, 1 otherwise.  One asm statement with its own branch: the row loops stay
-	// single basic blocks for the compiler's scheduler and register allocator.
-	auto prog_yield = [&](int seen) {
-		if (NWV == 8) {
-			const int ps = __builtin_amdgcn_readfirstlane(seen), pm = __builtin_amdgcn_readfirstlane(prog);
-			asm volatile("s_nop 0\n\ts_cmp_gt_i32 %0, %1\n\ts_cbranch_scc1 1f\n\ts_setprio 1\n\ts_branch 2f\n1:\n\ts_setprio 0\n2:"
-			             :: "s"(pm), "s"(ps) : "scc");
-		}
-	};
+	int prog = 0;                                // progress inside the current tile (StripRows: published per window row)
 	// per-wave phase clocks exist only in the -DSRH_PROFILE_PHASES diagnostic build: a handful of s_memtime per tile,
 	// none inside the block loops
 #ifdef SRH_PROFILE_PHASES
@@ -623,6 +651,7 @@ void twoview_strip_cost_kernel(const StripArgs A)
 					const int rc = c0 - cs;                 // tile column of the window's left edge
 					// 16-byte reads need an even index: an odd edge reads the copy shifted by one column
 					const double *rbase = (!PAD && (rc & 1)) ? &CS.rto[0][0] - 1 : &CS.rt[0][0];
+					StripRows<R, NWV, NBUF> rows{ S, rbase, s0, wcur, i, rc, wv, lane, partner, prog };
 					// bit j: candidate c0 + j is inside the pixel's range and its window in the other view is fully usable
 					unsigned vm = 0;
 #pragma unroll
@@ -644,121 +673,16 @@ void twoview_strip_cost_kernel(const StripArgs A)
 					auto two_sweeps = [&](auto fma_c, auto cert_c) {
 						constexpr bool FMAc = decltype(fma_c)::value, CERTc = decltype(cert_c)::value;
 						const double mL = CS.pc[cur][i][0], tw = CS.pc[cur][i][1], s2 = CS.pc[cur][i][2];
-						// window rows [ra, rb): all of them, as compile-time bounds, outside the border instantiation
-						const int ra = BORDER ? bra : 0, rb = BORDER ? brb : WS;
-						const int sa = BORDER ? (s0 + ra >= NS ? s0 + ra - NS : s0 + ra) : s0;
-						// Both passes are modulo-scheduled by hand (see twoview_dense_cost_kernel): a register is refilled
-						// with the next row's value right after its last use, so the LDS latency is always a row ahead.
-						double r_[NR], wv_[WS], acc[NCB];
-						{
-							const double2 *rp = reinterpret_cast<const double2 *>(rbase + sa*RW + rc);
-							const double2 *wp = reinterpret_cast<const double2 *>(&CS.w[wcur][ra][i][0]);
-#pragma unroll
-							for (int m = 0; m < NR/2; ++m) { const double2 v = rp[m]; r_[2*m] = v.x; r_[2*m + 1] = v.y; }
-#pragma unroll
-							for (int m = 0; m < (WS - 1)/2; ++m) { const double2 v = wp[m]; wv_[2*m] = v.x; wv_[2*m + 1] = v.y; }
-							wv_[WS - 1] = CS.w[wcur][ra][i][WS - 1];
-						}
-#pragma unroll
-						for (int j = 0; j < NCB; ++j) acc[j] = 0.0;
-						__builtin_amdgcn_s_waitcnt(0xC07F);              // lgkmcnt(0): the pre-header's reads have landed
-#pragma unroll 1
-						for (int row = ra; row < rb; ++row) {
-							int seen = 0;
-							prog_step(1, seen);
-							const int nrow = row + 1 < rb ? row + 1 : ra;         // last refill = row ra, for pass 2
-							const int nsl = s0 + nrow >= NS ? s0 + nrow - NS : s0 + nrow;
-							const double2 *rp = reinterpret_cast<const double2 *>(rbase + nsl*RW + rc);
-							const double2 *wp = reinterpret_cast<const double2 *>(&CS.w[wcur][nrow][i][0]);
-#pragma unroll
-							for (int col = 0; col < WS; ++col) {
-								if (FMAc) {
-#pragma unroll
-									for (int j = 0; j < NCB; ++j) acc[j] = __builtin_fma(wv_[col], r_[col + j], acc[j]);
-								} else {
-									double pr[NCB];
-#pragma unroll
-									for (int j = 0; j < NCB; ++j) pr[j] = wv_[col]*r_[col + j];
-									__builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-									for (int j = 0; j < NCB; ++j) acc[j] += pr[j];        // meanR += weight*gray
-								}
-								__builtin_amdgcn_sched_barrier(0);
-								if (col & 1) {
-									const double2 v = rp[col >> 1]; r_[col - 1] = v.x; r_[col] = v.y;
-									const double2 u = wp[col >> 1]; wv_[col - 1] = u.x; wv_[col] = u.y;
-									__builtin_amdgcn_sched_barrier(0);
-								}
-							}
-#pragma unroll
-							for (int m = (WS - 1)/2; m < NR/2; ++m) { const double2 v = rp[m]; r_[2*m] = v.x; r_[2*m + 1] = v.y; }
-							wv_[WS - 1] = CS.w[wcur][nrow][i][WS - 1];
-							prog_yield(seen);
-						}
-						double mR[NCB], s1[NCB], s3[NCB], av[WS];
-#pragma unroll
-						for (int col = 0; col < WS; ++col) av[col] = CS.lt[sa][i + col];
-#pragma unroll
-						for (int j = 0; j < NCB; ++j) { mR[j] = acc[j]/tw; s1[j] = 0.0; s3[j] = 0.0; }
-						__builtin_amdgcn_s_waitcnt(0xC07F);
-#pragma unroll 1
-						for (int row = ra; row < rb; ++row) {
-							int seen = 0;
-							prog_step(3, seen);
-							const int nrow = row + 1 < rb ? row + 1 : ra;
-							const int nsl = s0 + nrow >= NS ? s0 + nrow - NS : s0 + nrow;
-							const double2 *rp = reinterpret_cast<const double2 *>(rbase + nsl*RW + rc);
-							const double2 *wp = reinterpret_cast<const double2 *>(&CS.w[wcur][nrow][i][0]);
-							const double *lp = &CS.lt[nsl][i];
-#pragma unroll
-							for (int col = 0; col < WS; ++col) {
-								const double wt = wv_[col];
-								if (FMAc) {
-									const double a = __builtin_fma(wt, av[col], -mL);
-									double bb[NCB];
-#pragma unroll
-									for (int j = 0; j < NCB; ++j) bb[j] = __builtin_fma(wt, r_[col + j], -mR[j]);
-									__builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-									for (int j = 0; j < NCB; ++j) { s1[j] = __builtin_fma(a, bb[j], s1[j]); s3[j] = __builtin_fma(bb[j], bb[j], s3[j]); }
-								} else {
-									double bb[NCB], u1[NCB], u3[NCB];
-									const double pa = wt*av[col];
-#pragma unroll
-									for (int j = 0; j < NCB; ++j) bb[j] = wt*r_[col + j];
-									__builtin_amdgcn_sched_barrier(0);
-									const double a = pa - mL;                         // pixel_gray_l - meanL
-#pragma unroll
-									for (int j = 0; j < NCB; ++j) bb[j] = bb[j] - mR[j];   // pixel_gray_r - meanR
-									__builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-									for (int j = 0; j < NCB; ++j) { u1[j] = a*bb[j]; u3[j] = bb[j]*bb[j]; }
-									__builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-									for (int j = 0; j < NCB; ++j) { s1[j] += u1[j]; s3[j] += u3[j]; }
-								}
-								__builtin_amdgcn_sched_barrier(0);
-								av[col] = lp[col];
-								if (col & 1) {
-									const double2 v = rp[col >> 1]; r_[col - 1] = v.x; r_[col] = v.y;
-									const double2 u = wp[col >> 1]; wv_[col - 1] = u.x; wv_[col] = u.y;
-								}
-								__builtin_amdgcn_sched_barrier(0);
-							}
-#pragma unroll
-							for (int m = (WS - 1)/2; m < NR/2; ++m) { const double2 v = rp[m]; r_[2*m] = v.x; r_[2*m + 1] = v.y; }
-							wv_[WS - 1] = CS.w[wcur][nrow][i][WS - 1];
-							prog_yield(seen);
-						}
+						// window rows [bra, brb): all of them, as compile-time bounds, outside the border instantiation
+						double s1[NCB], s3[NCB];
+						block_two_sweeps<WS, NCB, FMAc>(rows, BORDER ? bra : 0, BORDER ? brb : WS, mL, tw, s1, s3);
 #pragma unroll
 						for (int j = 0; j < NCB; ++j) {
 							const int c = c0 + j;
 							if (c >= lo && c <= hi && rfull[rc + j] != 0) {
-								const double v = 255*(1.0 - fabs(s1[j]) / sqrt(s2 * s3[j]));
-								if (CERTc) {
-									if (!(s3[j] >= sig3) && A.redo) bad_blk = true;
-									crow[(size_t)(c - e_min)*ST_TP] = !(s3[j] >= sig3) ? __builtin_nan("") : (v > A.cb.m_hi ? A.max_color_diff : v);
-								} else crow[(size_t)(c - e_min)*ST_TP] = (v < A.max_color_diff) ? v : A.max_color_diff;
+								const bool okc = s3[j] >= sig3;
+								if (CERTc && !okc && A.redo) bad_blk = true;
+								crow[(size_t)(c - e_min)*ST_TP] = block_stored<CERTc, const double &>(two_sweep_finish(s1[j], s2, s3[j]), okc, A.cb.m_hi, A.max_color_diff);
 							}
 							__builtin_amdgcn_sched_barrier(0);
 						}
@@ -769,57 +693,8 @@ void twoview_strip_cost_kernel(const StripArgs A)
 						// ---- certified ONE-PASS form (srh_wta.hpp, CertBound): P = sum w r, Q = sum ((w l - meanL) w) r,
 						// U = sum w^2 r^2 in one sweep over the window; registers are refilled in place a row ahead, as below
 						const double mL = CS.pc[cur][i][0], itw = CS.pc[cur][i][3], s2 = CS.pc[cur][i][2];   // (slot 3 of a pixel with every tap usable: 1/totalWeight)
-						double r_[NR], q_[NR], w_[WS], l_[WS], P_[NCB], Q_[NCB], U_[NCB];
-						{
-							const double2 *rp = reinterpret_cast<const double2 *>(rbase + s0*RW + rc);
-							const double2 *wp = reinterpret_cast<const double2 *>(&CS.w[wcur][0][i][0]);
-#pragma unroll
-							for (int m = 0; m < NR/2; ++m) { const double2 v = rp[m]; r_[2*m] = v.x; r_[2*m + 1] = v.y; }
-#pragma unroll
-							for (int m = 0; m < (WS - 1)/2; ++m) { const double2 v = wp[m]; w_[2*m] = v.x; w_[2*m + 1] = v.y; }
-							w_[WS - 1] = CS.w[wcur][0][i][WS - 1];
-#pragma unroll
-							for (int col = 0; col < WS; ++col) l_[col] = CS.lt[s0][i + col];
-						}
-#pragma unroll
-						for (int j = 0; j < NCB; ++j) { P_[j] = 0.0; Q_[j] = 0.0; U_[j] = 0.0; }
-						__builtin_amdgcn_s_waitcnt(0xC07F);
-#pragma unroll 1
-						for (int row = 0; row < WS; ++row) {
-							int seen = 0;
-							prog_step(4, seen);
-							const int nrow = row + 1 < WS ? row + 1 : 0;          // (the last refill is never used)
-							const int nsl = s0 + nrow >= NS ? s0 + nrow - NS : s0 + nrow;
-							const double2 *rp = reinterpret_cast<const double2 *>(rbase + nsl*RW + rc);
-							const double2 *wp = reinterpret_cast<const double2 *>(&CS.w[wcur][nrow][i][0]);
-							const double *lp = &CS.lt[nsl][i];
-#pragma unroll
-							for (int k = 0; k < NCB - 1; ++k) q_[k] = r_[k]*r_[k];
-#pragma unroll
-							for (int col = 0; col < WS; ++col) {
-								q_[col + NCB - 1] = r_[col + NCB - 1]*r_[col + NCB - 1];
-								const double a = __builtin_fma(w_[col], l_[col], -mL);
-								const double c = a*w_[col], d = w_[col]*w_[col];
-								__builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-								for (int j = 0; j < NCB; ++j) P_[j] = __builtin_fma(w_[col], r_[col + j], P_[j]);
-#pragma unroll
-								for (int j = 0; j < NCB; ++j) Q_[j] = __builtin_fma(c, r_[col + j], Q_[j]);
-#pragma unroll
-								for (int j = 0; j < NCB; ++j) U_[j] = __builtin_fma(d, q_[col + j], U_[j]);
-								__builtin_amdgcn_sched_barrier(0);
-								l_[col] = lp[col];
-								if (col & 1) {
-									const double2 v = rp[col >> 1]; r_[col - 1] = v.x; r_[col] = v.y;
-									const double2 u = wp[col >> 1]; w_[col - 1] = u.x; w_[col] = u.y;
-								}
-								__builtin_amdgcn_sched_barrier(0);
-							}
-#pragma unroll
-							for (int m = (WS - 1)/2; m < NR/2; ++m) { const double2 v = rp[m]; r_[2*m] = v.x; r_[2*m + 1] = v.y; }
-							w_[WS - 1] = CS.w[wcur][nrow][i][WS - 1];
-							prog_yield(seen);
-						}
+						double P_[NCB], Q_[NCB], U_[NCB];
+						block_onepass<WS, NCB>(rows, mL, P_, Q_, U_);
 						constexpr double TT = (double)(WS*WS);
 						// every candidate of the block is finished (arithmetic on a column outside the range harms nobody); only the
 						// store looks at the candidate's bit -- no LDS read, wait and branch per candidate
@@ -833,7 +708,7 @@ void twoview_strip_cost_kernel(const StripArgs A)
 							const double v = onepass_finish(P_[j], Q_[j], U_[j], SA, itw, s2, TT, sig3, zmax2, okc);
 							const bool st = (vm >> j) & 1u;
 							bad_blk |= st & !okc & redo;
-							if (st) crow[(size_t)(c0 + j - e_min)*ST_TP] = !okc ? __builtin_nan("") : (v > mhi ? mcd : v);
+							if (st) crow[(size_t)(c0 + j - e_min)*ST_TP] = block_stored<true>(v, okc, mhi, mcd);
 						}
 					} else if (fast && !ONEPASS && !pix_exact) two_sweeps(std::integral_constant<bool, FMA>(), std::integral_constant<bool, CERT>());
 					if (!BORDER && fast && CERT && (pix_exact || bad_blk)) two_sweeps(std::false_type(), std::false_type());   // (bad_blk is only raised when A.redo)

@@ -86,7 +86,7 @@ struct WtaState {
 // of the real-number cost, the reference's arithmetic within half of k1/B + k2/A + k3: a candidate is
 // certified when sum3 >= sigma3(sum2) (the latter <= e0/2) and Q3 <= zmax2*sum3 (the former <= e0/2).
 // The FINISH of a one-pass candidate is free of IEEE divisions and of the IEEE square root as well (onepass_finish,
-// srh_internal.hpp): m = P*itw with itw = fl(1/tw) from the weights kernels (one more rounding on m: every gamma index of
+// srh_block.hpp): m = P*itw with itw = fl(1/tw) from the weights kernels (one more rounding on m: every gamma index of
 // the derivation goes up by one; the code takes gamma_(T+6) for both terms), 1/sqrt(sum2*sum3) by v_rsq_f64 and ONE
 // third-order Newton step whose own residual e = 1 - x*y0^2 is part of the certificate (|e| <= 2^-20, whatever the seed's
 // accuracy: y1 = y0*(1 + e/2 + 3e^2/8) is then within 2u of 1/sqrt(x)), and v = fma(-255, |sum1|*y1, 255): x, the product
@@ -141,7 +141,8 @@ inline CertBound cert_bound(const srh_params &P, bool mvs = false) {
 //                                                     there -- it does so only for a fused value above clamp + e0, and
 //                                                     the clamp is 1-Lipschitz, so c is the clamp -- or when a select
 //                                                     form computed it.  It is NOT proved for a fused value whose own
-//                                                     bits are the clamp's: the kernels store it as it is, and c may lie
+//                                                     bits are the clamp's: the kernels store it as it is (block_stored,
+//                                                     srh_block.hpp: the one statement of the rule), and c may lie
 //                                                     up to e0 below it.  A GAP of the certificate, the parent's
 //                                                     behaviour, left as it is; tests/test_wta_host.py keeps the case
 //                                                     (test_fused_cost_equal_to_the_clamp, a strict xfail);
