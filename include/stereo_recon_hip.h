@@ -212,6 +212,8 @@ enum { SRH_WTA_WINNERS = 1, SRH_WTA_COSTS = 2 };
  *   "strip"           1 (default): the dense cost kernel runs in its persistent strip form (one workgroup walks a
  *                     tile column down the rows, every input enters LDS by LDS-DMA); 0: one workgroup per tile;
  *                     4 / 8: force the 4-wave / 8-wave form of the strip kernel.  Results are identical bits.
+ *                     SRH_WEIGHT_GEODESIC with geodesic_sigma <= 0 (weights that are not finite outside the image) takes
+ *                     one workgroup per tile whatever the option says.
  *   "mvs_staged"      1 (default): the MultiViewStereo list cost kernel takes its 25-tap windows from LDS copies of the
  *                     other view (one box per stretch of list slots and wave) where they fit; 0: every window is gathered
  *                     from memory (round 2's kernel).  Results are identical bits.
@@ -715,6 +717,11 @@ int  srh_mvs_fused_device(srh_context *ctx, void **xyz, void **normals, void **r
  *                      elsewhere weightedMedian of G over the support window of I at the pixel (p->weight_kind,
  *                      p->window_radius <= 5: else SRH_E_UNSUPPORTED): taps with a depth not NaN, inside
  *                      [min_depth, max_depth] and a weight > 1e-10, the libstdc++ heap's pop order, NaN for fewer than two.
+ *                      The reference's loop also reads depths at taps OUTSIDE the image (another row, or past the map);
+ *                      such a tap has the window weight exp(-geodesic_init/geodesic_sigma) (adaptive: 0) and the device
+ *                      skips it, which is the reference's result only while that weight is not > 1e-10.  With
+ *                      SRH_WEIGHT_GEODESIC and geodesic_sigma <= 0 or exp(-geodesic_init/geodesic_sigma) > 1e-10:
+ *                      SRH_E_UNSUPPORTED, before anything is launched (srh_twoview_compute* under "filter_invalid" too).
  * Results are the same bits as the reference's loops.  Any slot works (MultiViewStereo views at radius 2 too); the
  * reference has this stage for TwoViewStereo (radius 5) only, the one parity target.  info may be NULL. */
 enum { SRH_FILTER_GAPS = 1, SRH_FILTER_MEDIAN = 2 };

@@ -2194,6 +2194,10 @@ static int twoview_wta_run(srh_context *c, const Lane &lane, srh_context::TvDefe
 	// the persistent strip form of the cost kernel: exact / fma arithmetic, candidate ranges of a 32-pixel tile inside one
 	// LDS chunk; anything else, or a range that turns out wider, takes the per-tile kernel
 	D.strip = dense && (P.sad || (c->strip != 0 && c->arith != 2)) && plan.cstride + SRH_WTILE <= strip_chunk_columns();
+	// (strip_select_block, the strip kernel's blocked select form, drops an unusable tap by multiplying with 0.0 and needs
+	// finite weights for it; geodesic_sigma <= 0 gives the taps outside the image, which keep geodesic_init, the weight
+	// +inf or NaN: such a pass takes the per-tile kernel, whose select forms are true selects)
+	if (!P.sad && p->weight_kind == SRH_WEIGHT_GEODESIC && !(p->geodesic_sigma > 0)) D.strip = false;
 	// certified arithmetic (arith = 3, the default): fused cost loops in the strip kernel + the certified scan; where the
 	// strip kernel does not run, or the parameters leave the bound no room, the reference's arithmetic
 	bool cert_ok = c->arith == 3 && !P.sad && cert_bound(*p).ok != 0;
@@ -2265,6 +2269,7 @@ extern "C" int srh_twoview_cost_rows(srh_context *c, int ref, int oth, const srh
 	TvDense D;
 	D.cstride = plan.cstride;
 	D.strip = (sad || c->strip != 0) && plan.cstride + SRH_WTILE <= strip_chunk_columns();
+	if (!sad && p->weight_kind == SRH_WEIGHT_GEODESIC && !(p->geodesic_sigma > 0)) D.strip = false;   // (as in the pass: finite weights only)
 	D.cert = form != 0 && !sad && cert_bound(*p).ok != 0;
 	if (form == 2) D.strip = D.cert = false;                      // (the f32 kernel is a per-tile kernel, as in the pass under arith = 2)
 	if ((rc = P.dense_prepare(D))) return rc;
@@ -2353,12 +2358,15 @@ static bool tv_pass_stands(const srh_context::TvDefer &d) {
 }
 
 static int twoview_filter(srh_context *c, int left, int right, const srh_params *p);
+static int check_filter(srh_context *c, int slot, const srh_params *p, int flags);
 
 extern "C" int srh_twoview_compute(srh_context *c, int left, int right, const srh_params *p,
                                    double *left_out, double *right_out)
 {
 	int rc;
 	if ((rc = check_slot(c, left, true)) || (rc = check_slot(c, right, true)) || (rc = check_params(p))) return rc;
+	// option "filter_invalid": what the hole filling refuses is refused before any launch, not after the two passes
+	if (c->filter_invalid && ((rc = check_filter(c, left, p, c->filter_invalid)) || (rc = check_filter(c, right, p, c->filter_invalid)))) return rc;
 	HIP_TRY(hipSetDevice(c->device));
 	for (auto &d : c->tv_defer) {
 		if (!d.host) HIP_TRY(hipHostMalloc((void **)&d.host, sizeof(Counters)));
@@ -3073,6 +3081,12 @@ static int check_filter(srh_context *c, int slot, const srh_params *p, int flags
 	if (flags < 0 || flags > (SRH_FILTER_GAPS | SRH_FILTER_MEDIAN)) return fail(SRH_E_INVALID, "filter flags %d unknown", flags);
 	if ((flags & SRH_FILTER_MEDIAN) && p->window_radius > 5)
 		return fail(SRH_E_UNSUPPORTED, "weighted median: window_radius %d > 5", p->window_radius);
+	// filter_median_kernel skips the taps outside the image; the reference reads depths there and keeps such a tap when
+	// its window weight exp(-geodesic_init/geodesic_sigma) is > 1e-10 (srh_filter.hip): the skip is its result only below
+	if ((flags & SRH_FILTER_MEDIAN) && p->weight_kind == SRH_WEIGHT_GEODESIC &&
+	    !(p->geodesic_sigma > 0 && exp(-p->geodesic_init/p->geodesic_sigma) <= 1e-10))
+		return fail(SRH_E_UNSUPPORTED, "weighted median: geodesic_init %g, geodesic_sigma %g give the taps outside the image a weight above 1e-10",
+		            p->geodesic_init, p->geodesic_sigma);
 	if ((size_t)c->views[slot].w*c->views[slot].h >= ((size_t)1 << 31))
 		return fail(SRH_E_UNSUPPORTED, "hole filling: view of %d x %d pixels", c->views[slot].w, c->views[slot].h);
 	return SRH_OK;
@@ -3528,6 +3542,7 @@ static int tv_stage_compute(srh_context *c, const TvStage &T, int left, int righ
 	int rc;
 	const ViewHost &L = c->views[left], &Rv = c->views[right];
 	if (L.w != Rv.w || L.h != Rv.h) return fail(SRH_E_INVALID, "TwoViewStereo needs equal-sized views");
+	if (c->filter_invalid && ((rc = check_filter(c, left, p, c->filter_invalid)) || (rc = check_filter(c, right, p, c->filter_invalid)))) return rc;
 	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
 	for (int k = 0; k < 2; ++k) {
 		const int ref = k == 0 ? left : right, oth = k == 0 ? right : left;

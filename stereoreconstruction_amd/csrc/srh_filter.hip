@@ -79,8 +79,9 @@ __global__ __launch_bounds__(FM_LANES) void filter_median_kernel(const ViewDev *
 		double *wb = wl + lane;
 		support_window(V, P, cx, cy, [&](int r, int c) -> double & { return wb[(r*WS + c)*FM_LANES]; });
 		// weightedMedian's keeping loop (:826-842).  The reference reads depths[PV(xt, yt)] also for taps outside the image
-		// (another row, or past the map); its window weight there is exp(-geodesic_init/sigma) = 0 (adaptive: 0), never
-		// > 1e-10, so such a tap is never kept and skipping it gives the reference's result wherever it does not fault.
+		// (another row, or past the map); its window weight there is exp(-geodesic_init/sigma) (adaptive: 0), which the
+		// host admits only when it is not > 1e-10 (check_filter, srh_api.hip; the defaults give 0), so such a tap is never
+		// kept and skipping it gives the reference's result wherever it does not fault.
 		uint8_t *h = hp + lane;
 		const ptrdiff_t gb = (ptrdiff_t)(cy - R)*W + (cx - R);     // G[gb + toff[t]]: tap t (in the image only)
 		int n = 0;

@@ -595,11 +595,14 @@ void twoview_rows_cost_kernel(const ViewDev *__restrict__ views, int ref, int ot
 				for (int col = 0; col < WS; ++col) {
 					const double gl = CS.lt[row][pi + col], wt = CS.w[row][pi][col];
 					const bool okl = gl == gl && wt > P.weight_cutoff;
-					const double pl = wt*(gl == gl ? gl : 0.0), kl = okl ? 1.0 : 0.0;
+					// (weight 0.0 for a tap whose own side is unusable, as in the first sweep: the weight of a tap outside the image
+					// is +inf under a negative geodesic_sigma, and inf*0.0 a NaN.  strip_select_block keeps the product form and
+					// is not run on such weights: TvPass, srh_api.hip)
+					const double w0 = okl ? wt : 0.0, pl = okl ? wt*gl : 0.0, kl = okl ? 1.0 : 0.0;
 #pragma unroll
 					for (int j = 0; j < RC_NCB; ++j) {
 						const double k = kl*rv[col + j];                       // 1.0: the tap counts for this candidate
-						const double a = (pl - mLs[j])*k, bq = (wt*rr[col + j] - mRs[j])*k;
+						const double a = (pl - mLs[j])*k, bq = (w0*rr[col + j] - mRs[j])*k;
 						s1[j] += a*bq;
 						s2v[j] += a*a;
 						s3[j] += bq*bq;

@@ -67,7 +67,7 @@ struct WtaState {
 // The dense cost loops run with fused multiply-adds (half the FP64 instructions); a depth map depends on costs only
 // through comparisons (the two above and the max_color_diff clamp, twoviewstereo.cpp:976), so the fused costs may stand in
 // for the reference's wherever no comparison's margin is inside the error bound.  For a fast-form candidate (all T taps
-// usable; weights in (0,1], grays in [0,255]; meanL, totalWeight and sum2 are the SAME bits in both arithmetics), with
+// usable; weights in (0,1] -- or up to wmax, see cert_bound --, grays in [0,255]; meanL, totalWeight and sum2 are the SAME bits in both arithmetics), with
 // u = 2^-53, gamma_k = k*u/(1-k*u), G = 256, A = sqrt(sum2), B = sqrt(sum3):
 //     eps_b = gamma_(T+4)*G   (error of w*g_R - meanR: the mean's T-term sum and division, the product, the subtraction)
 //     eps_a = 2*u*G           (error of w*g_L - meanL: meanL is shared)
@@ -95,7 +95,7 @@ struct WtaState {
 struct CertBound {
 	double e0, m_hi, k1, k2, room;
 	double zmax2;
-	int ok;                                 // 0: the parameters leave the bound no room / weights are not in (0,1]: exact arithmetic
+	int ok;                                 // 0: the parameters leave the bound no room / weights are not in (0, wmax]: exact arithmetic
 	SRH_NHD double sigma3(double s2) const {
 		const double d = room - k2/sqrt(s2);                      // (NaN or zero sum2: d is NaN or -inf)
 		if (!(d > 0)) return __builtin_inf();
@@ -106,7 +106,16 @@ struct CertBound {
 // mvs: the free cost_ncc of MultiViewStereo (multiviewstereo.cpp:113-189): the score sum1/sqrt(sum2*sum3) itself (no factor
 // 255, no clamp), 25 taps at the reference's radius; e0 = 2^-36 there (scores live in [-1, 1])
 inline CertBound cert_bound(const srh_params &P, bool mvs = false) {
-	const double u = 0x1p-53, G = 256.0;
+	// Weights above 1: a geodesic window started below zero (geodesic_init < 0, sigma > 0) keeps geodesic_init on every tap but
+	// the centre, whose distance stays in [geodesic_init, 0]: weights in [1, wmax], wmax = exp(-geodesic_init/geodesic_sigma).
+	// The derivation sees the weights only through G, the bound of |weight*gray|: eps_a and eps_b, hence k1 and k2, are
+	// linear in it; k3 and the one-pass form's z^2 = Q3/sum3 are ratios that a common factor of the weights leaves alone.
+	// So G = 256*wmax covers them (sum2 and sum3 grow by wmax^2 with it: as many candidates certify as at wmax = 1), up to
+	// the magnitude the other parameters are held to (wmax <= 1e5: no sum comes near the range's end).  With G = 256 the
+	// test sum3 >= sigma3(sum2) would admit bounds up to wmax*e0.
+	const bool geo = P.weight_kind == SRH_WEIGHT_GEODESIC;
+	const double wmax = geo && P.geodesic_sigma > 0 && P.geodesic_init < 0 ? exp(-P.geodesic_init/P.geodesic_sigma) : 1.0;
+	const double u = 0x1p-53, G = 256.0*wmax;
 	const int T = (2*P.window_radius + 1)*(2*P.window_radius + 1);
 	auto gamma = [&](int k) { return k*u/(1.0 - k*u); };
 	const double eps_b = gamma(T + 4)*G, eps_a = 2*u*G, rt = sqrt((double)T);
@@ -123,7 +132,7 @@ inline CertBound cert_bound(const srh_params &P, bool mvs = false) {
 		const double z = rhs > 0 ? (-3.0 + sqrt(9.0 + 4*2.002*rhs))/(2*2.002) : 0.0;
 		c.zmax2 = z*z*(1.0 - 0x1p-20);
 	}
-	const bool weights_ok = P.weight_kind == SRH_WEIGHT_GEODESIC ? P.geodesic_sigma > 0 : P.adaptive_color_sigma > 0;   // exp(-distance/sigma) <= 1
+	const bool weights_ok = geo ? P.geodesic_sigma > 0 && wmax <= 1e5 : P.adaptive_color_sigma > 0;   // exp(-distance/sigma) <= 1 (geodesic: <= wmax)
 	if (mvs) { c.ok = c.room > 0 && weights_ok && fabs(P.peak_threshold) <= 1e5; return c; }
 	// what the doubt tests below assume of the parameters: max_color_diff + e0 > max_color_diff (so below 2^22),
 	// wta_margin >= 0, and magnitudes <= 1e5

@@ -329,3 +329,28 @@ def test_bound_constants_are_the_documented_ones():
     assert capi.cert_sigma3(p, 0.0) == math.inf and capi.cert_sigma3(p, 1e-6) == math.inf
     for kw in (dict(wta_margin=-1e-3), dict(max_color_diff=1e7), dict(geodesic_sigma=0.0), dict(bad_ret=1e9)):
         assert capi.cert_bound(capi.params_twoview(**kw))["ok"] == 0, kw
+
+
+def test_weights_above_one_scale_the_bound():
+    """geodesic_init < 0 gives window weights in [1, wmax], wmax = exp(-geodesic_init/geodesic_sigma): the bound's G, hence k1
+    and k2, grow by wmax (srh_wta.hpp; tests/test_gpu_constants.py measures the fused rows against it on the device); beyond
+    wmax = 1e5, and for the sums' sake, no certificate.  Adaptive windows do not read geodesic_init."""
+    base = capi.cert_bound(capi.params_twoview())
+    for init, sigma in ((-100.0, 50.0), (-1.0, 50.0), (-100.0, 10.0)):
+        cb = capi.cert_bound(capi.params_twoview(geodesic_init=init, geodesic_sigma=sigma))
+        wmax = math.exp(-init / sigma)
+        assert cb["ok"] == 1 and cb["e0"] == base["e0"] and cb["k3"] == base["k3"] and cb["zmax2"] == base["zmax2"]
+        assert abs(cb["k1"] / base["k1"] - wmax) < 1e-12 * wmax and abs(cb["k2"] / base["k2"] - wmax) < 1e-12 * wmax
+        # the certification threshold moves with the weights: a window scaled by wmax certifies the same candidates
+        s2 = 1e4
+        assert abs(capi.cert_sigma3(capi.params_twoview(geodesic_init=init, geodesic_sigma=sigma), s2 * wmax ** 2) /
+                   (wmax ** 2 * capi.cert_sigma3(capi.params_twoview(), s2)) - 1.0) < 1e-9
+    for init in (0.0, 30.0, 1e300):
+        cb = capi.cert_bound(capi.params_twoview(geodesic_init=init))
+        assert cb["ok"] == 1 and cb["k1"] == base["k1"] and cb["k2"] == base["k2"]
+    assert capi.cert_bound(capi.params_twoview(geodesic_init=-1e4))["ok"] == 0              # wmax = e^200
+    assert capi.cert_bound(capi.params_twoview(geodesic_init=-600.0))["ok"] == 0            # wmax = e^12 > 1e5
+    assert capi.cert_bound(capi.params_twoview(geodesic_init=-100.0, geodesic_sigma=-50.0))["ok"] == 0
+    assert capi.cert_bound(capi.params_mvs(geodesic_init=-100.0), mvs=True)["ok"] == 1
+    adaptive = capi.cert_bound(capi.params_twoview(weight_kind=capi.WEIGHT_ADAPTIVE, geodesic_init=-100.0))
+    assert adaptive["ok"] == 1 and adaptive["k1"] == base["k1"]
