@@ -189,7 +189,7 @@ int  srh_synchronize(srh_context *ctx);
 enum { SRH_COST_NCC = 0, SRH_COST_SAD = 1 };
 /* By-products of the TwoView winner-take-all scan a pass keeps per reference pixel (option "wta_outputs") */
 enum { SRH_WTA_WINNERS = 1, SRH_WTA_COSTS = 2 };
-/* Tuning / test switches (results never depend on them, "arith" = 1 / 2, "cost" and "filter_invalid" excepted):
+/* Tuning / test switches (results never depend on them, "arith" = 1 / 2, "cost", "filter_invalid" and "speckle_*" excepted):
  *   "force_generic"   0 default paths; 1 never the dense row-aligned TwoView kernels nor the MVS list kernels;
  *                     2 additionally no candidate lists at all (one thread per pixel walks and costs its curve)
  *   "fused"           1: row-aligned pairs run the single fused kernel (geometry + cost + WTA per 16-pixel tile
@@ -279,6 +279,14 @@ enum { SRH_WTA_WINNERS = 1, SRH_WTA_COSTS = 2 };
  *   "filter_gap_width" the gap width srh_twoview_compute's filter uses (default 2, GAP_WIDTH_THRESHOLD)
  *   "filter_replay"   1: every median hole is selected by the exact replay of the heap (a test hook: identical bits; the
  *                     replay is today the only selection)
+ *   "speckle_min_size"  CHANGES RESULTS.  0 (default): off -- not one extra launch, allocation or copy.  n > 0:
+ *                     srh_twoview_compute, srh_twoview_compute_mrf and srh_twoview_compute_sgm run srh_view_filter_speckles
+ *                     with min_size = n and the reject value +INF on both maps, between the cross-check and the
+ *                     "filter_invalid" tail, with a stage text of its own ("Removing speckles...") at progress step 5, the
+ *                     cross-check's step.  Negative values: SRH_E_INVALID.
+ *   "speckle_diff_steps"  CHANGES RESULTS (under "speckle_min_size" only).  The stage's max_diff in depth steps (default 2):
+ *                     max_diff = (double)steps * ((max_depth - min_depth)/(double)(num_depth_levels - 1)).  Values < 1:
+ *                     SRH_E_INVALID.
  * The library reads no environment variable: what a host runs is what it set here. */
 int  srh_set_option(srh_context *ctx, const char *name, long value);
 
@@ -396,7 +404,7 @@ int  srh_twoview_pair_costs(srh_context *ctx, int ref_slot, int oth_slot, const 
 int  srh_debug_exp(srh_context *ctx, const double *x, int n, double *kernel_out, double *library_out);
 int  srh_twoview_cross_check(srh_context *ctx, int left_slot, int right_slot, const srh_params *p);
 /* computeDepthMaps minus colourisation (twoviewstereo.cpp:150-227): both passes +
- * cross-check, progress steps 1,3,5,8 (option "filter_invalid": 1,3,5,6[,7],8 and the hole filling); synchronous; host outputs may be NULL.  The two passes
+ * cross-check, progress steps 1,3,5,8 (option "filter_invalid": 1,3,5,6[,7],8 and the hole filling; option "speckle_min_size": a second 5, "Removing speckles...", and the speckle filter before it); synchronous; host outputs may be NULL.  The two passes
  * run side by side on the device (option "tv_overlap"); the progress steps are emitted as the
  * passes are QUEUED. */
 int  srh_twoview_compute(srh_context *ctx, int left_slot, int right_slot, const srh_params *p,
@@ -733,6 +741,45 @@ typedef struct srh_filter_info {
 } srh_filter_info;
 int  srh_view_filter_invalid(srh_context *ctx, int slot, const srh_params *p, int flags, int gap_width,
                              srh_filter_info *info);
+
+/* ---- speckle filter: small isolated regions of a depth map removed ----
+ * NOT IN THE REFERENCE (other stereo stacks have it: OpenCV's filterSpeckles).  A connected-component size filter, in place
+ * on `slot`'s depth map D (width w, height h) with the slot's mask M; it belongs between the cross-check and the hole
+ * filling, which otherwise copies a small island of wrong depth into the holes around it.
+ *   valid      a pixel with M == WHITE and isfinite(D) and D > 0.  The -1 of MultiViewStereo's "no peak" is therefore not
+ *              valid and stays -1; +INF, -INF, NaN and masked pixels are never written.
+ *   joined     two valid pixels that are 4-neighbours (left/right, up/down) are joined when fabs(Da - Db) <= max_diff,
+ *              evaluated in double.  The test is symmetric, so the components are a pure function of the map.
+ *   component  the transitive closure of the joins.  Its LABEL is the smallest linear pixel index y*w + x among its
+ *              members, its SIZE its member count.
+ *   removal    every pixel of a component with size < min_size is overwritten with the reject value: +INF (TwoViewStereo's
+ *              value for a rejected pixel, which the gap fill and the median then treat as a hole), or NaN with the flag
+ *              SRH_SPECKLE_TO_NAN (MultiViewStereo's cross-check value).  min_size <= 1 removes nothing.
+ *   max_diff   <= 0: 2.0 * ((p->max_depth - p->min_depth) / (double)(p->num_depth_levels - 1)), the "two depth steps"
+ *              srh_fuse_params.normal_depth_gap defaults to.
+ * The result is a pure function of the inputs: the same call gives the same bytes, and a second call with the same
+ * parameters removes nothing (removing a component neither joins nor splits the others).  labels_out (HOST, w*h int32, may
+ * be NULL) receives per pixel the component label as computed BEFORE the removal, -1 for a pixel that is not valid.
+ * s == NULL: the defaults; info may be NULL.  SRH_E_INVALID: an empty slot, min_size < 0, unknown flag bits, a max_diff
+ * that is not finite, num_depth_levels < 2 when the default max_diff is asked for.  The call runs on the context's stream
+ * and returns with the map updated; the cancel hook is polled between the launches (a cancelled call has not written D).
+ * It reads the image of the slot not at all and leaves mask, image and the WTA by-products untouched. */
+enum { SRH_SPECKLE_TO_NAN = 1 };
+typedef struct srh_speckle_params {
+	double  max_diff;           /* 0: two depth steps of p */
+	int32_t min_size;           /* 0: off (nothing is removed) */
+	int32_t flags;              /* 0, or SRH_SPECKLE_TO_NAN */
+} srh_speckle_params;
+void srh_speckle_params_defaults(srh_speckle_params *s);   /* 0, 0, 0; needs no device */
+typedef struct srh_speckle_info {
+	int64_t valid;               /* valid pixels on entry */
+	int64_t components;          /* components on entry */
+	int64_t removed_components;  /* components with size < min_size */
+	int64_t removed_pixels;      /* their pixels: what the call overwrote */
+	int64_t largest;             /* size of the largest component on entry (0: no valid pixel) */
+} srh_speckle_info;
+int  srh_view_filter_speckles(srh_context *ctx, int slot, const srh_params *p, const srh_speckle_params *s,
+                              srh_speckle_info *info, int32_t *labels_out);
 
 /* ---- epipolar curves ----
  * TwoViewStereo::epipolarCurve (public member, twoviewstereo.hpp:66-70, twoviewstereo.cpp:999-1054;

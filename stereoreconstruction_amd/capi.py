@@ -124,6 +124,20 @@ class FuseInfo(C.Structure):
                 ("n_unsupported", C.c_int64), ("n_normals", C.c_int64)]
 
 
+class SpeckleParams(C.Structure):
+    """srh_speckle_params"""
+    _fields_ = [("max_diff", C.c_double), ("min_size", C.c_int32), ("flags", C.c_int32)]
+
+
+class SpeckleInfo(C.Structure):
+    """srh_speckle_info"""
+    _fields_ = [("valid", C.c_int64), ("components", C.c_int64), ("removed_components", C.c_int64),
+                ("removed_pixels", C.c_int64), ("largest", C.c_int64)]
+
+
+# srh_view_filter_speckles flag: the reject value is NaN, not +INF
+SPECKLE_TO_NAN = 1
+
 # srh_mvs_fuse: bit 0 of a fused point's flags
 FUSE_HAS_NORMAL = 1
 
@@ -151,6 +165,7 @@ EXPORTS = [
     "srh_view_wta_outputs", "srh_view_wta_outputs_device", "srh_view_wta_outputs_state",
     "srh_twoview_wta", "srh_twoview_cross_check", "srh_twoview_compute", "srh_twoview_cost_rows", "srh_twoview_pair_costs", "srh_debug_exp",
     "srh_mvs_initial_estimate", "srh_mvs_cross_check", "srh_view_point_cloud", "srh_view_filter_invalid",
+    "srh_speckle_params_defaults", "srh_view_filter_speckles",
     "srh_fuse_params_defaults", "srh_mvs_fuse", "srh_mvs_fused_count", "srh_mvs_fused_download", "srh_mvs_fused_device",
     "srh_epipolar_curves",
     "srh_epipolar_preview", "srh_refraction_error",
@@ -275,6 +290,9 @@ def lib():
     L.srh_refraction_error.argtypes = [vp, C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]
     L.srh_view_point_cloud.argtypes = [vp, C.c_int, C.POINTER(Params), c_double_p, c_uint8_p, c_uint8_p, vp, vp, vp]
     L.srh_view_filter_invalid.argtypes = [vp, C.c_int, C.POINTER(Params), C.c_int, C.c_int, C.POINTER(FilterInfo)]
+    L.srh_speckle_params_defaults.argtypes = [C.POINTER(SpeckleParams)]
+    L.srh_speckle_params_defaults.restype = None
+    L.srh_view_filter_speckles.argtypes = [vp, C.c_int, C.POINTER(Params), C.POINTER(SpeckleParams), C.POINTER(SpeckleInfo), c_int32_p]
     L.srh_fuse_params_defaults.argtypes = [C.POINTER(FuseParams)]
     L.srh_fuse_params_defaults.restype = None
     L.srh_mvs_fuse.argtypes = [vp, c_int32_p, C.c_int, C.POINTER(Params), C.POINTER(FuseParams), C.POINTER(FuseInfo)]
@@ -768,6 +786,22 @@ class Context:
         info = FilterInfo()
         _check(lib().srh_view_filter_invalid(self._h, slot, C.byref(p), flags, gap_width, C.byref(info)))
         return {k: int(getattr(info, k)) for k, _ in FilterInfo._fields_}
+
+    def filter_speckles(self, slot, p, min_size, max_diff=0.0, flags=0, want_labels=False):
+        """The speckle filter on the slot's depth map, in place (srh_view_filter_speckles): the 4-connected components of
+        valid pixels whose depths differ by at most max_diff (<= 0: two depth steps of p), those smaller than min_size
+        overwritten with +INF (SPECKLE_TO_NAN: NaN) -> dict(valid, components, removed_components, removed_pixels, largest);
+        want_labels: (that dict, labels (h, w) int32: the components' labels before the removal, -1 = not valid)."""
+        s = SpeckleParams(float(max_diff), int(min_size), int(flags))
+        info = SpeckleInfo()
+        labels = None
+        if want_labels:
+            w, h = self.view_size(slot)
+            labels = np.empty((h, w), dtype=np.int32)
+        _check(lib().srh_view_filter_speckles(self._h, slot, C.byref(p), C.byref(s), C.byref(info),
+                                              labels.ctypes.data_as(c_int32_p) if want_labels else None))
+        out = {k: int(getattr(info, k)) for k, _ in SpeckleInfo._fields_}
+        return (out, labels) if want_labels else out
 
     def twoview_pair_costs(self, ref, oth, p, xy, kind=COST_SAD):
         """cost_sad (kind COST_SAD) or cost_ncc (COST_NCC) of arbitrary pairs: xy (n, 4) int rows (x1, y1, x2, y2), the

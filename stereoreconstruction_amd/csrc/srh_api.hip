@@ -5,6 +5,7 @@
 #include "srh_internal.hpp"
 #include "srh_geom.hpp"
 #include "srh_walk.hpp"
+#include "srh_speckle.hpp"
 
 #include <algorithm>
 #include <cassert>
@@ -386,6 +387,8 @@ struct srh_context {
 	int filter_invalid = 0;                             // option "filter_invalid": SRH_FILTER_* flags srh_twoview_compute ends with (0: none)
 	int filter_gap_width = 2;                           // option "filter_gap_width" (GAP_WIDTH_THRESHOLD)
 	int filter_replay = 0;                              // option "filter_replay": every median hole by the exact replay (test hook)
+	int speckle_min_size = 0;                           // option "speckle_min_size": srh_twoview_compute* remove components below it after the cross-check (0: off)
+	int speckle_diff_steps = 2;                         // option "speckle_diff_steps": that stage's max_diff in depth steps
 	int cost_kind = SRH_COST_NCC;                       // option "cost": the TwoView matching cost, SRH_COST_NCC or SRH_COST_SAD
 	int sad_dense = 0;                                  // option "sad_dense": cost_sad of row-aligned rigs on the dense plan (srh_sad_strip.hip)
 	int wta_outputs = 0;                                // option "wta_outputs": SRH_WTA_* planes a TwoView WTA pass keeps per reference pixel (never changes a depth map)
@@ -893,6 +896,14 @@ extern "C" int srh_set_option(srh_context *c, const char *name, long value) {
 	}
 	if (!strcmp(name, "filter_gap_width")) { c->filter_gap_width = (int)value; return SRH_OK; }
 	if (!strcmp(name, "filter_replay")) { c->filter_replay = value != 0; return SRH_OK; }
+	if (!strcmp(name, "speckle_min_size")) {
+		if (value < 0 || value > INT32_MAX) return fail(SRH_E_INVALID, "speckle_min_size must be in [0, 2^31)");
+		c->speckle_min_size = (int)value; return SRH_OK;
+	}
+	if (!strcmp(name, "speckle_diff_steps")) {
+		if (value < 1 || value > INT32_MAX) return fail(SRH_E_INVALID, "speckle_diff_steps must be >= 1");
+		c->speckle_diff_steps = (int)value; return SRH_OK;
+	}
 	if (!strcmp(name, "cost")) {
 		if (value != SRH_COST_NCC && value != SRH_COST_SAD) return fail(SRH_E_INVALID, "cost must be 0 (SRH_COST_NCC) or 1 (SRH_COST_SAD)");
 		c->cost_kind = (int)value; return SRH_OK;
@@ -2359,6 +2370,8 @@ static bool tv_pass_stands(const srh_context::TvDefer &d) {
 
 static int twoview_filter(srh_context *c, int left, int right, const srh_params *p);
 static int check_filter(srh_context *c, int slot, const srh_params *p, int flags);
+static int twoview_speckles(srh_context *c, int left, int right, const srh_params *p);
+static int check_twoview_speckles(srh_context *c, int left, int right, const srh_params *p);
 
 extern "C" int srh_twoview_compute(srh_context *c, int left, int right, const srh_params *p,
                                    double *left_out, double *right_out)
@@ -2367,6 +2380,9 @@ extern "C" int srh_twoview_compute(srh_context *c, int left, int right, const sr
 	if ((rc = check_slot(c, left, true)) || (rc = check_slot(c, right, true)) || (rc = check_params(p))) return rc;
 	// option "filter_invalid": what the hole filling refuses is refused before any launch, not after the two passes
 	if (c->filter_invalid && ((rc = check_filter(c, left, p, c->filter_invalid)) || (rc = check_filter(c, right, p, c->filter_invalid)))) return rc;
+	if (c->speckle_min_size && (rc = check_twoview_speckles(c, left, right, p))) return rc;
+	// the maps go to the host early only when nothing rewrites them after the cross-check
+	const bool tail = c->filter_invalid || c->speckle_min_size;
 	HIP_TRY(hipSetDevice(c->device));
 	for (auto &d : c->tv_defer) {
 		if (!d.host) HIP_TRY(hipHostMalloc((void **)&d.host, sizeof(Counters)));
@@ -2423,8 +2439,8 @@ extern "C" int srh_twoview_compute(srh_context *c, int left, int right, const sr
 		progress(c, 5, "Detecting inconsistencies...");
 		if ((rc = srh_twoview_cross_check(c, left, right, p))) return rc;
 		const ViewHost &L = c->views[left], &Rv = c->views[right];
-		if (left_out && !c->filter_invalid) HIP_TRY(hipMemcpyAsync(left_out, L.depth, (size_t)L.w*L.h*sizeof(double), hipMemcpyDeviceToHost, c->stream));
-		if (right_out && !c->filter_invalid) HIP_TRY(hipMemcpyAsync(right_out, Rv.depth, (size_t)Rv.w*Rv.h*sizeof(double), hipMemcpyDeviceToHost, c->stream));
+		if (left_out && !tail) HIP_TRY(hipMemcpyAsync(left_out, L.depth, (size_t)L.w*L.h*sizeof(double), hipMemcpyDeviceToHost, c->stream));
+		if (right_out && !tail) HIP_TRY(hipMemcpyAsync(right_out, Rv.depth, (size_t)Rv.w*Rv.h*sizeof(double), hipMemcpyDeviceToHost, c->stream));
 		HIP_TRY(hipStreamSynchronize(c->stream));
 		if (c->debug_trace)
 			for (srh_context::TvDefer *d : { &d0, &d1 })
@@ -2449,8 +2465,9 @@ extern "C" int srh_twoview_compute(srh_context *c, int left, int right, const sr
 			c->stats.n_flagged = (int64_t)d1.host->n_flagged;
 			c->stats.used_dense_path = d1.lists ? 0 : 1;
 			c->stats.used_fused_kernel = c->last_fused ? 1 : 0;
-			if (c->filter_invalid) {
-				if ((rc = twoview_filter(c, left, right, p))) return rc;
+			if (tail) {
+				if (c->speckle_min_size && (rc = twoview_speckles(c, left, right, p))) return rc;
+				if (c->filter_invalid && (rc = twoview_filter(c, left, right, p))) return rc;
 				if (left_out && (rc = srh_view_depth_download(c, left, left_out))) return rc;
 				if (right_out && (rc = srh_view_depth_download(c, right, right_out))) return rc;
 			}
@@ -2476,6 +2493,7 @@ extern "C" int srh_twoview_compute(srh_context *c, int left, int right, const sr
 	if ((rc = fetch_counters(c, c->main_lane(), c->stats.used_dense_path))) return rc;
 	progress(c, 5, "Detecting inconsistencies...");
 	if ((rc = srh_twoview_cross_check(c, left, right, p))) return rc;
+	if (c->speckle_min_size && (rc = twoview_speckles(c, left, right, p))) return rc;
 	if (c->filter_invalid && (rc = twoview_filter(c, left, right, p))) return rc;
 	if (left_out && (rc = srh_view_depth_download(c, left, left_out))) return rc;
 	if (right_out && (rc = srh_view_depth_download(c, right, right_out))) return rc;
@@ -3116,6 +3134,124 @@ static int twoview_filter(srh_context *c, int left, int right, const srh_params 
 	return filter_view(c, right, p, flags, c->filter_gap_width, nullptr, false);
 }
 
+// ------------------------------------------------------------------ speckle filter (srh_speckle.hip)
+extern "C" void srh_speckle_params_defaults(srh_speckle_params *s)
+{
+	if (!s) return;
+	s->max_diff = 0; s->min_size = 0; s->flags = 0;
+}
+
+// what needs no device: the slot, the parameters, and the max_diff the call runs with
+static int check_speckles(srh_context *c, int slot, const srh_params *p, const srh_speckle_params &s, double *max_diff)
+{
+	int rc;
+	if ((rc = check_slot(c, slot, true))) return rc;
+	if (!p) return fail(SRH_E_INVALID, "null params");
+	if (s.min_size < 0) return fail(SRH_E_INVALID, "speckle filter: min_size %d < 0", s.min_size);
+	if (s.flags & ~SRH_SPECKLE_TO_NAN) return fail(SRH_E_INVALID, "speckle filter: flags %d unknown", s.flags);
+	if (!std::isfinite(s.max_diff)) return fail(SRH_E_INVALID, "speckle filter: max_diff is not finite");
+	*max_diff = s.max_diff;
+	if (!(s.max_diff > 0)) {
+		if (p->num_depth_levels < 2) return fail(SRH_E_INVALID, "speckle filter: the default max_diff needs num_depth_levels >= 2, not %d", p->num_depth_levels);
+		*max_diff = cc::depth_steps(p->min_depth, p->max_depth, p->num_depth_levels, 2.0);
+		if (!std::isfinite(*max_diff)) return fail(SRH_E_INVALID, "speckle filter: min_depth %g, max_depth %g give no finite depth step", p->min_depth, p->max_depth);
+	}
+	if ((size_t)c->views[slot].w*c->views[slot].h >= ((size_t)1 << 31))
+		return fail(SRH_E_UNSUPPORTED, "speckle filter: view of %d x %d pixels", c->views[slot].w, c->views[slot].h);
+	return SRH_OK;
+}
+
+// One map.  Scratch in the band buffer (free between runs): the label planes A | B (n int32 each) | 5 counters.
+static int speckle_view(srh_context *c, int slot, double max_diff, int min_size, bool to_nan, srh_speckle_info *info, int32_t *labels_out)
+{
+	const ViewHost &v = c->views[slot];
+	const size_t n = (size_t)v.w*v.h;
+	int rc;
+	if ((rc = c->mem.band.wbuf.ensure(n + 5))) return rc;
+	int32_t *A = reinterpret_cast<int32_t *>((double *)c->mem.band.wbuf), *B = A + n;
+	unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(c->mem.band.wbuf + n);
+	HIP_TRY(hipMemsetAsync(d_cnt, 0, 5*sizeof(unsigned long long), c->stream));
+	{ Scope s(c, c->stream, "speckle_tile_kernel");
+	  launch_speckle_tiles(c->stream, v.mask, v.depth, v.w, v.h, max_diff, A); }
+	HIP_TRY(hipGetLastError());
+	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
+	{ Scope s(c, c->stream, "speckle_merge_kernel");
+	  launch_speckle_merge(c->stream, v.depth, v.w, v.h, max_diff, A); }
+	HIP_TRY(hipGetLastError());
+	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
+	{ Scope s(c, c->stream, "speckle_flatten_kernel");
+	  launch_speckle_flatten(c->stream, A, n, B); }
+	HIP_TRY(hipGetLastError());
+	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
+	HIP_TRY(hipMemsetAsync(A, 0, n*sizeof(int32_t), c->stream));       // A: the sizes, at the components' labels
+	{ Scope s(c, c->stream, "speckle_count_kernel");
+	  launch_speckle_count(c->stream, B, n, A); }
+	HIP_TRY(hipGetLastError());
+	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
+	{ Scope s(c, c->stream, "speckle_apply_kernel");
+	  launch_speckle_apply(c->stream, B, A, n, min_size, to_nan ? (double)NAN : (double)INFINITY, v.depth, d_cnt); }
+	HIP_TRY(hipGetLastError());
+	unsigned long long hc[5] = { 0, 0, 0, 0, 0 };
+	if (info) HIP_TRY(hipMemcpyAsync(hc, d_cnt, sizeof(hc), hipMemcpyDeviceToHost, c->stream));
+	if (labels_out) HIP_TRY(hipMemcpyAsync(labels_out, B, n*sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	if (info) {
+		info->valid = (int64_t)hc[0];
+		info->components = (int64_t)hc[1];
+		info->removed_components = (int64_t)hc[2];
+		info->removed_pixels = (int64_t)hc[3];
+		info->largest = (int64_t)hc[4];
+	}
+	return SRH_OK;
+}
+
+extern "C" int srh_view_filter_speckles(srh_context *c, int slot, const srh_params *p, const srh_speckle_params *s,
+                                        srh_speckle_info *info, int32_t *labels_out)
+{
+	int rc;
+	srh_speckle_params sp;
+	srh_speckle_params_defaults(&sp);
+	if (s) sp = *s;
+	double max_diff = 0;
+	if ((rc = check_speckles(c, slot, p, sp, &max_diff))) return rc;
+	HIP_TRY(hipSetDevice(c->device));
+	if (info) *info = srh_speckle_info();
+	return speckle_view(c, slot, max_diff, sp.min_size, (sp.flags & SRH_SPECKLE_TO_NAN) != 0, info, labels_out);
+}
+
+// srh_twoview_compute*'s stage under option "speckle_min_size": both maps, reject value +INF, behind the cross-check and
+// before the hole filling; its own stage text at the cross-check's progress step
+static int twoview_speckle_params(srh_context *c, const srh_params *p, srh_speckle_params *s)
+{
+	s->min_size = c->speckle_min_size; s->flags = 0;
+	s->max_diff = cc::depth_steps(p->min_depth, p->max_depth, p->num_depth_levels, (double)c->speckle_diff_steps);
+	if (!(s->max_diff > 0)) return fail(SRH_E_INVALID, "speckle_diff_steps %d of depth range [%g, %g] give no positive max_diff", c->speckle_diff_steps, p->min_depth, p->max_depth);
+	return SRH_OK;
+}
+
+static int check_twoview_speckles(srh_context *c, int left, int right, const srh_params *p)
+{
+	int rc;
+	srh_speckle_params s;
+	double max_diff;
+	if ((rc = check_params(p)) || (rc = twoview_speckle_params(c, p, &s))) return rc;
+	if ((rc = check_speckles(c, left, p, s, &max_diff)) || (rc = check_speckles(c, right, p, s, &max_diff))) return rc;
+	return SRH_OK;
+}
+
+static int twoview_speckles(srh_context *c, int left, int right, const srh_params *p)
+{
+	int rc;
+	srh_speckle_params s;
+	double max_diff = 0;
+	if ((rc = twoview_speckle_params(c, p, &s))) return rc;
+	if ((rc = check_speckles(c, left, p, s, &max_diff)) || (rc = check_speckles(c, right, p, s, &max_diff))) return rc;
+	progress(c, 5, "Removing speckles...");
+	if ((rc = speckle_view(c, left, max_diff, s.min_size, false, nullptr, nullptr))) return rc;
+	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
+	return speckle_view(c, right, max_diff, s.min_size, false, nullptr, nullptr);
+}
+
 // ------------------------------------------------------------------ epipolar curves on request
 extern "C" int srh_epipolar_curves(srh_context *c, int ref, int oth, const srh_params *p, int mvs,
                                    int nq, const int32_t *xy, int32_t *out_xy, int max_pts, int32_t *counts)
@@ -3543,6 +3679,7 @@ static int tv_stage_compute(srh_context *c, const TvStage &T, int left, int righ
 	const ViewHost &L = c->views[left], &Rv = c->views[right];
 	if (L.w != Rv.w || L.h != Rv.h) return fail(SRH_E_INVALID, "TwoViewStereo needs equal-sized views");
 	if (c->filter_invalid && ((rc = check_filter(c, left, p, c->filter_invalid)) || (rc = check_filter(c, right, p, c->filter_invalid)))) return rc;
+	if (c->speckle_min_size && (rc = check_twoview_speckles(c, left, right, p))) return rc;
 	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
 	for (int k = 0; k < 2; ++k) {
 		const int ref = k == 0 ? left : right, oth = k == 0 ? right : left;
@@ -3557,6 +3694,7 @@ static int tv_stage_compute(srh_context *c, const TvStage &T, int left, int righ
 	}
 	progress(c, 5, "Detecting inconsistencies...");
 	if ((rc = srh_twoview_cross_check(c, left, right, p))) return rc;
+	if (c->speckle_min_size && (rc = twoview_speckles(c, left, right, p))) return rc;
 	if (c->filter_invalid && (rc = twoview_filter(c, left, right, p))) return rc;
 	if (left_out && (rc = srh_view_depth_download(c, left, left_out))) return rc;
 	if (right_out && (rc = srh_view_depth_download(c, right, right_out))) return rc;

@@ -273,6 +273,13 @@ void launch_filter_holes(hipStream_t st, const uint8_t *mask, double *D, int w, 
                          unsigned long long *cnt);
 void launch_filter_median(hipStream_t st, const ViewDev *views, int slot, const srh_params &P, const double *G,
                           const uint32_t *holes, int nholes, double *D, unsigned long long *cnt);
+// speckle filter (srh_speckle.hip); A, B: int32 planes of w*h; cnt: 5 counters, see srh_speckle_info
+void launch_speckle_tiles(hipStream_t st, const uint8_t *mask, const double *D, int w, int h, double max_diff, int32_t *A);
+void launch_speckle_merge(hipStream_t st, const double *D, int w, int h, double max_diff, int32_t *A);
+void launch_speckle_flatten(hipStream_t st, const int32_t *A, size_t n, int32_t *B);
+void launch_speckle_count(hipStream_t st, const int32_t *B, size_t n, int32_t *size);
+void launch_speckle_apply(hipStream_t st, const int32_t *B, const int32_t *size, size_t n, int min_size, double reject, double *D,
+                          unsigned long long *cnt);
 // weighted SAD, TwoViewStereo::cost_sad (srh_sad.hip)
 // full (w*h bytes): 1 where the whole (2R+1)^2 window of cost_sad's OTHER-view side is usable (inside the image, mask WHITE)
 void launch_sad_full_window(hipStream_t st, const uint8_t *mask, int w, int h, int R, uint8_t *full);

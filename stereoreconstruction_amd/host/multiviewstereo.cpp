@@ -210,10 +210,23 @@ void MultiViewStereo::runTask() {
 	emitStage("Cross-checking");                       // :427-431, views in order
 	std::vector<int32_t> slots(nv);
 	for (int v = 0; v < nv; ++v) slots[v] = v;
+	bool checked = true;
 	for (int v = 0; v < nv; ++v) {
 		emitProgress(current_step++);
-		if (srh_mvs_cross_check(ctx_, slots.data(), nv, v, &params_) != SRH_OK) { error_ = srh_last_error(); break; }
+		if (srh_mvs_cross_check(ctx_, slots.data(), nv, v, &params_) != SRH_OK) { error_ = srh_last_error(); checked = false; break; }
 		if (isCancelled()) break;
+	}
+	if (speckleMinSize_ > 0 && checked && !isCancelled()) {
+		// the speckle filter (not in the reference), every view in order, before anything reads the maps; the cross-check's
+		// reject value (no step of its own: the step count is the reference's)
+		srh_speckle_params s;
+		srh_speckle_params_defaults(&s);
+		s.min_size = speckleMinSize_; s.max_diff = speckleMaxDiff_; s.flags = SRH_SPECKLE_TO_NAN;
+		for (int v = 0; v < nv; ++v) {
+			const int rc = srh_view_filter_speckles(ctx_, v, &params_, &s, nullptr, nullptr);
+			if (rc != SRH_OK && rc != SRH_E_CANCELLED) error_ = srh_last_error();
+			if (rc != SRH_OK || isCancelled()) break;
+		}
 	}
 	emitStage("Constructing depth maps");
 	for (int v = 0; v < nv; ++v) {

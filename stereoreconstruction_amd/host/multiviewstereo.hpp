@@ -101,6 +101,12 @@ public:
 	bool useSGM() const { return useSgm_; }
 	srh_mvs_sgm_params &sgmParams() { return sgmParams_; }
 	srh_sgm_info sgmInfo(CameraPtr view) const;
+	// Speckle filter after the cross-check (NOT IN THE REFERENCE; srh_view_filter_speckles with SRH_SPECKLE_TO_NAN): in
+	// every view's map the 4-connected components of valid pixels whose depths differ by at most maxDiff (<= 0: two depth
+	// steps), those smaller than minSize set to NaN -- before depthMap, pointCloud and fusedPointCloud read the maps.
+	// 0 (default): off.  The step count is unchanged.
+	void setSpeckleFilter(int minSize, double maxDiff = 0) { speckleMinSize_ = minSize; speckleMaxDiff_ = maxDiff; }
+	int speckleFilter() const { return speckleMinSize_; }
 	const std::string &lastError() const { return error_; }
 
 protected:
@@ -125,6 +131,8 @@ private:
 	std::vector<srh_sgm_info> sgmInfos_;
 	srh_fuse_params fuseParams_;
 	bool useMrf_ = false, useSgm_ = false;
+	int speckleMinSize_ = 0;
+	double speckleMaxDiff_ = 0;
 	srh_context *ctx_;
 	std::string error_;
 };

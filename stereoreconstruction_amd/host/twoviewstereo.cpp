@@ -240,6 +240,27 @@ void TwoViewStereo::filterInvalidPixels() {
 	if (rc != SRH_OK && rc != SRH_E_CANCELLED) error_ = srh_last_error();
 }
 
+void TwoViewStereo::filterSpeckles() {
+	if (!ctx_ || speckleMinSize <= 0) return;
+	if (speckleDiffSteps < 1) { error_ = "speckle filter: diffSteps must be >= 1"; return; }
+	srh_speckle_params s;
+	srh_speckle_params_defaults(&s);
+	s.min_size = speckleMinSize;
+	s.max_diff = static_cast<double>(speckleDiffSteps) * ((params_.max_depth - params_.min_depth)/static_cast<double>(params_.num_depth_levels - 1));
+	TwoViewHooks hooks = { this, &progressUpdate, &stageUpdate };
+	srh_set_hooks(ctx_, cancelFlag(), onProgress, &hooks);
+	emitProgress(5);
+	emitStage("Removing speckles...");
+	int rc = srh_view_depth_upload(ctx_, 0, computedDepthLeft.data());
+	if (rc == SRH_OK) rc = srh_view_depth_upload(ctx_, 1, computedDepthRight.data());
+	if (rc == SRH_OK) rc = srh_view_filter_speckles(ctx_, 0, &params_, &s, nullptr, nullptr);
+	if (rc == SRH_OK && !isCancelled()) rc = srh_view_filter_speckles(ctx_, 1, &params_, &s, nullptr, nullptr);
+	if (rc == SRH_OK) rc = srh_view_depth_download(ctx_, 0, computedDepthLeft.data());
+	if (rc == SRH_OK) rc = srh_view_depth_download(ctx_, 1, computedDepthRight.data());
+	srh_set_hooks(ctx_, nullptr, nullptr, nullptr);
+	if (rc != SRH_OK && rc != SRH_E_CANCELLED) error_ = srh_last_error();
+}
+
 double TwoViewStereo::depthFromLabel(int label) const {
 	double t = static_cast<double>(label) / (numDepthLevels - 1);
 	t /= (5.0 - 4.0*t);
@@ -255,7 +276,9 @@ void TwoViewStereo::computeDepthMaps() {
 	srh_set_hooks(ctx_, cancelFlag(), onProgress, &hooks);
 	srh_set_option(ctx_, "filter_invalid", filterFlags);
 	srh_set_option(ctx_, "sad_dense", sadDenseOn);
-	if (srh_set_option(ctx_, "cost", costKind) != SRH_OK || srh_set_option(ctx_, "wta_outputs", wtaFlags) != SRH_OK) {
+	if (srh_set_option(ctx_, "speckle_min_size", speckleMinSize) != SRH_OK ||
+	    (speckleMinSize && srh_set_option(ctx_, "speckle_diff_steps", speckleDiffSteps) != SRH_OK) ||
+	    srh_set_option(ctx_, "cost", costKind) != SRH_OK || srh_set_option(ctx_, "wta_outputs", wtaFlags) != SRH_OK) {
 		error_ = srh_last_error();
 		srh_set_hooks(ctx_, nullptr, nullptr, nullptr);
 		return;

@@ -46,6 +46,12 @@ public:
 	void setFilterInvalid(int flags) { filterFlags = flags; }
 	int filterInvalid() const { return filterFlags; }
 
+	// Speckle filter between the cross-check and the hole filling (NOT IN THE REFERENCE; srh_view_filter_speckles): the
+	// 4-connected components of valid pixels whose depths differ by at most diffSteps depth steps, those smaller than
+	// minSize set to +INF in both maps (options "speckle_min_size" / "speckle_diff_steps").  0 (default): off.
+	void setSpeckleFilter(int minSize, int diffSteps = 2) { speckleMinSize = minSize; speckleDiffSteps = diffSteps; }
+	int speckleFilter() const { return speckleMinSize; }
+
 	// Matching cost of the WTA: SRH_COST_NCC (0, default: cost_ncc, as the reference's computeCostVolumes) or SRH_COST_SAD
 	// (1: cost_sad, twoviewstereo.cpp:864-905).  The WTA, ratio test, cross-check and hole filling are the same for both.
 	void setCostFunction(int kind) { costKind = kind; }
@@ -127,6 +133,9 @@ protected:
 	// (weightedMedian is per pixel and stateful on the reference's weightFuncs: the device does it inside
 	// filterInvalidPixels.)
 	void filterInvalidPixels();
+	// ... and, for a subclass that wants it between the two, the speckle filter of setSpeckleFilter on both maps (nothing
+	// when that is off): uploads both maps, filters, downloads both, as filterInvalidPixels does
+	void filterSpeckles();
 	// the two matching costs (twoviewstereo.hpp:92-99) of reference pixel (x1,y1) against (x2,y2) of the other view.  The
 	// reference passes the two images and masks and reads the window of weightFuncs, which init_weights has set for
 	// (x1,y1) beforehand; as with epipolarCurve, all of that follows from the pixels and the direction: fromLeft = the
@@ -153,6 +162,7 @@ private:
 	DepthMap computedDepthLeft, computedDepthRight;
 	srh_params params_;
 	int filterFlags = 0;
+	int speckleMinSize = 0, speckleDiffSteps = 2;
 	int costKind = SRH_COST_NCC;
 	int sadDenseOn = 0;
 	int wtaFlags = 0;

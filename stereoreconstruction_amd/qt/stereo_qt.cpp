@@ -229,9 +229,17 @@ void TwoViewStereo::computeDepthMaps() {
 		cancelWord_ = isCancelled() ? 1 : 0;
 		srh_set_hooks(ctx_, &cancelWord_, relayToTwoView, this);
 		srh_set_option(ctx_, "filter_invalid", filterFlags);
+		if (srh_set_option(ctx_, "speckle_min_size", speckleMinSize) != SRH_OK ||
+		    (speckleMinSize && srh_set_option(ctx_, "speckle_diff_steps", speckleDiffSteps) != SRH_OK)) {
+			error_ = srh_last_error();
+			srh_set_option(ctx_, "filter_invalid", 0);
+			srh_set_hooks(ctx_, nullptr, nullptr, nullptr);
+			return;
+		}
 		const int rc = useSgm ? srh_twoview_compute_sgm(ctx_, 0, 1, &params_, &sgmParams_, computedDepthLeft.data(), computedDepthRight.data(), sgmInfo_)
 		                      : srh_twoview_compute_mrf(ctx_, 0, 1, &params_, &mrfParams_, computedDepthLeft.data(), computedDepthRight.data(), mrfInfo_);
 		srh_set_option(ctx_, "filter_invalid", 0);
+		srh_set_option(ctx_, "speckle_min_size", 0);
 		srh_set_hooks(ctx_, nullptr, nullptr, nullptr);
 		if (rc == SRH_E_CANCELLED) return;
 		if (rc != SRH_OK) { error_ = srh_last_error(); return; }
@@ -256,6 +264,10 @@ void TwoViewStereo::computeDepthMaps() {
 	if (isCancelled()) return;
 	fetchWtaOutputs();
 	if (!error_.isEmpty()) return;
+	if (speckleMinSize > 0) {
+		filterSpeckles();
+		if (isCancelled() || !error_.isEmpty()) return;
+	}
 	if (filterFlags) {
 		filterInvalidPixels();
 		if (isCancelled() || !error_.isEmpty()) return;
@@ -297,6 +309,23 @@ void TwoViewStereo::filterInvalidPixels() {
 	// (the reference's right-map loop tests left.width() (:748): the views are equal-sized, each map is filled over its own)
 	if (srh_view_filter_invalid(ctx_, 0, &params_, flags, 2, nullptr) != SRH_OK ||
 	    srh_view_filter_invalid(ctx_, 1, &params_, flags, 2, nullptr) != SRH_OK ||
+	    srh_view_depth_download(ctx_, 0, computedDepthLeft.data()) != SRH_OK ||
+	    srh_view_depth_download(ctx_, 1, computedDepthRight.data()) != SRH_OK) error_ = srh_last_error();
+}
+
+void TwoViewStereo::filterSpeckles() {
+	if (!ctx_ || speckleMinSize <= 0 || !uploadViews()) return;
+	if (speckleDiffSteps < 1) { error_ = "speckle filter: diffSteps must be >= 1"; return; }
+	srh_speckle_params s;
+	srh_speckle_params_defaults(&s);
+	s.min_size = speckleMinSize;
+	s.max_diff = static_cast<double>(speckleDiffSteps) * ((params_.max_depth - params_.min_depth)/static_cast<double>(params_.num_depth_levels - 1));
+	emit progressUpdate(5);
+	emit stageUpdate("Removing speckles...");
+	if (srh_view_depth_upload(ctx_, 0, computedDepthLeft.data()) != SRH_OK ||
+	    srh_view_depth_upload(ctx_, 1, computedDepthRight.data()) != SRH_OK ||
+	    srh_view_filter_speckles(ctx_, 0, &params_, &s, nullptr, nullptr) != SRH_OK ||
+	    srh_view_filter_speckles(ctx_, 1, &params_, &s, nullptr, nullptr) != SRH_OK ||
 	    srh_view_depth_download(ctx_, 0, computedDepthLeft.data()) != SRH_OK ||
 	    srh_view_depth_download(ctx_, 1, computedDepthRight.data()) != SRH_OK) error_ = srh_last_error();
 }
@@ -418,6 +447,15 @@ void MultiViewStereo::runTask() {
 		if (isCancelled()) return;
 		emit progressUpdate(step++);
 		if (srh_mvs_cross_check(ctx_, slotIds.data(), V, v, &params_) != SRH_OK) { error_ = srh_last_error(); return; }
+	}
+	if (speckleMinSize_ > 0) {                           // the speckle filter (not in the reference): NaN, as the cross-check rejects
+		srh_speckle_params s;
+		srh_speckle_params_defaults(&s);
+		s.min_size = speckleMinSize_; s.max_diff = speckleMaxDiff_; s.flags = SRH_SPECKLE_TO_NAN;
+		for (int v = 0; v < V; ++v) {
+			if (isCancelled()) return;
+			if (srh_view_filter_speckles(ctx_, v, &params_, &s, nullptr, nullptr) != SRH_OK) { error_ = srh_last_error(); return; }
+		}
 	}
 	for (int v = 0; v < V; ++v)
 		if (srh_view_depth_download(ctx_, v, computedDepths[v].data()) != SRH_OK) { error_ = srh_last_error(); return; }

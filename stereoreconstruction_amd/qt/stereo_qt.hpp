@@ -124,6 +124,9 @@ public:
 	QString lastError() const { return error_; }
 	// hole filling after the cross-check (SRH_FILTER_* flags); 0 (default) = the reference, call site under #if 0
 	void setFilterInvalid(int flags) { filterFlags = flags; }
+	// speckle filter between the cross-check and the hole filling (not in the reference; srh_view_filter_speckles): components
+	// of fewer than minSize pixels whose depths chain within diffSteps depth steps become +INF; 0 (default) = off
+	void setSpeckleFilter(int minSize, int diffSteps = 2) { speckleMinSize = minSize; speckleDiffSteps = diffSteps; }
 	// matching cost of the WTA: SRH_COST_NCC (0, default: cost_ncc, the reference's) or SRH_COST_SAD (1: cost_sad)
 	void setCostFunction(int kind) { costKind = kind; }
 	int costFunction() const { return costKind; }
@@ -170,6 +173,8 @@ protected:
 	// stereo/twoviewstereo.hpp, protected: the compiled body (row gap fill of both maps, progress 6), or what
 	// setFilterInvalid asks for (the median: progress 7 and the #if 0 half, twoviewstereo.cpp:769-810)
 	void filterInvalidPixels();
+	// the speckle filter of setSpeckleFilter on both maps (nothing when it is off), progress 5 "Removing speckles..."
+	void filterSpeckles();
 	// stereo/twoviewstereo.hpp:92-99, protected: cost_sad / cost_ncc of reference pixel (x1,y1) against (x2,y2) of the
 	// other view.  The reference passes both images and masks and reads weightFuncs, set by init_weights for (x1,y1); as
 	// with curveOfPixel all of it follows from the pixels and the direction (fromLeft: the left view is the reference).
@@ -192,6 +197,7 @@ private:
 	DepthMap computedDepthLeft, computedDepthRight;
 	srh_params params_;
 	int filterFlags = 0;
+	int speckleMinSize = 0, speckleDiffSteps = 2;
 	int costKind = SRH_COST_NCC;
 	int sadDenseOn = 0;
 	int wtaFlags = 0;
@@ -256,6 +262,9 @@ public:
 	// the depth maps of the last run's views, in their order, fused into one oriented cloud (srh_mvs_fuse with fuseParams())
 	std::vector<FusedPoint> fusedPointCloud();
 	srh_fuse_params &fuseParams() { return fuseParams_; }
+	// speckle filter after the cross-check (not in the reference; srh_view_filter_speckles, SRH_SPECKLE_TO_NAN): components of
+	// fewer than minSize pixels whose depths chain within maxDiff (<= 0: two depth steps) become NaN; 0 (default) = off
+	void setSpeckleFilter(int minSize, double maxDiff = 0) { speckleMinSize_ = minSize; speckleMaxDiff_ = maxDiff; }
 	QString lastError() const { return error_; }
 
 protected:
@@ -278,6 +287,8 @@ private:
 	std::vector<srh_sgm_info> sgmInfos_;
 	srh_fuse_params fuseParams_;
 	bool useMrf_ = false, useSgm_ = false;
+	int speckleMinSize_ = 0;
+	double speckleMaxDiff_ = 0;
 	srh_context *ctx_;
 	QString error_;
 };
