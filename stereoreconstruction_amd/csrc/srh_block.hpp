@@ -8,6 +8,7 @@
 //   block_two_sweeps   the reference's two sweeps (stereo/twoviewstereo.cpp:917-976: products first, sums second) over
 //                      window rows [ra, rb), or the same with fused multiply-adds (FMA): sum1 and sum3 of each candidate
 //   block_onepass      the certified one-pass form's sums P = sum w r, Q = sum ((w l - meanL) w) r, U = sum w^2 r^2
+//   block_onepass_taps the same sums, the tap products (w l - meanL) w read from the source instead of built per block
 //   two_sweep_finish   255*(1 - |sum1|/sqrt(sum2*sum3))
 //   onepass_finish     the one-pass cost from P, Q, U without an IEEE division or square root, and its certificate
 //   block_stored       what a cost kernel stores for a fast-form candidate: the clamped value (exact forms) or NaN, the
@@ -21,6 +22,8 @@
 //                                              read at an even index, two 8-byte reads, or a global pointer)
 //       void w2(int m, double &a, double &b)   weights 2m, 2m + 1 of the row;   double w(int col)   one weight
 //       double l(int col)                      the reference view's tap
+//       void c2(int m, double &a, double &b), double c(int col)   (sources of block_onepass_taps only, which need no l)
+//                                              the tap products fma(w, l, -meanL)*w, addressed like the weights
 //   int row_begin(int units), void row_end(int seen)   what runs at the start and the end of a window row (the strip
 //                                    kernel publishes its progress and yields to its SIMD partner; nothing elsewhere)
 // The schedule: the pre-header fills r[] and wv[] with the first row; a value's register is refilled with the NEXT row's
@@ -217,6 +220,64 @@ SRH_NHD void block_onepass(const Src src, double mL, double (&Pout)[NCB], double
 #pragma unroll
 		for (int m = (WS - 1)/2; m < NR/2; ++m) next.r2(m, r[2*m], r[2*m + 1]);
 		wv[WS - 1] = next.w(WS - 1);
+		src.row_end(seen);
+	}
+#pragma unroll
+	for (int j = 0; j < NCB; ++j) { Pout[j] = P[j]; Qout[j] = Q[j]; Uout[j] = U[j]; }
+}
+
+// The same sums from a source that SUPPLIES the tap products c_t = fma(w_t, l_t, -meanL)*w_t -- block_onepass's two
+// operations, in its order, done once per pixel instead of in every block of it (the strip kernel's 8-wave form keeps them
+// in LDS per tile): the same bits.  cv[] lives in the registers lv[] held and is refilled a row ahead with the weights; per
+// tap only d = w^2 is left.  A function of its own: block_onepass's text, and its callers' code, stay what they are.
+template <int WS, int NCB, class Src>
+SRH_NHD void block_onepass_taps(const Src src, double (&Pout)[NCB], double (&Qout)[NCB], double (&Uout)[NCB])
+{
+	double P[NCB], Q[NCB], U[NCB];
+	constexpr int NR = NCB + WS - 1;
+	static_assert(WS % 2 == 1 && NR % 2 == 0, "odd window, the other view's segment in pairs");
+	double r[NR], q[NR], wv[WS], cv[WS];
+	{
+		const auto first = src.row(0);
+#pragma unroll
+		for (int m = 0; m < NR/2; ++m) first.r2(m, r[2*m], r[2*m + 1]);
+#pragma unroll
+		for (int m = 0; m < (WS - 1)/2; ++m) { first.w2(m, wv[2*m], wv[2*m + 1]); first.c2(m, cv[2*m], cv[2*m + 1]); }
+		wv[WS - 1] = first.w(WS - 1);
+		cv[WS - 1] = first.c(WS - 1);
+	}
+#pragma unroll
+	for (int j = 0; j < NCB; ++j) { P[j] = 0.0; Q[j] = 0.0; U[j] = 0.0; }
+	if (Src::LDS_WAIT) SRH_LDS_WAIT();
+#pragma unroll 1
+	for (int row = 0; row < WS; ++row) {
+		const int seen = src.row_begin(4);
+		const auto next = src.row(row + 1 < WS ? row + 1 : 0);            // (the last refill is never used)
+#pragma unroll
+		for (int k = 0; k < NCB - 1; ++k) q[k] = r[k]*r[k];
+#pragma unroll
+		for (int col = 0; col < WS; ++col) {
+			q[col + NCB - 1] = r[col + NCB - 1]*r[col + NCB - 1];
+			const double d = wv[col]*wv[col];
+			SRH_SCHED_BARRIER();
+#pragma unroll
+			for (int j = 0; j < NCB; ++j) P[j] = __builtin_fma(wv[col], r[col + j], P[j]);
+#pragma unroll
+			for (int j = 0; j < NCB; ++j) Q[j] = __builtin_fma(cv[col], r[col + j], Q[j]);
+#pragma unroll
+			for (int j = 0; j < NCB; ++j) U[j] = __builtin_fma(d, q[col + j], U[j]);
+			SRH_SCHED_BARRIER();
+			if (col & 1) {
+				next.r2(col >> 1, r[col - 1], r[col]);
+				next.w2(col >> 1, wv[col - 1], wv[col]);
+				next.c2(col >> 1, cv[col - 1], cv[col]);
+			}
+			SRH_SCHED_BARRIER();
+		}
+#pragma unroll
+		for (int m = (WS - 1)/2; m < NR/2; ++m) next.r2(m, r[2*m], r[2*m + 1]);
+		wv[WS - 1] = next.w(WS - 1);
+		cv[WS - 1] = next.c(WS - 1);
 		src.row_end(seen);
 	}
 #pragma unroll

@@ -42,6 +42,11 @@ void strip_exp_set(int repeat) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_strip_exp_
 typedef __attribute__((address_space(3))) void st_lds_void;
 typedef __attribute__((address_space(1))) const void st_gbl_void;
 typedef __attribute__((address_space(3))) volatile int st_lds_vint;
+typedef __attribute__((address_space(3))) const volatile double st_lds_vdouble;
+
+// One 8-byte LDS read that stays one: ds_read_b64.  Two adjacent plain reads the compiler pairs into ds_read2_b64, which
+// the LDS serves at half the rate (profiles/microbench/lone_wave_issue_mi355x.txt: 32 cycles against 10-14 each).
+__device__ __forceinline__ double st_lds_read8(const double *p) { return *(st_lds_vdouble *)p; }
 
 // ------------------------------------------------------------------ padded planes
 __global__ void padded_plane_kernel(const double *__restrict__ gray_tv, int W, int H, double *__restrict__ out)
@@ -174,11 +179,13 @@ struct StripSmem {
 	static constexpr int GL_CAP = 3072;
 	static constexpr int GL_SINGLES = GL_CAP - ST_TP*NBMAX;
 	alignas(16) double w[NBUF][WS][ST_TP][WP];         // LDS image of the windows: [row][pixel][tap], as in the band buffer
+	// 8-wave form: the rows are read 8 bytes at a time (st_lds_read8), so blocks start at the pixel's first column, odd or
+	// even (no alignment pad), and a range of 8*16*k columns needs exactly k rounds -- on C3 no column is left to the fill
+	// kernel.  (A second copy of the rows shifted by one column used to serve the odd starts with 16-byte reads: 32 KB.)
 	alignas(16) double rt[NS][RW];
-	// 8-wave form: the same rows once more, shifted by one column (rto[s][k] = rt[s][k + 1]): a block that starts on
-	// an odd column still reads 16 aligned bytes at a time, so blocks start at the pixel's first column (no alignment
-	// pad) and a range of 8*16*k columns needs exactly k rounds -- on C3 no column is left to the fill kernel
-	alignas(16) double rto[NBUF == 2 ? NS : 1][RW];
+	// 8-wave form, one-pass arithmetic: the current tile's tap products c_t = fma(w_t, l_t, -meanL)*w_t, laid out like a window
+	// buffer and built once per tile (behind barrier A) -- a pixel's 32 blocks used to rebuild all 121 of them each
+	alignas(16) double c[NBUF == 2 ? WS : 1][NBUF == 2 ? ST_TP : 1][WP];
 	alignas(16) double lt[NS][LW];
 	alignas(16) double pc[2][ST_TP][SRH_PC];         // meanL, totalWeight, sum2, 0 | 1/totalWeight, SA, pad (srh_internal.hpp)
 	alignas(16) PixRange pr[2][ST_TP];
@@ -253,9 +260,14 @@ __device__ __noinline__ void strip_select_block(const StripSmem<R, NBUF> &S, int
 	for (int row = ra; row < rb; ++row) {
 		const int sl = s0 + row >= NS ? s0 + row - NS : s0 + row;
 		double rr[NR], rv[NR];
-		const double2 *rp = reinterpret_cast<const double2 *>((NBUF == 2 && (rc & 1)) ? &S.rto[sl][rc - 1] : &S.rt[sl][rc]);
+		if (NBUF == 2) {                                                  // any parity of rc: 8 bytes at a time
 #pragma unroll
-		for (int m = 0; m < NR/2; ++m) { const double2 v = rp[m]; rr[2*m] = v.x; rr[2*m + 1] = v.y; }
+			for (int m = 0; m < NR; ++m) rr[m] = st_lds_read8(&S.rt[sl][rc + m]);
+		} else {
+			const double2 *rp = reinterpret_cast<const double2 *>(&S.rt[sl][rc]);
+#pragma unroll
+			for (int m = 0; m < NR/2; ++m) { const double2 v = rp[m]; rr[2*m] = v.x; rr[2*m + 1] = v.y; }
+		}
 #pragma unroll
 		for (int m = 0; m < NR; ++m) { const bool okr = rr[m] == rr[m]; rv[m] = okr ? 1.0 : 0.0; rr[m] = okr ? rr[m] : 0.0; }
 #pragma unroll
@@ -280,9 +292,14 @@ __device__ __noinline__ void strip_select_block(const StripSmem<R, NBUF> &S, int
 	for (int row = ra; row < rb; ++row) {
 		const int sl = s0 + row >= NS ? s0 + row - NS : s0 + row;
 		double rr[NR], rv[NR];
-		const double2 *rp = reinterpret_cast<const double2 *>((NBUF == 2 && (rc & 1)) ? &S.rto[sl][rc - 1] : &S.rt[sl][rc]);
+		if (NBUF == 2) {                                                  // any parity of rc: 8 bytes at a time
 #pragma unroll
-		for (int m = 0; m < NR/2; ++m) { const double2 v = rp[m]; rr[2*m] = v.x; rr[2*m + 1] = v.y; }
+			for (int m = 0; m < NR; ++m) rr[m] = st_lds_read8(&S.rt[sl][rc + m]);
+		} else {
+			const double2 *rp = reinterpret_cast<const double2 *>(&S.rt[sl][rc]);
+#pragma unroll
+			for (int m = 0; m < NR/2; ++m) { const double2 v = rp[m]; rr[2*m] = v.x; rr[2*m + 1] = v.y; }
+		}
 #pragma unroll
 		for (int m = 0; m < NR; ++m) { const bool okr = rr[m] == rr[m]; rv[m] = okr ? 1.0 : 0.0; rr[m] = okr ? rr[m] : 0.0; }
 #pragma unroll
@@ -329,8 +346,8 @@ __device__ __noinline__ void strip_select_block(const StripSmem<R, NBUF> &S, int
 // the LDS copies of pconst and `full`; the band buffers are not touched (pconst slot 3 stays 0 there), so the certified
 // scan keeps treating the pixel's costs as the reference's very numbers (cert_pixel_exact) -- which they are, in every mode.
 // The row source of the block loops (srh_block.hpp) for the block at staged column rc of pixel i: window row `row` is ring
-// slot (s0 + row) mod NS; the other view's segment is read 16 bytes at a time from rbase (the rows, or their copy shifted by
-// one column for an odd rc); the weights from window buffer wb.
+// slot (s0 + row) mod NS; the other view's segment is read 16 bytes at a time (4-wave form: rc is even) or 8 bytes at a time
+// (8-wave form: rc of either parity); the weights from window buffer wb.
 // 8-wave form: at the start of a window row the wave publishes its progress and looks at its SIMD partner's; at the end it
 // yields (s_setprio 0) while ahead of the partner, 1 otherwise.  One asm statement with its own branch: the row loops stay
 // single basic blocks for the compiler's scheduler and register allocator.
@@ -339,20 +356,27 @@ struct StripRows {
 	typedef StripSmem<R, NBUF> Smem;
 	static constexpr bool LDS_WAIT = true;
 	Smem &S;
-	const double *rbase;
 	int s0, wb, i, rc, wv, lane, partner;
 	int &prog;
 	struct Row {
-		const double2 *rp, *wp;
+		const double *rp;
+		const double2 *wp;
 		const double *lp;
-		__device__ __forceinline__ void r2(int m, double &a, double &b) const { const double2 v = rp[m]; a = v.x; b = v.y; }
+		const double2 *cp;                     // the row's tap products (block_onepass_taps; 8-wave form)
+		__device__ __forceinline__ void c2(int m, double &a, double &b) const { const double2 v = cp[m]; a = v.x; b = v.y; }
+		__device__ __forceinline__ double c(int col) const { return reinterpret_cast<const double *>(cp)[col]; }
+		__device__ __forceinline__ void r2(int m, double &a, double &b) const {
+			if (NBUF == 2) { a = st_lds_read8(rp + 2*m); b = st_lds_read8(rp + 2*m + 1); }      // rc of either parity
+			else { const double2 v = reinterpret_cast<const double2 *>(rp)[m]; a = v.x; b = v.y; }   // rc even
+		}
 		__device__ __forceinline__ void w2(int m, double &a, double &b) const { const double2 v = wp[m]; a = v.x; b = v.y; }
 		__device__ __forceinline__ double w(int col) const { return reinterpret_cast<const double *>(wp)[col]; }
 		__device__ __forceinline__ double l(int col) const { return lp[col]; }
 	};
 	__device__ __forceinline__ Row row(int row) const {
 		const int sl = s0 + row >= Smem::NS ? s0 + row - Smem::NS : s0 + row;
-		return Row{ reinterpret_cast<const double2 *>(rbase + sl*Smem::RW + rc), reinterpret_cast<const double2 *>(&S.w[wb][row][i][0]), &S.lt[sl][i] };
+		return Row{ &S.rt[sl][rc], reinterpret_cast<const double2 *>(&S.w[wb][row][i][0]), &S.lt[sl][i],
+		            reinterpret_cast<const double2 *>(&S.c[NBUF == 2 ? row : 0][NBUF == 2 ? i : 0][0]) };
 	}
 	__device__ __forceinline__ int row_begin(int units) const {
 		int seen = 0;
@@ -383,7 +407,8 @@ void twoview_strip_cost_kernel(const StripArgs A)
 	constexpr int NR = NCB + 2*R;              // right-row values a block needs (even)
 	constexpr int G = 2*NWV;                   // block lanes per pixel
 	constexpr int NT = NWV*64;
-	constexpr bool PAD = NBUF == 1;            // blocks start on even columns (one copy of the rows); 8-wave form: at the pixel's first column
+	constexpr bool PAD = NBUF == 1;            // blocks start on even columns (16-byte row reads); 8-wave form: at the pixel's first column
+	constexpr bool TAPS = NBUF == 2 && ONEPASS && !BORDER;   // the tile's tap products in LDS (Smem::c), block_onepass_taps
 	static_assert(NR % 2 == 0, "16-byte rows");
 	static_assert((NWV == 4 && NBUF == 1) || (NWV == 8 && NBUF == 2), "two forms");
 	extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -488,11 +513,6 @@ void twoview_strip_cost_kernel(const StripArgs A)
 			if (wv < 3) { if (wv*1024 + lane*16 < RW*8) __builtin_amdgcn_global_load_lds((st_gbl_void *)((const char *)src + wv*1024 + lane*16),
 			                                                                              (st_lds_void *)((char *)&S.rt[sl][0] + wv*1024), 16, 0, 0); }
 			else if (wv == 3) st_dma16(A.ref_tvp + (size_t)(yy + SRH_PADY)*SP + (x0 - R + SRH_PADL), &S.lt[sl][0], LW*8, lane);
-			else if (NBUF == 2 && wv < 7) {
-				const int pc = wv - 4;                            // the copy shifted by one column
-				if (pc*1024 + lane*16 < RW*8) __builtin_amdgcn_global_load_lds((st_gbl_void *)((const char *)(src + 1) + pc*1024 + lane*16),
-				                                                                (st_lds_void *)((char *)&S.rto[sl][0] + pc*1024), 16, 0, 0);
-			}
 		};
 		static_assert(RW*8 <= 3*1024, "three pieces per row of the other view");
 		auto issue_full = [&](int fy, int fb) {
@@ -619,6 +639,27 @@ void twoview_strip_cost_kernel(const StripArgs A)
 				need_general = __any(bad) != 0;
 			}
 
+			// ---- the tile's tap products c_t = fma(w_t, l_t, -meanL)*w_t -- block_onepass's two operations, in its order, once per
+			// pixel: all lanes share the tile's WS x 32 x WP/2 pairs.  The windows, both rings and the constants have landed
+			// (barrier A, or the restage's own); the previous tile's plane is free (every wave has passed barrier A).  A pixel
+			// without a usable window of its own (slot 3 = 0) never reads its entries, whatever they come out as.
+			if (TAPS) {
+				constexpr int HP = WP/2, NPAIR = WS*ST_TP*HP;
+				// (a rolled loop, a pair at a time: unrolled, with the reads of all pairs in front, the kernel spills 15 more registers)
+				for (int e = tid; e < NPAIR; e += NT) {
+					const int row = e/(ST_TP*HP), pe = e - row*(ST_TP*HP), pi = pe/HP, col = 2*(pe - pi*HP);
+					const int sl = s0 + row >= NS ? s0 + row - NS : s0 + row;
+					const double mL = CS.pc[cur][pi][0];
+					const double2 wt = *reinterpret_cast<const double2 *>(&CS.w[wcur][row][pi][col]);
+					const bool two = col + 1 < WS;                             // (the row's pad tap: 0.0)
+					const double l0 = CS.lt[sl][pi + col], l1 = two ? CS.lt[sl][pi + col + 1] : 0.0;
+					double2 cc;
+					cc.x = __builtin_fma(wt.x, l0, -mL)*wt.x;
+					cc.y = two ? __builtin_fma(wt.y, l1, -mL)*wt.y : 0.0;
+					*reinterpret_cast<double2 *>(&S.c[row][pi][col]) = cc;
+				}
+				__syncthreads();
+			}
 			if (NWV == 8) { prog = 0; *(st_lds_vint *)&S.prog[wv][lane] = 0; __builtin_amdgcn_s_setprio(1); }
 			// ---- this lane's pixel
 			int e_min, e_max;
@@ -649,9 +690,7 @@ void twoview_strip_cost_kernel(const StripArgs A)
 				for (int b = g; b < (lall ? nblocks : 0); b += G) {
 					const int c0 = lo_e + b*NCB;
 					const int rc = c0 - cs;                 // tile column of the window's left edge
-					// 16-byte reads need an even index: an odd edge reads the copy shifted by one column
-					const double *rbase = (!PAD && (rc & 1)) ? &CS.rto[0][0] - 1 : &CS.rt[0][0];
-					StripRows<R, NWV, NBUF> rows{ S, rbase, s0, wcur, i, rc, wv, lane, partner, prog };
+					StripRows<R, NWV, NBUF> rows{ S, s0, wcur, i, rc, wv, lane, partner, prog };
 					// bit j: candidate c0 + j is inside the pixel's range and its window in the other view is fully usable
 					unsigned vm = 0;
 #pragma unroll
@@ -694,7 +733,8 @@ void twoview_strip_cost_kernel(const StripArgs A)
 						// U = sum w^2 r^2 in one sweep over the window; registers are refilled in place a row ahead, as below
 						const double mL = CS.pc[cur][i][0], itw = CS.pc[cur][i][3], s2 = CS.pc[cur][i][2];   // (slot 3 of a pixel with every tap usable: 1/totalWeight)
 						double P_[NCB], Q_[NCB], U_[NCB];
-						block_onepass<WS, NCB>(rows, mL, P_, Q_, U_);
+						if (TAPS) block_onepass_taps<WS, NCB>(rows, P_, Q_, U_);    // (meanL is in the tile's tap products)
+						else block_onepass<WS, NCB>(rows, mL, P_, Q_, U_);
 						constexpr double TT = (double)(WS*WS);
 						// every candidate of the block is finished (arithmetic on a column outside the range harms nobody); only the
 						// store looks at the candidate's bit -- no LDS read, wait and branch per candidate
@@ -829,6 +869,7 @@ template <int R, int NWV, int NBUF, int AR, bool BORDER>
 static void launch_strip_variant(hipStream_t st, const StripArgs &a, int num_cus)
 {
 	typedef StripSmem<R, NBUF> Smem;
+	static_assert(sizeof(Smem) <= (NBUF == 2 ? 160 : 80)*1024, "a compute unit's 160 KB of LDS: one 8-wave workgroup or two 4-wave ones");
 	size_t lds = sizeof(Smem);
 	(void)hipFuncSetAttribute((const void *)twoview_strip_cost_kernel<R, NWV, NBUF, AR, BORDER>,
 	                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

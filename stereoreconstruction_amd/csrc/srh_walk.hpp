@@ -406,8 +406,8 @@ __device__ __forceinline__ void pinhole_column_range(const Ray &ray, const srh_c
 // shared by `lanes` lanes.  When the last block would cost a whole extra round of the lanes for
 // at most two columns (typically the never-visited column of the last label plus the alignment
 // pad), it is left out: the scan evaluates such a column on demand with the general cost.
-// (pad: blocks start on even columns -- the kernels that keep ONE copy of the other view's rows in LDS and read it 16
-// bytes at a time; the 8-wave strip kernel keeps a second copy shifted by one column and starts its blocks at lo)
+// (pad: blocks start on even columns -- the kernels that read the other view's rows in LDS 16 bytes at a time; the
+// 8-wave strip kernel reads them 8 bytes at a time and starts its blocks at lo)
 __device__ __forceinline__ int dense_cover_hi(int lo, int hi, int ncb, int lanes, bool pad = true) {
 	const int lo_e = pad ? (lo & ~1) : lo;
 	const int nblocks = (hi - lo_e + ncb)/ncb;
