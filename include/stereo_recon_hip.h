@@ -781,6 +781,80 @@ typedef struct srh_speckle_info {
 int  srh_view_filter_speckles(srh_context *ctx, int slot, const srh_params *p, const srh_speckle_params *s,
                               srh_speckle_info *info, int32_t *labels_out);
 
+/* ---- rectification: a verged, distorted pair onto the row-aligned dense plan ----
+ * NOT IN THE REFERENCE (a stereo library is expected to rectify: OpenCV's stereoRectify + remap).  The dense plan, the fast
+ * path of srh_twoview_wta, is proposed only for two undistorted, non-refractive cameras with the same R, the same second and
+ * third rows of K and a baseline along the camera x axis: srh_twoview_row_aligned is that very test (1 / 0; *fx_bx, may be
+ * NULL, receives |fx * baseline| when 1).  Opt-in: nothing rectifies unless these entry points are called.
+ *
+ * srh_rectify_cameras (host math, needs no device): the rectified cameras ra, rb of the pair a, b, whose images (ALREADY
+ * scaled by image_scale, as everywhere) are w x h pixels.  In this order of operations, C_v the centres, rows of R_v:
+ *   r1 = (C_b - C_a)/|C_b - C_a|, negated if dot(r1, R_a.row0 + R_b.row0) < 0;   k = R_a.row2 + R_b.row2;
+ *   r2 = cross(k, r1) normalised;   r3 = cross(r1, r2);   Rn = rows r1, r2, r3 -- the very same doubles for both cameras;
+ *   Kn_v = [[f, 0, cx_v], [0, f, cy], [0, 0, 1]];   rv = srh_camera_from_krt(Kn_v, Rn, -Rn*C_v): no distortion, not refractive.
+ *   focal 0 (auto):  the mean of K_a[0], K_a[4], K_b[0], K_b[4].
+ *   cx_v NaN (auto): with d_v = Rn * R_v.row2 (the old optical axis in the new axes), (out_w/scale)/2 - f*d_v.x/d_v.z: the
+ *                    old optical axis lands on the middle column.  PER VIEW by default: the rig test compares rows 2 and 3
+ *                    of K only, and on a verged pair one shared cx pushes the object out of one frame.
+ *                    SRH_RECTIFY_SHARED_CX replaces both auto values by their mean (the classic disparity geometry).
+ *   cy NaN (auto):   (out_h/scale)/2 - f*mean_v(d_v.y/d_v.z).
+ *   out_w, out_h 0:  w, h.  They are the size of the rectified views in scaled pixels; only the auto principal point reads them here.
+ * SRH_E_INVALID: null pointers, w or h <= 0, image_scale <= 0, a negative or oversized output size, unknown flag bits, a
+ * focal or principal point that is not finite, coincident centres.  SRH_E_UNSUPPORTED: a refractive camera (no homography
+ * rectifies it); |cross(k, r1)| < 1e-6*|k| (the baseline runs along the viewing direction: forward motion); d_v.z <= 0.1 for
+ * either view (it looks more than 84 degrees away from the rectified axis).
+ *
+ * srh_view_rectify_map: where destination pixel (x, y) of a rectified view of out_w x out_h pixels with camera rect_cam reads
+ * the image of src_slot: uv_out (HOST, out_w*out_h pairs) receives (u, v) in the source's scaled raster, pixel centres at
+ * integers.  With s = image_scale:  ray = unproject(rect_cam, (x+0.5)/s, (y+0.5)/s);  P = ray.src + ray.dir;
+ * q = project(src camera, P);  u = q.x*s - 0.5, v = q.y*s - 0.5, where a value within 1e-11*(1 + |value|) of an integer is
+ * that integer (the round trip leaves about 1e-14 of noise: a whole-pixel shift then comes through byte for byte);  (NaN,
+ * NaN) where P lies behind the source camera or u, v are not finite.  The source camera may be distorted; a refractive one is SRH_E_UNSUPPORTED.
+ *
+ * srh_twoview_rectify: the views of src_a, src_b warped into dst_a, dst_b with the cameras of srh_rectify_cameras (r NULL:
+ * the defaults; p supplies image_scale).  Per destination pixel with a finite (u, v):  x0 = floor(u), y0 = floor(v) (saturating),
+ * a = u - x0, b = v - y0;  every one of the four channels is
+ *   floor(((1-a)*c00 + a*c10)*(1-b) + ((1-a)*c01 + a*c11)*b + 0.5) clamped to [0, 255], in double, no fused multiply-add,
+ * from the four taps CLAMPED into the source; the pixel is WHITE iff the four taps lie inside the source unclamped and are
+ * WHITE there -- where a tap whose weight is exactly 0 (a == 0: the right column, b == 0: the lower row) is not asked, so
+ * that a whole-pixel shift keeps its last column and row.  Elsewhere bytes 0,0,0,0 and not WHITE.  A destination slot then is what srh_view_upload of those pixels,
+ * that mask and the rectified camera leaves: derived planes recomputed, depth NaN, WTA by-products and peaks forgotten.
+ * Both warps are queued before either slot is written, so dst == src is legal (the four slots otherwise distinct per
+ * role: src_a != src_b, dst_a != dst_b).  A refusal leaves all four slots as they were.  info (may be NULL): the angle
+ * (radians) between each view's old optical axis and the rectified one, the WHITE pixels of each result, and fx_bx of the
+ * rectified pair.
+ *
+ * srh_view_depth_unrectify: the depth map of rect_slot (a rectified view; z along the rectified axis) brought into
+ * dst_slot (the view the user handed in: same centre within 1e-9*(1+|C|), else SRH_E_INVALID; may be distorted), written
+ * into dst_slot's depth map.  Per WHITE pixel (x, y) of dst:  ray = unproject(dst camera, (x+0.5)/s, (y+0.5)/s);
+ * q = project(rectified camera, ray.src + ray.dir);  (x2, y2) = (q.x*s, q.y*s);  behind the rectified camera or outside
+ * [0, w_r) x [0, h_r): depth NaN, index -1;  else dr = depth_rect[trunc(y2)][trunc(x2)] (the cross-check's pixel rule), copied
+ * through unchanged when it is not finite or <= 0 (+INF, NaN, MultiViewStereo's -1), else X = ray.src + ray.dir*(dr / dot(r3,
+ * ray.dir)) and the depth is dst's local z of X.  Pixels that are not WHITE get NaN.  src_index_out (HOST, w*h int32 of dst,
+ * may be NULL): trunc(y2)*w_r + trunc(x2), or -1.  Nearest-pixel on purpose: depth maps carry +INF / NaN classes that no
+ * interpolation keeps. */
+enum { SRH_RECTIFY_SHARED_CX = 1 };
+typedef struct srh_rectify_params {
+	double  focal;              /* 0: auto */
+	double  cx_a, cx_b, cy;     /* NaN: auto */
+	int32_t out_w, out_h;       /* 0: the size of view a; scaled pixels */
+	int32_t flags, reserved;    /* 0, or SRH_RECTIFY_SHARED_CX */
+} srh_rectify_params;
+void srh_rectify_params_defaults(srh_rectify_params *r);   /* 0, NaN, NaN, NaN, 0, 0, 0, 0; NULL ignored; needs no device */
+int  srh_rectify_cameras(const srh_camera *a, const srh_camera *b, int w, int h, double image_scale,
+                         const srh_rectify_params *r, srh_camera *ra, srh_camera *rb);
+int  srh_twoview_row_aligned(const srh_camera *a, const srh_camera *b, double *fx_bx);
+typedef struct srh_rectify_info {
+	double  angle_a, angle_b;   /* radians between the old and the rectified optical axis */
+	double  fx_bx;              /* of the rectified pair */
+	int64_t white_a, white_b;   /* WHITE pixels of the rectified views */
+} srh_rectify_info;
+int  srh_twoview_rectify(srh_context *ctx, int src_a, int src_b, int dst_a, int dst_b, const srh_params *p,
+                         const srh_rectify_params *r, srh_rectify_info *info);
+int  srh_view_rectify_map(srh_context *ctx, int src_slot, const srh_camera *rect_cam, int out_w, int out_h,
+                          double image_scale, double *uv_out);
+int  srh_view_depth_unrectify(srh_context *ctx, int rect_slot, int dst_slot, const srh_params *p, int32_t *src_index_out);
+
 /* ---- epipolar curves ----
  * TwoViewStereo::epipolarCurve (public member, twoviewstereo.hpp:66-70, twoviewstereo.cpp:999-1054;
  * the GUI's curve preview calls it, stereowidget.cpp:621-672) when mvs == 0, and

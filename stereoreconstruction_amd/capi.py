@@ -138,6 +138,22 @@ class SpeckleInfo(C.Structure):
 # srh_view_filter_speckles flag: the reject value is NaN, not +INF
 SPECKLE_TO_NAN = 1
 
+
+class RectifyParams(C.Structure):
+    """srh_rectify_params"""
+    _fields_ = [("focal", C.c_double), ("cx_a", C.c_double), ("cx_b", C.c_double), ("cy", C.c_double),
+                ("out_w", C.c_int32), ("out_h", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RectifyInfo(C.Structure):
+    """srh_rectify_info"""
+    _fields_ = [("angle_a", C.c_double), ("angle_b", C.c_double), ("fx_bx", C.c_double),
+                ("white_a", C.c_int64), ("white_b", C.c_int64)]
+
+
+# srh_rectify_params flag: one principal-point column for both rectified views (the mean of the two auto values)
+RECTIFY_SHARED_CX = 1
+
 # srh_mvs_fuse: bit 0 of a fused point's flags
 FUSE_HAS_NORMAL = 1
 
@@ -166,6 +182,8 @@ EXPORTS = [
     "srh_twoview_wta", "srh_twoview_cross_check", "srh_twoview_compute", "srh_twoview_cost_rows", "srh_twoview_pair_costs", "srh_debug_exp",
     "srh_mvs_initial_estimate", "srh_mvs_cross_check", "srh_view_point_cloud", "srh_view_filter_invalid",
     "srh_speckle_params_defaults", "srh_view_filter_speckles",
+    "srh_rectify_params_defaults", "srh_rectify_cameras", "srh_twoview_row_aligned", "srh_twoview_rectify",
+    "srh_view_rectify_map", "srh_view_depth_unrectify",
     "srh_fuse_params_defaults", "srh_mvs_fuse", "srh_mvs_fused_count", "srh_mvs_fused_download", "srh_mvs_fused_device",
     "srh_epipolar_curves",
     "srh_epipolar_preview", "srh_refraction_error",
@@ -293,6 +311,15 @@ def lib():
     L.srh_speckle_params_defaults.argtypes = [C.POINTER(SpeckleParams)]
     L.srh_speckle_params_defaults.restype = None
     L.srh_view_filter_speckles.argtypes = [vp, C.c_int, C.POINTER(Params), C.POINTER(SpeckleParams), C.POINTER(SpeckleInfo), c_int32_p]
+    L.srh_rectify_params_defaults.argtypes = [C.POINTER(RectifyParams)]
+    L.srh_rectify_params_defaults.restype = None
+    L.srh_rectify_cameras.argtypes = [C.POINTER(Camera), C.POINTER(Camera), C.c_int, C.c_int, C.c_double, C.POINTER(RectifyParams),
+                                      C.POINTER(Camera), C.POINTER(Camera)]
+    L.srh_twoview_row_aligned.argtypes = [C.POINTER(Camera), C.POINTER(Camera), c_double_p]
+    L.srh_twoview_rectify.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(Params), C.POINTER(RectifyParams),
+                                      C.POINTER(RectifyInfo)]
+    L.srh_view_rectify_map.argtypes = [vp, C.c_int, C.POINTER(Camera), C.c_int, C.c_int, C.c_double, c_double_p]
+    L.srh_view_depth_unrectify.argtypes = [vp, C.c_int, C.c_int, C.POINTER(Params), c_int32_p]
     L.srh_fuse_params_defaults.argtypes = [C.POINTER(FuseParams)]
     L.srh_fuse_params_defaults.restype = None
     L.srh_mvs_fuse.argtypes = [vp, c_int32_p, C.c_int, C.POINTER(Params), C.POINTER(FuseParams), C.POINTER(FuseInfo)]
@@ -407,6 +434,33 @@ def fuse_params(**kw):
             raise AttributeError(k)
         setattr(f, k, v)
     return f
+
+
+def rectify_params(**kw):
+    """srh_rectify_params with its defaults (focal 0 = auto, cx_a, cx_b, cy NaN = auto, out_w, out_h 0 = view a's size,
+    flags 0)."""
+    r = RectifyParams()
+    lib().srh_rectify_params_defaults(C.byref(r))
+    for k, v in kw.items():
+        if not hasattr(r, k):
+            raise AttributeError(k)
+        setattr(r, k, v)
+    return r
+
+
+def rectify_cameras(cam_a, cam_b, w, h, image_scale=1.0, r=None):
+    """The rectified cameras (ra, rb) of a pair whose scaled images are w x h (srh_rectify_cameras; needs no device)."""
+    ra, rb = Camera(), Camera()
+    _check(lib().srh_rectify_cameras(C.byref(cam_a), C.byref(cam_b), int(w), int(h), float(image_scale),
+                                     C.byref(r) if r is not None else None, C.byref(ra), C.byref(rb)))
+    return ra, rb
+
+
+def twoview_row_aligned(cam_a, cam_b):
+    """The dense plan's rig test (srh_twoview_row_aligned): (True, fx_bx) or (False, None)."""
+    f = C.c_double(0.0)
+    yes = lib().srh_twoview_row_aligned(C.byref(cam_a), C.byref(cam_b), C.byref(f))
+    return (True, f.value) if yes else (False, None)
 
 
 def _mrf_info(info):
@@ -802,6 +856,32 @@ class Context:
                                               labels.ctypes.data_as(c_int32_p) if want_labels else None))
         out = {k: int(getattr(info, k)) for k, _ in SpeckleInfo._fields_}
         return (out, labels) if want_labels else out
+
+    def twoview_rectify(self, src_a, src_b, dst_a, dst_b, p, r=None):
+        """The views of src_a, src_b warped onto the rectified cameras into dst_a, dst_b (srh_twoview_rectify; a destination
+        may be a source) -> dict(angle_a, angle_b, fx_bx, white_a, white_b)."""
+        info = RectifyInfo()
+        _check(lib().srh_twoview_rectify(self._h, src_a, src_b, dst_a, dst_b, C.byref(p), C.byref(r) if r is not None else None,
+                                         C.byref(info)))
+        return {k: getattr(info, k) for k, _ in RectifyInfo._fields_}
+
+    def rectify_map(self, src_slot, rect_cam, out_w, out_h, image_scale=1.0):
+        """(out_h, out_w, 2): where every pixel of a rectified view with camera rect_cam reads slot src_slot's image, (u, v)
+        with pixel centres at integers, NaN where it reads nothing (srh_view_rectify_map)."""
+        uv = np.empty((int(out_h), int(out_w), 2), dtype=np.float64)
+        _check(lib().srh_view_rectify_map(self._h, src_slot, C.byref(rect_cam), int(out_w), int(out_h), float(image_scale), _dptr(uv)))
+        return uv
+
+    def depth_unrectify(self, rect_slot, dst_slot, p, want_index=False):
+        """The depth map of the rectified view rect_slot into the depth map of dst_slot, the view the user handed in
+        (srh_view_depth_unrectify); want_index: returns (h, w) int32, the rectified pixel every pixel read (-1: none)."""
+        idx = None
+        if want_index:
+            w, h = self.view_size(dst_slot)
+            idx = np.empty((h, w), dtype=np.int32)
+        _check(lib().srh_view_depth_unrectify(self._h, rect_slot, dst_slot, C.byref(p),
+                                              idx.ctypes.data_as(c_int32_p) if idx is not None else None))
+        return idx
 
     def twoview_pair_costs(self, ref, oth, p, xy, kind=COST_SAD):
         """cost_sad (kind COST_SAD) or cost_ncc (COST_NCC) of arbitrary pairs: xy (n, 4) int rows (x1, y1, x2, y2), the

@@ -6,6 +6,7 @@
 #include "srh_geom.hpp"
 #include "srh_walk.hpp"
 #include "srh_speckle.hpp"
+#include "srh_rectify.hpp"
 
 #include <algorithm>
 #include <cassert>
@@ -1433,22 +1434,7 @@ static void run_weights(srh_context *c, const Lane &lane, int ref, int W, const 
 	launch_weights(lane.stream, c->d_views, ref, W, p, by, nr, lane.mem->band.wbuf, wstride, pconst, wimg);
 }
 
-// Can every epipolar curve of `a` in `b` stay on its own image row?  Undistorted, non-refractive
-// cameras with the same orientation and the same second and third rows of K, displaced along the
-// camera x axis.  This only *proposes* the dense path: the scan kernel verifies every candidate.
-static bool rig_is_row_aligned(const srh_camera &a, const srh_camera &b, double *fx_bx) {
-	if (a.is_distorted || b.is_distorted || a.is_refractive || b.is_refractive) return false;
-	for (int k = 0; k < 9; ++k) if (fabs(a.R[k] - b.R[k]) > 1e-13) return false;
-	for (int k = 3; k < 9; ++k) if (fabs(a.K[k] - b.K[k]) > 1e-9*(1.0 + fabs(a.K[k]))) return false;
-	if (fabs(a.K[1]) > 1e-12 || fabs(b.K[1]) > 1e-12 || fabs(a.K[3]) > 1e-12 || fabs(a.K[6]) > 1e-12 || fabs(a.K[7]) > 1e-12)
-		return false;
-	const Vec3 d = load3(b.C) - load3(a.C);
-	const Vec3 bc = matvec(a.R, d);                               // baseline in camera axes
-	const double len = norm(bc);
-	if (!(len > 0) || fabs(bc.y) > 1e-12*len || fabs(bc.z) > 1e-12*len) return false;
-	*fx_bx = fabs(b.K[0]*bc.x);
-	return true;
-}
+// (the rig test that proposes the dense path, rig_is_row_aligned: srh_rectify.hpp)
 
 // The WTA by-products of a pass ref -> oth (option "wta_outputs"): the planes exist and hold either what an earlier pass of
 // the same kind left (a pass over some rows writes those rows only, as it does in the depth map) or the "none" values.
@@ -3250,6 +3236,155 @@ static int twoview_speckles(srh_context *c, int left, int right, const srh_param
 	if ((rc = speckle_view(c, left, max_diff, s.min_size, false, nullptr, nullptr))) return rc;
 	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
 	return speckle_view(c, right, max_diff, s.min_size, false, nullptr, nullptr);
+}
+
+// ------------------------------------------------------------------ rectification (srh_rectify.hpp / .hip)
+extern "C" void srh_rectify_params_defaults(srh_rectify_params *r)
+{
+	if (!r) return;
+	r->focal = 0; r->cx_a = r->cx_b = r->cy = __builtin_nan("");
+	r->out_w = r->out_h = 0; r->flags = r->reserved = 0;
+}
+
+extern "C" int srh_twoview_row_aligned(const srh_camera *a, const srh_camera *b, double *fx_bx)
+{
+	if (!a || !b) return 0;
+	double f = 0;
+	const bool yes = rig_is_row_aligned(*a, *b, &f);
+	if (yes && fx_bx) *fx_bx = f;
+	return yes ? 1 : 0;
+}
+
+extern "C" int srh_rectify_cameras(const srh_camera *a, const srh_camera *b, int w, int h, double image_scale,
+                                   const srh_rectify_params *r, srh_camera *ra, srh_camera *rb)
+{
+	if (!a || !b || !ra || !rb) return fail(SRH_E_INVALID, "null argument");
+	srh_rectify_params rp;
+	srh_rectify_params_defaults(&rp);
+	if (r) rp = *r;
+	rect::Geometry g;
+	const char *why = "";
+	int rc = rect::geometry(*a, *b, w, h, image_scale, rp, g, &why);
+	if (rc) return fail(rc, "rectification: %s", why);
+	srh_camera ca, cb;
+	if ((rc = srh_camera_from_krt(g.Ka, g.Rn, g.ta, nullptr, nullptr, 0.0, 1.0, &ca))) return rc;
+	if ((rc = srh_camera_from_krt(g.Kb, g.Rn, g.tb, nullptr, nullptr, 0.0, 1.0, &cb))) return rc;
+	*ra = ca; *rb = cb;
+	return SRH_OK;
+}
+
+extern "C" int srh_view_rectify_map(srh_context *c, int src_slot, const srh_camera *rect_cam, int out_w, int out_h,
+                                    double image_scale, double *uv_out)
+{
+	int rc;
+	if ((rc = check_slot(c, src_slot, true))) return rc;
+	if (!rect_cam || !uv_out) return fail(SRH_E_INVALID, "null argument");
+	if (out_w <= 0 || out_h <= 0 || out_w > SRH_MAX_VIEW_DIM || out_h > SRH_MAX_VIEW_DIM) return fail(SRH_E_INVALID, "bad output size %dx%d", out_w, out_h);
+	if (!(image_scale > 0) || !std::isfinite(image_scale)) return fail(SRH_E_INVALID, "image_scale must be > 0");
+	if (c->views[src_slot].cam.is_refractive || rect_cam->is_refractive) return fail(SRH_E_UNSUPPORTED, "rectification: a refractive camera");
+	HIP_TRY(hipSetDevice(c->device));
+	const size_t n = (size_t)out_w*out_h;
+	DevBuf<double> uv;
+	hipError_t e = uv.alloc(2*n);
+	if (e == hipSuccess) {
+		Scope s(c, c->stream, "rectify_warp_kernel");
+		launch_rectify_warp(c->stream, c->d_views, src_slot, *rect_cam, out_w, out_h, image_scale, uv, nullptr, nullptr);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipMemcpyAsync(uv_out, uv, 2*n*sizeof(double), hipMemcpyDeviceToHost, c->stream);
+	const hipError_t es = hipStreamSynchronize(c->stream);
+	uv.release();
+	if (e == hipSuccess) e = es;
+	if (e != hipSuccess) return fail(SRH_E_DEVICE, "rectification map: %s", hipGetErrorString(e));
+	return SRH_OK;
+}
+
+extern "C" int srh_twoview_rectify(srh_context *c, int src_a, int src_b, int dst_a, int dst_b, const srh_params *p,
+                                   const srh_rectify_params *r, srh_rectify_info *info)
+{
+	int rc;
+	if ((rc = check_slot(c, src_a, true)) || (rc = check_slot(c, src_b, true)) || (rc = check_slot(c, dst_a, false)) ||
+	    (rc = check_slot(c, dst_b, false)) || (rc = check_params(p))) return rc;
+	if (src_a == src_b || dst_a == dst_b) return fail(SRH_E_INVALID, "rectification: the two sources (and the two destinations) are different slots");
+	// every refusal comes before a slot is touched
+	const srh_camera old_a = c->views[src_a].cam, old_b = c->views[src_b].cam;   // (copies: a source may be a destination)
+	const int aw = c->views[src_a].w, ah = c->views[src_a].h;
+	srh_rectify_params rp;
+	srh_rectify_params_defaults(&rp);
+	if (r) rp = *r;
+	srh_camera cam[2];
+	if ((rc = srh_rectify_cameras(&old_a, &old_b, aw, ah, p->image_scale, &rp, &cam[0], &cam[1]))) return rc;
+	const int ow = rp.out_w ? rp.out_w : aw, oh = rp.out_h ? rp.out_h : ah;
+	const size_t n = (size_t)ow*oh;
+	HIP_TRY(hipSetDevice(c->device));
+	// both warps are queued (and finished) before either destination is installed: a destination may be a source
+	DevBuf<uint32_t> img[2];
+	DevBuf<uint8_t> msk[2];
+	std::vector<uint8_t> hmask[2];
+	const int src[2] = { src_a, src_b }, dst[2] = { dst_a, dst_b };
+	auto run = [&]() -> int {
+		for (int k = 0; k < 2; ++k) {
+			HIP_TRY(img[k].alloc(n));
+			HIP_TRY(msk[k].alloc(n));
+			hmask[k].resize(n);
+		}
+		for (int k = 0; k < 2; ++k) {
+			{ Scope s(c, c->stream, "rectify_warp_kernel");
+			  launch_rectify_warp(c->stream, c->d_views, src[k], cam[k], ow, oh, p->image_scale, nullptr, img[k], msk[k]); }
+			HIP_TRY(hipGetLastError());
+			HIP_TRY(hipMemcpyAsync(hmask[k].data(), msk[k], n, hipMemcpyDeviceToHost, c->stream));
+		}
+		HIP_TRY(hipStreamSynchronize(c->stream));
+		for (int k = 0; k < 2; ++k) {
+			const int r2 = view_install(c, dst[k], ow, oh, img[k], msk[k], hmask[k].data(), hipMemcpyDeviceToDevice, &cam[k]);
+			if (r2) return r2;
+		}
+		return SRH_OK;
+	};
+	rc = run();
+	(void)hipStreamSynchronize(c->stream);
+	for (int k = 0; k < 2; ++k) { img[k].release(); msk[k].release(); }
+	if (rc) return rc;
+	if (info) {
+		info->angle_a = rect::axis_angle(old_a, cam[0]);
+		info->angle_b = rect::axis_angle(old_b, cam[1]);
+		info->fx_bx = 0;
+		(void)rig_is_row_aligned(cam[0], cam[1], &info->fx_bx);
+		int64_t wc[2] = { 0, 0 };
+		for (int k = 0; k < 2; ++k) for (size_t i = 0; i < n; ++i) wc[k] += hmask[k][i] == 1;
+		info->white_a = wc[0]; info->white_b = wc[1];
+	}
+	return SRH_OK;
+}
+
+extern "C" int srh_view_depth_unrectify(srh_context *c, int rect_slot, int dst_slot, const srh_params *p, int32_t *src_index_out)
+{
+	int rc;
+	if ((rc = check_slot(c, rect_slot, true)) || (rc = check_slot(c, dst_slot, true)) || (rc = check_params(p))) return rc;
+	if (rect_slot == dst_slot) return fail(SRH_E_INVALID, "unrectify: the rectified view and the destination are the same slot");
+	ViewHost &D = c->views[dst_slot];
+	const ViewHost &R = c->views[rect_slot];
+	if (D.cam.is_refractive || R.cam.is_refractive) return fail(SRH_E_UNSUPPORTED, "unrectify: a refractive camera");
+	const Vec3 dc = load3(D.cam.C) - load3(R.cam.C);
+	if (!(norm(dc) <= 1e-9*(1.0 + norm(load3(D.cam.C)))))
+		return fail(SRH_E_INVALID, "unrectify: the cameras of slots %d and %d do not share a centre (distance %g)", rect_slot, dst_slot, norm(dc));
+	HIP_TRY(hipSetDevice(c->device));
+	const size_t n = (size_t)D.w*D.h;
+	DevBuf<int32_t> index;
+	hipError_t e = hipSuccess;
+	if (src_index_out) e = index.alloc(n);
+	if (e == hipSuccess) {
+		Scope s(c, c->stream, "unrectify_kernel");
+		launch_unrectify(c->stream, c->d_views, rect_slot, dst_slot, D.w, D.h, p->image_scale, index);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess && src_index_out) e = hipMemcpyAsync(src_index_out, index, n*sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
+	const hipError_t es = hipStreamSynchronize(c->stream);
+	index.release();
+	if (e == hipSuccess) e = es;
+	if (e != hipSuccess) return fail(SRH_E_DEVICE, "unrectify: %s", hipGetErrorString(e));
+	D.wta_flags = 0;                                             // the map no longer comes from a WTA pass of this view
+	return SRH_OK;
 }
 
 // ------------------------------------------------------------------ epipolar curves on request

@@ -11,13 +11,19 @@
 // intersect / refract (util/ray.cpp:78-106).
 #pragma once
 
-#include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "stereo_recon_hip.h"
 
+// (a host compiler takes this header too: the CPU suite compiles it with g++, tests/rectify_host.cpp)
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
 #define SRH_HD __host__ __device__ __forceinline__
+#else
+#define SRH_HD inline
+#endif
 
 namespace srh {
 

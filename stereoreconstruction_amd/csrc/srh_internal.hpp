@@ -280,6 +280,12 @@ void launch_speckle_flatten(hipStream_t st, const int32_t *A, size_t n, int32_t 
 void launch_speckle_count(hipStream_t st, const int32_t *B, size_t n, int32_t *size);
 void launch_speckle_apply(hipStream_t st, const int32_t *B, const int32_t *size, size_t n, int min_size, double reject, double *D,
                           unsigned long long *cnt);
+// rectification (srh_rectify.hip).  The warp of slot `src` onto rect_cam, out_w x out_h: the map uv (2 doubles
+// per pixel, or null) and the warped rgba + mask (both, or both null).  The way back: slot dst's depth map (w x h) from
+// slot rect's, index (w*h, or null) = the rectified pixel every pixel read
+void launch_rectify_warp(hipStream_t st, const ViewDev *views, int src, const srh_camera &rect_cam, int out_w, int out_h, double s,
+                         double *uv, uint32_t *rgba, uint8_t *mask);
+void launch_unrectify(hipStream_t st, const ViewDev *views, int rect_slot, int dst_slot, int w, int h, double s, int32_t *index);
 // weighted SAD, TwoViewStereo::cost_sad (srh_sad.hip)
 // full (w*h bytes): 1 where the whole (2R+1)^2 window of cost_sad's OTHER-view side is usable (inside the image, mask WHITE)
 void launch_sad_full_window(hipStream_t st, const uint8_t *mask, int w, int h, int R, uint8_t *full);

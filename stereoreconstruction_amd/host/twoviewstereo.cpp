@@ -52,6 +52,9 @@ void TwoViewStereo::setUp(int deviceOrdinal) {
 	mrfInfo_[0] = mrfInfo_[1] = srh_mrf_info();
 	srh_twoview_sgm_params_defaults(&sgmParams_);
 	sgmInfo_[0] = sgmInfo_[1] = srh_sgm_info();
+	srh_rectify_params_defaults(&rectParams_);
+	rectInfo_ = srh_rectify_info();
+	rectCam_[0] = rectCam_[1] = srh_camera();
 	if (!ctx_ && error_.empty() && srh_create(deviceOrdinal, &ctx_) != SRH_OK) { error_ = srh_last_error(); ctx_ = nullptr; }
 }
 
@@ -188,19 +191,21 @@ void TwoViewStereo::computeCostVolumes(CameraPtr leftView_, CameraPtr rightView_
 	fetchWtaOutputs();
 }
 
-// the kept by-products of both passes (slot 0: the left map's, slot 1: the right map's); empty when nothing was kept
-void TwoViewStereo::fetchWtaOutputs() {
+// the kept by-products of both passes (leftSlot: the left map's, rightSlot: the right map's -- 0 and 1, or the rectified
+// views' slots); empty when nothing was kept
+void TwoViewStereo::fetchWtaOutputs(int leftSlot, int rightSlot) {
 	for (int k = 0; k < 2; ++k) { winners_[k].clear(); runners_[k].clear(); minCosts_[k].clear(); secondCosts_[k].clear(); }
 	if (!ctx_ || !wtaFlags) return;
 	for (int k = 0; k < 2; ++k) {
+		const int slot = k == 0 ? leftSlot : rightSlot;
 		int flags = 0, w = 0, h = 0;
-		if (srh_view_wta_outputs_state(ctx_, k, &flags, nullptr) != SRH_OK || srh_view_size(ctx_, k, &w, &h) != SRH_OK) { error_ = srh_last_error(); return; }
+		if (srh_view_wta_outputs_state(ctx_, slot, &flags, nullptr) != SRH_OK || srh_view_size(ctx_, slot, &w, &h) != SRH_OK) { error_ = srh_last_error(); return; }
 		if (!(flags & SRH_WTA_WINNERS)) continue;
 		const size_t n = static_cast<size_t>(w)*h;
 		const bool costs = (flags & SRH_WTA_COSTS) != 0;
 		winners_[k].resize(2*n); runners_[k].resize(2*n);
 		if (costs) { minCosts_[k].resize(n); secondCosts_[k].resize(n); }
-		if (srh_view_wta_outputs(ctx_, k, winners_[k].data(), runners_[k].data(), costs ? minCosts_[k].data() : nullptr,
+		if (srh_view_wta_outputs(ctx_, slot, winners_[k].data(), runners_[k].data(), costs ? minCosts_[k].data() : nullptr,
 		                         costs ? secondCosts_[k].data() : nullptr) != SRH_OK) {
 			error_ = srh_last_error();
 			winners_[k].clear(); runners_[k].clear(); minCosts_[k].clear(); secondCosts_[k].clear();
@@ -267,6 +272,40 @@ double TwoViewStereo::depthFromLabel(int label) const {
 	return minDepth*(1.0 - t) + maxDepth*t;
 }
 
+// setRectify(true): slots 0, 1 (uploaded) warped into slots 2, 3, and the rectified products of the views kept.  false: the
+// library refused the pair (lastError() says why) -- nothing is rectified and the rectified products are empty.
+bool TwoViewStereo::rectifyViews() {
+	rectInfo_ = srh_rectify_info();
+	for (int k = 0; k < 2; ++k) { rectDepth_[k].clear(); rectImage_[k] = Image(); rectMask_[k].clear(); rectCam_[k] = srh_camera(); }
+	const srh_camera lc = leftView->snapshot(), rc = rightView->snapshot();
+	if (srh_rectify_cameras(&lc, &rc, left.w, left.h, params_.image_scale, &rectParams_, &rectCam_[0], &rectCam_[1]) != SRH_OK ||
+	    srh_twoview_rectify(ctx_, 0, 1, 2, 3, &params_, &rectParams_, &rectInfo_) != SRH_OK) {
+		error_ = srh_last_error();
+		rectCam_[0] = rectCam_[1] = srh_camera();
+		return false;
+	}
+	for (int k = 0; k < 2; ++k) {
+		int w = 0, h = 0;
+		if (srh_view_size(ctx_, 2 + k, &w, &h) != SRH_OK) { error_ = srh_last_error(); return false; }
+		rectImage_[k] = Image(w, h);
+		rectMask_[k].resize(static_cast<size_t>(w)*h);
+		rectDepth_[k].assign(static_cast<size_t>(w)*h, std::numeric_limits<double>::quiet_NaN());
+		if (srh_view_image_download(ctx_, 2 + k, rectImage_[k].rgba.data(), rectMask_[k].data()) != SRH_OK) { error_ = srh_last_error(); return false; }
+	}
+	return true;
+}
+
+// the rectified maps (slots 2, 3, as the pipeline left them) into the views the caller handed in (slots 0, 1)
+bool TwoViewStereo::unrectifyMaps() {
+	if (srh_view_depth_unrectify(ctx_, 2, 0, &params_, nullptr) != SRH_OK || srh_view_depth_unrectify(ctx_, 3, 1, &params_, nullptr) != SRH_OK ||
+	    srh_view_depth_download(ctx_, 0, computedDepthLeft.data()) != SRH_OK ||
+	    srh_view_depth_download(ctx_, 1, computedDepthRight.data()) != SRH_OK) {
+		error_ = srh_last_error();
+		return false;
+	}
+	return true;
+}
+
 void TwoViewStereo::computeDepthMaps() {
 	// twoviewstereo.cpp:150-227: cost volumes (steps 1,3; setUseMRF / setUseSGM: + the optimiser / the aggregation, 2,4), cross-check (5), colourise, finished (8)
 	if (!ctx_) { if (error_.empty()) error_ = "no device context"; return; }
@@ -285,13 +324,18 @@ void TwoViewStereo::computeDepthMaps() {
 	}
 	mrfInfo_[0] = mrfInfo_[1] = srh_mrf_info();
 	sgmInfo_[0] = sgmInfo_[1] = srh_sgm_info();
-	const int rc_ = useSgm ? srh_twoview_compute_sgm(ctx_, 0, 1, &params_, &sgmParams_, computedDepthLeft.data(), computedDepthRight.data(), sgmInfo_)
-	              : useMrf ? srh_twoview_compute_mrf(ctx_, 0, 1, &params_, &mrfParams_, computedDepthLeft.data(), computedDepthRight.data(), mrfInfo_)
-	                       : srh_twoview_compute(ctx_, 0, 1, &params_, computedDepthLeft.data(), computedDepthRight.data());
+	// setRectify: the pipeline runs on the rectified views (slots 2, 3) into the rectified maps; a refused pair runs as it is
+	rectified_ = rectifyOn && rectifyViews();
+	const int ls = rectified_ ? 2 : 0, rs = rectified_ ? 3 : 1;
+	double *dl = rectified_ ? rectDepth_[0].data() : computedDepthLeft.data(), *dr = rectified_ ? rectDepth_[1].data() : computedDepthRight.data();
+	const int rc_ = useSgm ? srh_twoview_compute_sgm(ctx_, ls, rs, &params_, &sgmParams_, dl, dr, sgmInfo_)
+	              : useMrf ? srh_twoview_compute_mrf(ctx_, ls, rs, &params_, &mrfParams_, dl, dr, mrfInfo_)
+	                       : srh_twoview_compute(ctx_, ls, rs, &params_, dl, dr);
 	srh_set_hooks(ctx_, nullptr, nullptr, nullptr);
 	if (rc_ == SRH_E_CANCELLED) return;              // reference: silent return on cancel
 	if (rc_ != SRH_OK) { error_ = srh_last_error(); return; }
-	fetchWtaOutputs();
+	fetchWtaOutputs(ls, rs);
+	if (rectified_ && !unrectifyMaps()) return;
 	colorize(computedDepthLeft, resultLeft);
 	colorize(computedDepthRight, resultRight);
 }

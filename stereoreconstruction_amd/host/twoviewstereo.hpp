@@ -76,6 +76,30 @@ public:
 	const std::vector<double> &rightMinCosts() const { return minCosts_[1]; }
 	const std::vector<double> &rightSecondCosts() const { return secondCosts_[1]; }
 
+	// Rectification (NOT IN THE REFERENCE; stereo_recon_hip.h): off (default) nothing changes.  On,
+	// computeDepthMaps uploads the views as ever (slots 0, 1), warps them onto a rectified pair of cameras (slots 2, 3:
+	// srh_twoview_rectify with rectifyParams()), runs the whole configured pipeline on the rectified pair -- WTA or SGM or MRF,
+	// cross-check, speckles, hole filling -- where a verged, distorted pair gets the row-aligned dense plan, and brings both
+	// depth maps back (srh_view_depth_unrectify): leftDepths(), rightDepths() and the colourised maps stay in the views the
+	// caller handed in, at their size.  The rectified products are kept beside them: the rectified depth maps (z along the
+	// rectified axis), images (rectifiedLeftMaskBytes(): 1 = WHITE) and cameras, all of rectifyParams().out_w x out_h
+	// pixels (0: the left image's size), and what srh_twoview_rectify reported.  The WTA by-products of setKeepWtaOutputs,
+	// when kept, are in RECTIFIED coordinates: pixels of the rectified views, rectified size.  A pair the library refuses to
+	// rectify (a refractive camera, a baseline along the viewing direction, coincident centres) sets lastError() and runs
+	// unrectified: rectified() then says false and the rectified products are empty.
+	void setRectify(bool on) { rectifyOn = on; }
+	bool rectify() const { return rectifyOn; }
+	srh_rectify_params &rectifyParams() { return rectParams_; }   // focal, principal point, output size, SRH_RECTIFY_SHARED_CX
+	bool rectified() const { return rectified_; }                  // the last computeDepthMaps ran on the rectified pair
+	const DepthMap &rectifiedLeftDepths() const { return rectDepth_[0]; }
+	const DepthMap &rectifiedRightDepths() const { return rectDepth_[1]; }
+	const Image &rectifiedLeftImage() const { return rectImage_[0]; }
+	const Image &rectifiedRightImage() const { return rectImage_[1]; }
+	const std::vector<uint8_t> &rectifiedLeftMaskBytes() const { return rectMask_[0]; }
+	const std::vector<uint8_t> &rectifiedRightMaskBytes() const { return rectMask_[1]; }
+	const srh_camera &rectifiedCamera(bool left = true) const { return rectCam_[left ? 0 : 1]; }
+	const srh_rectify_info &rectifyInfo() const { return rectInfo_; }
+
 	// The MRF stage (a USE_MRF build of the reference, twoviewstereo.cpp:240-258, 308-403, 504-570; PARITY UNPINNED, see
 	// stereo_recon_hip.h): off (default) computeDepthMaps is the WTA of the reference as it is compiled; on, each direction's
 	// depth map comes from TRW-S over the full label cost volume (srh_twoview_compute_mrf: progress 1, 2 "Optimizing...",
@@ -148,7 +172,9 @@ private:
 	bool uploadViews();
 	void setUp(int deviceOrdinal);
 	double pairCost(int kind, int x1, int y1, int x2, int y2, bool fromLeft);
-	void fetchWtaOutputs();
+	void fetchWtaOutputs(int leftSlot = 0, int rightSlot = 1);
+	bool rectifyViews();
+	bool unrectifyMaps();
 	void colorize(const DepthMap &d, Image &out) const;
 	void colorFromDepth(double depth, uint8_t rgb[3]) const;
 
@@ -174,6 +200,13 @@ private:
 	bool useSgm = false;
 	srh_twoview_sgm_params sgmParams_;
 	srh_sgm_info sgmInfo_[2];
+	bool rectifyOn = false, rectified_ = false;
+	srh_rectify_params rectParams_;
+	srh_rectify_info rectInfo_;
+	srh_camera rectCam_[2];
+	DepthMap rectDepth_[2];
+	Image rectImage_[2];
+	std::vector<uint8_t> rectMask_[2];
 	srh_context *ctx_;
 	std::string error_;
 };

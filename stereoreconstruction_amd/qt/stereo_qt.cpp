@@ -128,6 +128,9 @@ TwoViewStereo::TwoViewStereo(CameraPtr leftView_, QImage left_, QImage leftMask_
 	mrfInfo_[0] = mrfInfo_[1] = srh_mrf_info();
 	srh_twoview_sgm_params_defaults(&sgmParams_);
 	sgmInfo_[0] = sgmInfo_[1] = srh_sgm_info();
+	srh_rectify_params_defaults(&rectParams_);
+	rectInfo_ = srh_rectify_info();
+	rectCam_[0] = rectCam_[1] = srh_camera();
 	if (srh_create(deviceOrdinal, &ctx_) != SRH_OK) { error_ = srh_last_error(); ctx_ = nullptr; }
 }
 
@@ -189,25 +192,49 @@ std::vector<std::array<double, 3> > TwoViewStereo::curveOfPixel(int x, int y, bo
 	return curve;
 }
 
-// the kept by-products of both passes (slot 0: the left map's, slot 1: the right map's); empty when nothing was kept
-void TwoViewStereo::fetchWtaOutputs() {
+// the kept by-products of both passes (leftSlot: the left map's, rightSlot: the right map's -- 0 and 1, or the rectified
+// views' slots); empty when nothing was kept
+void TwoViewStereo::fetchWtaOutputs(int leftSlot, int rightSlot) {
 	for (int k = 0; k < 2; ++k) { winners_[k].clear(); runners_[k].clear(); minCosts_[k].clear(); secondCosts_[k].clear(); }
 	if (!ctx_ || !wtaFlags) return;
 	for (int k = 0; k < 2; ++k) {
+		const int slot = k == 0 ? leftSlot : rightSlot;
 		int flags = 0, w = 0, h = 0;
-		if (srh_view_wta_outputs_state(ctx_, k, &flags, nullptr) != SRH_OK || srh_view_size(ctx_, k, &w, &h) != SRH_OK) { error_ = srh_last_error(); return; }
+		if (srh_view_wta_outputs_state(ctx_, slot, &flags, nullptr) != SRH_OK || srh_view_size(ctx_, slot, &w, &h) != SRH_OK) { error_ = srh_last_error(); return; }
 		if (!(flags & SRH_WTA_WINNERS)) continue;
 		const size_t n = static_cast<size_t>(w)*h;
 		const bool costs = (flags & SRH_WTA_COSTS) != 0;
 		winners_[k].resize(2*n); runners_[k].resize(2*n);
 		if (costs) { minCosts_[k].resize(n); secondCosts_[k].resize(n); }
-		if (srh_view_wta_outputs(ctx_, k, winners_[k].data(), runners_[k].data(), costs ? minCosts_[k].data() : nullptr,
+		if (srh_view_wta_outputs(ctx_, slot, winners_[k].data(), runners_[k].data(), costs ? minCosts_[k].data() : nullptr,
 		                         costs ? secondCosts_[k].data() : nullptr) != SRH_OK) {
 			error_ = srh_last_error();
 			winners_[k].clear(); runners_[k].clear(); minCosts_[k].clear(); secondCosts_[k].clear();
 			return;
 		}
 	}
+}
+
+// setRectify(true): slots 0, 1 (uploaded) warped into slots 2, 3, and the rectified products of the views kept.  false: the
+// library refused the pair (lastError() says why) -- nothing is rectified and the rectified products are empty.
+bool TwoViewStereo::rectifyViews() {
+	rectInfo_ = srh_rectify_info();
+	for (int k = 0; k < 2; ++k) { rectDepth_[k].clear(); rectImage_[k] = QImage(); rectCam_[k] = srh_camera(); }
+	if (srh_rectify_cameras(&leftCam, &rightCam, left.w, left.h, params_.image_scale, &rectParams_, &rectCam_[0], &rectCam_[1]) != SRH_OK ||
+	    srh_twoview_rectify(ctx_, 0, 1, 2, 3, &params_, &rectParams_, &rectInfo_) != SRH_OK) {
+		error_ = srh_last_error();
+		rectCam_[0] = rectCam_[1] = srh_camera();
+		return false;
+	}
+	for (int k = 0; k < 2; ++k) {
+		int w = 0, h = 0;
+		if (srh_view_size(ctx_, 2 + k, &w, &h) != SRH_OK) { error_ = srh_last_error(); return false; }
+		std::vector<unsigned char> rgba(static_cast<size_t>(w)*h*4);
+		if (srh_view_image_download(ctx_, 2 + k, rgba.data(), nullptr) != SRH_OK) { error_ = srh_last_error(); return false; }
+		rectImage_[k] = QImage(rgba.data(), w, h, 4*w, QImage::Format_RGBA8888).copy();      // (deep copy: `rgba` goes away)
+		rectDepth_[k].assign(static_cast<size_t>(w)*h, std::numeric_limits<double>::quiet_NaN());
+	}
+	return true;
 }
 
 void TwoViewStereo::computeDepthMaps() {
@@ -223,9 +250,13 @@ void TwoViewStereo::computeDepthMaps() {
 	if (srh_set_option(ctx_, "wta_outputs", wtaFlags) != SRH_OK) { error_ = srh_last_error(); return; }
 	mrfInfo_[0] = mrfInfo_[1] = srh_mrf_info();
 	sgmInfo_[0] = sgmInfo_[1] = srh_sgm_info();
-	if (useMrf || useSgm) {
-		// a USE_MRF build, or the semi-global aggregation: the library sequences the run and reports the steps
-		// (1, 2, 3, 4, 5, [6, 7,] 8) through its hook
+	// setRectify: the pipeline runs on the rectified views (slots 2, 3) into the rectified maps; a refused pair runs as it is
+	rectified_ = rectifyOn && rectifyViews();
+	if (useMrf || useSgm || rectified_) {
+		// a USE_MRF build, the semi-global aggregation, or a rectified pair: the library sequences the run and reports the
+		// steps (1, 2, 3, 4, 5, [6, 7,] 8) through its hook
+		const int ls = rectified_ ? 2 : 0, rs = rectified_ ? 3 : 1;
+		double *dl = rectified_ ? rectDepth_[0].data() : computedDepthLeft.data(), *dr = rectified_ ? rectDepth_[1].data() : computedDepthRight.data();
 		cancelWord_ = isCancelled() ? 1 : 0;
 		srh_set_hooks(ctx_, &cancelWord_, relayToTwoView, this);
 		srh_set_option(ctx_, "filter_invalid", filterFlags);
@@ -236,14 +267,19 @@ void TwoViewStereo::computeDepthMaps() {
 			srh_set_hooks(ctx_, nullptr, nullptr, nullptr);
 			return;
 		}
-		const int rc = useSgm ? srh_twoview_compute_sgm(ctx_, 0, 1, &params_, &sgmParams_, computedDepthLeft.data(), computedDepthRight.data(), sgmInfo_)
-		                      : srh_twoview_compute_mrf(ctx_, 0, 1, &params_, &mrfParams_, computedDepthLeft.data(), computedDepthRight.data(), mrfInfo_);
+		const int rc = useSgm ? srh_twoview_compute_sgm(ctx_, ls, rs, &params_, &sgmParams_, dl, dr, sgmInfo_)
+		             : useMrf ? srh_twoview_compute_mrf(ctx_, ls, rs, &params_, &mrfParams_, dl, dr, mrfInfo_)
+		                      : srh_twoview_compute(ctx_, ls, rs, &params_, dl, dr);
 		srh_set_option(ctx_, "filter_invalid", 0);
 		srh_set_option(ctx_, "speckle_min_size", 0);
 		srh_set_hooks(ctx_, nullptr, nullptr, nullptr);
 		if (rc == SRH_E_CANCELLED) return;
 		if (rc != SRH_OK) { error_ = srh_last_error(); return; }
-		fetchWtaOutputs();                                  // (no scan made these maps: the vectors come back empty)
+		fetchWtaOutputs(ls, rs);                            // (MRF / SGM: no scan made these maps, the vectors come back empty)
+		if (rectified_ &&                                   // the rectified maps into the views the caller handed in
+		    (srh_view_depth_unrectify(ctx_, 2, 0, &params_, nullptr) != SRH_OK || srh_view_depth_unrectify(ctx_, 3, 1, &params_, nullptr) != SRH_OK ||
+		     srh_view_depth_download(ctx_, 0, computedDepthLeft.data()) != SRH_OK ||
+		     srh_view_depth_download(ctx_, 1, computedDepthRight.data()) != SRH_OK)) { error_ = srh_last_error(); return; }
 		resultLeft = colorize(computedDepthLeft, left.w, left.h);
 		resultRight = colorize(computedDepthRight, right.w, right.h);
 		return;

@@ -164,6 +164,26 @@ public:
 	srh_twoview_sgm_params &sgmParams() { return sgmParams_; }     // smoothness term 1 / 2 / 0.25, path_mask 0xFF
 	// what the aggregation of the last computeDepthMaps reported for the left / right map (paths 0: none ran)
 	const srh_sgm_info &sgmInfo(bool left = true) const { return sgmInfo_[left ? 0 : 1]; }
+
+	// Rectification (NOT IN THE REFERENCE; stereo_recon_hip.h): off (default) nothing changes.  On, the views
+	// are warped onto a rectified pair of cameras (srh_twoview_rectify with rectifyParams(), slots 2, 3), the whole configured
+	// pipeline -- WTA or SGM or MRF, cross-check, speckles, hole filling; sequenced by the library, which reports the steps
+	// through its hook -- runs on the rectified pair, where a verged, distorted pair gets the row-aligned dense plan, and
+	// both depth maps come back (srh_view_depth_unrectify): leftDepths(), rightDepths(), leftDepthMap() and rightDepthMap()
+	// stay in the views the caller handed in.  The rectified depth maps (z along the rectified axis), images and cameras, of
+	// rectifyParams().out_w x out_h pixels (0: the left image's size), are kept beside them.  The WTA by-products of
+	// setKeepWtaOutputs, when kept, are in RECTIFIED coordinates.  A pair the library refuses to rectify (a refractive
+	// camera, a baseline along the viewing direction) sets lastError() and runs unrectified: rectified() says false.
+	void setRectify(bool on) { rectifyOn = on; }
+	bool rectify() const { return rectifyOn; }
+	srh_rectify_params &rectifyParams() { return rectParams_; }
+	bool rectified() const { return rectified_; }
+	const DepthMap &rectifiedLeftDepths() const { return rectDepth_[0]; }
+	const DepthMap &rectifiedRightDepths() const { return rectDepth_[1]; }
+	QImage rectifiedLeftImage() const { return rectImage_[0]; }
+	QImage rectifiedRightImage() const { return rectImage_[1]; }
+	const srh_camera &rectifiedCamera(bool left = true) const { return rectCam_[left ? 0 : 1]; }
+	const srh_rectify_info &rectifyInfo() const { return rectInfo_; }
 	void relayProgress(int step, const char *stage);       // (the library's progress hook lands here)
 
 public: // Task implementation continued: public in the reference as well (stereo/twoviewstereo.hpp:50-52)
@@ -184,7 +204,8 @@ protected:
 
 private:
 	double pairCost(int kind, int x1, int y1, int x2, int y2, bool fromLeft);
-	void fetchWtaOutputs();
+	void fetchWtaOutputs(int leftSlot = 0, int rightSlot = 1);
+	bool rectifyViews();
 	QImage colorize(const DepthMap &d, int w, int h) const;
 	CameraPtr leftView, rightView;
 	srh_camera leftCam, rightCam;                          // snapshots taken by the constructor (srq::cameraInfo)
@@ -209,7 +230,13 @@ private:
 	bool useSgm = false;
 	srh_twoview_sgm_params sgmParams_;
 	srh_sgm_info sgmInfo_[2];
-	volatile int cancelWord_ = 0;                          // what the library polls: set from isCancelled() at progress steps
+	bool rectifyOn = false, rectified_ = false;
+	srh_rectify_params rectParams_;
+	srh_rectify_info rectInfo_;
+	srh_camera rectCam_[2];
+	DepthMap rectDepth_[2];
+	QImage rectImage_[2];
+	volatile int cancelWord_ = 0;                         // what the library polls: set from isCancelled() at progress steps
 	srh_context *ctx_;
 	mutable bool uploaded_ = false;                        // views resident on the device (epipolarCurve before computeDepthMaps)
 	bool uploadViews() const;
