@@ -7,6 +7,7 @@
 
 #include "stereo_recon_hip.h"
 #include "srh_wta.hpp"
+#include "srh_stripframe.hpp"
 
 namespace srh {
 
@@ -54,16 +55,8 @@ __host__ __device__ inline size_t wimg_offset(int W, int R, int band_row, int x)
 	const size_t tile = (size_t)band_row*((W + SRH_WTILE - 1)/SRH_WTILE) + x/SRH_WTILE;
 	return tile*SRH_WTILE*(size_t)((2*R + 1)*wimg_wp(R)) + (size_t)(x % SRH_WTILE)*wimg_wp(R);
 }
-// NaN-bordered copy of a view's gray_tv plane (and zero-bordered copy of its "window fully usable" plane):
-// every row piece a tile stages lies inside the allocation, so the LDS-DMA needs no bounds handling and the
-// border taps arrive as NaN (= "tap skipped", vectorimage.cpp:115-119,129-155).
-#define SRH_PADL 8
-#define SRH_PADR 344          // >= CHUNK + R + NCB + 2 of the strip kernel
-#define SRH_PADY 8
-__host__ __device__ inline int padded_stride(int w) { return w + SRH_PADL + SRH_PADR; }
-__host__ __device__ inline size_t padded_size(int w, int h) { return (size_t)padded_stride(w)*(size_t)(h + 2*SRH_PADY); }
-// candidate column range of a reference pixel on its own row of the other view (empty: hi < lo)
-struct PixRange { int32_t lo, hi; };
+// The NaN-bordered planes the strip kernels stage from (SRH_PADL / SRH_PADR / SRH_PADY, padded_stride, padded_size) and
+// PixRange, a pixel's candidate column range: srh_stripframe.hpp (host-clean: the CPU suite compiles it)
 
 // ---- certified fused arithmetic (option "arith" = 3): CertBound, cert_bound(), cert_sure, cert_pixel_exact and the scans'
 // doubt tests live in srh_wta.hpp (host-clean: the CPU suite compiles it), with the derivation; DESIGN.md section 2b

@@ -1,6 +1,7 @@
 // srh_sad_strip.hip -- TwoViewStereo::cost_sad (stereo/twoviewstereo.cpp:864-905) for row-aligned rigs as a PERSISTENT
-// kernel that fills the dense plan's cost rows (option "sad_dense"): the structure of
-// twoview_strip_cost_kernel (srh_strip.hip, 4-wave form), the sums of twoview_rows_sad_kernel (srh_sad.hip).
+// kernel that fills the dense plan's cost rows (option "sad_dense"): the frame of
+// twoview_strip_cost_kernel's 4-wave form (srh_stripframe.hpp: shared, not copied), the sums of twoview_rows_sad_kernel
+// (srh_sad.hip).
 //
 //   * a workgroup owns a vertical strip of one tile column (work items from the ticket counter, tall items first) and
 //     keeps the rows of both views in an LDS ring of 2R+2 slots: one new row per view and tile;
@@ -24,52 +25,29 @@
 
 namespace srh {
 
-#define SS_TP 32                       // pixels per tile (= SRH_WTILE)
-#define SS_NCB 8                       // candidate columns per block
-#define SS_G 8                         // block lanes per pixel
+#define SS_G 8                        // block lanes per pixel
 #define SS_NT 256                      // threads: 4 waves, 8 pixels x 8 block lanes each
-#define SS_CHUNK 320                   // candidate columns a tile can hold in LDS (= strip_chunk_columns())
 
-typedef __attribute__((address_space(3))) void ss_lds_void;
-typedef __attribute__((address_space(1))) const void ss_gbl_void;
-
-// ------------------------------------------------------------------ padded planes
-// out[(y+PADY)*SP + x+PADL] = gray(x, y) where the mask is WHITE, NaN elsewhere and outside the image: cost_sad's
-// other-side tap (right.pixel() behind rightMask; sad_tap, srh_walk.hpp)
-__global__ void padded_gray_kernel(const double *__restrict__ gray, const uint8_t *__restrict__ mask, int W, int H,
-                                   double *__restrict__ out)
-{
-	const int SP = padded_stride(W), HP = H + 2*SRH_PADY;
-	const size_t n = (size_t)SP*HP;
-	const double nan = __builtin_nan("");
-	for (size_t k = (size_t)blockIdx.x*blockDim.x + threadIdx.x; k < n; k += (size_t)gridDim.x*blockDim.x) {
-		const int x = (int)(k % (size_t)SP) - SRH_PADL, y = (int)(k / (size_t)SP) - SRH_PADY;
-		const bool in = x >= 0 && y >= 0 && x < W && y < H;
-		out[k] = (in && mask[(size_t)y*W + x] == 1) ? gray[(size_t)y*W + x] : nan;
+// ------------------------------------------------------------------ padded planes (padded_raster_kernel, srh_stripframe.hpp)
+// gray(x, y) where the mask is WHITE, NaN elsewhere and outside the image: cost_sad's other-side tap (right.pixel()
+// behind rightMask; sad_tap, srh_walk.hpp)
+struct PaddedGray {
+	const double *gray; const uint8_t *mask; int W;
+	__device__ double operator()(int x, int y, bool in) const {
+		return (in && mask[(size_t)y*W + x] == 1) ? gray[(size_t)y*W + x] : __builtin_nan("");
 	}
-}
-
+};
 void launch_padded_gray(hipStream_t st, const double *gray, const uint8_t *mask, int w, int h, double *out) {
-	size_t n = padded_size(w, h);
-	size_t b = (n + 255)/256; if (b > 4096) b = 4096;
-	hipLaunchKernelGGL(padded_gray_kernel, dim3((unsigned)b), dim3(256), 0, st, gray, mask, w, h, out);
+	launch_padded_raster(st, w, h, out, PaddedGray{ gray, mask, w });
 }
 
-// zero-bordered copy of a W x H byte plane (sad_full_window_kernel's) on the padded raster
-__global__ void padded_bytes_kernel(const uint8_t *__restrict__ in, int W, int H, uint8_t *__restrict__ out)
-{
-	const int SP = padded_stride(W), HP = H + 2*SRH_PADY;
-	const size_t n = (size_t)SP*HP;
-	for (size_t k = (size_t)blockIdx.x*blockDim.x + threadIdx.x; k < n; k += (size_t)gridDim.x*blockDim.x) {
-		const int x = (int)(k % (size_t)SP) - SRH_PADL, y = (int)(k / (size_t)SP) - SRH_PADY;
-		out[k] = (x >= 0 && y >= 0 && x < W && y < H) ? in[(size_t)y*W + x] : 0;
-	}
-}
-
+// zero-bordered copy of a W x H byte plane (sad_full_window_kernel's)
+struct PaddedBytes {
+	const uint8_t *in; int W;
+	__device__ uint8_t operator()(int x, int y, bool inside) const { return inside ? in[(size_t)y*W + x] : 0; }
+};
 void launch_padded_bytes(hipStream_t st, const uint8_t *in, int w, int h, uint8_t *out) {
-	size_t n = padded_size(w, h);
-	size_t b = (n + 255)/256; if (b > 4096) b = 4096;
-	hipLaunchKernelGGL(padded_bytes_kernel, dim3((unsigned)b), dim3(256), 0, st, in, w, h, out);
+	launch_padded_raster(st, w, h, out, PaddedBytes{ in, w });
 }
 
 // ------------------------------------------------------------------ the kernel
@@ -82,65 +60,27 @@ struct SadStripArgs {
 	const uint8_t *oth_fullp;               // zero-bordered cost_sad "window fully usable" plane of the other view
 	double *cost; int cstride;              // cost rows, tile-transposed: ((tile*cstride) + k)*32 + pixel
 	Counters *cnt;
-	int n1, n2;                             // rows [0,n1) in 16-row items, [n1,n2) in 8-row items, the rest in 4-row items
-	int nitems;
+	StripItems items;                       // the band's work items (srh_stripframe.hpp)
 	double weight_cutoff, bad_ret, max_color_diff;
 };
 
-// work items as the NCC strip kernel cuts them: 3/4 of the rows in 16-row items, 2/3 of the rest in 8-row items, the
-// remainder in 4-row items
-static void sad_strip_items(SadStripArgs &a) {
-	a.n1 = ((a.nrows*3/4)/16)*16;
-	a.n2 = a.n1 + (((a.nrows - a.n1)*2/3)/8)*8;
-	const int nseg = a.n1/16 + (a.n2 - a.n1)/8 + (a.nrows - a.n2 + 3)/4;
-	a.nitems = nseg*((a.W + SS_TP - 1)/SS_TP);
-}
-
 template <int R>
-struct SadStripSmem {
-	static constexpr int WS = 2*R + 1;
-	static constexpr int WP = (WS + 1) & ~1;                 // taps per window row, padded even
-	static constexpr int WPIX = WS*WP;                       // doubles per pixel window
-	static constexpr int RW = SS_CHUNK + 2*R + SS_NCB + 2;   // staged width of the other view's rows (even)
-	static constexpr int LW = (SS_TP + 2*R + 1) & ~1;        // staged width of the reference rows (even)
-	static constexpr int NS = WS + 1;                        // row slots of the rings: the window's rows + the next one
-	static constexpr int FW = (RW + 4 + 15) & ~15;           // bytes of a staged "full" row piece (dword granules + slack)
-	static constexpr int NBMAX = SS_CHUNK/SS_NCB + 1;        // 8-column blocks a pixel can have
-	alignas(16) double w[WS][SS_TP][WP];       // LDS image of the windows: [row][pixel][tap]; per tile, a skipped tap's weight -> +0.0
-	alignas(16) double rt[NS][RW];             // ring: the other view's rows (NaN: tap unusable)
-	alignas(16) double lt[NS][LW];             // ring: the reference rows (NaN: tap unusable)
-	alignas(16) double l0[WS][LW];             // the current window's reference rows, NaN -> 0.0 (by window row, not ring slot)
-	alignas(16) PixRange pr[2][SS_TP];
-	alignas(16) unsigned char full[2][FW];
-	unsigned short okm[WS][SS_TP];             // bit col: tap (row, col) of the pixel counts on the reference side
-	unsigned short glist[SS_TP*NBMAX];         // select-form work list: pixel*64 + block
+struct SadStripSmem : StripGeom<R> {
+	typedef StripGeom<R> G;                    // the tile and staging geometry (srh_stripframe.hpp)
+	alignas(16) double w[G::WS][STRIP_TP][G::WP];    // LDS image of the windows: [row][pixel][tap]; per tile, a skipped tap's weight -> +0.0
+	alignas(16) double rt[G::NS][G::RW];       // ring: the other view's rows (NaN: tap unusable)
+	alignas(16) double lt[G::NS][G::LW];       // ring: the reference rows (NaN: tap unusable)
+	alignas(16) double l0[G::WS][G::LW];       // the current window's reference rows, NaN -> 0.0 (by window row, not ring slot)
+	alignas(16) PixRange pr[2][STRIP_TP];
+	alignas(16) unsigned char full[2][G::FW];
+	unsigned short okm[G::WS][STRIP_TP];       // bit col: tap (row, col) of the pixel counts on the reference side
+	unsigned short glist[STRIP_TP*G::NBMAX];   // select-form work list: pixel*64 + block
 	int glist_n;
 	int item;
-	static_assert(NBMAX <= 64, "work-list entry = pixel*64 + block");
-	static_assert(RW % 2 == 0 && LW % 2 == 0 && WP % 2 == 0, "16-byte rows");
-	static_assert(RW*8 <= 3*1024, "three pieces per row of the other view");
-	static_assert(RW - R + 4 <= SRH_PADR + 1, "padded planes cover every staged piece");
-	static_assert(R + 1 <= SRH_PADY, "padded planes cover the rows above and below the image");
+	static_assert(G::NBMAX <= 64, "work-list entry = pixel*64 + block");
 };
 
 static_assert(sizeof(SadStripSmem<5>) <= 80*1024 && sizeof(SadStripSmem<2>) <= 80*1024, "two workgroups share a CU's 160 KB of LDS");
-
-// lanes [0, nbytes/16) of the wave copy 16 bytes each from src + 16*lane to LDS dst + 16*lane, 1 KiB per instruction
-__device__ __forceinline__ void ss_dma16(const void *src, void *dst, int nbytes, int lane) {
-	for (int off = 0; off < nbytes; off += 1024) {
-		if (off + lane*16 < nbytes)
-			__builtin_amdgcn_global_load_lds((ss_gbl_void *)((const char *)src + off + lane*16),
-			                                 (ss_lds_void *)((char *)dst + off), 16, 0, 0);
-	}
-}
-// the same in 4-byte granules (sources that are only 4-byte aligned)
-__device__ __forceinline__ void ss_dma4(const void *src, void *dst, int nbytes, int lane) {
-	for (int off = 0; off < nbytes; off += 256) {
-		if (off + lane*4 < nbytes)
-			__builtin_amdgcn_global_load_lds((ss_gbl_void *)((const char *)src + off + lane*4),
-			                                 (ss_lds_void *)((char *)dst + off), 4, 0, 0);
-	}
-}
 
 // One 8-column block of pixel `pi` in the select form (the select form of twoview_rows_sad_kernel, the rows taken from
 // the rings): every tap guarded, a skipped tap adds +0.0, numPixels and totalWeight per candidate.  Candidates whose bit
@@ -150,7 +90,7 @@ __device__ __forceinline__ void sad_strip_select_block(const SadStripSmem<R> &S,
                                                     double *__restrict__ dst, double bad_ret, double mcd)
 {
 	typedef SadStripSmem<R> Smem;
-	constexpr int WS = Smem::WS, NS = Smem::NS, NCB = SS_NCB, NR = NCB + 2*R;
+	constexpr int WS = Smem::WS, NS = Smem::NS, NCB = STRIP_NCB, NR = NCB + 2*R;
 	double s[NCB], t[NCB];
 	int np[NCB];
 #pragma unroll
@@ -159,7 +99,7 @@ __device__ __forceinline__ void sad_strip_select_block(const SadStripSmem<R> &S,
 	for (int row = 0; row < WS; ++row) {
 		const unsigned okm = S.okm[row][pi];
 		if (okm == 0) continue;                                // (no tap of this window row counts: every term a skipped +0.0)
-		const int sl = s0 + row >= NS ? s0 + row - NS : s0 + row;
+		const int sl = ring_slot(s0, row, NS);
 		double rr[NR];
 		bool rv[NR];
 		const double2 *rp = reinterpret_cast<const double2 *>(&S.rt[sl][rc]);
@@ -184,7 +124,7 @@ __device__ __forceinline__ void sad_strip_select_block(const SadStripSmem<R> &S,
 	}
 #pragma unroll
 	for (int j = 0; j < NCB; ++j)
-		if ((store >> j) & 1u) dst[(ptrdiff_t)j*SS_TP] = (np[j] <= 4 || t[j] <= 1e-10) ? bad_ret : s[j] / t[j];
+		if ((store >> j) & 1u) dst[(ptrdiff_t)j*STRIP_TP] = (np[j] <= 4 || t[j] <= 1e-10) ? bad_ret : s[j] / t[j];
 }
 
 template <int R>
@@ -192,8 +132,8 @@ __global__ __launch_bounds__(SS_NT, 2)
 void twoview_strip_sad_kernel(const SadStripArgs A)
 {
 	typedef SadStripSmem<R> Smem;
-	constexpr int WS = Smem::WS, WP = Smem::WP, WPIX = Smem::WPIX, RW = Smem::RW, LW = Smem::LW, NS = Smem::NS;
-	constexpr int NCB = SS_NCB, CHUNK = SS_CHUNK, G = SS_G, NT = SS_NT;
+	constexpr int WS = Smem::WS, WP = Smem::WP, WPIX = Smem::WPIX, LW = Smem::LW, NS = Smem::NS;
+	constexpr int NCB = STRIP_NCB, CHUNK = STRIP_CHUNK, G = SS_G, NT = SS_NT;
 	constexpr int NR = NCB + 2*R;              // right-row values a block needs (even)
 	static_assert(NR % 2 == 0, "16-byte rows");
 	extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -206,7 +146,7 @@ void twoview_strip_sad_kernel(const SadStripArgs A)
 	const int i = wv*8 + (lane & 7);             // pixel within the tile: the wave owns pixels 8*wv .. 8*wv + 7
 	const int g = lane >> 3;                     // block lane of the pixel
 	const int W = A.W;
-	const int tiles_per_row = (W + SS_TP - 1)/SS_TP;
+	const int tiles_per_row = (W + STRIP_TP - 1)/STRIP_TP;
 	const int SP = padded_stride(W);
 	const double mcd = A.max_color_diff;
 	const bool fast_ok = mcd == mcd;             // (fmin and the reference's select agree for any non-NaN bound; srh_sad.hip)
@@ -214,46 +154,32 @@ void twoview_strip_sad_kernel(const SadStripArgs A)
 
 	for (;;) {
 		// ---- next work item: (row segment, tile column); tall segments first, so the tail of the launch is short
-		if (tid == 0) S.item = (int)atomicAdd(&A.cnt->strip_ticket, 1u);
-		__syncthreads();                           // also: every wave has left the previous item's last tile
-		const int item = __builtin_amdgcn_readfirstlane(S.item);
-		if (item >= A.nitems) break;
-		const int seg = item / tiles_per_row, tx = item - seg*tiles_per_row;
-		int ya, nh;
-		{
-			const int s16 = A.n1 >> 4, s8 = (A.n2 - A.n1) >> 3;
-			if (seg < s16) { ya = seg*16; nh = 16; }
-			else if (seg < s16 + s8) { ya = A.n1 + (seg - s16)*8; nh = 8; }
-			else { ya = A.n2 + (seg - s16 - s8)*4; nh = 4; }
-			if (ya + nh > A.nrows) nh = A.nrows - ya;
-		}
-		const int x0 = tx*SS_TP;
+		const int item = strip_draw_item(&A.cnt->strip_ticket, &S.item, tid);
+		if (item >= A.items.nitems) break;
+		int tx, ya, nh;
+		A.items.segment(item, tiles_per_row, A.nrows, tx, ya, nh);
+		const int x0 = tx*STRIP_TP;
 		const int x = x0 + i;
 		int cs = 0, rowbase = 0;                   // staging origin (column, even) and the image row held by slot 0
 
 		// one tile's own inputs (nothing here depends on the staging origin): ranges, windows
 		auto issue_tile_inputs = [&](int r, int buf, bool ranges, bool windows) {
 			const size_t px0 = (size_t)r*W + x0;
-			if (ranges && wv == 1) ss_dma4(A.prange + px0, &S.pr[buf][0], SS_TP*8, lane);
+			if (ranges && wv == 1) strip_dma4(A.prange + px0, &S.pr[buf][0], STRIP_TP*8, lane);
 			if (windows) {
 				// each wave its own pixels' windows (8 pixels x WP taps of every window row): nobody else touches them
 				// outside the select form
-				const double *wt = A.wimg + ((size_t)r*tiles_per_row + tx)*(size_t)(SS_TP*WPIX);
+				const double *wt = A.wimg + ((size_t)r*tiles_per_row + tx)*(size_t)(STRIP_TP*WPIX);
 				for (int a = 0; a < WS; ++a)
-					ss_dma16(wt + (size_t)a*(SS_TP*WP) + wv*8*WP, &S.w[a][wv*8][0], 8*WP*8, lane);
+					strip_dma16(wt + (size_t)a*(STRIP_TP*WP) + wv*8*WP, &S.w[a][wv*8][0], 8*WP*8, lane);
 			}
 		};
-		// image row `yy` of both views into ring slot `sl`
+		// image row `yy` of both views into ring slot `sl`; "full" bytes of row `fy` into full[fb] (the last wave)
 		auto issue_row = [&](int yy, int sl) {
-			const double *src = A.oth_grayp + (size_t)(yy + SRH_PADY)*SP + (cs - R + SRH_PADL);
-			if (wv < 3) { if (wv*1024 + lane*16 < RW*8) __builtin_amdgcn_global_load_lds((ss_gbl_void *)((const char *)src + wv*1024 + lane*16),
-			                                                                              (ss_lds_void *)((char *)&S.rt[sl][0] + wv*1024), 16, 0, 0); }
-			else ss_dma16(A.ref_tvp + (size_t)(yy + SRH_PADY)*SP + (x0 - R + SRH_PADL), &S.lt[sl][0], LW*8, lane);
+			strip_request_row<R>(A.oth_grayp, A.ref_tvp, SP, yy, cs, x0, &S.rt[sl][0], &S.lt[sl][0], wv, lane);
 		};
-		// "full" bytes [cs, cs + RW) of row fy, from the 4-byte granule that holds the first one
 		auto issue_full = [&](int fy, int fb) {
-			const size_t a0 = (size_t)(fy + SRH_PADY)*SP + (size_t)(cs + SRH_PADL);
-			if (wv == 3) ss_dma4(A.oth_fullp + (a0 & ~(size_t)3), &S.full[fb][0], (RW + 4 + 3) & ~3, lane);
+			if (wv == 3) strip_request_full<R>(A.oth_fullp, SP, fy, cs, &S.full[fb][0], lane);
 		};
 
 		bool first = true;
@@ -267,25 +193,16 @@ void twoview_strip_sad_kernel(const SadStripArgs A)
 			__builtin_amdgcn_s_barrier();
 
 			// ---- B: the tile's candidate ranges (every wave works out the union for itself: 32 values)
-			int cmin, cmax, cmin_raw;
+			int cmax, cmin_raw;
 			{
 				const int pi = lane & 31;
-				const PixRange q = CS.pr[cur][pi];
-				int lo = q.lo, hi = q.hi;
-				if (x0 + pi >= W) { lo = 0; hi = -1; }
-				int mn = hi >= lo ? lo : 2147483647, mx = hi >= lo ? hi : -2147483647;
-#pragma unroll
-				for (int d = 16; d >= 1; d >>= 1) {
-					const int on = __shfl_xor(mn, d, 64), ox = __shfl_xor(mx, d, 64);
-					mn = on < mn ? on : mn; mx = ox > mx ? ox : mx;
-				}
-				cmin_raw = __builtin_amdgcn_readfirstlane(mn);
-				cmax = __builtin_amdgcn_readfirstlane(mx);
-				cmin = cmin_raw & ~1;
+				int lo, hi;
+				strip_pixel_range(CS.pr[cur][pi], x0 + pi < W, lo, hi);
+				tile_range_union(lo, hi, cmin_raw, cmax);
 			}
+			const int cmin = cmin_raw & ~1;
 			const bool any = cmin_raw <= cmax;
-			// (re)stage the rings when the strip starts or the ranges have moved outside the staged columns
-			if (first || (any && (cmin < cs || cmax > cs + CHUNK - 1))) {
+			if (needs_restage(first, any, cmin, cmax, cs)) {
 				if (!first) __builtin_amdgcn_s_barrier();          // (a restage in mid-strip: nobody reads the rings any more)
 				cs = any ? cmin : 0;
 				rowbase = y - R;
@@ -294,11 +211,7 @@ void twoview_strip_sad_kernel(const SadStripArgs A)
 				asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 				__builtin_amdgcn_s_barrier();
 			}
-			if (any && cmax > cs + CHUNK - 1) {
-				// a candidate range wider than the chunk: not this kernel's case (the host falls back)
-				if (tid == 0) atomicAdd(&A.cnt->strip_overflow, 1ull);
-				cmax = cs + CHUNK - 1;
-			}
+			strip_clamp_to_chunk(any, cs, cmax, tid, &A.cnt->strip_overflow);
 			first = false;
 			const int s0 = (y - R - rowbase) % NS;                   // ring slot of the window's first row
 
@@ -306,7 +219,7 @@ void twoview_strip_sad_kernel(const SadStripArgs A)
 			// skipped tap's weight becomes +0.0 and its gray value 0.0, so that it adds 0 * min(|0 - r|, MAX) = +0.0 in
 			// the fast form; a bit per tap for the select form.  Each wave its own pixels' windows.
 			for (int row = g; row < WS; row += G) {
-				const int sl = s0 + row >= NS ? s0 + row - NS : s0 + row;
+				const int sl = ring_slot(s0, row, NS);
 				unsigned m = 0;
 #pragma unroll
 				for (int col = 0; col < WS; ++col) {
@@ -319,7 +232,7 @@ void twoview_strip_sad_kernel(const SadStripArgs A)
 			}
 			for (int k = tid; k < WS*LW; k += NT) {
 				const int row = k / LW, cc = k - row*LW;
-				const int sl = s0 + row >= NS ? s0 + row - NS : s0 + row;
+				const int sl = ring_slot(s0, row, NS);
 				const double v = CS.lt[sl][cc];
 				S.l0[row][cc] = v == v ? v : 0.0;
 			}
@@ -331,8 +244,7 @@ void twoview_strip_sad_kernel(const SadStripArgs A)
 				issue_full(y + 1, nxt);
 				issue_tile_inputs(r + 1, nxt, true, false);
 			}
-			const int foff = (int)(((size_t)(y + SRH_PADY)*SP + (size_t)(cs + SRH_PADL)) & 3);   // first byte inside its granule
-			const unsigned char *rfull = &CS.full[cur][foff];
+			const unsigned char *rfull = &CS.full[cur][full_offset(y, SP, cs)];
 
 			// ---- does any candidate of the tile need the select form?  (uniform: every wave looks at the whole tile)
 			bool need_select = false;
@@ -349,9 +261,7 @@ void twoview_strip_sad_kernel(const SadStripArgs A)
 			// ---- this lane's pixel
 			int e_min, e_max;
 			{
-				const PixRange q = CS.pr[cur][i];
-				e_min = q.lo; e_max = q.hi;
-				if (x >= W) { e_min = 0; e_max = -1; }
+				strip_pixel_range(CS.pr[cur][i], x < W, e_min, e_max);
 				if (e_max > e_min + A.cstride - 1) e_max = e_min + A.cstride - 1;   // (pixel_range_kernel never leaves more)
 			}
 			const size_t tile = (size_t)r*tiles_per_row + tx;
@@ -367,11 +277,9 @@ void twoview_strip_sad_kernel(const SadStripArgs A)
 					npx += __builtin_popcount((unsigned)CS.okm[row][i]);
 				}
 				const bool bad_full = npx <= 4 || tw <= 1e-10;
-				const int lo = e_min > cs ? e_min : cs;
-				const int hi = e_max < cs + CHUNK - 1 ? e_max : cs + CHUNK - 1;
-				const int lo_e = lo & ~1;                                // blocks start on even columns (>= cs)
-				const int nblocks = hi >= lo ? (hi - lo_e + NCB)/NCB : 0;
-				double *crow = A.cost + tile*(size_t)A.cstride*SS_TP + i;
+				int lo, hi, lo_e, nblocks;
+				strip_lane_blocks<true>(e_min, e_max, cs, lo, hi, lo_e, nblocks);   // blocks start on even columns (>= cs)
+				double *crow = A.cost + tile*(size_t)A.cstride*STRIP_TP + i;
 				// phase 1: blocks of NCB candidates in the fast form
 				for (int b = g; b < (fast_ok ? nblocks : 0); b += G) {
 					const int c0 = lo_e + b*NCB;
@@ -393,7 +301,7 @@ void twoview_strip_sad_kernel(const SadStripArgs A)
 						for (int j = 0; j < NC; ++j) acc[j] = 0.0;
 #pragma unroll 1
 						for (int row = 0; row < WS; ++row) {
-							const int sl = s0 + row >= NS ? s0 + row - NS : s0 + row;
+							const int sl = ring_slot(s0, row, NS);
 							double rr[NRC], we[WP], gl[WS];
 							const double2 *rp = reinterpret_cast<const double2 *>(&CS.rt[sl][rc]);
 							const double2 *wp = reinterpret_cast<const double2 *>(&CS.w[row][i][0]);
@@ -411,7 +319,7 @@ void twoview_strip_sad_kernel(const SadStripArgs A)
 						}
 #pragma unroll
 						for (int j = 0; j < NC; ++j)
-							if ((vm >> j) & 1u) crow[(size_t)(c0 + j - e_min)*SS_TP] = bad_full ? A.bad_ret : acc[j] / tw;
+							if ((vm >> j) & 1u) crow[(size_t)(c0 + j - e_min)*STRIP_TP] = bad_full ? A.bad_ret : acc[j] / tw;
 					};
 					// a pixel's last block often holds one or two columns only (the alignment pad in front, a range of 8k + 1
 					// columns) and is a round of the block lanes all by itself: it is swept two candidates wide
@@ -425,10 +333,8 @@ void twoview_strip_sad_kernel(const SadStripArgs A)
 				if (tid == 0) S.glist_n = 0;
 				__syncthreads();
 				auto block_need = [&](int pi, int b, int &c0, int &qlo) -> unsigned {
-					const PixRange q = CS.pr[cur][pi];
-					qlo = q.lo;
-					int qhi = q.hi;
-					if (x0 + pi >= W) { qlo = 0; qhi = -1; }
+					int qhi;
+					strip_pixel_range(CS.pr[cur][pi], x0 + pi < W, qlo, qhi);
 					if (qhi > qlo + A.cstride - 1) qhi = qlo + A.cstride - 1;
 					if (qhi > cs + CHUNK - 1) qhi = cs + CHUNK - 1;
 					const int ql = qlo > cs ? qlo : cs;
@@ -442,7 +348,7 @@ void twoview_strip_sad_kernel(const SadStripArgs A)
 					}
 					return need;
 				};
-				for (int p = tid; p < SS_TP*Smem::NBMAX; p += NT) {
+				for (int p = tid; p < STRIP_TP*Smem::NBMAX; p += NT) {
 					const int pi = p / Smem::NBMAX, b = p - pi*Smem::NBMAX;
 					int c0, qlo;
 					if (block_need(pi, b, c0, qlo)) S.glist[atomicAdd(&S.glist_n, 1)] = (unsigned short)(pi*64 + b);
@@ -455,7 +361,7 @@ void twoview_strip_sad_kernel(const SadStripArgs A)
 					const unsigned store = block_need(pi, b, c0, qlo);
 					n_dev += __builtin_popcount(store);
 					sad_strip_select_block<R>(CS, s0, pi, c0 - cs, store,
-					                          A.cost + (tile*(size_t)A.cstride)*SS_TP + (ptrdiff_t)(c0 - qlo)*SS_TP + pi,
+					                          A.cost + (tile*(size_t)A.cstride)*STRIP_TP + (ptrdiff_t)(c0 - qlo)*STRIP_TP + pi,
 					                          A.bad_ret, mcd);
 				}
 				__syncthreads();     // the select form reads any pixel's window: all of it done before a window is replaced
@@ -467,33 +373,21 @@ void twoview_strip_sad_kernel(const SadStripArgs A)
 	block_count_add(&A.cnt->n_eval_device, n_dev);
 }
 
-template <int R>
-static void launch_sad_strip_variant(hipStream_t st, const SadStripArgs &a, int num_cus)
-{
-	typedef SadStripSmem<R> Smem;
-	const size_t lds = sizeof(Smem);
-	(void)hipFuncSetAttribute((const void *)twoview_strip_sad_kernel<R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-	int grid = num_cus*2;
-	if (grid > a.nitems) grid = a.nitems;
-	if (grid < 1) grid = 1;
-	hipLaunchKernelGGL((twoview_strip_sad_kernel<R>), dim3((unsigned)grid), dim3(SS_NT), lds, st, a);
-}
-
 bool launch_twoview_strip_sad(hipStream_t st, int width, int height, const srh_params &P, int y0, int nrows,
                               const double *wimg, const PixRange *prange, const double *ref_tvp, const double *oth_grayp,
                               const uint8_t *oth_fullp, double *cost, int cstride, Counters *cnt, int num_cus)
 {
-	if (SS_CHUNK != strip_chunk_columns()) return false;
 	SadStripArgs a;
 	a.W = width; a.H = height; a.y0 = y0; a.nrows = nrows;
 	a.wimg = wimg; a.prange = prange;
 	a.ref_tvp = ref_tvp; a.oth_grayp = oth_grayp; a.oth_fullp = oth_fullp;
 	a.cost = cost; a.cstride = cstride; a.cnt = cnt;
 	a.weight_cutoff = P.weight_cutoff; a.bad_ret = P.bad_ret; a.max_color_diff = P.max_color_diff;
-	sad_strip_items(a);
+	a.items = StripItems::cut(nrows, width);
+	// two workgroups per compute unit
 	switch (P.window_radius) {
-	case 5: launch_sad_strip_variant<5>(st, a, num_cus); return true;
-	case 2: launch_sad_strip_variant<2>(st, a, num_cus); return true;
+	case 5: launch_strip(st, twoview_strip_sad_kernel<5>, a, sizeof(SadStripSmem<5>), SS_NT, 2, num_cus, a.items.nitems); return true;
+	case 2: launch_strip(st, twoview_strip_sad_kernel<2>, a, sizeof(SadStripSmem<2>), SS_NT, 2, num_cus, a.items.nitems); return true;
 	default: return false;
 	}
 }

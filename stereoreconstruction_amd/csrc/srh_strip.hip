@@ -34,13 +34,6 @@ __device__ int g_strip_exp_repeat = 1;
 void strip_exp_set(int repeat) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_strip_exp_repeat), &repeat, sizeof(int)); }
 #endif
 
-#define ST_TP 32                       // pixels per tile (= SRH_WTILE)
-#define ST_NCB 8                       // candidate columns per block
-#define ST_CHUNK 320                   // candidate columns a tile can hold in LDS
-#define ST_BROWS 1                     // rows per work item of the border instantiation
-
-typedef __attribute__((address_space(3))) void st_lds_void;
-typedef __attribute__((address_space(1))) const void st_gbl_void;
 typedef __attribute__((address_space(3))) volatile int st_lds_vint;
 typedef __attribute__((address_space(3))) const volatile double st_lds_vdouble;
 
@@ -48,46 +41,32 @@ typedef __attribute__((address_space(3))) const volatile double st_lds_vdouble;
 // the LDS serves at half the rate (profiles/microbench/lone_wave_issue_mi355x.txt: 32 cycles against 10-14 each).
 __device__ __forceinline__ double st_lds_read8(const double *p) { return *(st_lds_vdouble *)p; }
 
-// ------------------------------------------------------------------ padded planes
-__global__ void padded_plane_kernel(const double *__restrict__ gray_tv, int W, int H, double *__restrict__ out)
-{
-	const int SP = padded_stride(W), HP = H + 2*SRH_PADY;
-	const size_t n = (size_t)SP*HP;
-	const double nan = __builtin_nan("");
-	for (size_t k = (size_t)blockIdx.x*blockDim.x + threadIdx.x; k < n; k += (size_t)gridDim.x*blockDim.x) {
-		const int x = (int)(k % (size_t)SP) - SRH_PADL, y = (int)(k / (size_t)SP) - SRH_PADY;
-		out[k] = (x >= 0 && y >= 0 && x < W && y < H) ? gray_tv[(size_t)y*W + x] : nan;
-	}
-}
-
+// ------------------------------------------------------------------ padded planes (padded_raster_kernel, srh_stripframe.hpp)
+// gray_tv inside the image, NaN outside
+struct PaddedPlane {
+	const double *gray_tv; int W;
+	__device__ double operator()(int x, int y, bool in) const { return in ? gray_tv[(size_t)y*W + x] : __builtin_nan(""); }
+};
 void launch_padded_plane(hipStream_t st, const double *gray_tv, int w, int h, double *out) {
-	size_t n = padded_size(w, h);
-	size_t b = (n + 255)/256; if (b > 4096) b = 4096;
-	hipLaunchKernelGGL(padded_plane_kernel, dim3((unsigned)b), dim3(256), 0, st, gray_tv, w, h, out);
+	launch_padded_raster(st, w, h, out, PaddedPlane{ gray_tv, w });
 }
 
-// out[(y+PADY)*SP + x+PADL] = 1 where the whole (2R+1)^2 TwoView window centred on (x, y) is usable
-// (inside the image, every gray_tv tap valid), 0 elsewhere -- full_window_kernel (srh_list.hip) on the padded raster
-__global__ void padded_full_kernel(const double *__restrict__ gray_tv, int W, int H, int R, uint8_t *__restrict__ out)
-{
-	const int SP = padded_stride(W), HP = H + 2*SRH_PADY;
-	const size_t n = (size_t)SP*HP;
-	for (size_t k = (size_t)blockIdx.x*blockDim.x + threadIdx.x; k < n; k += (size_t)gridDim.x*blockDim.x) {
-		const int x = (int)(k % (size_t)SP) - SRH_PADL, y = (int)(k / (size_t)SP) - SRH_PADY;
+// 1 where the whole (2R+1)^2 TwoView window centred on (x, y) is usable (inside the image, every gray_tv tap valid), 0
+// elsewhere -- full_window_kernel (srh_list.hip) on the padded raster
+struct PaddedFull {
+	const double *gray_tv; int W, H, R;
+	__device__ uint8_t operator()(int x, int y, bool) const {
 		bool ok = x - R >= 0 && y - R >= 0 && x + R < W && y + R < H;
 		for (int row = -R; ok && row <= R; ++row)
 			for (int col = -R; col <= R; ++col) {
 				const double v = gray_tv[(size_t)(y + row)*W + (x + col)];
 				ok = ok && (v == v);
 			}
-		out[k] = ok ? 1 : 0;
+		return ok ? 1 : 0;
 	}
-}
-
+};
 void launch_padded_full(hipStream_t st, const double *gray_tv, int w, int h, int R, uint8_t *out) {
-	size_t n = padded_size(w, h);
-	size_t b = (n + 255)/256; if (b > 4096) b = 4096;
-	hipLaunchKernelGGL(padded_full_kernel, dim3((unsigned)b), dim3(256), 0, st, gray_tv, w, h, R, out);
+	launch_padded_raster(st, w, h, out, PaddedFull{ gray_tv, w, h, R });
 }
 
 // ------------------------------------------------------------------ candidate ranges
@@ -134,7 +113,7 @@ void launch_pixel_range(hipStream_t st, const ViewDev *views, int ref, int oth, 
 	                   views, ref, oth, P, y0, nrows, tnum, cstride, prange, 8, lanes, padded ? 1 : 0, filllist);
 }
 
-int strip_chunk_columns() { return ST_CHUNK; }
+int strip_chunk_columns() { return STRIP_CHUNK; }
 
 // ------------------------------------------------------------------ the strip kernel
 struct StripArgs {
@@ -146,77 +125,39 @@ struct StripArgs {
 	const uint8_t *oth_fullp;               // zero-bordered "window fully usable" plane of the other view
 	double *cost; int cstride;              // cost rows, tile-transposed: ((tile*cstride) + k)*32 + pixel
 	Counters *cnt;
-	int n1, n2;                             // rows [0,n1) in 16-row items, [n1,n2) in 8-row items, the rest in 4-row items
-	                                        // (border instantiation: rows [0,n1) and [n2,nrows), in ST_BROWS-row items)
-	int nitems;
+	StripItems items;                       // the band's work items; border instantiation: those of its border rows (srh_stripframe.hpp)
 	double weight_cutoff, bad_ret, max_color_diff;
 	CertBound cb;                           // certified arithmetic (AR == 3): the constants of the error bound, srh_internal.hpp
 	int redo;                               // certified forms: 1 = uncovered candidates re-evaluated in place in the reference's arithmetic (default); 0 = raw
 };
 
-// work items of the main instantiation: tall items first -- 3/4 of the rows in 16-row items, 2/3 of the rest in 8-row items,
-// the remainder in 4-row items
-static void strip_items(StripArgs &a) {
-	a.n1 = ((a.nrows*3/4)/16)*16;
-	a.n2 = a.n1 + (((a.nrows - a.n1)*2/3)/8)*8;
-	const int nseg = a.n1/16 + (a.n2 - a.n1)/8 + (a.nrows - a.n2 + 3)/4;
-	a.nitems = nseg*((a.W + ST_TP - 1)/ST_TP);
-}
-
 template <int R, int NBUF>
-struct StripSmem {
-	static constexpr int WS = 2*R + 1;
-	static constexpr int T = WS*WS;
-	static constexpr int WP = (WS + 1) & ~1;                 // taps per window row, padded even
-	static constexpr int WPIX = WS*WP;                       // doubles per pixel window
-	static constexpr int RW = ST_CHUNK + 2*R + ST_NCB + 2;   // staged width of the other view's rows (even)
-	static constexpr int LW = (ST_TP + 2*R + 1) & ~1;        // staged width of the reference rows (even)
-	static constexpr int NS = WS + 1;                        // row slots of the rings: the window's rows + the next one
-	static constexpr int FW = (RW + 4 + 15) & ~15;           // bytes of a staged "full" row piece (dword granules + slack)
+struct StripSmem : StripGeom<R> {
+	typedef StripGeom<R> G;                    // the tile and staging geometry (srh_stripframe.hpp)
 	// phase-2 work lists in one array: 8-column blocks for the blocked select form from the front
-	// (at most ST_TP*(CHUNK/NCB + 1) of them), single candidates for the per-candidate form from the back
-	static constexpr int NBMAX = ST_CHUNK/ST_NCB + 1;
+	// (at most STRIP_TP*NBMAX of them), single candidates for the per-candidate form from the back
 	static constexpr int GL_CAP = 3072;
-	static constexpr int GL_SINGLES = GL_CAP - ST_TP*NBMAX;
-	alignas(16) double w[NBUF][WS][ST_TP][WP];         // LDS image of the windows: [row][pixel][tap], as in the band buffer
+	static constexpr int GL_SINGLES = GL_CAP - STRIP_TP*G::NBMAX;
+	alignas(16) double w[NBUF][G::WS][STRIP_TP][G::WP];         // LDS image of the windows: [row][pixel][tap], as in the band buffer
 	// 8-wave form: the rows are read 8 bytes at a time (st_lds_read8), so blocks start at the pixel's first column, odd or
 	// even (no alignment pad), and a range of 8*16*k columns needs exactly k rounds -- on C3 no column is left to the fill
 	// kernel.  (A second copy of the rows shifted by one column used to serve the odd starts with 16-byte reads: 32 KB.)
-	alignas(16) double rt[NS][RW];
+	alignas(16) double rt[G::NS][G::RW];
 	// 8-wave form, one-pass arithmetic: the current tile's tap products c_t = fma(w_t, l_t, -meanL)*w_t, laid out like a window
 	// buffer and built once per tile (behind barrier A) -- a pixel's 32 blocks used to rebuild all 121 of them each
-	alignas(16) double c[NBUF == 2 ? WS : 1][NBUF == 2 ? ST_TP : 1][WP];
-	alignas(16) double lt[NS][LW];
-	alignas(16) double pc[2][ST_TP][SRH_PC];         // meanL, totalWeight, sum2, 0 | 1/totalWeight, SA, pad (srh_internal.hpp)
-	alignas(16) PixRange pr[2][ST_TP];
-	alignas(16) unsigned char full[2][FW];
+	alignas(16) double c[NBUF == 2 ? G::WS : 1][NBUF == 2 ? STRIP_TP : 1][G::WP];
+	alignas(16) double lt[G::NS][G::LW];
+	alignas(16) double pc[2][STRIP_TP][SRH_PC];         // meanL, totalWeight, sum2, 0 | 1/totalWeight, SA, pad (srh_internal.hpp)
+	alignas(16) PixRange pr[2][STRIP_TP];
+	alignas(16) unsigned char full[2][G::FW];
 	unsigned short glist[GL_CAP];
 	int glist_n, gsingle_n;
 	int item;
-	unsigned long long badcols[ST_CHUNK/64 + 2];   // bit k: the window of candidate column cs + k is not fully usable
+	unsigned long long badcols[STRIP_CHUNK/64 + 2];   // bit k: the window of candidate column cs + k is not fully usable
 	int simd[8];                  // SIMD of each wave of the workgroup (8-wave form: which two waves share one)
 	int prog[NBUF == 2 ? 8 : 1][64];   // progress of each wave inside the current tile, in window rows (pass 2 rows count 3); one copy per lane: no lane masking in the hot loops
-	static_assert(ST_CHUNK <= 512 && ST_TP <= 64, "work-list entry = pixel*512 + column in 16 bits");
-	static_assert(RW % 2 == 0 && LW % 2 == 0 && WP % 2 == 0, "16-byte rows");
-	static_assert(RW - R + 4 <= SRH_PADR + 1, "padded planes cover every staged piece");
+	static_assert(STRIP_CHUNK <= 512 && STRIP_TP <= 64, "work-list entry = pixel*512 + column in 16 bits");
 };
-
-// lanes [0, nbytes/16) of the wave copy 16 bytes each from src + 16*lane to LDS dst + 16*lane, 1 KiB per instruction
-__device__ __forceinline__ void st_dma16(const void *src, void *dst, int nbytes, int lane) {
-	for (int off = 0; off < nbytes; off += 1024) {
-		if (off + lane*16 < nbytes)
-			__builtin_amdgcn_global_load_lds((st_gbl_void *)((const char *)src + off + lane*16),
-			                                 (st_lds_void *)((char *)dst + off), 16, 0, 0);
-	}
-}
-// the same in 4-byte granules (sources that are only 4-byte aligned)
-__device__ __forceinline__ void st_dma4(const void *src, void *dst, int nbytes, int lane) {
-	for (int off = 0; off < nbytes; off += 256) {
-		if (off + lane*4 < nbytes)
-			__builtin_amdgcn_global_load_lds((st_gbl_void *)((const char *)src + off + lane*4),
-			                                 (st_lds_void *)((char *)dst + off), 4, 0, 0);
-	}
-}
 
 // general (any validity pattern) cost of one candidate from the LDS tiles: ncc_select_cost (srh_ncc.hpp) with the rows
 // taken from the rings
@@ -227,7 +168,7 @@ __device__ __noinline__ double strip_cost_general(const StripSmem<R, NBUF> &S, i
 	typedef StripSmem<R, NBUF> Smem;
 	constexpr int WS = Smem::WS, NS = Smem::NS;
 	return ncc_select_cost<WS>([&](int row, double *gl, double *gr, double *wt) {
-		const int sl = s0 + row >= NS ? s0 + row - NS : s0 + row;
+		const int sl = ring_slot(s0, row, NS);
 #pragma unroll
 		for (int col = 0; col < WS; ++col) { gl[col] = S.lt[sl][i + col]; gr[col] = S.rt[sl][rc + col]; wt[col] = S.w[wb][row][i][col]; }
 	}, weight_cutoff, bad_ret, max_color_diff);
@@ -247,7 +188,7 @@ __device__ __noinline__ void strip_select_block(const StripSmem<R, NBUF> &S, int
 	// every term below a zero: they are left out -- a third of this routine's work on the image's first and last rows, whose
 	// every candidate comes here.
 	typedef StripSmem<R, NBUF> Smem;
-	constexpr int WS = Smem::WS, NS = Smem::NS, NCB = ST_NCB, NR = NCB + 2*R;
+	constexpr int WS = Smem::WS, NS = Smem::NS, NCB = STRIP_NCB, NR = NCB + 2*R;
 	// "A skipped tap adds +0.0 to every sum" WITHOUT a select per tap and candidate (six v_cndmask_b32 and a compare for each of
 	// the 968 pairs of a block, twice): the validity of a value is settled once per value -- an unusable gray value becomes 0.0
 	// with a flag 0.0 / 1.0 beside it, a tap whose own side is unusable gets weight 0.0 -- and what the reference skips is
@@ -258,7 +199,7 @@ __device__ __noinline__ void strip_select_block(const StripSmem<R, NBUF> &S, int
 	for (int j = 0; j < NCB; ++j) { mLs[j] = 0.0; mRs[j] = 0.0; tws[j] = 0.0; }
 #pragma unroll 1
 	for (int row = ra; row < rb; ++row) {
-		const int sl = s0 + row >= NS ? s0 + row - NS : s0 + row;
+		const int sl = ring_slot(s0, row, NS);
 		double rr[NR], rv[NR];
 		if (NBUF == 2) {                                                  // any parity of rc: 8 bytes at a time
 #pragma unroll
@@ -290,7 +231,7 @@ __device__ __noinline__ void strip_select_block(const StripSmem<R, NBUF> &S, int
 	for (int j = 0; j < NCB; ++j) { s1[j] = 0.0; s2v[j] = 0.0; s3[j] = 0.0; }
 #pragma unroll 1
 	for (int row = ra; row < rb; ++row) {
-		const int sl = s0 + row >= NS ? s0 + row - NS : s0 + row;
+		const int sl = ring_slot(s0, row, NS);
 		double rr[NR], rv[NR];
 		if (NBUF == 2) {                                                  // any parity of rc: 8 bytes at a time
 #pragma unroll
@@ -325,7 +266,7 @@ __device__ __noinline__ void strip_select_block(const StripSmem<R, NBUF> &S, int
 				const double v = 255*(1.0 - fabs(s1[j]) / sqrt(s2v[j] * s3[j]));
 				result = (v < max_color_diff) ? v : max_color_diff;
 			}
-			dst[(ptrdiff_t)j*ST_TP] = result;
+			dst[(ptrdiff_t)j*STRIP_TP] = result;
 		}
 	}
 }
@@ -374,7 +315,7 @@ struct StripRows {
 		__device__ __forceinline__ double l(int col) const { return lp[col]; }
 	};
 	__device__ __forceinline__ Row row(int row) const {
-		const int sl = s0 + row >= Smem::NS ? s0 + row - Smem::NS : s0 + row;
+		const int sl = ring_slot(s0, row, Smem::NS);
 		return Row{ &S.rt[sl][rc], reinterpret_cast<const double2 *>(&S.w[wb][row][i][0]), &S.lt[sl][i],
 		            reinterpret_cast<const double2 *>(&S.c[NBUF == 2 ? row : 0][NBUF == 2 ? i : 0][0]) };
 	}
@@ -402,8 +343,8 @@ void twoview_strip_cost_kernel(const StripArgs A)
 {
 	constexpr bool FMA = AR != 0, CERT = AR == 3 || AR == 5, ONEPASS = AR == 5;
 	typedef StripSmem<R, NBUF> Smem;
-	constexpr int WS = Smem::WS, WP = Smem::WP, WPIX = Smem::WPIX, RW = Smem::RW, LW = Smem::LW, NS = Smem::NS;
-	constexpr int NCB = ST_NCB, CHUNK = ST_CHUNK;
+	constexpr int WS = Smem::WS, WP = Smem::WP, WPIX = Smem::WPIX, RW = Smem::RW, NS = Smem::NS;
+	constexpr int NCB = STRIP_NCB, CHUNK = STRIP_CHUNK;
 	constexpr int NR = NCB + 2*R;              // right-row values a block needs (even)
 	constexpr int G = 2*NWV;                   // block lanes per pixel
 	constexpr int NT = NWV*64;
@@ -422,7 +363,7 @@ void twoview_strip_cost_kernel(const StripArgs A)
 	const int i = pg*8 + (lane & 7);             // pixel within the tile (pixel-fastest inside a wave)
 	const int g = (lane >> 3) + 8*(wv >> 2);     // block lane of the pixel
 	const int W = A.W;
-	const int tiles_per_row = (W + ST_TP - 1)/ST_TP;
+	const int tiles_per_row = (W + STRIP_TP - 1)/STRIP_TP;
 	const int SP = padded_stride(W);
 	unsigned n_dev = 0;
 	// 8-wave form: the two waves of a SIMD share its FP64 pipe, and the arbiter serves the older one first -- left alone,
@@ -454,71 +395,44 @@ void twoview_strip_cost_kernel(const StripArgs A)
 
 	for (;;) {
 		// ---- next work item: (row segment, tile column); tall segments first, so the tail of the launch is short
-		if (tid == 0) S.item = (int)atomicAdd(BORDER ? &A.cnt->strip_ticket_border : &A.cnt->strip_ticket, 1u);
-		__syncthreads();                           // also: every wave has left the previous item's last tile
-		const int item = __builtin_amdgcn_readfirstlane(S.item);
+		const int item = strip_draw_item(BORDER ? &A.cnt->strip_ticket_border : &A.cnt->strip_ticket, &S.item, tid);
 		ST_STAMP(0);                                  // ticket + waiting for the workgroup's other waves
-		if (item >= A.nitems) break;
-		int seg = item / tiles_per_row, tx = item - seg*tiles_per_row;
-		if (BORDER) {
-			// tile column major, the two edge columns first: their corner pixels leave the most to phase 2, so they should not
-			// be the launch's last items
-			const int nseg = (A.n1 + ST_BROWS - 1)/ST_BROWS + (A.nrows - A.n2 + ST_BROWS - 1)/ST_BROWS;
-			const int k = item / nseg;
-			seg = item - k*nseg;
-			tx = k == 0 ? 0 : k == 1 ? tiles_per_row - 1 : k - 1;
-		}
-		int ya, nh;
-		if (BORDER) {
-			// rows [0, n1) and [n2, nrows) of the band, in items of up to ST_BROWS rows
-			const int st = (A.n1 + ST_BROWS - 1)/ST_BROWS;
-			if (seg < st) { ya = seg*ST_BROWS; nh = A.n1 - ya; }
-			else { ya = A.n2 + (seg - st)*ST_BROWS; nh = A.nrows - ya; }
-			if (nh > ST_BROWS) nh = ST_BROWS;
-		} else {
-			const int s16 = A.n1 >> 4, s8 = (A.n2 - A.n1) >> 3;
-			if (seg < s16) { ya = seg*16; nh = 16; }
-			else if (seg < s16 + s8) { ya = A.n1 + (seg - s16)*8; nh = 8; }
-			else { ya = A.n2 + (seg - s16 - s8)*4; nh = 4; }
-			if (ya + nh > A.nrows) nh = A.nrows - ya;
-		}
-		const int x0 = tx*ST_TP;
+		if (item >= A.items.nitems) break;
+		int tx, ya, nh;
+		if (BORDER) A.items.segment_border(item, tiles_per_row, A.nrows, tx, ya, nh);
+		else A.items.segment(item, tiles_per_row, A.nrows, tx, ya, nh);
+		const int x0 = tx*STRIP_TP;
 		const int x = x0 + i;
 		int cs = 0, rowbase = 0;                   // staging origin (column, even) and the image row held by slot 0
 
 		// one tile's own inputs (nothing here depends on the staging origin): constants, ranges, [windows]
 		auto issue_tile_inputs = [&](int r, int buf, int wb, bool consts, bool windows) {
 			const size_t px0 = (size_t)r*W + x0;
-			if (consts && wv == 0) st_dma16(A.pconst + px0*SRH_PC, &S.pc[buf][0][0], ST_TP*SRH_PC*8, lane);
-			if (consts && wv == 1) st_dma4(A.prange + px0, &S.pr[buf][0], ST_TP*8, lane);
+			if (consts && wv == 0) strip_dma16(A.pconst + px0*SRH_PC, &S.pc[buf][0][0], STRIP_TP*SRH_PC*8, lane);
+			if (consts && wv == 1) strip_dma4(A.prange + px0, &S.pr[buf][0], STRIP_TP*8, lane);
 			if (windows) {
-				const double *wt = A.wimg + ((size_t)r*tiles_per_row + tx)*(size_t)(ST_TP*WPIX);
+				const double *wt = A.wimg + ((size_t)r*tiles_per_row + tx)*(size_t)(STRIP_TP*WPIX);
 				if (NBUF == 1) {
 					// each wave its own pixels' windows (8 pixels x WP taps of every window row): nobody else reads
 					// them in the block loops
 					for (int a = 0; a < WS; ++a)
-						st_dma16(wt + (size_t)a*(ST_TP*WP) + pg*8*WP, &S.w[wb][a][pg*8][0], 8*WP*8, lane);
+						strip_dma16(wt + (size_t)a*(STRIP_TP*WP) + pg*8*WP, &S.w[wb][a][pg*8][0], 8*WP*8, lane);
 				} else {
-					constexpr int NBYTES = ST_TP*WPIX*8;
+					constexpr int NBYTES = STRIP_TP*WPIX*8;
 					for (int off = wv*1024; off < NBYTES; off += NWV*1024)
 						if (off + lane*16 < NBYTES)
-							__builtin_amdgcn_global_load_lds((st_gbl_void *)((const char *)wt + off + lane*16),
-							                                 (st_lds_void *)((char *)&S.w[wb][0][0][0] + off), 16, 0, 0);
+							__builtin_amdgcn_global_load_lds((strip_gbl_void *)((const char *)wt + off + lane*16),
+							                                 (strip_lds_void *)((char *)&S.w[wb][0][0][0] + off), 16, 0, 0);
 				}
 			}
 		};
 		// image row `yy` of both views into ring slot `sl`, "full" bytes of row `fy` into full[fb]
+		// (the last wave; BORDER: worked out per tile)
 		auto issue_row = [&](int yy, int sl) {
-			const double *src = A.oth_tvp + (size_t)(yy + SRH_PADY)*SP + (cs - R + SRH_PADL);
-			if (wv < 3) { if (wv*1024 + lane*16 < RW*8) __builtin_amdgcn_global_load_lds((st_gbl_void *)((const char *)src + wv*1024 + lane*16),
-			                                                                              (st_lds_void *)((char *)&S.rt[sl][0] + wv*1024), 16, 0, 0); }
-			else if (wv == 3) st_dma16(A.ref_tvp + (size_t)(yy + SRH_PADY)*SP + (x0 - R + SRH_PADL), &S.lt[sl][0], LW*8, lane);
+			strip_request_row<R>(A.oth_tvp, A.ref_tvp, SP, yy, cs, x0, &S.rt[sl][0], &S.lt[sl][0], wv, lane);
 		};
-		static_assert(RW*8 <= 3*1024, "three pieces per row of the other view");
 		auto issue_full = [&](int fy, int fb) {
-			// bytes [cs, cs + RW) of row fy, from the 4-byte granule that holds the first one (BORDER: worked out per tile)
-			const size_t a0 = (size_t)(fy + SRH_PADY)*SP + (size_t)(cs + SRH_PADL);
-			if (!BORDER && wv == NWV - 1) st_dma4(A.oth_fullp + (a0 & ~(size_t)3), &S.full[fb][0], (RW + 4 + 3) & ~3, lane);
+			if (!BORDER && wv == NWV - 1) strip_request_full<R>(A.oth_fullp, SP, fy, cs, &S.full[fb][0], lane);
 		};
 
 		bool first = true;
@@ -535,35 +449,17 @@ void twoview_strip_cost_kernel(const StripArgs A)
 			ST_STAMP(2);                               // waiting for the other waves
 
 			// ---- B: the tile's candidate ranges (every wave works out the union for itself: 32 values)
-			int cmin, cmax, cmin_raw;
+			int cmax, cmin_raw;
 			{
 				const int pi = lane & 31;
-				const PixRange q = CS.pr[cur][pi];
-				int lo = q.lo, hi = q.hi;
-				if (x0 + pi >= W) { lo = 0; hi = -1; }
+				int lo, hi;
+				strip_pixel_range(CS.pr[cur][pi], x0 + pi < W, lo, hi);
 				if (hi >= lo) hi = dense_cover_hi(lo, hi, NCB, G, PAD);
-				int mn = hi >= lo ? lo : 2147483647, mx = hi >= lo ? hi : -2147483647;
-				// (within each row of 16 lanes by DPP rotations -- four steps, no LDS; the two rows by lane reads.  As five
-				// butterfly steps of ds_bpermute each reduction was five dependent LDS round trips)
-#define ST_ROR(v, n) __builtin_amdgcn_update_dpp(0, (v), 0x120 + (n), 0xf, 0xf, false)
-#pragma unroll
-				for (int d = 8; d >= 1; d >>= 1) {
-					const int on = d == 8 ? ST_ROR(mn, 8) : d == 4 ? ST_ROR(mn, 4) : d == 2 ? ST_ROR(mn, 2) : ST_ROR(mn, 1);
-					const int ox = d == 8 ? ST_ROR(mx, 8) : d == 4 ? ST_ROR(mx, 4) : d == 2 ? ST_ROR(mx, 2) : ST_ROR(mx, 1);
-					mn = on < mn ? on : mn; mx = ox > mx ? ox : mx;
-				}
-#undef ST_ROR
-				{
-					const int m0 = __builtin_amdgcn_readlane(mn, 0), m1 = __builtin_amdgcn_readlane(mn, 16);
-					const int x0_ = __builtin_amdgcn_readlane(mx, 0), x1_ = __builtin_amdgcn_readlane(mx, 16);
-					cmin_raw = m0 < m1 ? m0 : m1;
-					cmax = x0_ > x1_ ? x0_ : x1_;
-				}
-				cmin = cmin_raw & ~1;
+				tile_range_union(lo, hi, cmin_raw, cmax);
 			}
+			const int cmin = cmin_raw & ~1;
 			const bool any = cmin_raw <= cmax;
-			// (re)stage the rings when the strip starts or the ranges have moved outside the staged columns
-			if (first || (any && (cmin < cs || cmax > cs + CHUNK - 1))) {
+			if (needs_restage(first, any, cmin, cmax, cs)) {
 				if (!first) __builtin_amdgcn_s_barrier();          // (a restage in mid-strip: nobody reads the rings any more)
 				cs = any ? cmin : 0;
 				rowbase = y - R;
@@ -572,11 +468,7 @@ void twoview_strip_cost_kernel(const StripArgs A)
 				asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 				__builtin_amdgcn_s_barrier();
 			}
-			if (any && cmax > cs + CHUNK - 1) {
-				// a candidate range wider than the chunk: not this kernel's case (the host falls back)
-				if (tid == 0) atomicAdd(&A.cnt->strip_overflow, 1ull);
-				cmax = cs + CHUNK - 1;
-			}
+			strip_clamp_to_chunk(any, cs, cmax, tid, &A.cnt->strip_overflow);
 			first = false;
 			const int s0 = (y - R - rowbase) % NS;                   // ring slot of the window's first row
 			// ---- request the next tile's row, constants, ranges [and windows] now: they travel under the block loops
@@ -585,8 +477,7 @@ void twoview_strip_cost_kernel(const StripArgs A)
 				issue_full(y + 1, nxt);
 				issue_tile_inputs(r + 1, nxt, wnxt, true, NBUF == 2);
 			}
-			const int foff = BORDER ? 0 : (int)(((size_t)(y + SRH_PADY)*SP + (size_t)(cs + SRH_PADL)) & 3);   // first byte inside its granule
-			const unsigned char *rfull = &CS.full[cur][foff];
+			const unsigned char *rfull = &CS.full[cur][BORDER ? 0 : full_offset(y, SP, cs)];
 			// window rows on image rows with usable taps at all (rows 0 .. H - 2: the last row's gray_tv is NaN like everything
 			// outside), as phase 2 has them; [0, WS) as constants in the main instantiation
 			const int bra = BORDER ? (y < R ? R - y : 0) : 0;
@@ -597,7 +488,7 @@ void twoview_strip_cost_kernel(const StripArgs A)
 				for (int k = tid; k < RW; k += NT) {
 					bool ok = true;
 					for (int row = bra; row < brb; ++row) {
-						const int sl = s0 + row >= NS ? s0 + row - NS : s0 + row;
+						const int sl = ring_slot(s0, row, NS);
 						const double v = CS.rt[sl][k];
 						ok = ok && v == v;
 					}
@@ -606,7 +497,7 @@ void twoview_strip_cost_kernel(const StripArgs A)
 				// ... and the pixel's constants over [bra, brb), one lane per pixel, in the reference's order and operations
 				if (g == 0) {
 					const PixelConstants c = pixel_constants<WS, false>([&](int row, double *gl, double *wt) {
-						const int sl = s0 + row >= NS ? s0 + row - NS : s0 + row;
+						const int sl = ring_slot(s0, row, NS);
 						for (int col = 0; col < WS; ++col) { gl[col] = CS.lt[sl][i + col]; wt[col] = CS.w[wcur][row][i][col]; }
 					}, A.weight_cutoff, x < W, bra, brb);
 					S.pc[cur][i][0] = c.mL; S.pc[cur][i][1] = c.tw; S.pc[cur][i][2] = c.s2; S.pc[cur][i][3] = c.all ? 1.0/c.tw : 0.0;
@@ -644,11 +535,11 @@ void twoview_strip_cost_kernel(const StripArgs A)
 			// (barrier A, or the restage's own); the previous tile's plane is free (every wave has passed barrier A).  A pixel
 			// without a usable window of its own (slot 3 = 0) never reads its entries, whatever they come out as.
 			if (TAPS) {
-				constexpr int HP = WP/2, NPAIR = WS*ST_TP*HP;
+				constexpr int HP = WP/2, NPAIR = WS*STRIP_TP*HP;
 				// (a rolled loop, a pair at a time: unrolled, with the reads of all pairs in front, the kernel spills 15 more registers)
 				for (int e = tid; e < NPAIR; e += NT) {
-					const int row = e/(ST_TP*HP), pe = e - row*(ST_TP*HP), pi = pe/HP, col = 2*(pe - pi*HP);
-					const int sl = s0 + row >= NS ? s0 + row - NS : s0 + row;
+					const int row = e/(STRIP_TP*HP), pe = e - row*(STRIP_TP*HP), pi = pe/HP, col = 2*(pe - pi*HP);
+					const int sl = ring_slot(s0, row, NS);
 					const double mL = CS.pc[cur][pi][0];
 					const double2 wt = *reinterpret_cast<const double2 *>(&CS.w[wcur][row][pi][col]);
 					const bool two = col + 1 < WS;                             // (the row's pad tap: 0.0)
@@ -664,9 +555,7 @@ void twoview_strip_cost_kernel(const StripArgs A)
 			// ---- this lane's pixel
 			int e_min, e_max;
 			{
-				const PixRange q = CS.pr[cur][i];
-				e_min = q.lo; e_max = q.hi;
-				if (x >= W) { e_min = 0; e_max = -1; }
+				strip_pixel_range(CS.pr[cur][i], x < W, e_min, e_max);
 				if (e_max >= e_min) e_max = dense_cover_hi(e_min, e_max, NCB, G, PAD);
 			}
 			const bool lall = CS.pc[cur][i][3] != 0.0;
@@ -676,11 +565,9 @@ void twoview_strip_cost_kernel(const StripArgs A)
 			const size_t tile = (size_t)r*tiles_per_row + tx;
 			ST_STAMP(3);                               // ranges, (re)staging, requests for the next tile, form of the tile
 			if (e_max >= e_min) {
-				const int lo = e_min > cs ? e_min : cs;
-				const int hi = e_max < cs + CHUNK - 1 ? e_max : cs + CHUNK - 1;
-				const int lo_e = PAD ? (lo & ~1) : lo;                  // blocks start on even columns (>= cs) / at the first column
-				const int nblocks = hi >= lo ? (hi - lo_e + NCB)/NCB : 0;
-				double *crow = A.cost + tile*(size_t)A.cstride*ST_TP + i;
+				int lo, hi, lo_e, nblocks;
+				strip_lane_blocks<PAD>(e_min, e_max, cs, lo, hi, lo_e, nblocks);   // blocks start on even columns (>= cs) / at the first column
+				double *crow = A.cost + tile*(size_t)A.cstride*STRIP_TP + i;
 				// phase 1: blocks of NCB candidates in the fast form (all taps usable on both sides): meanL, totalWeight,
 				// sum2 and a_t = w_t*gl_t - meanL do not depend on the candidate (twoviewstereo.cpp:917-976, same order)
 #ifdef SRH_EXPERIMENT
@@ -721,7 +608,7 @@ void twoview_strip_cost_kernel(const StripArgs A)
 							if (c >= lo && c <= hi && rfull[rc + j] != 0) {
 								const bool okc = s3[j] >= sig3;
 								if (CERTc && !okc && A.redo) bad_blk = true;
-								crow[(size_t)(c - e_min)*ST_TP] = block_stored<CERTc, const double &>(two_sweep_finish(s1[j], s2, s3[j]), okc, A.cb.m_hi, A.max_color_diff);
+								crow[(size_t)(c - e_min)*STRIP_TP] = block_stored<CERTc, const double &>(two_sweep_finish(s1[j], s2, s3[j]), okc, A.cb.m_hi, A.max_color_diff);
 							}
 							__builtin_amdgcn_sched_barrier(0);
 						}
@@ -748,7 +635,7 @@ void twoview_strip_cost_kernel(const StripArgs A)
 							const double v = onepass_finish(P_[j], Q_[j], U_[j], SA, itw, s2, TT, sig3, zmax2, okc);
 							const bool st = (vm >> j) & 1u;
 							bad_blk |= st & !okc & redo;
-							if (st) crow[(size_t)(c0 + j - e_min)*ST_TP] = block_stored<true>(v, okc, mhi, mcd);
+							if (st) crow[(size_t)(c0 + j - e_min)*STRIP_TP] = block_stored<true>(v, okc, mhi, mcd);
 						}
 					} else if (fast && !ONEPASS && !pix_exact) two_sweeps(std::integral_constant<bool, FMA>(), std::integral_constant<bool, CERT>());
 					if (!BORDER && fast && CERT && (pix_exact || bad_blk)) two_sweeps(std::false_type(), std::false_type());   // (bad_blk is only raised when A.redo)
@@ -761,11 +648,10 @@ void twoview_strip_cost_kernel(const StripArgs A)
 			if (need_general) {
 				if (tid == 0) { S.glist_n = 0; S.gsingle_n = 0; }
 				__syncthreads();
-				for (int p = tid; p < ST_TP*Smem::NBMAX; p += NT) {
+				for (int p = tid; p < STRIP_TP*Smem::NBMAX; p += NT) {
 					const int pi = p / Smem::NBMAX, b = p % Smem::NBMAX;
-					const PixRange q = CS.pr[cur][pi];
-					int qlo = q.lo, qhi = q.hi;
-					if (x0 + pi >= W) { qlo = 0; qhi = -1; }
+					int qlo, qhi;
+					strip_pixel_range(CS.pr[cur][pi], x0 + pi < W, qlo, qhi);
 					if (qhi >= qlo) qhi = dense_cover_hi(qlo, qhi, NCB, G, PAD);
 					if (qhi > cs + CHUNK - 1) qhi = cs + CHUNK - 1;
 					if (qhi < qlo) continue;
@@ -827,7 +713,7 @@ void twoview_strip_cost_kernel(const StripArgs A)
 						if (c >= pq.lo && c <= qhi && !(pall && rfull[c - cs])) { store |= 1u << j; ++n_dev; }
 					}
 					strip_select_block<R, NBUF>(CS, wcur, s0, pi, c0 - cs, store,
-					                            A.cost + (tile*(size_t)A.cstride)*ST_TP + (ptrdiff_t)(c0 - pq.lo)*ST_TP + pi,
+					                            A.cost + (tile*(size_t)A.cstride)*STRIP_TP + (ptrdiff_t)(c0 - pq.lo)*STRIP_TP + pi,
 					                            A.weight_cutoff, A.bad_ret, A.max_color_diff,
 					                            y < R ? R - y : 0, y + R > A.H - 2 ? WS - (y + R - (A.H - 2)) : WS);
 				}
@@ -837,7 +723,7 @@ void twoview_strip_cost_kernel(const StripArgs A)
 					if (e == 0xffffu) continue;
 					const int pi = e >> 9, k = e & 511;
 					++n_dev;
-					A.cost[(tile*(size_t)A.cstride + (size_t)(cs + k - CS.pr[cur][pi].lo))*ST_TP + pi] =
+					A.cost[(tile*(size_t)A.cstride + (size_t)(cs + k - CS.pr[cur][pi].lo))*STRIP_TP + pi] =
 						strip_cost_general<R, NBUF>(CS, wcur, s0, pi, k, A.weight_cutoff, A.bad_ret, A.max_color_diff);
 				}
 				ST_STAMP(7);                           // phase 2: single candidates
@@ -870,13 +756,7 @@ static void launch_strip_variant(hipStream_t st, const StripArgs &a, int num_cus
 {
 	typedef StripSmem<R, NBUF> Smem;
 	static_assert(sizeof(Smem) <= (NBUF == 2 ? 160 : 80)*1024, "a compute unit's 160 KB of LDS: one 8-wave workgroup or two 4-wave ones");
-	size_t lds = sizeof(Smem);
-	(void)hipFuncSetAttribute((const void *)twoview_strip_cost_kernel<R, NWV, NBUF, AR, BORDER>,
-	                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-	int grid = num_cus*(NBUF == 2 ? 1 : 2);
-	if (grid > a.nitems) grid = a.nitems;
-	if (grid < 1) grid = 1;
-	hipLaunchKernelGGL((twoview_strip_cost_kernel<R, NWV, NBUF, AR, BORDER>), dim3((unsigned)grid), dim3(NWV*64), lds, st, a);
+	launch_strip(st, twoview_strip_cost_kernel<R, NWV, NBUF, AR, BORDER>, a, sizeof(Smem), NWV*64, NBUF == 2 ? 1 : 2, num_cus, a.items.nitems);
 }
 
 // The band's rows whose window the image's top or bottom edge cuts, [0, t) and [b, nrows), go to the border instantiation
@@ -885,18 +765,18 @@ static void launch_strip_variant(hipStream_t st, const StripArgs &a, int num_cus
 template <int R, int NWV, int NBUF>
 static void launch_strip_arith(hipStream_t st, const StripArgs &a, int num_cus, int arith)
 {
-	const int tiles_per_row = (a.W + ST_TP - 1)/ST_TP;
-	const int t = std::min(std::max(R - a.y0, 0), a.nrows);
-	const int b = std::min(std::max(a.H - 1 - R - a.y0, t), a.nrows);
+	const int tiles_per_row = (a.W + STRIP_TP - 1)/STRIP_TP;
+	int t, b;
+	StripItems::border_rows(a.y0, a.nrows, a.H, R, t, b);
 	if (b > t) {
 		StripArgs m = a;
 		const size_t tiles = (size_t)t*tiles_per_row;
 		m.y0 = a.y0 + t; m.nrows = b - t;
-		m.wimg = a.wimg + tiles*(ST_TP*StripSmem<R, NBUF>::WPIX);
+		m.wimg = a.wimg + tiles*(STRIP_TP*StripSmem<R, NBUF>::WPIX);
 		m.pconst = a.pconst + (size_t)t*a.W*SRH_PC;
 		m.prange = a.prange + (size_t)t*a.W;
-		m.cost = a.cost + tiles*(size_t)a.cstride*ST_TP;
-		strip_items(m);
+		m.cost = a.cost + tiles*(size_t)a.cstride*STRIP_TP;
+		m.items = StripItems::cut(m.nrows, m.W);
 		if (arith == 5) launch_strip_variant<R, NWV, NBUF, 5, false>(st, m, num_cus);
 		else if (arith == 3) launch_strip_variant<R, NWV, NBUF, 3, false>(st, m, num_cus);
 		else if (arith == 1) launch_strip_variant<R, NWV, NBUF, 1, false>(st, m, num_cus);
@@ -904,8 +784,7 @@ static void launch_strip_arith(hipStream_t st, const StripArgs &a, int num_cus, 
 	}
 	if (t > 0 || b < a.nrows) {
 		StripArgs e = a;
-		e.n1 = t; e.n2 = b;
-		e.nitems = ((t + ST_BROWS - 1)/ST_BROWS + (a.nrows - b + ST_BROWS - 1)/ST_BROWS)*tiles_per_row;
+		e.items = StripItems::cut_border(t, b, a.nrows, a.W);
 		launch_strip_variant<R, NWV, NBUF, 0, true>(st, e, num_cus);
 	}
 }
@@ -914,7 +793,7 @@ static void launch_strip_arith(hipStream_t st, const StripArgs &a, int num_cus, 
 int strip_block_lanes(int cstride, int form) {
 	if (form == 4) return 8;
 	if (form == 8) return 16;
-	return cstride > 16*ST_NCB ? 16 : 8;
+	return cstride > 16*STRIP_NCB ? 16 : 8;
 }
 
 bool launch_twoview_strip_cost(hipStream_t st, const ViewDev *views, int ref, int oth, int width, int height,
