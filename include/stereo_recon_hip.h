@@ -273,6 +273,16 @@ enum { SRH_WTA_WINNERS = 1, SRH_WTA_COSTS = 2 };
  *                     SRH_E_INVALID.  16 / 32 bytes per pixel of the reference view in device memory, allocated by the first
  *                     pass that keeps them; read with srh_view_wta_outputs*.  They describe the WTA stage: the cross-check and
  *                     "filter_invalid" do not touch them.
+ *   "subpixel"        CHANGES RESULTS.  0 (default): off -- not one extra launch, allocation or store.  1: every TwoView WTA pass
+ *                     (srh_twoview_wta, both passes of srh_twoview_compute, row ranges included) refines the depth of the rows
+ *                     it has decided before it returns, hence before the cross-check, the speckle filter and the hole filling:
+ *                     a parabola through the reference's costs of the kept winner and of its two neighbours on the pixel's
+ *                     curve -- the visited pixels at Chebyshev distance 1 from the winner whose candidate depths lie next
+ *                     below and next above the winner's -- places the match between two pixels of the other view, and the
+ *                     depth is triangulated there (DESIGN.md 4n has the definition).  Internally the pass keeps winners and
+ *                     costs as under "wta_outputs" = 3; what srh_view_wta_outputs* show is still what "wta_outputs" asked
+ *                     for.  Read with srh_view_subpixel*.  No effect on srh_twoview_compute_mrf / _sgm (no scan runs there)
+ *                     and on MultiViewStereo.  Other values: SRH_E_INVALID.
  *   "filter_invalid"  0 (default, as the reference's call site under #if 0): srh_twoview_compute ends with the cross-check;
  *                     SRH_FILTER_* flags (1 gaps, 2 median, 3 both): it then runs srh_view_filter_invalid on both maps,
  *                     with progress steps 6 "Filling invalid pixels..." and, with the median, 7 "Filtering invalid pixels..."
@@ -354,6 +364,26 @@ int  srh_view_depth_device_ptr(srh_context *ctx, int slot, void **dev_ptr);
 int  srh_view_wta_outputs(srh_context *ctx, int slot, int32_t *win_xy, int32_t *runner_xy, double *min_cost, double *second_cost);
 int  srh_view_wta_outputs_device(srh_context *ctx, int slot, void **win_xy, void **runner_xy, void **min_cost, void **second_cost);
 int  srh_view_wta_outputs_state(srh_context *ctx, int slot, int *flags, int *oth_slot);
+/* What option "subpixel" did to each pixel of the last TwoView WTA pass that had `slot` as its reference view:
+ *   SRH_SUBPX_NONE          no finite depth or no kept winner (NaN, +INF, outside the mask): nothing to refine
+ *   SRH_SUBPX_NO_NEIGHBOUR  the curve has no visited pixel beside the winner with a smaller, or none with a larger, depth
+ *   SRH_SUBPX_FLAT          D = (cm - c0) + (cp - c0) is not > 0: the three costs have no minimum between the neighbours
+ *   SRH_SUBPX_OUTSIDE       |delta| = |0.5*(cm - cp)/D| is not <= 0.5: the parabola's minimum lies beyond half a step
+ *   SRH_SUBPX_REFINED       the depth was triangulated at winner + |delta|*(neighbour - winner) (delta == 0: its bits kept)
+ * delta: w*h doubles, 0 where the pixel is not refined; > 0 towards n+, the neighbour of larger depth.  neigh_xy: w*h*4
+ * int32 (n-.x, n-.y, n+.x, n+.y), (-1, -1) = none.  cls: w*h bytes.  Rows no pass has written hold NONE, 0 and (-1, -1).
+ * srh_view_subpixel: host buffers, each may be NULL, synchronous; srh_view_subpixel_device: the device planes themselves;
+ * srh_view_subpixel_info: the pixels of each class in the slot's plane.  All three return SRH_E_INVALID where
+ * srh_view_wta_outputs does (nothing held, uploaded since, map from the MRF / SGM stage) and when the pass ran with the
+ * option off. */
+enum { SRH_SUBPX_NONE = 0, SRH_SUBPX_NO_NEIGHBOUR = 1, SRH_SUBPX_FLAT = 2, SRH_SUBPX_OUTSIDE = 3, SRH_SUBPX_REFINED = 4 };
+typedef struct srh_subpixel_info {
+	int64_t n_class[5];          /* pixels per SRH_SUBPX_* class */
+	int64_t n_moved;             /* of the REFINED ones: delta != 0 */
+} srh_subpixel_info;
+int  srh_view_subpixel(srh_context *ctx, int slot, double *delta, int32_t *neigh_xy, uint8_t *cls);
+int  srh_view_subpixel_device(srh_context *ctx, int slot, void **delta, void **neigh_xy, void **cls);
+int  srh_view_subpixel_info(srh_context *ctx, int slot, srh_subpixel_info *info);
 /* Asynchronous device-to-device copy of the slot's depth map (w*h doubles) into caller-owned
  * DEVICE memory of `dst_bytes` bytes (e.g. a tensor that RCCL then gathers); ordered on the context
  * stream.  SRH_E_INVALID when the buffer is smaller than the map (views may differ in size). */

@@ -135,6 +135,11 @@ class SpeckleInfo(C.Structure):
                 ("removed_pixels", C.c_int64), ("largest", C.c_int64)]
 
 
+class SubpixelInfo(C.Structure):
+    """srh_subpixel_info"""
+    _fields_ = [("n_class", C.c_int64 * 5), ("n_moved", C.c_int64)]
+
+
 # srh_view_filter_speckles flag: the reject value is NaN, not +INF
 SPECKLE_TO_NAN = 1
 
@@ -162,6 +167,8 @@ COST_NCC, COST_SAD = 0, 1
 
 # option "wta_outputs": the by-products of the WTA scan a pass keeps (SRH_WTA_*)
 WTA_WINNERS, WTA_COSTS = 1, 2
+# option "subpixel": what the refinement did to a pixel (SRH_SUBPX_*)
+SUBPX_NONE, SUBPX_NO_NEIGHBOUR, SUBPX_FLAT, SUBPX_OUTSIDE, SUBPX_REFINED = 0, 1, 2, 3, 4
 # scaling at file resolution (SRH_SCALE_*, SRH_MASK_*)
 SCALE_SMOOTH, SCALE_FAST = 0, 1
 MASK_NONE, MASK_ALPHA_FAST, MASK_IMAGE_SMOOTH = 0, 1, 2
@@ -179,6 +186,7 @@ EXPORTS = [
     "srh_view_depth_download", "srh_view_depth_upload",
     "srh_view_depth_device_ptr", "srh_view_depth_copy_to_device", "srh_view_depth_copy_from_device",
     "srh_view_wta_outputs", "srh_view_wta_outputs_device", "srh_view_wta_outputs_state",
+    "srh_view_subpixel", "srh_view_subpixel_device", "srh_view_subpixel_info",
     "srh_twoview_wta", "srh_twoview_cross_check", "srh_twoview_compute", "srh_twoview_cost_rows", "srh_twoview_pair_costs", "srh_debug_exp",
     "srh_mvs_initial_estimate", "srh_mvs_cross_check", "srh_view_point_cloud", "srh_view_filter_invalid",
     "srh_speckle_params_defaults", "srh_view_filter_speckles",
@@ -269,6 +277,9 @@ def lib():
     L.srh_view_wta_outputs.argtypes = [vp, C.c_int, c_int32_p, c_int32_p, c_double_p, c_double_p]
     L.srh_view_wta_outputs_device.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.srh_view_wta_outputs_state.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.srh_view_subpixel.argtypes = [vp, C.c_int, c_double_p, c_int32_p, C.POINTER(C.c_uint8)]
+    L.srh_view_subpixel_device.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.srh_view_subpixel_info.argtypes = [vp, C.c_int, C.POINTER(SubpixelInfo)]
     L.srh_mrf_params_defaults.argtypes = [C.POINTER(SrhMrfParams)]
     L.srh_mrf_params_defaults.restype = None
     L.srh_mvs_mrf_estimate.argtypes = [vp, C.c_int, C.c_int, C.c_void_p, C.POINTER(SrhMrfParams), C.POINTER(SrhMrfInfo)]
@@ -728,6 +739,30 @@ class Context:
         _check(lib().srh_view_wta_outputs_device(self._h, slot, C.byref(p[0]), C.byref(p[1]),
                                                  C.byref(p[2]) if costs else None, C.byref(p[3]) if costs else None))
         return tuple(q.value for q in p)
+
+    def subpixel(self, slot):
+        """What option "subpixel" did in the slot's last WTA pass as the reference view (srh_view_subpixel): dict(delta
+        (h, w), 0 where the pixel is not refined; neigh_xy (h, w, 4) int32 = (n-.x, n-.y, n+.x, n+.y), (-1, -1) = none;
+        cls (h, w) uint8 of SUBPX_*)."""
+        w, h = self.view_size(slot)
+        out = {"delta": np.empty((h, w), dtype=np.float64), "neigh_xy": np.empty((h, w, 4), dtype=np.int32),
+               "cls": np.empty((h, w), dtype=np.uint8)}
+        _check(lib().srh_view_subpixel(self._h, slot, _dptr(out["delta"]), out["neigh_xy"].ctypes.data_as(c_int32_p),
+                                       out["cls"].ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    def subpixel_device(self, slot):
+        """Device addresses (delta, neigh_xy, cls) of the slot's sub-pixel planes (srh_view_subpixel_device)."""
+        p = [C.c_void_p() for _ in range(3)]
+        _check(lib().srh_view_subpixel_device(self._h, slot, C.byref(p[0]), C.byref(p[1]), C.byref(p[2])))
+        return tuple(q.value for q in p)
+
+    def subpixel_info(self, slot):
+        """dict(n_class = pixels per SUBPX_* class (5 ints), n_moved = refined pixels with delta != 0) of the slot's
+        planes (srh_view_subpixel_info)."""
+        i = SubpixelInfo()
+        _check(lib().srh_view_subpixel_info(self._h, slot, C.byref(i)))
+        return {"n_class": [int(v) for v in i.n_class], "n_moved": int(i.n_moved)}
 
     def copy_depth_to_device(self, slot, dst_dev_ptr, dst_bytes):
         _check(lib().srh_view_depth_copy_to_device(self._h, slot, C.c_void_p(dst_dev_ptr), C.c_size_t(dst_bytes)))

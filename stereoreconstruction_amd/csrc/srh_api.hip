@@ -3,6 +3,7 @@
 // the kernels in srh_kernels.hip / srh_dense.hip.  There is no CPU fallback: without
 // a HIP device srh_create fails with SRH_E_NO_DEVICE.
 #include "srh_internal.hpp"
+#include "srh_subpixel.hpp"
 #include "srh_geom.hpp"
 #include "srh_walk.hpp"
 #include "srh_speckle.hpp"
@@ -192,9 +193,10 @@ struct BandBuffers {
 	DevBuf<int32_t> lmeta;
 	DevBuf<uint32_t> mvs_wdesc;     // window descriptors of the MultiViewStereo walk kernel's waves
 	DevBuf<int32_t> mvs_nwin;
+	DevBuf<double> subpx_tdist;     // option "subpixel": per-label plane table of the neighbours kernel's walk
 	template <class F> void each(F f) {
 		f(wbuf); f(cost); f(tnum); f(pconst); f(prange); f(filllist); f(cflag); f(stpl); f(tileflag);
-		f(lcount); f(lcand); f(lrowinfo); f(lmeta); f(mvs_wdesc); f(mvs_nwin);
+		f(lcount); f(lcand); f(lrowinfo); f(lmeta); f(mvs_wdesc); f(mvs_nwin); f(subpx_tdist);
 	}
 	size_t bytes() { size_t b = 0; each([&](auto &x) { b += x.bytes(); }); return b; }
 	void release() { each([](auto &x) { x.release(); }); }
@@ -274,6 +276,12 @@ struct ViewHost {
 	DevBuf<int32_t> wta_xy;
 	DevBuf<double>  wta_cost;
 	int wta_flags = 0, wta_oth = -1;            // what the planes hold (SRH_WTA_*; 0: nothing, or stale) and against which slot
+	int wta_asked = 0;                          // of wta_flags, what option "wta_outputs" asked for: what the getters show (option "subpixel" keeps all)
+	// option "subpixel" (DESIGN.md 4n): delta, (n-, n+) and the class of every pixel of that pass; subpx: the pass refined
+	DevBuf<double>  subpx_delta;
+	DevBuf<int32_t> subpx_neigh;
+	DevBuf<uint8_t> subpx_cls;
+	bool subpx = false;
 	DevBuf<double> peaks; int peaks_k = 0;      // top-K peaks of the last initial estimate
 	DevBuf<double> mrf;                         // this view's own TRW-S scratch
 	DevBuf<double> sgm;                         // this view's own aggregation scratch (srh_mvs_sgm_estimate_views)
@@ -392,6 +400,9 @@ struct srh_context {
 	int speckle_diff_steps = 2;                         // option "speckle_diff_steps": that stage's max_diff in depth steps
 	int cost_kind = SRH_COST_NCC;                       // option "cost": the TwoView matching cost, SRH_COST_NCC or SRH_COST_SAD
 	int sad_dense = 0;                                  // option "sad_dense": cost_sad of row-aligned rigs on the dense plan (srh_sad_strip.hip)
+	int subpixel = 0;                                   // option "subpixel": every TwoView WTA pass refines its rows (srh_subpixel.hip; CHANGES RESULTS)
+	// what a TwoView WTA pass keeps per reference pixel: what "wta_outputs" asks for; under "subpixel" winners and costs
+	int wta_keep() const { return subpixel ? (SRH_WTA_WINNERS | SRH_WTA_COSTS) : wta_outputs; }
 	int wta_outputs = 0;                                // option "wta_outputs": SRH_WTA_* planes a TwoView WTA pass keeps per reference pixel (never changes a depth map)
 	// srh_mvs_fuse (srh_fuse.hip): the fused cloud of the last call -- one block carved into the arrays of
 	// fuse_out -- and the call's scratch (point maps, flags, staging planes), which goes back to the pool when the call ends
@@ -786,6 +797,7 @@ static void free_view(ViewHost &v) {
 	v.rgba.release(); v.mask.release(); v.gray.release(); v.gray_tv.release(); v.depth.release(); v.edges.release();
 	v.full.release(); v.fulls.release(); v.grayp.release(); v.fullsp.release(); v.tvp.release(); v.geo5.release(); v.fullp.release(); v.act.release(); v.peaks.release(); v.mrf.release(); v.sgm.release();
 	v.wta_xy.release(); v.wta_cost.release();
+	v.subpx_delta.release(); v.subpx_neigh.release(); v.subpx_cls.release();
 	v = ViewHost();
 }
 
@@ -914,6 +926,10 @@ extern "C" int srh_set_option(srh_context *c, const char *name, long value) {
 		if (value != 0 && value != SRH_WTA_WINNERS && value != (SRH_WTA_WINNERS | SRH_WTA_COSTS))
 			return fail(SRH_E_INVALID, "wta_outputs must be 0, 1 (SRH_WTA_WINNERS) or 3 (SRH_WTA_WINNERS | SRH_WTA_COSTS): the costs are those of the kept winners");
 		c->wta_outputs = (int)value; return SRH_OK;
+	}
+	if (!strcmp(name, "subpixel")) {
+		if (value != 0 && value != 1) return fail(SRH_E_INVALID, "subpixel must be 0 or 1");
+		c->subpixel = (int)value; return SRH_OK;
 	}
 	if (!strcmp(name, "tscan")) { c->tscan = value != 0; return SRH_OK; }
 	if (!strcmp(name, "tscan_bound")) { c->tscan_bound = value != 0; return SRH_OK; }
@@ -1196,16 +1212,16 @@ extern "C" int srh_view_depth_device_ptr(srh_context *c, int slot, void **dev_pt
 // ---- by-products of the WTA scan (option "wta_outputs")
 static int check_wta_outputs(srh_context *c, int slot, bool costs) {
 	const ViewHost &v = c->views[slot];
-	if (!v.wta_flags) return fail(SRH_E_INVALID, "view slot %d holds no WTA outputs (option \"wta_outputs\" off, no WTA pass since the upload, or its depth map came from the MRF stage)", slot);
-	if (costs && !(v.wta_flags & SRH_WTA_COSTS)) return fail(SRH_E_INVALID, "view slot %d kept the winners only (wta_outputs = 1): no cost planes", slot);
+	if (!(v.wta_flags & v.wta_asked)) return fail(SRH_E_INVALID, "view slot %d holds no WTA outputs (option \"wta_outputs\" off, no WTA pass since the upload, or its depth map came from the MRF stage)", slot);
+	if (costs && !(v.wta_flags & v.wta_asked & SRH_WTA_COSTS)) return fail(SRH_E_INVALID, "view slot %d kept the winners only (wta_outputs = 1): no cost planes", slot);
 	return SRH_OK;
 }
 
 extern "C" int srh_view_wta_outputs_state(srh_context *c, int slot, int *flags, int *oth_slot) {
 	int rc = check_slot(c, slot, true); if (rc) return rc;
 	const ViewHost &v = c->views[slot];
-	if (flags) *flags = v.wta_flags;
-	if (oth_slot) *oth_slot = v.wta_flags ? v.wta_oth : -1;
+	if (flags) *flags = v.wta_flags & v.wta_asked;
+	if (oth_slot) *oth_slot = (v.wta_flags & v.wta_asked) ? v.wta_oth : -1;
 	return SRH_OK;
 }
 
@@ -1232,6 +1248,54 @@ extern "C" int srh_view_wta_outputs(srh_context *c, int slot, int32_t *win_xy, i
 	if (min_cost) HIP_TRY(hipMemcpyAsync(min_cost, v.wta_cost, n*sizeof(double), hipMemcpyDeviceToHost, c->stream));
 	if (second_cost) HIP_TRY(hipMemcpyAsync(second_cost, v.wta_cost + n, n*sizeof(double), hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
+	return SRH_OK;
+}
+
+// ---- what option "subpixel" did to the pixels of the slot's last pass (srh_subpixel.hip)
+static int check_subpixel(srh_context *c, int slot) {
+	const ViewHost &v = c->views[slot];
+	if (!v.wta_flags || !v.subpx) return fail(SRH_E_INVALID, "view slot %d holds no sub-pixel planes (option \"subpixel\" off, no WTA pass since the upload, or its depth map came from the MRF / SGM stage)", slot);
+	return SRH_OK;
+}
+
+extern "C" int srh_view_subpixel_device(srh_context *c, int slot, void **delta, void **neigh_xy, void **cls) {
+	int rc = check_slot(c, slot, true); if (rc) return rc;
+	if ((rc = check_subpixel(c, slot))) return rc;
+	const ViewHost &v = c->views[slot];
+	if (delta) *delta = v.subpx_delta;
+	if (neigh_xy) *neigh_xy = v.subpx_neigh;
+	if (cls) *cls = v.subpx_cls;
+	return SRH_OK;
+}
+
+extern "C" int srh_view_subpixel(srh_context *c, int slot, double *delta, int32_t *neigh_xy, uint8_t *cls) {
+	int rc = check_slot(c, slot, true); if (rc) return rc;
+	if ((rc = check_subpixel(c, slot))) return rc;
+	HIP_TRY(hipSetDevice(c->device));
+	const ViewHost &v = c->views[slot];
+	const size_t n = (size_t)v.w*v.h;
+	if (delta) HIP_TRY(hipMemcpyAsync(delta, v.subpx_delta, n*sizeof(double), hipMemcpyDeviceToHost, c->stream));
+	if (neigh_xy) HIP_TRY(hipMemcpyAsync(neigh_xy, v.subpx_neigh, 4*n*sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+	if (cls) HIP_TRY(hipMemcpyAsync(cls, v.subpx_cls, n, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	return SRH_OK;
+}
+
+// (the counts are taken from the planes when asked for: a pass pays nothing for them)
+extern "C" int srh_view_subpixel_info(srh_context *c, int slot, srh_subpixel_info *info) {
+	int rc = check_slot(c, slot, true); if (rc) return rc;
+	if (!info) return fail(SRH_E_INVALID, "null output");
+	if ((rc = check_subpixel(c, slot))) return rc;
+	const ViewHost &v = c->views[slot];
+	const size_t n = (size_t)v.w*v.h;
+	std::vector<uint8_t> k(n);
+	std::vector<double> d(n);
+	if ((rc = srh_view_subpixel(c, slot, d.data(), nullptr, k.data()))) return rc;
+	memset(info, 0, sizeof(*info));
+	for (size_t i = 0; i < n; ++i) {
+		if (k[i] <= SRH_SUBPX_REFINED) ++info->n_class[k[i]];
+		if (k[i] == SRH_SUBPX_REFINED && d[i] != 0) ++info->n_moved;
+	}
 	return SRH_OK;
 }
 
@@ -1442,14 +1506,27 @@ static void run_weights(srh_context *c, const Lane &lane, int ref, int W, const 
 // no allocation, no launch -- the slot's planes, if any, no longer describe its depth map.
 static int ensure_wta_planes(srh_context *c, hipStream_t st, int ref, int oth) {
 	ViewHost &v = c->views[ref];
-	if (!c->wta_outputs) { v.wta_flags = 0; return SRH_OK; }
+	const int keep = c->wta_keep();
+	if (!keep) { v.wta_flags = 0; v.subpx = false; return SRH_OK; }
 	const size_t n = (size_t)v.w*v.h;
-	if (v.wta_flags == c->wta_outputs && v.wta_oth == oth) return SRH_OK;
+	const bool subpx = c->subpixel != 0;
+	v.wta_asked = c->wta_outputs;
+	if (v.wta_flags == keep && v.wta_oth == oth && v.subpx == subpx) return SRH_OK;
 	if (!v.wta_xy) HIP_TRY(v.wta_xy.alloc(4*n));
-	if ((c->wta_outputs & SRH_WTA_COSTS) && !v.wta_cost) HIP_TRY(v.wta_cost.alloc(2*n));
+	if ((keep & SRH_WTA_COSTS) && !v.wta_cost) HIP_TRY(v.wta_cost.alloc(2*n));
+	if (subpx) {
+		if (!v.subpx_delta) HIP_TRY(v.subpx_delta.alloc(n));
+		if (!v.subpx_neigh) HIP_TRY(v.subpx_neigh.alloc(4*n));
+		if (!v.subpx_cls) HIP_TRY(v.subpx_cls.alloc(n));
+	}
 	HIP_TRY(hipMemsetAsync(v.wta_xy, 0xff, 4*n*sizeof(int32_t), st));           // (-1, -1): no winner, no runner-up
-	if (c->wta_outputs & SRH_WTA_COSTS) launch_fill(st, v.wta_cost, 2*n, __builtin_inf());
-	v.wta_flags = c->wta_outputs; v.wta_oth = oth;
+	if (keep & SRH_WTA_COSTS) launch_fill(st, v.wta_cost, 2*n, __builtin_inf());
+	if (subpx) {                                                                 // no pixel refined, no neighbour, class NONE
+		HIP_TRY(hipMemsetAsync(v.subpx_delta, 0, n*sizeof(double), st));
+		HIP_TRY(hipMemsetAsync(v.subpx_neigh, 0xff, 4*n*sizeof(int32_t), st));
+		HIP_TRY(hipMemsetAsync(v.subpx_cls, SRH_SUBPX_NONE, n, st));
+	}
+	v.wta_flags = keep; v.wta_oth = oth; v.subpx = subpx;
 	return SRH_OK;
 }
 
@@ -1594,6 +1671,7 @@ struct TvPass {
 	size_t budget = 0;
 	bool sad = false;
 	int32_t *wout = nullptr;
+	const double *subpx_tdist = nullptr;      // option "subpixel": the pass's label plane table (label_plane_table_kernel)
 
 	size_t rows_per_band(size_t bytes) const;
 	void winner_costs(int by, int nr, bool wimg_layout) const;
@@ -1636,11 +1714,20 @@ size_t TvPass::rows_per_band(size_t bytes) const {
 }
 
 void TvPass::winner_costs(int by, int nr, bool wimg_layout) const {
-	if (!wout || !(c->wta_outputs & SRH_WTA_COSTS)) return;
-	Scope s(c, lane.stream, "twoview_winner_costs_kernel");
-	double *mc = c->views[ref].wta_cost;
-	launch_twoview_winner_costs(lane.stream, c->d_views, ref, oth, W, *p, sad, by, nr, lane.mem->band.wbuf, wimg_layout,
-	                            wout, mc, mc + (size_t)W*H);
+	if (!wout || !(c->wta_keep() & SRH_WTA_COSTS)) return;
+	const ViewHost &v = c->views[ref];
+	double *mc = v.wta_cost;
+	{ Scope s(c, lane.stream, "twoview_winner_costs_kernel");
+	  launch_twoview_winner_costs(lane.stream, c->d_views, ref, oth, W, *p, sad, by, nr, lane.mem->band.wbuf, wimg_layout,
+	                              wout, mc, mc + (size_t)W*H); }
+	if (!c->subpixel) return;
+	// option "subpixel": the band's winners, their costs and its depths are final here and its windows still in the buffer.
+	// A repeated attempt rewrites the rows' depths and winners first and is refined again: the planes follow the attempt that stands.
+	{ Scope s(c, lane.stream, "subpixel_neighbours_kernel");
+	  launch_subpixel_neighbours(lane.stream, c->d_views, ref, oth, W, *p, by, nr, subpx_tdist, wout, v.subpx_neigh, v.subpx_cls); }
+	{ Scope s(c, lane.stream, "subpixel_refine_kernel");
+	  launch_subpixel_refine(lane.stream, c->d_views, ref, oth, W, *p, sad, by, nr, lane.mem->band.wbuf, wimg_layout, wout, mc,
+	                         v.subpx_neigh, v.subpx_cls, v.subpx_delta); }
 }
 
 // The exact redo of flagged pixels is launched for a CAPACITY -- the whole band: the list buffer holds every pixel of it,
@@ -2171,7 +2258,15 @@ static int twoview_wta_run(srh_context *c, const Lane &lane, srh_context::TvDefe
 	if ((rc = tv_pass_init(P, c, lane, ref, oth, p, y0, y1))) return rc;
 	if (P.y1 <= P.y0) return SRH_OK;
 	if ((rc = ensure_wta_planes(c, lane.stream, ref, oth))) return rc;
-	P.wout = c->wta_outputs ? (int32_t *)c->views[ref].wta_xy : nullptr;
+	P.wout = c->wta_keep() ? (int32_t *)c->views[ref].wta_xy : nullptr;
+	if (c->subpixel) {
+		// the label-only part of pointFromDepth for the neighbours kernel's walk (a buffer of its own: band.tnum holds
+		// whatever table the pass's own path reads)
+		if ((rc = lane.mem->band.subpx_tdist.ensure((size_t)p->num_depth_levels))) return rc;
+		Scope s(c, lane.stream, "label_plane_table_kernel");
+		launch_label_plane_table(lane.stream, c->d_views, ref, *p, false, lane.mem->band.subpx_tdist);
+		P.subpx_tdist = lane.mem->band.subpx_tdist;
+	}
 	const TvPlan plan = P.plan();
 
 	c->last_fused = false;

@@ -182,6 +182,7 @@ void TwoViewStereo::computeCostVolumes(CameraPtr leftView_, CameraPtr rightView_
 	if (srh_set_option(ctx_, "cost", costKind) != SRH_OK) { error_ = srh_last_error(); return; }
 	srh_set_option(ctx_, "sad_dense", sadDenseOn);
 	if (srh_set_option(ctx_, "wta_outputs", wtaFlags) != SRH_OK) { error_ = srh_last_error(); return; }
+	srh_set_option(ctx_, "subpixel", subpixelOn ? 1 : 0);
 	if (srh_twoview_wta(ctx_, 0, 1, &params_, 0, 0) != SRH_OK || srh_twoview_wta(ctx_, 1, 0, &params_, 0, 0) != SRH_OK ||
 	    srh_view_depth_download(ctx_, 0, computedDepthLeft.data()) != SRH_OK ||
 	    srh_view_depth_download(ctx_, 1, computedDepthRight.data()) != SRH_OK) {
@@ -194,8 +195,17 @@ void TwoViewStereo::computeCostVolumes(CameraPtr leftView_, CameraPtr rightView_
 // the kept by-products of both passes (leftSlot: the left map's, rightSlot: the right map's -- 0 and 1, or the rectified
 // views' slots); empty when nothing was kept
 void TwoViewStereo::fetchWtaOutputs(int leftSlot, int rightSlot) {
-	for (int k = 0; k < 2; ++k) { winners_[k].clear(); runners_[k].clear(); minCosts_[k].clear(); secondCosts_[k].clear(); }
-	if (!ctx_ || !wtaFlags) return;
+	for (int k = 0; k < 2; ++k) { winners_[k].clear(); runners_[k].clear(); minCosts_[k].clear(); secondCosts_[k].clear(); subDelta_[k].clear(); }
+	if (!ctx_) return;
+	// setSubpixel: the deltas of both passes (a slot whose map no scan made holds none: the vector stays empty)
+	for (int k = 0; subpixelOn && k < 2; ++k) {
+		const int slot = k == 0 ? leftSlot : rightSlot;
+		int w = 0, h = 0;
+		if (srh_view_size(ctx_, slot, &w, &h) != SRH_OK) { error_ = srh_last_error(); return; }
+		subDelta_[k].resize(static_cast<size_t>(w)*h);
+		if (srh_view_subpixel(ctx_, slot, subDelta_[k].data(), nullptr, nullptr) != SRH_OK) subDelta_[k].clear();
+	}
+	if (!wtaFlags) return;
 	for (int k = 0; k < 2; ++k) {
 		const int slot = k == 0 ? leftSlot : rightSlot;
 		int flags = 0, w = 0, h = 0;
@@ -315,6 +325,7 @@ void TwoViewStereo::computeDepthMaps() {
 	srh_set_hooks(ctx_, cancelFlag(), onProgress, &hooks);
 	srh_set_option(ctx_, "filter_invalid", filterFlags);
 	srh_set_option(ctx_, "sad_dense", sadDenseOn);
+	srh_set_option(ctx_, "subpixel", subpixelOn ? 1 : 0);
 	if (srh_set_option(ctx_, "speckle_min_size", speckleMinSize) != SRH_OK ||
 	    (speckleMinSize && srh_set_option(ctx_, "speckle_diff_steps", speckleDiffSteps) != SRH_OK) ||
 	    srh_set_option(ctx_, "cost", costKind) != SRH_OK || srh_set_option(ctx_, "wta_outputs", wtaFlags) != SRH_OK) {

@@ -147,6 +147,17 @@ public:
 	const std::vector<int32_t> &rightRunnersUp() const { return runners_[1]; }
 	const std::vector<double> &rightMinCosts() const { return minCosts_[1]; }
 	const std::vector<double> &rightSecondCosts() const { return secondCosts_[1]; }
+
+	// Sub-pixel depth (NOT IN THE REFERENCE; option "subpixel", stereo_recon_hip.h): off (default) nothing
+	// changes.  On, each WTA pass refines its map before the cross-check: a parabola through the costs of the winner and of
+	// its two neighbours on the pixel's curve places the match between two pixels of the other view, and the depth is
+	// triangulated there.  After computeDepthMaps(): delta per pixel of each map (0 where the pixel was not refined; > 0
+	// towards the neighbour of larger depth), in RECTIFIED coordinates and size under setRectify, as the winners are.  Empty
+	// vectors when the option is off, or under setUseMRF(true) / setUseSGM(true) (no scan makes those maps).
+	void setSubpixel(bool on) { subpixelOn = on; }
+	bool subpixel() const { return subpixelOn; }
+	const std::vector<double> &leftSubpixelDelta() const { return subDelta_[0]; }
+	const std::vector<double> &rightSubpixelDelta() const { return subDelta_[1]; }
 	// the MRF stage (a USE_MRF build of the reference; PARITY UNPINNED, stereo_recon_hip.h): off (default) = the WTA; on, each
 	// map comes from TRW-S over the label cost volume (srh_twoview_compute_mrf: progress 1, 2 "Optimizing...", 3, 4, 5, 8),
 	// cross-check and optional hole filling unchanged.  Cancellation is observed at every progress step.
@@ -222,6 +233,8 @@ private:
 	int costKind = SRH_COST_NCC;
 	int sadDenseOn = 0;
 	int wtaFlags = 0;
+	bool subpixelOn = false;
+	std::vector<double> subDelta_[2];
 	std::vector<int32_t> winners_[2], runners_[2];
 	std::vector<double> minCosts_[2], secondCosts_[2];
 	bool useMrf = false;
