@@ -2851,7 +2851,6 @@ static int mvs_generic_run(srh_context *c, const Lane &lane, int view, const int
 	const int T = (2*p->window_radius + 1)*(2*p->window_radius + 1);
 	const int rows = band_rows(c, W, H, T);
 	if ((rc = lane.mem->band.wbuf.ensure(wbuf_doubles(W, rows, T)))) return rc;
-	if ((rc = lane.mem->band.cost.ensure((size_t)rows*W*2*(size_t)std::max(nneigh, 1)))) return rc;   // per-neighbour best (cost, depth)
 	HIP_TRY(hipMemsetAsync(lane.mem->cnt, 0, sizeof(Counters), lane.stream));
 	for (int by = y0; by < y1; by += rows) {
 		if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
@@ -2859,7 +2858,7 @@ static int mvs_generic_run(srh_context *c, const Lane &lane, int view, const int
 		run_weights(c, lane, view, W, *p, by, nr, SRH_WTILE);
 		{ Scope s(c, lane.stream, "mvs_generic_kernel");
 		  launch_mvs_generic(lane.stream, c->d_views, view, neigh, nneigh, W, *p, by, nr, lane.mem->band.wbuf, SRH_WTILE,
-		                     (double *)peaks_dev, c->force_generic ? nullptr : lane.mem->band.cost, lane.mem->cnt); }
+		                     (double *)peaks_dev, lane.mem->cnt); }
 	}
 	HIP_TRY(hipGetLastError());
 	c->stats.used_dense_path = 0;

@@ -134,7 +134,7 @@ void launch_twoview_cross_check(hipStream_t st, const ViewDev *views, int self, 
                                 const srh_params &P);
 void launch_mvs_generic(hipStream_t st, const ViewDev *views, int ref, const int32_t *neigh, int nneigh, int width,
                         const srh_params &P, int y0, int nrows, const double *wbuf, size_t wstride,
-                        double *peaks, double *best, Counters *cnt);
+                        double *peaks, Counters *cnt);
 void launch_mvs_cross_check(hipStream_t st, const ViewDev *views, const int32_t *slots_dev, int nviews,
                             int view_index, int w, int h, const srh_params &P);
 

@@ -526,14 +526,11 @@ struct MvsRegVisitor {
 	}
 };
 
-// `best` != nullptr: blockIdx.y selects ONE neighbour and the thread leaves its largest (cost, depth)
-// pair in best[(blockIdx.y*npix + q)*2 ..]; mvs_combine_kernel takes the maximum over the neighbours
-// (the non-MRF result is a maximum over all candidates, so the neighbours can run side by side).
 template <int R>
 __global__ __launch_bounds__(128)
 void mvs_reg_kernel(const ViewDev *__restrict__ views, int ref, NeighList nl, int nneigh, srh_params P,
                     int y0, int nrows, const double *__restrict__ wbuf, size_t wstride,
-                    double *__restrict__ peaks, double *__restrict__ best, Counters *__restrict__ cnt)
+                    double *__restrict__ peaks, Counters *__restrict__ cnt)
 {
 	constexpr int WS = 2*R + 1, T = WS*WS;
 	const ViewDev &A = views[ref];
@@ -581,8 +578,7 @@ void mvs_reg_kernel(const ViewDev *__restrict__ views, int ref, NeighList nl, in
 			}
 			const Ray ray = cam_unproject(A.cam, (x + 0.5) / P.image_scale, (y + 0.5) / P.image_scale);
 			MvsRegVisitor<R> vis = { A, &A, P, ray, w, a, x, y, okL, all, tw, s2, 0.0, -1.0, pk, 0, 0, 0, &A, false };
-			const int nfirst = best ? (int)blockIdx.y : 0, nlast = best ? (int)blockIdx.y + 1 : nneigh;
-			for (int ni = nfirst; ni < nlast; ++ni) {
+			for (int ni = 0; ni < nneigh; ++ni) {
 				const int v2 = nl.n[ni];
 				vis.B = &views[v2];
 				walk_curve<true>(ray, A.cam, views[v2], P, vis);
@@ -590,13 +586,8 @@ void mvs_reg_kernel(const ViewDev *__restrict__ views, int ref, NeighList nl, in
 			vis.finish();
 			n_eval = vis.n;
 			depth = vis.bestDepth;
-			if (best) {
-				double *b = best + ((size_t)blockIdx.y*((size_t)nrows*W) + q)*2;
-				b[0] = vis.bestCost; b[1] = vis.bestDepth;
-				if (blockIdx.y != 0) n_pix = 0;
-			}
 		}
-		if (!best) A.depth[pv] = depth;
+		A.depth[pv] = depth;
 	}
 	block_count_add(&cnt->n_eval, n_eval);
 	block_count_add(&cnt->n_eval_device, n_eval);
@@ -1550,20 +1541,13 @@ __global__ void mvs_combine_kernel(const ViewDev *__restrict__ views, int ref, i
 
 void launch_mvs_generic(hipStream_t st, const ViewDev *views, int ref, const int32_t *neigh, int nneigh, int width,
                         const srh_params &P, int y0, int nrows, const double *wbuf, size_t wstride,
-                        double *peaks, double *best, Counters *cnt)
+                        double *peaks, Counters *cnt)
 {
 	const size_t n = (size_t)nrows*width;
 	const NeighList nl = make_neigh_list(neigh, nneigh);
 	if (P.window_radius == 2) {
-		if (best && !peaks && nneigh > 1) {                         // neighbours side by side + maximum
-			hipLaunchKernelGGL(mvs_reg_kernel<2>, dim3((unsigned)((n + 127)/128), (unsigned)nneigh), dim3(128), 0, st,
-			                   views, ref, nl, nneigh, P, y0, nrows, wbuf, wstride, peaks, best, cnt);
-			hipLaunchKernelGGL(mvs_combine_kernel, dim3((unsigned)((n + 255)/256)), dim3(256), 0, st,
-			                   views, ref, nneigh, y0, nrows, best, (const double *)nullptr, (double *)nullptr, 0);
-			return;
-		}
 		hipLaunchKernelGGL(mvs_reg_kernel<2>, dim3((unsigned)((n + 127)/128)), dim3(128), 0, st,
-		                   views, ref, nl, nneigh, P, y0, nrows, wbuf, wstride, peaks, (double *)nullptr, cnt);
+		                   views, ref, nl, nneigh, P, y0, nrows, wbuf, wstride, peaks, cnt);
 		return;
 	}
 	hipLaunchKernelGGL(mvs_generic_kernel, dim3((unsigned)((n + 127)/128)), dim3(128), 0, st,

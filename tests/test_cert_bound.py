@@ -200,8 +200,9 @@ def place_sum3(w, base, noise, tw, target):
     return hi
 
 
-@pytest.mark.parametrize("radius", [5, 2])
+@pytest.mark.parametrize("radius", [5, 2, 1, 3, 4])
 def test_twoview_bound_at_the_certification_thresholds(radius):
+    # (r = 1, 3, 4: the list kernels' instantiations run the certified arithmetic too -- 9, 49 and 81 taps, 60 windows as at r = 2)
     p = capi.params_twoview(window_radius=radius)
     cb = capi.cert_bound(p)
     assert cb["ok"] == 1 and cb["taps"] == (2 * radius + 1) ** 2

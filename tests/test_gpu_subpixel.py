@@ -93,10 +93,16 @@ def test_against_the_cpu_reference(hip_ctx, name):
     within 1e-9 relative.  Left out: a pixel whose winner already disagrees (the decision-gap rule of
     test_gpu_wta_outputs.py), or that the reference's own numbers put within that error of a class boundary: D <= 4e or
     ||delta| - 0.5| <= 3e/D.  At most 1 % of the WHITE pixels."""
-    case = cases.get_twoview(name)
+    compare_with_the_cpu_reference(hip_ctx, name, cases.get_twoview(name))
+
+
+def compare_with_the_cpu_reference(hip_ctx, name, case):
+    """the comparison of test_against_the_cpu_reference on any case (tests/test_gpu_radii_twoview.py: other radii); `name`
+    keys the shared reference and tags the messages -> per direction (pixels left out, class counts)"""
     p = _setup(hip_ctx, case)
     imgs, ocams, op = cases.oracle_inputs(case)
     reference = _reference(name, case)
+    figures = []
     for k, (ref, oth) in enumerate(DIRECTIONS):
         integer, diag, want = reference[k]
         with _options(hip_ctx, subpixel=1, wta_outputs=3):
@@ -133,6 +139,8 @@ def test_against_the_cpu_reference(hip_ctx, name):
         assert ok, "%s %d>%d: %s" % (name, ref, oth, msg)
         assert (got["cls"][~white] == SR.NONE).all() and (got["neigh_xy"][~white] == -1).all() and (got["delta"][~white] == 0).all()
         assert (got["delta"][got["cls"] != SR.REFINED] == 0).all()
+        figures.append((left_out, np.bincount(got["cls"].ravel(), minlength=5)))
+    return figures
 
 
 # ---------------------------------------------------------------------------------------------- 2. bit-exact replay

@@ -102,6 +102,27 @@ def _close(got, want):
     return ok
 
 
+def compare_planes_with_the_oracle(got, diag, white, imgs, ocams, op, ref, oth, name):
+    """The decision-gap rule: winners equal and both costs within 1e-9 relative of the oracle's diagnostics, except at pixels
+    whose closest decision the oracle's own replay puts within 1e-7 of flipping -- at most 1 % of the WHITE pixels; nothing
+    outside the mask.  -> the number of pixels excused (tests/test_gpu_radii_twoview.py applies it at other radii)"""
+    agree = (got["win_xy"] == diag["win_xy"]).all(axis=2) & _close(got["min_cost"], diag["min_cost"]) & \
+        _close(got["second_cost"], diag["second_cost"])
+    bad = np.argwhere(~agree)
+    print("%s %d>%d: %d of %d WHITE pixels disagree with the oracle" % (name, ref, oth, len(bad), white.sum()))
+    for y, x in bad:
+        gap = _decision_gap(imgs, ocams, op, ref, oth, int(x), int(y))
+        print("  (%d,%d): win %s / %s, min %r / %r, second %r / %r, decision gap %.3g" % (
+            x, y, got["win_xy"][y, x], diag["win_xy"][y, x], got["min_cost"][y, x], diag["min_cost"][y, x],
+            got["second_cost"][y, x], diag["second_cost"][y, x], gap))
+        assert gap <= 1e-7, "%s %d>%d pixel (%d,%d): disagrees with the oracle, no decision within 1e-7 of flipping (gap %g)" % (name, ref, oth, x, y, gap)
+    assert len(bad) <= 0.01 * white.sum()
+    # outside the mask: nothing
+    assert (got["win_xy"][~white] == -1).all() and (got["runner_xy"][~white] == -1).all()
+    assert np.isposinf(got["min_cost"][~white]).all() and np.isposinf(got["second_cost"][~white]).all()
+    return len(bad)
+
+
 @pytest.mark.parametrize("name", ORACLE_CASES)
 def test_planes_against_the_oracle(hip_ctx, name):
     case, p = _setup(hip_ctx, name)
@@ -111,20 +132,7 @@ def test_planes_against_the_oracle(hip_ctx, name):
         with _options(hip_ctx, wta_outputs=3):
             _, got, _ = _pass(hip_ctx, ref, oth, p)
         white = case["views"][ref][1] == 1
-        agree = (got["win_xy"] == diag["win_xy"]).all(axis=2) & _close(got["min_cost"], diag["min_cost"]) & \
-            _close(got["second_cost"], diag["second_cost"])
-        bad = np.argwhere(~agree)
-        print("%s %d>%d: %d of %d WHITE pixels disagree with the oracle" % (name, ref, oth, len(bad), white.sum()))
-        for y, x in bad:
-            gap = _decision_gap(imgs, ocams, op, ref, oth, int(x), int(y))
-            print("  (%d,%d): win %s / %s, min %r / %r, second %r / %r, decision gap %.3g" % (
-                x, y, got["win_xy"][y, x], diag["win_xy"][y, x], got["min_cost"][y, x], diag["min_cost"][y, x],
-                got["second_cost"][y, x], diag["second_cost"][y, x], gap))
-            assert gap <= 1e-7, "%s %d>%d pixel (%d,%d): disagrees with the oracle, no decision within 1e-7 of flipping (gap %g)" % (name, ref, oth, x, y, gap)
-        assert len(bad) <= 0.01 * white.sum()
-        # outside the mask: nothing
-        assert (got["win_xy"][~white] == -1).all() and (got["runner_xy"][~white] == -1).all()
-        assert np.isposinf(got["min_cost"][~white]).all() and np.isposinf(got["second_cost"][~white]).all()
+        compare_planes_with_the_oracle(got, diag, white, imgs, ocams, op, ref, oth, name)
         # the awkward classes occur: no candidate at all, a single improvement (no runner-up)
         none = white & (got["win_xy"][..., 0] < 0)
         single = (got["win_xy"][..., 0] >= 0) & (got["runner_xy"][..., 0] < 0)
