@@ -12,7 +12,15 @@ namespace srh {
 
 // Can every epipolar curve of `a` in `b` stay on its own image row?  Undistorted, non-refractive
 // cameras with the same orientation and the same second and third rows of K, displaced along the
-// camera x axis.  This only *proposes* the dense path: the scan kernel verifies every candidate.
+// camera x axis.  K's FIRST row is not compared: fx and cx may differ per view (srh_twoview_rectify hands over one cx per
+// view), and then a pixel's candidates are no fixed shift of x -- with fx_b != fx_a they slide by (fx_b/fx_a - 1)(x - cx_a).
+// fx_bx = |fx_b * baseline| is the widest range in columns per unit of inverse depth, the plan's stride.
+// This only *proposes* the dense path.  What keeps a proposal right, or refutes it: every pixel's column range is its own
+// (pinhole_column_range projects the pixel's own ray at both ends of the depth range with the other view's K), the scan
+// counts a candidate off its row or outside that range (`ty != y || tx < lo || tx > hi`, Counters::not_row_aligned) and the
+// driver then repeats the pass on the general kernels, and the template scan serves a pixel only under its per-pixel bound
+// or its label-by-label tier (ts_pixel_passes), which know nothing of the rig.  tests/test_gpu_rigs.py holds all of it to
+// the oracle on the rigs of tests/rig_cases.py.
 // (srh_twoview_row_aligned exports it; TvPass::plan calls it.)
 inline bool rig_is_row_aligned(const srh_camera &a, const srh_camera &b, double *fx_bx) {
 	if (a.is_distorted || b.is_distorted || a.is_refractive || b.is_refractive) return false;

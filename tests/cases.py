@@ -24,6 +24,15 @@ def _rot_z(a):
     return np.array([[c, -s, 0], [s, c, 0], [0, 0, 1]])
 
 
+def object_masks(w, h):
+    """the left and right masks of twoview_case(masks=True): two ellipses, the left one with a hole (tests/rig_cases.py too)"""
+    yy, xx = np.mgrid[0:h, 0:w]
+    ml = (((xx - w * 0.45) ** 2 / (w * 0.42) ** 2 + (yy - h * 0.5) ** 2 / (h * 0.45) ** 2) < 1).astype(np.uint8)
+    mr = (((xx - w * 0.40) ** 2 / (w * 0.45) ** 2 + (yy - h * 0.5) ** 2 / (h * 0.47) ** 2) < 1).astype(np.uint8)
+    ml[h // 3, w // 3:w // 3 + 5] = 0          # a hole inside the object
+    return ml, mr
+
+
 def twoview_case(name, w=64, h=40, D=16, seed=0x5EED0A00, weight_kind=1, radius=5,
                  masks=False, distortion=False, verged=False, refractive=False, scale=1.0):
     """A two-view scene on the synthetic rectified pair, optionally perturbed."""
@@ -49,10 +58,7 @@ def twoview_case(name, w=64, h=40, D=16, seed=0x5EED0A00, weight_kind=1, radius=
     if refractive:
         plane = (np.array([0.0, 0.0, 1.0]), 0.1, 1.333)
     if masks:
-        yy, xx = np.mgrid[0:h, 0:w]
-        ml = (((xx - w * 0.45) ** 2 / (w * 0.42) ** 2 + (yy - h * 0.5) ** 2 / (h * 0.45) ** 2) < 1).astype(np.uint8)
-        mr = (((xx - w * 0.40) ** 2 / (w * 0.45) ** 2 + (yy - h * 0.5) ** 2 / (h * 0.47) ** 2) < 1).astype(np.uint8)
-        ml[h // 3, w // 3:w // 3 + 5] = 0          # a hole inside the object
+        ml, mr = object_masks(w, h)
     params = dict(min_depth=zmin, max_depth=zmax, num_depth_levels=D, window_radius=radius,
                   weight_kind=weight_kind, image_scale=scale)
     views = [(L, ml, (Kl, Rl, tl), dist_l, plane), (R, mr, (Kr, Rr, tr), dist_r, plane)]

@@ -56,21 +56,30 @@ def _options(ctx, **opts):
 
 @functools.lru_cache(maxsize=None)
 def _case(shape, radius, kind, masks=False, general=False):
-    case = SS.small_twoview(*shape, radius, kind, masks=masks, verged=general, distortion=general)
+    return case_inputs(SS.small_twoview(*shape, radius, kind, masks=masks, verged=general, distortion=general))
+
+
+def case_inputs(case):
+    """a case dict with its oracle and library inputs (tests/test_gpu_rigs.py builds its cases with this too)"""
     imgs, ocams, op = cases.oracle_inputs(case)
     cams, p = cases.hip_inputs(case)
-    return types.SimpleNamespace(case=case, imgs=imgs, ocams=ocams, op=op, cams=cams, p=p, w=shape[0], h=shape[1],
+    h, w = case["views"][0][1].shape
+    return types.SimpleNamespace(case=case, imgs=imgs, ocams=ocams, op=op, cams=cams, p=p, w=w, h=h,
                                  white=[v[1] == 1 for v in case["views"]], tag=case["name"])
+
+
+def oracle_passes(c):
+    """the CPU oracle's two passes on case `c`, (depth, diag) each"""
+    out = [O.twoview_wta(c.imgs[r], c.imgs[o], c.ocams[r], c.ocams[o], c.op, want_diag=True) for r, o in DIRECTIONS]
+    for d, diag in out:
+        d.setflags(write=False)
+    return out
 
 
 @functools.lru_cache(maxsize=None)
 def _oracle(shape, radius, kind, masks=False, general=False):
     """the CPU oracle's two passes, (depth, diag) each: computed once, shared, never written to"""
-    c = _case(shape, radius, kind, masks, general)
-    out = [O.twoview_wta(c.imgs[r], c.imgs[o], c.ocams[r], c.ocams[o], c.op, want_diag=True) for r, o in DIRECTIONS]
-    for d, diag in out:
-        d.setflags(write=False)
-    return out
+    return oracle_passes(_case(shape, radius, kind, masks, general))
 
 
 def _upload(ctx, c):
@@ -130,12 +139,19 @@ DECLINES = {
 @kinds
 @_shapes(SS.TWOVIEW_SHAPES)
 def test_every_rectified_path_gives_the_walk_kernels_bits(hip_ctx, shape, radius, kind):
-    c = _case(shape, radius, kind)
+    check_every_rectified_path(hip_ctx, _case(shape, radius, kind), lambda tag: DECLINES.get((shape, radius, tag)),
+                               windows=(radius, kind) == (5, 1))
+
+
+def check_every_rectified_path(hip_ctx, c, declined, windows=False):
+    """every entry of PATHS on case `c` against the walk kernel; declined(tag) -> the rule by which the driver declines the
+    path on this case, or None; windows: check the windows kernel each path launches too (tests/test_gpu_rigs.py shares this)"""
+    check_windows = windows
     _upload(hip_ctx, c)
     want = WO._yardstick(hip_ctx, c.p)
     for tag, opts, ran in PATHS:
-        declines = (shape, radius, tag) in DECLINES
-        windows = WINDOW_KERNELS.get(tag) if (radius, kind) == (5, 1) and not declines else None
+        declines = declined(tag) is not None
+        windows = WINDOW_KERNELS.get(tag) if check_windows and not declines else None
         with _options(hip_ctx, wta_outputs=3, **opts):
             for k, (ref, oth) in enumerate(DIRECTIONS):
                 if windows:
@@ -152,7 +168,7 @@ def test_every_rectified_path_gives_the_walk_kernels_bits(hip_ctx, shape, radius
                     launched = set(hip_ctx.profile().keys())
                     assert windows[0] in launched and windows[1] not in launched, "%s: windows by %s" % (what, sorted(k for k in launched if "geodesic" in k or "weights" in k))
                 if declines:
-                    assert not ran(st), "%s: listed as declined (%s), but the path ran: %s" % (what, DECLINES[(shape, radius, tag)], st)
+                    assert not ran(st), "%s: listed as declined (%s), but the path ran: %s" % (what, declined(tag), st)
                 else:
                     assert ran(st), "%s: the intended path did not run: %s" % (what, st)
                 WO._same_planes(got, want[k][1], what)
@@ -317,7 +333,10 @@ def test_exact_cost_rows_against_the_oracle(hip_ctx, shape, radius, kind, masks)
 @kinds
 @_shapes(SS.TWOVIEW_SHAPES)
 def test_sad_maps_on_both_plans(hip_ctx, shape, radius, kind, masks):
-    c = _case(shape, radius, kind, masks)
+    check_sad_maps_on_both_plans(hip_ctx, _case(shape, radius, kind, masks))
+
+
+def check_sad_maps_on_both_plans(hip_ctx, c):
     _upload(hip_ctx, c)
     want = [S.twoview_wta_sad(c.imgs[r], c.imgs[o], c.ocams[r], c.ocams[o], c.op) for r, o in DIRECTIONS]
     got = {}
@@ -339,7 +358,13 @@ def test_sad_maps_on_both_plans(hip_ctx, shape, radius, kind, masks):
 @kinds
 @_shapes([(9, 4, 8), (12, 12, 8), (33, 9, 40), (65, 12, 8)])
 def test_rows_one_at_a_time_give_the_whole_pass(hip_ctx, shape, radius, kind, opts):
-    c = _case(shape, radius, kind)
+    check_row_bands_give_the_whole_pass(hip_ctx, _case(shape, radius, kind), opts)
+
+
+def check_row_bands_give_the_whole_pass(hip_ctx, c, opts, bands=None):
+    """`bands`: the (y0, y1) the pass is split into, every row on its own by default"""
+    bands = [(y, y + 1) for y in range(c.h)] if bands is None else bands
+    assert sorted(y for y0, y1 in bands for y in range(y0, y1)) == list(range(c.h))
     _upload(hip_ctx, c)
     blank = np.full((c.h, c.w), np.nan)
     for ref, oth in DIRECTIONS:
@@ -348,9 +373,9 @@ def test_rows_one_at_a_time_give_the_whole_pass(hip_ctx, shape, radius, kind, op
             whole = hip_ctx.download_depth(ref)
             hip_ctx.upload_depth(ref, blank)
             assert np.isnan(hip_ctx.download_depth(ref)).all()
-            for y in range(c.h):
-                hip_ctx.twoview_wta(ref, oth, c.p, y, y + 1)
-            _assert_bits(hip_ctx.download_depth(ref), whole, "%s %s %d>%d row by row" % (c.tag, opts, ref, oth))
+            for y0, y1 in bands:
+                hip_ctx.twoview_wta(ref, oth, c.p, y0, y1)
+            _assert_bits(hip_ctx.download_depth(ref), whole, "%s %s %d>%d in %d bands" % (c.tag, opts, ref, oth, len(bands)))
         assert not np.isnan(whole).all()
 
 
@@ -361,8 +386,11 @@ COMPUTE_CASES = [(s, False) for s in SS.TWOVIEW_SHAPES] + [(s, True) for s in ((
 @kinds
 @pytest.mark.parametrize("shape,masks", COMPUTE_CASES, ids=[SS.shape_id(s) + ("-masks" if m else "") for s, m in COMPUTE_CASES])
 def test_compute_against_the_oracles_passes_and_cross_check(hip_ctx, shape, masks, radius, kind):
-    c = _case(shape, radius, kind, masks)
-    (dl, _), (dr, _) = _oracle(shape, radius, kind, masks)
+    check_compute(hip_ctx, _case(shape, radius, kind, masks), _oracle(shape, radius, kind, masks))
+
+
+def check_compute(hip_ctx, c, oracle):
+    (dl, _), (dr, _) = oracle
     want = O.twoview_cross_check(c.ocams[0], c.ocams[1], c.op, dl, dr)
     _upload(hip_ctx, c)
     for overlap in (1, 0):
@@ -489,7 +517,10 @@ def test_mvs_staged_and_gathering_kernels_both_take_waves(hip_ctx, kind, distort
 @kinds
 @_shapes([(5, 5, 3), (9, 4, 8), (33, 9, 40)])
 def test_label_costs(hip_ctx, shape, radius, kind):
-    c = _case(shape, radius, kind)
+    check_label_costs(hip_ctx, _case(shape, radius, kind))
+
+
+def check_label_costs(hip_ctx, c):
     _upload(hip_ctx, c)
     fill = MR.fill_value(c.p.window_radius, c.p.bad_ret)
     for ref, oth in DIRECTIONS:
