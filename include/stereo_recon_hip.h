@@ -283,6 +283,9 @@ enum { SRH_WTA_WINNERS = 1, SRH_WTA_COSTS = 2 };
  *                     costs as under "wta_outputs" = 3; what srh_view_wta_outputs* show is still what "wta_outputs" asked
  *                     for.  Read with srh_view_subpixel*.  No effect on srh_twoview_compute_mrf / _sgm (no scan runs there)
  *                     and on MultiViewStereo.  Other values: SRH_E_INVALID.
+ *   "mvs_subpixel_search"  how srh_mvs_view_subpixel finds a pixel's winner: 0 (default) among the curve pixels near the
+ *                     projection of the pixel's point, exhaustively where that finds none; 1: exhaustively everywhere (the
+ *                     same planes: the law the default is tested against).  Other values: SRH_E_INVALID.
  *   "filter_invalid"  0 (default, as the reference's call site under #if 0): srh_twoview_compute ends with the cross-check;
  *                     SRH_FILTER_* flags (1 gaps, 2 median, 3 both): it then runs srh_view_filter_invalid on both maps,
  *                     with progress steps 6 "Filling invalid pixels..." and, with the median, 7 "Filtering invalid pixels..."
@@ -384,6 +387,34 @@ typedef struct srh_subpixel_info {
 int  srh_view_subpixel(srh_context *ctx, int slot, double *delta, int32_t *neigh_xy, uint8_t *cls);
 int  srh_view_subpixel_device(srh_context *ctx, int slot, void **delta, void **neigh_xy, void **cls);
 int  srh_view_subpixel_info(srh_context *ctx, int slot, srh_subpixel_info *info);
+/* Sub-pixel depth for a MultiViewStereo view, as a stage of its own on the slot's FINISHED depth map: no
+ * estimator keeps the (neighbour, pixel) that gave a depth, but the map identifies it.  Per pixel of view_slot, z0 its depth:
+ *   SRH_SUBPX_NONE          outside the mask, z0 not finite, or z0 <= 0 (NaN, +INF, the "no peak" value -1)
+ *   the winner              the first (i, q) -- neighbours in the order of neigh_slots, q in the order of the pixel's
+ *                           MultiViewStereo curve in that neighbour -- whose candidate depth equals z0 bit for bit
+ *   SRH_SUBPX_NO_WINNER     there is none: the depth is no candidate depth of these neighbours
+ *   n-, n+, the classes     as under option "subpixel", on the winner's curve, with the free cost_ncc of MultiViewStereo
+ *                           (higher is better) of the pixel against n-, the winner and n+: classify(-c-, -c0, -c+)
+ * IT REFINES WHATEVER THE SLOT HOLDS, whichever call made it -- srh_mvs_initial_estimate, _mrf, _sgm or srh_view_depth_upload
+ * -- so call it once per estimate, before srh_view_filter_speckles and srh_mvs_cross_check, with the neighbour list the
+ * estimate used.  A refined map identifies no winner: a second call leaves NO_WINNER nearly everywhere and changes (nearly)
+ * nothing; it is idempotent only by that accident.
+ * The winner is searched among the curve pixels near the projection of the pixel's point at z0 into each neighbour, and a
+ * pixel with no winner there is searched exhaustively (info->n_fallback counts those); option "mvs_subpixel_search" = 1
+ * searches every pixel exhaustively: the same planes, several times the work.
+ * win: w*h*3 int32 per pixel -- the index into neigh_slots, then cx, cy; (-1, -1, -1) = none.  delta, neigh_xy, cls: as
+ * srh_view_subpixel.  All four are HOST buffers and each may be NULL; info may be NULL.  Synchronous; whatever "mvs_async"
+ * has in flight is completed first.  The support windows are computed band by band ("band_budget_mb").  nneigh 0..8.
+ * SRH_E_INVALID: a slot without an image, view_slot among its neighbours, nneigh out of range.  Nothing of the stage is
+ * allocated or launched unless it is called. */
+enum { SRH_SUBPX_NO_WINNER = 5 };
+typedef struct srh_mvs_subpixel_info {
+	int64_t n_class[6];          /* pixels per SRH_SUBPX_* class, SRH_SUBPX_NO_WINNER included */
+	int64_t n_moved;             /* of the REFINED ones: delta != 0 */
+	int64_t n_fallback;          /* pixels the narrowed search handed to the exhaustive one (the NO_WINNER ones among them) */
+} srh_mvs_subpixel_info;
+int  srh_mvs_view_subpixel(srh_context *ctx, int view_slot, const int32_t *neigh_slots, int nneigh, const srh_params *p,
+                           srh_mvs_subpixel_info *info, double *delta, int32_t *win, int32_t *neigh_xy, uint8_t *cls);
 /* Asynchronous device-to-device copy of the slot's depth map (w*h doubles) into caller-owned
  * DEVICE memory of `dst_bytes` bytes (e.g. a tensor that RCCL then gathers); ordered on the context
  * stream.  SRH_E_INVALID when the buffer is smaller than the map (views may differ in size). */

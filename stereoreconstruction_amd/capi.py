@@ -140,6 +140,11 @@ class SubpixelInfo(C.Structure):
     _fields_ = [("n_class", C.c_int64 * 5), ("n_moved", C.c_int64)]
 
 
+class MvsSubpixelInfo(C.Structure):
+    """srh_mvs_subpixel_info"""
+    _fields_ = [("n_class", C.c_int64 * 6), ("n_moved", C.c_int64), ("n_fallback", C.c_int64)]
+
+
 # srh_view_filter_speckles flag: the reject value is NaN, not +INF
 SPECKLE_TO_NAN = 1
 
@@ -169,6 +174,8 @@ COST_NCC, COST_SAD = 0, 1
 WTA_WINNERS, WTA_COSTS = 1, 2
 # option "subpixel": what the refinement did to a pixel (SRH_SUBPX_*)
 SUBPX_NONE, SUBPX_NO_NEIGHBOUR, SUBPX_FLAT, SUBPX_OUTSIDE, SUBPX_REFINED = 0, 1, 2, 3, 4
+# srh_mvs_view_subpixel only: the depth is no candidate depth of the neighbours given
+SUBPX_NO_WINNER = 5
 # scaling at file resolution (SRH_SCALE_*, SRH_MASK_*)
 SCALE_SMOOTH, SCALE_FAST = 0, 1
 MASK_NONE, MASK_ALPHA_FAST, MASK_IMAGE_SMOOTH = 0, 1, 2
@@ -186,7 +193,7 @@ EXPORTS = [
     "srh_view_depth_download", "srh_view_depth_upload",
     "srh_view_depth_device_ptr", "srh_view_depth_copy_to_device", "srh_view_depth_copy_from_device",
     "srh_view_wta_outputs", "srh_view_wta_outputs_device", "srh_view_wta_outputs_state",
-    "srh_view_subpixel", "srh_view_subpixel_device", "srh_view_subpixel_info",
+    "srh_view_subpixel", "srh_view_subpixel_device", "srh_view_subpixel_info", "srh_mvs_view_subpixel",
     "srh_twoview_wta", "srh_twoview_cross_check", "srh_twoview_compute", "srh_twoview_cost_rows", "srh_twoview_pair_costs", "srh_debug_exp",
     "srh_mvs_initial_estimate", "srh_mvs_cross_check", "srh_view_point_cloud", "srh_view_filter_invalid",
     "srh_speckle_params_defaults", "srh_view_filter_speckles",
@@ -280,6 +287,8 @@ def lib():
     L.srh_view_subpixel.argtypes = [vp, C.c_int, c_double_p, c_int32_p, C.POINTER(C.c_uint8)]
     L.srh_view_subpixel_device.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.srh_view_subpixel_info.argtypes = [vp, C.c_int, C.POINTER(SubpixelInfo)]
+    L.srh_mvs_view_subpixel.argtypes = [vp, C.c_int, c_int32_p, C.c_int, C.POINTER(Params), C.POINTER(MvsSubpixelInfo),
+                                        c_double_p, c_int32_p, c_int32_p, C.POINTER(C.c_uint8)]
     L.srh_mrf_params_defaults.argtypes = [C.POINTER(SrhMrfParams)]
     L.srh_mrf_params_defaults.restype = None
     L.srh_mvs_mrf_estimate.argtypes = [vp, C.c_int, C.c_int, C.c_void_p, C.POINTER(SrhMrfParams), C.POINTER(SrhMrfInfo)]
@@ -817,6 +826,26 @@ class Context:
         ng = np.ascontiguousarray(neigh_slots, dtype=np.int32)
         _check(lib().srh_mvs_initial_estimate(self._h, view_slot, ng.ctypes.data_as(c_int32_p), len(ng),
                                               C.byref(p), y0, y1, C.c_void_p(peaks_dev) if peaks_dev else None))
+
+    def mvs_view_subpixel(self, view_slot, neigh_slots, p, want_planes=False):
+        """Sub-pixel depth for the slot's finished depth map (srh_mvs_view_subpixel): it refines whatever the slot holds, so
+        call it once per estimate, with the estimate's neighbour list.  -> dict(n_class = pixels per SUBPX_* class (6
+        ints, SUBPX_NO_WINNER last), n_moved, n_fallback); with want_planes also delta (h, w), win (h, w, 3) int32 =
+        (index into neigh_slots, cx, cy), neigh_xy (h, w, 4) int32 and cls (h, w) uint8."""
+        ng = np.ascontiguousarray(neigh_slots, dtype=np.int32)
+        i = MvsSubpixelInfo()
+        out = {}
+        if want_planes:
+            w, h = self.view_size(view_slot)
+            out = {"delta": np.empty((h, w), dtype=np.float64), "win": np.empty((h, w, 3), dtype=np.int32),
+                   "neigh_xy": np.empty((h, w, 4), dtype=np.int32), "cls": np.empty((h, w), dtype=np.uint8)}
+        _check(lib().srh_mvs_view_subpixel(self._h, view_slot, ng.ctypes.data_as(c_int32_p), len(ng), C.byref(p), C.byref(i),
+                                           _dptr(out["delta"]) if want_planes else None,
+                                           out["win"].ctypes.data_as(c_int32_p) if want_planes else None,
+                                           out["neigh_xy"].ctypes.data_as(c_int32_p) if want_planes else None,
+                                           out["cls"].ctypes.data_as(C.POINTER(C.c_uint8)) if want_planes else None))
+        out.update(n_class=[int(v) for v in i.n_class], n_moved=int(i.n_moved), n_fallback=int(i.n_fallback))
+        return out
 
     def mvs_cross_check(self, slots, view_index, p):
         s = np.ascontiguousarray(slots, dtype=np.int32)

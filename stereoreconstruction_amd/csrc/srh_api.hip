@@ -4,6 +4,7 @@
 // a HIP device srh_create fails with SRH_E_NO_DEVICE.
 #include "srh_internal.hpp"
 #include "srh_subpixel.hpp"
+#include "srh_mvs_subpixel.hpp"
 #include "srh_geom.hpp"
 #include "srh_walk.hpp"
 #include "srh_speckle.hpp"
@@ -319,6 +320,8 @@ struct srh_context {
 	hipEvent_t views_go = nullptr;                                  //   which start behind this event on the context's stream
 	void *mrf_host = nullptr;                                       // pinned: per view {energy, pad, status[4]}
 	DevBuf<double> mrf_peaks;                           // top-K peaks of srh_mvs_initial_estimate_mrf
+	DevBuf<double> mvs_subpx;                           // srh_mvs_view_subpixel: the call's counters and planes (allocated by the first call)
+	int mvs_subpx_search = 0;                           // option "mvs_subpixel_search": 1 = the winner search is exhaustive for every pixel
 	double *mvsgm_host = nullptr;                       // pinned: one energy per view of the MultiView aggregation
 	// the label-volume stages (LabelStage above): the scratch of each is carved by its kernel file's layout
 	LabelStage mrf   { "single-view MRF", "MRF", 'K' };             // MultiViewStereo TRW-S (srh_mrf.hip)
@@ -831,6 +834,7 @@ extern "C" void srh_destroy(srh_context *c) {
 		if (T.done) hipEventDestroy(T.done);
 	}
 	c->mrf_peaks.release();
+	c->mvs_subpx.release();
 	for (LabelStage *S : c->label_stages) S->release();
 	c->fuse_result.release(); c->fuse_scratch.release();
 	for (int i = 0; i < SRH_MAX_VIEWS; ++i) if (c->mrf_stream[i]) hipStreamDestroy(c->mrf_stream[i]);
@@ -930,6 +934,10 @@ extern "C" int srh_set_option(srh_context *c, const char *name, long value) {
 	if (!strcmp(name, "subpixel")) {
 		if (value != 0 && value != 1) return fail(SRH_E_INVALID, "subpixel must be 0 or 1");
 		c->subpixel = (int)value; return SRH_OK;
+	}
+	if (!strcmp(name, "mvs_subpixel_search")) {
+		if (value != 0 && value != 1) return fail(SRH_E_INVALID, "mvs_subpixel_search must be 0 or 1");
+		c->mvs_subpx_search = (int)value; return SRH_OK;
 	}
 	if (!strcmp(name, "tscan")) { c->tscan = value != 0; return SRH_OK; }
 	if (!strcmp(name, "tscan_bound")) { c->tscan_bound = value != 0; return SRH_OK; }
@@ -2891,6 +2899,67 @@ extern "C" int srh_mvs_initial_estimate(srh_context *c, int view, const int32_t 
 	if (!c) return fail(SRH_E_INVALID, "null context");
 	return with_thinner_bands(c, [&] { return mvs_initial_estimate_run(c, view, neigh, nneigh, p, y0, y1, peaks_dev); });
 }
+
+// ---- sub-pixel depth for a view's finished map (srh_mvs_subpixel.hip): the winner search over the whole view,
+// then band by band the support windows and the refine kernel.  The call's planes live in one block of the context:
+// counters | neigh_xy | delta | win | cls
+extern "C" int srh_mvs_view_subpixel(srh_context *c, int view, const int32_t *neigh, int nneigh, const srh_params *p,
+                                     srh_mvs_subpixel_info *info, double *delta, int32_t *win, int32_t *neigh_xy, uint8_t *cls)
+{
+	int rc;
+	if ((rc = check_slot(c, view, true)) || (rc = check_params(p))) return rc;          // (settles what "mvs_async" has in flight)
+	if (nneigh < 0 || nneigh > SRH_MAX_NEIGH) return fail(SRH_E_INVALID, "nneigh %d outside [0,%d]", nneigh, SRH_MAX_NEIGH);
+	if (nneigh > 0 && !neigh) return fail(SRH_E_INVALID, "null neighbour list");
+	for (int i = 0; i < nneigh; ++i) {
+		if ((rc = check_slot(c, neigh[i], true, false))) return rc;
+		if (neigh[i] == view) return fail(SRH_E_INVALID, "view %d listed as its own neighbour", view);
+	}
+	HIP_TRY(hipSetDevice(c->device));
+	const ViewHost &A = c->views[view];
+	const int W = A.w, H = A.h;
+	const size_t n = (size_t)W*H;
+	const int T = (2*p->window_radius + 1)*(2*p->window_radius + 1);
+	// doubles: 8 counters, 2n of neigh_xy, n of delta, 3n int32 of win (rounded up), n bytes of cls (rounded up)
+	const size_t win_d = (3*n + 1)/2, cls_d = (n + 7)/8;
+	if ((rc = c->mvs_subpx.ensure(SRH_MVSSUB_COUNTERS + n + 2*n + win_d + cls_d))) return rc;
+	unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(c->mvs_subpx.p);
+	int32_t *d_neigh = reinterpret_cast<int32_t *>(c->mvs_subpx + SRH_MVSSUB_COUNTERS);      // (16-byte aligned: stored as int4)
+	double *d_delta = c->mvs_subpx + SRH_MVSSUB_COUNTERS + 2*n;
+	int32_t *d_win = reinterpret_cast<int32_t *>(d_delta + n);
+	uint8_t *d_cls = reinterpret_cast<uint8_t *>(d_delta + n + win_d);
+	const Lane lane = c->main_lane();
+	rc = with_thinner_bands(c, [&] {
+		int rc2;
+		const int rows = band_rows(c, W, H, T);
+		if ((rc2 = lane.mem->band.wbuf.ensure(wbuf_doubles(W, rows, T)))) return rc2;
+		HIP_TRY(hipMemsetAsync(d_cnt, 0, SRH_MVSSUB_COUNTERS*sizeof(unsigned long long), lane.stream));
+		{ Scope s(c, lane.stream, "mvs_subpixel_search_kernel");
+		  launch_mvs_subpixel_search(lane.stream, c->d_views, view, neigh, nneigh, W, *p, 0, H, c->mvs_subpx_search != 0, d_win, d_neigh, d_cls, d_cnt); }
+		for (int by = 0; by < H; by += rows) {
+			const int nr = std::min(rows, H - by);
+			run_weights(c, lane, view, W, *p, by, nr, SRH_WTILE);
+			Scope s(c, lane.stream, "mvs_subpixel_refine_kernel");
+			launch_mvs_subpixel_refine(lane.stream, c->d_views, view, neigh, nneigh, W, *p, by, nr, lane.mem->band.wbuf, d_win, d_neigh, d_cls, d_delta, d_cnt);
+		}
+		HIP_TRY(hipGetLastError());
+		return (int)SRH_OK;
+	});
+	if (rc) return rc;
+	unsigned long long h_cnt[SRH_MVSSUB_COUNTERS] = { 0 };
+	HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, lane.stream));
+	if (delta) HIP_TRY(hipMemcpyAsync(delta, d_delta, n*sizeof(double), hipMemcpyDeviceToHost, lane.stream));
+	if (neigh_xy) HIP_TRY(hipMemcpyAsync(neigh_xy, d_neigh, 4*n*sizeof(int32_t), hipMemcpyDeviceToHost, lane.stream));
+	if (win) HIP_TRY(hipMemcpyAsync(win, d_win, 3*n*sizeof(int32_t), hipMemcpyDeviceToHost, lane.stream));
+	if (cls) HIP_TRY(hipMemcpyAsync(cls, d_cls, n, hipMemcpyDeviceToHost, lane.stream));
+	HIP_TRY(hipStreamSynchronize(lane.stream));
+	if (info) {
+		for (int k = 0; k < 6; ++k) info->n_class[k] = (int64_t)h_cnt[k];
+		info->n_moved = (int64_t)h_cnt[6];
+		info->n_fallback = (int64_t)h_cnt[7];
+	}
+	return SRH_OK;
+}
+
 // the view list travels once per run: MultiViewStereo::crossCheck is called per view with the same list, and a copy per
 // call (from caller memory: with a host wait) put a copy, two dispatch gaps and a host round trip between the kernels
 static int slots_to_device(srh_context *c, const int32_t *slots, int nviews) {

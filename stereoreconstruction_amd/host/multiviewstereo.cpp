@@ -67,6 +67,7 @@ void MultiViewStereo::initialize(const std::vector<CameraPtr> &views_, const std
 	}
 	neighbours.assign(views.size(), std::vector<int>());
 	sgmInfos_.assign(views.size(), srh_sgm_info());
+	subpixelInfos_.clear();
 }
 
 void MultiViewStereo::initialize(ProjectPtr project_, ImageSetPtr imageSet__, const std::vector<CameraPtr> &views_,
@@ -201,6 +202,17 @@ void MultiViewStereo::runTask() {
 		if (rc == SRH_E_CANCELLED || isCancelled()) { srh_set_hooks(ctx_, nullptr, nullptr, nullptr); return; }
 		if (rc != SRH_OK) { error_ = srh_last_error(); srh_set_hooks(ctx_, nullptr, nullptr, nullptr); return; }
 	}
+	if (subpixel_) {
+		// sub-pixel depth (not in the reference): every view's finished map -- the WTA's, the MRF's or the aggregation's --
+		// with the neighbour list its estimate used, before anything else reads it (no step of its own)
+		subpixelInfos_.assign(nv, srh_mvs_subpixel_info());
+		for (int v = 0; v < nv; ++v) {
+			const int rc = srh_mvs_view_subpixel(ctx_, v, &neigh[static_cast<size_t>(v)*params_.num_neighbours], count[v], &params_,
+			                                     &subpixelInfos_[v], nullptr, nullptr, nullptr, nullptr);
+			if (rc == SRH_E_CANCELLED || isCancelled()) { srh_set_hooks(ctx_, nullptr, nullptr, nullptr); return; }
+			if (rc != SRH_OK) { error_ = srh_last_error(); srh_set_hooks(ctx_, nullptr, nullptr, nullptr); return; }
+		}
+	}
 	emitStage("Constructing depth maps");
 	for (int v = 0; v < nv; ++v) {
 		srh_view_depth_download(ctx_, v, computedDepths[v].data());
@@ -234,6 +246,12 @@ void MultiViewStereo::runTask() {
 		colorize(v);
 	}
 	srh_set_hooks(ctx_, nullptr, nullptr, nullptr);
+}
+
+srh_mvs_subpixel_info MultiViewStereo::subpixelInfo(CameraPtr view) const {
+	for (size_t v = 0; v < views.size() && v < subpixelInfos_.size(); ++v)
+		if (views[v] == view) return subpixelInfos_[v];
+	return srh_mvs_subpixel_info();
 }
 
 srh_sgm_info MultiViewStereo::sgmInfo(CameraPtr view) const {

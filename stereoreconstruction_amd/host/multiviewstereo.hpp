@@ -101,6 +101,13 @@ public:
 	bool useSGM() const { return useSgm_; }
 	srh_mvs_sgm_params &sgmParams() { return sgmParams_; }
 	srh_sgm_info sgmInfo(CameraPtr view) const;
+	// Sub-pixel depth (NOT IN THE REFERENCE; srh_mvs_view_subpixel): every view's map is refined after its
+	// estimate -- the WTA's, setUseMRF's or setUseSGM's -- with the neighbour list the estimate used, before the cross-check
+	// and the speckle filter.  Off by default: the maps are the reference's.  The step count is unchanged.
+	// subpixelInfo(view): the pixels per class of the last run (all zero before one, with the stage off, or for an unknown view).
+	void setSubpixel(bool on) { subpixel_ = on; }
+	bool subpixel() const { return subpixel_; }
+	srh_mvs_subpixel_info subpixelInfo(CameraPtr view) const;
 	// Speckle filter after the cross-check (NOT IN THE REFERENCE; srh_view_filter_speckles with SRH_SPECKLE_TO_NAN): in
 	// every view's map the 4-connected components of valid pixels whose depths differ by at most maxDiff (<= 0: two depth
 	// steps), those smaller than minSize set to NaN -- before depthMap, pointCloud and fusedPointCloud read the maps.
@@ -131,6 +138,8 @@ private:
 	std::vector<srh_sgm_info> sgmInfos_;
 	srh_fuse_params fuseParams_;
 	bool useMrf_ = false, useSgm_ = false;
+	bool subpixel_ = false;
+	std::vector<srh_mvs_subpixel_info> subpixelInfos_;
 	int speckleMinSize_ = 0;
 	double speckleMaxDiff_ = 0;
 	srh_context *ctx_;

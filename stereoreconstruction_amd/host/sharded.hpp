@@ -182,8 +182,23 @@ public:
 	}
 	bool ok() const { return ok_; }
 	size_t viewSize(int v) const { int w = 0, h = 0; srh_view_size(ctx_, v, &w, &h); return static_cast<size_t>(w)*h; }
-	bool initialEstimate(int v) { return srh_mvs_initial_estimate(ctx_, v, &neigh_[static_cast<size_t>(v)*nn_], count_[v], &p_, 0, 0, nullptr) == SRH_OK; }
-	bool finish() { return srh_synchronize(ctx_) == SRH_OK; }                     // settles the estimates in flight (capacity check, redo)
+	// sub-pixel depth (MultiViewStereo::setSubpixel; srh_mvs_view_subpixel): finish() refines the views THIS context estimated,
+	// with their neighbour lists, before their maps travel
+	void setSubpixel(bool on) { subpixel_ = on; }
+	bool initialEstimate(int v) {
+		if (srh_mvs_initial_estimate(ctx_, v, &neigh_[static_cast<size_t>(v)*nn_], count_[v], &p_, 0, 0, nullptr) != SRH_OK) return false;
+		estimated_.push_back(v);
+		return true;
+	}
+	bool finish() {                                                               // settles the estimates in flight (capacity check, redo)
+		bool ok = srh_synchronize(ctx_) == SRH_OK;
+		for (size_t k = 0; k < estimated_.size() && ok && subpixel_; ++k) {
+			const int v = estimated_[k];
+			ok = srh_mvs_view_subpixel(ctx_, v, &neigh_[static_cast<size_t>(v)*nn_], count_[v], &p_, nullptr, nullptr, nullptr, nullptr, nullptr) == SRH_OK;
+		}
+		estimated_.clear();
+		return ok;
+	}
 	bool getDepth(int v, double *out) { return srh_view_depth_download(ctx_, v, out) == SRH_OK; }
 	bool setDepth(int v, const double *in) { return srh_view_depth_upload(ctx_, v, in) == SRH_OK; }
 	bool crossCheck(int v) { return srh_mvs_cross_check(ctx_, slots_.data(), static_cast<int>(slots_.size()), v, &p_) == SRH_OK; }
@@ -193,6 +208,8 @@ private:
 	srh_params p_;
 	int nn_;
 	std::vector<int32_t> neigh_, count_, slots_;
+	std::vector<int> estimated_;
+	bool subpixel_ = false;
 	bool ok_;
 };
 

@@ -484,6 +484,14 @@ void MultiViewStereo::runTask() {
 		sgmInfos_.assign(V, srh_sgm_info());
 		if (srh_mvs_sgm_estimate_views(ctx_, all.data(), V, &sgmParams_, sgmInfos_.data()) != SRH_OK) { error_ = srh_last_error(); return; }
 	}
+	if (subpixel_) {                                     // sub-pixel depth (not in the reference): every view's finished map, no step of its own
+		subpixelInfos_.assign(V, srh_mvs_subpixel_info());
+		for (int v = 0; v < V; ++v) {
+			if (isCancelled()) return;
+			if (srh_mvs_view_subpixel(ctx_, v, &neigh[static_cast<size_t>(v)*nn], count[v], &params_, &subpixelInfos_[v],
+			                          nullptr, nullptr, nullptr, nullptr) != SRH_OK) { error_ = srh_last_error(); return; }
+		}
+	}
 	for (int v = 0; v < V; ++v)
 		if (srh_view_depth_download(ctx_, v, computedDepths[v].data()) != SRH_OK) { error_ = srh_last_error(); return; }
 	emit stageUpdate(tr("Constructing depth maps"));

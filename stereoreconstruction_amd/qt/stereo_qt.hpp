@@ -302,6 +302,12 @@ public:
 	// the depth maps of the last run's views, in their order, fused into one oriented cloud (srh_mvs_fuse with fuseParams())
 	std::vector<FusedPoint> fusedPointCloud();
 	srh_fuse_params &fuseParams() { return fuseParams_; }
+	// sub-pixel depth (NOT IN THE REFERENCE; srh_mvs_view_subpixel): every view's map is refined after its estimate
+	// (WTA, setUseMRF or setUseSGM) with the estimate's neighbour list, before the cross-check and the speckle filter.  Off by
+	// default; the step count is unchanged.  subpixelInfo(viewIndex): the pixels per class of the last run
+	void setSubpixel(bool on) { subpixel_ = on; }
+	bool subpixel() const { return subpixel_; }
+	srh_mvs_subpixel_info subpixelInfo(int viewIndex) const { return viewIndex >= 0 && viewIndex < static_cast<int>(subpixelInfos_.size()) ? subpixelInfos_[viewIndex] : srh_mvs_subpixel_info(); }
 	// speckle filter after the cross-check (not in the reference; srh_view_filter_speckles, SRH_SPECKLE_TO_NAN): components of
 	// fewer than minSize pixels whose depths chain within maxDiff (<= 0: two depth steps) become NaN; 0 (default) = off
 	void setSpeckleFilter(int minSize, double maxDiff = 0) { speckleMinSize_ = minSize; speckleMaxDiff_ = maxDiff; }
@@ -327,6 +333,8 @@ private:
 	std::vector<srh_sgm_info> sgmInfos_;
 	srh_fuse_params fuseParams_;
 	bool useMrf_ = false, useSgm_ = false;
+	bool subpixel_ = false;
+	std::vector<srh_mvs_subpixel_info> subpixelInfos_;
 	int speckleMinSize_ = 0;
 	double speckleMaxDiff_ = 0;
 	srh_context *ctx_;
