@@ -1,6 +1,6 @@
 // srh_api.hip -- the C-ABI of include/stereo_recon_hip.h: context, view upload,
 // run entry points, measurement.  Host code only; every numeric result comes from
-// the kernels in srh_kernels.hip / srh_dense.hip.  There is no CPU fallback: without
+// the kernels in srh_kernels.hip / srh_mvs.hip / srh_dense.hip.  There is no CPU fallback: without
 // a HIP device srh_create fails with SRH_E_NO_DEVICE.
 #include "srh_internal.hpp"
 #include "srh_subpixel.hpp"

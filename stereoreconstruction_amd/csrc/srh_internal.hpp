@@ -1,5 +1,5 @@
 // srh_internal.hpp -- shared between the C-ABI host layer (srh_api.hip) and the
-// gfx950 kernels (srh_kernels.hip).  Not installed.
+// gfx950 kernels (srh_kernels.hip, srh_mvs.hip, srh_dense.hip, ...).  Not installed.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -115,7 +115,7 @@ inline NeighList make_neigh_list(const int32_t *neigh, int nneigh) {
 // Per-pixel result of the curve-extent pass (dense path planning)
 struct Extent { int32_t xmin, xmax; };
 
-// ---- launch wrappers (srh_kernels.hip / srh_dense.hip); all asynchronous on `st` ----
+// ---- launch wrappers (srh_kernels.hip / srh_dense.hip; launch_mvs_*: srh_mvs.hip); all asynchronous on `st` ----
 void launch_prep_view(hipStream_t st, const uint32_t *rgba, const uint8_t *mask, int w, int h,
                       double *gray, double *gray_tv);
 void launch_fill(hipStream_t st, double *p, size_t n, double v);

@@ -12,6 +12,7 @@
 #include "srh_internal.hpp"
 #include "srh_geom.hpp"
 #include "srh_ncc.hpp"
+#include "srh_mvs_ncc.hpp"
 
 namespace srh {
 
@@ -537,43 +538,16 @@ __device__ __forceinline__ double mvs_tap(const ViewDev &V, int x, int y) {
 	return V.gray[(size_t)y*V.w + x];
 }
 
+// the free cost_ncc for a window of any radius (mvs_select_cost_n, srh_mvs_ncc.hpp)
 __device__ __forceinline__ double mvs_cost(const ViewDev &A, const ViewDev &B, const double *__restrict__ wq,
                                            size_t wstride, const srh_params &P, int x1, int y1, int x2, int y2)
 {
 	const int R = P.window_radius, WS = 2*R + 1;
-	double meanL = 0, meanR = 0, totalWeight = 0.0;
-	for (int row = -R; row <= R; ++row) {
-		for (int col = -R; col <= R; ++col) {
-			const double gl = mvs_tap(A, x1 + col, y1 + row);
-			const double gr = mvs_tap(B, x2 + col, y2 + row);
-			const double weight = wq[(size_t)((row + R)*WS + (col + R))*wstride];
-			if (gl == gl && gr == gr && weight > P.weight_cutoff) {
-				meanL += weight*gl;
-				meanR += weight*gr;
-				totalWeight += weight;
-			}
-		}
-	}
-	if (totalWeight < 1e-10) return 0;
-	meanL /= totalWeight;
-	meanR /= totalWeight;
-	double sum1 = 0, sum2 = 0, sum3 = 0;
-	for (int row = -R; row <= R; ++row) {
-		for (int col = -R; col <= R; ++col) {
-			const double gl = mvs_tap(A, x1 + col, y1 + row);
-			const double gr = mvs_tap(B, x2 + col, y2 + row);
-			const double weight = wq[(size_t)((row + R)*WS + (col + R))*wstride];
-			if (gl == gl && gr == gr && weight > P.weight_cutoff) {
-				const double pgl = weight*gl;
-				const double pgr = weight*gr;
-				sum1 += (pgl - meanL)*(pgr - meanR);
-				sum2 += (pgl - meanL)*(pgl - meanL);
-				sum3 += (pgr - meanR)*(pgr - meanR);
-			}
-		}
-	}
-	if (sum2 * sum3 < 1e-10) return 0;
-	return sum1 / sqrt(sum2 * sum3);
+	return mvs_select_cost_n(WS, [&](int row, int col, double &gl, double &gr, double &wt) {
+		gl = mvs_tap(A, x1 - R + col, y1 - R + row);
+		gr = mvs_tap(B, x2 - R + col, y2 - R + row);
+		wt = wq[(size_t)(row*WS + col)*wstride];
+	}, P.weight_cutoff);
 }
 
 __device__ __forceinline__ double candidate_depth(const srh_camera &refcam, const srh_camera &othcam,

@@ -1,6 +1,6 @@
 """MultiViewStereo away from window radius 2.  srh_mvs_initial_estimate takes the candidate-list path only at r = 2
 (mvs_initial_estimate_run, csrc/srh_api.hip); every other radius goes through mvs_generic_run to mvs_generic_kernel
-(csrc/srh_kernels.hip): the curve walk, mvs_cost and the top-K insertion inline, one thread per pixel.  The stock inputs all
+(csrc/srh_mvs.hip): the curve walk, mvs_cost and the top-K insertion (csrc/srh_mvs_ncc.hpp), one thread per pixel.  The stock inputs all
 have r = 2, and option force_generic = 1 at r = 2 runs mvs_reg_kernel<2>, so this file is what runs mvs_generic_kernel: whole
 maps, peaks, row ranges, bands, views thinner than the window, the options that must not matter, and the MRF, SGM and
 cross-check stages that consume what it writes.

@@ -474,12 +474,14 @@ def test_mvs(hip_ctx, shape, kind, distortion):
         assert np.allclose(got[..., 0], want_pk[..., 0], rtol=0, atol=1e-12), c.tag
         assert np.allclose(got[..., 1], want_pk[..., 1], rtol=1e-9, atol=0), c.tag
         _assert_depth(hip_ctx.download_depth(0), depth, c.tag + " with peaks")
-        pk2 = torch.full((h, w, c.p.top_k, 2), 7.0, dtype=torch.float64, device="cuda:0")
-        torch.cuda.synchronize()
-        with _options(hip_ctx, force_generic=1):
-            hip_ctx.mvs_initial_estimate(0, c.neigh[0], c.p, peaks_dev=pk2.data_ptr())
-            hip_ctx.synchronize()
-        assert np.array_equal(got.view(np.uint64), pk2.cpu().numpy().view(np.uint64)), c.tag
+        # the inline kernel, and the gathering kernel's top-K form for every wave (mvs_list_cost_kernel<2, true>)
+        for opt in ("force_generic", "mvs_staged"):
+            pk2 = torch.full((h, w, c.p.top_k, 2), 7.0, dtype=torch.float64, device="cuda:0")
+            torch.cuda.synchronize()
+            with _options(hip_ctx, **{opt: 1 if opt == "force_generic" else 0}):
+                hip_ctx.mvs_initial_estimate(0, c.neigh[0], c.p, peaks_dev=pk2.data_ptr())
+                hip_ctx.synchronize()
+            assert np.array_equal(got.view(np.uint64), pk2.cpu().numpy().view(np.uint64)), (c.tag, opt)
 
 
 @pytest.mark.parametrize("kind,distortion", SS.MVS_KINDS, ids=["geodesic", "adaptive_distorted"])
