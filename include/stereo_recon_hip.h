@@ -185,8 +185,9 @@ void srh_destroy(srh_context *ctx);
 int  srh_set_stream(srh_context *ctx, void *hip_stream);
 int  srh_set_hooks(srh_context *ctx, const volatile int *cancel, srh_progress_fn progress, void *user);
 int  srh_synchronize(srh_context *ctx);
-/* TwoView matching cost (option "cost"): TwoViewStereo::cost_ncc (default) or cost_sad (twoviewstereo.cpp:864-905) */
-enum { SRH_COST_NCC = 0, SRH_COST_SAD = 1 };
+/* TwoView matching cost (option "cost"): TwoViewStereo::cost_ncc (default), cost_sad (twoviewstereo.cpp:864-905), or the
+ * support-weighted census cost, which the reference does not have.  The value 2 is not a cost. */
+enum { SRH_COST_NCC = 0, SRH_COST_SAD = 1, SRH_COST_CENSUS = 3 };
 /* By-products of the TwoView winner-take-all scan a pass keeps per reference pixel (option "wta_outputs") */
 enum { SRH_WTA_WINNERS = 1, SRH_WTA_COSTS = 2 };
 /* Tuning / test switches (results never depend on them, "arith" = 1 / 2, "cost", "filter_invalid" and "speckle_*" excepted):
@@ -252,7 +253,14 @@ enum { SRH_WTA_WINNERS = 1, SRH_WTA_COSTS = 2 };
  *                     "arith" does not apply to it.  By default it runs on the candidate lists, rectified rigs too; with
  *                     "sad_dense" = 1 a rectified rig takes the dense plan, its cost rows filled by the persistent SAD
  *                     strip kernel (there is no per-tile and no fused SAD kernel).  srh_twoview_cost_rows under SAD needs
- *                     "sad_dense" = 1 (else SRH_E_UNSUPPORTED).
+ *                     "sad_dense" = 1 (else SRH_E_UNSUPPORTED).  SRH_COST_CENSUS (3; not in the reference): cost_sad's tap
+ *                     rule, totalWeight, numPixels and bad_ret rule with the per-tap term replaced by the Hamming distance
+ *                     of the two pixels' census signatures (srh_view_census), sum = fma(weight, distance, sum); the result
+ *                     is sum / totalWeight, a value in [0, 62]; max_color_diff is not read.  The WTA, ratio test,
+ *                     cross-check, filters, label cost volume, "wta_outputs" and "subpixel" run unchanged on it.  Census
+ *                     runs on the candidate lists (row runs, list order) and the walk kernel only: never the dense, strip
+ *                     or fused plan (srh_stats.used_dense_path is 0), "arith" and "sad_dense" do not apply, and
+ *                     srh_twoview_cost_rows returns SRH_E_UNSUPPORTED.  Any other value: SRH_E_INVALID.
  *   "sad_dense"       0 (default): cost_sad on the candidate lists.  1: under "cost" = SRH_COST_SAD a pair that is row-aligned
  *                     (the rig test of the NCC dense plan), with window radius 5 or 2, "force_generic" off and a candidate
  *                     range that fits the strip kernel's chunk (cstride + 32 <= 320 columns) takes the row-aligned dense
@@ -352,6 +360,12 @@ int  srh_view_upload_scaled(srh_context *ctx, int slot, int src_w, int src_h, co
 int  srh_view_image_download(srh_context *ctx, int slot, uint8_t *rgba_out, uint8_t *mask_out);
 /* The context keeps one depth map (w*h doubles) per view slot in device memory. */
 int  srh_view_depth_download(srh_context *ctx, int slot, double *host_out);
+/* The census signature plane of a view, w*h words row-major to a HOST buffer: one 64-bit signature per pixel, taken from
+ * toGray of every pixel (the mask is not consulted).  Bit k = (dy + 3)*9 + (dx + 4), dy in -3..3, dx in -4..4, is set iff
+ * (dx, dy) != (0, 0), the neighbour (x + dx, y + dy) lies inside the image and its gray value is smaller than the centre's;
+ * bits 31 and 63 are always 0.  The 9x7 size does not depend on window_radius.  Made on first use after an upload and kept
+ * with the slot; what "cost" = SRH_COST_CENSUS matches on.  Synchronous. */
+int  srh_view_census(srh_context *ctx, int slot, uint64_t *host_out);
 int  srh_view_depth_upload(srh_context *ctx, int slot, const double *host_in);
 int  srh_view_depth_device_ptr(srh_context *ctx, int slot, void **dev_ptr);
 /* The by-products of the last TwoView WTA pass that had `slot` as its reference view (option "wta_outputs"):
@@ -449,13 +463,13 @@ int  srh_twoview_wta(srh_context *ctx, int ref_slot, int oth_slot, const srh_par
  * *cstride_out (to size the buffer: rows * ceil(w/32)*32 * cstride doubles).  The rows must fit one band;
  * SRH_E_UNSUPPORTED when the pair does not take the dense plan.  Under "cost" = SRH_COST_SAD with "sad_dense" = 1: the
  * SAD cost rows in the same layout, *used_strip_kernel = 1; form must be 0 (else SRH_E_INVALID), raw is ignored; with
- * "sad_dense" = 0: SRH_E_UNSUPPORTED. */
+ * "sad_dense" = 0: SRH_E_UNSUPPORTED.  Under "cost" = SRH_COST_CENSUS: SRH_E_UNSUPPORTED. */
 int  srh_twoview_cost_rows(srh_context *ctx, int ref_slot, int other_slot, const srh_params *p, int y0, int y1, int form, int raw,
                            double *cost_out, size_t cost_doubles, int32_t *range_out, int *cstride_out, int *used_strip_kernel);
-/* cost_sad (kind SRH_COST_SAD) or cost_ncc (SRH_COST_NCC) of n arbitrary pairs: xy holds n x (x1, y1, x2, y2), (x1, y1) a
+/* cost_sad (kind SRH_COST_SAD), cost_ncc (SRH_COST_NCC) or the census cost (SRH_COST_CENSUS) of n arbitrary pairs: xy holds n x (x1, y1, x2, y2), (x1, y1) a
  * pixel of ref_slot (else SRH_E_INVALID), (x2, y2) any pixel position of oth_slot (taps outside it are skipped).  The
  * support window of (x1, y1) is built on the device (p->weight_kind, p->window_radius <= 5).  Host pointers; synchronous.
- * The backend of the host classes' protected cost_sad / cost_ncc. */
+ * The backend of the host classes' protected cost_sad / cost_ncc / cost_census. */
 int  srh_twoview_pair_costs(srh_context *ctx, int ref_slot, int oth_slot, const srh_params *p, int kind, int n,
                             const int32_t *xy, double *out);
 /* DIAGNOSTIC (tests/test_gpu_geodesic_exp.py): the GeodesicWeight kernels evaluate exp(-w/sigma) (geodesicweight.cpp:128-130)

@@ -1,0 +1,51 @@
+"""The census matching cost against SAD and NCC at 1920x1080x256: for the rectified geodesic pair (C3
+inputs) or the refractive pair (C5), `steps` timed srh_twoview_compute calls of each cost on one context, the three costs
+ALTERNATING call by call (NCC, SAD, census, NCC, ...) after one warm-up call each, so that drift of the clocks falls on
+all three alike; prints one JSON line with the median wall-clock milliseconds per pair.  Run under rocprofv3
+--kernel-trace --stats (profiles/census_trace.sh) for the per-kernel numbers.
+
+usage: python3 profiles/census_pair.py STEPS c3|c5"""
+import json
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, ".")
+from stereoreconstruction_amd import capi, synthetic  # noqa: E402
+
+COSTS = (("ncc", capi.COST_NCC), ("sad", capi.COST_SAD), ("census", capi.COST_CENSUS))
+
+
+def main(steps, geometry):
+    W, H, D = 1920, 1080, 256
+    seed, plane = {"c3": (0x5EED0003, (None, 0.0, 1.0)),
+                   "c5": (0x5EED0050, (np.array([0.0, 0.0, 1.0]), 0.1, 1.333))}[geometry]
+    ctx = capi.Context(0)
+    ctx.set_option("tv_overlap", 0)          # the two passes one after the other: each kernel's own duration
+    L, R, ml, mr, _ = synthetic.rectified_pair(W, H, D, seed)
+    (Kl, Rl, tl), (Kr, Rr, tr) = synthetic.rectified_cameras(W, H)
+    zmin, zmax = synthetic.rectified_depth_range(W, D)
+    ctx.upload_view(0, L, ml, capi.camera_from_krt(Kl, Rl, tl, None, *plane))
+    ctx.upload_view(1, R, mr, capi.camera_from_krt(Kr, Rr, tr, None, *plane))
+    p = capi.params_twoview(min_depth=zmin, max_depth=zmax, num_depth_levels=D, weight_kind=capi.WEIGHT_GEODESIC)
+    t = {name: [] for name, _ in COSTS}
+    for name, cost in COSTS:                 # warm-up: buffers, learnt list capacities, the signature planes
+        ctx.set_option("cost", cost)
+        ctx.twoview_compute(0, 1, p)
+    for _ in range(steps):
+        for name, cost in COSTS:
+            ctx.set_option("cost", cost)
+            t0 = time.perf_counter()
+            ctx.twoview_compute(0, 1, p)
+            t[name].append((time.perf_counter() - t0) * 1e3)
+    ctx.set_option("cost", capi.COST_NCC)
+    ctx.close()
+    out = {"geometry": geometry, "steps": steps}
+    for name, _ in COSTS:
+        out["%s_ms" % name] = round(float(np.median(t[name])), 3)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main(int(sys.argv[1]) if len(sys.argv) > 1 else 20, sys.argv[2] if len(sys.argv) > 2 else "c3")

@@ -167,8 +167,10 @@ RECTIFY_SHARED_CX = 1
 # srh_mvs_fuse: bit 0 of a fused point's flags
 FUSE_HAS_NORMAL = 1
 
-# option "cost" / srh_twoview_pair_costs kind: TwoViewStereo::cost_ncc, cost_sad
+# option "cost" / srh_twoview_pair_costs kind: TwoViewStereo::cost_ncc, cost_sad; the support-weighted census cost (not in
+# the reference; 2 is no cost)
 COST_NCC, COST_SAD = 0, 1
+COST_CENSUS = 3
 
 # option "wta_outputs": the by-products of the WTA scan a pass keeps (SRH_WTA_*)
 WTA_WINNERS, WTA_COSTS = 1, 2
@@ -190,7 +192,7 @@ EXPORTS = [
     "srh_mvs_neighbours", "srh_cert_bound", "srh_cert_sigma3", "srh_tscan_bound",
     "srh_create", "srh_destroy", "srh_set_stream", "srh_set_hooks", "srh_synchronize", "srh_set_option",
     "srh_view_upload", "srh_view_size", "srh_scaled_size", "srh_image_scale", "srh_view_upload_scaled", "srh_view_image_download",
-    "srh_view_depth_download", "srh_view_depth_upload",
+    "srh_view_depth_download", "srh_view_depth_upload", "srh_view_census",
     "srh_view_depth_device_ptr", "srh_view_depth_copy_to_device", "srh_view_depth_copy_from_device",
     "srh_view_wta_outputs", "srh_view_wta_outputs_device", "srh_view_wta_outputs_state",
     "srh_view_subpixel", "srh_view_subpixel_device", "srh_view_subpixel_info", "srh_mvs_view_subpixel",
@@ -280,6 +282,7 @@ def lib():
     L.srh_view_image_download.argtypes = [vp, C.c_int, c_uint8_p, c_uint8_p]
     L.srh_view_depth_download.argtypes = [vp, C.c_int, c_double_p]
     L.srh_view_depth_upload.argtypes = [vp, C.c_int, c_double_p]
+    L.srh_view_census.argtypes = [vp, C.c_int, C.POINTER(C.c_uint64)]
     L.srh_view_depth_device_ptr.argtypes = [vp, C.c_int, C.POINTER(vp)]
     L.srh_view_wta_outputs.argtypes = [vp, C.c_int, c_int32_p, c_int32_p, c_double_p, c_double_p]
     L.srh_view_wta_outputs_device.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
@@ -707,6 +710,14 @@ class Context:
         _check(lib().srh_view_depth_download(self._h, slot, _dptr(out)))
         return out
 
+    def view_census(self, slot):
+        """The 9x7 census signatures of a view -> (h, w) uint64 (srh_view_census): bit (dy + 3)*9 + (dx + 4) is set iff the
+        neighbour lies inside the image and is darker than the centre; what COST_CENSUS matches on."""
+        w, h = self.view_size(slot)
+        out = np.empty((h, w), dtype=np.uint64)
+        _check(lib().srh_view_census(self._h, slot, out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return out
+
     def upload_depth(self, slot, depth):
         w, h = self.view_size(slot)
         d = np.ascontiguousarray(depth, dtype=np.float64)
@@ -948,7 +959,7 @@ class Context:
         return idx
 
     def twoview_pair_costs(self, ref, oth, p, xy, kind=COST_SAD):
-        """cost_sad (kind COST_SAD) or cost_ncc (COST_NCC) of arbitrary pairs: xy (n, 4) int rows (x1, y1, x2, y2), the
+        """cost_sad (kind COST_SAD), cost_ncc (COST_NCC) or the census cost (COST_CENSUS) of arbitrary pairs: xy (n, 4) int rows (x1, y1, x2, y2), the
         support window of (x1, y1) in view `ref` -> (n,) float64 (srh_twoview_pair_costs)."""
         a = np.ascontiguousarray(np.asarray(xy, dtype=np.int32).reshape(-1, 4))
         out = np.empty(a.shape[0], np.float64)

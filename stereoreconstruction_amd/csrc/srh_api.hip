@@ -260,6 +260,8 @@ struct ViewHost {
 	// cost_sad on the dense plan (srh_sad_strip.hip): NaN-bordered copy of gray where the mask is WHITE, zero-bordered copy of `fulls`
 	DevBuf<double>   grayp; bool grayp_valid = false;
 	DevBuf<uint8_t>  fullsp; int fullsp_r = 0;
+	// option "cost" = SRH_COST_CENSUS (srh_census.hip): the 9x7 census signatures of `gray`, made on first use after an upload
+	DevBuf<uint64_t> census; bool census_valid = false;
 	// how the candidate lists of this view against slot j are best evaluated, learnt from the last run:
 	// 0 unknown, 1 row runs (srh_rows.hip), 2 list order (srh_list.hip: steep curves)
 	uint8_t   list_mode[SRH_MAX_VIEWS] = {0};
@@ -401,7 +403,7 @@ struct srh_context {
 	int filter_replay = 0;                              // option "filter_replay": every median hole by the exact replay (test hook)
 	int speckle_min_size = 0;                           // option "speckle_min_size": srh_twoview_compute* remove components below it after the cross-check (0: off)
 	int speckle_diff_steps = 2;                         // option "speckle_diff_steps": that stage's max_diff in depth steps
-	int cost_kind = SRH_COST_NCC;                       // option "cost": the TwoView matching cost, SRH_COST_NCC or SRH_COST_SAD
+	int cost_kind = SRH_COST_NCC;                       // option "cost": the TwoView matching cost, SRH_COST_NCC, SRH_COST_SAD or SRH_COST_CENSUS
 	int sad_dense = 0;                                  // option "sad_dense": cost_sad of row-aligned rigs on the dense plan (srh_sad_strip.hip)
 	int subpixel = 0;                                   // option "subpixel": every TwoView WTA pass refines its rows (srh_subpixel.hip; CHANGES RESULTS)
 	// what a TwoView WTA pass keeps per reference pixel: what "wta_outputs" asks for; under "subpixel" winners and costs
@@ -798,7 +800,7 @@ extern "C" int srh_create(int device, srh_context **out) {
 static void free_view(ViewHost &v) {
 	if (v.rgba || v.gray || v.edges || v.tvp || v.geo5) (void)hipDeviceSynchronize();
 	v.rgba.release(); v.mask.release(); v.gray.release(); v.gray_tv.release(); v.depth.release(); v.edges.release();
-	v.full.release(); v.fulls.release(); v.grayp.release(); v.fullsp.release(); v.tvp.release(); v.geo5.release(); v.fullp.release(); v.act.release(); v.peaks.release(); v.mrf.release(); v.sgm.release();
+	v.full.release(); v.fulls.release(); v.census.release(); v.grayp.release(); v.fullsp.release(); v.tvp.release(); v.geo5.release(); v.fullp.release(); v.act.release(); v.peaks.release(); v.mrf.release(); v.sgm.release();
 	v.wta_xy.release(); v.wta_cost.release();
 	v.subpx_delta.release(); v.subpx_neigh.release(); v.subpx_cls.release();
 	v = ViewHost();
@@ -922,7 +924,8 @@ extern "C" int srh_set_option(srh_context *c, const char *name, long value) {
 		c->speckle_diff_steps = (int)value; return SRH_OK;
 	}
 	if (!strcmp(name, "cost")) {
-		if (value != SRH_COST_NCC && value != SRH_COST_SAD) return fail(SRH_E_INVALID, "cost must be 0 (SRH_COST_NCC) or 1 (SRH_COST_SAD)");
+		if (value != SRH_COST_NCC && value != SRH_COST_SAD && value != SRH_COST_CENSUS)
+			return fail(SRH_E_INVALID, "cost must be 0 (SRH_COST_NCC), 1 (SRH_COST_SAD) or 3 (SRH_COST_CENSUS)");
 		c->cost_kind = (int)value; return SRH_OK;
 	}
 	if (!strcmp(name, "sad_dense")) { c->sad_dense = value != 0; return SRH_OK; }
@@ -993,7 +996,7 @@ static int view_install(srh_context *c, int slot, int w, int h, const void *rgba
 	}
 	v.cam = *cam;
 	v.full_r = 0; v.fulls_r = 0;                                // recomputed on demand for the new pixels
-	v.tvp_valid = false; v.fullp_r = 0; v.grayp_valid = false; v.fullsp_r = 0; v.geo5_valid = false; v.geo5_denied = false;
+	v.tvp_valid = false; v.fullp_r = 0; v.grayp_valid = false; v.census_valid = false; v.fullsp_r = 0; v.geo5_valid = false; v.geo5_denied = false;
 	v.peaks_k = 0;                                              // the top-K peaks belonged to the previous image
 	v.wta_flags = 0; v.wta_oth = -1;                            // and so did the WTA by-products
 	for (LabelStage *S : c->label_stages) S->forget_if(w, h);   // and so may what a label stage reports
@@ -1009,6 +1012,7 @@ static int view_install(srh_context *c, int slot, int w, int h, const void *rgba
 	ViewDev d;
 	d.w = w; d.h = h; d.rgba = v.rgba; d.mask = v.mask; d.gray = v.gray; d.gray_tv = v.gray_tv; d.depth = v.depth;
 	d.cam = v.cam;
+	d.census = v.census;                                        // (null, or a plane of this size that ensure_census refills)
 	HIP_TRY(hipMemcpyAsync(c->d_views + slot, &d, sizeof(d), hipMemcpyHostToDevice, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));   // the host buffers and `d` may go away after return
 	HIP_TRY(hipGetLastError());
@@ -1614,6 +1618,23 @@ static int ensure_fulls(srh_context *c, hipStream_t st, ViewHost &v, int R) {
 	return SRH_OK;
 }
 
+// The census signatures of a view (option "cost" = SRH_COST_CENSUS), made on first use after an upload, on `st`; the
+// kernels find the plane through the slot's ViewDev
+static int ensure_census(srh_context *c, hipStream_t st, int slot) {
+	ViewHost &v = c->views[slot];
+	if (v.census_valid) return SRH_OK;
+	if (!v.census) {
+		HIP_TRY(v.census.alloc((size_t)v.w*v.h));
+		const uint64_t *dp = v.census;
+		HIP_TRY(hipMemcpyAsync((char *)(ViewDev *)(c->d_views + slot) + offsetof(ViewDev, census), &dp, sizeof(dp), hipMemcpyHostToDevice, st));
+		HIP_TRY(hipStreamSynchronize(st));                          // (`dp` goes away)
+	}
+	Scope s(c, st, "census_kernel");
+	launch_census(st, v.gray, v.w, v.h, v.census);
+	v.census_valid = true;
+	return SRH_OK;
+}
+
 // cost_ncc's "window fully usable" plane of radius R, with its two counts behind it (option "rows_masked")
 static int ensure_full(srh_context *c, hipStream_t st, ViewHost &v, int R) {
 	if (v.full_r == R) return SRH_OK;
@@ -1677,7 +1698,8 @@ struct TvPass {
 	const srh_params *p = nullptr;
 	int W = 0, H = 0, y0 = 0, y1 = 0, R = 0, T = 0;
 	size_t budget = 0;
-	bool sad = false;
+	int kind = SRH_COST_NCC;                  // option "cost"; sad / census: the kind is SRH_COST_SAD / SRH_COST_CENSUS
+	bool sad = false, census = false;
 	int32_t *wout = nullptr;
 	const double *subpx_tdist = nullptr;      // option "subpixel": the pass's label plane table (label_plane_table_kernel)
 
@@ -1711,7 +1733,9 @@ static int tv_pass_init(TvPass &P, srh_context *c, const Lane &lane, int ref, in
 	P.y1 = (y1 <= 0 || y1 > P.H) ? P.H : y1;
 	P.R = p->window_radius;
 	P.T = (2*P.R + 1)*(2*P.R + 1);
-	P.sad = c->cost_kind == SRH_COST_SAD;
+	P.kind = c->cost_kind;
+	P.sad = P.kind == SRH_COST_SAD;
+	P.census = P.kind == SRH_COST_CENSUS;
 	if (P.y1 > P.y0) P.budget = band_budget(c);
 	return SRH_OK;
 }
@@ -1726,7 +1750,7 @@ void TvPass::winner_costs(int by, int nr, bool wimg_layout) const {
 	const ViewHost &v = c->views[ref];
 	double *mc = v.wta_cost;
 	{ Scope s(c, lane.stream, "twoview_winner_costs_kernel");
-	  launch_twoview_winner_costs(lane.stream, c->d_views, ref, oth, W, *p, sad, by, nr, lane.mem->band.wbuf, wimg_layout,
+	  launch_twoview_winner_costs(lane.stream, c->d_views, ref, oth, W, *p, kind, by, nr, lane.mem->band.wbuf, wimg_layout,
 	                              wout, mc, mc + (size_t)W*H); }
 	if (!c->subpixel) return;
 	// option "subpixel": the band's winners, their costs and its depths are final here and its windows still in the buffer.
@@ -1734,7 +1758,7 @@ void TvPass::winner_costs(int by, int nr, bool wimg_layout) const {
 	{ Scope s(c, lane.stream, "subpixel_neighbours_kernel");
 	  launch_subpixel_neighbours(lane.stream, c->d_views, ref, oth, W, *p, by, nr, subpx_tdist, wout, v.subpx_neigh, v.subpx_cls); }
 	{ Scope s(c, lane.stream, "subpixel_refine_kernel");
-	  launch_subpixel_refine(lane.stream, c->d_views, ref, oth, W, *p, sad, by, nr, lane.mem->band.wbuf, wimg_layout, wout, mc,
+	  launch_subpixel_refine(lane.stream, c->d_views, ref, oth, W, *p, kind, by, nr, lane.mem->band.wbuf, wimg_layout, wout, mc,
 	                         v.subpx_neigh, v.subpx_cls, v.subpx_delta); }
 }
 
@@ -1752,11 +1776,12 @@ static double disparity_span(const srh_params &p, double fx_bx) {
 
 // ---- plan: dense row-aligned kernels (or the fused kernel), or the general kernels.  Launches nothing.
 // (cost_sad: the dense plan only with option "sad_dense", its cost rows filled by twoview_strip_sad_kernel; no per-tile
-// and no fused kernel -- without the option rectified rigs take the row-run lists too)
+// and no fused kernel -- without the option rectified rigs take the row-run lists too; DESIGN.md 4c.  The census cost has
+// the candidate lists and the walk kernel only)
 TvPlan TvPass::plan() const {
 	const ViewHost &L = c->views[ref], &Rv = c->views[oth];
 	TvPlan pl;
-	pl.dense = !c->force_generic && (!sad || c->sad_dense) && (R == 5 || R == 2);
+	pl.dense = !c->force_generic && !census && (!sad || c->sad_dense) && (R == 5 || R == 2);
 	double fx_bx = 0;
 	if (pl.dense && !rig_is_row_aligned(L.cam, Rv.cam, &fx_bx)) {
 		// test hook: any pinhole pair may be *proposed* (the scan kernel refutes the proposal, see the controller's redo)
@@ -1838,7 +1863,7 @@ int TvPass::lists_prepare(TvLists &S) const {
 	int rc;
 	if ((rc = lane.mem->band.lcount.ensure((size_t)(y1 - y0)*W))) return rc;
 	ViewHost &O = c->views[oth];
-	if ((rc = sad ? ensure_fulls(c, lane.stream, O, R) : ensure_full(c, lane.stream, O, R))) return rc;
+	if ((rc = (sad || census) ? ensure_fulls(c, lane.stream, O, R) : ensure_full(c, lane.stream, O, R))) return rc;
 	// the label-only part of pointFromDepth, once per pass instead of once per pixel and label
 	if ((rc = lane.mem->band.tnum.ensure((size_t)p->num_depth_levels))) return rc;
 	{ Scope s(c, lane.stream, "label_plane_table_kernel");
@@ -1873,7 +1898,7 @@ int TvPass::lists_rows_band(const TvLists &S, int by, int nr) const {
 	int32_t *cnt_band = lane.mem->band.lcount + (size_t)(by - y0)*W;
 	// the row-run cost kernel takes the pixels' constants (meanL, totalWeight, sum2, 1/totalWeight, SA) from the weights
 	// kernel, which has the window in registers anyway, instead of making them on one lane in eight per tile
-	double *pconst = sad ? nullptr : (double *)lane.mem->band.pconst;
+	double *pconst = (sad || census) ? nullptr : (double *)lane.mem->band.pconst;
 	// The list kernel does not need the support windows, and its last waves drain for long (a wave walks
 	// its 64 curves for ~2 ms): the windows are computed on a side stream queued behind it -- the geodesic
 	// kernel's register-heavy waves only find room on a SIMD once the list kernel's have left it.
@@ -1898,6 +1923,10 @@ int TvPass::lists_rows_band(const TvLists &S, int by, int nr) const {
 		Scope s(c, lane.stream, "twoview_rows_sad_kernel");
 		launch_twoview_rows_sad(lane.stream, c->d_views, ref, oth, W, *p, by, nr, lane.mem->band.wbuf, O.fulls,
 		                        lane.mem->band.lrowinfo, lane.mem->band.lmeta, lane.mem->band.cost, S.smax, lane.mem->cnt);
+	} else if (census) {
+		Scope s(c, lane.stream, "twoview_rows_census_kernel");
+		launch_twoview_rows_census(lane.stream, c->d_views, ref, oth, W, *p, by, nr, lane.mem->band.wbuf, O.fulls,
+		                           lane.mem->band.lrowinfo, lane.mem->band.lmeta, lane.mem->band.cost, S.smax, lane.mem->cnt);
 	} else {
 		Scope s(c, lane.stream, "twoview_rows_cost_kernel");
 		launch_twoview_rows_cost(lane.stream, c->d_views, ref, oth, W, *p, by, nr, lane.mem->band.wbuf, O.full,
@@ -1940,7 +1969,7 @@ int TvPass::lists_pass(TvLists &S) const {
 	const size_t px64 = (lrows*W + 63) & ~(size_t)63, px32 = lrows*(size_t)((W + 7)/8)*8;        /* (cost slots: tiles of 8 pixels) */
 	if ((rc = lane.mem->band.cost.ensure((rows_mode ? px32 : lrows*W)*(size_t)ccap))) return rc;
 	if ((rc = lane.mem->band.lcand.ensure((rows_mode ? px64 : lrows*W)*(size_t)S.cmax))) return rc;
-	if (rows_mode && !sad && (rc = lane.mem->band.pconst.ensure((lrows*(size_t)W + SRH_WTILE)*SRH_PC))) return rc;
+	if (rows_mode && !sad && !census && (rc = lane.mem->band.pconst.ensure((lrows*(size_t)W + SRH_WTILE)*SRH_PC))) return rc;
 	if (rows_mode) {
 		if ((rc = lane.mem->band.lrowinfo.ensure(px64*(size_t)SRH_ROWS_NR))) return rc;
 		if ((rc = lane.mem->band.lmeta.ensure(lrows*W))) return rc;
@@ -1964,6 +1993,10 @@ int TvPass::lists_pass(TvLists &S) const {
 				Scope s(c, lane.stream, "twoview_list_sad_kernel");
 				launch_twoview_list_sad(lane.stream, c->d_views, ref, oth, W, *p, by, nr, lane.mem->band.wbuf,
 				                        cnt_band, lane.mem->band.lcand, lane.mem->band.cost, S.cmax, lane.mem->cnt);
+			} else if (census) {
+				Scope s(c, lane.stream, "twoview_list_census_kernel");
+				launch_twoview_list_census(lane.stream, c->d_views, ref, oth, W, *p, by, nr, lane.mem->band.wbuf,
+				                           cnt_band, lane.mem->band.lcand, lane.mem->band.cost, S.cmax, lane.mem->cnt);
 			} else {
 				Scope s(c, lane.stream, "twoview_list_cost_kernel");
 				launch_twoview_list_cost(lane.stream, c->d_views, ref, oth, W, *p, by, nr, lane.mem->band.wbuf, c->views[oth].full,
@@ -2248,7 +2281,7 @@ int TvPass::run_walk() const {
 		const int nr = std::min(rows, y1 - by);
 		run_weights(c, lane, ref, W, *p, by, nr, SRH_WTILE);
 		{ Scope s(c, lane.stream, "twoview_generic_kernel");
-		  launch_twoview_generic(lane.stream, c->d_views, ref, oth, W, *p, by, nr, lane.mem->band.wbuf, SRH_WTILE, lane.mem->cnt, sad, wout); }
+		  launch_twoview_generic(lane.stream, c->d_views, ref, oth, W, *p, by, nr, lane.mem->band.wbuf, SRH_WTILE, lane.mem->cnt, kind, wout); }
 		winner_costs(by, nr, false);
 	}
 	HIP_TRY(hipGetLastError());
@@ -2266,6 +2299,8 @@ static int twoview_wta_run(srh_context *c, const Lane &lane, srh_context::TvDefe
 	if ((rc = tv_pass_init(P, c, lane, ref, oth, p, y0, y1))) return rc;
 	if (P.y1 <= P.y0) return SRH_OK;
 	if ((rc = ensure_wta_planes(c, lane.stream, ref, oth))) return rc;
+	// (srh_twoview_compute made both views' signatures before its streams forked: nothing is queued here then)
+	if (P.census && ((rc = ensure_census(c, lane.stream, ref)) || (rc = ensure_census(c, lane.stream, oth)))) return rc;
 	P.wout = c->wta_keep() ? (int32_t *)c->views[ref].wta_xy : nullptr;
 	if (c->subpixel) {
 		// the label-only part of pointFromDepth for the neighbours kernel's walk (a buffer of its own: band.tnum holds
@@ -2300,7 +2335,7 @@ static int twoview_wta_run(srh_context *c, const Lane &lane, srh_context::TvDefe
 	if (!P.sad && p->weight_kind == SRH_WEIGHT_GEODESIC && !(p->geodesic_sigma > 0)) D.strip = false;
 	// certified arithmetic (arith = 3, the default): fused cost loops in the strip kernel + the certified scan; where the
 	// strip kernel does not run, or the parameters leave the bound no room, the reference's arithmetic
-	bool cert_ok = c->arith == 3 && !P.sad && cert_bound(*p).ok != 0;
+	bool cert_ok = c->arith == 3 && !P.sad && !P.census && cert_bound(*p).ok != 0;
 	c->stats.n_certified = c->stats.n_flagged = 0;
 	// (a negative wta_margin -- not the reference's: its margin is the constant +1e-10, twoviewstereo.cpp:293 -- makes a
 	// revisited winner beat itself, so the candidate lists' dropped joint duplicates would matter: the walk kernel, which
@@ -2356,6 +2391,7 @@ extern "C" int srh_twoview_cost_rows(srh_context *c, int ref, int oth, const srh
 	if (form != 0 && form != 3 && form != 5 && form != 1 && form != 2) return fail(SRH_E_INVALID, "form must be 0, 1, 2, 3 or 5");
 	if ((form == 3 || form == 5) && !cert_bound(*p).ok) return fail(SRH_E_UNSUPPORTED, "the parameters leave the error bound no room");
 	const bool sad = c->cost_kind == SRH_COST_SAD;
+	if (c->cost_kind == SRH_COST_CENSUS) return fail(SRH_E_UNSUPPORTED, "the census cost has no cost rows: it never takes the dense plan");
 	if (sad && !c->sad_dense) return fail(SRH_E_UNSUPPORTED, "cost rows of cost_sad exist on the dense plan only (option sad_dense)");
 	if (sad && form != 0) return fail(SRH_E_INVALID, "cost_sad has the reference's arithmetic only: form must be 0");
 	TvPass P;
@@ -2399,7 +2435,8 @@ extern "C" int srh_twoview_pair_costs(srh_context *c, int ref, int oth, const sr
 {
 	int rc;
 	if ((rc = check_slot(c, ref, true)) || (rc = check_slot(c, oth, true)) || (rc = check_params(p))) return rc;
-	if (kind != SRH_COST_NCC && kind != SRH_COST_SAD) return fail(SRH_E_INVALID, "kind must be SRH_COST_NCC or SRH_COST_SAD");
+	if (kind != SRH_COST_NCC && kind != SRH_COST_SAD && kind != SRH_COST_CENSUS)
+		return fail(SRH_E_INVALID, "kind must be SRH_COST_NCC, SRH_COST_SAD or SRH_COST_CENSUS");
 	if (n < 0 || (n > 0 && (!xy || !out))) return fail(SRH_E_INVALID, "null pairs or output");
 	if (p->window_radius > 5) return fail(SRH_E_UNSUPPORTED, "pair costs take window radii up to 5");
 	if (n == 0) return SRH_OK;
@@ -2408,16 +2445,31 @@ extern "C" int srh_twoview_pair_costs(srh_context *c, int ref, int oth, const sr
 		if (xy[4*k] < 0 || xy[4*k + 1] < 0 || xy[4*k] >= L.w || xy[4*k + 1] >= L.h)
 			return fail(SRH_E_INVALID, "pair %d: reference pixel (%d, %d) outside the %dx%d view", k, xy[4*k], xy[4*k + 1], L.w, L.h);
 	HIP_TRY(hipSetDevice(c->device));
+	if (kind == SRH_COST_CENSUS && ((rc = ensure_census(c, c->stream, ref)) || (rc = ensure_census(c, c->stream, oth)))) return rc;
 	DevBuf<int32_t> dxy; DevBuf<double> dout;
 	HIP_TRY(dxy.alloc((size_t)4*n));
 	HIP_TRY(dout.alloc((size_t)n));
 	HIP_TRY(hipMemcpyAsync(dxy, xy, (size_t)4*n*sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
 	{ Scope s(c, c->stream, "pair_costs_kernel");
-	  launch_pair_costs(c->stream, c->d_views, ref, oth, *p, kind == SRH_COST_SAD, n, dxy, dout); }
+	  launch_pair_costs(c->stream, c->d_views, ref, oth, *p, kind, n, dxy, dout); }
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(out, dout, (size_t)n*sizeof(double), hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	dxy.free(); dout.free();
+	return SRH_OK;
+}
+
+// the census signature plane of a view (w*h words), made if the slot does not hold it yet; synchronous, host pointer
+extern "C" int srh_view_census(srh_context *c, int slot, uint64_t *out) {
+	int rc;
+	if ((rc = check_slot(c, slot, true))) return rc;
+	if (!out) return fail(SRH_E_INVALID, "null output");
+	HIP_TRY(hipSetDevice(c->device));
+	if ((rc = ensure_census(c, c->stream, slot))) return rc;
+	HIP_TRY(hipGetLastError());
+	const ViewHost &v = c->views[slot];
+	HIP_TRY(hipMemcpyAsync(out, v.census, (size_t)v.w*v.h*sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
 	return SRH_OK;
 }
 
@@ -2488,6 +2540,8 @@ extern "C" int srh_twoview_compute(srh_context *c, int left, int right, const sr
 			HIP_TRY(T.mem.span.alloc(4));
 		}
 		// the NaN-bordered planes both passes read (tv_dense_prepare makes them on demand, on its own stream) exist at `go`
+		// (and so do the census signatures of both views)
+		if (c->cost_kind == SRH_COST_CENSUS && ((rc = ensure_census(c, c->stream, left)) || (rc = ensure_census(c, c->stream, right)))) return rc;
 		if (c->cost_kind == SRH_COST_SAD && c->sad_dense && (p->window_radius == 5 || p->window_radius == 2))
 			for (int k = 0; k < 2; ++k)
 				if ((rc = ensure_sad_planes(c, c->stream, c->views[k == 0 ? left : right], p->window_radius))) return rc;
@@ -3962,8 +4016,9 @@ static int tv_stage_costs(srh_context *c, const TvStage &T, int ref, int oth, co
 	int rc;
 	const ViewHost &v = c->views[ref];
 	if ((rc = tv_stage_reserve(c, T, v.w, v.h, p->num_depth_levels, true))) return rc;
+	if (c->cost_kind == SRH_COST_CENSUS && ((rc = ensure_census(c, c->stream, ref)) || (rc = ensure_census(c, c->stream, oth)))) return rc;
 	Scope s(c, c->stream, "twoview_label_costs_kernel");
-	HIP_TRY(launch_twoview_label_costs(c->stream, c->d_views, ref, oth, v.w, *p, c->cost_kind == SRH_COST_SAD, 0, v.h,
+	HIP_TRY(launch_twoview_label_costs(c->stream, c->d_views, ref, oth, v.w, *p, c->cost_kind, 0, v.h,
 	                                   (2*p->window_radius + 1)*p->bad_ret, (c->*T.state).costs, nullptr));
 	return SRH_OK;
 }
@@ -4077,6 +4132,10 @@ extern "C" int srh_twoview_label_costs(srh_context *c, int ref, int oth, const s
 	if (y1 <= 0) y1 = v.h;
 	if (y0 < 0 || y0 >= y1 || y1 > v.h) return fail(SRH_E_INVALID, "rows [%d,%d) outside the view's %d rows", y0, y1, v.h);
 	HIP_TRY(hipSetDevice(c->device));
+	if (c->cost_kind == SRH_COST_CENSUS) {
+		int rc;
+		if ((rc = ensure_census(c, c->stream, ref)) || (rc = ensure_census(c, c->stream, oth))) return rc;
+	}
 	const int D = p->num_depth_levels;
 	const size_t n = (size_t)(y1 - y0)*v.w*D;
 	DevBuf<double> dcost; DevBuf<int32_t> dpix;
@@ -4085,7 +4144,7 @@ extern "C" int srh_twoview_label_costs(srh_context *c, int ref, int oth, const s
 		return done(fail(SRH_E_DEVICE, "label costs: no device memory for %zu bytes", n*(sizeof(double) + (pixel_out ? 2*sizeof(int32_t) : 0))));
 	hipError_t e;
 	{ Scope s(c, c->stream, "twoview_label_costs_kernel");
-	  e = launch_twoview_label_costs(c->stream, c->d_views, ref, oth, v.w, *p, c->cost_kind == SRH_COST_SAD, y0, y1 - y0,
+	  e = launch_twoview_label_costs(c->stream, c->d_views, ref, oth, v.w, *p, c->cost_kind, y0, y1 - y0,
 	                                 (2*p->window_radius + 1)*p->bad_ret, dcost, pixel_out ? (int32_t *)dpix : nullptr); }
 	if (e == hipSuccess) e = hipMemcpyAsync(cost_out, dcost, n*sizeof(double), hipMemcpyDeviceToHost, c->stream);
 	if (e == hipSuccess && pixel_out) e = hipMemcpyAsync(pixel_out, dpix, 2*n*sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);

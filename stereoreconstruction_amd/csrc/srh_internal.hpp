@@ -18,6 +18,8 @@ namespace srh {
 //   gray_tv f64  toGray where the TwoView tap test   8 B/pixel  (mask WHITE && sample() valid:
 //                passes, NaN elsewhere                           x+1<w && y+1<h)
 //   depth   f64  result map                          8 B/pixel
+//   census  u64  9x7 census signature of `gray`      8 B/pixel  (option "cost" = SRH_COST_CENSUS; null until a census
+//                                                                run asks for it: census_kernel)
 struct ViewDev {
 	int32_t w, h;
 	const uint32_t *rgba;
@@ -26,6 +28,7 @@ struct ViewDev {
 	const double   *gray_tv;
 	double         *depth;
 	srh_camera      cam;
+	const uint64_t *census;
 };
 
 // Support-window buffer of one row band: tile-major, a tile = SRH_WTILE consecutive
@@ -76,8 +79,8 @@ __device__ __forceinline__ void wta_store(int32_t *__restrict__ wout, size_t npi
 }
 #endif
 // exact costs of the two pairs (srh_wta_out.hip): min_cost[npix] and second_cost[npix] of rows [y0, y0 + nrows), in the
-// reference's arithmetic (tv_cost / tv_cost_sad: the bits of pair_costs_kernel), from the band's window buffer in either layout
-void launch_twoview_winner_costs(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P, bool sad,
+// reference's arithmetic (tv_cost_of under cost kind `kind`: the bits of pair_costs_kernel), from the band's window buffer in either layout
+void launch_twoview_winner_costs(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P, int kind,
                                  int y0, int nrows, const double *wbuf, bool wimg, const int32_t *wout,
                                  double *min_cost, double *second_cost);
 
@@ -128,7 +131,7 @@ void launch_fill(hipStream_t st, double *p, size_t n, double v);
 void launch_weights(hipStream_t st, const ViewDev *views, int ref, int width, const srh_params &P,
                     int y0, int nrows, double *wbuf, size_t wstride, double *pconst = nullptr, bool wimg = false);
 void launch_twoview_generic(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P,
-                            int y0, int nrows, const double *wbuf, size_t wstride, Counters *cnt, bool sad = false,
+                            int y0, int nrows, const double *wbuf, size_t wstride, Counters *cnt, int kind = SRH_COST_NCC,
                             int32_t *wout = nullptr);
 void launch_twoview_cross_check(hipStream_t st, const ViewDev *views, int self, int other, int w, int h,
                                 const srh_params &P);
@@ -298,9 +301,20 @@ void launch_padded_bytes(hipStream_t st, const uint8_t *in, int w, int h, uint8_
 bool launch_twoview_strip_sad(hipStream_t st, int width, int height, const srh_params &P, int y0, int nrows,
                               const double *wimg, const PixRange *prange, const double *ref_tvp, const double *oth_grayp,
                               const uint8_t *oth_fullp, double *cost, int cstride, Counters *cnt, int num_cus);
-// cost of arbitrary pairs xy[4k..4k+3] = (x1, y1, x2, y2), the window of (x1, y1) built per lane; sad: cost_sad, else cost_ncc
-void launch_pair_costs(hipStream_t st, const ViewDev *views, int ref, int oth, const srh_params &P, bool sad, int n,
+// cost of arbitrary pairs xy[4k..4k+3] = (x1, y1, x2, y2), the window of (x1, y1) built per lane; kind: SRH_COST_*
+void launch_pair_costs(hipStream_t st, const ViewDev *views, int ref, int oth, const srh_params &P, int kind, int n,
                        const int32_t *xy, double *out);
+// support-weighted census, option "cost" = SRH_COST_CENSUS (srh_census.hip)
+// the 9x7 signature plane of a w x h gray plane
+void launch_census(hipStream_t st, const double *gray, int w, int h, uint64_t *out);
+// the row-run lists' cost slots (srh_rows.hip layout); windows in the LDS-image layout, full_oth: launch_sad_full_window's plane
+bool launch_twoview_rows_census(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P,
+                                int y0, int nrows, const double *wbuf, const uint8_t *full_oth,
+                                const uint32_t *rowinfo, const int32_t *meta, double *cost, int smax, Counters *cnt);
+// the list-order costs (srh_list.hip layout); the windows tile-major
+void launch_twoview_list_census(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P,
+                                int y0, int nrows, const double *wbuf, const int32_t *count, const uint32_t *cand,
+                                double *cost, int cmax, Counters *cnt);
 void launch_point_cloud(hipStream_t st, const ViewDev *views, int slot, int w, int h, const srh_params &P,
                         double *xyz, uint8_t *rgb, uint8_t *valid, unsigned long long *counts);
 // depth-map fusion (srh_fuse.hip).  Per entry of the slot list: its point map (3 doubles per pixel, from
@@ -388,7 +402,7 @@ hipError_t launch_twoview_sgm_path(hipStream_t st, double *buf, const double *co
 hipError_t launch_twoview_sgm_readoff(hipStream_t st, const ViewDev *views, int slot, const srh_params &P, double *buf, int w, int h, int L);
 hipError_t launch_twoview_sgm_energy(hipStream_t st, double *buf, const double *costs, int w, int h, int L, double lambda, double smax);
 // the label cost volume of rows [y0, y0 + nrows): cost [pixel][label], pixel (optional) [pixel][label][x2, y2]
-hipError_t launch_twoview_label_costs(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P, bool sad,
+hipError_t launch_twoview_label_costs(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P, int kind,
                                       int y0, int nrows, double fill, double *cost, int32_t *pixel);
 void launch_epipolar_preview(hipStream_t st, const ViewDev *views, int ref, int oth, double zmin, double zmax, int nd,
                              int nq, const double *xy, double *out, int32_t *counts);

@@ -120,7 +120,7 @@ void launch_weights(hipStream_t st, const ViewDev *views, int ref, int width, co
 
 // ------------------------------------------------------------------ TwoView, general geometry
 // the rule and its state: srh_wta.hpp (WTA, option "wta_outputs": the runner-up travels along)
-template <bool SAD, bool WTA>
+template <int KIND, bool WTA>
 struct TwoViewDirectVisitor {
 	const ViewDev &L, &Rv;
 	const double *wq;
@@ -130,14 +130,14 @@ struct TwoViewDirectVisitor {
 	WtaState<WtaXY, WTA> st;
 	unsigned n;
 	__device__ __forceinline__ void operator()(int cx, int cy) {
-		const double cost = SAD ? tv_cost_sad(L, Rv, wq, wstride, P, x, y, cx, cy) : tv_cost(L, Rv, wq, wstride, P, x, y, cx, cy);
+		const double cost = tv_cost_of(KIND, L, Rv, wq, wstride, P, x, y, cx, cy);
 		++n;
 		st.take(cost, WtaXY{ cx, cy }, P.wta_margin);
 	}
 };
 
-// SAD: the cost is cost_sad (option "cost" = SRH_COST_SAD), else cost_ncc; WTA: winner and runner-up into wout (wta_store)
-template <bool SAD, bool WTA>
+// KIND: the cost (option "cost", SRH_COST_*); WTA: winner and runner-up into wout (wta_store)
+template <int KIND, bool WTA>
 __global__ void twoview_generic_kernel(const ViewDev *__restrict__ views, int ref, int oth, srh_params P,
                                        int y0, int nrows, const double *__restrict__ wbuf, size_t wstride,
                                        Counters *__restrict__ cnt, int32_t *__restrict__ wout)
@@ -156,7 +156,7 @@ __global__ void twoview_generic_kernel(const ViewDev *__restrict__ views, int re
 			n_pix = 1;
 			const Ray ray = cam_unproject(L.cam, (x + 0.5) / P.image_scale, (y + 0.5) / P.image_scale);
 			const int T = (2*P.window_radius + 1)*(2*P.window_radius + 1);
-			TwoViewDirectVisitor<SAD, WTA> vis = { L, Rv, wbuf + wbuf_offset(W, T, (int)(q / W), x), wstride, P, x, y,
+			TwoViewDirectVisitor<KIND, WTA> vis = { L, Rv, wbuf + wbuf_offset(W, T, (int)(q / W), x), wstride, P, x, y,
 			                             WtaState<WtaXY, WTA>(WtaXY{ -1, -1 }), 0 };
 			walk_curve<false>(ray, L.cam, Rv, P, vis);
 			n_eval = vis.n;
@@ -175,13 +175,14 @@ __global__ void twoview_generic_kernel(const ViewDev *__restrict__ views, int re
 }
 
 void launch_twoview_generic(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P,
-                            int y0, int nrows, const double *wbuf, size_t wstride, Counters *cnt, bool sad, int32_t *wout)
+                            int y0, int nrows, const double *wbuf, size_t wstride, Counters *cnt, int kind, int32_t *wout)
 {
 	const size_t n = (size_t)nrows*width;
 	const dim3 grid((unsigned)((n + 127)/128)), block(128);
 #define SRH_GEN_LAUNCH(S_, W_) hipLaunchKernelGGL((twoview_generic_kernel<S_, W_>), grid, block, 0, st, views, ref, oth, P, y0, nrows, wbuf, wstride, cnt, wout)
-	if (sad) { if (wout) SRH_GEN_LAUNCH(true, true); else SRH_GEN_LAUNCH(true, false); }
-	else     { if (wout) SRH_GEN_LAUNCH(false, true); else SRH_GEN_LAUNCH(false, false); }
+	if (kind == SRH_COST_SAD)         { if (wout) SRH_GEN_LAUNCH(SRH_COST_SAD, true); else SRH_GEN_LAUNCH(SRH_COST_SAD, false); }
+	else if (kind == SRH_COST_CENSUS) { if (wout) SRH_GEN_LAUNCH(SRH_COST_CENSUS, true); else SRH_GEN_LAUNCH(SRH_COST_CENSUS, false); }
+	else                              { if (wout) SRH_GEN_LAUNCH(SRH_COST_NCC, true); else SRH_GEN_LAUNCH(SRH_COST_NCC, false); }
 #undef SRH_GEN_LAUNCH
 }
 

@@ -4,7 +4,7 @@
 //   sad_full_window_kernel   per pixel of the other view: is cost_sad's whole window usable there (inside, mask WHITE)?
 //   twoview_rows_sad_kernel  the row-run lists' cost slots (srh_rows.hip layout), blocks of 8 adjacent columns
 //   twoview_list_sad_kernel  the list-order costs (srh_list.hip layout): steep curves
-//   pair_costs_kernel        cost_sad / cost_ncc of arbitrary pairs, the window built per lane (srh_twoview_pair_costs)
+//   pair_costs_kernel        the cost (any SRH_COST_* kind) of arbitrary pairs, the window built per lane (srh_twoview_pair_costs)
 //
 // The scans of srh_rows.hip / srh_list.hip run unchanged on these costs.  Every cost has the reference's bits: the same
 // operations in the same order, a skipped tap adds +0.0 (every term is >= 0 and the sums start at +0.0).
@@ -285,7 +285,7 @@ void launch_twoview_list_sad(hipStream_t st, const ViewDev *views, int ref, int 
 #define PC_LANES 64
 #define PC_TAPS 121
 __global__ __launch_bounds__(PC_LANES)
-void pair_costs_kernel(const ViewDev *__restrict__ views, int ref, int oth, srh_params P, int sad, int n,
+void pair_costs_kernel(const ViewDev *__restrict__ views, int ref, int oth, srh_params P, int kind, int n,
                        const int32_t *__restrict__ xy, double *__restrict__ out)
 {
 	__shared__ double wl[PC_TAPS*PC_LANES];
@@ -298,16 +298,15 @@ void pair_costs_kernel(const ViewDev *__restrict__ views, int ref, int oth, srh_
 	const int WS = 2*P.window_radius + 1;
 	double *wb = wl + lane;
 	support_window(L, P, x1, y1, [&](int r, int c) -> double & { return wb[(r*WS + c)*PC_LANES]; });
-	out[k] = sad ? tv_cost_sad(L, Rv, wb, PC_LANES, P, x1, y1, x2, y2)
-	             : tv_cost(L, Rv, wb, PC_LANES, P, x1, y1, x2, y2);
+	out[k] = tv_cost_of(kind, L, Rv, wb, PC_LANES, P, x1, y1, x2, y2);
 }
 
-void launch_pair_costs(hipStream_t st, const ViewDev *views, int ref, int oth, const srh_params &P, bool sad, int n,
+void launch_pair_costs(hipStream_t st, const ViewDev *views, int ref, int oth, const srh_params &P, int kind, int n,
                        const int32_t *xy, double *out)
 {
 	if (n <= 0) return;
 	hipLaunchKernelGGL(pair_costs_kernel, dim3((unsigned)((n + PC_LANES - 1)/PC_LANES)), dim3(PC_LANES), 0, st,
-	                   views, ref, oth, P, sad ? 1 : 0, n, xy, out);
+	                   views, ref, oth, P, kind, n, xy, out);
 }
 
 } // namespace srh

@@ -8,7 +8,7 @@
 //      S at Chebyshev distance 1 from the kept winner w.  Of A, scanned in ascending (qy, qx), n- is the q with the largest
 //      candidate_depth(q) < z0 and n+ the one with the smallest candidate_depth(q) > z0 (strict comparisons: the first q met
 //      wins a tie; a q at z0 or with a NaN depth is on neither side).  z0 is the pixel's depth as the scan left it.
-//   2. cm, c0, cp = the reference's cost (tv_cost / tv_cost_sad: the bits of pair_costs_kernel) of the pixel against
+//   2. cm, c0, cp = the reference-form cost (tv_cost_of under the pass's cost kind: the bits of pair_costs_kernel) of the pixel against
 //      n-, w, n+; c0 is the kept min_cost.
 //   3. D = (cm - c0) + (cp - c0); delta = 0.5*(cm - cp)/D; refined when D > 0 and |delta| <= 0.5.  The new depth is
 //      candidate_depth at w + |delta|*(n - w), n = n+ for delta > 0, else n-; delta == 0 keeps the depth's bits.
@@ -71,7 +71,7 @@ void launch_subpixel_neighbours(hipStream_t st, const ViewDev *views, int ref, i
 }
 
 __global__ __launch_bounds__(64)
-void subpixel_refine_kernel(const ViewDev *__restrict__ views, int ref, int oth, srh_params P, int sad,
+void subpixel_refine_kernel(const ViewDev *__restrict__ views, int ref, int oth, srh_params P, int kind,
                             int y0, int nrows, const double *__restrict__ wbuf, int wimg,
                             const int32_t *__restrict__ win_xy, const double *__restrict__ min_cost,
                             const int32_t *__restrict__ neigh, uint8_t *__restrict__ cls, double *__restrict__ delta)
@@ -94,12 +94,10 @@ void subpixel_refine_kernel(const ViewDev *__restrict__ views, int ref, int oth,
 		const int R = P.window_radius, WS = 2*R + 1;
 		if (wimg) {
 			const double *wq = wbuf + wimg_offset(W, R, trow, x);
-			v = sad ? tv_cost_sad(L, Rv, wq, 1, P, x, y, c.x, c.y, (size_t)wimg_row_stride(R))
-			        : tv_cost(L, Rv, wq, 1, P, x, y, c.x, c.y, (size_t)wimg_row_stride(R));
+			v = tv_cost_of(kind, L, Rv, wq, 1, P, x, y, c.x, c.y, (size_t)wimg_row_stride(R));
 		} else {
 			const double *wq = wbuf + wbuf_offset(W, WS*WS, trow, x);
-			v = sad ? tv_cost_sad(L, Rv, wq, SRH_WTILE, P, x, y, c.x, c.y)
-			        : tv_cost(L, Rv, wq, SRH_WTILE, P, x, y, c.x, c.y);
+			v = tv_cost_of(kind, L, Rv, wq, SRH_WTILE, P, x, y, c.x, c.y);
 		}
 	}
 	// the other half-wave's cost of the same pixel: lane ^ 32 (both are here, see above)
@@ -130,14 +128,14 @@ void subpixel_refine_kernel(const ViewDev *__restrict__ views, int ref, int oth,
 	delta[pv] = d;
 }
 
-void launch_subpixel_refine(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P, bool sad,
+void launch_subpixel_refine(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P, int kind,
                             int y0, int nrows, const double *wbuf, bool wimg, const int32_t *win_xy, const double *min_cost,
                             const int32_t *neigh, uint8_t *cls, double *delta)
 {
 	if (nrows <= 0) return;
 	const unsigned tiles = (unsigned)((width + SRH_WTILE - 1)/SRH_WTILE);
 	hipLaunchKernelGGL(subpixel_refine_kernel, dim3(tiles*(unsigned)nrows), dim3(64), 0, st,
-	                   views, ref, oth, P, sad ? 1 : 0, y0, nrows, wbuf, wimg ? 1 : 0, win_xy, min_cost, neigh, cls, delta);
+	                   views, ref, oth, P, kind, y0, nrows, wbuf, wimg ? 1 : 0, win_xy, min_cost, neigh, cls, delta);
 }
 
 } // namespace srh

@@ -12,7 +12,7 @@ void launch_subpixel_neighbours(hipStream_t st, const ViewDev *views, int ref, i
                                 int y0, int nrows, const double *tdist, const int32_t *win_xy, int32_t *neigh, uint8_t *cls);
 // the same rows: the costs of n- and n+ in the reference's arithmetic from the band's window buffer (either layout, as
 // launch_twoview_winner_costs), c0 from min_cost; delta and the final class of every pixel, the depth of the refined ones
-void launch_subpixel_refine(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P, bool sad,
+void launch_subpixel_refine(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P, int kind,
                             int y0, int nrows, const double *wbuf, bool wimg, const int32_t *win_xy, const double *min_cost,
                             const int32_t *neigh, uint8_t *cls, double *delta);
 

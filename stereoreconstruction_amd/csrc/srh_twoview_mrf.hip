@@ -380,7 +380,7 @@ __global__ void twoview_mrf_depth_kernel(const ViewDev *__restrict__ views, int 
 #define LC_PARTS 4
 #define LC_TAPS 121
 __global__ __launch_bounds__(LC_LANES*LC_PARTS)
-void twoview_label_costs_kernel(const ViewDev *__restrict__ views, int ref, int oth, srh_params P, int sad, int y0, int nrows,
+void twoview_label_costs_kernel(const ViewDev *__restrict__ views, int ref, int oth, srh_params P, int kind, int y0, int nrows,
                                 double fill, double *__restrict__ cost, int32_t *__restrict__ pixel)
 {
 	__shared__ double wl[LC_TAPS*LC_LANES];
@@ -423,7 +423,7 @@ void twoview_label_costs_kernel(const ViewDev *__restrict__ views, int ref, int 
 		}
 		const int x2 = trunc_sat(point.x*P.image_scale), y2 = trunc_sat(point.y*P.image_scale);
 		if (!(have && x2 == lx && y2 == ly)) {
-			lcost = sad ? tv_cost_sad(L, Rv, wb, LC_LANES, P, x, y, x2, y2) : tv_cost(L, Rv, wb, LC_LANES, P, x, y, x2, y2);
+			lcost = tv_cost_of(kind, L, Rv, wb, LC_LANES, P, x, y, x2, y2);
 			lx = x2; ly = y2; have = true;
 		}
 		out[d] = lcost;
@@ -547,13 +547,13 @@ hipError_t launch_twoview_mrf_depth(hipStream_t st, const ViewDev *views, int sl
 	return hipGetLastError();
 }
 
-hipError_t launch_twoview_label_costs(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P, bool sad,
+hipError_t launch_twoview_label_costs(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P, int kind,
                                       int y0, int nrows, double fill, double *cost, int32_t *pixel)
 {
 	const size_t n = (size_t)nrows*width;
 	if (!n) return hipSuccess;
 	hipLaunchKernelGGL(twoview_label_costs_kernel, dim3((unsigned)((n + LC_LANES - 1)/LC_LANES)), dim3(LC_LANES*LC_PARTS), 0, st,
-	                   views, ref, oth, P, sad ? 1 : 0, y0, nrows, fill, cost, pixel);
+	                   views, ref, oth, P, kind, y0, nrows, fill, cost, pixel);
 	return hipGetLastError();
 }
 

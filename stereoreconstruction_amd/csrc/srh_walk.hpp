@@ -1,10 +1,11 @@
-// srh_walk.hpp -- device-side epipolar-curve walker, the two weighted-NCC costs and the weighted SAD.
+// srh_walk.hpp -- device-side epipolar-curve walker, the two weighted-NCC costs, the weighted SAD and the weighted census.
 //
 //   walk_curve<MVS>   TwoViewStereo::epipolarCurve (stereo/twoviewstereo.cpp:999-1054) /
 //                     MultiViewStereo::epipolarCurve (stereo/multiviewstereo.cpp:754-810):
 //                     calls vis(cx, cy) for every candidate pixel, in the reference's order.
 //   tv_cost           TwoViewStereo::cost_ncc (twoviewstereo.cpp:909-977), lower is better
 //   tv_cost_sad       TwoViewStereo::cost_sad (twoviewstereo.cpp:864-905), lower is better
+//   tv_cost_census    support-weighted Hamming distance of 9x7 census signatures (not in the reference)
 //   mvs_cost          free cost_ncc (multiviewstereo.cpp:113-189), higher is better
 //   candidate_depth   camera-space z of the two-ray mid-point (twoviewstereo.cpp:287-300)
 #pragma once
@@ -498,6 +499,46 @@ __device__ __forceinline__ double tv_cost_sad(const ViewDev &L, const ViewDev &R
 	}
 	if (numPixels <= 4 || totalWeight <= 1e-10) return P.bad_ret;
 	return sum / totalWeight;
+}
+
+// The support-weighted census cost (option "cost" = SRH_COST_CENSUS), lower is better; window layout as
+// tv_cost.  cost_sad's tap rule and bad_ret rule unchanged; the per-tap term is the Hamming distance of the two pixels'
+// signatures (ViewDev::census, census_kernel), an exact small integer, accumulated with ONE fused multiply-add: there is
+// no reference arithmetic to preserve, and the library builds with contraction off, so the fusion is spelt out.
+__device__ __forceinline__ double tv_cost_census(const ViewDev &L, const ViewDev &Rv, const double *__restrict__ wq,
+                                                 size_t wstride, const srh_params &P, int x1, int y1, int x2, int y2,
+                                                 size_t wrow = 0)
+{
+	const int R = P.window_radius, WS = 2*R + 1;
+	if (wrow == 0) wrow = (size_t)WS*wstride;
+	int numPixels = 0;
+	double sum = 0.0, totalWeight = 0.0;
+	for (int row = -R; row <= R; ++row) {
+		for (int col = -R; col <= R; ++col) {
+			const int lx = x1 + col, ly = y1 + row, rx = x2 + col, ry = y2 + row;
+			const double gl = tv_tap(L, lx, ly);
+			const bool okr = rx >= 0 && ry >= 0 && rx < Rv.w && ry < Rv.h && Rv.mask[(size_t)ry*Rv.w + rx] == 1;
+			const double weight = wq[(size_t)(row + R)*wrow + (size_t)(col + R)*wstride];
+			if (gl == gl && okr && weight > P.weight_cutoff) {
+				const unsigned long long d = L.census[(size_t)ly*L.w + lx] ^ Rv.census[(size_t)ry*Rv.w + rx];
+				sum = __builtin_fma(weight, (double)__builtin_popcountll(d), sum);
+				totalWeight += weight;
+				++numPixels;
+			}
+		}
+	}
+	if (numPixels <= 4 || totalWeight <= 1e-10) return P.bad_ret;
+	return sum / totalWeight;
+}
+
+// the reference-form cost of one pair under cost kind `kind` (SRH_COST_*)
+__device__ __forceinline__ double tv_cost_of(int kind, const ViewDev &L, const ViewDev &Rv, const double *__restrict__ wq,
+                                             size_t wstride, const srh_params &P, int x1, int y1, int x2, int y2,
+                                             size_t wrow = 0)
+{
+	return kind == SRH_COST_SAD ? tv_cost_sad(L, Rv, wq, wstride, P, x1, y1, x2, y2, wrow)
+	     : kind == SRH_COST_CENSUS ? tv_cost_census(L, Rv, wq, wstride, P, x1, y1, x2, y2, wrow)
+	     : tv_cost(L, Rv, wq, wstride, P, x1, y1, x2, y2, wrow);
 }
 
 // cost_ncc in the reference's arithmetic for ANY validity pattern (ncc_select_cost, srh_ncc.hpp: the same sums, same order

@@ -3,7 +3,7 @@
 // The scan kernels keep WHICH candidate won and which one held the minimum before it (wta_store, srh_internal.hpp); the
 // costs they compared are, under the certified arithmetic, fused approximations whose decisions are proven and whose
 // numbers are not the reference's.  So the two costs of a pixel are evaluated here, once, in the reference's arithmetic:
-// tv_cost / tv_cost_sad of srh_walk.hpp, the functions pair_costs_kernel evaluates -- the same operations in the same
+// tv_cost / tv_cost_sad / tv_cost_census of srh_walk.hpp, the functions pair_costs_kernel evaluates -- the same operations in the same
 // order under -ffp-contract=off, hence the same bits, whatever arithmetic chose the winner.
 //
 // Launched per band on the pass's stream behind the last kernel that can still change the band's winners (the scan, its
@@ -18,7 +18,7 @@
 namespace srh {
 
 __global__ __launch_bounds__(64)
-void twoview_winner_costs_kernel(const ViewDev *__restrict__ views, int ref, int oth, srh_params P, int sad,
+void twoview_winner_costs_kernel(const ViewDev *__restrict__ views, int ref, int oth, srh_params P, int kind,
                                  int y0, int nrows, const double *__restrict__ wbuf, int wimg,
                                  const int32_t *__restrict__ wout, double *__restrict__ min_cost, double *__restrict__ second_cost)
 {
@@ -39,25 +39,23 @@ void twoview_winner_costs_kernel(const ViewDev *__restrict__ views, int ref, int
 		const int R = P.window_radius, WS = 2*R + 1;
 		if (wimg) {
 			const double *wq = wbuf + wimg_offset(W, R, trow, x);
-			v = sad ? tv_cost_sad(L, Rv, wq, 1, P, x, y, c.x, c.y, (size_t)wimg_row_stride(R))
-			        : tv_cost(L, Rv, wq, 1, P, x, y, c.x, c.y, (size_t)wimg_row_stride(R));
+			v = tv_cost_of(kind, L, Rv, wq, 1, P, x, y, c.x, c.y, (size_t)wimg_row_stride(R));
 		} else {
 			const double *wq = wbuf + wbuf_offset(W, WS*WS, trow, x);
-			v = sad ? tv_cost_sad(L, Rv, wq, SRH_WTILE, P, x, y, c.x, c.y)
-			        : tv_cost(L, Rv, wq, SRH_WTILE, P, x, y, c.x, c.y);
+			v = tv_cost_of(kind, L, Rv, wq, SRH_WTILE, P, x, y, c.x, c.y);
 		}
 	}
 	(which ? second_cost : min_cost)[pv] = v;
 }
 
-void launch_twoview_winner_costs(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P, bool sad,
+void launch_twoview_winner_costs(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P, int kind,
                                  int y0, int nrows, const double *wbuf, bool wimg, const int32_t *wout,
                                  double *min_cost, double *second_cost)
 {
 	if (nrows <= 0) return;
 	const unsigned tiles = (unsigned)((width + SRH_WTILE - 1)/SRH_WTILE);
 	hipLaunchKernelGGL(twoview_winner_costs_kernel, dim3(tiles*(unsigned)nrows), dim3(64), 0, st,
-	                   views, ref, oth, P, sad ? 1 : 0, y0, nrows, wbuf, wimg ? 1 : 0, wout, min_cost, second_cost);
+	                   views, ref, oth, P, kind, y0, nrows, wbuf, wimg ? 1 : 0, wout, min_cost, second_cost);
 }
 
 } // namespace srh

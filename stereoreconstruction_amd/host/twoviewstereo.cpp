@@ -171,6 +171,10 @@ double TwoViewStereo::cost_sad(int x1, int y1, int x2, int y2, bool fromLeft) {
 	return pairCost(SRH_COST_SAD, x1, y1, x2, y2, fromLeft);
 }
 
+double TwoViewStereo::cost_census(int x1, int y1, int x2, int y2, bool fromLeft) {
+	return pairCost(SRH_COST_CENSUS, x1, y1, x2, y2, fromLeft);
+}
+
 double TwoViewStereo::cost_ncc(int x1, int y1, int x2, int y2, bool fromLeft) {
 	return pairCost(SRH_COST_NCC, x1, y1, x2, y2, fromLeft);
 }

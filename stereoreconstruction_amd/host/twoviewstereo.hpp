@@ -53,7 +53,8 @@ public:
 	int speckleFilter() const { return speckleMinSize; }
 
 	// Matching cost of the WTA: SRH_COST_NCC (0, default: cost_ncc, as the reference's computeCostVolumes) or SRH_COST_SAD
-	// (1: cost_sad, twoviewstereo.cpp:864-905).  The WTA, ratio test, cross-check and hole filling are the same for both.
+	// (1: cost_sad, twoviewstereo.cpp:864-905) or SRH_COST_CENSUS (3: the support-weighted census cost, not in the
+	// reference).  The WTA, ratio test, cross-check and hole filling are the same for all.
 	void setCostFunction(int kind) { costKind = kind; }
 	int costFunction() const { return costKind; }
 	// SAD of a rectified pair on the dense plan (option "sad_dense": 1 = on, 0 = default): a tuning switch, never the result
@@ -177,6 +178,8 @@ protected:
 	// left view is the reference, else the right one.  The window is built on the device for each call (one round trip:
 	// srh_twoview_pair_costs takes many pairs at once).  NaN when the device call fails (lastError()).
 	double cost_sad(int x1, int y1, int x2, int y2, bool fromLeft = true);
+	// (not in the reference: the census cost of option "cost" = SRH_COST_CENSUS, same conventions)
+	double cost_census(int x1, int y1, int x2, int y2, bool fromLeft = true);
 	double cost_ncc(int x1, int y1, int x2, int y2, bool fromLeft = true);
 
 private:

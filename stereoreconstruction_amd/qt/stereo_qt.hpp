@@ -127,7 +127,8 @@ public:
 	// speckle filter between the cross-check and the hole filling (not in the reference; srh_view_filter_speckles): components
 	// of fewer than minSize pixels whose depths chain within diffSteps depth steps become +INF; 0 (default) = off
 	void setSpeckleFilter(int minSize, int diffSteps = 2) { speckleMinSize = minSize; speckleDiffSteps = diffSteps; }
-	// matching cost of the WTA: SRH_COST_NCC (0, default: cost_ncc, the reference's) or SRH_COST_SAD (1: cost_sad)
+	// matching cost of the WTA: SRH_COST_NCC (0, default: cost_ncc, the reference's), SRH_COST_SAD (1: cost_sad) or
+	// SRH_COST_CENSUS (3: the support-weighted census cost, not in the reference)
 	void setCostFunction(int kind) { costKind = kind; }
 	int costFunction() const { return costKind; }
 	// SAD of a rectified pair on the dense plan (option "sad_dense": 1 = on, 0 = default): a tuning switch, never the result
@@ -211,6 +212,7 @@ protected:
 	// with curveOfPixel all of it follows from the pixels and the direction (fromLeft: the left view is the reference).
 	// One device round trip per call (srh_twoview_pair_costs takes many pairs); NaN when it fails (lastError()).
 	double cost_sad(int x1, int y1, int x2, int y2, bool fromLeft = true);
+	double cost_census(int x1, int y1, int x2, int y2, bool fromLeft = true);   // (not in the reference)
 	double cost_ncc(int x1, int y1, int x2, int y2, bool fromLeft = true);
 
 private:
