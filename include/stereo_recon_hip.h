@@ -257,10 +257,12 @@ enum { SRH_WTA_WINNERS = 1, SRH_WTA_COSTS = 2 };
  *                     rule, totalWeight, numPixels and bad_ret rule with the per-tap term replaced by the Hamming distance
  *                     of the two pixels' census signatures (srh_view_census), sum = fma(weight, distance, sum); the result
  *                     is sum / totalWeight, a value in [0, 62]; max_color_diff is not read.  The WTA, ratio test,
- *                     cross-check, filters, label cost volume, "wta_outputs" and "subpixel" run unchanged on it.  Census
- *                     runs on the candidate lists (row runs, list order) and the walk kernel only: never the dense, strip
- *                     or fused plan (srh_stats.used_dense_path is 0), "arith" and "sad_dense" do not apply, and
- *                     srh_twoview_cost_rows returns SRH_E_UNSUPPORTED.  Any other value: SRH_E_INVALID.
+ *                     cross-check, filters, label cost volume, "wta_outputs" and "subpixel" run unchanged on it.  By
+ *                     default census runs on the candidate lists (row runs, list order) and the walk kernel only
+ *                     (srh_stats.used_dense_path is 0) and srh_twoview_cost_rows returns SRH_E_UNSUPPORTED; with
+ *                     "census_dense" = 1 a rectified rig takes the dense plan, its cost rows filled by the persistent
+ *                     census strip kernel (there is no per-tile and no fused census kernel).  "arith" and "sad_dense" do
+ *                     not apply to it.  Any other value: SRH_E_INVALID.
  *   "sad_dense"       0 (default): cost_sad on the candidate lists.  1: under "cost" = SRH_COST_SAD a pair that is row-aligned
  *                     (the rig test of the NCC dense plan), with window radius 5 or 2, "force_generic" off and a candidate
  *                     range that fits the strip kernel's chunk (cstride + 32 <= 320 columns) takes the row-aligned dense
@@ -271,6 +273,13 @@ enum { SRH_WTA_WINNERS = 1, SRH_WTA_COSTS = 2 };
  *                     than the chunk after all, a candidate off its row, "force_dense" included) -- runs on the row-run,
  *                     list-order or walk kernels exactly as with 0.  The fused plan is never taken under SAD.  Nothing
  *                     changes under "cost" = SRH_COST_NCC.  Identical bits: a tuning switch like "strip" and "tscan".
+ *   "census_dense"    0 (default): the census cost on the candidate lists.  1: under "cost" = SRH_COST_CENSUS a pair that
+ *                     meets "sad_dense"'s conditions (row-aligned rig, window radius 5 or 2, "force_generic" off, cstride + 32
+ *                     <= 320 columns) takes the row-aligned dense plan: twoview_strip_census_kernel fills the cost rows
+ *                     (every column of every pixel's range), the range, template and scan kernels run unchanged behind it,
+ *                     uncertified; srh_stats.used_dense_path and used_strip_kernel are then 1.  Any other pair, and a plan
+ *                     the device refutes, runs on the row-run, list-order or walk kernels exactly as with 0.  Nothing
+ *                     changes under the other costs.  Identical bits: a tuning switch.
  *   "wta_outputs"     never changes a depth map.  0 (default): a WTA pass keeps the depth only -- no allocation, no extra store.
  *                     SRH_WTA_WINNERS (1): every pass ref -> oth (srh_twoview_wta, both passes of srh_twoview_compute) also keeps,
  *                     per reference pixel, win_xy -- the candidate pixel of `oth` that held minCost at the end of the scan -- and
@@ -463,7 +472,8 @@ int  srh_twoview_wta(srh_context *ctx, int ref_slot, int oth_slot, const srh_par
  * *cstride_out (to size the buffer: rows * ceil(w/32)*32 * cstride doubles).  The rows must fit one band;
  * SRH_E_UNSUPPORTED when the pair does not take the dense plan.  Under "cost" = SRH_COST_SAD with "sad_dense" = 1: the
  * SAD cost rows in the same layout, *used_strip_kernel = 1; form must be 0 (else SRH_E_INVALID), raw is ignored; with
- * "sad_dense" = 0: SRH_E_UNSUPPORTED.  Under "cost" = SRH_COST_CENSUS: SRH_E_UNSUPPORTED. */
+ * "sad_dense" = 0: SRH_E_UNSUPPORTED.  Under "cost" = SRH_COST_CENSUS the same with "census_dense": the census cost rows
+ * with the option 1 and form 0, SRH_E_INVALID for another form, SRH_E_UNSUPPORTED with the option 0. */
 int  srh_twoview_cost_rows(srh_context *ctx, int ref_slot, int other_slot, const srh_params *p, int y0, int y1, int form, int raw,
                            double *cost_out, size_t cost_doubles, int32_t *range_out, int *cstride_out, int *used_strip_kernel);
 /* cost_sad (kind SRH_COST_SAD), cost_ncc (SRH_COST_NCC) or the census cost (SRH_COST_CENSUS) of n arbitrary pairs: xy holds n x (x1, y1, x2, y2), (x1, y1) a

@@ -821,7 +821,8 @@ class Context:
         lo + k, range (rows, w, 2) int32, used_strip_kernel).  form: 0 the reference's arithmetic, 3 / 5 the certified
         forms, 1 fused unchecked, 2 the single-precision kernel in the form of option "f32_form" (per tile:
         used_strip_kernel is False; raw is ignored).  Under set_option("cost", COST_SAD) the rows are cost_sad's and
-        need set_option("sad_dense", 1) and form 0 (anything else raises); an entry no kernel wrote is a NaN with all bits set."""
+        need set_option("sad_dense", 1) and form 0 (anything else raises); under COST_CENSUS they are the census cost's and
+        need set_option("census_dense", 1) and form 0 likewise; an entry no kernel wrote is a NaN with all bits set."""
         w, h = self.view_size(ref)
         cs, us = C.c_int(0), C.c_int(0)
         _check(lib().srh_twoview_cost_rows(self._h, ref, oth, C.byref(p), y0, y1, form, 1 if raw else 0, None, 0, None, C.byref(cs), C.byref(us)))

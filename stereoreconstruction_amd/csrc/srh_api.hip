@@ -262,6 +262,9 @@ struct ViewHost {
 	DevBuf<uint8_t>  fullsp; int fullsp_r = 0;
 	// option "cost" = SRH_COST_CENSUS (srh_census.hip): the 9x7 census signatures of `gray`, made on first use after an upload
 	DevBuf<uint64_t> census; bool census_valid = false;
+	// the census cost on the dense plan (srh_census_strip.hip): `census` on the padded raster as the other side's taps (unusable
+	// behind the mask) and as the reference side's (unusable where gray_tv is NaN)
+	DevBuf<uint64_t> cenothp, cenrefp; bool cenp_valid = false;
 	// how the candidate lists of this view against slot j are best evaluated, learnt from the last run:
 	// 0 unknown, 1 row runs (srh_rows.hip), 2 list order (srh_list.hip: steep curves)
 	uint8_t   list_mode[SRH_MAX_VIEWS] = {0};
@@ -405,6 +408,7 @@ struct srh_context {
 	int speckle_diff_steps = 2;                         // option "speckle_diff_steps": that stage's max_diff in depth steps
 	int cost_kind = SRH_COST_NCC;                       // option "cost": the TwoView matching cost, SRH_COST_NCC, SRH_COST_SAD or SRH_COST_CENSUS
 	int sad_dense = 0;                                  // option "sad_dense": cost_sad of row-aligned rigs on the dense plan (srh_sad_strip.hip)
+	int census_dense = 0;                               // option "census_dense": the census cost of row-aligned rigs on the dense plan (srh_census_strip.hip)
 	int subpixel = 0;                                   // option "subpixel": every TwoView WTA pass refines its rows (srh_subpixel.hip; CHANGES RESULTS)
 	// what a TwoView WTA pass keeps per reference pixel: what "wta_outputs" asks for; under "subpixel" winners and costs
 	int wta_keep() const { return subpixel ? (SRH_WTA_WINNERS | SRH_WTA_COSTS) : wta_outputs; }
@@ -800,7 +804,7 @@ extern "C" int srh_create(int device, srh_context **out) {
 static void free_view(ViewHost &v) {
 	if (v.rgba || v.gray || v.edges || v.tvp || v.geo5) (void)hipDeviceSynchronize();
 	v.rgba.release(); v.mask.release(); v.gray.release(); v.gray_tv.release(); v.depth.release(); v.edges.release();
-	v.full.release(); v.fulls.release(); v.census.release(); v.grayp.release(); v.fullsp.release(); v.tvp.release(); v.geo5.release(); v.fullp.release(); v.act.release(); v.peaks.release(); v.mrf.release(); v.sgm.release();
+	v.full.release(); v.fulls.release(); v.census.release(); v.cenothp.release(); v.cenrefp.release(); v.grayp.release(); v.fullsp.release(); v.tvp.release(); v.geo5.release(); v.fullp.release(); v.act.release(); v.peaks.release(); v.mrf.release(); v.sgm.release();
 	v.wta_xy.release(); v.wta_cost.release();
 	v.subpx_delta.release(); v.subpx_neigh.release(); v.subpx_cls.release();
 	v = ViewHost();
@@ -929,6 +933,7 @@ extern "C" int srh_set_option(srh_context *c, const char *name, long value) {
 		c->cost_kind = (int)value; return SRH_OK;
 	}
 	if (!strcmp(name, "sad_dense")) { c->sad_dense = value != 0; return SRH_OK; }
+	if (!strcmp(name, "census_dense")) { c->census_dense = value != 0; return SRH_OK; }
 	if (!strcmp(name, "wta_outputs")) {
 		if (value != 0 && value != SRH_WTA_WINNERS && value != (SRH_WTA_WINNERS | SRH_WTA_COSTS))
 			return fail(SRH_E_INVALID, "wta_outputs must be 0, 1 (SRH_WTA_WINNERS) or 3 (SRH_WTA_WINNERS | SRH_WTA_COSTS): the costs are those of the kept winners");
@@ -996,7 +1001,7 @@ static int view_install(srh_context *c, int slot, int w, int h, const void *rgba
 	}
 	v.cam = *cam;
 	v.full_r = 0; v.fulls_r = 0;                                // recomputed on demand for the new pixels
-	v.tvp_valid = false; v.fullp_r = 0; v.grayp_valid = false; v.census_valid = false; v.fullsp_r = 0; v.geo5_valid = false; v.geo5_denied = false;
+	v.tvp_valid = false; v.fullp_r = 0; v.grayp_valid = false; v.census_valid = false; v.cenp_valid = false; v.fullsp_r = 0; v.geo5_valid = false; v.geo5_denied = false;
 	v.peaks_k = 0;                                              // the top-K peaks belonged to the previous image
 	v.wta_flags = 0; v.wta_oth = -1;                            // and so did the WTA by-products
 	for (LabelStage *S : c->label_stages) S->forget_if(w, h);   // and so may what a label stage reports
@@ -1632,6 +1637,7 @@ static int ensure_census(srh_context *c, hipStream_t st, int slot) {
 	Scope s(c, st, "census_kernel");
 	launch_census(st, v.gray, v.w, v.h, v.census);
 	v.census_valid = true;
+	v.cenp_valid = false;
 	return SRH_OK;
 }
 
@@ -1643,6 +1649,19 @@ static int ensure_full(srh_context *c, hipStream_t st, ViewHost &v, int R) {
 	HIP_TRY(hipMemsetAsync(stat, 0, 2*sizeof(uint32_t), st));
 	launch_full_window(st, v.gray_tv, v.w, v.h, R, v.full, stat);
 	v.full_r = R;
+	return SRH_OK;
+}
+
+// the zero-bordered copy of cost_sad's "window fully usable" plane of radius R (the SAD and the census strip kernels')
+static int ensure_fullsp(srh_context *c, hipStream_t st, ViewHost &v, int R) {
+	int rc;
+	if ((rc = ensure_fulls(c, st, v, R))) return rc;
+	if (!v.fullsp) HIP_TRY(v.fullsp.alloc(padded_size(v.w, v.h)));
+	if (v.fullsp_r != R) {
+		Scope s(c, st, "padded_bytes_kernel");
+		launch_padded_bytes(st, v.fulls, v.w, v.h, v.fullsp);
+		v.fullsp_r = R;
+	}
 	return SRH_OK;
 }
 
@@ -1658,14 +1677,24 @@ static int ensure_sad_planes(srh_context *c, hipStream_t st, ViewHost &v, int R)
 		launch_padded_gray(st, v.gray, v.mask, v.w, v.h, v.grayp);
 		v.grayp_valid = true;
 	}
-	if ((rc = ensure_fulls(c, st, v, R))) return rc;
-	if (!v.fullsp) HIP_TRY(v.fullsp.alloc(padded_size(v.w, v.h)));
-	if (v.fullsp_r != R) {
-		Scope s(c, st, "padded_bytes_kernel");
-		launch_padded_bytes(st, v.fulls, v.w, v.h, v.fullsp);
-		v.fullsp_r = R;
+	return ensure_fullsp(c, st, v, R);
+}
+
+// The planes twoview_strip_census_kernel stages from (option "census_dense"), made on first use after an upload, on `st`:
+// the view's signatures on the padded raster, once as the other side's taps and once as the reference side's, and the
+// zero-bordered copy of cost_sad's "window fully usable" plane of radius R (the same definition of "fully usable")
+static int ensure_census_planes(srh_context *c, hipStream_t st, int slot, int R) {
+	ViewHost &v = c->views[slot];
+	int rc;
+	if ((rc = ensure_census(c, st, slot))) return rc;
+	if (!v.cenothp) HIP_TRY(v.cenothp.alloc(padded_size(v.w, v.h)));
+	if (!v.cenrefp) HIP_TRY(v.cenrefp.alloc(padded_size(v.w, v.h)));
+	if (!v.cenp_valid) {
+		Scope s(c, st, "padded_census_kernel");
+		launch_padded_census(st, v.census, v.mask, v.gray_tv, v.w, v.h, v.cenothp, v.cenrefp);
+		v.cenp_valid = true;
 	}
-	return SRH_OK;
+	return ensure_fullsp(c, st, v, R);
 }
 
 // ---- the TwoView WTA pass driver: a pass descriptor, a plan that launches nothing, one runner per path (fused kernel,
@@ -1700,6 +1729,7 @@ struct TvPass {
 	size_t budget = 0;
 	int kind = SRH_COST_NCC;                  // option "cost"; sad / census: the kind is SRH_COST_SAD / SRH_COST_CENSUS
 	bool sad = false, census = false;
+	bool strip_only = false;                  // cost_sad and the census cost: on the dense plan the strip form only, every column written
 	int32_t *wout = nullptr;
 	const double *subpx_tdist = nullptr;      // option "subpixel": the pass's label plane table (label_plane_table_kernel)
 
@@ -1736,6 +1766,7 @@ static int tv_pass_init(TvPass &P, srh_context *c, const Lane &lane, int ref, in
 	P.kind = c->cost_kind;
 	P.sad = P.kind == SRH_COST_SAD;
 	P.census = P.kind == SRH_COST_CENSUS;
+	P.strip_only = P.sad || P.census;
 	if (P.y1 > P.y0) P.budget = band_budget(c);
 	return SRH_OK;
 }
@@ -1776,12 +1807,12 @@ static double disparity_span(const srh_params &p, double fx_bx) {
 
 // ---- plan: dense row-aligned kernels (or the fused kernel), or the general kernels.  Launches nothing.
 // (cost_sad: the dense plan only with option "sad_dense", its cost rows filled by twoview_strip_sad_kernel; no per-tile
-// and no fused kernel -- without the option rectified rigs take the row-run lists too; DESIGN.md 4c.  The census cost has
-// the candidate lists and the walk kernel only)
+// and no fused kernel -- without the option rectified rigs take the row-run lists too; DESIGN.md 4c.  The census cost
+// likewise: option "census_dense", twoview_strip_census_kernel)
 TvPlan TvPass::plan() const {
 	const ViewHost &L = c->views[ref], &Rv = c->views[oth];
 	TvPlan pl;
-	pl.dense = !c->force_generic && !census && (!sad || c->sad_dense) && (R == 5 || R == 2);
+	pl.dense = !c->force_generic && (!census || c->census_dense) && (!sad || c->sad_dense) && (R == 5 || R == 2);
 	double fx_bx = 0;
 	if (pl.dense && !rig_is_row_aligned(L.cam, Rv.cam, &fx_bx)) {
 		// test hook: any pinhole pair may be *proposed* (the scan kernel refutes the proposal, see the controller's redo)
@@ -1794,9 +1825,9 @@ TvPlan TvPass::plan() const {
 	if (!(p->min_depth > 0) || !(p->max_depth > 0) || !(span < 4096.0)) pl.dense = false;
 	else pl.cstride = (((int)ceil(span) + 3) + 7) & ~7;
 	if (pl.cstride > W + 8) pl.cstride = (W + 8 + 7) & ~7;
-	// cost_sad has the strip form only: a range wider than its chunk takes the candidate lists
-	if (sad && pl.dense && pl.cstride + SRH_WTILE > strip_chunk_columns()) pl.dense = false;
-	pl.fused = pl.dense && !sad && c->use_fused && (c->arith == 0 || c->arith == 3) &&
+	// cost_sad and the census cost have the strip form only: a range wider than its chunk takes the candidate lists
+	if (strip_only && pl.dense && pl.cstride + SRH_WTILE > strip_chunk_columns()) pl.dense = false;
+	pl.fused = pl.dense && !strip_only && c->use_fused && (c->arith == 0 || c->arith == 3) &&
 	           p->num_depth_levels <= SRH_FUSED_MAXC && span + 1.0 <= (double)SRH_FUSED_MAXC;
 	return pl;
 }
@@ -2092,7 +2123,7 @@ int TvPass::dense_prepare(TvDense &D) const {
 	for (int pass = 0; pass < 2; ++pass) {
 		const int wdoubles = D.strip ? (2*R + 1)*wimg_wp(R) : T;    // doubles per pixel window in the band buffer
 		D.rows = rows_per_band((size_t)wdoubles*sizeof(double) + (size_t)D.cstride*sizeof(double));
-		if (D.strip && !sad && c->strip == 1 && (size_t)((W + SRH_WTILE - 1)/SRH_WTILE)*D.rows < (size_t)48*2*c->num_cus) D.strip = false;
+		if (D.strip && !strip_only && c->strip == 1 && (size_t)((W + SRH_WTILE - 1)/SRH_WTILE)*D.rows < (size_t)48*2*c->num_cus) D.strip = false;
 		else break;
 	}
 	const size_t rows = D.rows;
@@ -2101,7 +2132,7 @@ int TvPass::dense_prepare(TvDense &D) const {
 	// (+ one tile of slack: the strip kernel copies whole 32-pixel pieces of these rows)
 	if ((rc = lane.mem->band.pconst.ensure((rows*(size_t)W + SRH_WTILE)*SRH_PC))) return rc;
 	if ((rc = lane.mem->band.prange.ensure(rows*(size_t)W + SRH_WTILE))) return rc;
-	if (!sad && (rc = lane.mem->band.filllist.ensure(rows*(size_t)W + 1))) return rc;    // (capacity: the band's pixels)
+	if (!strip_only && (rc = lane.mem->band.filllist.ensure(rows*(size_t)W + 1))) return rc;    // (capacity: the band's pixels)
 	if (D.tscan && (rc = lane.mem->band.tileflag.ensure(rows*(size_t)((W + 63)/64) + 1))) return rc;
 	if (D.cert && (rc = lane.mem->band.cflag.ensure(rows*(size_t)W + 1))) return rc;
 	D.lanes = D.strip ? strip_block_lanes(D.cstride, c->strip == 1 ? 0 : c->strip) : 8;
@@ -2110,6 +2141,8 @@ int TvPass::dense_prepare(TvDense &D) const {
 	if ((rc = ensure_tvp(c, lane.stream, c->views[ref])) || (rc = ensure_tvp(c, lane.stream, c->views[oth]))) return rc;
 	if (D.strip && sad) {
 		if ((rc = ensure_sad_planes(c, lane.stream, c->views[oth], R))) return rc;
+	} else if (D.strip && census) {
+		if ((rc = ensure_census_planes(c, lane.stream, ref, R)) || (rc = ensure_census_planes(c, lane.stream, oth, R))) return rc;
 	} else if (D.strip) {
 		// zero-bordered "window fully usable" plane of the other view
 		ViewHost &O = c->views[oth];
@@ -2149,7 +2182,7 @@ bool TvPass::dense_fill_padded(const TvDense &D, int arith) const { return D.str
 // windows kernel's waves, the template's workgroup (80 registers per lane, 45 KB of LDS) does not and starts when the
 // windows kernel leaves -- behind the range kernel it holds nothing up (profiles/dense_tail_timeline.txt).
 int TvPass::dense_band_inputs(TvDense &D, int by, int nr, int arith) const {
-	uint32_t *filllist = sad ? nullptr : (uint32_t *)lane.mem->band.filllist;
+	uint32_t *filllist = strip_only ? nullptr : (uint32_t *)lane.mem->band.filllist;
 	const bool side = c->side_weights != 0;
 	if (side) {
 		if (!c->side_stream) {
@@ -2160,7 +2193,7 @@ int TvPass::dense_band_inputs(TvDense &D, int by, int nr, int arith) const {
 		if (!c->side_tpl) HIP_TRY(hipEventCreateWithFlags(&c->side_tpl, hipEventDisableTiming));
 		HIP_TRY(hipEventRecord(c->side_go, lane.stream));
 	}
-	run_weights(c, lane, ref, W, *p, by, nr, SRH_WTILE, !sad ? (double *)lane.mem->band.pconst : nullptr, D.strip);
+	run_weights(c, lane, ref, W, *p, by, nr, SRH_WTILE, !strip_only ? (double *)lane.mem->band.pconst : nullptr, D.strip);
 	const bool tables = side && D.tables_pending;
 	D.tables_pending = false;
 	// where table, ranges and template are made: the pass's scratch, on the side stream or on the pass's own
@@ -2198,6 +2231,15 @@ int TvPass::dense_cost_pass(const TvDense &D, int by, int nr, int arith, bool ra
 		if (!launch_twoview_strip_sad(lane.stream, W, H, *p, by, nr, lane.mem->band.wbuf, lane.mem->band.prange, c->views[ref].tvp,
 		                              c->views[oth].grayp, c->views[oth].fullsp, lane.mem->band.cost, cstride, lane.mem->cnt, c->num_cus))
 			return fail(SRH_E_UNSUPPORTED, "twoview_strip_sad_kernel: no instantiation for radius %d", R);
+		return SRH_OK;
+	}
+	if (census) {
+		// (likewise: every column of [lo, hi] is written)
+		HIP_TRY(hipMemsetAsync(&lane.mem->cnt->strip_ticket, 0, 2*sizeof(unsigned int), lane.stream));
+		Scope s(c, lane.stream, "twoview_strip_census_kernel");
+		if (!launch_twoview_strip_census(lane.stream, W, H, *p, by, nr, lane.mem->band.wbuf, lane.mem->band.prange, c->views[ref].cenrefp,
+		                                 c->views[oth].cenothp, c->views[oth].fullsp, lane.mem->band.cost, cstride, lane.mem->cnt, c->num_cus))
+			return fail(SRH_E_UNSUPPORTED, "twoview_strip_census_kernel: no instantiation for radius %d", R);
 		return SRH_OK;
 	}
 	if (D.strip) {
@@ -2289,7 +2331,7 @@ int TvPass::run_walk() const {
 }
 
 // The controller: the plan's first choice, then at most four attempts, each read by its counters -- a strip overflow takes
-// the per-tile kernel (cost_sad, which has the strip form only: the candidate lists), a certified pass with more flagged
+// the per-tile kernel (cost_sad and the census cost, which have the strip form only: the candidate lists), a certified pass with more flagged
 // pixels than its redo covers the reference's arithmetic, a dense plan the device refutes the general kernels.  On a
 // call's first attempt srh_twoview_compute's passes (defer) are handed over unverified instead.
 // (a HIP error or a refused band buffer returns straight out: with_thinner_bands retries the whole call)
@@ -2328,11 +2370,11 @@ static int twoview_wta_run(srh_context *c, const Lane &lane, srh_context::TvDefe
 	D.cstride = plan.cstride;
 	// the persistent strip form of the cost kernel: exact / fma arithmetic, candidate ranges of a 32-pixel tile inside one
 	// LDS chunk; anything else, or a range that turns out wider, takes the per-tile kernel
-	D.strip = dense && (P.sad || (c->strip != 0 && c->arith != 2)) && plan.cstride + SRH_WTILE <= strip_chunk_columns();
+	D.strip = dense && (P.strip_only || (c->strip != 0 && c->arith != 2)) && plan.cstride + SRH_WTILE <= strip_chunk_columns();
 	// (strip_select_block, the strip kernel's blocked select form, drops an unusable tap by multiplying with 0.0 and needs
 	// finite weights for it; geodesic_sigma <= 0 gives the taps outside the image, which keep geodesic_init, the weight
 	// +inf or NaN: such a pass takes the per-tile kernel, whose select forms are true selects)
-	if (!P.sad && p->weight_kind == SRH_WEIGHT_GEODESIC && !(p->geodesic_sigma > 0)) D.strip = false;
+	if (!P.strip_only && p->weight_kind == SRH_WEIGHT_GEODESIC && !(p->geodesic_sigma > 0)) D.strip = false;
 	// certified arithmetic (arith = 3, the default): fused cost loops in the strip kernel + the certified scan; where the
 	// strip kernel does not run, or the parameters leave the bound no room, the reference's arithmetic
 	bool cert_ok = c->arith == 3 && !P.sad && !P.census && cert_bound(*p).ok != 0;
@@ -2360,7 +2402,7 @@ static int twoview_wta_run(srh_context *c, const Lane &lane, srh_context::TvDefe
 		Counters hc;
 		if ((rc = read_back(lane.stream, &hc, lane.mem->cnt, sizeof(hc)))) return rc;
 		const TvVerdict v = tv_dense_verdict(hc, D.strip);
-		if (v == TV_STRIP_OVERFLOW) { D.strip = false; if (P.sad) dense = false; continue; }
+		if (v == TV_STRIP_OVERFLOW) { D.strip = false; if (P.strip_only) dense = false; continue; }
 		if (v == TV_CERT_OVERFLOW) { cert_ok = false; continue; }
 		c->stats.n_certified = (int64_t)hc.n_certified; c->stats.n_flagged = (int64_t)hc.n_flagged;
 		if (v == TV_STANDS) break;
@@ -2390,10 +2432,11 @@ extern "C" int srh_twoview_cost_rows(srh_context *c, int ref, int oth, const srh
 	if ((rc = check_slot(c, ref, true)) || (rc = check_slot(c, oth, true)) || (rc = check_params(p))) return rc;
 	if (form != 0 && form != 3 && form != 5 && form != 1 && form != 2) return fail(SRH_E_INVALID, "form must be 0, 1, 2, 3 or 5");
 	if ((form == 3 || form == 5) && !cert_bound(*p).ok) return fail(SRH_E_UNSUPPORTED, "the parameters leave the error bound no room");
-	const bool sad = c->cost_kind == SRH_COST_SAD;
-	if (c->cost_kind == SRH_COST_CENSUS) return fail(SRH_E_UNSUPPORTED, "the census cost has no cost rows: it never takes the dense plan");
+	const bool sad = c->cost_kind == SRH_COST_SAD, census = c->cost_kind == SRH_COST_CENSUS;
+	const bool strip_only = sad || census;
+	if (census && !c->census_dense) return fail(SRH_E_UNSUPPORTED, "cost rows of the census cost exist on the dense plan only (option census_dense)");
 	if (sad && !c->sad_dense) return fail(SRH_E_UNSUPPORTED, "cost rows of cost_sad exist on the dense plan only (option sad_dense)");
-	if (sad && form != 0) return fail(SRH_E_INVALID, "cost_sad has the reference's arithmetic only: form must be 0");
+	if (strip_only && form != 0) return fail(SRH_E_INVALID, "cost_sad and the census cost have one arithmetic only: form must be 0");
 	TvPass P;
 	if ((rc = tv_pass_init(P, c, c->main_lane(), ref, oth, p, y0, y1))) return rc;
 	const TvPlan plan = P.plan();
@@ -2404,9 +2447,9 @@ extern "C" int srh_twoview_cost_rows(srh_context *c, int ref, int oth, const srh
 	HIP_TRY(hipMemsetAsync(c->mem.cnt, 0, sizeof(Counters), c->stream));
 	TvDense D;
 	D.cstride = plan.cstride;
-	D.strip = (sad || c->strip != 0) && plan.cstride + SRH_WTILE <= strip_chunk_columns();
-	if (!sad && p->weight_kind == SRH_WEIGHT_GEODESIC && !(p->geodesic_sigma > 0)) D.strip = false;   // (as in the pass: finite weights only)
-	D.cert = form != 0 && !sad && cert_bound(*p).ok != 0;
+	D.strip = (strip_only || c->strip != 0) && plan.cstride + SRH_WTILE <= strip_chunk_columns();
+	if (!strip_only && p->weight_kind == SRH_WEIGHT_GEODESIC && !(p->geodesic_sigma > 0)) D.strip = false;   // (as in the pass: finite weights only)
+	D.cert = form != 0 && !strip_only && cert_bound(*p).ok != 0;
 	if (form == 2) D.strip = D.cert = false;                      // (the f32 kernel is a per-tile kernel, as in the pass under arith = 2)
 	if ((rc = P.dense_prepare(D))) return rc;
 	if (cancelled(c)) return fail(SRH_E_CANCELLED, "cancelled");
@@ -2545,6 +2588,9 @@ extern "C" int srh_twoview_compute(srh_context *c, int left, int right, const sr
 		if (c->cost_kind == SRH_COST_SAD && c->sad_dense && (p->window_radius == 5 || p->window_radius == 2))
 			for (int k = 0; k < 2; ++k)
 				if ((rc = ensure_sad_planes(c, c->stream, c->views[k == 0 ? left : right], p->window_radius))) return rc;
+		if (c->cost_kind == SRH_COST_CENSUS && c->census_dense && (p->window_radius == 5 || p->window_radius == 2))
+			for (int k = 0; k < 2; ++k)
+				if ((rc = ensure_census_planes(c, c->stream, k == 0 ? left : right, p->window_radius))) return rc;
 		if ((p->window_radius == 5 || p->window_radius == 2) &&
 		    ((rc = ensure_tvp(c, c->stream, c->views[left])) || (rc = ensure_tvp(c, c->stream, c->views[right])))) return rc;
 		// (and the WTA by-products' planes of both views, option "wta_outputs", are allocated and hold their "none" values there)

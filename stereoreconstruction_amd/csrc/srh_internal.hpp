@@ -315,6 +315,15 @@ bool launch_twoview_rows_census(hipStream_t st, const ViewDev *views, int ref, i
 void launch_twoview_list_census(hipStream_t st, const ViewDev *views, int ref, int oth, int width, const srh_params &P,
                                 int y0, int nrows, const double *wbuf, const int32_t *count, const uint32_t *cand,
                                 double *cost, int cmax, Counters *cnt);
+// the census cost on the row-aligned dense plan (srh_census_strip.hip; option "census_dense"): a view's signatures on the
+// padded raster of padded_size(w, h) as the other side's taps (unusable behind the mask) and as the reference side's
+// (unusable where gray_tv is NaN), then the persistent kernel that fills every column [lo, hi] of the band's cost rows;
+// oth_fullp: launch_padded_bytes' copy of launch_sad_full_window's plane
+void launch_padded_census(hipStream_t st, const uint64_t *census, const uint8_t *mask, const double *gray_tv, int w, int h,
+                          uint64_t *out_other, uint64_t *out_ref);
+bool launch_twoview_strip_census(hipStream_t st, int width, int height, const srh_params &P, int y0, int nrows,
+                                 const double *wimg, const PixRange *prange, const uint64_t *ref_cenp, const uint64_t *oth_cenp,
+                                 const uint8_t *oth_fullp, double *cost, int cstride, Counters *cnt, int num_cus);
 void launch_point_cloud(hipStream_t st, const ViewDev *views, int slot, int w, int h, const srh_params &P,
                         double *xyz, uint8_t *rgb, uint8_t *valid, unsigned long long *counts);
 // depth-map fusion (srh_fuse.hip).  Per entry of the slot list: its point map (3 doubles per pixel, from

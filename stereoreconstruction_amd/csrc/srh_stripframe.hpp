@@ -1,6 +1,7 @@
 // srh_stripframe.hpp -- the FRAME of the persistent strip kernels of the dense TwoView plan, stated once:
-// twoview_strip_cost_kernel (srh_strip.hip, NCC) and twoview_strip_sad_kernel (srh_sad_strip.hip, SAD) differ in their block
-// loops, select forms and per-tile passes; what surrounds those is here.
+// twoview_strip_cost_kernel (srh_strip.hip, NCC), twoview_strip_sad_kernel (srh_sad_strip.hip, SAD) and
+// twoview_strip_census_kernel (srh_census_strip.hip, census) differ in their block loops, select forms and per-tile passes;
+// what surrounds those is here.
 //
 //   padded raster      SRH_PADL / SRH_PADR / SRH_PADY, padded_stride, padded_size, padded_raster_xy (raster index -> image
 //                      position and "inside"), padded_raster_kernel + launch_padded_raster: a plane is one functor
@@ -234,10 +235,12 @@ __device__ __forceinline__ int full_offset(int y, int SP, int cs) {
 
 // Requests, by wave role.  Image row `yy` of both views into one ring slot: waves 0-2 a 1 KiB piece each of the other view's
 // row from column cs - R, wave 3 the reference row from column x0 - R.
-template <int R>
-__device__ __forceinline__ void strip_request_row(const double *othp, const double *refp, int SP, int yy, int cs, int x0,
-                                                  double *rt, double *lt, int wv, int lane) {
-	const double *src = othp + (size_t)(yy + SRH_PADY)*SP + (cs - R + SRH_PADL);
+// (T: the planes' 8-byte word -- gray values, or the census kernel's signatures)
+template <int R, class T>
+__device__ __forceinline__ void strip_request_row(const T *othp, const T *refp, int SP, int yy, int cs, int x0,
+                                                  T *rt, T *lt, int wv, int lane) {
+	static_assert(sizeof(T) == 8, "rows of 8-byte words");
+	const T *src = othp + (size_t)(yy + SRH_PADY)*SP + (cs - R + SRH_PADL);
 	if (wv < 3) {
 		if (wv*1024 + lane*16 < StripGeom<R>::RW*8)
 			__builtin_amdgcn_global_load_lds((strip_gbl_void *)((const char *)src + wv*1024 + lane*16),

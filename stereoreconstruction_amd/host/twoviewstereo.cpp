@@ -185,6 +185,7 @@ void TwoViewStereo::computeCostVolumes(CameraPtr leftView_, CameraPtr rightView_
 	if (!uploadViews()) return;
 	if (srh_set_option(ctx_, "cost", costKind) != SRH_OK) { error_ = srh_last_error(); return; }
 	srh_set_option(ctx_, "sad_dense", sadDenseOn);
+	srh_set_option(ctx_, "census_dense", censusDenseOn);
 	if (srh_set_option(ctx_, "wta_outputs", wtaFlags) != SRH_OK) { error_ = srh_last_error(); return; }
 	srh_set_option(ctx_, "subpixel", subpixelOn ? 1 : 0);
 	if (srh_twoview_wta(ctx_, 0, 1, &params_, 0, 0) != SRH_OK || srh_twoview_wta(ctx_, 1, 0, &params_, 0, 0) != SRH_OK ||
@@ -329,6 +330,7 @@ void TwoViewStereo::computeDepthMaps() {
 	srh_set_hooks(ctx_, cancelFlag(), onProgress, &hooks);
 	srh_set_option(ctx_, "filter_invalid", filterFlags);
 	srh_set_option(ctx_, "sad_dense", sadDenseOn);
+	srh_set_option(ctx_, "census_dense", censusDenseOn);
 	srh_set_option(ctx_, "subpixel", subpixelOn ? 1 : 0);
 	if (srh_set_option(ctx_, "speckle_min_size", speckleMinSize) != SRH_OK ||
 	    (speckleMinSize && srh_set_option(ctx_, "speckle_diff_steps", speckleDiffSteps) != SRH_OK) ||

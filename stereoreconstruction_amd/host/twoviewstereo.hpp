@@ -60,6 +60,9 @@ public:
 	// SAD of a rectified pair on the dense plan (option "sad_dense": 1 = on, 0 = default): a tuning switch, never the result
 	void setSadDense(int on) { sadDenseOn = on; }
 	int sadDense() const { return sadDenseOn; }
+	// the census cost of a rectified pair on the dense plan (option "census_dense": 1 = on, 0 = default): likewise
+	void setCensusDense(int on) { censusDenseOn = on; }
+	int censusDense() const { return censusDenseOn; }
 
 	// By-products of the WTA scan (option "wta_outputs"; never the depth maps): SRH_WTA_WINNERS (1) keeps, per pixel of each
 	// map, the candidate pixel of the other view that won and the one that held the minimum before it (its cost is the
@@ -205,6 +208,7 @@ private:
 	int speckleMinSize = 0, speckleDiffSteps = 2;
 	int costKind = SRH_COST_NCC;
 	int sadDenseOn = 0;
+	int censusDenseOn = 0;
 	int wtaFlags = 0;
 	bool subpixelOn = false;
 	std::vector<double> subDelta_[2];

@@ -256,6 +256,7 @@ void TwoViewStereo::computeDepthMaps() {
 	if (!uploadViews()) return;
 	if (srh_set_option(ctx_, "cost", costKind) != SRH_OK) { error_ = srh_last_error(); return; }
 	srh_set_option(ctx_, "sad_dense", sadDenseOn);
+	srh_set_option(ctx_, "census_dense", censusDenseOn);
 	if (srh_set_option(ctx_, "wta_outputs", wtaFlags) != SRH_OK) { error_ = srh_last_error(); return; }
 	srh_set_option(ctx_, "subpixel", subpixelOn ? 1 : 0);
 	mrfInfo_[0] = mrfInfo_[1] = srh_mrf_info();
